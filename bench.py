@@ -8,19 +8,24 @@ timed region and stay resident in HBM; the per-lane choice-RNG stream continues 
 plays different playouts.  Steps are independent batches (as in root-parallel MCTS) and are submitted in GROUPS of up
 to `--group` batches per launch (oakgpu_rollout_group_dev): one playout queue, one tail per group.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1: one process per GPU, lanes sharded by rank (weak scaling: 65,536 playouts per GPU and step, disjoint seeds); the
 path's single exchange is an RCCL all-gather of the fp32 leaf values back to every root -- ONE collective per group
 launch (G x 256 KiB per rank), on its own stream.
 
-Prints ONE JSON line (rank 0).  The line is the configs[1] record; with the default `--workload all` it also carries
-the rest of BASELINE.json's metric as sub-records with their own timed regions: `leaf` (leaf-evals/s of the
-768-256-256-256-1 network, fp32-MFMA roofline, per-kernel microseconds) and `config3` (configs[2]: turn-step + leaf
-evaluation every turn).  `roofline` of the headline record prices the rollout kernel against the HBM roof with the
-ALGORITHMIC bytes of SURVEY 8(d): 802 B per turn-step (401 read + 401 written of per-lane state); every record has a
+Prints ONE JSON line (rank 0).  The line is the configs[1] record: a plain run sets up, warms up, times the K steps and
+prints it, nothing else.  With `--full` (and the default `--workload all`) it also carries the rest of BASELINE.json's
+metric as sub-records with their own timed regions: `leaf` (leaf-evals/s of the 768-256-256-256-1 network, fp32-MFMA
+roofline, per-kernel microseconds), `config3` (configs[2]: turn-step + leaf evaluation every turn), `config4` and
+`config5`.  `roofline` of the headline record prices the rollout kernel against the HBM roof with the ALGORITHMIC bytes
+of SURVEY 8(d): 802 B per turn-step (401 read + 401 written of per-lane state); with `--full` every record has a
 `cpu_baseline` at N = 1: the CPU oracle (a restatement, not the Oak binary) on all host cores.
+
+`--dump-outputs DIR` writes what the headline's last timed step computed -- the outputs a caller of
+oakgpu_rollout_group_dev receives for that batch -- as DIR/<name>.npy (float32); the inputs depend on the arguments only,
+so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -65,11 +70,20 @@ def main():
                          "whole batch + a leaf eval of every lane, every turn; search = tree search with batched leaves "
                          "(oakgpu_search), iterations/s on one random OU root")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the `leaf`, `config3`, `config4` and `config5` sub-records of --workload all "
+                         "and the CPU baselines (unless --no-cpu-baseline).  Off: a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the headline's last timed step (rank 0's batch) as DIR/<name>.npy")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch / rendezvous / exchange / accounting rehearsal WITHOUT a GPU: gloo backend, CPU tensors, the kernel "
                          "replaced by a stub that writes a rank-and-batch pattern (no engine, no oracle); the line says dry_run: true "
                          "and its value measures nothing.  tests/test_bench_launch.py runs `bench.py --gpus 2 --dry-run` here.")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.dry_run or args.workload not in ("all", "rollout")):
+        ap.error("--dump-outputs writes the headline's (rollout) outputs: not with --dry-run or --workload %s" % args.workload)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` with no launcher around it: start the N ranks ourselves, BEFORE this process has made
@@ -126,13 +140,13 @@ def main():
             rec["vs_baseline"] = None
             print(json.dumps(rec), flush=True)
     else:
-        # default ("all"): the headline configs[1] line carries the whole BASELINE metric -- turn-steps/s of batched
-        # playouts plus, as sub-records with their own timed regions, leaf-evals/s (`leaf`), configs[2] (`config3`),
+        # default ("all"): the headline configs[1] line; with --full it carries the whole BASELINE metric -- turn-steps/s of
+        # batched playouts plus, as sub-records with their own timed regions, leaf-evals/s (`leaf`), configs[2] (`config3`),
         # configs[3] (`config4`: root-parallel MCTS step, STRONG scaling -- so one `--gpus N` command yields both curves)
         # and configs[4] (`config5`: tree search with network leaves + exact Nash at the root)
         out = rollout_workload(args, torch, dev, rank, local_rank, world, dist, force_dist)
         subs = {}
-        if args.workload == "all":
+        if args.workload == "all" and args.full:
             subs.update(leaf_records(args, torch, dev, rank, local_rank, world, dist) or {})
             for name, fn in (("config4", config4_workload), ("config5", search_workload)):
                 try:
@@ -142,7 +156,7 @@ def main():
                     print("bench.py: sub-record %s failed: %s" % (name, rec["error"]), file=sys.stderr, flush=True)
                 if rank == 0:
                     subs[name] = rec
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:   # after every GPU timed region
+        if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:   # after every GPU timed region
             out["cpu_baseline"] = cpu_baseline(args.batch)
             if isinstance(subs.get("config4"), dict) and "error" not in subs["config4"]:
                 subs["config4"]["cpu_baseline"] = cpu_baseline_config4()
@@ -327,6 +341,10 @@ def rollout_workload(args, torch, dev, rank, local_rank, world, dist, force_dist
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # the last timed step = the last batch of the last group
+        last = slots[(len(timed) - 1) % S]
+        dump_outputs(args.dump_outputs, last.values[timed[-1] - 1], last.results[timed[-1] - 1], last.steps_out[timed[-1] - 1],
+                     last.prng[timed[-1] - 1])
 
     total_steps = sum(sl.total for sl in slots)
     my_steps = int(total_steps.item())
@@ -426,6 +444,26 @@ def rollout_workload(args, torch, dev, rank, local_rank, world, dist, force_dist
     # (the CPU baseline is timed by the caller AFTER every GPU record: 10-30 s of host work between two GPU timed regions let
     # the device clock down, and the next region then measured the ramp)
     return out
+
+
+DUMP_MAX_LANES = 1 << 20       # 44 B per lane as float32: <= 46 MB a dump
+
+
+def dump_outputs(out_dir, values, results, steps, prng):
+    """--dump-outputs: one batch of the rollout's outputs, as its caller receives them, to out_dir/<name>.npy in float32 (every
+    value is exact: results are bytes, turn-steps <= 1000, the advanced fast_prng state as its 8 bytes per lane).  A batch of more
+    than DUMP_MAX_LANES lanes is written as a fixed seeded sample of them, whose lane numbers go to lane_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"values": values, "results": results, "turn_steps": steps, "prng_state": prng}
+    arrays = {k: v.cpu().numpy().astype(np.float32) for k, v in arrays.items()}
+    n = arrays["values"].shape[0]
+    if n > DUMP_MAX_LANES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_LANES, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["lane_index"] = idx.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def leaf_records(args, torch, dev, rank, local_rank, world, dist, which=("leaf", "config3")):
@@ -685,7 +723,7 @@ def leaf_records(args, torch, dev, rank, local_rank, world, dist, which=("leaf",
                          "avg_step_ms": avg_s * 1e3, "algorithmic_flop_per_leaf": main_f + emb_f},
         }
         out["config3"] = rec
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # CPU baselines after both GPU timed regions (see main)
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:   # CPU baselines after both GPU timed regions (see main)
         if "leaf" in out:
             out["leaf"]["cpu_baseline"] = cpu_baseline_leaf(path, mid, dur_mid)
         if "config3" in out:

@@ -53,7 +53,8 @@ def test_gpus_2_rehearsal_on_one_gpu_runs_the_real_exchange_path():
     """BENCH_REHEARSAL=1: `python bench.py --gpus 2` self-launches two ranks that SHARE GPU 0 over gloo -- the real kernels and
     the real N > 1 code path of every record (disjoint lane blocks, one gather per group on its own stream, the row check of
     the gather, sums over ranks, config4's root split with its all-gather of per-root means) on a one-GPU box."""
-    p = _run(["--gpus", "2", "--steps", "8", "--warmup", "2", "--group", "4", "--batch", "16384", "--no-cpu-baseline"], {"BENCH_REHEARSAL": "1"})
+    p = _run(["--gpus", "2", "--steps", "8", "--warmup", "2", "--group", "4", "--batch", "16384", "--no-cpu-baseline", "--full"],
+             {"BENCH_REHEARSAL": "1"})
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -64,3 +65,28 @@ def test_gpus_2_rehearsal_on_one_gpu_runs_the_real_exchange_path():
         assert sub in rec and "error" not in rec[sub], (sub, rec.get(sub))
     assert rec["config4"]["scaling"] == "strong" and rec["config4"]["config"]["roots_per_gpu"] == 128
     assert rec["config4"]["ranks_seen"] == 2 and 0.3 < rec["config4"]["config"]["mean_root_value"] < 0.7
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_dumps_reproducible_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` (no --full): the configs[1] record alone -- no sub-record, no CPU baseline -- with
+    K timed steps; --dump-outputs writes the last timed step's outputs, and a second run with the same arguments writes the same."""
+    import numpy as np
+    recs = []
+    for run in ("a", "b"):
+        p = _run(["--gpus", "1", "--steps", "5", "--warmup", "2", "--group", "2", "--batch", "8192", "--dump-outputs", str(tmp_path / run)])
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        recs.append(json.loads(lines[0]))
+    for rec in recs:
+        assert rec["metric"] == "turn-steps/s (batched playouts)" and rec["unit"] == "turn-steps/s" and rec["higher_is_better"] is True
+        assert rec["steps"] == 5 and rec["config"]["groups"] == 3 and rec["ms_per_step"] > 0 and rec["dtype"] == "u16"
+        assert not {"leaf", "config3", "config4", "config5", "cpu_baseline"} & set(rec), sorted(rec)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["prng_state.npy", "results.npy", "turn_steps.npy", "values.npy"] == sorted(os.listdir(tmp_path / "b"))
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float32 and a.shape[0] == 8192 and np.array_equal(a, b), name
+    steps, values = np.load(tmp_path / "a" / "turn_steps.npy"), np.load(tmp_path / "a" / "values.npy")
+    assert 0 <= steps.min() and steps.max() <= 1000 and set(np.unique(values)) <= {0.0, 0.5, 1.0}

@@ -7,12 +7,12 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 O=gpurun_out/r05
 mkdir -p $O; rm -rf $O/stats $O/pmc_*
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err
 echo "driver bench done"; cut -c1-200 $O/bench_driver.json
-python3 bench.py > $O/bench.json 2> $O/bench.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
 echo "default bench done"; cut -c1-200 $O/bench.json
 # the driver's command (minus the CPU legs) under the profiler: per-kernel durations of rollout AND leaf kernels
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/stats.log 2>&1
 echo "kernel trace done"
 # PMC passes (own runs, --kernel-trace only): one group launch of 20 batches = the headline step structure
 R="python3 bench.py --workload rollout --steps 20 --warmup 0 --no-cpu-baseline"
