@@ -535,6 +535,15 @@ int oakgpu_leaf_eval_cached_dev(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t 
 /* Diagnostic (synchronises the context's stream): how many party slots the LAST oakgpu_leaf_eval_cached_dev call of this
  * context re-embedded (the cache misses of nn/battle/cache.h:81-126), of the n x 10 it looked at. */
 int oakgpu_leaf_cache_last_count(oakgpu_ctx *ctx, uint32_t *slots_recomputed);
+/* Diagnostic (read-only, no launch): the kernel each embedding pass of an oakgpu_leaf_eval*_dev call of this context would take
+ * for this network now -- the routing leaf_eval_impl itself launches by (the network's widths, whether its embedding nets are
+ * safe on the bf16 pipe, the context's kernel timing, the OAKGPU_EMBED_* environment).  The cached call runs the work-list
+ * form of the same party kernel.  *party / *actives (nullable) = OAKGPU_EMBED_FORM_*, 0 where the pass is switched off;
+ * *party_blocks (nullable) = the 32-wide output blocks each wave of the party row kernel computes (1 or 2), 0 for the tile form. */
+#define OAKGPU_EMBED_FORM_TILE 1  /* k_embed_lds: 64-item tiles, fp32 MFMA */
+#define OAKGPU_EMBED_FORM_ROWS 2  /* k_embed_prows / k_embed_arows, one launch each */
+#define OAKGPU_EMBED_FORM_FUSED 3 /* k_embed_both: the two row kernels in one launch */
+int oakgpu_leaf_embed_forms(oakgpu_ctx *ctx, const oakgpu_net *net, int *party, int *actives, int *party_blocks);
 
 /* value_policy_inference (network.h:102-123): value plus, per side, the logits of the <= 9 legal choices
  * (choices n x 9 bytes + counts n bytes per side, as produced by oakgpu_choices*; logits n x 9 floats,

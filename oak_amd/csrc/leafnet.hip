@@ -1308,9 +1308,12 @@ __device__ __forceinline__ void embed_prows_body(const EmbedTileArgs &a, float *
   EL_FLUSH();
 }
 
+// 32-wide output blocks per wave of the party row kernel (also reported by oakgpu_leaf_embed_forms)
+__host__ __device__ constexpr int prows_blocks(int p_out) { return p_out <= 32 ? 1 : 2; }
+
 template <bool LIST>
 __device__ __forceinline__ void embed_prows_dispatch(const EmbedTileArgs &a, float *lds_f, const uint32_t bid, const uint32_t nblocks) {
-  if (a.net.p_out <= 32) embed_prows_body<LIST, 1>(a, lds_f, bid, nblocks); // wave-uniform
+  if (prows_blocks(a.net.p_out) == 1) embed_prows_body<LIST, 1>(a, lds_f, bid, nblocks); // wave-uniform
   else embed_prows_body<LIST, 2>(a, lds_f, bid, nblocks);
 }
 
@@ -3063,6 +3066,27 @@ int oakgpu_leaf_set_lds_limits(void) { // per DEVICE (hipFuncSetAttribute applie
   return 0;
 }
 
+// The kernel each embedding pass takes (OAKGPU_EMBED_FORM_*, 0: pass switched off): what leaf_eval_impl launches by and
+// oakgpu_leaf_embed_forms reports.
+struct EmbedRoute { int party, actives; };
+static EmbedRoute embed_route(oakgpu_ctx *ctx, const oakgpu_net *net) {
+  const oak::NetDev &D = net->dev;
+  // The row kernels (k_embed_prows / k_embed_arows) take embedding nets up to 128 hidden channels, party outputs up to 64
+  // and active outputs up to 128; anything wider goes to k_embed_lds (the 64-item tile form).  OAKGPU_EMBED_TILE=1 forces
+  // the tile form (A/B and a second implementation for the tests).
+  static const bool force_tile = getenv("OAKGPU_EMBED_TILE") != nullptr;
+  static const int kinds = getenv("OAKGPU_EMBED_KINDS") ? atoi(getenv("OAKGPU_EMBED_KINDS")) : 3; // diagnostics: 1 party, 2 actives
+  static const bool split = getenv("OAKGPU_EMBED_SPLIT") != nullptr; // A/B: the two passes as two launches
+  const bool rows = !force_tile && net->embed_safe; // (the row kernels multiply as bf16 triples: see embed_safe)
+  const bool prow_ok = rows && D.p_hidden <= 128 && D.p_out <= 64, arow_ok = rows && D.a_hidden <= 128 && D.a_out <= 32 * oak::AR_MAX_NBO;
+  // default: both embedding passes in one launch (k_embed_both).  Not while the per-kernel timing diagnostic is on (it
+  // wants an event between the passes).
+  const bool timing = oakgpu_ctx_timing_events(ctx) != nullptr;
+  if (prow_ok && arow_ok && kinds == 3 && !split && !timing) return {OAKGPU_EMBED_FORM_FUSED, OAKGPU_EMBED_FORM_FUSED};
+  return {(kinds & 1) ? (prow_ok ? OAKGPU_EMBED_FORM_ROWS : OAKGPU_EMBED_FORM_TILE) : 0,
+          (kinds & 2) ? (arow_ok ? OAKGPU_EMBED_FORM_ROWS : OAKGPU_EMBED_FORM_TILE) : 0};
+}
+
 static int leaf_eval_impl(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battles, const uint8_t *durations, uint32_t n,
                           float *values, float *embedding_out, const oak::PolicyArgs *pol, uint32_t *slot_tags = nullptr) {
   if (!ctx || !net) return oakgpu_fail_msg("oakgpu_leaf_eval_dev: null ctx/net");
@@ -3077,17 +3101,10 @@ static int leaf_eval_impl(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battl
     if (!emb) return -1;
   }
   const oak::NetDev &D = net->dev;
-  // The row kernels (k_embed_prows / k_embed_arows) take embedding nets up to 128 hidden channels, party outputs up to 64
-  // and active outputs up to 128; anything wider goes to k_embed_lds (the 64-item tile form).  OAKGPU_EMBED_TILE=1 forces
-  // the tile form (A/B and a second implementation for the tests).
-  static const bool force_tile = getenv("OAKGPU_EMBED_TILE") != nullptr;
-  const bool rows = !force_tile && net->embed_safe; // (the row kernels multiply as bf16 triples: see embed_safe)
-  const bool prow_ok = rows && D.p_hidden <= 128 && D.p_out <= 64, arow_ok = rows && D.a_hidden <= 128 && D.a_out <= 32 * oak::AR_MAX_NBO;
+  const EmbedRoute route = embed_route(ctx, net);
   hipEvent_t *tev = (hipEvent_t *)oakgpu_ctx_timing_events(ctx); // diagnostic only (oakgpu_set_kernel_timing)
-  static const int kinds = getenv("OAKGPU_EMBED_KINDS") ? atoi(getenv("OAKGPU_EMBED_KINDS")) : 3; // diagnostics: 1 party, 2 actives
-  static const bool split = getenv("OAKGPU_EMBED_SPLIT") != nullptr; // A/B: the two passes as two launches
   oak::EmbedTileArgs tp{D, battles, durations, n, emb, 0, nullptr, nullptr}, tact{D, battles, durations, n, emb, 1, nullptr, nullptr};
-  if (slot_tags && (kinds & 1)) { // cached party-slot pass: tag comparison first, then only the changed slots (work list)
+  if (slot_tags && route.party) { // cached party-slot pass: tag comparison first, then only the changed slots (work list)
     uint8_t *ws = (uint8_t *)oakgpu_ctx_workspace(ctx, 2, (size_t)n * 10 * sizeof(oak::PartyWork) + 16);
     if (!ws) return -1;
     uint32_t *count = (uint32_t *)ws;
@@ -3103,25 +3120,24 @@ static int leaf_eval_impl(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battl
   const uint32_t wg_p = slot_tags ? 256u : (wg_p0 < 256 ? wg_p0 : 256); // (a work list's length is only known on the device)
   const uint32_t nmt_a = (n * 2 + oak::ER_ITEMS - 1) / oak::ER_ITEMS, wg_a0 = (nmt_a + oak::AR_WAVES - 1) / oak::AR_WAVES, wg_a = wg_a0 < 256 ? wg_a0 : 256;
   const size_t ar_lds = oak::ar_bytes((D.a_out + 31) / 32);
-  // default: both embedding passes in one launch (k_embed_both).  Not while the per-kernel timing diagnostic is on (it
-  // wants an event between the passes).
-  if (prow_ok && arow_ok && kinds == 3 && !split && !tev) {
+  if (route.party == OAKGPU_EMBED_FORM_FUSED) {
     const size_t lds = oak::PR_BYTES > ar_lds ? oak::PR_BYTES : ar_lds;
     if (slot_tags) hipLaunchKernelGGL(oak::k_embed_both<true>, dim3(wg_p + wg_a), dim3(oak::PR_BLOCK), lds, stream, tp, tact, wg_p);
     else hipLaunchKernelGGL(oak::k_embed_both<false>, dim3(wg_p + wg_a), dim3(oak::PR_BLOCK), lds, stream, tp, tact, wg_p);
   } else {
-    if (kinds & 1) {
+    if (route.party) {
+      const bool prow = route.party == OAKGPU_EMBED_FORM_ROWS;
       const uint32_t ntiles = (n * 10u + oak::ET - 1) / oak::ET, grid = ntiles < 256 ? ntiles : 256;
       // (the work list goes through the same kernel as the plain pass, so that cached and plain embeddings are bit-identical)
-      if (prow_ok && slot_tags) hipLaunchKernelGGL(oak::k_embed_prows<true>, dim3(wg_p), dim3(oak::PR_BLOCK), oak::PR_BYTES, stream, tp);
-      else if (prow_ok) hipLaunchKernelGGL(oak::k_embed_prows<false>, dim3(wg_p), dim3(oak::PR_BLOCK), oak::PR_BYTES, stream, tp);
+      if (prow && slot_tags) hipLaunchKernelGGL(oak::k_embed_prows<true>, dim3(wg_p), dim3(oak::PR_BLOCK), oak::PR_BYTES, stream, tp);
+      else if (prow) hipLaunchKernelGGL(oak::k_embed_prows<false>, dim3(wg_p), dim3(oak::PR_BLOCK), oak::PR_BYTES, stream, tp);
       else if (slot_tags) hipLaunchKernelGGL((oak::k_embed_lds<false, true>), dim3(grid), dim3(oak::EL_BLOCK), oak::ELayout<false>::BYTES, stream, tp);
       else hipLaunchKernelGGL(oak::k_embed_lds<false>, dim3(grid), dim3(oak::EL_BLOCK), oak::ELayout<false>::BYTES, stream, tp);
     }
     if (tev) (void)hipEventRecord(tev[1], stream);
-    if (kinds & 2) {
+    if (route.actives) {
       const uint32_t ntiles = (n * 2u + oak::ET - 1) / oak::ET, grid = ntiles < 256 ? ntiles : 256;
-      if (arow_ok) hipLaunchKernelGGL(oak::k_embed_arows, dim3(wg_a), dim3(oak::AR_BLOCK), ar_lds, stream, tact);
+      if (route.actives == OAKGPU_EMBED_FORM_ROWS) hipLaunchKernelGGL(oak::k_embed_arows, dim3(wg_a), dim3(oak::AR_BLOCK), ar_lds, stream, tact);
       else hipLaunchKernelGGL(oak::k_embed_lds<true>, dim3(grid), dim3(oak::EL_BLOCK), oak::ELayout<true>::BYTES, stream, tact);
     }
   }
@@ -3197,6 +3213,15 @@ int oakgpu_leaf_cache_last_count(oakgpu_ctx *ctx, uint32_t *slots_recomputed) { 
   hipError_t e = hipMemcpyAsync(slots_recomputed, count, 4, hipMemcpyDeviceToHost, stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
   if (e != hipSuccess) return oakgpu_fail_hip((int)e, "oakgpu_leaf_cache_last_count");
+  return 0;
+}
+
+int oakgpu_leaf_embed_forms(oakgpu_ctx *ctx, const oakgpu_net *net, int *party, int *actives, int *party_blocks) {
+  if (!ctx || !net) return oakgpu_fail_msg("oakgpu_leaf_embed_forms: null ctx/net");
+  const EmbedRoute route = embed_route(ctx, net);
+  if (party) *party = route.party;
+  if (actives) *actives = route.actives;
+  if (party_blocks) *party_blocks = route.party == OAKGPU_EMBED_FORM_ROWS || route.party == OAKGPU_EMBED_FORM_FUSED ? oak::prows_blocks(net->dev.p_out) : 0;
   return 0;
 }
 

@@ -200,3 +200,233 @@ def root_steps_reference(root_b, root_d, root_r, lane_prng, reps, steps, slice, 
         else:
             executed[k] += int(ln.sum())
     return count, sum2, executed
+
+
+# ---- the party-slot cache key (include/oakgpu.h, oakgpu_leaf_eval_cached_dev) ---------------------------------------------
+_STATUS_KEY = None
+
+
+def _status_key_table():
+    """[status, sleep turns] -> the key's status byte: 0 for no status, else nn_oracle.status_index + 1."""
+    global _STATUS_KEY
+    if _STATUS_KEY is None:
+        import sys
+        sys.path.insert(0, os.path.join(ROOT, "oracle"))
+        import nn_oracle
+        t = np.zeros((256, 8), dtype=np.uint8)
+        for st in range(1, 256):
+            for sl in range(8):
+                t[st, sl] = nn_oracle.status_index(st, sl) + 1
+        _STATUS_KEY = t
+    return _STATUS_KEY
+
+
+def party_slot_keys(battles, durations):
+    """Host restatement of the cache's slot key, from the contract alone: bench slot q (0-4) of side s is the Pokemon named by order
+    byte 177 + q of the side's 184 bytes; order id 0 or stored hp 0 -> dead; else the 24 stored bytes with hp (bytes 18-19) dropped,
+    each move's PP byte reduced to has-PP and the status byte replaced by its encoder index + 1 (0: none), the sleep turns being
+    (side's durations word >> 3 (q + 1)) & 7.  battles [n, 384], durations [n, 8] -> keys uint8 [n, 10, 24] (item = side * 5 + q;
+    a dead slot's key is all 0xFF, which no live key is: its byte 19 is 0), live bool [n, 10]."""
+    b = np.ascontiguousarray(battles, dtype=np.uint8)
+    n = b.shape[0]
+    sides = b[:, :368].reshape(n, 2, 184)
+    ids = sides[:, :, 177:182].astype(np.int64)                                  # [n, 2, 5]
+    party = sides[:, :, :144].reshape(n, 2, 6, 24)
+    pk = np.take_along_axis(party, np.maximum(ids - 1, 0)[..., None], axis=2)     # [n, 2, 5, 24]
+    hp = pk[..., 18].astype(np.uint32) | (pk[..., 19].astype(np.uint32) << 8)
+    live = (ids != 0) & (hp != 0)
+    dur = np.ascontiguousarray(durations, dtype=np.uint8).view("<u4").reshape(n, 2).astype(np.uint32)
+    sleep = (dur[:, :, None] >> (3 * np.arange(1, 6, dtype=np.uint32))[None, None, :]) & 7    # [n, 2, 5]
+    key = pk.copy()
+    key[..., 18:20] = 0
+    key[..., 11:18:2] = key[..., 11:18:2] != 0
+    key[..., 20] = np.where(pk[..., 20] != 0, _status_key_table()[pk[..., 20], sleep], 0)
+    key[~live] = 0xFF
+    return key.reshape(n, 10, 24), live.reshape(n, 10)
+
+
+def expected_recomputes(prev_keys, keys, live):
+    """The slots a cached call must re-embed: the live ones whose key differs from the previous call's (every live slot on the first
+    call, prev_keys None)."""
+    if prev_keys is None:
+        return int(live.sum())
+    return int((live & (prev_keys != keys).any(axis=-1)).sum())
+
+
+# ---- one field of one bench slot at a time (tests of the cache key) ----------------------------------------------------------
+def bench_slot_choice(battles, seed):
+    """Per lane, the (side, order position 1-5) of a live bench Pokemon, chosen at random (any bench position where none is live)."""
+    rng = np.random.default_rng(seed)
+    n = battles.shape[0]
+    side, pos = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    for i in range(n):
+        cand = []
+        for s in range(2):
+            for p in range(1, 6):
+                pid = int(battles[i, 184 * s + 176 + p])
+                if pid and (int(battles[i, 184 * s + 24 * (pid - 1) + 18]) | int(battles[i, 184 * s + 24 * (pid - 1) + 19])):
+                    cand.append((s, p))
+        if not cand:
+            cand = [(int(rng.integers(0, 2)), int(rng.integers(1, 6)))]
+        side[i], pos[i] = cand[int(rng.integers(0, len(cand)))]
+    return side, pos
+
+
+def _other(rng, cur, lo, hi):
+    """A random value in [lo, hi] other than cur."""
+    v = int(rng.integers(lo, hi))
+    return v + 1 if v >= cur else v
+
+
+SLEEP_STATUS, REST = 0x07, 0x80
+
+
+def bench_slot_mutations():
+    """The mutation classes, in the order they are applied (several need the state the one before left: hp restored after hp 0, PP back
+    from 0, a sleep after PAR ...).  Each is (name, fn(b, d, side, pos, rng, memo)) editing ONE bench slot of every lane in place
+    (b [n, 384], d [n, 8]); only valid field values are written (type nibbles 0-14, move ids 0-165, real statuses)."""
+    def pk_off(b, i, s, p):
+        pid = int(b[i, 184 * s + 176 + p])
+        return 184 * s + 24 * (pid - 1) if pid else None
+
+    def each(f):
+        def run(b, d, side, pos, rng, memo):
+            for i in range(b.shape[0]):
+                o = pk_off(b, i, int(side[i]), int(pos[i]))
+                if o is not None:
+                    f(b, d, i, int(side[i]), int(pos[i]), o, rng, memo)
+        return run
+
+    def u16(b, i, o):
+        return int(b[i, o]) | (int(b[i, o + 1]) << 8)
+
+    def put16(b, i, o, v):
+        b[i, o], b[i, o + 1] = v & 0xFF, v >> 8
+
+    def set_hp(b, d, i, s, p, o, rng, memo):
+        if u16(b, i, o + 18):
+            put16(b, i, o + 18, _other(rng, u16(b, i, o + 18), 1, max(u16(b, i, o), 2)))
+
+    def hp_zero(b, d, i, s, p, o, rng, memo):
+        memo["hp", i] = u16(b, i, o + 18)
+        put16(b, i, o + 18, 0)
+
+    def hp_restore(b, d, i, s, p, o, rng, memo):
+        put16(b, i, o + 18, memo.get(("hp", i), 0))
+
+    def stat(k):
+        def f(b, d, i, s, p, o, rng, memo):
+            put16(b, i, o + 2 * k, _other(rng, u16(b, i, o + 2 * k), 1, 999))
+        return f
+
+    def move(m):
+        def f(b, d, i, s, p, o, rng, memo):
+            b[i, o + 10 + 2 * m] = (0, 165, _other(rng, int(b[i, o + 10 + 2 * m]), 1, 164))[i % 3]
+        return f
+
+    def pp_slot(b, i, o):                  # a move slot with PP, slot i % 4 first: every slot's has-PP bit gets its turn
+        for m in range(i, i + 4):
+            if b[i, o + 11 + 2 * (m % 4)]:
+                return m % 4
+        return None
+
+    def pp_change(b, d, i, s, p, o, rng, memo):
+        m = pp_slot(b, i, o)
+        if m is not None:
+            b[i, o + 11 + 2 * m] = _other(rng, int(b[i, o + 11 + 2 * m]), 1, 63)
+
+    def pp_zero(b, d, i, s, p, o, rng, memo):
+        m = pp_slot(b, i, o)
+        memo["pp", i] = (m, int(b[i, o + 11 + 2 * m])) if m is not None else None
+        if m is not None:
+            b[i, o + 11 + 2 * m] = 0
+
+    def pp_back(b, d, i, s, p, o, rng, memo):
+        if memo.get(("pp", i)) is not None:
+            m, pp = memo["pp", i]
+            b[i, o + 11 + 2 * m] = pp
+
+    def set_turns(d, i, s, p, v):          # the sleep turns of order position p: bits 3p .. 3p + 2 of the side's durations word
+        w = int.from_bytes(bytes(d[i, 4 * s:4 * s + 4]), "little")
+        w = (w & ~(7 << (3 * p))) | (v << (3 * p))
+        d[i, 4 * s:4 * s + 4] = np.frombuffer(w.to_bytes(4, "little"), np.uint8)
+
+    def status(v, turns=None):
+        def f(b, d, i, s, p, o, rng, memo):
+            b[i, o + 20] = v(rng) if callable(v) else v
+            if turns is not None:
+                set_turns(d, i, s, p, turns)
+        return f
+
+    def turns_change(b, d, i, s, p, o, rng, memo):
+        w = int.from_bytes(bytes(d[i, 4 * s:4 * s + 4]), "little")
+        set_turns(d, i, s, p, _other(rng, (w >> (3 * p)) & 7, 0, 7))
+
+    def sleep_counter(b, d, i, s, p, o, rng, memo):
+        st = int(b[i, o + 20])
+        b[i, o + 20] = (st & ~SLEEP_STATUS) | _other(rng, st & SLEEP_STATUS, 1, 7)
+
+    def byte(k, lo, hi):
+        def f(b, d, i, s, p, o, rng, memo):
+            b[i, o + k] = _other(rng, int(b[i, o + k]), lo, hi)
+        return f
+
+    def types(b, d, i, s, p, o, rng, memo):
+        t = int(b[i, o + 22])
+        while int(b[i, o + 22]) == t:
+            b[i, o + 22] = int(rng.integers(0, 15)) | (int(rng.integers(0, 15)) << 4)
+
+    def swap_bench(b, d, side, pos, rng, memo):
+        for i in range(b.shape[0]):
+            a, c = 184 * int(side[i]) + 176 + int(pos[i]), 184 * int(side[i]) + 176 + 1 + int(pos[i]) % 5
+            b[i, a], b[i, c] = b[i, c], b[i, a]
+
+    def swap_active(b, d, side, pos, rng, memo):
+        for i in range(b.shape[0]):
+            a, c = 184 * int(side[i]) + 176, 184 * int(side[i]) + 176 + int(pos[i])
+            b[i, a], b[i, c] = b[i, c], b[i, a]
+
+    def empty(b, d, side, pos, rng, memo):
+        for i in range(b.shape[0]):
+            b[i, 184 * int(side[i]) + 176 + int(pos[i])] = 0
+
+    clear = ("status_clear", each(status(0)))
+    return [
+        ("none", lambda *a: None),
+        ("hp", each(set_hp)),
+        ("hp_zero", each(hp_zero)),
+        ("hp_restore", each(hp_restore)),
+    ] + [("stat_%s" % nm, each(stat(k))) for k, nm in enumerate(("hp_max", "atk", "def", "spe", "spc"))] + [
+        ("move_%d" % (m + 1), each(move(m))) for m in range(4)] + [
+        ("pp_nonzero_to_nonzero", each(pp_change)),
+        ("pp_to_zero", each(pp_zero)),
+        ("pp_from_zero", each(pp_back)),
+        clear, ("status_psn", each(status(0x08))),
+        clear, ("status_brn", each(status(0x10))),
+        clear, ("status_frz", each(status(0x20))),
+        clear, ("status_par", each(status(0x40, turns=0))),
+        ("par_to_sleep_turns_0", each(status(lambda rng: int(rng.integers(1, 8))))),
+        ("sleep_counter", each(sleep_counter)),
+        ("sleep_turns_asleep", each(turns_change)),
+        clear, ("status_sleep", each(status(lambda rng: int(rng.integers(1, 8))))),
+        clear, ("status_rest", each(status(lambda rng: REST | int(rng.integers(1, 3))))),
+        ("sleep_turns_rest", each(turns_change)),
+        clear, ("sleep_turns_awake", each(turns_change)),
+        ("species", each(byte(21, 1, 151))),
+        ("level", each(byte(23, 1, 100))),
+        ("types", each(types)),
+        ("swap_bench", swap_bench),
+        ("swap_active", swap_active),
+        ("empty_slot", empty),
+    ]
+
+
+def midgame_batch(n, seed0, steps=(20, 30, 40)):
+    """n random OU battles, consecutive thirds advanced steps[0] / [1] / [2] random turn-steps on the oracle -> (battles, durations)."""
+    b, d, p, r = make_random_ou_batch(n, seed0=seed0)
+    parts = np.array_split(np.arange(n), len(steps))
+    for k, idx in zip(steps, parts):
+        bb, dd, pp, rr = (np.ascontiguousarray(x[idx]) for x in (b, d, p, r))
+        rollout_batch(bb, dd, rr, pp, max_steps=k, threads=4)
+        b[idx], d[idx] = bb, dd
+    return b, d

@@ -1,5 +1,6 @@
 """GPU: fused leaf evaluator (K2 encode+embed, K3 fp32-MFMA main net) vs the numpy oracle.
 Tolerance from BASELINE.json north_star: |value - reference| <= 1e-5."""
+import ctypes as C
 import os
 import sys
 
@@ -538,44 +539,195 @@ def test_two_contexts_share_one_network(gpu_ctx):
     other.close()
 
 
-def test_cached_leaf_eval_equals_plain_eval_over_a_resident_batch(gpu_ctx, tmp_path):
-    """oakgpu_leaf_eval_cached_dev (party-slot embeddings cached by exact identity tags, the GPU form of PokemonCache): a
-    resident batch stepped turn by turn on the device -- values AND embeddings are bit-identical to the uncached evaluator
-    every turn; then other battles are loaded into the same lanes WITHOUT resetting the tags, and it is still exact."""
+# The forms of the cached call's embedding passes (OAKGPU_EMBED_FORM_*, include/oakgpu.h): case -> (party pass, actives' pass, output
+# blocks per wave of the party row kernel), as oakgpu_leaf_embed_forms reports them.  The cached party pass is the work-list (LIST)
+# instantiation of the party kernel named: fused = k_embed_both<true> (embed_prows_body<true, NBO>), rows = k_embed_prows<true>
+# launched alone, tile = k_embed_lds<false, true>.
+FUSED, ROWS, TILE = 3, 2, 1
+CACHE_FORMS = {
+    "rows_nbo2": (FUSED, FUSED, 2),            # NET256: party out 59
+    "rows_nbo1": (FUSED, FUSED, 1),            # net_tiny: party out 8
+    "prows_timing": (ROWS, ROWS, 2),           # NET256 on a context with kernel timing on (an event between the passes)
+    "prows_wide_actives": (ROWS, TILE, 2),     # active out 128: beyond the row kernel
+    "tile_list_wide": (TILE, ROWS, 0),         # party out 99
+    "tile_list_unsafe": (TILE, TILE, 0),       # second-layer weights above 2^20: not embed_safe
+}
+
+
+class _CacheCase:
+    """The network (and context) of one CACHE_FORMS case, its oracle, and the check that the case runs the forms it is named after."""
+
+    def __init__(self, gpu_ctx, tmp_path, case):
+        from oak_amd import _lib, netfile
+        from oak_amd.engine import Context, Network
+        self.ctx, self.own_ctx = gpu_ctx, None
+        path = oracle_path = NET256
+        if case == "rows_nbo1":
+            path = oracle_path = os.path.join(ROOT, "tests", "golden", "net_tiny.battle.net")
+        elif case == "prows_wide_actives":
+            path = oracle_path = str(tmp_path / "wide_actives.battle.net")
+            netfile.write_random_net(path, seed=3, hidden=64, value_hidden=224, pokemon_hidden=64, active_hidden=96, pokemon_out=64, active_out=128)
+        elif case == "tile_list_wide":
+            path = oracle_path = str(tmp_path / "wide_party.battle.net")
+            netfile.write_random_net(path, seed=3, hidden=64, value_hidden=32, pokemon_out=99)
+        elif case == "tile_list_unsafe":       # as test_bf16_triple_embedding_nets_at_the_edges_of_the_exponent_range[down110_up110]: the same function
+            path = str(tmp_path / "unsafe.battle.net")
+            _rewrite_net(NET256, path, lambda i, b, W: (b * np.float32(2.0 ** -110), W * np.float32(2.0 ** -110)) if i in (0, 2)
+                         else (b, W * np.float32(2.0 ** 110)) if i in (1, 3) else (b, W))
+        if case == "prows_timing":
+            self.ctx = self.own_ctx = Context(0)
+            _lib.check(self.ctx.lib.oakgpu_set_kernel_timing(self.ctx.handle, 1))
+        self.lib, self.h = self.ctx.lib, self.ctx.handle
+        self.net = Network(self.ctx, path=path)
+        self.onet = NN.Net(oracle_path)
+        forms = [C.c_int(-1), C.c_int(-1), C.c_int(-1)]
+        _lib.check(self.lib.oakgpu_leaf_embed_forms(self.h, self.net.handle, *[C.byref(f) for f in forms]))
+        assert tuple(f.value for f in forms) == CACHE_FORMS[case], (case, [f.value for f in forms])
+        self.emb_dim = self.net.shape()[0]
+
+    def close(self):
+        self.net.close()
+        if self.own_ctx is not None:
+            self.own_ctx.close()
+
+
+class _CachedAndPlain:
+    """A resident batch's persistent cache buffers: every call() runs oakgpu_leaf_eval_dev and oakgpu_leaf_eval_cached_dev on the
+    device battles, asserts that embeddings and values are bit-identical and that the call re-embedded exactly the slots the host
+    restatement of the key (oracle_lib.party_slot_keys) says changed; returns the cached embeddings and values."""
+
+    def __init__(self, cc, n):
+        from hipmem import Dev
+        self.cc, self.n, self.prev = cc, n, None
+        self.v_plain, self.v_cached = Dev(np.zeros(n, np.float32)), Dev(np.zeros(n, np.float32))
+        self.e_plain = Dev(np.zeros((n, cc.emb_dim), np.float32))
+        self.e_cached = Dev(np.zeros((n, cc.emb_dim), np.float32), fill=0x7F)    # garbage: every slot must get written
+        self.tags = Dev(np.zeros((n, 10, 6), np.uint32), fill=0xFF)
+
+    def call(self, gb, gd, battles, durations, what):
+        from oak_amd import _lib
+        cc, n = self.cc, self.n
+        _lib.check(cc.lib.oakgpu_leaf_eval_dev(cc.h, cc.net.handle, gb.p, gd.p, n, self.v_plain.p, self.e_plain.p))
+        _lib.check(cc.lib.oakgpu_leaf_eval_cached_dev(cc.h, cc.net.handle, gb.p, gd.p, n, self.v_cached.p, self.e_cached.p, self.tags.p))
+        got = C.c_uint32()
+        _lib.check(cc.lib.oakgpu_leaf_cache_last_count(cc.h, C.byref(got)))
+        cc.ctx.synchronize()
+        ep, ec = self.e_plain.host(), self.e_cached.host()
+        bad = np.nonzero((ep != ec).any(axis=1))[0]
+        assert bad.size == 0, (what, int(bad[0]), np.nonzero(ep[bad[0]] != ec[bad[0]])[0][:8])
+        vc = self.v_cached.host()
+        assert (self.v_plain.host() == vc).all(), what
+        keys, live = O.party_slot_keys(battles, durations)
+        exp = O.expected_recomputes(self.prev, keys, live)
+        hit = 1.0 - got.value / max(int(live.sum()), 1)
+        assert got.value == exp, (what, "recomputed", got.value, "expected", exp, "of live", int(live.sum()), "hit rate %.4f" % hit)
+        self.prev = keys
+        return ec, vc
+
+    def free(self):
+        for x in (self.v_plain, self.v_cached, self.e_plain, self.e_cached, self.tags):
+            x.free()
+
+
+@pytest.mark.parametrize("case,n", [(c, 3001) for c in CACHE_FORMS] + [(c, n) for c in ("rows_nbo2", "tile_list_wide") for n in (1, 205)])
+def test_cached_leaf_eval_equals_plain_eval_over_a_resident_batch(gpu_ctx, tmp_path, case, n):
+    """oakgpu_leaf_eval_cached_dev (party-slot embeddings cached by exact identity tags, the GPU form of PokemonCache) in every form
+    of its party pass: a resident batch stepped turn by turn on the device -- values AND embeddings are bit-identical to the uncached
+    evaluator every turn, and each call re-embeds exactly the slots whose key changed (all live slots on the first call); then other
+    battles are loaded into the same lanes WITHOUT resetting the tags, and it is still exact.  205 lanes = 2,050 slots cross one
+    k_party_tags block (2,048 slots)."""
     from hipmem import Dev
     from oak_amd import _lib
-    from oak_amd.engine import Network
-    path = NET256
-    net = Network(gpu_ctx, path=path)
-    lib, h = gpu_ctx.lib, gpu_ctx.handle
-    n = 3001
+    cc = _CacheCase(gpu_ctx, tmp_path, case)
+    lib, h = cc.lib, cc.h
     b, d, p, r = O.make_random_ou_batch(n, seed0=0xCAC4E)
     gb, gd, gp, gr = Dev(b), Dev(d), Dev(p), Dev(r)
     steps, vals = Dev(np.zeros(n, np.uint32)), Dev(np.zeros(n, np.float32))
-    v_plain, v_cached = Dev(np.zeros(n, np.float32)), Dev(np.zeros(n, np.float32))
-    e_plain, e_cached = Dev(np.zeros((n, 768), np.float32)), Dev(np.zeros((n, 768), np.float32), fill=0x7F)   # garbage: every slot must get written
-    tags = Dev(np.zeros((n, 10, 6), np.uint32), fill=0xFF)
+    cp = _CachedAndPlain(cc, n)
     for turn in range(45):
         if turn == 30:      # new battles in the same lanes, tags NOT reset: a tag is the slot's whole identity
             b2, d2, p2, r2 = O.make_random_ou_batch(n, seed0=0xBEEF00)
             gb.put(b2); gd.put(d2); gp.put(p2); gr.put(r2)
         _lib.check(lib.oakgpu_rollout_dev(h, gb.p, gd.p, gr.p, gp.p, n, 1, 0, gr.p, steps.p, vals.p, gb.p, gd.p))   # one turn, in place
-        _lib.check(lib.oakgpu_leaf_eval_dev(h, net.handle, gb.p, gd.p, n, v_plain.p, e_plain.p))
-        _lib.check(lib.oakgpu_leaf_eval_cached_dev(h, net.handle, gb.p, gd.p, n, v_cached.p, e_cached.p, tags.p))
-        gpu_ctx.synchronize()
-        ep, ec = e_plain.host(), e_cached.host()
-        bad = np.nonzero((ep != ec).any(axis=1))[0]
-        assert bad.size == 0, (turn, int(bad[0]), np.nonzero(ep[bad[0]] != ec[bad[0]])[0][:8])
-        assert (v_plain.host() == v_cached.host()).all(), turn
+        cc.ctx.synchronize()
+        ec, vc = cp.call(gb, gd, gb.host(), gd.host(), (case, turn))
     # and both agree with the oracle on the final states
     fb, fd = gb.host(), gd.host()
-    onet = NN.Net(path)
-    vc = v_cached.host()
     for i in range(0, n, 97):
-        assert abs(float(vc[i]) - float(NN.value_inference(onet, fb[i], fd[i]))) <= TOL
-    for x in (gb, gd, gp, gr, steps, vals, v_plain, v_cached, e_plain, e_cached, tags):
+        assert abs(float(vc[i]) - float(NN.value_inference(cc.onet, fb[i], fd[i]))) <= TOL
+    for x in (gb, gd, gp, gr, steps, vals):
         x.free()
-    net.close()
+    cp.free()
+    cc.close()
+
+
+@pytest.mark.parametrize("case", ["rows_nbo2", "tile_list_wide"])
+def test_cached_leaf_eval_follows_every_field_of_a_bench_slot(gpu_ctx, tmp_path, case):
+    """One field of one bench slot of every lane changed per call (oracle_lib.bench_slot_mutations: hp, hp 0 and back, each stat,
+    each move id -- to 0 and to Struggle too --, PP amounts and has-PP, every status, PAR -> sleep at 0 turns, the hidden sleep
+    counter, the slot's sleep-turn bits asleep / under Rest / awake, species, level, types, order swaps, an emptied slot): each call
+    re-embeds exactly the slots whose key changed, is bit-identical to the uncached evaluator, and embedding and value of every lane
+    agree with the numpy oracle; a slot whose hp went to 0, or whose order byte was cleared, has an all-zero block."""
+    from hipmem import Dev
+    cc = _CacheCase(gpu_ctx, tmp_path, case)
+    n = 512
+    b, d = O.midgame_batch(n, seed0=0x5107)
+    side, pos = O.bench_slot_choice(b, seed=11)
+    rng, memo = np.random.default_rng(12), {}
+    gb, gd = Dev(b), Dev(d)
+    cp = _CachedAndPlain(cc, n)
+    onet = cc.onet
+    block = side * onet.side_dim + (1 + onet.aod) + (pos - 1) * (1 + onet.pod)      # the chosen slot's block: hp ratio, embedding
+    lanes = np.arange(n)
+    for name, fn in [("fill", None)] + O.bench_slot_mutations():
+        if fn is not None:
+            fn(b, d, side, pos, rng, memo)
+            gb.put(b); gd.put(d)
+        ec, vc = cp.call(gb, gd, b, d, (case, name))
+        for i in range(n):
+            oe = NN.battle_embedding(onet, b[i], d[i])
+            assert np.abs(ec[i] - oe).max() <= 2e-5, (case, name, i, int(np.abs(ec[i] - oe).argmax()))
+            assert abs(float(vc[i]) - float(onet.main_value(oe))) <= TOL, (case, name, i)
+        if name in ("hp_zero", "empty_slot"):
+            assert (ec[lanes[:, None], block[:, None] + np.arange(1 + onet.pod)] == 0).all(), name
+        if name == "hp":                                     # the hp-ratio column follows without a recompute
+            pid = b[lanes, 184 * side + 176 + pos].astype(np.int64)
+            pk = b[lanes[:, None], 184 * side[:, None] + 24 * np.maximum(pid - 1, 0)[:, None] + np.arange(24)]
+            hp, mx = pk[:, 18] + 256 * pk[:, 19].astype(np.int64), pk[:, 0] + 256 * pk[:, 1].astype(np.int64)
+            live = (pid > 0) & (hp > 0)
+            assert (ec[lanes, block][live] == (hp[live].astype(np.float32) / mx[live].astype(np.float32))).all()
+    gb.free(); gd.free()
+    cp.free()
+    cc.close()
+
+
+def test_cached_leaf_eval_full_size(gpu_ctx):
+    """BASELINE configs[2] at full size: 65,536 resident lanes on the 768-256-256-256-1 net, one turn-step then a cached leaf
+    evaluation, 12 times: every turn cached and plain are bit-identical on every lane and the recompute count is the host
+    restatement's; after the last turn every 32nd lane against the C oracle."""
+    from hipmem import Dev
+    from oak_amd import _lib
+    cc = _CacheCase(gpu_ctx, None, "rows_nbo2")
+    lib, h = cc.lib, cc.h
+    n = 65536
+    b, d, p, r = O.make_random_ou_batch(n, seed0=0xF1115123)
+    gb, gd, gp, gr = Dev(b), Dev(d), Dev(p), Dev(r)
+    steps, vals = Dev(np.zeros(n, np.uint32)), Dev(np.zeros(n, np.float32))
+    cp = _CachedAndPlain(cc, n)
+    for turn in range(12):
+        _lib.check(lib.oakgpu_rollout_dev(h, gb.p, gd.p, gr.p, gp.p, n, 1, 0, gr.p, steps.p, vals.p, gb.p, gd.p))
+        cc.ctx.synchronize()
+        fb, fd = gb.host(), gd.host()
+        _, vc = cp.call(gb, gd, fb, fd, ("full size", turn))
+    cnet = O.CNet(NET256)
+    idx = np.arange(0, n, 32)
+    exp = cnet.value_inference_batch(np.ascontiguousarray(fb[idx]), np.ascontiguousarray(fd[idx]), threads=8)
+    assert np.abs(vc[idx] - exp).max() <= TOL
+    cnet.close()
+    for x in (gb, gd, gp, gr, steps, vals):
+        x.free()
+    cp.free()
+    cc.close()
 
 
 def test_active_move_slots_that_differ_from_the_stored_ones(gpu_ctx):
