@@ -276,8 +276,9 @@ int oakgpu_solve_matrix(const int32_t *payoffs, int m, int n, int discretize_fac
  * reference's binaries and pyoak.search configure it.  budget "4096" | "100ms" | "8s"; bandit "ucb-1.0" | "ucb1-2.0" |
  * "pucb-1.5" | "exp3-<gamma>[-<alpha>]" | "pexp3-..."; eval "" / "mc" | "fp" | <.battle.net path> (loaded once per device
  * and kept, like Agent::network_ptr); matrix_ucb "" | "<delay>-<interval>-<minimum>-<c>".  Unparsable strings fail with
- * the reference's error texts (where it throws std::runtime_error); `table` and `discrete` agents are refused: those two
- * components are not built.  batch = descents in flight, 0 = chosen from the budget. */
+ * the reference's error texts (where it throws std::runtime_error); `table` agents are refused (transposition-table heaps are
+ * not built).  `discrete` loads the <.battle.net> through oakgpu_net_load_discrete (the int8 main net, kept apart from the fp32
+ * network of the same path).  batch = descents in flight, 0 = chosen from the budget. */
 typedef struct {
   const char *budget, *bandit, *eval, *matrix_ucb;
   int discrete, table;
@@ -489,6 +490,21 @@ int oakgpu_random_ou_battles_dev(oakgpu_ctx *ctx, uint64_t seed0, uint32_t n, ui
 int oakgpu_net_load(oakgpu_ctx *ctx, const char *path, oakgpu_net **out);
 int oakgpu_net_load_memory(oakgpu_ctx *ctx, const void *bytes, size_t size, oakgpu_net **out);
 void oakgpu_net_free(oakgpu_ctx *ctx, oakgpu_net *net);
+/* The quantized ("discrete") network: Agent.discrete (search.cc:100-147, nn/battle/quantized).  The file's header must encode
+ * clamp activations; the main net must be 768-H-H-VH-1 with H, VH, PH in {32, 64, 128}, VH <= H, PH <= H; every main-net weight
+ * strictly inside (-2, 2).  Failures carry the reference's texts ("Agent: .discrete was specified but ...", "Invalid layer size
+ * for quantized net ...", "<i>non clamped<w>").  Main-net weights become int8 trunc(64 w), biases int32 trunc((64 b) 127); the
+ * embedding nets stay fp32 (party slots evaluated with ReLU, the actives with clamp, as the reference's caches fill them).  The
+ * leaf entry points (oakgpu_leaf_eval*, oakgpu_leaf_eval_policy*, oakgpu_leaf_eval_cached_dev) take such a handle: the
+ * embedding becomes bytes static_cast<uint8_t>(127 f) and the main net runs in int32 on the i8 matrix pipe (k_mainnet_i8),
+ * bit-exact to the reference's integer arithmetic; embedding_out stays the fp32 embedding before quantization. */
+int oakgpu_net_load_discrete(oakgpu_ctx *ctx, const char *path, oakgpu_net **out);
+int oakgpu_net_load_discrete_memory(oakgpu_ctx *ctx, const void *bytes, size_t size, oakgpu_net **out);
+int oakgpu_net_is_discrete(const oakgpu_net *net);
+/* Diagnostic: the quantized network's integer intermediates for n leaves -- q_embedding (n x 768 bytes, the main net's input)
+ * and value_acc (n int32: value_fc3's output; value = sigmoid(value_acc / 8128)).  Device pointers; the network must be discrete. */
+int oakgpu_leaf_eval_discrete_raw_dev(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battles, const uint8_t *durations, uint32_t n,
+                                      uint8_t *q_embedding, int32_t *value_acc);
 /* MainNet::shape() (main-net.h:32-34): fc0.in, fc0.out, value_fc2.out, p1_policy_fc2.out */
 int oakgpu_net_shape(const oakgpu_net *net, int *in_dim, int *hidden, int *value_hidden, int *policy_hidden);
 /* How the main net's three dense layers are multiplied (results are fp32 either way, held to the same 1e-5 against the
@@ -501,6 +517,7 @@ int oakgpu_net_shape(const oakgpu_net *net, int *in_dim, int *hidden, int *value
 #define OAKGPU_MAIN_FP32 0
 #define OAKGPU_MAIN_SPLIT 1
 #define OAKGPU_MAIN_PAIR 2
+#define OAKGPU_MAIN_INT8 3 /* a network of oakgpu_net_load_discrete*: reported only, never settable (set returns -1) */
 int oakgpu_net_set_main_precision(oakgpu_net *net, int mode);
 /* Edges of the bf16-triple form.  (1) A parameter file with a NaN / inf anywhere is REFUSED by oakgpu_net_load* ("non-finite
  * parameter ... in <layer>"); the reference loads it and propagates NaN (nn/affine.h:72-85 is a plain fp32 W x + b).  (2) A

@@ -89,6 +89,11 @@ private:
 class Network {
 public:
   Network(Context &ctx, const std::string &path) : ctx_{ctx} { check(oakgpu_net_load(ctx_.get(), path.c_str(), &net_)); }
+  // discrete = the quantized int8 main net (Agent.discrete): oakgpu_net_load_discrete
+  Network(Context &ctx, const std::string &path, bool discrete) : ctx_{ctx} {
+    check(discrete ? oakgpu_net_load_discrete(ctx_.get(), path.c_str(), &net_) : oakgpu_net_load(ctx_.get(), path.c_str(), &net_));
+  }
+  bool discrete() const { return oakgpu_net_is_discrete(net_) != 0; }
   ~Network() { oakgpu_net_free(ctx_.get(), net_); }
   Network(const Network &) = delete;
   Network &operator=(const Network &) = delete;

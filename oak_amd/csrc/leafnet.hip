@@ -2444,9 +2444,13 @@ __global__ __launch_bounds__(PolicyRows<PB>::BLOCK) void k_policy_rows(PolicyArg
 
 } // namespace oak
 
+#include "mainnet_i8.hpp"
+
 // =================================== C ABI =====================================================
 struct oakgpu_net {
   oak::NetDev dev;
+  bool discrete = false; // loaded by oakgpu_net_load_discrete*: the main net runs quantized (k_mainnet_i8, q), the embedding nets as below
+  oak::QNetDev q{};
   std::vector<void *> allocs;
   int in_dim, hidden, value_hidden, policy_hidden; // unpadded, as in the file
   int device;        // the device the weights live on
@@ -2813,6 +2817,79 @@ std::vector<float> prows_image(const HostAffine &p0, const HostAffine &p1) {
   return img;
 }
 
+// ---- the quantized main net (oakgpu_net_load_discrete*): nn/battle/quantized/affine.h:74-99, main-net.h:36-66
+std::string float_text(float v) { char buf[64]; snprintf(buf, sizeof buf, "%f", (double)v); return buf; } // std::to_string(float)
+// visit_quantized_network's shape checks, in its order (network.h:182-275)
+int quant_shape_check(uint32_t in, uint32_t h, uint32_t vh, uint32_t ph) {
+  auto bad = [](const std::string &m) { return oakgpu_fail_msg(("Invalid layer size for quantized net " + m + " (check code for valid sizes).").c_str()); };
+  auto ok = [](uint32_t x) { return x == 32 || x == 64 || x == 128; };
+  if (in != 768) return bad("Side dim: " + std::to_string(in));
+  if (!ok(h)) return bad("Hidden: " + std::to_string(h));
+  if (!ok(vh)) return bad("Value hidden: " + std::to_string(vh));
+  if (!ok(ph)) return bad("Policy hidden: " + std::to_string(ph));
+  if (h < vh) return bad("Value hidden cannot be larger than hidden.");
+  if (h < ph) return bad("Policy hidden cannot be larger than hidden.");
+  return 0;
+}
+// AffineTransform::try_copy_parameters: weight int8 = trunc(w * 64), refused unless strictly inside (-2, 2) (NaN included: its
+// text is the reference's); bias int32 = trunc((b * 64) * 127), two fp32 operations (the reference's cast of a bias outside int32
+// is undefined: refused here).  `rows` pads the output rows with zeros (the policy fc3 layers: 315 -> 320).
+struct QLayer { std::vector<int8_t> w; std::vector<int32_t> b; };
+int quantize_layer(const HostAffine &a, uint32_t in, uint32_t out, uint32_t rows, const char *name, QLayer &q) {
+  if (a.in != in) return oakgpu_fail_msg("bad in dim");
+  if (std::min(a.out, rows) != out) return oakgpu_fail_msg("bad out dim");
+  q.w.assign((size_t)rows * in, 0);
+  q.b.assign(rows, 0);
+  for (size_t i = 0; i < (size_t)out * in; ++i) {
+    const float x = a.w[i];
+    if (!(x < 2.0f) || !(x > -2.0f)) return oakgpu_fail_msg((std::to_string(i) + "non clamped" + float_text(x)).c_str());
+    q.w[i] = (int8_t)(x * 64.0f);
+  }
+  for (uint32_t i = 0; i < out; ++i) {
+    const float x = (a.b[i] * 64.0f) * 127.0f;
+    if (!(x >= -2147483648.0f && x < 2147483648.0f))
+      return oakgpu_fail_msg(("quantized net: bias " + std::to_string(i) + " of " + name + " is outside int32 (" + float_text(a.b[i]) + ")").c_str());
+    q.b[i] = (int32_t)x;
+  }
+  return 0;
+}
+// k_mainnet_i8's LDS image.  fc0: 16 bytes ((t * NB + b) * 64 + lane) = W0[32 b + (lane & 31)][32 t + 16 (lane >> 5) + j];
+// fc1 and value_fc2 (input = the previous layer's accumulators): 16 bytes ((s * NBo + b) * 64 + lane) =
+// W[32 b + (lane & 31)][32 s + (j & 3) + 8 (j >> 2) + 4 (lane >> 5)] -- the k of byte j of lane half h in an accumulator tile.
+std::vector<uint8_t> qnet_image(const QLayer &fc0, const QLayer &fc1, const QLayer &v2, int H, int VH) {
+  const int NB = H / 32, NBv = VH / 32;
+  std::vector<uint8_t> img(oak::qi_lds_bytes(H, VH), 0);
+  uint8_t *p = img.data();
+  for (int t = 0; t < oak::QI_T0; ++t)
+    for (int b = 0; b < NB; ++b)
+      for (int lane = 0; lane < 64; ++lane)
+        for (int j = 0; j < 16; ++j)
+          p[((size_t)(t * NB + b) * 64 + lane) * 16 + j] = (uint8_t)fc0.w[(size_t)(32 * b + (lane & 31)) * oak::QI_IN + 32 * t + 16 * (lane >> 5) + j];
+  p += (size_t)oak::QI_T0 * NB * 1024;
+  auto acc_order = [&](const QLayer &q, int nbo) {
+    for (int s = 0; s < NB; ++s)
+      for (int b = 0; b < nbo; ++b)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int j = 0; j < 16; ++j)
+            p[((size_t)(s * nbo + b) * 64 + lane) * 16 + j] = (uint8_t)q.w[(size_t)(32 * b + (lane & 31)) * H + 32 * s + (j & 3) + 8 * (j >> 2) + 4 * (lane >> 5)];
+    p += (size_t)NB * nbo * 1024;
+  };
+  acc_order(fc1, NB);
+  acc_order(v2, NBv);
+  return img;
+}
+template <class T>
+int upload_raw(oakgpu_net *net, const std::vector<T> &h, const T **out) {
+  void *d = nullptr;
+  hipError_t e = hipMalloc(&d, h.size() * sizeof(T));
+  if (e != hipSuccess) return oakgpu_fail_hip((int)e, "hipMalloc(net)");
+  net->allocs.push_back(d);
+  e = hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return oakgpu_fail_hip((int)e, "hipMemcpy(net)");
+  *out = (const T *)d;
+  return 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -2825,17 +2902,31 @@ void oakgpu_net_free(oakgpu_ctx *ctx, oakgpu_net *net) {
   delete net;
 }
 
-int oakgpu_net_load_memory(oakgpu_ctx *ctx, const void *bytes, size_t size, oakgpu_net **out) {
+static int net_load_impl(oakgpu_ctx *ctx, const void *bytes, size_t size, bool discrete, oakgpu_net **out) {
   if (!ctx || !bytes || !out) return oakgpu_fail_msg("oakgpu_net_load_memory: null argument");
   const uint8_t *p = (const uint8_t *)bytes, *end = p + size;
   if (size < 8) return oakgpu_fail_msg("network file: truncated header");
   const int activation = (int)p[0] + 1; // search.cc:127-131: byte0 = activation - 1
+  if (discrete && activation != 2) return oakgpu_fail_msg("Agent: .discrete was specified but the parsed header does not encode clamped activations.");
   if (activation != 1 && activation != 2) return oakgpu_fail_msg("network file: unknown activation byte");
   p += 8;
   HostAffine L[12]; // p0 p1 a0 a1 fc0 fc1 v2 v3 q1a q1b q2a q2b
   for (int i = 0; i < 12; ++i)
     if (!read_affine(p, end, L[i])) return oakgpu_fail_msg("network file: truncated or malformed layer");
   if (p != end) return oakgpu_fail_msg("network file: trailing bytes (network.h:60-63)");
+  // the quantized main net (search.cc:104-122): shapes as visit_quantized_network checks them, then try_copy_parameters layer by
+  // layer in main-net.h:36-66's order; a NaN weight is refused there as "non clamped", before the non-finite check below
+  QLayer Q[8]; // fc0 fc1 value_fc2 value_fc3 p1_fc2 p2_fc2 p1_fc3 p2_fc3
+  if (discrete) {
+    const uint32_t qh = L[4].out, qvh = L[6].out, qph = L[8].out;
+    if (int rc = quant_shape_check(L[4].in, qh, qvh, qph)) return rc;
+    const struct { int layer; uint32_t in, out, rows; const char *name; } qs[8] = {
+        {4, 768, qh, qh, "main_net.fc0"}, {5, qh, qh, qh, "main_net.fc1"}, {6, qh, qvh, qvh, "main_net.value_fc2"}, {7, qvh, 1, 1, "main_net.value_fc3"},
+        {8, qh, qph, qph, "main_net.p1_policy_fc2"}, {10, qh, qph, qph, "main_net.p2_policy_fc2"},
+        {9, qph, 315, 320, "main_net.p1_policy_fc3"}, {11, qph, 315, 320, "main_net.p2_policy_fc3"}};
+    for (int i = 0; i < 8; ++i)
+      if (int rc = quantize_layer(L[qs[i].layer], qs[i].in, qs[i].out, qs[i].rows, qs[i].name, Q[i])) return rc;
+  }
   // Non-finite parameters are refused.  The reference would load them and propagate NaN / inf through every inference (its
   // value_inference asserts !isnan in debug builds, network.h:77); a file with such a parameter is a failed training run, and
   // here an infinite weight would also split into (inf, NaN, NaN) on the bf16 pipe -- a different wrong answer than fp32's.
@@ -2981,12 +3072,38 @@ int oakgpu_net_load_memory(oakgpu_ctx *ctx, const void *bytes, size_t size, oakg
       rc = rc ? rc : upload(net, policy_triple_order(q2a, H, PB), &D.q2a_t);
     }
   }
+  if (discrete && !rc) {
+    oak::QNetDev &q = net->q;
+    q.H = (int)fc0.out; q.VH = (int)v2.out; q.PH = (int)L[8].out;
+    const std::vector<uint8_t> img = qnet_image(Q[0], Q[1], Q[2], q.H, q.VH);
+    q.img_bytes = (int)img.size();
+    q.b3 = Q[3].b[0];
+    rc = rc ? rc : upload_raw(net, img, &q.img);
+    rc = rc ? rc : upload_raw(net, Q[0].b, &q.b0);
+    rc = rc ? rc : upload_raw(net, Q[1].b, &q.b1);
+    rc = rc ? rc : upload_raw(net, Q[2].b, &q.b2);
+    rc = rc ? rc : upload_raw(net, Q[3].w, &q.w3);
+    for (int hd = 0; hd < 2; ++hd) {
+      rc = rc ? rc : upload_raw(net, Q[4 + hd].w, &q.pw2[hd]);
+      rc = rc ? rc : upload_raw(net, Q[4 + hd].b, &q.pb2[hd]);
+      rc = rc ? rc : upload_raw(net, Q[6 + hd].w, &q.pw3[hd]);
+      rc = rc ? rc : upload_raw(net, Q[6 + hd].b, &q.pb3[hd]);
+    }
+    net->discrete = true;
+  }
   if (rc) { oakgpu_net_free(ctx, net); return rc; }
   *out = net;
   return 0;
 }
 
-int oakgpu_net_load(oakgpu_ctx *ctx, const char *path, oakgpu_net **out) {
+int oakgpu_net_load_memory(oakgpu_ctx *ctx, const void *bytes, size_t size, oakgpu_net **out) {
+  return net_load_impl(ctx, bytes, size, false, out);
+}
+int oakgpu_net_load_discrete_memory(oakgpu_ctx *ctx, const void *bytes, size_t size, oakgpu_net **out) {
+  return net_load_impl(ctx, bytes, size, true, out);
+}
+
+static int net_load_file(oakgpu_ctx *ctx, const char *path, bool discrete, oakgpu_net **out) {
   if (!path) return oakgpu_fail_msg("oakgpu_net_load: null path");
   FILE *f = fopen(path, "rb");
   if (!f) return oakgpu_fail_msg((std::string("Cannot open network file: ") + path).c_str());
@@ -2995,10 +3112,14 @@ int oakgpu_net_load(oakgpu_ctx *ctx, const char *path, oakgpu_net **out) {
   size_t r;
   while ((r = fread(tmp, 1, sizeof tmp, f)) > 0) buf.insert(buf.end(), tmp, tmp + r);
   fclose(f);
-  return oakgpu_net_load_memory(ctx, buf.data(), buf.size(), out);
+  return net_load_impl(ctx, buf.data(), buf.size(), discrete, out);
 }
+int oakgpu_net_load(oakgpu_ctx *ctx, const char *path, oakgpu_net **out) { return net_load_file(ctx, path, false, out); }
+int oakgpu_net_load_discrete(oakgpu_ctx *ctx, const char *path, oakgpu_net **out) { return net_load_file(ctx, path, true, out); }
+int oakgpu_net_is_discrete(const oakgpu_net *net) { return net && net->discrete ? 1 : 0; }
 
 int oakgpu_net_set_main_precision(oakgpu_net *net, int mode) {
+  if (net && net->discrete) { oakgpu_fail_msg("oakgpu_net_set_main_precision: the network is quantized (OAKGPU_MAIN_INT8)"); return -1; }
   if (!net || (mode != OAKGPU_MAIN_FP32 && mode != OAKGPU_MAIN_SPLIT && mode != OAKGPU_MAIN_PAIR)) { oakgpu_fail_msg("oakgpu_net_set_main_precision: bad argument"); return -1; }
   const int prev = net->main_mode;
   // (a request the network's weights do not allow is not honoured: fp16 pairs fall back to bf16 triples, those -- a main-net weight
@@ -3011,7 +3132,7 @@ int oakgpu_net_set_main_precision(oakgpu_net *net, int mode) {
 int oakgpu_net_main_precision(const oakgpu_net *net, int *split_allowed) {
   if (!net) { oakgpu_fail_msg("oakgpu_net_main_precision: null net"); return -1; }
   if (split_allowed) *split_allowed = net->split_safe ? 1 : 0;
-  return net->main_mode;
+  return net->discrete ? OAKGPU_MAIN_INT8 : net->main_mode;
 }
 
 int oakgpu_net_shape(const oakgpu_net *net, int *in_dim, int *hidden, int *value_hidden, int *policy_hidden) {
@@ -3051,6 +3172,10 @@ int oakgpu_leaf_set_lds_limits(void) { // per DEVICE (hipFuncSetAttribute applie
   OAK_POLICY_ATTR(1) OAK_POLICY_ATTR(2) OAK_POLICY_ATTR(4) OAK_POLICY_ATTR(8)
 #undef OAK_POLICY_ATTR
   if (e != hipSuccess) return oakgpu_fail_hip((int)e, "hipFuncSetAttribute(k_policy_rows)");
+  e = hipFuncSetAttribute((const void *)oak::k_mainnet_i8<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)oak::qi_lds_bytes(128, 128));
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void *)oak::k_mainnet_i8<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)oak::qi_lds_bytes(64, 64));
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void *)oak::k_mainnet_i8<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)oak::qi_lds_bytes(32, 32));
+  if (e != hipSuccess) return oakgpu_fail_hip((int)e, "hipFuncSetAttribute(k_mainnet_i8)");
   e = hipFuncSetAttribute((const void *)oak::k_mainnet_wave, hipFuncAttributeMaxDynamicSharedMemorySize, (int)oak::MW_BYTES);
   if (e != hipSuccess) return oakgpu_fail_hip((int)e, "hipFuncSetAttribute(k_mainnet_wave)");
   e = hipFuncSetAttribute((const void *)oak::k_mainnet_split<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)oak::MSplit<8>::LDS);
@@ -3088,7 +3213,8 @@ static EmbedRoute embed_route(oakgpu_ctx *ctx, const oakgpu_net *net) {
 }
 
 static int leaf_eval_impl(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battles, const uint8_t *durations, uint32_t n,
-                          float *values, float *embedding_out, const oak::PolicyArgs *pol, uint32_t *slot_tags = nullptr) {
+                          float *values, float *embedding_out, const oak::PolicyArgs *pol, uint32_t *slot_tags = nullptr,
+                          uint8_t *q_embedding = nullptr, int32_t *value_acc = nullptr) {
   if (!ctx || !net) return oakgpu_fail_msg("oakgpu_leaf_eval_dev: null ctx/net");
   if (n == 0) return 0;
   if (!battles || !durations || !values) return oakgpu_fail_msg("oakgpu_leaf_eval_dev: null required pointer");
@@ -3104,6 +3230,10 @@ static int leaf_eval_impl(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battl
   const EmbedRoute route = embed_route(ctx, net);
   hipEvent_t *tev = (hipEvent_t *)oakgpu_ctx_timing_events(ctx); // diagnostic only (oakgpu_set_kernel_timing)
   oak::EmbedTileArgs tp{D, battles, durations, n, emb, 0, nullptr, nullptr}, tact{D, battles, durations, n, emb, 1, nullptr, nullptr};
+  if (net->discrete) { // the quantized network's embeddings: party slots from the ReLU network's cache, actives with clamp (search.cc:104-135, cache.h)
+    tp.net.activation = 1;
+    tact.net.activation = 2;
+  }
   if (slot_tags && route.party) { // cached party-slot pass: tag comparison first, then only the changed slots (work list)
     uint8_t *ws = (uint8_t *)oakgpu_ctx_workspace(ctx, 2, (size_t)n * 10 * sizeof(oak::PartyWork) + 16);
     if (!ws) return -1;
@@ -3147,6 +3277,25 @@ static int leaf_eval_impl(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battl
     if (!h1) return -1;
   }
   if (tev) (void)hipEventRecord(tev[2], stream);
+  if (net->discrete) { // the quantized main net and policy heads (mainnet_i8.hpp)
+    const oak::QNetDev &Q = net->q;
+    oak::QMainArgs qa{Q, emb, n, values, pol ? (uint8_t *)h1 : nullptr, q_embedding, value_acc};
+    const uint32_t wgs = ((n + 31) / 32 + 3) / 4, cap = Q.H == 128 ? 256u : 512u, grid = wgs < cap ? wgs : cap;
+    const size_t lds = oak::qi_lds_bytes(Q.H, Q.VH);
+    if (Q.H == 128) hipLaunchKernelGGL(oak::k_mainnet_i8<128>, dim3(grid), dim3(oak::QI_BLOCK), lds, stream, qa);
+    else if (Q.H == 64) hipLaunchKernelGGL(oak::k_mainnet_i8<64>, dim3(grid), dim3(oak::QI_BLOCK), lds, stream, qa);
+    else hipLaunchKernelGGL(oak::k_mainnet_i8<32>, dim3(grid), dim3(oak::QI_BLOCK), lds, stream, qa);
+    if (tev) (void)hipEventRecord(tev[3], stream);
+    if (pol) {
+      oak::QPolicyArgs qp{Q, (const uint8_t *)h1, pol->battles, {pol->choices[0], pol->choices[1]}, {pol->counts[0], pol->counts[1]},
+                          {pol->logits[0], pol->logits[1]}, n};
+      const uint32_t pw = (n + 3) / 4, pgrid = pw < 1024 ? pw : 1024;
+      hipLaunchKernelGGL(oak::k_policy_i8, dim3(pgrid), dim3(oak::QI_BLOCK), 0, stream, qp);
+    }
+    hipError_t qe = hipGetLastError();
+    if (qe != hipSuccess) return oakgpu_fail_hip((int)qe, "leaf_eval launch (int8 main net)");
+    return 0;
+  }
   oak::MainArgs ma{D, emb, n, values, h1};
   {
     const uint32_t wgs = ((n + 31) / 32 + 3) / 4, grid = wgs < 256 ? wgs : 256;
@@ -3202,6 +3351,18 @@ int oakgpu_leaf_eval_cached_dev(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t 
                                 float *values, float *embedding, uint32_t *slot_tags) {
   if (!embedding || !slot_tags) return oakgpu_fail_msg("oakgpu_leaf_eval_cached_dev: the persistent embedding and tag buffers are required");
   return leaf_eval_impl(ctx, net, battles, durations, n, values, embedding, nullptr, slot_tags);
+}
+
+int oakgpu_leaf_eval_discrete_raw_dev(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battles, const uint8_t *durations, uint32_t n,
+                                      uint8_t *q_embedding, int32_t *value_acc) {
+  if (!ctx || !net) return oakgpu_fail_msg("oakgpu_leaf_eval_discrete_raw_dev: null ctx/net");
+  if (!net->discrete) return oakgpu_fail_msg("oakgpu_leaf_eval_discrete_raw_dev: the network is not quantized (oakgpu_net_load_discrete)");
+  if (!q_embedding || !value_acc) return oakgpu_fail_msg("oakgpu_leaf_eval_discrete_raw_dev: null output");
+  if (n == 0) return 0;
+  if (int rc = oakgpu_ctx_enter(ctx)) return rc;
+  float *values = (float *)oakgpu_ctx_workspace(ctx, 1, (size_t)n * 4);
+  if (!values) return -1;
+  return leaf_eval_impl(ctx, net, battles, durations, n, values, nullptr, nullptr, nullptr, q_embedding, value_acc);
 }
 
 int oakgpu_leaf_cache_last_count(oakgpu_ctx *ctx, uint32_t *slots_recomputed) { // diagnostic: synchronises the stream

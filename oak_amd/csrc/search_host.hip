@@ -1177,8 +1177,8 @@ int oakgpu_search(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battle, const
 
 // ---- RuntimeSearch::run (cpp/include/util/search.h:17-66, cpp/src/search.cc:150-313): the Agent's strings select budget,
 // bandit, evaluator and MatrixUCB at run time.  Same mini-languages and the same error texts as the reference, where it
-// throws std::runtime_error; what this build does not have (transposition-table heaps, the int8 "discrete" network) is
-// refused by name instead of being silently replaced.
+// throws std::runtime_error; what this build does not have (transposition-table heaps) is refused by name instead of being
+// silently replaced.  A `discrete` agent loads its network through oakgpu_net_load_discrete (the int8 main net).
 #include <map>
 #include <mutex>
 #include <string>
@@ -1197,7 +1197,7 @@ std::vector<std::string> split(const std::string &s, char sep) {
 bool to_float(const std::string &s, float &v) { char *e = nullptr; v = strtof(s.c_str(), &e); return e && e != s.c_str() && *e == 0; }
 bool to_u64(const std::string &s, uint64_t &v) { char *e = nullptr; v = strtoull(s.c_str(), &e, 10); return !s.empty() && e && *e == 0 && s[0] != '-'; }
 std::mutex g_net_mu;
-std::map<std::pair<int, std::string>, oakgpu_net *> g_nets; // Agent::network_ptr (search.cc:62-148), shared per (device, path)
+std::map<std::pair<int, std::pair<std::string, bool>>, oakgpu_net *> g_nets; // Agent::network_ptr (search.cc:62-148), shared per (device, path, discrete)
 } // namespace
 
 void oakgpu_set_thread_search_threads(int threads) { tl_search_threads = threads > 0 ? threads : 0; }
@@ -1313,7 +1313,6 @@ extern "C" int oakgpu_search_agent_heap(oakgpu_ctx *ctx, oakgpu_heap *heap, cons
     P.mucb_minimum = (uint32_t)minimum;
   }
   if (agent->table) return oakgpu_fail_msg("RuntimeSearch: transposition-table heaps (search/hash.h) are not built in this library");
-  if (agent->discrete) return oakgpu_fail_msg("RuntimeSearch: the int8 (discrete) network (nn/battle/quantized) is not built in this library; use the fp32 network");
   // descents in flight: the caller's choice, or a size that keeps the GPU busy without starving the tree of feedback
   if (batch) P.batch = batch;
   else if (P.duration_us) P.batch = 4096;
@@ -1321,11 +1320,11 @@ extern "C" int oakgpu_search_agent_heap(oakgpu_ctx *ctx, oakgpu_heap *heap, cons
   oakgpu_net *net = nullptr;
   if (P.eval == 1) { // Agent::initialize_network (search.cc:62-148): read once, keep
     std::lock_guard<std::mutex> lock(g_net_mu);
-    const auto key = std::make_pair(oakgpu_ctx_device(ctx), eval);
+    const auto key = std::make_pair(oakgpu_ctx_device(ctx), std::make_pair(eval, agent->discrete != 0));
     auto it = g_nets.find(key);
     if (it == g_nets.end()) {
       oakgpu_net *n = nullptr;
-      if (int rc = oakgpu_net_load(ctx, eval.c_str(), &n)) return rc;
+      if (int rc = agent->discrete ? oakgpu_net_load_discrete(ctx, eval.c_str(), &n) : oakgpu_net_load(ctx, eval.c_str(), &n)) return rc;
       it = g_nets.emplace(key, n).first;
     }
     net = it->second;

@@ -208,16 +208,20 @@ def mt19937_uniform_64(seed, count, skip=0):
 class Network:
     """Battle network on the GPU.  Mirrors NN::Battle::Network (nn/battle/network.h:22-176): constructed
     from a `.battle.net` parameter file; raises RuntimeError (OakGpuError) on an unreadable or malformed
-    file like the reference's loader (search.cc:62-148)."""
+    file like the reference's loader (search.cc:62-148).  discrete=True loads the quantized int8 main net
+    (Agent.discrete, nn/battle/quantized): a clamp-header file whose main net has the quantized shapes."""
 
-    def __init__(self, ctx, path=None, data=None):
+    def __init__(self, ctx, path=None, data=None, discrete=False):
         self.ctx = ctx
+        self.discrete = bool(discrete)
         h = C.c_void_p()
         if path is not None:
-            _lib.check(ctx.lib.oakgpu_net_load(ctx.handle, os.fsencode(path), C.byref(h)))
+            load = ctx.lib.oakgpu_net_load_discrete if discrete else ctx.lib.oakgpu_net_load
+            _lib.check(load(ctx.handle, os.fsencode(path), C.byref(h)))
         else:
             buf = (C.c_ubyte * len(data)).from_buffer_copy(data)
-            _lib.check(ctx.lib.oakgpu_net_load_memory(ctx.handle, buf, len(data), C.byref(h)))
+            load = ctx.lib.oakgpu_net_load_discrete_memory if discrete else ctx.lib.oakgpu_net_load_memory
+            _lib.check(load(ctx.handle, buf, len(data), C.byref(h)))
         self.handle = h
 
     def shape(self):
@@ -232,7 +236,7 @@ class Network:
         mode = self.ctx.lib.oakgpu_net_main_precision(self.handle, C.byref(allowed))
         if mode < 0:
             raise _lib.OakGpuError("oakgpu_net_main_precision failed")
-        return ("fp32", "split", "pair")[mode], bool(allowed.value)
+        return ("fp32", "split", "pair", "int8")[mode], bool(allowed.value)
 
     def set_main_precision(self, mode):
         """"pair" (default: fp32 values as scaled fp16 pairs on the fp16 matrix pipe, fp32 accumulation), "split" (bf16 triples) or
