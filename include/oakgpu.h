@@ -425,6 +425,40 @@ int oakgpu_frames_write(const uint8_t *battle /* 384 */, uint8_t result, const o
                         uint8_t *buffer, size_t capacity, size_t *written);
 int oakgpu_frames_read(const uint8_t *buffer, size_t size, uint8_t *battle /* 384, nullable */, uint8_t *result /* nullable */,
                        oakgpu_frame_update *updates /* nullable */, uint32_t capacity, uint32_t *count, size_t *consumed);
+
+/* ---- Replay check of `.battle.data` records (cpp/include/py/battle/frames.h:52-67, for a whole corpus at once): every game is
+ * replayed on the GPU from its stored battle (zero durations, default options) through its stored choices.  Per frame k, in
+ * this order, the first failing check ends the game: the engine's result is already terminal (EARLY_END); P1's, then P2's
+ * legal-choice count differs from m, n (COUNT); c1, then c2 is not among its player's legal choices (ILLEGAL, membership: the
+ * record does not fix the list's order); then update(c1, c2).  After the last frame: the engine's result differs from the stored
+ * result byte, a result that is not terminal included (RESULT), else OK.  A record damaged inside its own length (the ones
+ * oakgpu_frames_read refuses with "truncated update", "malformed update" or "frame count does not match the record") is
+ * MALFORMED and not replayed.  A game's report depends on its own record only.
+ *   report: frame = the frame index of the verdict (the frame count for OK and RESULT; 0 for MALFORMED); player = 1, 2 or 0;
+ * expected = the record's byte (m, n, c1 / c2, or the stored result for EARLY_END, RESULT and OK); got = the engine's byte: its
+ * legal-choice count for that player (COUNT, ILLEGAL), its result byte (EARLY_END, RESULT, OK).
+ *   battles / durations (nullable, n x 384 / n x 8): the state at the verdict -- before frame k's update for EARLY_END, COUNT and
+ * ILLEGAL, after the last update for OK and RESULT; zeros for MALFORMED. */
+typedef struct { uint32_t frame; uint8_t status, player, expected, got; } oakgpu_replay_report;
+enum { OAKGPU_REPLAY_OK = 0, OAKGPU_REPLAY_COUNT = 1, OAKGPU_REPLAY_ILLEGAL = 2, OAKGPU_REPLAY_EARLY_END = 3, OAKGPU_REPLAY_RESULT = 4,
+       OAKGPU_REPLAY_MALFORMED = 5 };
+/* host: record boundaries + oakgpu_frames_read's validation of every record.  Indexing stops at the first record whose length
+ * field cannot be trusted (a header cut short, a length below 391 bytes or past the buffer's end): *stopped_at = that byte offset
+ * (size when the whole buffer was indexed), *n_records = the records in front of it.  offsets / frames / malformed all NULL:
+ * count only; otherwise all three, with capacity >= *n_records. */
+int oakgpu_replay_index(const uint8_t *buffer, size_t size, uint64_t *offsets, uint16_t *frames, uint8_t *malformed,
+                        uint32_t capacity, uint32_t *n_records, size_t *stopped_at);
+/* device: records (the file bytes, unchanged) + their index (device arrays) -> one report per record (device), in the context's
+ * stream.  The frame counts are read back to order the games longest first (the call waits for the stream once, before the launch). */
+int oakgpu_replay_records_dev(oakgpu_ctx *ctx, const uint8_t *records, const uint64_t *offsets, const uint16_t *frames,
+                              const uint8_t *malformed, uint32_t n, oakgpu_replay_report *reports,
+                              uint8_t *battles /* n x 384, nullable */, uint8_t *durations /* n x 8, nullable */);
+/* host buffer in, host reports out: index, upload, replay, download.  Fails when the buffer holds more than `capacity` records. */
+int oakgpu_replay_records(oakgpu_ctx *ctx, const uint8_t *buffer, size_t size, oakgpu_replay_report *reports, uint32_t capacity,
+                          uint32_t *n_records, size_t *stopped_at, uint8_t *battles /* nullable */, uint8_t *durations /* nullable */);
+/* the compile-time engine switches this library was built with (DESIGN 0 order): MULTIHIT_ROLL_FIRST, PSYWAVE_SHOWDOWN,
+ * COUNTER_SHOWDOWN, ACCURACY_LAST.  The default build reports 1, 1, 0, 0. */
+int oakgpu_engine_switches(int out[4]);
 /* One self-play game, the per-game loop of the reference's data generator (cpp/src/generate.cc:238-322): PKMN::battle(teams,
  * battle_seed) + opening update, then per turn oakgpu_search -> RuntimePolicy::process_and_sample for both sides
  * (util/policy.h:22-106; mode words e / n / x / p with optional weights, e.g. "e0.9-x0.1"; p = prior + empirical, the

@@ -11,6 +11,7 @@
 //   OakGPU::solve_matrix       <- LRSNash::solve_fast as called at mcts.h:643-649 / pyoak.cc:394-426 (exact)
 //   OakGPU::SharedDeviceRollout<- benchmark.cc:23-31: n playouts from one root driven by ONE sequential std::mt19937
 //   OakGPU::Frames             <- Train::Battle::CompressedFrames (train/battle/compressed-frame.h:37-243)
+//   OakGPU::replay_check       <- the replay self-check of py/battle/frames.h:52-67, for a whole file at once
 //   OakGPU::Exchange           <- the path's one collective: per-root means on the device + RCCL all-gather (no reference analogue)
 // Errors surface as std::runtime_error, like the reference's loaders (cpp/src/search.cc:81-146).
 #pragma once
@@ -296,6 +297,30 @@ private:
   uint8_t battle_[OAKGPU_BATTLE_SIZE];
   std::vector<oakgpu_frame_update> updates_;
 };
+
+// The replay check of a `.battle.data` file's bytes on the GPU (oakgpu_replay_records; the rules are in oakgpu.h): one report per
+// record, its byte offset, where indexing stopped, and with want_states the battle and durations at each verdict.
+struct ReplayCheck {
+  std::vector<oakgpu_replay_report> reports;
+  std::vector<uint64_t> offsets;
+  size_t stopped_at = 0;
+  std::vector<uint8_t> battles, durations; // n x 384, n x 8 (want_states)
+};
+inline ReplayCheck replay_check(Context &ctx, const std::vector<uint8_t> &bytes, bool want_states = false) {
+  ReplayCheck out;
+  uint32_t n = 0;
+  check(oakgpu_replay_index(bytes.data(), bytes.size(), nullptr, nullptr, nullptr, 0, &n, &out.stopped_at));
+  if (n == 0) return out;
+  out.offsets.resize(n);
+  std::vector<uint16_t> frames(n);
+  std::vector<uint8_t> malformed(n);
+  check(oakgpu_replay_index(bytes.data(), bytes.size(), out.offsets.data(), frames.data(), malformed.data(), n, &n, nullptr));
+  out.reports.resize(n);
+  if (want_states) { out.battles.resize(size_t{n} * OAKGPU_BATTLE_SIZE); out.durations.resize(size_t{n} * 8); }
+  check(oakgpu_replay_records(ctx.get(), bytes.data(), bytes.size(), out.reports.data(), n, &n, &out.stopped_at,
+                              want_states ? out.battles.data() : nullptr, want_states ? out.durations.data() : nullptr));
+  return out;
+}
 
 // The path's one exchange step for root-parallel search sharded over the GPUs of a node (one process per GPU): reduce the
 // rank's leaf values to one mean per root on the device, then ONE ncclAllGather (RCCL over xGMI) of those means.

@@ -22,6 +22,7 @@ SYMBOLS = [
     "oakgpu_segment_mean_dev", "oakgpu_comm_unique_id", "oakgpu_comm_create", "oakgpu_comm_destroy", "oakgpu_all_gather_dev",
     "oakgpu_root_steps_create", "oakgpu_root_steps_destroy", "oakgpu_root_steps_launch_dev", "oakgpu_root_steps_capacity", "oakgpu_root_steps_reserve",
     "oakgpu_endless_battle_check", "oakgpu_frames_size", "oakgpu_frames_write", "oakgpu_frames_read", "oakgpu_selfplay_game", "oakgpu_selfplay_games", "oakgpu_poke_engine_eval_dev", "oakgpu_poke_engine_eval",
+    "oakgpu_replay_index", "oakgpu_replay_records_dev", "oakgpu_replay_records", "oakgpu_engine_switches",
 ]
 
 
@@ -151,6 +152,10 @@ def load():
     lib.oakgpu_frames_size.argtypes = [C.POINTER(FrameUpdate), u32]
     lib.oakgpu_frames_write.argtypes = [vp, C.c_uint8, C.POINTER(FrameUpdate), u32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.oakgpu_frames_read.argtypes = [vp, C.c_size_t, vp, C.POINTER(C.c_uint8), C.POINTER(FrameUpdate), u32, C.POINTER(u32), C.POINTER(C.c_size_t)]
+    lib.oakgpu_replay_index.argtypes = [vp, C.c_size_t, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(C.c_size_t)]
+    lib.oakgpu_replay_records_dev.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, vp]
+    lib.oakgpu_replay_records.argtypes = [vp, vp, C.c_size_t, vp, u32, C.POINTER(u32), C.POINTER(C.c_size_t), vp, vp]
+    lib.oakgpu_engine_switches.argtypes = [C.POINTER(C.c_int * 4)]
     lib.oakgpu_selfplay_game.argtypes = [vp, vp, vp, u64, C.POINTER(SelfplayParams), vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(u32),
                                          C.POINTER(C.c_uint8)]
     lib.oakgpu_selfplay_games.argtypes = [C.POINTER(vp), vp, vp, C.POINTER(u64), C.POINTER(SelfplayParams), u32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t),

@@ -14,6 +14,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <random>
 #include <mutex>
 #include <string>
@@ -1299,6 +1300,178 @@ __global__ __launch_bounds__(64, 2) void k_tree_step_staged(TreeStepArgs a) {
 #undef TS_PTR
 }
 
+// ---- Replay check of `.battle.data` records (oakgpu_replay_records_dev; the contract is in include/oakgpu.h) ------------------
+// A replay turn is a rollout turn-step whose choices are read from the record instead of drawn, so the kernel is the queue kernel's
+// shape on the register engine: persistent lanes, one game each, refilled from eight queue heads when their game ends, the queue
+// ordered longest game first by the host.  Records stay in their on-disk layout; a battle can start at any byte, so k_replay_gather
+// first copies every stored battle to a 16-byte aligned slot (the engine's dword loads and its immutable-data pointer `gin` read
+// it there) and derives the first request from it.
+struct ReplayArgs {
+  const uint8_t *records;   // the file bytes, unchanged
+  const uint64_t *offsets;  // n: byte offset of each record
+  const uint16_t *frames;   // n: frame count of each record
+  const uint32_t *order;    // n_live: queue position -> record (longest first; MALFORMED records are not queued)
+  const uint8_t *aligned;   // n x 384: the stored battles, aligned (k_replay_gather)
+  const uint8_t *first;     // n: the first request, PKMN::result(battle)
+  uint32_t *reports;        // n x 2 dwords (oakgpu_replay_report)
+  uint8_t *battles_out;     // nullable, n x 384
+  uint8_t *durations_out;   // nullable, n x 8
+  uint32_t *heads;          // QUEUE_HEADS counters, QUEUE_HEAD_STRIDE words apart (zeroed before every launch)
+  uint32_t n_live;
+};
+constexpr int REPLAY_COLD_BYTES = (sizeof(ReplayArgs) + 15) & ~15;
+constexpr int REPLAY_LDS_BYTES = 24 * 64 * 4 + TABLE_LDS_PAD + REPLAY_COLD_BYTES;
+
+__device__ __forceinline__ void replay_report(uint32_t *reports, uint32_t idx, uint32_t frame, uint32_t status, uint32_t player,
+                                              uint32_t expected, uint32_t got) {
+  *(uint2 *)(reports + 2 * (size_t)idx) = make_uint2(frame, status | (player << 8) | (expected << 16) | (got << 24)); // one 8-byte vector store
+}
+
+// One wave per record: the stored battle (byte-aligned in the record) -> its aligned slot, the first request; a MALFORMED record gets
+// its report here (and zero states), it is not replayed.
+__global__ __launch_bounds__(256) void k_replay_gather(ReplayArgs a, const uint8_t *malformed, uint32_t n) {
+  const uint32_t rec = blockIdx.x * 4 + (threadIdx.x >> 6), wl = threadIdx.x & 63;
+  if (rec >= n) return;
+  if (malformed[rec]) {
+    if (wl == 0) replay_report(a.reports, rec, 0, OAKGPU_REPLAY_MALFORMED, 0, 0, 0);
+    if (a.battles_out) for (uint32_t j = wl; j < 96; j += 64) ((uint32_t *)(a.battles_out + (size_t)rec * 384))[j] = 0;
+    if (a.durations_out && wl < 2) ((uint32_t *)(a.durations_out + (size_t)rec * 8))[wl] = 0;
+    return;
+  }
+  const uint8_t *src = a.records + a.offsets[rec] + 6; // u32 length, u16 frame count, then the battle
+  uint32_t *dst = (uint32_t *)(a.aligned + (size_t)rec * 384);
+  for (uint32_t j = wl; j < 96; j += 64)
+    dst[j] = (uint32_t)src[4 * j] | ((uint32_t)src[4 * j + 1] << 8) | ((uint32_t)src[4 * j + 2] << 16) | ((uint32_t)src[4 * j + 3] << 24);
+  if (wl == 0) { // PKMN::result(battle) (pkmn.h:235-272)
+    bool alive[2] = {false, false}, fainted[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+#pragma unroll
+      for (int i = 0; i < 6; ++i) alive[s] |= (src[184 * s + 24 * i + 18] | src[184 * s + 24 * i + 19]) != 0;
+      const uint32_t o = src[184 * s + 176], i = o ? (o <= 6 ? o - 1 : 5) : 0; // (order bytes outside 1..6 do not occur in a battle)
+      fainted[s] = (src[184 * s + 24 * i + 18] | src[184 * s + 24 * i + 19]) == 0;
+    }
+    uint32_t r;
+    if (!alive[0]) r = mk_result(alive[1] ? R_LOSE : R_TIE, 0, 0);
+    else if (!alive[1]) r = mk_result(R_WIN, 0, 0);
+    else if (fainted[0]) r = mk_result(0, C_SWITCH, fainted[1] ? C_SWITCH : C_PASS);
+    else if (fainted[1]) r = mk_result(0, C_PASS, C_SWITCH);
+    else r = mk_result(0, C_MOVE, C_MOVE);
+    ((uint8_t *)a.first)[rec] = (uint8_t)r;
+  }
+}
+
+__device__ __forceinline__ bool replay_member(uint32_t n, uint64_t lo, uint32_t hi, uint32_t c) { // c among the n choice bytes
+  bool in = false;
+#pragma unroll
+  for (uint32_t i = 0; i < OAKGPU_MAX_CHOICES; ++i) in |= i < n && (i < 8 ? (uint32_t)(lo >> (8 * i)) & 0xFF : hi) == c;
+  return in;
+}
+
+constexpr uint32_t REPLAY_NONE = 0xFFFFFFFFu, REPLAY_DONE = 0xFFFFFFFEu;
+template <int WPS>
+__global__ __launch_bounds__(64, WPS) void k_replay_records(ReplayArgs a_in) {
+  extern __shared__ __align__(16) uint8_t smem[];
+  lds_u32 *party = (lds_u32 *)smem;
+  using ER = EngineR<64, false>;
+  Tables T = stage_default_tables((lds_u8 *)smem + ER::PARTY_WORDS * 64 * 4);
+  // the pointers are parked in LDS and read back on the cold paths (refill, verdict): k_rollout_queue's reason -- as kernel arguments
+  // they would hold SGPRs the turn-step's exec masks need
+  lds_u32 *cold = (lds_u32 *)((lds_u8 *)smem + ER::PARTY_WORDS * 64 * 4 + TABLE_LDS_PAD);
+  if (threadIdx.x < sizeof(ReplayArgs) / 4) cold[threadIdx.x] = ((const uint32_t *)&a_in)[threadIdx.x];
+  __syncthreads();
+#define RA_PTR(field, type) cold_ptr_at<type>(cold, offsetof(ReplayArgs, field))
+  const uint32_t wl = threadIdx.x & 63;
+  const uint32_t n_live = (uint32_t)__builtin_amdgcn_readfirstlane((int)cold[offsetof(ReplayArgs, n_live) / 4]);
+  ER e;
+  e.m = party + threadIdx.x;
+  e.T = T;
+  uint32_t idx = REPLAY_NONE, r = 0, k = 0, nf = 0, mn = 0, c1 = 0, c2 = 0;
+  const uint8_t *fp = nullptr; // the next frame of this lane's record
+  // wave-uniform scalar state in one word: bits 8-10 the current queue head, 12-15 heads seen dry, 16-23 an iteration counter, bit 0 dry
+  uint32_t ust = (blockIdx.x & 7u) << 8;
+  for (;;) {
+    const bool need = idx == REPLAY_NONE;
+    const uint64_t mask = __ballot(need);
+    bool load = false;
+    ust = (ust & ~0xFF0000u) | ((ust + 0x10000u) & 0xFF0000u);
+    // refills in batches (k_rollout_queue's rule: every REFILL_EVERY-th iteration, or at once when REFILL_LANES lanes are free, or
+    // when no lane has a game) -- a refill is a returning atomic and dependent loads for the whole wave
+    if (mask && !(ust & 1u) && (((ust >> 16) & (REFILL_EVERY - 1)) == 0 || (uint32_t)__popcll(mask) >= REFILL_LANES || __ballot(idx < REPLAY_DONE) == 0)) {
+      uint64_t rem = mask;
+      uint32_t my = 0;
+      bool got = false;
+      for (;;) { // head s hands out the queue positions s, s + 8, s + 16, ... (k_rollout_queue)
+        const uint32_t shard = (ust >> 8) & 7u, need_n = (uint32_t)__popcll(rem);
+        const uint32_t lim = n_live > shard ? (n_live - shard + 7u) >> 3 : 0u;
+        uint32_t base = 0;
+        if (wl == 0) base = atomicAdd(RA_PTR(heads, uint32_t *) + shard * QUEUE_HEAD_STRIDE, need_n);
+        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+        const uint32_t avail = base < lim ? (lim - base < need_n ? lim - base : need_n) : 0u;
+        const uint32_t rank = (uint32_t)__popcll(rem & ((1ull << wl) - 1));
+        if (((rem >> wl) & 1) && rank < avail) { my = shard + ((base + rank) << 3); got = true; }
+        if (avail == need_n) break;
+        rem = __ballot(need && !got);
+        ust = (ust & ~(7u << 8)) | (((shard + 1u) & 7u) << 8);
+        ust += 1u << 12;
+        if (((ust >> 12) & 15u) >= 8u) { ust |= 1u; break; }
+      }
+      if (need) {
+        if (got) { idx = RA_PTR(order, const uint32_t *)[my]; load = true; }
+        else idx = REPLAY_DONE;
+      }
+    } else if (mask && (ust & 1u) && need) idx = REPLAY_DONE;
+    if (__ballot(load)) {
+      if (load) {
+        e.load_battle_global(RA_PTR(aligned, const uint8_t *) + (size_t)idx * 384, 0, 0); // zero durations (frames.h:57-59)
+        r = RA_PTR(first, const uint8_t *)[idx];
+        nf = RA_PTR(frames, const uint16_t *)[idx];
+        fp = RA_PTR(records, const uint8_t *) + RA_PTR(offsets, const uint64_t *)[idx] + 391;
+        k = 0;
+        if (nf) { mn = fp[0]; c1 = fp[1]; c2 = fp[2]; }
+      }
+    }
+    if (__ballot(idx != REPLAY_DONE) == 0) break;
+    if (idx < REPLAY_DONE) {
+      uint32_t status = 0xFF, player = 0, expected = 0, got = 0;
+      if (k == nf) { // after the last frame
+        expected = RA_PTR(records, const uint8_t *)[RA_PTR(offsets, const uint64_t *)[idx] + 390];
+        status = r == expected ? OAKGPU_REPLAY_OK : OAKGPU_REPLAY_RESULT;
+        got = r;
+      } else if (r & 15) {
+        expected = RA_PTR(records, const uint8_t *)[RA_PTR(offsets, const uint64_t *)[idx] + 390];
+        status = OAKGPU_REPLAY_EARLY_END;
+        got = r;
+      } else {
+        const uint32_t m = (mn & 15) + 1, n = (mn >> 4) + 1;
+        const auto l1 = e.choices(e.S, (r >> 4) & 3); // (normalised frame: S = P1, F = P2)
+        const auto l2 = e.choices(e.F, (r >> 6) & 3);
+        if (l1.n != m) { status = OAKGPU_REPLAY_COUNT; player = 1; expected = m; got = l1.n; }
+        else if (l2.n != n) { status = OAKGPU_REPLAY_COUNT; player = 2; expected = n; got = l2.n; }
+        else if (!replay_member(l1.n, l1.lo, l1.hi, c1)) { status = OAKGPU_REPLAY_ILLEGAL; player = 1; expected = c1; got = l1.n; }
+        else if (!replay_member(l2.n, l2.lo, l2.hi, c2)) { status = OAKGPU_REPLAY_ILLEGAL; player = 2; expected = c2; got = l2.n; }
+        else {
+          // the next frame's three bytes are loaded before this turn's update: the dependent load overlaps the turn-step
+          const uint32_t a1 = c1, a2 = c2;
+          fp += 11 + 4 * (m + n);
+          if (k + 1 < nf) { mn = fp[0]; c1 = fp[1]; c2 = fp[2]; }
+          r = e.update(a1, a2);
+          ++k;
+        }
+      }
+      if (status != 0xFF) { // the verdict: report, state at the verdict, lane free
+        replay_report(RA_PTR(reports, uint32_t *), idx, k, status, player, expected, got);
+        uint8_t *bout = RA_PTR(battles_out, uint8_t *);
+        if (bout) e.store_battle_global(bout + (size_t)idx * 384);
+        uint32_t *dout = RA_PTR(durations_out, uint32_t *);
+        if (dout) *(uint2 *)(dout + 2 * (size_t)idx) = make_uint2(e.S.dur, e.F.dur);
+        idx = REPLAY_NONE;
+      }
+    }
+  }
+#undef RA_PTR
+}
+
 // ---- PokeEngine::Eval (cpp/include/search/poke-engine-evaluate.h:9-204): the hand-written fp32 position score the
 // reference uses as its default data-generation evaluator.  One lane per battle, straight from the AoS bytes.
 __device__ __forceinline__ float pe_boost(uint32_t nib) { // get_boost_multiplier (:52-85) of a 4-bit two's-complement stage
@@ -1533,6 +1706,7 @@ struct oakgpu_ctx {
   int timing;               // oakgpu_set_kernel_timing
   hipEvent_t tev[4];
   bool tev_valid;
+  Block replay_ws{nullptr, 0};             // oakgpu_replay_records_dev: queue heads, queue order, first requests, aligned battles
   void *attachment = nullptr;              // oakgpu_internal.h: the tree search's cached batch slots
   void (*attachment_dtor)(void *) = nullptr;
 };
@@ -1725,6 +1899,7 @@ void oakgpu_destroy(oakgpu_ctx *c) {
   if (c->d_order) (void)hipFree(c->d_order);
   for (auto &b : c->stage) if (b.p) (void)hipFree(b.p);
   for (auto &b : c->ws) if (b.p) (void)hipFree(b.p);
+  if (c->replay_ws.p) (void)hipFree(c->replay_ws.p);
   if (c->tev_valid) for (auto &e : c->tev) (void)hipEventDestroy(e);
   if (c->h_table) {
     (void)hipHostFree(c->h_table);
@@ -2520,6 +2695,98 @@ int oakgpu_init_battles(oakgpu_ctx *c, const uint8_t *teams, const uint64_t *see
   DOWN(durations, d);
   DOWN(results, rs);
   HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---- replay check (include/oakgpu.h): the queue order is built on the host from the frame counts -- longest game first, so the
+// launch ends on short games instead of a lone 1,000-turn chain -- then k_replay_gather and the persistent k_replay_records.
+static int replay_launch(oakgpu_ctx *c, const uint8_t *records, const uint64_t *offsets, const uint16_t *frames, const uint8_t *malformed,
+                         const uint16_t *h_frames, const uint8_t *h_malformed, uint32_t n, oakgpu_replay_report *reports, uint8_t *battles,
+                         uint8_t *durations) {
+  std::vector<uint32_t> start(65537, 0), order;
+  for (uint32_t i = 0; i < n; ++i) if (!h_malformed[i]) ++start[65535 - h_frames[i] + 1]; // counting sort, frame counts descending
+  for (int b = 1; b <= 65536; ++b) start[b] += start[b - 1];
+  const uint32_t n_live = start[65536];
+  order.resize(n_live ? n_live : 1);
+  for (uint32_t i = 0; i < n; ++i) if (!h_malformed[i]) order[start[65535 - h_frames[i]]++] = i;
+  constexpr size_t HEADS_BYTES = oak::QUEUE_HEADS * oak::QUEUE_HEAD_STRIDE * 4;
+  const size_t order_bytes = ((size_t)n * 4 + 15) & ~(size_t)15, first_bytes = ((size_t)n + 15) & ~(size_t)15;
+  uint8_t *ws = (uint8_t *)grow_block(c, c->replay_ws, HEADS_BYTES + order_bytes + first_bytes + (size_t)n * 384);
+  if (!ws) return -1;
+  uint32_t *heads = (uint32_t *)ws, *d_order = (uint32_t *)(ws + HEADS_BYTES);
+  uint8_t *first = ws + HEADS_BYTES + order_bytes, *aligned = first + first_bytes;
+  HIPCHK(hipMemsetAsync(heads, 0, HEADS_BYTES, c->stream));
+  if (n_live) HIPCHK(hipMemcpyAsync(d_order, order.data(), (size_t)n_live * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream)); // (`order` is pageable host memory that dies with this call)
+  const oak::ReplayArgs a{records, offsets, frames, d_order, aligned, first, (uint32_t *)reports, battles, durations, heads, n_live};
+  hipLaunchKernelGGL(oak::k_replay_gather, dim3((n + 3) / 4), dim3(256), 0, c->stream, a, malformed, n);
+  if (n_live) {
+    const uint32_t resident = (uint32_t)c->n_cu * 4u * 4u; // four waves per SIMD, as k_rollout_queue<64, 4>
+    const uint32_t waves = std::min((n_live + 63) / 64, resident);
+    hipLaunchKernelGGL((oak::k_replay_records<4>), dim3(waves), dim3(64), oak::REPLAY_LDS_BYTES, c->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int oakgpu_replay_records_dev(oakgpu_ctx *c, const uint8_t *records, const uint64_t *offsets, const uint16_t *frames, const uint8_t *malformed,
+                              uint32_t n, oakgpu_replay_report *reports, uint8_t *battles, uint8_t *durations) {
+  if (!c) return bad("null ctx");
+  if (n == 0) return 0;
+  if (!records || !offsets || !frames || !malformed || !reports) return bad("oakgpu_replay_records_dev: null required pointer");
+  if (((uintptr_t)offsets & 7) || ((uintptr_t)frames & 1) || ((uintptr_t)reports & 7) || ((uintptr_t)battles & 15) || ((uintptr_t)durations & 7))
+    return bad("oakgpu_replay_records_dev: misaligned array (offsets, reports, durations: 8 bytes; frames: 2; battles: 16)");
+  HIPCHK(hipSetDevice(c->device));
+  std::vector<uint16_t> h_frames(n);
+  std::vector<uint8_t> h_malformed(n);
+  HIPCHK(hipMemcpyAsync(h_frames.data(), frames, (size_t)n * 2, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(h_malformed.data(), malformed, n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return replay_launch(c, records, offsets, frames, malformed, h_frames.data(), h_malformed.data(), n, reports, battles, durations);
+}
+
+int oakgpu_replay_records(oakgpu_ctx *c, const uint8_t *buffer, size_t size, oakgpu_replay_report *reports, uint32_t capacity,
+                          uint32_t *n_records, size_t *stopped_at, uint8_t *battles, uint8_t *durations) {
+  if (!c) return bad("null ctx");
+  if ((!buffer && size) || !n_records) return bad("oakgpu_replay_records: null argument");
+  uint32_t n = 0;
+  size_t stop = 0;
+  if (int rc = oakgpu_replay_index(buffer, size, nullptr, nullptr, nullptr, 0, &n, &stop)) return rc;
+  *n_records = n;
+  if (stopped_at) *stopped_at = stop;
+  if (n == 0) return 0;
+  if (!reports) return bad("oakgpu_replay_records: null reports");
+  if (n > capacity) return bad("oakgpu_replay_records: more records than the caller's capacity");
+  std::vector<uint64_t> offs(n);
+  std::vector<uint16_t> fr(n);
+  std::vector<uint8_t> mal(n);
+  if (int rc = oakgpu_replay_index(buffer, stop, offs.data(), fr.data(), mal.data(), n, &n, nullptr)) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  OakHostCall hc(c);
+  DevBuf rb, ob, fb, mb, rp, bb, db;
+  UP(rb, buffer, stop);
+  UP(ob, offs.data(), (size_t)n * 8);
+  UP(fb, fr.data(), (size_t)n * 2);
+  UP(mb, mal.data(), n);
+  UP(rp, (const void *)nullptr, (size_t)n * 8);
+  if (battles) UP(bb, (const void *)nullptr, (size_t)n * 384);
+  if (durations) UP(db, (const void *)nullptr, (size_t)n * 8);
+  if (int rc = replay_launch(c, (const uint8_t *)rb.p, (const uint64_t *)ob.p, (const uint16_t *)fb.p, (const uint8_t *)mb.p, fr.data(), mal.data(), n,
+                             (oakgpu_replay_report *)rp.p, (uint8_t *)bb.p, (uint8_t *)db.p))
+    return rc;
+  DOWN(reports, rp);
+  DOWN(battles, bb);
+  DOWN(durations, db);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int oakgpu_engine_switches(int out[4]) { // the unit's own compile-time switches (tools/engine_variants.sh builds this file with others)
+  if (!out) return bad("oakgpu_engine_switches: null argument");
+  out[0] = OAK_MULTIHIT_ROLL_FIRST;
+  out[1] = OAK_PSYWAVE_SHOWDOWN;
+  out[2] = OAK_COUNTER_SHOWDOWN;
+  out[3] = OAK_ACCURACY_LAST;
   return 0;
 }
 

@@ -1,10 +1,16 @@
 // oak_amd/csrc/oakgpu_internal.h -- shared between the translation units of liboakgpu.so.
 #pragma once
 #include <stddef.h>
+#include <stdint.h>
 struct oakgpu_ctx;
 int oakgpu_fail_hip(int hip_error, const char *what); // records hipGetErrorString, returns the code
 int oakgpu_fail_msg(const char *what);                 // records the message, returns -1
 int oakgpu_ctx_device(const oakgpu_ctx *ctx);
+// One `.battle.data` record at the head of a buffer (selfplay.hip): OAKGPU_RECORD_OK, _MALFORMED (damaged inside its own length; *total
+// is trustworthy) or _STOP (the length field is not).  *msg: oakgpu_frames_read's message.  _length checks the header only.
+enum { OAKGPU_RECORD_OK = 0, OAKGPU_RECORD_MALFORMED = 1, OAKGPU_RECORD_STOP = 2 };
+int oakgpu_record_scan(const uint8_t *buffer, size_t size, uint32_t *total, uint16_t *n_frames, const char **msg);
+int oakgpu_record_scan_length(const uint8_t *buffer, size_t size, uint32_t *total, uint16_t *n_frames, const char **msg);
 void *oakgpu_ctx_stream(const oakgpu_ctx *ctx);        // hipStream_t
 int oakgpu_ctx_enter(oakgpu_ctx *ctx);                 // hipSetDevice(ctx->device): first line of every entry point that launches or allocates
 // Per-context device workspaces (slot 0: battle embeddings, 1: policy activations, 2: party-slot work list): grow-only, one per context = one

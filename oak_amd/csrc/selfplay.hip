@@ -97,6 +97,34 @@ bool set_cant_hit_ghosts(const uint8_t *set) {
 
 } // namespace
 
+// The checks of CompressedFrames::read on one record at the head of `buffer` (shared by oakgpu_frames_read and oakgpu_replay_index, with
+// oakgpu_frames_read's messages).  OAKGPU_RECORD_STOP: the length field cannot be trusted -- a header cut short, or a length below
+// the fixed part or past the buffer's end -- so nothing behind this point can be found.  OAKGPU_RECORD_MALFORMED: the record is
+// damaged inside its own length (an m or n nibble above 8, an update past the record's end, a frame count that disagrees with the
+// header); *total is still where the next record starts.
+int oakgpu_record_scan_length(const uint8_t *buffer, size_t size, uint32_t *total, uint16_t *n_frames, const char **msg) {
+  if (size < 4 + 2 + 384 + 1) { *msg = "oakgpu_frames_read: truncated record"; return OAKGPU_RECORD_STOP; }
+  const uint8_t *p = buffer;
+  *total = get<uint32_t>(p);
+  *n_frames = get<uint16_t>(p);
+  if (*total > size || *total < 4 + 2 + 384 + 1) { *msg = "oakgpu_frames_read: record length out of range"; return OAKGPU_RECORD_STOP; }
+  return OAKGPU_RECORD_OK;
+}
+int oakgpu_record_scan(const uint8_t *buffer, size_t size, uint32_t *total, uint16_t *n_frames, const char **msg) {
+  if (const int kind = oakgpu_record_scan_length(buffer, size, total, n_frames, msg)) return kind;
+  const uint8_t *p = buffer + 4 + 2 + 384 + 1, *end = buffer + *total;
+  uint32_t n_read = 0;
+  while (p < end) {
+    if ((size_t)(end - p) < 3) { *msg = "oakgpu_frames_read: truncated update"; return OAKGPU_RECORD_MALFORMED; }
+    const uint32_t m = (*p & 15) + 1, n = (*p >> 4) + 1;
+    if (m > 9 || n > 9 || (size_t)(end - p) < update_bytes(m, n)) { *msg = "oakgpu_frames_read: malformed update"; return OAKGPU_RECORD_MALFORMED; }
+    p += update_bytes(m, n);
+    ++n_read;
+  }
+  if (n_read != *n_frames) { *msg = "oakgpu_frames_read: frame count does not match the record"; return OAKGPU_RECORD_MALFORMED; }
+  return OAKGPU_RECORD_OK;
+}
+
 extern "C" {
 
 // 1 when EVERY pairing of the two teams is Ghost against Ghost with no move on either side that can hit a Ghost -- the match-ups the
@@ -150,21 +178,21 @@ int oakgpu_frames_write(const uint8_t *battle, uint8_t result, const oakgpu_fram
 int oakgpu_frames_read(const uint8_t *buffer, size_t size, uint8_t *battle, uint8_t *result, oakgpu_frame_update *updates,
                        uint32_t capacity, uint32_t *count, size_t *consumed) {
   if (!buffer || !count) return oakgpu_fail_msg("oakgpu_frames_read: null argument");
-  if (size < 4 + 2 + 384 + 1) return oakgpu_fail_msg("oakgpu_frames_read: truncated record");
-  const uint8_t *p = buffer;
-  const uint32_t total = get<uint32_t>(p);
-  const uint16_t frames = get<uint16_t>(p);
-  if (total > size || total < 4 + 2 + 384 + 1) return oakgpu_fail_msg("oakgpu_frames_read: record length out of range");
+  uint32_t total = 0;
+  uint16_t frames = 0;
+  const char *msg = nullptr;
+  const int kind = oakgpu_record_scan(buffer, size, &total, &frames, &msg);
+  if (kind == OAKGPU_RECORD_STOP) return oakgpu_fail_msg(msg);
+  const uint8_t *p = buffer + 6;
   if (battle) memcpy(battle, p, 384);
   p += 384;
   if (result) *result = *p;
   ++p;
+  if (kind == OAKGPU_RECORD_MALFORMED) return oakgpu_fail_msg(msg);
   uint32_t n_read = 0;
-  while ((size_t)(p - buffer) < total) {      // CompressedFrames::read (:224-243)
-    if ((size_t)(buffer + total - p) < 3) return oakgpu_fail_msg("oakgpu_frames_read: truncated update");
+  while ((size_t)(p - buffer) < total) {      // CompressedFrames::read (:224-243); oakgpu_record_scan has checked every bound
     const uint8_t mn = *p;
     const uint32_t m = (mn & 15) + 1, n = (mn >> 4) + 1;
-    if (m > 9 || n > 9 || (size_t)(buffer + total - p) < update_bytes(m, n)) return oakgpu_fail_msg("oakgpu_frames_read: malformed update");
     ++p;
     oakgpu_frame_update u{};
     u.m = (uint8_t)m; u.n = (uint8_t)n;
@@ -179,10 +207,53 @@ int oakgpu_frames_read(const uint8_t *buffer, size_t size, uint8_t *battle, uint
     if (updates && n_read < capacity) updates[n_read] = u;
     ++n_read;
   }
-  if (n_read != frames) return oakgpu_fail_msg("oakgpu_frames_read: frame count does not match the record");
   if (updates && n_read > capacity) return oakgpu_fail_msg("oakgpu_frames_read: more frames than the caller's capacity");
   *count = n_read;
   if (consumed) *consumed = total;
+  return 0;
+}
+
+// Record boundaries + the per-frame validation of oakgpu_frames_read, for the replay check (oakgpu_replay_records).  Boundaries are
+// found in one sequential walk over the length fields (a record's length is where the next one starts); the records' own frames are
+// then checked on up to 16 host threads.
+int oakgpu_replay_index(const uint8_t *buffer, size_t size, uint64_t *offsets, uint16_t *frames, uint8_t *malformed, uint32_t capacity,
+                        uint32_t *n_records, size_t *stopped_at) {
+  if ((!buffer && size) || !n_records) return oakgpu_fail_msg("oakgpu_replay_index: null argument");
+  std::vector<uint64_t> offs;
+  size_t pos = 0;
+  while (pos < size) {
+    uint32_t total = 0;
+    uint16_t nf = 0;
+    const char *msg = nullptr;
+    if (oakgpu_record_scan_length(buffer + pos, size - pos, &total, &nf, &msg) != OAKGPU_RECORD_OK) break;
+    if (offs.size() == 0xFFFFFFFFu) break;
+    offs.push_back(pos);
+    pos += total;
+  }
+  *n_records = (uint32_t)offs.size();
+  if (stopped_at) *stopped_at = pos;
+  if (!offsets && !frames && !malformed) return 0; // counting call
+  if (!offsets || !frames || !malformed) return oakgpu_fail_msg("oakgpu_replay_index: offsets, frames and malformed go together");
+  if (offs.size() > capacity) return oakgpu_fail_msg("oakgpu_replay_index: more records than the caller's capacity");
+  const size_t n = offs.size();
+  auto scan = [&](size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; ++i) {
+      uint32_t total = 0;
+      uint16_t nf = 0;
+      const char *msg = nullptr;
+      const int kind = oakgpu_record_scan(buffer + offs[i], size - offs[i], &total, &nf, &msg);
+      offsets[i] = offs[i];
+      frames[i] = nf;
+      malformed[i] = kind == OAKGPU_RECORD_MALFORMED ? 1 : 0;
+    }
+  };
+  const unsigned hw = std::thread::hardware_concurrency();
+  const size_t threads = std::min<size_t>({(size_t)16, hw ? (size_t)hw : 1, n / 4096 + 1}); // (a GPU job's 16 CPUs at most)
+  if (threads <= 1) { scan(0, n); return 0; }
+  std::vector<std::thread> pool;
+  const size_t per = (n + threads - 1) / threads;
+  for (size_t t = 0; t < threads; ++t) pool.emplace_back(scan, std::min(n, t * per), std::min(n, (t + 1) * per));
+  for (auto &th : pool) th.join();
   return 0;
 }
 

@@ -111,3 +111,148 @@ def selfplay_games(ctxs, teams, battle_seeds, seeds, iterations=1 << 12, batch=1
     _lib.check(ctxs[0].lib.oakgpu_selfplay_games(cp, evaluator.handle if use_net else None, t.ctypes.data_as(C.c_void_p), bs, prms, n, int(threads_per_game),
                                                  out.ctypes.data_as(C.c_void_p), cap, written, frames, result))
     return [(out[g, :written[g]].tobytes(), int(frames[g]), int(result[g])) for g in range(n)]
+
+
+# ---- replay check of `.battle.data` records on the GPU (oakgpu_replay_records; the rules are in include/oakgpu.h) ----------------
+REPLAY_STATUS = ("OK", "COUNT", "ILLEGAL", "EARLY_END", "RESULT", "MALFORMED")
+REPORT_DTYPE = np.dtype([("status", np.uint8), ("player", np.uint8), ("frame", np.uint32), ("expected", np.uint8), ("got", np.uint8),
+                         ("offset", np.uint64)])
+_RAW_REPORT = np.dtype([("frame", "<u4"), ("status", "u1"), ("player", "u1"), ("expected", "u1"), ("got", "u1")])   # oakgpu_replay_report
+
+
+def replay_index(data):
+    """Record boundaries of a `.battle.data` byte string and oakgpu_frames_read's validation of each record.  Returns
+    {"offsets": uint64[n], "frames": uint16[n], "malformed": bool[n], "stopped_at": int}; indexing stops at the first record whose
+    length field cannot be trusted (stopped_at = len(data) when it does not)."""
+    lib = _lib.load()
+    buf = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, np.uint8)
+    n, stop = C.c_uint32(0), C.c_size_t(0)
+    p = buf.ctypes.data_as(C.c_void_p)
+    _lib.check(lib.oakgpu_replay_index(p, len(data), None, None, None, 0, C.byref(n), C.byref(stop)))
+    offs, fr, mal = np.zeros(max(n.value, 1), np.uint64), np.zeros(max(n.value, 1), np.uint16), np.zeros(max(n.value, 1), np.uint8)
+    if n.value:
+        _lib.check(lib.oakgpu_replay_index(p, len(data), offs.ctypes.data_as(C.c_void_p), fr.ctypes.data_as(C.c_void_p),
+                                           mal.ctypes.data_as(C.c_void_p), n.value, C.byref(n), None))
+    k = n.value
+    return {"offsets": offs[:k], "frames": fr[:k], "malformed": mal[:k].astype(bool), "stopped_at": int(stop.value)}
+
+
+def replay_check(ctx, data, want_states=False):
+    """Replay every record of a `.battle.data` byte string on the GPU through its stored choices.  Returns {"reports": structured
+    array (status, player, frame, expected, got, offset) per record, "stopped_at": int, "battles": uint8[n, 384] and "durations":
+    uint8[n, 8] at each verdict (want_states) or None}."""
+    lib = ctx.lib
+    idx = replay_index(data)
+    n = len(idx["offsets"])
+    reports = np.zeros(n, dtype=REPORT_DTYPE)
+    battles = np.zeros((n, 384), np.uint8) if want_states else None
+    durations = np.zeros((n, 8), np.uint8) if want_states else None
+    if n:
+        buf = np.frombuffer(data, dtype=np.uint8)
+        raw = np.zeros(n, dtype=_RAW_REPORT)
+        got, stop = C.c_uint32(0), C.c_size_t(0)
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        _lib.check(lib.oakgpu_replay_records(ctx.handle, vp(buf), len(data), vp(raw), n, C.byref(got), C.byref(stop), vp(battles), vp(durations)))
+        assert got.value == n and stop.value == idx["stopped_at"]
+        for f in ("status", "player", "frame", "expected", "got"):
+            reports[f] = raw[f]
+        reports["offset"] = idx["offsets"]
+    return {"reports": reports, "stopped_at": idx["stopped_at"], "battles": battles, "durations": durations}
+
+
+def engine_switches():
+    """The compile-time engine switches of the loaded library (DESIGN 0 order): MULTIHIT_ROLL_FIRST, PSYWAVE_SHOWDOWN, COUNTER_SHOWDOWN,
+    ACCURACY_LAST."""
+    lib = _lib.load()
+    out = (C.c_int * 4)()
+    _lib.check(lib.oakgpu_engine_switches(C.byref(out)))
+    return {"MULTIHIT_ROLL_FIRST": out[0], "PSYWAVE_SHOWDOWN": out[1], "COUNTER_SHOWDOWN": out[2], "ACCURACY_LAST": out[3]}
+
+
+def _whole_records(f, chunk_bytes):
+    """Yield (file offset, bytes) pieces of an open `.battle.data` file, each ending on a record boundary, of about chunk_bytes
+    (more when one record is longer), then (stop offset or None, b"")."""
+    import struct
+    f.seek(0, 2)
+    size = f.tell()
+    f.seek(0)
+    base, carry = 0, b""
+    while True:
+        fresh = f.read(max(chunk_bytes - len(carry), 1 << 16))
+        buf = carry + fresh
+        at_eof = f.tell() >= size
+        if not buf:
+            yield None, b""
+            return
+        idx = replay_index(buf)
+        s = idx["stopped_at"]
+        if s == len(buf):
+            yield base, buf
+            base, carry = base + s, b""
+            if at_eof:
+                yield None, b""
+                return
+            continue
+        # indexing stopped inside this piece: a chunk boundary (read on) or a record whose length cannot be trusted (stop)
+        rest, left = len(buf) - s, size - f.tell()
+        true_stop = at_eof
+        if not at_eof and rest >= 6:
+            total = struct.unpack_from("<I", buf, s)[0]
+            true_stop = total < 391 or total > rest + left
+        if s:
+            yield base, buf[:s]
+        if true_stop:
+            yield base + s, b""
+            return
+        base, carry = base + s, buf[s:]
+
+
+def replay_check_files(ctx, paths, chunk_bytes=64 << 20, want_states=False):
+    """Replay every record of many `.battle.data` files: small files are packed into one launch up to chunk_bytes, large ones read
+    in pieces that end on record boundaries (a record is never split between launches).  Returns {"reports": structured array with
+    a "file" field (index into paths) beside replay_check's fields, "offset" = byte offset in that file; "files": [{"path", "size",
+    "records", "stopped_at" (None when the whole file was indexed)}]; "battles" / "durations" as replay_check}."""
+    import os
+    dtype = np.dtype(REPORT_DTYPE.descr + [("file", np.uint32)])
+    out, states, files = [], [], []
+    pend, pend_map = [], []   # pieces waiting for a launch, (file, file offset, offset in the launch buffer)
+
+    def flush():
+        if not pend:
+            return
+        blob = b"".join(pend)
+        res = replay_check(ctx, blob, want_states)
+        rep = res["reports"]
+        starts = np.array([m[2] for m in pend_map], dtype=np.uint64)
+        seg = np.searchsorted(starts, rep["offset"], side="right") - 1
+        r = np.zeros(len(rep), dtype=dtype)
+        for name in REPORT_DTYPE.names:
+            r[name] = rep[name]
+        r["file"] = np.array([pend_map[s][0] for s in seg], dtype=np.uint32)
+        r["offset"] = rep["offset"] - starts[seg] + np.array([pend_map[s][1] for s in seg], dtype=np.uint64)
+        out.append(r)
+        if want_states:
+            states.append((res["battles"], res["durations"]))
+        pend.clear()
+        pend_map.clear()
+
+    for fi, path in enumerate(paths):
+        info = {"path": str(path), "size": os.path.getsize(path), "records": 0, "stopped_at": None}
+        with open(path, "rb") as f:
+            for off, piece in _whole_records(f, chunk_bytes):
+                if not piece:
+                    info["stopped_at"] = off
+                    continue
+                if pend and sum(len(p) for p in pend) + len(piece) > chunk_bytes:
+                    flush()
+                pend_map.append((fi, off, sum(len(p) for p in pend)))
+                pend.append(piece)
+                info["records"] += len(replay_index(piece)["offsets"])
+        files.append(info)
+    flush()
+    reports = np.concatenate(out) if out else np.zeros(0, dtype=dtype)
+    res = {"reports": reports, "files": files, "battles": None, "durations": None}
+    if want_states:
+        res["battles"] = np.concatenate([s[0] for s in states]) if states else np.zeros((0, 384), np.uint8)
+        res["durations"] = np.concatenate([s[1] for s in states]) if states else np.zeros((0, 8), np.uint8)
+    return res
