@@ -568,6 +568,16 @@ int oakgpu_net_set_main_precision(oakgpu_net *net, int mode);
  * on fp32 MFMA by (2).  Returns the mode in effect (-1: null net); *split_allowed
  * (nullable) = 0 for a network of case (2). */
 int oakgpu_net_main_precision(const oakgpu_net *net, int *split_allowed);
+/* The policy heads (oakgpu_leaf_eval_policy*) follow rule (2) with a check of their own: their fc2 multiplies as bf16 triples beside a
+ * main net on pairs or triples, and on fp32 MFMA beside a main net on fp32 MFMA -- or when ANY weight of the heads, fc2 or fc3, is
+ * above 2^20 in magnitude, whatever the main net's mode.  fc3 counts because it is the later layer of (2): fc2 x 2^-120 in front
+ * of fc3 x 2^+120 is the same function in fp32, but on the triples what fc2's low parts lose comes back multiplied up (measured
+ * with fc2 alone checked: logits 2.3e-4 off at 2^+-120, still 3.3e-7 at 2^+-110 -- the bf16 pipe keeps subnormal parts;
+ * tests/test_gpu_policy.py::test_compensated_heads).  Diagnostic: the form fc2 takes now (-1: null net). */
+#define OAKGPU_POLICY_FORM_FP32 0
+#define OAKGPU_POLICY_FORM_TRIPLE 1
+#define OAKGPU_POLICY_FORM_INT8 2 /* a network of oakgpu_net_load_discrete*: k_policy_i8 */
+int oakgpu_net_policy_form(const oakgpu_net *net);
 int oakgpu_leaf_eval_dev(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battles, const uint8_t *durations,
                          uint32_t n, float *values, float *embedding_out);
 int oakgpu_leaf_eval(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battles, const uint8_t *durations, uint32_t n,

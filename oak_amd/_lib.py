@@ -13,7 +13,7 @@ SYMBOLS = [
     "oakgpu_mt19937_fill", "oakgpu_rollout_draws_dev", "oakgpu_rollout_shared_device", "oakgpu_update_dev", "oakgpu_update",
     "oakgpu_choices_dev", "oakgpu_choices", "oakgpu_init_battles_dev", "oakgpu_init_battles",
     "oakgpu_set_ou_pools", "oakgpu_random_ou_battles_dev",
-    "oakgpu_net_load", "oakgpu_net_load_memory", "oakgpu_net_free", "oakgpu_net_shape", "oakgpu_net_set_main_precision", "oakgpu_net_main_precision",
+    "oakgpu_net_load", "oakgpu_net_load_memory", "oakgpu_net_free", "oakgpu_net_shape", "oakgpu_net_set_main_precision", "oakgpu_net_main_precision", "oakgpu_net_policy_form",
     "oakgpu_net_load_discrete", "oakgpu_net_load_discrete_memory", "oakgpu_net_is_discrete", "oakgpu_leaf_eval_discrete_raw_dev",
     "oakgpu_leaf_eval_dev", "oakgpu_leaf_eval", "oakgpu_leaf_eval_cached_dev", "oakgpu_leaf_cache_last_count", "oakgpu_leaf_embed_forms", "oakgpu_leaf_eval_policy_dev", "oakgpu_leaf_eval_policy",
     "oakgpu_heap_create", "oakgpu_heap_destroy", "oakgpu_heap_empty", "oakgpu_heap_clear", "oakgpu_heap_kind", "oakgpu_heap_nodes", "oakgpu_heap_update",
@@ -181,6 +181,7 @@ def load():
     lib.oakgpu_net_shape.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.oakgpu_net_set_main_precision.argtypes = [vp, C.c_int]
     lib.oakgpu_net_main_precision.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.oakgpu_net_policy_form.argtypes = [vp]
     lib.oakgpu_net_load_discrete.argtypes = [vp, C.c_char_p, C.POINTER(vp)]
     lib.oakgpu_net_load_discrete_memory.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp)]
     lib.oakgpu_net_is_discrete.argtypes = [vp]

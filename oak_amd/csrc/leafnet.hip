@@ -3063,10 +3063,12 @@ static int net_load_impl(oakgpu_ctx *ctx, const void *bytes, size_t size, bool d
       rc = rc ? rc : upload(net, policy_rows_image(q1b, PH), &D.q1b_img);
       rc = rc ? rc : upload(net, policy_rows_image(q2b, PH), &D.q2b_img);
     }
-    // the triples only while no fc2 weight is above 2^20 in magnitude (as for the main net: split_safe)
+    // the triples only while no weight of the heads is above 2^20 in magnitude (as for the main net: split_safe).  fc3 counts too:
+    // it is the later layer that multiplies back up what a flushed low part lost in fc2 (fc2 x 2^-120 in front of fc3 x 2^+120 is
+    // the same function in fp32; on the triples the logits were 2.3e-4 off -- tests/test_gpu_policy.py, down120_up120)
     bool psafe = true;
-    for (float v : q1a.w) psafe = psafe && std::fabs(v) <= 1048576.0f;
-    for (float v : q2a.w) psafe = psafe && std::fabs(v) <= 1048576.0f;
+    for (const HostAffine *a : {&q1a, &q2a, &q1b, &q2b})
+      for (float v : a->w) psafe = psafe && std::fabs(v) <= 0x1p20f;
     if (psafe) {
       rc = rc ? rc : upload(net, policy_triple_order(q1a, H, PB), &D.q1a_t);
       rc = rc ? rc : upload(net, policy_triple_order(q2a, H, PB), &D.q2a_t);
@@ -3133,6 +3135,16 @@ int oakgpu_net_main_precision(const oakgpu_net *net, int *split_allowed) {
   if (!net) { oakgpu_fail_msg("oakgpu_net_main_precision: null net"); return -1; }
   if (split_allowed) *split_allowed = net->split_safe ? 1 : 0;
   return net->discrete ? OAKGPU_MAIN_INT8 : net->main_mode;
+}
+
+// fc2 of the heads as bf16 triples when the main net runs on the bf16 / fp16 pipe and no weight of the heads forbids it (q1a_t), else on fp32 MFMA
+static bool policy_triple(const oakgpu_net *net) {
+  return net->main_mode != OAKGPU_MAIN_FP32 && net->dev.q1a_t != nullptr && net->dev.q2a_t != nullptr;
+}
+
+int oakgpu_net_policy_form(const oakgpu_net *net) {
+  if (!net) { oakgpu_fail_msg("oakgpu_net_policy_form: null net"); return -1; }
+  return net->discrete ? OAKGPU_POLICY_FORM_INT8 : policy_triple(net) ? OAKGPU_POLICY_FORM_TRIPLE : OAKGPU_POLICY_FORM_FP32;
 }
 
 int oakgpu_net_shape(const oakgpu_net *net, int *in_dim, int *hidden, int *value_hidden, int *policy_hidden) {
@@ -3316,8 +3328,7 @@ static int leaf_eval_impl(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battl
     pa.h1 = h1;
     const uint32_t ptiles = (n + 31) / 32;
     auto pgrid = [&](uint32_t waves) { const uint32_t wgs = (ptiles + waves - 1) / waves; return dim3(wgs < 256 ? wgs : 256); };
-    // fc2 as bf16 triples when the main net runs that way and no fc2 weight forbids it (q1a_t), else on fp32 MFMA
-    const bool triple = net->main_mode != OAKGPU_MAIN_FP32 && D.q1a_t != nullptr && D.q2a_t != nullptr; // (the heads stay on bf16 triples beside a main net on fp16 pairs)
+    const bool triple = policy_triple(net); // (the heads stay on bf16 triples beside a main net on fp16 pairs)
 #define OAK_POLICY_LAUNCH(PBV)                                                                                                                            \
   do {                                                                                                                                                    \
     if (triple) hipLaunchKernelGGL((oak::k_policy_rows<PBV, true>), pgrid(oak::PolicyRows<PBV>::WAVES), dim3(oak::PolicyRows<PBV>::BLOCK), oak::PolicyRows<PBV>::LDS, stream, pa);  \

@@ -238,6 +238,13 @@ class Network:
             raise _lib.OakGpuError("oakgpu_net_main_precision failed")
         return ("fp32", "split", "pair", "int8")[mode], bool(allowed.value)
 
+    def policy_form(self):
+        """How the policy heads' fc2 multiplies now: "triple" (bf16 triples), "fp32" (fp32 MFMA) or "int8": oakgpu_net_policy_form."""
+        form = self.ctx.lib.oakgpu_net_policy_form(self.handle)
+        if form < 0:
+            raise _lib.OakGpuError("oakgpu_net_policy_form failed")
+        return ("fp32", "triple", "int8")[form]
+
     def set_main_precision(self, mode):
         """"pair" (default: fp32 values as scaled fp16 pairs on the fp16 matrix pipe, fp32 accumulation), "split" (bf16 triples) or
         "fp32" (fp32 MFMA); include/oakgpu.h: oakgpu_net_set_main_precision.  Returns the previous mode."""
