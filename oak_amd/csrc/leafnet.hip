@@ -4,7 +4,9 @@
 //   K2  k_embed_both (k_embed_prows + k_embed_arows; k_embed_lds for embedding widths those do not take):
 //                   Encode::Battle::{Pokemon,ActivePokemon}::write (encode/battle/battle.h:208-214, 544-551) fused with
 //                   EmbeddingNet::propagate (nn/ffn.h:47-51, affine.h:87-103) and write_battle_embedding
-//                   (network.h:131-175): first-layer weights resident in LDS, dense parts on fp32 MFMA.  The reference's
+//                   (network.h:131-175): first-layer weights resident in LDS.  Row kernels: one-hot / move rows added in fp32, the
+//                   first layer's dense part as bf16 triples, the second layer as scaled fp16 pairs (fp32 accumulation, fp32
+//                   results); k_embed_lds: both layers on fp32 MFMA.  The reference's
 //                   per-battle embedding cache (nn/battle/cache.h) is oakgpu_leaf_eval_cached_dev (k_party_tags).
 //   K3  k_mainnet_wave : MainNet::propagate value path (nn/battle/main-net.h:57-64) + sigmoid, the three dense layers on
 //                   v_mfma_f32_32x32x2_f32 (exact fp32); k_policy: the policy heads (main-net.h:67-107).
@@ -852,7 +854,7 @@ constexpr int AR_WAVE_WORDS = ER_ITEMS * AR_ITEM_WORDS;
 constexpr int AR_WAVES = OAK_EMBED_WAVES, AR_BLOCK = 64 * AR_WAVES;
 constexpr int AR_DENSE_WORDS = AR_KT * 4 * 3 * 64 * 2; // the dense weights' triples: [k-step][channel block][h m l][lane] x 8 B (dense_layer_bf16)
 constexpr int AR_COMBINED = 428; // first precombined (active + stored) move row of a_w0d: behind W0^T's 427 rows and the zero row
-constexpr int AR_MAX_NBO = 3; // W1 as bf16 triples: 24 KB per 32-wide output block; four blocks (outputs above 96) do not fit beside the rest
+constexpr int AR_MAX_NBO = 3; // W1's image (scaled fp16 pairs in the 3 x 1 KB per k-step the bf16 triples had: embed_pair_order): 24 KB per 32-wide output block; four blocks (outputs above 96) do not fit beside the rest
 constexpr size_t ar_bytes(int nbo) { return (size_t)((AR_SPARSE + 1) * ER_RS + AR_DENSE_WORDS + AR_WAVES * AR_WAVE_WORDS + 64 * nbo) * 4 + (size_t)nbo * E2_BLOCK_BYTES; }
 // channel held by register s (0..63) of a lane in half hh: the C layout of four 32x32 MFMA blocks, block b's row i being
 // channel 4 i + b (so that a lane's float4 of a weight row feeds the four blocks)
@@ -872,7 +874,7 @@ __device__ __forceinline__ void embed_arows_body(const EmbedTileArgs &a, float *
   const int out_dim = N.a_out;
   float *W0s = lds_f;                                   // sparse rows, channels in natural order, + a zero row
   float *Wd = W0s + (AR_SPARSE + 1) * ER_RS;            // dense fragment: [k-step][channel block][lane]
-  const uint8_t *W1t = (const uint8_t *)(Wd + AR_DENSE_WORDS); // the second layer's bf16 triples: [block][k-step][h m l][lane] x 16 B
+  const uint8_t *W1t = (const uint8_t *)(Wd + AR_DENSE_WORDS); // the second layer's scaled fp16 pairs: [block][k-step][h l (unused)][lane] x 16 B
   const float *b1s = (const float *)(W1t + NBO * E2_BLOCK_BYTES);
   constexpr int img_words = ar_img_words(NBO);
   stage_image_dma<BLOCK>(lds_f, N.a_img, img_words);
@@ -1070,7 +1072,7 @@ __device__ __forceinline__ void embed_arows_body(const EmbedTileArgs &a, float *
     __builtin_amdgcn_sched_barrier(0);
     EL_MARK(4);
     if (next < nmt) encode_load2(next); // (the slot byte of LOAD 1 arrived during the first layer)
-    // ---- second layer on the bf16 pipe (embed_layer2): W1's triples from LDS ----
+    // ---- second layer on the fp16 pipe (embed_layer2): W1's scaled pairs from LDS ----
     // wave priority: second layer 3 > first layer 2 > encode / scatter 0 -- whoever can feed the matrix pipe issues first
     __builtin_amdgcn_s_setprio(3);
     f32x16 acc[NBO];
@@ -1112,8 +1114,8 @@ __global__ __launch_bounds__(AR_BLOCK) void k_embed_arows(EmbedTileArgs a) {
 // types; 193 possible rows, all LDS-resident in natural channel order): in k-step t the half-wave hh sums the 7 rows of
 // item 2t + hh, a whole 512-byte row per ds_read_b128 and so free of the bank conflicts of k_embed_rows (every lane another
 // row at the same column), and selector MFMAs transpose the sums into the item lanes.  Second layer (<= 2 output
-// blocks) with W1's bf16 triples from LDS.  The input is read straight from global memory (the encode of a Pokemon is 12
-// features; no staging).  LDS: 194 x 512 B rows + 3 KB dense fragment + 48 KB W1 triples + bias + 512 B per wave.
+// blocks) with W1's scaled fp16 pairs from LDS (embed_layer2).  The input is read straight from global memory (the encode of a
+// Pokemon is 12 features; no staging).  LDS: 194 x 512 B rows + 3 KB dense fragment + 48 KB W1 image + bias + 512 B per wave.
 constexpr int PR_SPARSE = 193, PR_ZERO = 193, PR_KT = 1, PR_HOT = 7; // (6 dense features: one k-step of eight)
 constexpr int PR_ITEM_WORDS = 8;                 // 7 LDS byte offsets of the item's one-hot rows, ready to use (+ 1 pad: two 16-byte reads)
 constexpr int PR_WAVE_WORDS = ER_ITEMS * PR_ITEM_WORDS;
@@ -1133,7 +1135,7 @@ __device__ __forceinline__ void embed_prows_body(const EmbedTileArgs &a, float *
   if (bid >= nmt) return; // (a very short work list: no weights staged for nothing)
   float *W0s = lds_f;                                   // rows 5..197 of W0^T, channels in natural order, + a zero row
   float *Wd = W0s + (PR_SPARSE + 1) * ER_RS;            // dense fragment
-  const uint8_t *W1t = (const uint8_t *)(Wd + PR_DENSE_WORDS); // second layer's bf16 triples: [block][k-step][h m l][lane] x 16 B
+  const uint8_t *W1t = (const uint8_t *)(Wd + PR_DENSE_WORDS); // second layer's scaled fp16 pairs: [block][k-step][h l (unused)][lane] x 16 B
   const float *b1s = (const float *)(W1t + NBO * E2_BLOCK_BYTES);
   constexpr int img_words = pr_img_words(NBO);
   stage_image_dma<PR_BLOCK>(lds_f, N.p_img, img_words);
@@ -1287,7 +1289,7 @@ __device__ __forceinline__ void embed_prows_body(const EmbedTileArgs &a, float *
     EL_MARK(4);
     const uint32_t next = mt + stride;
     if (next < nmt) encode_load(next); // the next mini-tile's raw input: asked for now, looked at after the second layer
-    // ---- second layer on the bf16 pipe (embed_layer2) ----
+    // ---- second layer on the fp16 pipe (embed_layer2: scaled fp16 pairs) ----
     // wave priority: second layer 3 > first layer 2 > encode / scatter 0 -- whoever can feed the matrix pipe issues first
     __builtin_amdgcn_s_setprio(3);
     f32x16 acc[NBO];
@@ -2457,7 +2459,7 @@ struct oakgpu_net {
   int main_mode;     // which kernel runs the main net: 0 = k_mainnet_wave (fp32 MFMA), 1 = k_mainnet_split (bf16 triples), 2 = k_mainnet_pair (fp16 pairs)
   bool pair_safe;    // every main-net layer passes pair_layer_ok (rows keep fp32 accuracy as scaled fp16 pairs, no dwarfed column): k_mainnet_pair may run
   bool split_safe;   // no main-net weight above 2^20 in magnitude: what a flushed low bf16 part loses cannot be amplified back (else fp32 MFMA only)
-  bool embed_safe;   // ... and none in the embedding nets' second layers either: the embedding passes' triples are safe (else k_embed_lds: fp32 MFMA)
+  bool embed_safe;   // ... and none in the embedding nets' second layers either, which also pass pair_layer_ok: the row kernels' bf16 triples (first layer's dense part) and scaled fp16 pairs (second layer) are safe (else k_embed_lds: fp32 MFMA)
 };
 
 namespace {
@@ -3024,7 +3026,8 @@ static int net_load_impl(oakgpu_ctx *ctx, const void *bytes, size_t size, bool d
     for (const HostAffine *a : {&fc0, &fc1, &v2})
       for (float v : a->w) safe = safe && std::fabs(v) <= 0x1p20f;
     net->split_safe = safe;
-    // The embedding passes (k_embed_prows / k_embed_arows) multiply as bf16 triples too (round 4).  What a flushed part loses there is
+    // The row kernels of the embedding passes (k_embed_prows / k_embed_arows) multiply the dense part of their first layer as bf16
+    // triples (the one-hot and move rows are added in fp32; the second layer: scaled fp16 pairs, below).  What a flushed part loses there is
     // amplified by whatever comes BEHIND it -- the embedding nets' own second layers (L[1], L[3]) and the main net -- so a network
     // with a weight above 2^20 in any of those runs its embedding nets through k_embed_lds (fp32 MFMA), whatever the main net's mode
     // (round-4 advice: a layer scaled by 2^-110 in front of one scaled by 2^+110 is the same function in fp32).
@@ -3209,12 +3212,12 @@ struct EmbedRoute { int party, actives; };
 static EmbedRoute embed_route(oakgpu_ctx *ctx, const oakgpu_net *net) {
   const oak::NetDev &D = net->dev;
   // The row kernels (k_embed_prows / k_embed_arows) take embedding nets up to 128 hidden channels, party outputs up to 64
-  // and active outputs up to 128; anything wider goes to k_embed_lds (the 64-item tile form).  OAKGPU_EMBED_TILE=1 forces
+  // and active outputs up to 96 (AR_MAX_NBO blocks); anything wider goes to k_embed_lds (the 64-item tile form).  OAKGPU_EMBED_TILE=1 forces
   // the tile form (A/B and a second implementation for the tests).
   static const bool force_tile = getenv("OAKGPU_EMBED_TILE") != nullptr;
   static const int kinds = getenv("OAKGPU_EMBED_KINDS") ? atoi(getenv("OAKGPU_EMBED_KINDS")) : 3; // diagnostics: 1 party, 2 actives
   static const bool split = getenv("OAKGPU_EMBED_SPLIT") != nullptr; // A/B: the two passes as two launches
-  const bool rows = !force_tile && net->embed_safe; // (the row kernels multiply as bf16 triples: see embed_safe)
+  const bool rows = !force_tile && net->embed_safe; // (the row kernels multiply as bf16 triples and scaled fp16 pairs: see embed_safe)
   const bool prow_ok = rows && D.p_hidden <= 128 && D.p_out <= 64, arow_ok = rows && D.a_hidden <= 128 && D.a_out <= 32 * oak::AR_MAX_NBO;
   // default: both embedding passes in one launch (k_embed_both).  Not while the per-kernel timing diagnostic is on (it
   // wants an event between the passes).
