@@ -456,6 +456,69 @@ int oakgpu_replay_records_dev(oakgpu_ctx *ctx, const uint8_t *records, const uin
 /* host buffer in, host reports out: index, upload, replay, download.  Fails when the buffer holds more than `capacity` records. */
 int oakgpu_replay_records(oakgpu_ctx *ctx, const uint8_t *buffer, size_t size, oakgpu_replay_report *reports, uint32_t capacity,
                           uint32_t *n_records, size_t *stopped_at, uint8_t *battles /* nullable */, uint8_t *durations /* nullable */);
+/* ---- Training batches from `.battle.data` records (the reference's loader: pyoak.sample + EncodedBattleFrames, cpp/src/pyoak.cc:111-245,
+ * py/battle/encoded-frames.h, py/battle/target.h -- there on CPU threads, one file open and one replay per sample).
+ * A corpus is a buffer of records uploaded once, indexed by oakgpu_replay_index's rules (records behind `stopped_at` are not part of
+ * it) with every stored battle copied to an aligned slot.  A PICK is (record r, frame f); its row holds what EncodedFrames::write and
+ * Target::write produce for the state reached from the record's stored battle by update() through the stored choices of frames
+ * 0 .. f-1 (zero durations at the start, no damage-roll clamp: the replay check's walk):
+ *   pokemon [n,2,6,198] f32  slot 0: the DENSE Encode::Battle::Pokemon::write of the active's stored Pokemon with duration.sleep(0);
+ *                            slots 1..5: the Pokemon at order[slot] with duration.sleep(slot); all zero when order[slot] == 0 or hp == 0
+ *   active  [n,2,1,229] f32  the DENSE Encode::Battle::Active::write(side.active, duration); all zero when the active's stored hp is 0
+ *   hp      [n,2,6,1]   f32  (float)hp / (float)stats.hp, 0 for the dead and empty slots above
+ *   choice_indices [n,2,9] i64  Policy::get_index of the engine's legal choices for the state's request, in the engine's order, for
+ *                            i < k; 315 (Policy::n_dim) in every other cell
+ *   k, choice [n,2,1] u8     the frame's m, n and c1, c2;  iterations [n,1] u32
+ *   empirical_policies, nash_policies [n,2,9] f32   (float)u16 / 65535.0f for the first k entries, 0 behind them
+ *   empirical_value, nash_value [n,1] f32 likewise;  score [n,1] f32: WIN 1, LOSE 0, TIE 0.5 of the stored result
+ *   status [n] u8, where [n] u32   below
+ * The dense encoders are not the leaf evaluator's sparse ones: a move cell is ASSIGNED bool(pp) slot by slot, so a move held in two
+ * slots shows its last slot's value (the sparse form adds 1 per slot with PP); the disabled move's cell is left as it is (the
+ * reference's zero lands behind the move block, where the duration writer or the next row overwrites it); equal types give one 1.
+ * Every quotient is a correctly rounded fp32 division: rows are bit for bit the reference's.
+ *   A pick is OK when r names a record that is not MALFORMED (else MALFORMED, where = 0) and f < frames[r] (else OAKGPU_PICK_RANGE,
+ * as for r past the last record; where = f), the stored result byte's type is 1..3 (else RESULT, where = frames[r]: there is no
+ * score), and on every frame 0 .. f the replay check's per-frame checks hold in its order: the game has not ended (EARLY_END), both
+ * legal-choice counts equal m, n (COUNT), both stored choices are legal (ILLEGAL); where = the failing frame, and f itself for an OK pick.  The game's FINAL
+ * result is not re-derived for a pick -- a record whose last update ends elsewhere than its result byte says still yields OK picks;
+ * that check is oakgpu_replay_records'.  Every cell of rows 0 .. n-1 of every tensor is written by the call (all zero for a pick
+ * that is not OK, status and where excepted), nothing outside them is touched, and row i depends on pick i alone. */
+enum { OAKGPU_PICK_RANGE = 6 };
+typedef struct oakgpu_corpus oakgpu_corpus;
+typedef struct {
+  float *pokemon, *active, *hp;   /* pokemon: 16-byte aligned; active, hp: 8 */
+  int64_t *choice_indices;
+  uint8_t *k, *choice;
+  uint32_t *iterations;
+  float *empirical_policies, *nash_policies, *empirical_value, *nash_value, *score;
+  uint8_t *status;
+  uint32_t *where;
+} oakgpu_encoded_frames;
+typedef struct { uint32_t records, malformed; uint64_t frames /* of the records that are not malformed */; size_t stopped_at; } oakgpu_corpus_stats;
+/* buffer: host bytes (copied; the caller's buffer is free when the call returns).  The corpus belongs to ctx and must be destroyed
+ * before it. */
+int oakgpu_corpus_create(oakgpu_ctx *ctx, const uint8_t *buffer, size_t size, oakgpu_corpus **out);
+void oakgpu_corpus_destroy(oakgpu_corpus *corpus);
+int oakgpu_corpus_info(const oakgpu_corpus *corpus, oakgpu_corpus_stats *info);
+/* picks: n x 2 u32 (r, f), device.  Asynchronous on the context's stream (the corpus' workspace grows on the first call of a size). */
+int oakgpu_frames_encode_dev(oakgpu_ctx *ctx, oakgpu_corpus *corpus, const uint32_t *picks, uint32_t n, const oakgpu_encoded_frames *out);
+/* pyoak.sample's rule with a stream per draw.  Eligible records: not MALFORMED, frames <= max_battle_length (0 = no limit), at least
+ * one frame with iterations >= min_iterations; in record order, E of them (E == 0 fails).  Draw i: fast_prng seeded with seed + i;
+ * r = eligible[uniform_64 % E]; f = the (uniform_64 % V[r])-th of r's V[r] valid frames in frame order.  So draw i does not depend
+ * on n.  picks_out (nullable, n x 2 u32, device) receives the picks.  The first call with a new (max_battle_length, min_iterations)
+ * counts the valid frames on the GPU and waits for the stream once to list the eligible records; later calls are asynchronous. */
+int oakgpu_frames_sample_dev(oakgpu_ctx *ctx, oakgpu_corpus *corpus, uint32_t n, uint64_t seed, uint32_t max_battle_length,
+                             uint32_t min_iterations, uint32_t *picks_out, const oakgpu_encoded_frames *out);
+/* The position encoder alone, for callers that hold states: battles n x 384 (16-byte aligned), durations n x 8, results n (the
+ * request bytes) -> pokemon, active, hp, choice_indices and k (the engine's legal-choice counts; 0 for a finished battle). */
+int oakgpu_encode_battles_dev(oakgpu_ctx *ctx, const uint8_t *battles, const uint8_t *durations, const uint8_t *results, uint32_t n,
+                              float *pokemon, float *active, float *hp, int64_t *choice_indices, uint8_t *k);
+/* host arrays in and out (staged; the calls wait for the stream).  ok_rows (nullable): how many rows have status OK. */
+int oakgpu_frames_encode(oakgpu_ctx *ctx, oakgpu_corpus *corpus, const uint32_t *picks, uint32_t n, const oakgpu_encoded_frames *out,
+                         uint32_t *ok_rows);
+int oakgpu_frames_sample(oakgpu_ctx *ctx, oakgpu_corpus *corpus, uint32_t n, uint64_t seed, uint32_t max_battle_length,
+                         uint32_t min_iterations, uint32_t *picks_out, const oakgpu_encoded_frames *out, uint32_t *ok_rows);
+
 /* the compile-time engine switches this library was built with (DESIGN 0 order): MULTIHIT_ROLL_FIRST, PSYWAVE_SHOWDOWN,
  * COUNTER_SHOWDOWN, ACCURACY_LAST.  The default build reports 1, 1, 0, 0. */
 int oakgpu_engine_switches(int out[4]);

@@ -12,6 +12,7 @@
 //   OakGPU::SharedDeviceRollout<- benchmark.cc:23-31: n playouts from one root driven by ONE sequential std::mt19937
 //   OakGPU::Frames             <- Train::Battle::CompressedFrames (train/battle/compressed-frame.h:37-243)
 //   OakGPU::replay_check       <- the replay self-check of py/battle/frames.h:52-67, for a whole file at once
+//   OakGPU::FrameCorpus, EncodedFrames <- pyoak.sample + Py::Battle::EncodedFrames (pyoak.cc:111-245, py/battle/encoded-frames.h)
 //   OakGPU::Exchange           <- the path's one collective: per-root means on the device + RCCL all-gather (no reference analogue)
 // Errors surface as std::runtime_error, like the reference's loaders (cpp/src/search.cc:81-146).
 #pragma once
@@ -321,6 +322,58 @@ inline ReplayCheck replay_check(Context &ctx, const std::vector<uint8_t> &bytes,
                               want_states ? out.battles.data() : nullptr, want_states ? out.durations.data() : nullptr));
   return out;
 }
+
+// A training batch in host memory: the reference's EncodedFrames + Target fields (py/battle/encoded-frames.h:23-41, py/battle/target.h:17-40)
+// as flat row-major vectors, plus status / where / picks (the contract of a row is in oakgpu.h).
+struct EncodedFrames {
+  explicit EncodedFrames(size_t sz)
+      : size{sz}, pokemon(sz * 2 * 6 * 198), active(sz * 2 * 229), hp(sz * 2 * 6), empirical_policies(sz * 18), nash_policies(sz * 18), empirical_value(sz),
+        nash_value(sz), score(sz), choice_indices(sz * 18), k(sz * 2), choice(sz * 2), status(sz), iterations(sz), where(sz), picks(sz * 2) {}
+  size_t size;
+  std::vector<float> pokemon, active, hp, empirical_policies, nash_policies, empirical_value, nash_value, score;
+  std::vector<int64_t> choice_indices;
+  std::vector<uint8_t> k, choice, status;
+  std::vector<uint32_t> iterations, where, picks;
+  oakgpu_encoded_frames pointers() {
+    return oakgpu_encoded_frames{pokemon.data(), active.data(), hp.data(), choice_indices.data(), k.data(), choice.data(), iterations.data(),
+                                 empirical_policies.data(), nash_policies.data(), empirical_value.data(), nash_value.data(), score.data(), status.data(),
+                                 where.data()};
+  }
+};
+
+// `.battle.data` records on the device (oakgpu_corpus_*): uploaded and indexed once, then batches are drawn (pyoak.sample's rule, pyoak.cc:111-245)
+// or picked, replayed and encoded on the GPU.  Must not outlive its Context.  Both calls return the number of OK rows.
+class FrameCorpus {
+public:
+  FrameCorpus(Context &ctx, const std::vector<uint8_t> &bytes) : ctx_{ctx.get()} { check(oakgpu_corpus_create(ctx_, bytes.data(), bytes.size(), &corpus_)); }
+  ~FrameCorpus() { oakgpu_corpus_destroy(corpus_); }
+  FrameCorpus(const FrameCorpus &) = delete;
+  FrameCorpus &operator=(const FrameCorpus &) = delete;
+  oakgpu_corpus *get() const noexcept { return corpus_; }
+  oakgpu_corpus_stats info() const {
+    oakgpu_corpus_stats st{};
+    check(oakgpu_corpus_info(corpus_, &st));
+    return st;
+  }
+  // rows 0 .. n-1 of `out` from out.picks[0 .. 2n) = (record, frame) pairs
+  uint32_t encode(EncodedFrames &out, uint32_t n) {
+    if (n > out.size) throw std::runtime_error{"oakgpu: more picks than rows"};
+    const oakgpu_encoded_frames p = out.pointers();
+    uint32_t ok = 0;
+    check(oakgpu_frames_encode(ctx_, corpus_, out.picks.data(), n, &p, &ok));
+    return ok;
+  }
+  uint32_t sample(EncodedFrames &out, uint64_t seed, uint32_t max_battle_length = 0, uint32_t min_iterations = 1) {
+    const oakgpu_encoded_frames p = out.pointers();
+    uint32_t ok = 0;
+    check(oakgpu_frames_sample(ctx_, corpus_, static_cast<uint32_t>(out.size), seed, max_battle_length, min_iterations, out.picks.data(), &p, &ok));
+    return ok;
+  }
+
+private:
+  oakgpu_ctx *ctx_{};
+  oakgpu_corpus *corpus_{};
+};
 
 // The path's one exchange step for root-parallel search sharded over the GPUs of a node (one process per GPU): reduce the
 // rank's leaf values to one mean per root on the device, then ONE ncclAllGather (RCCL over xGMI) of those means.

@@ -23,6 +23,8 @@ SYMBOLS = [
     "oakgpu_root_steps_create", "oakgpu_root_steps_destroy", "oakgpu_root_steps_launch_dev", "oakgpu_root_steps_capacity", "oakgpu_root_steps_reserve",
     "oakgpu_endless_battle_check", "oakgpu_frames_size", "oakgpu_frames_write", "oakgpu_frames_read", "oakgpu_selfplay_game", "oakgpu_selfplay_games", "oakgpu_poke_engine_eval_dev", "oakgpu_poke_engine_eval",
     "oakgpu_replay_index", "oakgpu_replay_records_dev", "oakgpu_replay_records", "oakgpu_engine_switches",
+    "oakgpu_corpus_create", "oakgpu_corpus_destroy", "oakgpu_corpus_info", "oakgpu_frames_encode_dev", "oakgpu_frames_sample_dev", "oakgpu_encode_battles_dev",
+    "oakgpu_frames_encode", "oakgpu_frames_sample",
 ]
 
 
@@ -61,6 +63,15 @@ class FrameUpdate(C.Structure):       # oakgpu_frame_update
 class SelfplayParams(C.Structure):    # oakgpu_selfplay_params
     _fields_ = [("search", SearchParams), ("policy_mode", C.c_char * 16), ("policy_temp", C.c_double), ("policy_min", C.c_double),
                 ("max_battle_length", C.c_uint32), ("seed", C.c_uint64), ("keep_node", C.c_int32), ("nodes_kept", C.c_uint32)]
+
+
+class EncodedFrames(C.Structure):     # oakgpu_encoded_frames: one pointer per tensor, device or host as the call says
+    _fields_ = [(name, C.c_void_p) for name in ("pokemon", "active", "hp", "choice_indices", "k", "choice", "iterations", "empirical_policies",
+                                                "nash_policies", "empirical_value", "nash_value", "score", "status", "where")]
+
+
+class CorpusStats(C.Structure):       # oakgpu_corpus_stats
+    _fields_ = [("records", C.c_uint32), ("malformed", C.c_uint32), ("frames", C.c_uint64), ("stopped_at", C.c_size_t)]
 
 
 # include/pkmn.h: the libpkmn-named single-battle ABI (batch-of-one wrappers, pkmn_shim.hip)
@@ -156,6 +167,15 @@ def load():
     lib.oakgpu_replay_records_dev.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, vp]
     lib.oakgpu_replay_records.argtypes = [vp, vp, C.c_size_t, vp, u32, C.POINTER(u32), C.POINTER(C.c_size_t), vp, vp]
     lib.oakgpu_engine_switches.argtypes = [C.POINTER(C.c_int * 4)]
+    lib.oakgpu_corpus_create.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp)]
+    lib.oakgpu_corpus_destroy.argtypes = [vp]
+    lib.oakgpu_corpus_destroy.restype = None
+    lib.oakgpu_corpus_info.argtypes = [vp, C.POINTER(CorpusStats)]
+    lib.oakgpu_frames_encode_dev.argtypes = [vp, vp, vp, u32, C.POINTER(EncodedFrames)]
+    lib.oakgpu_frames_sample_dev.argtypes = [vp, vp, u32, u64, u32, u32, vp, C.POINTER(EncodedFrames)]
+    lib.oakgpu_encode_battles_dev.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+    lib.oakgpu_frames_encode.argtypes = [vp, vp, vp, u32, C.POINTER(EncodedFrames), C.POINTER(u32)]
+    lib.oakgpu_frames_sample.argtypes = [vp, vp, u32, u64, u32, u32, vp, C.POINTER(EncodedFrames), C.POINTER(u32)]
     lib.oakgpu_selfplay_game.argtypes = [vp, vp, vp, u64, C.POINTER(SelfplayParams), vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(u32),
                                          C.POINTER(C.c_uint8)]
     lib.oakgpu_selfplay_games.argtypes = [C.POINTER(vp), vp, vp, C.POINTER(u64), C.POINTER(SelfplayParams), u32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t),

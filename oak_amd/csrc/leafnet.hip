@@ -23,6 +23,7 @@
 
 #include "../../include/oakgpu.h"
 #include "oakgpu_internal.h"
+#include "encode_index.hpp"
 
 namespace oak {
 
@@ -79,12 +80,6 @@ __device__ __forceinline__ float act_fn(float x, int activation) {
 }
 
 // ---- K2 ---------------------------------------------------------------------------------------
-
-__device__ __forceinline__ uint32_t status_index(uint32_t status, uint32_t sleeps) { // battle.h:103-123
-  if (!(status & 7)) return (uint32_t)__builtin_ctz(status) - 3;
-  if (!(status & 0x80)) return 3 + sleeps;
-  return 14 - (status & 7);
-}
 
 // Feature `j` (0..11) of Encode::Battle::Pokemon (battle.h:16-214) from the 6 dwords of a party slot:
 // 0-4 stats, 5-8 move slots, 9 status, 10-11 types.  Returns false when the feature is absent.
@@ -2226,22 +2221,7 @@ __global__ __launch_bounds__(MN_BLOCK) void k_mainnet_pair(MainArgs a) {
 }
 
 // ---- policy heads: value_policy_inference's logits (network.h:102-123, main-net.h:67-107) ----------
-// Encode::Battle::Policy::get_index (encode/battle/policy.h:29-58) on the raw battle bytes
-__device__ __forceinline__ uint32_t policy_index(const uint8_t *side, uint32_t choice) {
-  const uint32_t kind = choice & 3, data = choice >> 2;
-  if (kind == 1) {
-    if (data == 0) return 0; // Struggle / forced continue: only ever a sole option (policy.h:11-19)
-    const uint32_t sid = side[176] - 1u;
-    const uint32_t mid = side[24 * sid + 10 + 2 * (data - 1)]; // side.stored().moves[data - 1].id
-    return mid == 0 ? 0 : mid - 1;
-  }
-  if (kind == 2) {
-    const uint32_t pid = side[176 + data - 1];
-    return 164 + side[24 * (pid - 1) + 21] - 1u;
-  }
-  return 0;
-}
-
+// (Encode::Battle::Policy::get_index on the raw battle bytes: policy_index, encode_index.hpp)
 struct PolicyArgs {
   NetDev net;
   const float *h1;  // n x H

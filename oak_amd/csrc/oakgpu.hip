@@ -24,6 +24,7 @@
 #include "gen1_device.hpp"
 #include "gen1_regs.hpp"
 #include "oakgpu_internal.h"
+#include "fast_prng.hpp"
 
 namespace oak {
 
@@ -83,47 +84,6 @@ __device__ __forceinline__ void store_state(const lds_u32 *state, uint8_t *battl
     dst[i] = state[w * BLK + b];
   }
 }
-
-// ---- fast_prng (cpp/include/util/random.h:67-133): 2 x u32 of state per lane ---------------
-struct FastPrng {
-  uint32_t s0, s1;
-  __device__ __forceinline__ static uint32_t rotl(uint32_t x, int k) { return (x << k) | (x >> (32 - k)); }
-  __device__ __forceinline__ uint32_t next32() {
-    uint32_t result = rotl(s0 + s1, 9) + s0;
-    s1 ^= s0;
-    s0 = rotl(s0, 13) ^ s1 ^ (s1 << 5);
-    s1 = rotl(s1, 28);
-    return result;
-  }
-  // std::seed_seq{lo32, hi32}.generate(2 words), random.h:99-105
-  __device__ void seed(uint64_t seed) {
-    const uint32_t v[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-    uint32_t b0 = 0x8b8b8b8bu, b1 = 0x8b8b8b8bu;
-    // n = 2, s = 2, t = 0, p = q = 1, m = 3; indices alternate between the two words
-#pragma unroll
-    for (uint32_t k = 0; k < 3; ++k) {
-      uint32_t &bk = (k & 1) ? b1 : b0, &bo = (k & 1) ? b0 : b1; // bk = b[k%2], bo = b[(k+1)%2] = b[(k-1)%2]
-      uint32_t arg = bk ^ bo ^ bo;
-      uint32_t r1 = 1664525u * (arg ^ (arg >> 27));
-      uint32_t r2 = r1 + (k == 0 ? 2u : (k & 1) + v[k - 1 < 2 ? k - 1 : 0]);
-      bo += r1;
-      bo += r2;
-      bk = r2;
-    }
-#pragma unroll
-    for (uint32_t k = 3; k < 5; ++k) {
-      uint32_t &bk = (k & 1) ? b1 : b0, &bo = (k & 1) ? b0 : b1;
-      uint32_t arg = bk + bo + bo;
-      uint32_t r3 = 1566083941u * (arg ^ (arg >> 27));
-      uint32_t r4 = r3 - (k & 1);
-      bo ^= r3;
-      bo ^= r4;
-      bk = r4;
-    }
-    s0 = b0;
-    s1 = b1;
-  }
-};
 
 __device__ __forceinline__ uint32_t mod64_small(uint32_t hi, uint32_t lo, uint32_t m) {
   // (hi * 2^32 + lo) % m for small m, 32-bit ops only
@@ -2725,6 +2685,17 @@ static int replay_launch(oakgpu_ctx *c, const uint8_t *records, const uint64_t *
     const uint32_t waves = std::min((n_live + 63) / 64, resident);
     hipLaunchKernelGGL((oak::k_replay_records<4>), dim3(waves), dim3(64), oak::REPLAY_LDS_BYTES, c->stream, a);
   }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// k_replay_gather alone, for the training-frame corpus (trainframes.hip): aligned battles + first requests of n indexed records, in the
+// context's stream.  `reports` (n x 2 dwords, scratch) takes the MALFORMED reports the kernel writes.
+int oakgpu_replay_gather_dev(oakgpu_ctx *c, const uint8_t *records, const uint64_t *offsets, const uint8_t *malformed, uint32_t n,
+                             uint8_t *aligned, uint8_t *first, uint32_t *reports) {
+  if (n == 0) return 0;
+  const oak::ReplayArgs a{records, offsets, nullptr, nullptr, aligned, first, reports, nullptr, nullptr, nullptr, 0};
+  hipLaunchKernelGGL(oak::k_replay_gather, dim3((n + 3) / 4), dim3(256), 0, c->stream, a, malformed, n);
   HIPCHK(hipGetLastError());
   return 0;
 }

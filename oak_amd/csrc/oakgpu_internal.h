@@ -28,6 +28,9 @@ struct OakHostCall {
   ~OakHostCall() { oakgpu_stage_end(c); }
   void *get(size_t bytes) { return oakgpu_stage_get(c, bytes); }
 };
+// oakgpu.hip: k_replay_gather alone (aligned battles + first requests of n indexed records; `reports` = n x 2 dwords of scratch)
+extern "C" int oakgpu_replay_gather_dev(oakgpu_ctx *ctx, const uint8_t *records, const uint64_t *offsets, const uint8_t *malformed, uint32_t n,
+                                        uint8_t *aligned, uint8_t *first, uint32_t *reports);
 extern "C" int oakgpu_leaf_set_lds_limits(void);                // leafnet.hip: per-device kernel attributes (called by oakgpu_create)
 // Optional per-kernel timing of the leaf evaluator (oakgpu_set_kernel_timing): 4 events = before the party-slot
 // embedding pass, before the actives' pass, before the main net, after it.  nullptr when timing is off.

@@ -11,9 +11,14 @@
 //   solve_matrix(row_payoff, discretize_factor) -> (p1, p2, value)                        :394-426, 711
 //   read_battle_data(path) -> [(bytes, frame_count), ...]                                 :43-71, 713
 //   network hyper-parameter constants                                                     :586-596
-// Every battle operation goes through the C ABI (GPU); this file holds no battle arithmetic.  Not carried over: the
-// training-data loaders of pyoak (EncodedBattleFrames, sample, BuildTrajectories): training stays with the reference's
-// Python, outside the hot path.  Heap keeps the tree between searches (RuntimeSearch::Heap over oakgpu_heap; its C++
+//   EncodedBattleFrames(size) {the reference's numpy fields + status, where, picks}, clear(), from_bytes(bytes, size)  py/battle/encoded-frames.h
+//   SampleIndexer() {get(path), prune(paths), size()}, sample(encoded_frames, indexer, threads, max_battle_length, min_iterations)  :73-245
+// Every battle operation goes through the C ABI (GPU); this file holds no battle arithmetic.  The battle training-data loader
+// (EncodedBattleFrames, SampleIndexer, sample) is the GPU loader of include/oakgpu.h behind the reference's names: the indexer's
+// files are uploaded once as a corpus (again when a path joins or leaves, or a file's size or time of last write changes) and a call draws, replays and encodes `size` rows on
+// the device, then copies them into the numpy fields; `threads` is accepted and ignored, the seed comes from std::random_device
+// as in the reference.  oak_amd/train.py is the same loader on torch tensors, without the copy.  Not carried over:
+// BuildTrajectories, which stays with the reference's Python.  Heap keeps the tree between searches (RuntimeSearch::Heap over oakgpu_heap; its C++
 // `update(i, j, obs)` is exposed too, and `update(input, c1, c2)` returns the 16-byte observation that call needs), an
 // `output` passed to search() is resumed like MCTS::Search::run's by-value Output (mcts.h:153-155), p{1,2}_prior are the
 // softmax of the root's policy logits for contextual bandits (mcts.h:196-209).  cpp_inference takes a game record as
@@ -24,10 +29,14 @@
 #include <pybind11/stl.h>
 
 #include <cstring>
+#include <filesystem>
 #include <fstream>
+#include <memory>
 #include <mutex>
 #include <random>
 #include <stdexcept>
+#include <algorithm>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -76,6 +85,116 @@ oakgpu_ctx *context() { // one context per process, created on first use (device
   }
   return ctx;
 }
+
+// Py::Battle::EncodedFrames + Target (py/battle/encoded-frames.h:23-50, py/battle/target.h:17-53): the same numpy fields, plus the
+// loader's status / where per row (include/oakgpu.h)
+struct EncodedBattleFrames {
+  size_t size;
+  py::array_t<float> pokemon, active, hp;
+  py::array_t<int64_t> choice_indices;
+  py::array_t<uint8_t> k, choice;
+  py::array_t<uint32_t> iterations;
+  py::array_t<float> empirical_policies, nash_policies, empirical_value, nash_value, score;
+  py::array_t<uint8_t> status;
+  py::array_t<uint32_t> where, picks; // picks: the (record, frame) behind each row, records counted over the indexer's files in path order
+  explicit EncodedBattleFrames(size_t sz)
+      : size{sz}, pokemon(std::vector<size_t>{sz, 2, 6, 198}), active(std::vector<size_t>{sz, 2, 1, 229}), hp(std::vector<size_t>{sz, 2, 6, 1}),
+        choice_indices(std::vector<size_t>{sz, 2, 9}), k(std::vector<size_t>{sz, 2, 1}), choice(std::vector<size_t>{sz, 2, 1}),
+        iterations(std::vector<size_t>{sz, 1}), empirical_policies(std::vector<size_t>{sz, 2, 9}), nash_policies(std::vector<size_t>{sz, 2, 9}),
+        empirical_value(std::vector<size_t>{sz, 1}), nash_value(std::vector<size_t>{sz, 1}), score(std::vector<size_t>{sz, 1}),
+        status(std::vector<size_t>{sz}), where(std::vector<size_t>{sz}), picks(std::vector<size_t>{sz, 2}) {
+    clear();
+  }
+  template <class T> static void zero(py::array_t<T> &a) { std::fill_n(a.mutable_data(), a.size(), T{}); }
+  void clear() {
+    zero(pokemon); zero(active); zero(hp); zero(choice_indices); zero(k); zero(choice); zero(iterations); zero(empirical_policies);
+    zero(nash_policies); zero(empirical_value); zero(nash_value); zero(score); zero(status); zero(where); zero(picks);
+  }
+  oakgpu_encoded_frames pointers() {
+    return oakgpu_encoded_frames{pokemon.mutable_data(), active.mutable_data(), hp.mutable_data(), choice_indices.mutable_data(), k.mutable_data(),
+                                 choice.mutable_data(), iterations.mutable_data(), empirical_policies.mutable_data(), nash_policies.mutable_data(),
+                                 empirical_value.mutable_data(), nash_value.mutable_data(), score.mutable_data(), status.mutable_data(),
+                                 where.mutable_data()};
+  }
+};
+
+std::vector<char> read_file(const std::string &path, const char *who) {
+  std::ifstream file(path, std::ios::binary);
+  if (!file) throw std::runtime_error(std::string(who) + ": Failed to open file: " + path);
+  return std::vector<char>((std::istreambuf_iterator<char>(file)), std::istreambuf_iterator<char>());
+}
+
+// SampleIndexer (pyoak.cc:73-109): path -> [(byte offset, frame count), ...]; here it also owns the device corpus of its files
+struct SampleIndexer {
+  std::map<std::string, py::list> data;
+  oakgpu_corpus *corpus = nullptr;
+  struct FileKey { // a file as uploaded: a file that grew or was rewritten under its name is read again
+    std::string path;
+    uintmax_t size;
+    std::filesystem::file_time_type written;
+    bool operator==(const FileKey &o) const { return path == o.path && size == o.size && written == o.written; }
+  };
+  std::vector<FileKey> corpus_files;
+  SampleIndexer() = default;
+  SampleIndexer(const SampleIndexer &) = delete;
+  SampleIndexer &operator=(const SampleIndexer &) = delete;
+  ~SampleIndexer() {
+    std::lock_guard<std::mutex> lock(g_ctx_mu);
+    drop();
+  }
+  void drop() { // (under g_ctx_mu)
+    if (corpus) oakgpu_corpus_destroy(corpus);
+    corpus = nullptr;
+    corpus_files.clear();
+  }
+  size_t size() const { return data.size(); }
+  py::list get(const std::string &path) {
+    auto it = data.find(path);
+    if (it != data.end()) return it->second;
+    const std::vector<char> bytes = read_file(path, "SampleIndexer.get");
+    uint32_t n = 0;
+    size_t stop = 0;
+    check(oakgpu_replay_index((const uint8_t *)bytes.data(), bytes.size(), nullptr, nullptr, nullptr, 0, &n, &stop));
+    std::vector<uint64_t> offs(n ? n : 1);
+    std::vector<uint16_t> frames(n ? n : 1);
+    std::vector<uint8_t> malformed(n ? n : 1);
+    if (n) check(oakgpu_replay_index((const uint8_t *)bytes.data(), stop, offs.data(), frames.data(), malformed.data(), n, &n, nullptr));
+    py::list out;
+    for (uint32_t i = 0; i < n; ++i) out.append(py::make_tuple((int)offs[i], (int)frames[i]));
+    data[path] = out;
+    return out;
+  }
+  void prune(const std::vector<std::string> &paths) { // keeps the listed paths only
+    for (auto it = data.begin(); it != data.end();)
+      it = std::find(paths.begin(), paths.end(), it->first) == paths.end() ? data.erase(it) : std::next(it);
+  }
+  // The files of `data`, in path order, uploaded once per set of (path, size, time of last write); under g_ctx_mu.  A changed set is
+  // read and concatenated in host memory again as a whole.  The lists get() returned are not refreshed (the reference's are not).
+  oakgpu_corpus *device_corpus() {
+    std::vector<FileKey> files;
+    for (const auto &kv : data) {
+      std::error_code ec1, ec2;
+      const uintmax_t size = std::filesystem::file_size(kv.first, ec1);
+      const auto written = std::filesystem::last_write_time(kv.first, ec2);
+      if (ec1 || ec2) throw std::runtime_error("sample: Failed to open file: " + kv.first);
+      files.push_back(FileKey{kv.first, size, written});
+    }
+    if (corpus && files == corpus_files) return corpus;
+    drop();
+    std::vector<uint8_t> all;
+    for (const auto &file : files) {
+      const std::string &path = file.path;
+      const std::vector<char> bytes = read_file(path, "sample");
+      uint32_t n = 0;
+      size_t stop = 0; // (bytes behind a record whose length cannot be trusted are left out, so that the next file's records follow)
+      check(oakgpu_replay_index((const uint8_t *)bytes.data(), bytes.size(), nullptr, nullptr, nullptr, 0, &n, &stop));
+      all.insert(all.end(), bytes.begin(), bytes.begin() + (std::ptrdiff_t)stop);
+    }
+    check(oakgpu_corpus_create(context(), all.data(), all.size(), &corpus));
+    corpus_files = files;
+    return corpus;
+  }
+};
 
 template <class T, class F> py::array_t<T> vec9(F f) {
   py::array_t<T> arr(9);
@@ -351,6 +470,75 @@ PYBIND11_MODULE(pyoak, m) {
         return result;
       },
       py::arg("path"));
+
+  py::class_<EncodedBattleFrames>(m, "EncodedBattleFrames")
+      .def(py::init<size_t>(), py::arg("size"))
+      .def_readonly("size", &EncodedBattleFrames::size)
+      .def_readonly("pokemon", &EncodedBattleFrames::pokemon)
+      .def_readonly("active", &EncodedBattleFrames::active)
+      .def_readonly("hp", &EncodedBattleFrames::hp)
+      .def_readonly("choice_indices", &EncodedBattleFrames::choice_indices)
+      .def_readonly("k", &EncodedBattleFrames::k)
+      .def_readonly("choice", &EncodedBattleFrames::choice)
+      .def_readonly("iterations", &EncodedBattleFrames::iterations)
+      .def_readonly("empirical_policies", &EncodedBattleFrames::empirical_policies)
+      .def_readonly("nash_policies", &EncodedBattleFrames::nash_policies)
+      .def_readonly("empirical_value", &EncodedBattleFrames::empirical_value)
+      .def_readonly("nash_value", &EncodedBattleFrames::nash_value)
+      .def_readonly("score", &EncodedBattleFrames::score)
+      .def_readonly("status", &EncodedBattleFrames::status)
+      .def_readonly("where", &EncodedBattleFrames::where)
+      .def_readonly("picks", &EncodedBattleFrames::picks)
+      .def("clear", &EncodedBattleFrames::clear)
+      .def_static(
+          "from_bytes",
+          [](const py::bytes &record, size_t size) { // encoded-frames.h:111-133: every frame of one game record, rows 0 .. frames-1
+            const std::string bytes = record;
+            auto out = std::make_unique<EncodedBattleFrames>(size);
+            std::lock_guard<std::mutex> lock(g_ctx_mu);
+            oakgpu_corpus *corpus = nullptr;
+            check(oakgpu_corpus_create(context(), (const uint8_t *)bytes.data(), bytes.size(), &corpus));
+            oakgpu_corpus_stats st{};
+            int rc = oakgpu_corpus_info(corpus, &st);
+            if (!rc && (st.records != 1 || st.malformed)) rc = -2;
+            if (!rc && st.frames > size) rc = -3;
+            if (!rc) {
+              uint32_t *picks = out->picks.mutable_data();
+              for (uint32_t f = 0; f < st.frames; ++f) picks[2 * f + 1] = f;
+              const oakgpu_encoded_frames p = out->pointers();
+              rc = oakgpu_frames_encode(context(), corpus, picks, (uint32_t)st.frames, &p, nullptr);
+            }
+            oakgpu_corpus_destroy(corpus);
+            if (rc == -2) throw std::runtime_error("EncodedBattleFrames.from_bytes: expected exactly one well-formed game record");
+            if (rc == -3) throw std::runtime_error("EncodedBattleFrames.from_bytes: the record has more frames than `size`");
+            check(rc);
+            return out;
+          },
+          py::arg("data"), py::arg("size"));
+
+  py::class_<SampleIndexer>(m, "SampleIndexer")
+      .def(py::init<>())
+      .def("get", &SampleIndexer::get, py::arg("path"))
+      .def("prune", &SampleIndexer::prune, py::arg("paths"))
+      .def("size", &SampleIndexer::size);
+
+  m.def(
+      "sample",
+      [](EncodedBattleFrames &frames, SampleIndexer &indexer, size_t /*threads*/, size_t max_battle_length, size_t min_iterations) -> size_t {
+        // pyoak.cc:111-245.  Returns the rows written with status OK (all `size` of them on records that pass the replay check).
+        if (frames.size == 0) return 0;
+        std::lock_guard<std::mutex> lock(g_ctx_mu);
+        oakgpu_corpus *corpus = indexer.device_corpus();
+        std::random_device rd;
+        const uint64_t seed = ((uint64_t)rd() << 32) | rd();
+        const oakgpu_encoded_frames p = frames.pointers();
+        uint32_t ok = 0;
+        const uint32_t max_len = max_battle_length > 65535 ? 0u : (uint32_t)max_battle_length; // (a record holds at most 65,535 frames: no limit)
+        const uint32_t min_it = (uint32_t)std::min<size_t>(min_iterations, 0xFFFFFFFFu);
+        check(oakgpu_frames_sample(context(), corpus, (uint32_t)frames.size, seed, max_len, min_it, frames.picks.mutable_data(), &p, &ok));
+        return ok;
+      },
+      py::arg("encoded_frames"), py::arg("indexer"), py::arg("threads"), py::arg("max_battle_length"), py::arg("min_iterations"));
 
   // Battle net hyper-parameters (pyoak.cc:586-596; nn/default-hyperparameters.h:10-18, encode/battle/*.h dims)
   m.attr("pokemon_in_dim") = 198;
