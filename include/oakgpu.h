@@ -681,6 +681,62 @@ int oakgpu_leaf_eval_policy(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *bat
                             const uint8_t *p1_choices, const uint8_t *p1_counts, const uint8_t *p2_choices,
                             const uint8_t *p2_counts, float *values, float *p1_logits, float *p2_logits);
 
+/* The bench-slot embedding table of a search: NN::Battle::PokemonCache (nn/battle/cache.h:18-131) as the reference uses it -- 240
+ * embeddings (16 has-PP patterns x 15 status indices, key = Encode::Battle::pokemon_key, encode/battle/key.h:65-71) for each of the
+ * 12 stored Pokemon of a ROOT battle, computed once, after which a leaf's ten bench slots are row copies and only its two actives
+ * go through an embedding network.  A table holds up to max_roots roots and belongs to one network, which must outlive it (a quantized network's table
+ * holds the ReLU embeddings its party slots take) and one device; any context of that device may fill or read it.
+ *   fill: the 2,880 variants of every root through the party kernel's work-list form, in the form the plain call takes for this
+ * network and context, so a row equals what oakgpu_leaf_eval_dev computes for that variant, bit for bit.  The device-pointer fill
+ * is asynchronous on the context's stream (a table call on ANOTHER stream waits for it through an event; do not refill while other
+ * streams still read) and, like every device array of battles in this header, wants root_battles aligned to 8 bytes (the kernels read
+ * them two dwords at a time; any hipMalloc'd array of whole battles is); the host-pointer fill returns with the table complete.  A fill replaces all roots: n_roots in 1..max_roots.
+ *   lookup (the two eval calls): oakgpu_leaf_eval_dev / oakgpu_leaf_eval_policy_dev with the party pass replaced.  Leaf i belongs to
+ * root root_of[i] (device array of n; NULL = all root 0).  A live bench slot whose stored identity -- stats, move ids, species, types,
+ * level -- equals the table's Pokemon at (root, side, team index) takes that Pokemon's row; any other live slot is embedded by the
+ * work-list kernel as the cached call's changed slots are, so the results equal the plain call's for ANY leaf, descended from the
+ * root or not.  A root_of entry beyond the filled roots is never followed: the leaf's slots are embedded as misses and the leaf is
+ * counted (see the diagnostic).  Refused: null pointers, a table of another network or device, n_roots of 0 or above max_roots, an
+ * eval before the first fill. */
+typedef struct oakgpu_party_table oakgpu_party_table;
+int oakgpu_party_table_create(oakgpu_ctx *ctx, oakgpu_net *net, uint32_t max_roots, oakgpu_party_table **out);
+void oakgpu_party_table_destroy(oakgpu_ctx *ctx, oakgpu_party_table *table); /* synchronises the device; ctx may be NULL */
+int oakgpu_party_table_fill_dev(oakgpu_ctx *ctx, oakgpu_party_table *table, const uint8_t *root_battles, uint32_t n_roots);
+int oakgpu_party_table_fill(oakgpu_ctx *ctx, oakgpu_party_table *table, const uint8_t *root_battles, uint32_t n_roots);
+int oakgpu_leaf_eval_table_dev(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_party_table *table, const uint32_t *root_of, const uint8_t *battles,
+                               const uint8_t *durations, uint32_t n, float *values, float *embedding_out);
+int oakgpu_leaf_eval_policy_table_dev(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_party_table *table, const uint32_t *root_of, const uint8_t *battles,
+                                      const uint8_t *durations, uint32_t n, const uint8_t *p1_choices, const uint8_t *p1_counts,
+                                      const uint8_t *p2_choices, const uint8_t *p2_counts, float *values, float *p1_logits, float *p2_logits);
+/* The same two calls on host arrays (root_of too), staged like oakgpu_leaf_eval / oakgpu_leaf_eval_policy: PCIe-inclusive conveniences. */
+int oakgpu_leaf_eval_table(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_party_table *table, const uint32_t *root_of, const uint8_t *battles,
+                           const uint8_t *durations, uint32_t n, float *values, float *embedding_out);
+int oakgpu_leaf_eval_policy_table(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_party_table *table, const uint32_t *root_of, const uint8_t *battles,
+                                  const uint8_t *durations, uint32_t n, const uint8_t *p1_choices, const uint8_t *p1_counts,
+                                  const uint8_t *p2_choices, const uint8_t *p2_counts, float *values, float *p1_logits, float *p2_logits);
+/* Diagnostic (synchronises the context's stream): the bench slots the LAST table eval of this context found no row for and
+ * embedded, of the n x 10 it looked at.  Fails, with the count in the message and *slots still set, when that call had root_of
+ * entries beyond the filled roots.  Refused when the context's last work-list call was not an eval through this table (none yet, or
+ * oakgpu_leaf_eval_cached_dev or a training-batch call since: they share the counters' memory). */
+int oakgpu_party_table_last_misses(oakgpu_ctx *ctx, oakgpu_party_table *table, uint32_t *slots);
+/* Diagnostic: the 240 rows (rows: host, 240 x the party embedding width, row = key) of Pokemon `pokemon` (0..5, team order) of
+ * `side` (0, 1) of filled root `root`; the width itself (the party embedding net's output size; -1: null table). */
+int oakgpu_party_table_rows(oakgpu_ctx *ctx, oakgpu_party_table *table, uint32_t root, int side, int pokemon, float *rows);
+int oakgpu_party_table_width(const oakgpu_party_table *table);
+/* Host only, no GPU: the key of a stored Pokemon (24 bytes) with its public sleep turns, and the variant the fill stores under a key
+ * (`out`, `sleep` nullable; differs from `base` in the four PP bytes and the status byte only; non-zero for key >= 240) -- the
+ * inline functions the kernels use. */
+uint8_t oakgpu_party_key(const uint8_t pokemon[24], uint8_t sleep);
+int oakgpu_party_variant(const uint8_t base[24], uint8_t key, uint8_t out[24], uint8_t *sleep);
+/* The tree search (oakgpu_search, _search_heap, _search_agent(_heap), _search_many, oakgpu_selfplay_game(s)) with a network
+ * evaluator, fp32 or quantized, on this context: on = 1 fills a one-root table from the search's root before the first batch and
+ * sends the evaluation of every leaf batch through it (a contextual bandit's root priors, a batch of one before the table exists,
+ * stay on the plain call).  No result changes (tests/test_gpu_party_table.py).  Returns the previous value; default 0, or 1 for
+ * contexts created while OAKGPU_PARTY_TABLE=1 is set.  The diagnostic counts, since the context was created, the searches on it that
+ * filled a table and the leaf batches they evaluated through one (fills, evals nullable). */
+int oakgpu_set_search_party_table(oakgpu_ctx *ctx, int on);
+int oakgpu_search_party_table_stats(oakgpu_ctx *ctx, uint64_t *fills, uint64_t *evals);
+
 #ifdef __cplusplus
 }
 #endif

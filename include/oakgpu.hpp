@@ -40,6 +40,15 @@ public:
   Context &operator=(const Context &) = delete;
   oakgpu_ctx *get() const noexcept { return ctx_; }
   void synchronize() { check(oakgpu_synchronize(ctx_)); }
+  // tree searches of this context look bench-slot embeddings up in a table filled from the search's root (no result changes;
+  // default off); returns the previous value
+  bool set_search_party_table(bool on) { return oakgpu_set_search_party_table(ctx_, on ? 1 : 0) != 0; }
+  // {searches of this context that filled such a table, leaf batches they evaluated through one}
+  std::pair<uint64_t, uint64_t> search_party_table_stats() const {
+    uint64_t fills = 0, evals = 0;
+    check(oakgpu_search_party_table_stats(ctx_, &fills, &evals));
+    return {fills, evals};
+  }
 
 private:
   oakgpu_ctx *ctx_{};
@@ -87,6 +96,8 @@ public:
 private:
   Context &ctx_;
 };
+
+class PartyTable;
 
 class Network {
 public:
@@ -175,12 +186,62 @@ public:
     check(oakgpu_leaf_eval_cached_dev(ctx_.get(), net_, battles, durations, n, values, embedding, slot_tags));
   }
 
+  // The same two calls with the bench slots looked up in a filled PartyTable of this network (device pointers; root_of: n root
+  // indices on the device, or nullptr = all root 0).  Results equal the plain calls'.
+  inline void value_inference_table_dev(PartyTable &table, const uint32_t *root_of, const uint8_t *battles, const uint8_t *durations, uint32_t n,
+                                        float *values, float *embedding_out = nullptr);
+  inline void value_policy_inference_table_dev(PartyTable &table, const uint32_t *root_of, const uint8_t *battles, const uint8_t *durations, uint32_t n,
+                                               const uint8_t *p1_choices, const uint8_t *p1_counts, const uint8_t *p2_choices,
+                                               const uint8_t *p2_counts, float *values, float *p1_logits, float *p2_logits);
+
   oakgpu_net *get() const noexcept { return net_; }
 
 private:
   Context &ctx_;
   oakgpu_net *net_{};
 };
+
+// NN::Battle::PokemonCache filled once per root (nn/battle/cache.h:18-131): the 240 embeddings of each of a root battle's 12
+// stored Pokemon, after which a leaf's bench slots are row copies.  Fill per search, or once per game -- a team's stored identity
+// never changes; a slot the table does not hold is embedded as usual.  The network must outlive the table.
+class PartyTable {
+public:
+  PartyTable(Context &ctx, Network &net, uint32_t max_roots = 1) : ctx_{ctx} { check(oakgpu_party_table_create(ctx.get(), net.get(), max_roots, &t_)); }
+  ~PartyTable() { oakgpu_party_table_destroy(ctx_.get(), t_); }
+  PartyTable(const PartyTable &) = delete;
+  PartyTable &operator=(const PartyTable &) = delete;
+  // n_roots x OAKGPU_BATTLE_SIZE bytes on the host (returns with the table complete) / on the device (asynchronous on the context's stream)
+  void fill(const uint8_t *root_battles, uint32_t n_roots = 1) { check(oakgpu_party_table_fill(ctx_.get(), t_, root_battles, n_roots)); }
+  void fill_dev(const uint8_t *root_battles, uint32_t n_roots = 1) { check(oakgpu_party_table_fill_dev(ctx_.get(), t_, root_battles, n_roots)); }
+  int width() const noexcept { return oakgpu_party_table_width(t_); }
+  // diagnostics: the 240 x width() rows of one Pokemon; the bench slots the context's last table call had to embed
+  std::vector<float> rows(uint32_t root, int side, int pokemon) {
+    std::vector<float> out(size_t{240} * static_cast<size_t>(width()));
+    check(oakgpu_party_table_rows(ctx_.get(), t_, root, side, pokemon, out.data()));
+    return out;
+  }
+  uint32_t last_misses() {
+    uint32_t slots = 0;
+    check(oakgpu_party_table_last_misses(ctx_.get(), t_, &slots));
+    return slots;
+  }
+  oakgpu_party_table *get() const noexcept { return t_; }
+
+private:
+  Context &ctx_;
+  oakgpu_party_table *t_{};
+};
+
+inline void Network::value_inference_table_dev(PartyTable &table, const uint32_t *root_of, const uint8_t *battles, const uint8_t *durations, uint32_t n,
+                                               float *values, float *embedding_out) {
+  check(oakgpu_leaf_eval_table_dev(ctx_.get(), net_, table.get(), root_of, battles, durations, n, values, embedding_out));
+}
+inline void Network::value_policy_inference_table_dev(PartyTable &table, const uint32_t *root_of, const uint8_t *battles, const uint8_t *durations,
+                                                      uint32_t n, const uint8_t *p1_choices, const uint8_t *p1_counts, const uint8_t *p2_choices,
+                                                      const uint8_t *p2_counts, float *values, float *p1_logits, float *p2_logits) {
+  check(oakgpu_leaf_eval_policy_table_dev(ctx_.get(), net_, table.get(), root_of, battles, durations, n, p1_choices, p1_counts, p2_choices, p2_counts,
+                                          values, p1_logits, p2_logits));
+}
 
 // RuntimeSearch::Heap (util/search.h:17-32, search.cc:17-58): the tree of a search kept between searches.
 class Heap {

@@ -25,6 +25,9 @@ SYMBOLS = [
     "oakgpu_replay_index", "oakgpu_replay_records_dev", "oakgpu_replay_records", "oakgpu_engine_switches",
     "oakgpu_corpus_create", "oakgpu_corpus_destroy", "oakgpu_corpus_info", "oakgpu_frames_encode_dev", "oakgpu_frames_sample_dev", "oakgpu_encode_battles_dev",
     "oakgpu_frames_encode", "oakgpu_frames_sample",
+    "oakgpu_party_table_create", "oakgpu_party_table_destroy", "oakgpu_party_table_fill_dev", "oakgpu_party_table_fill", "oakgpu_leaf_eval_table_dev",
+    "oakgpu_leaf_eval_policy_table_dev", "oakgpu_party_table_last_misses", "oakgpu_party_table_rows", "oakgpu_party_table_width", "oakgpu_party_key", "oakgpu_party_variant",
+    "oakgpu_set_search_party_table", "oakgpu_search_party_table_stats", "oakgpu_leaf_eval_table", "oakgpu_leaf_eval_policy_table",
 ]
 
 
@@ -213,6 +216,23 @@ def load():
     lib.oakgpu_leaf_embed_forms.argtypes = [vp, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.oakgpu_leaf_eval_policy_dev.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
     lib.oakgpu_leaf_eval_policy.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
+    lib.oakgpu_party_table_create.argtypes = [vp, vp, u32, C.POINTER(vp)]
+    lib.oakgpu_party_table_destroy.argtypes = [vp, vp]
+    lib.oakgpu_party_table_destroy.restype = None
+    lib.oakgpu_party_table_fill_dev.argtypes = [vp, vp, vp, u32]
+    lib.oakgpu_party_table_fill.argtypes = [vp, vp, vp, u32]
+    lib.oakgpu_leaf_eval_table_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp]
+    lib.oakgpu_leaf_eval_policy_table_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
+    lib.oakgpu_party_table_last_misses.argtypes = [vp, vp, C.POINTER(u32)]
+    lib.oakgpu_party_table_rows.argtypes = [vp, vp, u32, i32, i32, vp]
+    lib.oakgpu_party_table_width.argtypes = [vp]
+    lib.oakgpu_party_key.argtypes = [vp, C.c_uint8]
+    lib.oakgpu_party_key.restype = C.c_uint8
+    lib.oakgpu_party_variant.argtypes = [vp, C.c_uint8, vp, C.POINTER(C.c_uint8)]
+    lib.oakgpu_set_search_party_table.argtypes = [vp, i32]
+    lib.oakgpu_search_party_table_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    lib.oakgpu_leaf_eval_table.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp]
+    lib.oakgpu_leaf_eval_policy_table.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 

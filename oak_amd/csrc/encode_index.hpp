@@ -6,7 +6,7 @@
 
 namespace oak {
 
-__device__ __forceinline__ uint32_t status_index(uint32_t status, uint32_t sleeps) { // battle.h:103-123
+__host__ __device__ __forceinline__ uint32_t status_index(uint32_t status, uint32_t sleeps) { // battle.h:103-123
   if (!(status & 7)) return (uint32_t)__builtin_ctz(status) - 3;
   if (!(status & 0x80)) return 3 + sleeps;
   return 14 - (status & 7);

@@ -16,6 +16,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 #include <cmath>
 #include <string>
 #include <type_traits>
@@ -24,6 +25,7 @@
 #include "../../include/oakgpu.h"
 #include "oakgpu_internal.h"
 #include "encode_index.hpp"
+#include "party_key.hpp"
 
 namespace oak {
 
@@ -1435,6 +1437,121 @@ __global__ __launch_bounds__(256) void k_party_tags(NetDev N, const uint8_t *bat
   }
 }
 
+// ---- the per-search bench-slot table (oakgpu_party_table_*): NN::Battle::PokemonCache filled once per root ------------------------
+// A tree search's leaves are new states every batch, so tags kept per lane do not apply; what stays is the ROOT's twelve stored
+// Pokemon, whose identity no turn changes.  k_party_variants writes their 240 variants (cache.h:81-126) as PartyWork records and
+// the party kernel's LIST form embeds them -- the arithmetic of the plain pass, bit for bit -- into a buffer laid out as
+// PSEUDO-LEAVES: variant `key` of Pokemon p (side * 6 + id - 1) of root r is item r * 2880 + p * 240 + key, i.e. bench slot
+// (key % 10) of pseudo-leaf r * 288 + p * 24 + key / 10, so the LIST kernel's own addressing serves and the store needs no second
+// mode.  k_party_lookup then replaces the party pass of a leaf batch by row copies; a slot whose identity differs from the table's
+// Pokemon at its (root, side, id - 1) goes to a work list for the LIST kernel, as in the cached call.
+constexpr uint32_t PT_LEAVES = 12 * PARTY_KEYS / 10; // pseudo-leaves per root
+__global__ __launch_bounds__(256) void k_party_variants(const uint8_t *roots, uint32_t n_roots, PartyWork *work, uint32_t *ident, uint32_t *work_count) {
+  const uint32_t v = blockIdx.x * 256 + threadIdx.x, total = n_roots * 12 * PARTY_KEYS;
+  if (v == 0) *work_count = total;
+  if (v >= total) return;
+  const uint32_t poke = v / PARTY_KEYS, key = v - poke * PARTY_KEYS, root = poke / 12, p = poke - root * 12;
+  const uint2 *b = (const uint2 *)((const uint32_t *)roots + (size_t)root * 96 + (p / 6) * 46 + (p % 6) * 6);
+  const uint2 b0 = b[0], b1 = b[1], b2 = b[2];
+  const uint32_t base[6] = {b0.x, b0.y, b1.x, b1.y, b2.x, b2.y};
+  const bool empty = ((base[5] >> 8) & 0xFF) == 0;
+  uint32_t var[6], sleep;
+  (void)party_variant(base, key, var, sleep);
+  // hp is no input of the embedding (network.h:153-160): a non-zero one makes the LIST kernel embed the record -- a Pokemon that has
+  // fainted at the root included -- and a zero one makes it zero the block (an empty team slot)
+  var[4] = empty ? 0u : (var[4] & 0xFFFFu) | (1u << 16);
+  work[v] = PartyWork{v, {var[0], var[1], var[2], var[3], var[4], var[5]}, sleep};
+  if (key == 0) {
+    uint32_t c[PARTY_IDENT_WORDS];
+    party_identity(base, c);
+#pragma unroll
+    for (uint32_t k = 0; k < PARTY_IDENT_WORDS; ++k) ident[(size_t)poke * PARTY_IDENT_WORDS + k] = empty ? PARTY_IDENT_EMPTY : c[k];
+  }
+}
+
+// The lookup: a wave takes PL_SIDES sides of the batch.  Lane 5 g + s (< 5 PL_SIDES) decides bench slot s of side g -- order bytes,
+// sleep turns and root index in one round trip, the slot's Pokemon and the table's identity in a second -- and then the whole wave
+// writes each side's five blocks, which lie back to back in the embedding row, as ONE run of 5 (1 + p_out) floats: every store
+// instruction covers 256 contiguous bytes (dword stores: a block starts on a 16-byte boundary only when (1 + p_out) % 4 == 0 and
+// the row does, so a wider store would need a form per alignment, and 256-byte runs of dword stores already reach the store rate).
+constexpr int PL_SIDES = 8;
+constexpr uint32_t PL_ZERO = 0xFFFFFFFFu, PL_MISS = 0xFFFFFFFEu, PL_SKIP = 0xFFFFFFFDu;
+struct PartyLookupArgs {
+  int emb_dim, side_dim, a_out, p_out;
+  const uint8_t *battles, *durations;
+  uint32_t n;
+  float *emb;
+  const float *rows;     // the table's pseudo-leaf embedding rows
+  const uint32_t *ident; // roots x 12 x PARTY_IDENT_WORDS
+  const uint32_t *root_of; // nullable: all 0
+  uint32_t n_roots;
+  PartyWork *work;
+  uint32_t *counters; // [0] work-list length = misses, [1] leaves whose root_of entry is out of range
+};
+__global__ __launch_bounds__(256) void k_party_lookup(PartyLookupArgs a) {
+  const uint32_t lane = threadIdx.x & 63, wave = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const uint32_t side0 = wave * PL_SIDES, n_sides = a.n * 2;
+  if (side0 >= n_sides) return; // (wave-uniform)
+  const uint32_t B = 1 + (uint32_t)a.p_out;
+  const uint32_t sg = lane / 5, slot = lane - sg * 5, pos = slot + 1;
+  const bool mine = lane < 5 * PL_SIDES && side0 + sg < n_sides;
+  const uint32_t S = mine ? side0 + sg : side0; // (clamped: the loads stay unconditional)
+  const uint32_t leaf = S >> 1, side = S & 1;
+  const uint32_t *sb = (const uint32_t *)a.battles + (size_t)leaf * 96 + side * 46;
+  const uint2 ow = *(const uint2 *)(sb + 44);
+  const uint32_t dur = ((const uint32_t *)a.durations)[(size_t)leaf * 2 + side];
+  const uint32_t root = a.root_of ? a.root_of[leaf] : 0;
+  uint32_t id = pos < 4 ? (ow.x >> (8 * pos)) & 0xFF : (ow.y >> (8 * (pos - 4))) & 0xFF;
+  if (id > 6) id = 0; // (no such team slot: empty, as the plain pass's selection leaves it)
+  const bool bad_root = root >= a.n_roots; // counted, never followed: the slot is embedded like any other miss
+  const uint32_t idc = id ? id - 1 : 0, rootc = bad_root ? 0 : root;
+  const uint2 *pp = (const uint2 *)(sb + 6 * idc);
+  const uint2 *tp = (const uint2 *)(a.ident + ((size_t)rootc * 12 + side * 6 + idc) * PARTY_IDENT_WORDS);
+  const uint2 p0 = pp[0], p1 = pp[1], p2 = pp[2], t0 = tp[0], t1 = tp[1], t2 = tp[2];
+  const uint32_t pk[6] = {id ? p0.x : 0, id ? p0.y : 0, id ? p1.x : 0, id ? p1.y : 0, id ? p2.x : 0, id ? p2.y : 0};
+  const uint32_t hp = pk[4] >> 16, sleep = (dur >> (3 * pos)) & 7;
+  uint32_t src = PL_SKIP; // float offset of the row's block (hp cell first) in the table, or what to do instead
+  float hpr = 0.0f;
+  if (mine) {
+    if (hp == 0) src = PL_ZERO; // empty or fainted: zero block, hp cell included (network.h:153-160)
+    else {
+      hpr = (float)hp / (float)(pk[0] & 0xFFFF);
+      uint32_t c[PARTY_IDENT_WORDS];
+      party_identity(pk, c);
+      const bool same = !bad_root && c[0] == t0.x && c[1] == t0.y && c[2] == t1.x && c[3] == t1.y && c[4] == t2.x && c[5] == t2.y;
+      const uint32_t key = party_key(pk, sleep), q = key % 10;
+      src = same ? (rootc * PT_LEAVES + (side * 6 + idc) * (PARTY_KEYS / 10) + key / 10) * (uint32_t)a.emb_dim + (q / 5) * (uint32_t)a.side_dim +
+                       (1 + (uint32_t)a.a_out) + (q % 5) * B
+                 : PL_MISS;
+    }
+    if (bad_root && lane % 10 == 0) atomicAdd(a.counters + 1, 1u); // (once per leaf: slot 0 of side 0)
+  }
+  const bool miss = src == PL_MISS;
+  const uint64_t mm = __ballot(miss);
+  if (mm) { // rare: one atomic per wave that has misses
+    uint32_t at = 0;
+    if (lane == 0) at = atomicAdd(a.counters, (uint32_t)__popcll(mm));
+    at = __shfl(at, 0, 64);
+    if (miss) a.work[at + (uint32_t)__popcll(mm & ((1ull << lane) - 1))] = PartyWork{leaf * 10 + side * 5 + slot, {pk[0], pk[1], pk[2], pk[3], pk[4], pk[5]}, sleep};
+  }
+  const uint32_t run = 5 * B;
+  for (uint32_t g = 0; g < (uint32_t)PL_SIDES && side0 + g < n_sides; ++g) { // (wave-uniform bounds: every lane takes part in the shuffles)
+    const uint32_t Sg = side0 + g;
+    float *dst = a.emb + (size_t)(Sg >> 1) * a.emb_dim + (Sg & 1) * a.side_dim + (1 + a.a_out);
+    for (uint32_t j0 = 0; j0 < run; j0 += 64) {
+      const uint32_t j = j0 + lane, jc = j < run ? j : run - 1;
+      const uint32_t sl = (jc >= B) + (jc >= 2 * B) + (jc >= 3 * B) + (jc >= 4 * B), o = jc - sl * B;
+      const uint32_t s = __shfl(src, g * 5 + sl, 64);
+      const float h = __shfl(hpr, g * 5 + sl, 64);
+      if (j < run) {
+        if (s == PL_ZERO) dst[j] = 0.0f;
+        else if (o == 0) dst[j] = h; // (a miss's hp cell too: the LIST kernel writes the same value again)
+        else if (s != PL_MISS) dst[j] = a.rows[s + o];
+      }
+    }
+  }
+}
+
 // ---- K3: main net on fp32 MFMA ------------------------------------------------------------------
 constexpr int MN_BLOCK = 256; // 4 waves
 constexpr int MAXH = 256;
@@ -2440,6 +2557,8 @@ struct oakgpu_net {
   bool pair_safe;    // every main-net layer passes pair_layer_ok (rows keep fp32 accuracy as scaled fp16 pairs, no dwarfed column): k_mainnet_pair may run
   bool split_safe;   // no main-net weight above 2^20 in magnitude: what a flushed low bf16 part loses cannot be amplified back (else fp32 MFMA only)
   bool embed_safe;   // ... and none in the embedding nets' second layers either, which also pass pair_layer_ok: the row kernels' bf16 triples (first layer's dense part) and scaled fp16 pairs (second layer) are safe (else k_embed_lds: fp32 MFMA)
+  uint64_t serial = next_serial(); // tells a network from an earlier one freed at the same address (oakgpu_party_table)
+  static uint64_t next_serial() { static std::atomic<uint64_t> n{0}; return ++n; }
 };
 
 namespace {
@@ -3189,6 +3308,22 @@ int oakgpu_leaf_set_lds_limits(void) { // per DEVICE (hipFuncSetAttribute applie
 // The kernel each embedding pass takes (OAKGPU_EMBED_FORM_*, 0: pass switched off): what leaf_eval_impl launches by and
 // oakgpu_leaf_embed_forms reports.
 struct EmbedRoute { int party, actives; };
+
+// The per-search bench-slot table (include/oakgpu.h: oakgpu_party_table_*; kernels: k_party_variants, k_party_lookup)
+struct oakgpu_party_table {
+  oakgpu_net *net;
+  uint64_t net_serial;
+  int device;
+  int p_out;
+  uint32_t max_roots, n_roots = 0; // n_roots: what the last fill stored (0: never filled)
+  float *rows = nullptr;           // max_roots x PT_LEAVES pseudo-leaf embedding rows
+  uint32_t *ident = nullptr;       // max_roots x 12 x PARTY_IDENT_WORDS
+  oak::PartyWork *work = nullptr;  // the fill's records: max_roots x 2880
+  uint32_t *work_count = nullptr;
+  uint8_t *roots = nullptr;        // staging of the host-pointer fill: max_roots x 384
+  hipEvent_t filled{};             // recorded behind every fill, on the stream it ran on
+  void *filled_on = nullptr;
+};
 static EmbedRoute embed_route(oakgpu_ctx *ctx, const oakgpu_net *net) {
   const oak::NetDev &D = net->dev;
   // The row kernels (k_embed_prows / k_embed_arows) take embedding nets up to 128 hidden channels, party outputs up to 64
@@ -3209,7 +3344,8 @@ static EmbedRoute embed_route(oakgpu_ctx *ctx, const oakgpu_net *net) {
 
 static int leaf_eval_impl(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battles, const uint8_t *durations, uint32_t n,
                           float *values, float *embedding_out, const oak::PolicyArgs *pol, uint32_t *slot_tags = nullptr,
-                          uint8_t *q_embedding = nullptr, int32_t *value_acc = nullptr) {
+                          uint8_t *q_embedding = nullptr, int32_t *value_acc = nullptr, oakgpu_party_table *table = nullptr,
+                          const uint32_t *root_of = nullptr) {
   if (!ctx || !net) return oakgpu_fail_msg("oakgpu_leaf_eval_dev: null ctx/net");
   if (n == 0) return 0;
   if (!battles || !durations || !values) return oakgpu_fail_msg("oakgpu_leaf_eval_dev: null required pointer");
@@ -3240,23 +3376,42 @@ static int leaf_eval_impl(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battl
     hipLaunchKernelGGL(oak::k_party_tags, dim3((n * 10 + 256 * oak::TAG_R - 1) / (256 * oak::TAG_R)), dim3(256), 0, stream, D, battles, durations, n, emb, slot_tags, work, count);
     tp.work = work;
     tp.work_count = count;
+  } else if (table && route.party) { // table party-slot pass: row copies first, then only the slots the table does not hold (work list)
+    uint8_t *ws = (uint8_t *)oakgpu_ctx_workspace(ctx, 2, (size_t)n * 10 * sizeof(oak::PartyWork) + 16);
+    if (!ws) return -1;
+    uint32_t *count = (uint32_t *)ws; // [0] misses, [1] leaves with a root_of entry out of range (oakgpu_party_table_last_misses)
+    oak::PartyWork *work = (oak::PartyWork *)(ws + 16);
+    if (table->filled_on && table->filled_on != (void *)stream) { // filled on another context's stream: its fill comes first
+      hipError_t we = hipStreamWaitEvent(stream, table->filled, 0);
+      if (we != hipSuccess) return oakgpu_fail_hip((int)we, "hipStreamWaitEvent(party table fill)");
+    }
+    hipError_t me = hipMemsetAsync(count, 0, 8, stream);
+    if (me != hipSuccess) return oakgpu_fail_hip((int)me, "hipMemsetAsync(work count)");
+    if (tev) (void)hipEventRecord(tev[0], stream);
+    oak::PartyLookupArgs la{D.emb_dim, D.side_dim, D.a_out, D.p_out, battles, durations, n, emb, table->rows, table->ident, root_of, table->n_roots, work, count};
+    const uint32_t waves = (n * 2 + oak::PL_SIDES - 1) / oak::PL_SIDES;
+    hipLaunchKernelGGL(oak::k_party_lookup, dim3((waves + 3) / 4), dim3(256), 0, stream, la);
+    oakgpu_ctx_set_ws2_owner(ctx, table);
+    tp.work = work;
+    tp.work_count = count;
   } else if (tev) (void)hipEventRecord(tev[0], stream);
+  const bool list = tp.work != nullptr; // the party pass runs its work-list form
   const uint32_t nmt_p = (n * 10 + oak::ER_ITEMS - 1) / oak::ER_ITEMS, wg_p0 = (nmt_p + oak::PR_WAVES - 1) / oak::PR_WAVES;
-  const uint32_t wg_p = slot_tags ? 256u : (wg_p0 < 256 ? wg_p0 : 256); // (a work list's length is only known on the device)
+  const uint32_t wg_p = list ? 256u : (wg_p0 < 256 ? wg_p0 : 256); // (a work list's length is only known on the device)
   const uint32_t nmt_a = (n * 2 + oak::ER_ITEMS - 1) / oak::ER_ITEMS, wg_a0 = (nmt_a + oak::AR_WAVES - 1) / oak::AR_WAVES, wg_a = wg_a0 < 256 ? wg_a0 : 256;
   const size_t ar_lds = oak::ar_bytes((D.a_out + 31) / 32);
   if (route.party == OAKGPU_EMBED_FORM_FUSED) {
     const size_t lds = oak::PR_BYTES > ar_lds ? oak::PR_BYTES : ar_lds;
-    if (slot_tags) hipLaunchKernelGGL(oak::k_embed_both<true>, dim3(wg_p + wg_a), dim3(oak::PR_BLOCK), lds, stream, tp, tact, wg_p);
+    if (list) hipLaunchKernelGGL(oak::k_embed_both<true>, dim3(wg_p + wg_a), dim3(oak::PR_BLOCK), lds, stream, tp, tact, wg_p);
     else hipLaunchKernelGGL(oak::k_embed_both<false>, dim3(wg_p + wg_a), dim3(oak::PR_BLOCK), lds, stream, tp, tact, wg_p);
   } else {
     if (route.party) {
       const bool prow = route.party == OAKGPU_EMBED_FORM_ROWS;
       const uint32_t ntiles = (n * 10u + oak::ET - 1) / oak::ET, grid = ntiles < 256 ? ntiles : 256;
       // (the work list goes through the same kernel as the plain pass, so that cached and plain embeddings are bit-identical)
-      if (prow && slot_tags) hipLaunchKernelGGL(oak::k_embed_prows<true>, dim3(wg_p), dim3(oak::PR_BLOCK), oak::PR_BYTES, stream, tp);
+      if (prow && list) hipLaunchKernelGGL(oak::k_embed_prows<true>, dim3(wg_p), dim3(oak::PR_BLOCK), oak::PR_BYTES, stream, tp);
       else if (prow) hipLaunchKernelGGL(oak::k_embed_prows<false>, dim3(wg_p), dim3(oak::PR_BLOCK), oak::PR_BYTES, stream, tp);
-      else if (slot_tags) hipLaunchKernelGGL((oak::k_embed_lds<false, true>), dim3(grid), dim3(oak::EL_BLOCK), oak::ELayout<false>::BYTES, stream, tp);
+      else if (list) hipLaunchKernelGGL((oak::k_embed_lds<false, true>), dim3(grid), dim3(oak::EL_BLOCK), oak::ELayout<false>::BYTES, stream, tp);
       else hipLaunchKernelGGL(oak::k_embed_lds<false>, dim3(grid), dim3(oak::EL_BLOCK), oak::ELayout<false>::BYTES, stream, tp);
     }
     if (tev) (void)hipEventRecord(tev[1], stream);
@@ -3394,12 +3549,199 @@ int oakgpu_leaf_eval_policy_dev(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t 
   return leaf_eval_impl(ctx, net, battles, durations, n, values, nullptr, &pa);
 }
 
+// ---- the per-search bench-slot table ----
+void oakgpu_party_table_destroy(oakgpu_ctx *ctx, oakgpu_party_table *t) {
+  if (!t) return;
+  if (ctx) (void)oakgpu_ctx_enter(ctx); else (void)hipSetDevice(t->device);
+  if (ctx && oakgpu_ctx_ws2_owner(ctx) == (const void *)t) oakgpu_ctx_set_ws2_owner(ctx, nullptr);
+  (void)hipDeviceSynchronize(); // (any context's stream may still read the rows)
+  if (t->rows) (void)hipFree(t->rows);
+  if (t->ident) (void)hipFree(t->ident);
+  if (t->work) (void)hipFree(t->work);
+  if (t->work_count) (void)hipFree(t->work_count);
+  if (t->roots) (void)hipFree(t->roots);
+  if (t->filled) (void)hipEventDestroy(t->filled);
+  delete t;
+}
+
+int oakgpu_party_table_create(oakgpu_ctx *ctx, oakgpu_net *net, uint32_t max_roots, oakgpu_party_table **out) {
+  if (!ctx || !net || !out) return oakgpu_fail_msg("oakgpu_party_table_create: null pointer");
+  *out = nullptr;
+  if (net->device != oakgpu_ctx_device(ctx)) return oakgpu_fail_msg("oakgpu_party_table_create: the network was loaded on another device than the context's");
+  // (row offsets are 32-bit float indices, in the table as in the batch embedding)
+  if (max_roots == 0 || (uint64_t)max_roots * oak::PT_LEAVES * (uint64_t)net->dev.emb_dim >= (1ull << 31))
+    return oakgpu_fail_msg("oakgpu_party_table_create: max_roots must be at least 1 and the table below 2^31 floats");
+  if (int rc = oakgpu_ctx_enter(ctx)) return rc;
+  oakgpu_party_table *t = new oakgpu_party_table();
+  t->net = net;
+  t->net_serial = net->serial;
+  t->p_out = net->dev.p_out;
+  t->device = net->device;
+  t->max_roots = max_roots;
+  const size_t variants = (size_t)max_roots * 12 * oak::PARTY_KEYS;
+  hipError_t e = hipMalloc((void **)&t->rows, (size_t)max_roots * oak::PT_LEAVES * net->dev.emb_dim * 4);
+  if (e == hipSuccess) e = hipMalloc((void **)&t->ident, (size_t)max_roots * 12 * oak::PARTY_IDENT_WORDS * 4);
+  if (e == hipSuccess) e = hipMalloc((void **)&t->work, variants * sizeof(oak::PartyWork));
+  if (e == hipSuccess) e = hipMalloc((void **)&t->work_count, 16);
+  if (e == hipSuccess) e = hipMalloc((void **)&t->roots, (size_t)max_roots * 384);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&t->filled, hipEventDisableTiming);
+  if (e != hipSuccess) { oakgpu_party_table_destroy(ctx, t); return oakgpu_fail_hip((int)e, "oakgpu_party_table_create"); }
+  *out = t;
+  return 0;
+}
+
+static int party_table_check(const char *who, oakgpu_ctx *ctx, const oakgpu_net *net, const oakgpu_party_table *t) {
+  if (t->device != oakgpu_ctx_device(ctx)) return oakgpu_fail_msg((std::string(who) + ": the table was made on another device than the context's").c_str());
+  if (net && (t->net != net || t->net_serial != net->serial)) return oakgpu_fail_msg((std::string(who) + ": the table was made for another network").c_str());
+  return 0;
+}
+
+int oakgpu_party_table_fill_dev(oakgpu_ctx *ctx, oakgpu_party_table *t, const uint8_t *root_battles, uint32_t n_roots) {
+  if (!ctx || !t || !root_battles) return oakgpu_fail_msg("oakgpu_party_table_fill_dev: null pointer");
+  if (int rc = party_table_check("oakgpu_party_table_fill_dev", ctx, nullptr, t)) return rc;
+  if (n_roots == 0 || n_roots > t->max_roots) return oakgpu_fail_msg("oakgpu_party_table_fill_dev: n_roots must be in 1..max_roots of the table");
+  if (int rc = oakgpu_ctx_enter(ctx)) return rc;
+  hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(ctx);
+  oakgpu_net *net = t->net;
+  const oak::NetDev &D = net->dev;
+  const uint32_t variants = n_roots * 12 * oak::PARTY_KEYS;
+  hipLaunchKernelGGL(oak::k_party_variants, dim3((variants + 255) / 256), dim3(256), 0, stream, root_battles, n_roots, t->work, t->ident, t->work_count);
+  // the variants through the party kernel's work-list form, in the form the plain call takes for this network and context
+  oak::EmbedTileArgs tp{D, nullptr, nullptr, n_roots * oak::PT_LEAVES, t->rows, 0, t->work, t->work_count};
+  if (net->discrete) tp.net.activation = 1; // (as leaf_eval_impl sets it for the party slots of a quantized network)
+  const EmbedRoute route = embed_route(ctx, net);
+  const uint32_t nmt = (variants + oak::ER_ITEMS - 1) / oak::ER_ITEMS, wg0 = (nmt + oak::PR_WAVES - 1) / oak::PR_WAVES, wg = wg0 < 256 ? wg0 : 256;
+  if (route.party == OAKGPU_EMBED_FORM_FUSED) { // k_embed_both with no workgroup for the actives' pass
+    oak::EmbedTileArgs none{D, nullptr, nullptr, 0, t->rows, 1, nullptr, nullptr};
+    const size_t ar_lds = oak::ar_bytes((D.a_out + 31) / 32), lds = oak::PR_BYTES > ar_lds ? oak::PR_BYTES : ar_lds;
+    hipLaunchKernelGGL(oak::k_embed_both<true>, dim3(wg), dim3(oak::PR_BLOCK), lds, stream, tp, none, wg);
+  } else if (route.party == OAKGPU_EMBED_FORM_ROWS) {
+    hipLaunchKernelGGL(oak::k_embed_prows<true>, dim3(wg), dim3(oak::PR_BLOCK), oak::PR_BYTES, stream, tp);
+  } else if (route.party == OAKGPU_EMBED_FORM_TILE) {
+    const uint32_t ntiles = (variants + oak::ET - 1) / oak::ET, grid = ntiles < 256 ? ntiles : 256;
+    hipLaunchKernelGGL((oak::k_embed_lds<false, true>), dim3(grid), dim3(oak::EL_BLOCK), oak::ELayout<false>::BYTES, stream, tp);
+  } // (0: the party pass is switched off by the diagnostic environment, and the table calls skip the lookup as well)
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipEventRecord(t->filled, stream);
+  if (e != hipSuccess) return oakgpu_fail_hip((int)e, "oakgpu_party_table_fill_dev");
+  t->n_roots = n_roots;
+  t->filled_on = (void *)stream;
+  return 0;
+}
+
+int oakgpu_party_table_fill(oakgpu_ctx *ctx, oakgpu_party_table *t, const uint8_t *root_battles, uint32_t n_roots) {
+  if (!ctx || !t || !root_battles) return oakgpu_fail_msg("oakgpu_party_table_fill: null pointer");
+  if (int rc = party_table_check("oakgpu_party_table_fill", ctx, nullptr, t)) return rc;
+  if (n_roots == 0 || n_roots > t->max_roots) return oakgpu_fail_msg("oakgpu_party_table_fill: n_roots must be in 1..max_roots of the table");
+  if (int rc = oakgpu_ctx_enter(ctx)) return rc;
+  hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(ctx);
+  hipError_t e = hipMemcpyAsync(t->roots, root_battles, (size_t)n_roots * 384, hipMemcpyHostToDevice, stream);
+  if (e != hipSuccess) return oakgpu_fail_hip((int)e, "oakgpu_party_table_fill: copy of the roots");
+  const int rc = oakgpu_party_table_fill_dev(ctx, t, t->roots, n_roots);
+  e = hipStreamSynchronize(stream); // the caller's buffer is free again, and the table complete for every stream
+  if (rc) return rc;
+  if (e != hipSuccess) return oakgpu_fail_hip((int)e, "oakgpu_party_table_fill");
+  t->filled_on = nullptr;
+  return 0;
+}
+
+int oakgpu_party_table_is_for(const oakgpu_party_table *t, const oakgpu_net *net) { return t && net && t->net == net && t->net_serial == net->serial; }
+
+static int party_table_eval_check(const char *who, oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_party_table *t) {
+  if (!ctx || !net || !t) return oakgpu_fail_msg((std::string(who) + ": null ctx/net/table").c_str());
+  if (int rc = party_table_check(who, ctx, net, t)) return rc;
+  if (t->n_roots == 0) return oakgpu_fail_msg((std::string(who) + ": the table has not been filled (oakgpu_party_table_fill*)").c_str());
+  return 0;
+}
+
+int oakgpu_leaf_eval_table_dev(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_party_table *table, const uint32_t *root_of, const uint8_t *battles,
+                               const uint8_t *durations, uint32_t n, float *values, float *embedding_out) {
+  if (int rc = party_table_eval_check("oakgpu_leaf_eval_table_dev", ctx, net, table)) return rc;
+  return leaf_eval_impl(ctx, net, battles, durations, n, values, embedding_out, nullptr, nullptr, nullptr, nullptr, table, root_of);
+}
+
+int oakgpu_leaf_eval_policy_table_dev(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_party_table *table, const uint32_t *root_of, const uint8_t *battles,
+                                      const uint8_t *durations, uint32_t n, const uint8_t *p1_choices, const uint8_t *p1_counts,
+                                      const uint8_t *p2_choices, const uint8_t *p2_counts, float *values, float *p1_logits, float *p2_logits) {
+  if (int rc = party_table_eval_check("oakgpu_leaf_eval_policy_table_dev", ctx, net, table)) return rc;
+  if (!p1_choices || !p1_counts || !p2_choices || !p2_counts || !p1_logits || !p2_logits)
+    return oakgpu_fail_msg("oakgpu_leaf_eval_policy_table_dev: null pointer");
+  oak::PolicyArgs pa{};
+  pa.battles = battles;
+  pa.choices[0] = p1_choices; pa.choices[1] = p2_choices;
+  pa.counts[0] = p1_counts; pa.counts[1] = p2_counts;
+  pa.logits[0] = p1_logits; pa.logits[1] = p2_logits;
+  pa.n = n;
+  return leaf_eval_impl(ctx, net, battles, durations, n, values, nullptr, &pa, nullptr, nullptr, nullptr, table, root_of);
+}
+
+int oakgpu_party_table_last_misses(oakgpu_ctx *ctx, oakgpu_party_table *t, uint32_t *slots) { // diagnostic: synchronises the stream
+  if (!ctx || !t || !slots) return oakgpu_fail_msg("oakgpu_party_table_last_misses: null pointer");
+  if (int rc = party_table_check("oakgpu_party_table_last_misses", ctx, nullptr, t)) return rc;
+  if (int rc = oakgpu_ctx_enter(ctx)) return rc;
+  hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(ctx);
+  if (oakgpu_ctx_ws2_owner(ctx) != (const void *)t)
+    return oakgpu_fail_msg("oakgpu_party_table_last_misses: the context's last work-list call was not an eval through this table");
+  const uint32_t *count = (const uint32_t *)oakgpu_ctx_workspace(ctx, 2, 16);
+  if (!count) return -1;
+  oakgpu_ctx_set_ws2_owner(ctx, t); // (reading changes nothing)
+  uint32_t w[2] = {0, 0};
+  hipError_t e = hipMemcpyAsync(w, count, 8, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return oakgpu_fail_hip((int)e, "oakgpu_party_table_last_misses");
+  *slots = w[0];
+  if (w[1]) return oakgpu_fail_msg(("oakgpu_party_table_last_misses: " + std::to_string(w[1]) + " leaves of the last call had a root_of entry beyond the table's " +
+                                    std::to_string(t->n_roots) + " filled roots (their slots were embedded as misses)").c_str());
+  return 0;
+}
+
+int oakgpu_party_table_rows(oakgpu_ctx *ctx, oakgpu_party_table *t, uint32_t root, int side, int pokemon, float *rows) {
+  if (!ctx || !t || !rows) return oakgpu_fail_msg("oakgpu_party_table_rows: null pointer");
+  if (int rc = party_table_check("oakgpu_party_table_rows", ctx, nullptr, t)) return rc;
+  if (root >= t->n_roots || side < 0 || side > 1 || pokemon < 0 || pokemon > 5)
+    return oakgpu_fail_msg("oakgpu_party_table_rows: root beyond the filled roots, or side / pokemon out of range");
+  if (int rc = oakgpu_ctx_enter(ctx)) return rc;
+  hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(ctx);
+  const oak::NetDev &D = t->net->dev;
+  const uint32_t leaves = oak::PARTY_KEYS / 10; // the Pokemon's pseudo-leaves lie back to back
+  std::vector<float> img((size_t)leaves * D.emb_dim);
+  const float *src = t->rows + ((size_t)root * oak::PT_LEAVES + (size_t)(side * 6 + pokemon) * leaves) * D.emb_dim;
+  hipError_t e = hipSuccess;
+  if (t->filled_on && t->filled_on != (void *)stream) e = hipStreamWaitEvent(stream, t->filled, 0);
+  if (e == hipSuccess) e = hipMemcpyAsync(img.data(), src, img.size() * 4, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return oakgpu_fail_hip((int)e, "oakgpu_party_table_rows");
+  for (uint32_t key = 0; key < oak::PARTY_KEYS; ++key) {
+    const uint32_t q = key % 10;
+    const float *row = img.data() + (size_t)(key / 10) * D.emb_dim + (q / 5) * D.side_dim + (1 + D.a_out) + (q % 5) * (1 + D.p_out) + 1;
+    memcpy(rows + (size_t)key * D.p_out, row, (size_t)D.p_out * 4);
+  }
+  return 0;
+}
+
+int oakgpu_party_table_width(const oakgpu_party_table *t) { return t ? t->p_out : -1; }
+
+uint8_t oakgpu_party_key(const uint8_t pokemon[24], uint8_t sleep) {
+  uint32_t pk[6];
+  memcpy(pk, pokemon, 24);
+  return (uint8_t)oak::party_key(pk, sleep);
+}
+
+int oakgpu_party_variant(const uint8_t base[24], uint8_t key, uint8_t out[24], uint8_t *sleep) {
+  uint32_t b[6], v[6], s = 0;
+  memcpy(b, base, 24);
+  const bool ok = oak::party_variant(b, key, v, s);
+  if (out) memcpy(out, v, 24);
+  if (sleep) *sleep = (uint8_t)s;
+  return ok ? 0 : 1;
+}
+
 #define TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return oakgpu_fail_hip((int)e_, #x); } while (0)
 #define STAGE(var, bytes) void *var = hc.get(bytes); if (!var) return -1
 
-int oakgpu_leaf_eval(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battles, const uint8_t *durations, uint32_t n,
-                     float *values, float *embedding_out) {
-  if (!ctx || !net) return oakgpu_fail_msg("oakgpu_leaf_eval: null ctx/net");
+// (table != NULL: the host-pointer form of oakgpu_leaf_eval_table_dev; root_of is a host array then as well)
+static int leaf_eval_host(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_party_table *table, const uint32_t *root_of, const uint8_t *battles,
+                          const uint8_t *durations, uint32_t n, float *values, float *embedding_out) {
   if (n == 0) return 0;
   if (!battles || !durations || !values) return oakgpu_fail_msg("oakgpu_leaf_eval: null required pointer");
   if (int rc = oakgpu_ctx_enter(ctx)) return rc;
@@ -3408,21 +3750,34 @@ int oakgpu_leaf_eval(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battles, c
   STAGE(db, (size_t)n * 384);
   STAGE(dd, (size_t)n * 8);
   STAGE(dv, (size_t)n * 4);
-  void *de = nullptr;
+  void *de = nullptr, *dr = nullptr;
   if (embedding_out) { de = hc.get((size_t)n * net->dev.emb_dim * 4); if (!de) return -1; }
+  if (table && root_of) { dr = hc.get((size_t)n * 4); if (!dr) return -1; TRY(hipMemcpyAsync(dr, root_of, (size_t)n * 4, hipMemcpyHostToDevice, stream)); }
   TRY(hipMemcpyAsync(db, battles, (size_t)n * 384, hipMemcpyHostToDevice, stream));
   TRY(hipMemcpyAsync(dd, durations, (size_t)n * 8, hipMemcpyHostToDevice, stream));
-  if (int rc = oakgpu_leaf_eval_dev(ctx, net, (const uint8_t *)db, (const uint8_t *)dd, n, (float *)dv, (float *)de)) return rc;
+  if (int rc = table ? oakgpu_leaf_eval_table_dev(ctx, net, table, (const uint32_t *)dr, (const uint8_t *)db, (const uint8_t *)dd, n, (float *)dv, (float *)de)
+                     : oakgpu_leaf_eval_dev(ctx, net, (const uint8_t *)db, (const uint8_t *)dd, n, (float *)dv, (float *)de)) return rc;
   TRY(hipMemcpyAsync(values, dv, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
   if (embedding_out) TRY(hipMemcpyAsync(embedding_out, de, (size_t)n * net->dev.emb_dim * 4, hipMemcpyDeviceToHost, stream));
   TRY(hipStreamSynchronize(stream));
   return 0;
 }
 
-int oakgpu_leaf_eval_policy(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battles, const uint8_t *durations, uint32_t n,
-                            const uint8_t *p1_choices, const uint8_t *p1_counts, const uint8_t *p2_choices, const uint8_t *p2_counts,
-                            float *values, float *p1_logits, float *p2_logits) {
-  if (!ctx || !net) return oakgpu_fail_msg("oakgpu_leaf_eval_policy: null ctx/net");
+int oakgpu_leaf_eval(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battles, const uint8_t *durations, uint32_t n,
+                     float *values, float *embedding_out) {
+  if (!ctx || !net) return oakgpu_fail_msg("oakgpu_leaf_eval: null ctx/net");
+  return leaf_eval_host(ctx, net, nullptr, nullptr, battles, durations, n, values, embedding_out);
+}
+
+int oakgpu_leaf_eval_table(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_party_table *table, const uint32_t *root_of, const uint8_t *battles,
+                           const uint8_t *durations, uint32_t n, float *values, float *embedding_out) {
+  if (int rc = party_table_eval_check("oakgpu_leaf_eval_table", ctx, net, table)) return rc;
+  return leaf_eval_host(ctx, net, table, root_of, battles, durations, n, values, embedding_out);
+}
+
+static int leaf_eval_policy_host(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_party_table *table, const uint32_t *root_of, const uint8_t *battles,
+                                 const uint8_t *durations, uint32_t n, const uint8_t *p1_choices, const uint8_t *p1_counts, const uint8_t *p2_choices,
+                                 const uint8_t *p2_counts, float *values, float *p1_logits, float *p2_logits) {
   if (n == 0) return 0;
   if (!battles || !durations || !values || !p1_choices || !p1_counts || !p2_choices || !p2_counts || !p1_logits || !p2_logits)
     return oakgpu_fail_msg("oakgpu_leaf_eval_policy: null required pointer");
@@ -3432,19 +3787,37 @@ int oakgpu_leaf_eval_policy(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *bat
   STAGE(db, (size_t)n * 384); STAGE(dd, (size_t)n * 8); STAGE(dv, (size_t)n * 4);
   STAGE(dc1, (size_t)n * 9); STAGE(dc2, (size_t)n * 9); STAGE(dn1, n); STAGE(dn2, n);
   STAGE(dl1, (size_t)n * 36); STAGE(dl2, (size_t)n * 36);
+  void *dr = nullptr;
+  if (table && root_of) { dr = hc.get((size_t)n * 4); if (!dr) return -1; TRY(hipMemcpyAsync(dr, root_of, (size_t)n * 4, hipMemcpyHostToDevice, stream)); }
   TRY(hipMemcpyAsync(db, battles, (size_t)n * 384, hipMemcpyHostToDevice, stream));
   TRY(hipMemcpyAsync(dd, durations, (size_t)n * 8, hipMemcpyHostToDevice, stream));
   TRY(hipMemcpyAsync(dc1, p1_choices, (size_t)n * 9, hipMemcpyHostToDevice, stream));
   TRY(hipMemcpyAsync(dc2, p2_choices, (size_t)n * 9, hipMemcpyHostToDevice, stream));
   TRY(hipMemcpyAsync(dn1, p1_counts, n, hipMemcpyHostToDevice, stream));
   TRY(hipMemcpyAsync(dn2, p2_counts, n, hipMemcpyHostToDevice, stream));
-  if (int rc = oakgpu_leaf_eval_policy_dev(ctx, net, (const uint8_t *)db, (const uint8_t *)dd, n, (const uint8_t *)dc1, (const uint8_t *)dn1,
-                                           (const uint8_t *)dc2, (const uint8_t *)dn2, (float *)dv, (float *)dl1, (float *)dl2)) return rc;
+  if (int rc = table ? oakgpu_leaf_eval_policy_table_dev(ctx, net, table, (const uint32_t *)dr, (const uint8_t *)db, (const uint8_t *)dd, n, (const uint8_t *)dc1,
+                                                         (const uint8_t *)dn1, (const uint8_t *)dc2, (const uint8_t *)dn2, (float *)dv, (float *)dl1, (float *)dl2)
+                     : oakgpu_leaf_eval_policy_dev(ctx, net, (const uint8_t *)db, (const uint8_t *)dd, n, (const uint8_t *)dc1, (const uint8_t *)dn1,
+                                                   (const uint8_t *)dc2, (const uint8_t *)dn2, (float *)dv, (float *)dl1, (float *)dl2)) return rc;
   TRY(hipMemcpyAsync(values, dv, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
   TRY(hipMemcpyAsync(p1_logits, dl1, (size_t)n * 36, hipMemcpyDeviceToHost, stream));
   TRY(hipMemcpyAsync(p2_logits, dl2, (size_t)n * 36, hipMemcpyDeviceToHost, stream));
   TRY(hipStreamSynchronize(stream));
   return 0;
+}
+
+int oakgpu_leaf_eval_policy(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battles, const uint8_t *durations, uint32_t n,
+                            const uint8_t *p1_choices, const uint8_t *p1_counts, const uint8_t *p2_choices, const uint8_t *p2_counts,
+                            float *values, float *p1_logits, float *p2_logits) {
+  if (!ctx || !net) return oakgpu_fail_msg("oakgpu_leaf_eval_policy: null ctx/net");
+  return leaf_eval_policy_host(ctx, net, nullptr, nullptr, battles, durations, n, p1_choices, p1_counts, p2_choices, p2_counts, values, p1_logits, p2_logits);
+}
+
+int oakgpu_leaf_eval_policy_table(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_party_table *table, const uint32_t *root_of, const uint8_t *battles,
+                                  const uint8_t *durations, uint32_t n, const uint8_t *p1_choices, const uint8_t *p1_counts, const uint8_t *p2_choices,
+                                  const uint8_t *p2_counts, float *values, float *p1_logits, float *p2_logits) {
+  if (int rc = party_table_eval_check("oakgpu_leaf_eval_policy_table", ctx, net, table)) return rc;
+  return leaf_eval_policy_host(ctx, net, table, root_of, battles, durations, n, p1_choices, p1_counts, p2_choices, p2_counts, values, p1_logits, p2_logits);
 }
 #undef TRY
 #undef STAGE

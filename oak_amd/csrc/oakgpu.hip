@@ -1641,6 +1641,9 @@ struct oakgpu_ctx {
   size_t scratch_n;
   int rounds_auto;        // 1 (default): every launch is one dispatch; 0 after oakgpu_set_regroup: the rounds it asked for
   int concurrent_hint;    // set by callers that keep several contexts busy at once (the tree search): small launches run in rounds
+  int search_party_table; // oakgpu_set_search_party_table: the tree search's network evaluations look bench slots up in a per-search table
+  uint64_t search_table_fills = 0, search_table_evals = 0; // oakgpu_search_party_table_stats
+  const void *ws2_owner = nullptr; // the party table whose eval wrote workspace 2's counters last (null: someone else did)
   int tail_below;         // > 0: a SATURATED launch parks the lanes of dry waves with fewer live lanes than this and ONE follow-up
   int tail_waves;         //      dispatch of this many waves (0 = one per CU) finishes them, a few to a wave (the tail)
   int tail_lanes;         //      lanes per wave of that dispatch that take playouts (0 = all 64)
@@ -1702,7 +1705,13 @@ static void *grow_block(oakgpu_ctx *c, oakgpu_ctx::Block &b, size_t bytes) {
   return b.p;
 }
 void **oakgpu_ctx_timing_events(oakgpu_ctx *c) { return c->timing && c->tev_valid ? (void **)c->tev : nullptr; }
-void *oakgpu_ctx_workspace(oakgpu_ctx *c, int slot, size_t bytes) { return grow_block(c, c->ws[slot % 3], bytes ? bytes : 1); }
+void *oakgpu_ctx_workspace(oakgpu_ctx *c, int slot, size_t bytes) {
+  if (slot % 3 == 2) c->ws2_owner = nullptr; // (whoever asks for the work-list block is about to write its head)
+  return grow_block(c, c->ws[slot % 3], bytes ? bytes : 1);
+}
+void oakgpu_ctx_set_ws2_owner(oakgpu_ctx *c, const void *table) { c->ws2_owner = table; }
+const void *oakgpu_ctx_ws2_owner(const oakgpu_ctx *c) { return c->ws2_owner; }
+void oakgpu_ctx_count_search_table(oakgpu_ctx *c, uint64_t fills, uint64_t evals) { c->search_table_fills += fills; c->search_table_evals += evals; }
 void oakgpu_stage_begin(oakgpu_ctx *c) { c->stage_cursor = 0; }
 void oakgpu_stage_end(oakgpu_ctx *c) { (void)hipStreamSynchronize(c->stream); }
 void *oakgpu_stage_get(oakgpu_ctx *c, size_t bytes) {
@@ -1711,6 +1720,7 @@ void *oakgpu_stage_get(oakgpu_ctx *c, size_t bytes) {
 }
 void *oakgpu_ctx_stream(const oakgpu_ctx *c) { return (void *)c->stream; }
 int oakgpu_ctx_set_concurrent_hint(oakgpu_ctx *c, int on) { const int old = c->concurrent_hint; c->concurrent_hint = on; return old; }
+int oakgpu_ctx_search_party_table(const oakgpu_ctx *c) { return c->search_party_table; }
 void *oakgpu_ctx_attachment(const oakgpu_ctx *c) { return c->attachment; }
 void oakgpu_ctx_set_attachment(oakgpu_ctx *c, void *p, void (*dtor)(void *)) {
   if (c->attachment && c->attachment_dtor) c->attachment_dtor(c->attachment);
@@ -1800,6 +1810,8 @@ int oakgpu_create(oakgpu_ctx **out, int device) {
   c->tev_valid = false;
   c->rounds_auto = 1;
   c->concurrent_hint = 0;
+  c->search_party_table = 0;
+  if (const char *env = getenv("OAKGPU_PARTY_TABLE")) c->search_party_table = atoi(env) != 0;
   if (const char *env = getenv("OAKGPU_ROUNDS_AUTO")) c->rounds_auto = atoi(env) != 0;
   {
     hipDeviceProp_t prop;
@@ -1931,6 +1943,20 @@ int oakgpu_set_spread(oakgpu_ctx *c, int lanes) {
 int oakgpu_set_standstill_skip(oakgpu_ctx *c, int on) {
   if (!c) return bad("null ctx");
   c->standstill_skip = on != 0;
+  return 0;
+}
+
+int oakgpu_set_search_party_table(oakgpu_ctx *c, int on) {
+  if (!c) return bad("null ctx");
+  const int old = c->search_party_table;
+  c->search_party_table = on != 0;
+  return old;
+}
+
+int oakgpu_search_party_table_stats(oakgpu_ctx *c, uint64_t *fills, uint64_t *evals) {
+  if (!c) return bad("null ctx");
+  if (fills) *fills = c->search_table_fills;
+  if (evals) *evals = c->search_table_evals;
   return 0;
 }
 

@@ -43,6 +43,16 @@ void oakgpu_ctx_set_attachment(oakgpu_ctx *ctx, void *p, void (*dtor)(void *));
 // do not fill the device then run in regrouping rounds, whose dispatch boundaries let the other context's small kernels in.
 // Returns the previous value.
 int oakgpu_ctx_set_concurrent_hint(oakgpu_ctx *ctx, int on);
+int oakgpu_ctx_search_party_table(const oakgpu_ctx *ctx); // oakgpu_set_search_party_table's switch
+void oakgpu_ctx_count_search_table(oakgpu_ctx *ctx, uint64_t fills, uint64_t evals); // oakgpu_search_party_table_stats' counters
+// Workspace 2's first words are the last work-list call's counters.  A table eval names its table as their owner once it has the block;
+// any later oakgpu_ctx_workspace(ctx, 2, ...) -- the cached call, the training-batch call -- clears the owner again.
+void oakgpu_ctx_set_ws2_owner(oakgpu_ctx *ctx, const void *table);
+const void *oakgpu_ctx_ws2_owner(const oakgpu_ctx *ctx);
+// leafnet.hip: whether the bench-slot table was made for this network (and not for one since freed at the same address)
+struct oakgpu_party_table;
+struct oakgpu_net;
+extern "C" int oakgpu_party_table_is_for(const oakgpu_party_table *table, const oakgpu_net *net);
 // Host threads of the tree walks started by the CALLING thread (0 = the default rule): callers that run several searches side
 // by side -- oakgpu_search_many, oakgpu_selfplay_games -- give each its share of the cores.
 void oakgpu_set_thread_search_threads(int threads);

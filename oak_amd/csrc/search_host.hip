@@ -498,7 +498,11 @@ struct Slot {
     return 0;
   }
 };
-struct SearchScratch { Slot slots[2]; };
+struct SearchScratch {
+  Slot slots[2];
+  oakgpu_party_table *table = nullptr; // oakgpu_set_search_party_table: one root's bench-slot embeddings, refilled by every search
+  ~SearchScratch() { if (table) oakgpu_party_table_destroy(nullptr, table); }
+};
 thread_local int tl_search_threads = 0; // > 0: host threads of the searches started by THIS thread (set by oakgpu_search_many's workers)
 void scratch_dtor(void *p) { delete (SearchScratch *)p; }
 } // namespace
@@ -771,6 +775,19 @@ int oakgpu_search_heap(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_heap *heap, cons
     int old[2] = {0, 0};
     ~HintGuard() { for (int q = 0; q < 2; ++q) if (c[q]) oakgpu_ctx_set_concurrent_hint(c[q], old[q]); }
   } hint_guard;
+  // The bench-slot table (off by default): filled from this search's root before the first batch -- the host-pointer fill
+  // returns with the table complete, so either slot's stream may read it -- and both network calls of launch_eval go through it.
+  oakgpu_party_table *table = nullptr;
+  if (use_net && oakgpu_ctx_search_party_table(ctx)) {
+    if (scratch->table && !oakgpu_party_table_is_for(scratch->table, net)) { // (the last search here ran another network)
+      oakgpu_party_table_destroy(ctx, scratch->table);
+      scratch->table = nullptr;
+    }
+    if (!scratch->table) RC(oakgpu_party_table_create(ctx, net, 1, &scratch->table));
+    RC(oakgpu_party_table_fill(ctx, scratch->table, battle, 1));
+    table = scratch->table;
+    oakgpu_ctx_count_search_table(ctx, 1, 0);
+  }
   for (int si = 0; si < n_slots; ++si) {
     Slot &S = slots[si];
     RC(S.allocate(ctx, si, B, pucb, emb_dim));
@@ -1051,11 +1068,15 @@ int oakgpu_search_heap(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_heap *heap, cons
     } else if (!use_net) {
       RC(oakgpu_rollout_dev(S.ctx, S.d_b, S.d_d, S.d_r, S.d_prng, nb, 1000, 0, S.d_rout, S.d_steps, S.d_values, nullptr, nullptr));
     } else if (pucb) {
-      RC(oakgpu_leaf_eval_policy_dev(S.ctx, net, S.d_b, S.d_d, nb, S.d_ch1, S.d_cnt1, S.d_ch2, S.d_cnt2, S.d_values, S.d_l1, S.d_l2));
+      if (table) oakgpu_ctx_count_search_table(ctx, 0, 1);
+      if (table) RC(oakgpu_leaf_eval_policy_table_dev(S.ctx, net, table, nullptr, S.d_b, S.d_d, nb, S.d_ch1, S.d_cnt1, S.d_ch2, S.d_cnt2, S.d_values, S.d_l1, S.d_l2));
+      else RC(oakgpu_leaf_eval_policy_dev(S.ctx, net, S.d_b, S.d_d, nb, S.d_ch1, S.d_cnt1, S.d_ch2, S.d_cnt2, S.d_values, S.d_l1, S.d_l2));
       HIPRC(hipMemcpyAsync(S.h_l1, S.d_l1, (size_t)nb * 9 * 4, hipMemcpyDeviceToHost, S.stream));
       HIPRC(hipMemcpyAsync(S.h_l2, S.d_l2, (size_t)nb * 9 * 4, hipMemcpyDeviceToHost, S.stream));
     } else {
-      RC(oakgpu_leaf_eval_dev(S.ctx, net, S.d_b, S.d_d, nb, S.d_values, S.d_emb));
+      if (table) oakgpu_ctx_count_search_table(ctx, 0, 1);
+      if (table) RC(oakgpu_leaf_eval_table_dev(S.ctx, net, table, nullptr, S.d_b, S.d_d, nb, S.d_values, S.d_emb));
+      else RC(oakgpu_leaf_eval_dev(S.ctx, net, S.d_b, S.d_d, nb, S.d_values, S.d_emb));
     }
     HIPRC(hipMemcpyAsync(S.h_values, S.d_values, (size_t)nb * 4, hipMemcpyDeviceToHost, S.stream));
     return 0;

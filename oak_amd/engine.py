@@ -9,6 +9,7 @@ through the C ABI of liboakgpu.so (include/oakgpu.h); nothing here computes on t
   Context.choices(...)   <- pkmn_gen1_battle_choices               libpkmn/pkmn.h:141-156
   Context.battle(...)    <- PKMN::battle(p1, p2, seed)             libpkmn/pkmn.h:50-57
   Network.value_inference(...) <- NN::Battle::NetworkImpl::value_inference  nn/battle/network.h:72-79
+  PartyTable(...)        <- NN::Battle::PokemonCache, filled per search    nn/battle/cache.h:18-131
 """
 import ctypes as C
 import os
@@ -36,6 +37,7 @@ class Context:
         h = C.c_void_p()
         _lib.check(self.lib.oakgpu_create(C.byref(h), device))
         self.handle = h
+        self.device = device
         self._pools = False
 
     def close(self):
@@ -76,6 +78,17 @@ class Context:
     def set_migration_window(self, window=48):
         """Donate a playout whose actives stood still for `window` turn-steps (oakgpu_set_migration_window; 0 = off)."""
         _lib.check(self.lib.oakgpu_set_migration_window(self.handle, int(window)))
+
+    def set_search_party_table(self, on=True):
+        """The tree searches of this context look bench-slot embeddings up in a table filled from the search's root (results are
+        unchanged; default off): oakgpu_set_search_party_table.  Returns the previous value."""
+        return bool(self.lib.oakgpu_set_search_party_table(self.handle, int(bool(on))))
+
+    def search_party_table_stats(self):
+        """(searches of this context that filled a bench-slot table, leaf batches they evaluated through one) since it was created."""
+        fills, evals = C.c_uint64(), C.c_uint64()
+        _lib.check(self.lib.oakgpu_search_party_table_stats(self.handle, C.byref(fills), C.byref(evals)))
+        return fills.value, evals.value
 
     def set_standstill_skip(self, on=True):
         """The queue kernel's exact fast-forward of proven frozen standstills (oakgpu_set_standstill_skip); results never change."""
@@ -253,24 +266,39 @@ class Network:
             raise _lib.OakGpuError("oakgpu_net_set_main_precision failed")
         return ("fp32", "split", "pair")[prev]
 
-    def value_inference(self, battles, durations, return_embedding=False):
+    def value_inference(self, battles, durations, return_embedding=False, table=None, root_of=None):
+        """table (a filled PartyTable of this network): the bench slots are looked up in it, leaf i in root root_of[i] (None: all
+        root 0); the results equal the plain call's."""
         battles = _u8(battles)
         n = battles.shape[0]
         durations = _u8(durations, (n, 8))
         values = np.zeros(n, dtype=np.float32)
         emb = np.zeros((n, self.shape()[0]), dtype=np.float32) if return_embedding else None
+        if table is not None:
+            ro = None if root_of is None else np.ascontiguousarray(root_of, dtype=np.uint32).reshape(n)
+            _lib.check(self.ctx.lib.oakgpu_leaf_eval_table(self.ctx.handle, self.handle, table.handle, _p(ro), _p(battles), _p(durations), n,
+                                                           _p(values), _p(emb)))
+            return (values, emb) if return_embedding else values
         _lib.check(self.ctx.lib.oakgpu_leaf_eval(self.ctx.handle, self.handle, _p(battles), _p(durations), n,
                                                  _p(values), _p(emb)))
         return (values, emb) if return_embedding else values
 
-    def value_policy_inference(self, battles, durations, p1_choices, p1_counts, p2_choices, p2_counts):
+    def value_policy_inference(self, battles, durations, p1_choices, p1_counts, p2_choices, p2_counts, table=None, root_of=None):
         """(values[n], p1_logits[n, 9], p2_logits[n, 9]) -- NetworkImpl::value_policy_inference, network.h:102-123.
-        choices / counts as returned by Context.choices()."""
+        choices / counts as returned by Context.choices().  table / root_of: as in value_inference."""
         battles = _u8(battles)
         n = battles.shape[0]
         values = np.zeros(n, dtype=np.float32)
         l1 = np.zeros((n, 9), dtype=np.float32)
         l2 = np.zeros((n, 9), dtype=np.float32)
+        if table is not None:
+            ro = None if root_of is None else np.ascontiguousarray(root_of, dtype=np.uint32).reshape(n)
+            _lib.check(self.ctx.lib.oakgpu_leaf_eval_policy_table(self.ctx.handle, self.handle, table.handle, _p(ro), _p(battles),
+                                                                  _p(_u8(durations, (n, 8))), n,
+                                                                  _p(_u8(p1_choices, (n, 9))), _p(_u8(p1_counts, (n,))),
+                                                                  _p(_u8(p2_choices, (n, 9))), _p(_u8(p2_counts, (n,))),
+                                                                  _p(values), _p(l1), _p(l2)))
+            return values, l1, l2
         _lib.check(self.ctx.lib.oakgpu_leaf_eval_policy(self.ctx.handle, self.handle, _p(battles), _p(_u8(durations, (n, 8))), n,
                                                         _p(_u8(p1_choices, (n, 9))), _p(_u8(p1_counts, (n,))),
                                                         _p(_u8(p2_choices, (n, 9))), _p(_u8(p2_counts, (n,))),
@@ -281,3 +309,53 @@ class Network:
         if self.handle:
             self.ctx.lib.oakgpu_net_free(self.ctx.handle, self.handle)
             self.handle = None
+
+
+class PartyTable:
+    """The bench-slot embedding table of a search (oakgpu_party_table, include/oakgpu.h): NN::Battle::PokemonCache filled once per
+    root -- 240 embeddings for each of a root battle's 12 stored Pokemon -- so that a leaf's bench slots are row copies.  Fill it per
+    search, or once per game (a team's stored identity never changes); slots it does not hold are embedded as usual."""
+
+    def __init__(self, ctx, net, max_roots=1):
+        self.ctx, self.net, self.device = ctx, net, ctx.device
+        h = C.c_void_p()
+        _lib.check(ctx.lib.oakgpu_party_table_create(ctx.handle, net.handle, int(max_roots), C.byref(h)))
+        self.handle = h
+        self.width = int(ctx.lib.oakgpu_party_table_width(h))
+
+    def fill(self, battles):
+        """battles [n_roots, 384] (or one battle of 384 bytes): replaces every root of the table."""
+        battles = _u8(battles).reshape(-1, 384)
+        _lib.check(self.ctx.lib.oakgpu_party_table_fill(self.ctx.handle, self.handle, _p(battles), battles.shape[0]))
+        return self
+
+    def rows(self, root, side, pokemon):
+        """[240, party embedding width]: row `key` of Pokemon `pokemon` (0-5, team order) of `side` of filled root `root`."""
+        out = np.zeros((240, self.width), dtype=np.float32)
+        _lib.check(self.ctx.lib.oakgpu_party_table_rows(self.ctx.handle, self.handle, int(root), int(side), int(pokemon), _p(out)))
+        return out
+
+    def last_misses(self):
+        """Bench slots the last table call of the context found no row for (and embedded); raises when that call had root_of entries
+        beyond the filled roots.  Synchronises."""
+        got = C.c_uint32()
+        _lib.check(self.ctx.lib.oakgpu_party_table_last_misses(self.ctx.handle, self.handle, C.byref(got)))
+        return got.value
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.oakgpu_party_table_destroy(self.ctx.handle, self.handle)
+            self.handle = None
+
+
+def party_key(pokemon, sleep=0):
+    """Encode::Battle::pokemon_key (encode/battle/key.h:65-71) of 24 stored-Pokemon bytes: host only."""
+    return int(_lib.load().oakgpu_party_key(_p(_u8(pokemon, (24,))), int(sleep)))
+
+
+def party_variant(base, key):
+    """(24 bytes, sleep turns): the variant of `base` the table's fill stores under `key` (< 240)."""
+    out, sleep = np.zeros(24, dtype=np.uint8), C.c_uint8()
+    if _lib.load().oakgpu_party_variant(_p(_u8(base, (24,))), int(key), _p(out), C.byref(sleep)) != 0:
+        raise ValueError("party_variant: key %d is not below 240" % key)
+    return out, sleep.value
