@@ -519,6 +519,73 @@ int oakgpu_frames_encode(oakgpu_ctx *ctx, oakgpu_corpus *corpus, const uint32_t 
 int oakgpu_frames_sample(oakgpu_ctx *ctx, oakgpu_corpus *corpus, uint32_t n, uint64_t seed, uint32_t max_battle_length,
                          uint32_t min_iterations, uint32_t *picks_out, const oakgpu_encoded_frames *out, uint32_t *ok_rows);
 
+/* ---- A network evaluated on EVERY frame of a corpus: what pyoak.cpp_inference (cpp/src/pyoak.cc:331-392) returns for one record and
+ * the terms battle.py's loss (src/oak/battle.py:203-262) would report, for all records at once.  Each record is walked ONCE (the walk of
+ * a pick, with every frame written down) and the evaluator runs once per CHUNK: a range of consecutive whole records.
+ *   Rows.  Record r owns rows bases[r] .. bases[r+1]-1 of the corpus, one per frame in frame order; bases = prefix sums of the frame
+ * counts, a MALFORMED record counting 0 (it has no rows).  Inside a chunk that starts at record `first` the rows are numbered from
+ * bases[first].  Row (r, f) holds the state in front of frame f: battle, durations, the request byte, both sides' legal choices in
+ * the engine's order with their counts.  status / where of the row are those of the pick (r, f) above: OK (where = f), or the
+ * record's verdict -- COUNT, ILLEGAL, EARLY_END with where = the failing frame, from that frame on; RESULT with where = frames[r]
+ * on every row.  A row that is not OK is all zero apart from status and where, in every array of every call below.
+ *   The calls write every cell of the chunk's rows and nothing outside them; a row depends on its record alone, so the chunking
+ * changes no result.  They fail, before anything is launched, when the chunk's rows exceed rows_capacity (what the caller's arrays
+ * hold) or the record range leaves the corpus.  The *_dev calls take device arrays and are asynchronous on the context's stream (the
+ * corpus' workspace grows on the first call of a size, waiting for the stream then); the others take host arrays and return complete. */
+int oakgpu_corpus_frame_bases(const oakgpu_corpus *corpus, uint64_t *bases /* records + 1 */);
+/* Host only, no GPU: consecutive record ranges, each as large as fits in chunk_rows (0 = 65,536) rows.  Chunk i is records
+ * first_record[i] .. first_record[i+1]-1; first_record[*n_chunks] = n.  first_record NULL: count only; otherwise capacity >=
+ * *n_chunks + 1.  Fails when one record alone has more frames than chunk_rows; the message names the record.  malformed is nullable. */
+int oakgpu_corpus_chunks(const uint16_t *frames, const uint8_t *malformed, uint32_t n, uint32_t chunk_rows, uint32_t *first_record,
+                         uint32_t capacity, uint32_t *n_chunks);
+/* The walk alone: battles rows x 384 (16-byte aligned), durations rows x 8 (8-byte aligned), results rows, choices rows x 9 and
+ * counts rows per side, status rows, where rows (u32). */
+int oakgpu_corpus_states_dev(oakgpu_ctx *ctx, oakgpu_corpus *corpus, uint32_t first_record, uint32_t n_records, uint32_t rows_capacity,
+                             uint8_t *battles, uint8_t *durations, uint8_t *results, uint8_t *p1_choices, uint8_t *p1_counts,
+                             uint8_t *p2_choices, uint8_t *p2_counts, uint8_t *status, uint32_t *where);
+int oakgpu_corpus_states(oakgpu_ctx *ctx, oakgpu_corpus *corpus, uint32_t first_record, uint32_t n_records, uint32_t rows_capacity,
+                         uint8_t *battles, uint8_t *durations, uint8_t *results, uint8_t *p1_choices, uint8_t *p1_counts,
+                         uint8_t *p2_choices, uint8_t *p2_counts, uint8_t *status, uint32_t *where);
+/* The walk, then the leaf evaluator's value-and-policy call over the chunk's rows in ONE call of that many leaves (fp32 and discrete
+ * networks alike), then the policies.  Every pointer is nullable:
+ *   value [rows] f32; policy_logit [rows,2,9] f32: the legal logits, 0 behind the count; policy [rows,2,9] f32: the fp32 softmax over
+ * the first k logits (shifted by their maximum), 0 behind them -- cpp_inference's `policy`; k [rows,2] u8; choices [rows,2,9] u8;
+ * status [rows] u8; where [rows] u32. */
+typedef struct {
+  float *value, *policy_logit, *policy;
+  uint8_t *k, *choices, *status;
+  uint32_t *where;
+} oakgpu_corpus_eval;
+int oakgpu_corpus_inference_dev(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_corpus *corpus, uint32_t first_record, uint32_t n_records,
+                                uint32_t rows_capacity, const oakgpu_corpus_eval *out);
+/* The loss terms of a row against its frame's stored targets (u16 / 65535.0f, the values the training rows carry), in fp32:
+ *   sq_err = (value - vt)^2 with vt = (wn * nash_value + we * empirical_value) + ws * score           (battle.py:227-231)
+ *   ce[s]  = -sum_i t_i * logp_i / max(1, #{t_i != 0}), t_i = (1 - pn) * empirical_i + pn * nash_i over side s' k legal choices,
+ *            logp = the log-softmax of its k legal logits                                                (battle.py:203-209, 238-245)
+ * A row that is not OK (excluded = 2) or whose iterations are below min_iterations (excluded = 1) has zero terms; the others have
+ * excluded = 0.  Per record of the chunk: record_sums [n_records,3] f64 = the sums of sq_err, ce[0], ce[1] over its rows with
+ * excluded = 0, in frame order; record_counts [n_records,3] u32 = how many of its rows have excluded = 0, 1, 2.  All five arrays of
+ * `terms` are required (record_sums 8-byte aligned); `out` is nullable, as is each pointer in it. */
+typedef struct { float wn, we, ws, pn; uint32_t min_iterations; } oakgpu_loss_params;
+typedef struct {
+  float *sq_err, *ce /* [rows,2] */;
+  uint8_t *excluded;
+  double *record_sums;
+  uint32_t *record_counts;
+} oakgpu_corpus_terms;
+int oakgpu_corpus_loss_dev(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_corpus *corpus, uint32_t first_record, uint32_t n_records,
+                           uint32_t rows_capacity, const oakgpu_loss_params *p, const oakgpu_corpus_eval *out, const oakgpu_corpus_terms *terms);
+/* Host forms, chunk by chunk (chunk_rows = 0: 65,536).  inference: host arrays of bases[first + n] - bases[first] rows.  evaluate:
+ * the whole corpus; the per-record float64 sums are added in record order on the host, so the totals do not depend on chunk_rows.
+ *   sq_err, ce1, ce2: the sums over the `rows` included rows; excluded: rows left out for their iterations; failed: rows that are not
+ * OK; mse = sq_err / rows, ce_p1 = ce1 / rows, ce_p2 = ce2 / rows (battle.py's batch means; 0 when rows = 0).  per_record (nullable):
+ * one entry per record of the corpus. */
+typedef struct { double sq_err, ce1, ce2; uint64_t rows, excluded, failed; double mse, ce_p1, ce_p2; } oakgpu_corpus_losses;
+int oakgpu_corpus_inference(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_corpus *corpus, uint32_t first_record, uint32_t n_records,
+                            uint32_t chunk_rows, const oakgpu_corpus_eval *out);
+int oakgpu_corpus_evaluate(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_corpus *corpus, const oakgpu_loss_params *p, uint32_t chunk_rows,
+                           oakgpu_corpus_losses *total, oakgpu_corpus_losses *per_record);
+
 /* the compile-time engine switches this library was built with (DESIGN 0 order): MULTIHIT_ROLL_FIRST, PSYWAVE_SHOWDOWN,
  * COUNTER_SHOWDOWN, ACCURACY_LAST.  The default build reports 1, 1, 0, 0. */
 int oakgpu_engine_switches(int out[4]);

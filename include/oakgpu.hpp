@@ -13,9 +13,11 @@
 //   OakGPU::Frames             <- Train::Battle::CompressedFrames (train/battle/compressed-frame.h:37-243)
 //   OakGPU::replay_check       <- the replay self-check of py/battle/frames.h:52-67, for a whole file at once
 //   OakGPU::FrameCorpus, EncodedFrames <- pyoak.sample + Py::Battle::EncodedFrames (pyoak.cc:111-245, py/battle/encoded-frames.h)
+//   OakGPU::FrameCorpus::inference / evaluate <- pyoak.cpp_inference over a whole corpus (pyoak.cc:331-392) and battle.py's loss terms
 //   OakGPU::Exchange           <- the path's one collective: per-root means on the device + RCCL all-gather (no reference analogue)
 // Errors surface as std::runtime_error, like the reference's loaders (cpp/src/search.cc:81-146).
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
@@ -429,6 +431,35 @@ public:
     uint32_t ok = 0;
     check(oakgpu_frames_sample(ctx_, corpus_, static_cast<uint32_t>(out.size), seed, max_battle_length, min_iterations, out.picks.data(), &p, &ok));
     return ok;
+  }
+  // ---- every frame of the corpus (oakgpu_corpus_inference / _evaluate): record r owns rows bases[r] .. bases[r+1]-1
+  std::vector<uint64_t> frame_bases() const {
+    std::vector<uint64_t> bases(static_cast<size_t>(info().records) + 1);
+    check(oakgpu_corpus_frame_bases(corpus_, bases.data()));
+    return bases;
+  }
+  // pyoak.cpp_inference's fields for every row, flat row-major: value [F], policy_logit / policy [F,2,9], k [F,2], status, where [F]
+  struct Output {
+    std::vector<float> value, policy_logit, policy;
+    std::vector<uint8_t> k, choices, status;
+    std::vector<uint32_t> where;
+  };
+  Output inference(Network &net, uint32_t chunk_rows = 0) {
+    const size_t rows = static_cast<size_t>(info().frames);
+    Output o;
+    o.value.resize(rows); o.policy_logit.resize(rows * 18); o.policy.resize(rows * 18); o.k.resize(rows * 2); o.choices.resize(rows * 18);
+    o.status.resize(rows); o.where.resize(rows);
+    const oakgpu_corpus_eval p{o.value.data(), o.policy_logit.data(), o.policy.data(), o.k.data(), o.choices.data(), o.status.data(), o.where.data()};
+    check(oakgpu_corpus_inference(ctx_, net.get(), corpus_, 0, info().records, chunk_rows, &p));
+    return o;
+  }
+  // battle.py's loss terms over the corpus; per_record (nullable) receives one entry per record
+  oakgpu_corpus_losses evaluate(Network &net, const oakgpu_loss_params &p, uint32_t chunk_rows = 0, std::vector<oakgpu_corpus_losses> *per_record = nullptr) {
+    oakgpu_corpus_losses total{};
+    if (per_record) per_record->assign(std::max<size_t>(info().records, 1), oakgpu_corpus_losses{});
+    check(oakgpu_corpus_evaluate(ctx_, net.get(), corpus_, &p, chunk_rows, &total, per_record ? per_record->data() : nullptr));
+    if (per_record) per_record->resize(info().records);
+    return total;
   }
 
 private:

@@ -25,6 +25,8 @@ SYMBOLS = [
     "oakgpu_replay_index", "oakgpu_replay_records_dev", "oakgpu_replay_records", "oakgpu_engine_switches",
     "oakgpu_corpus_create", "oakgpu_corpus_destroy", "oakgpu_corpus_info", "oakgpu_frames_encode_dev", "oakgpu_frames_sample_dev", "oakgpu_encode_battles_dev",
     "oakgpu_frames_encode", "oakgpu_frames_sample",
+    "oakgpu_corpus_frame_bases", "oakgpu_corpus_chunks", "oakgpu_corpus_states_dev", "oakgpu_corpus_states", "oakgpu_corpus_inference_dev", "oakgpu_corpus_loss_dev",
+    "oakgpu_corpus_inference", "oakgpu_corpus_evaluate",
     "oakgpu_party_table_create", "oakgpu_party_table_destroy", "oakgpu_party_table_fill_dev", "oakgpu_party_table_fill", "oakgpu_leaf_eval_table_dev",
     "oakgpu_leaf_eval_policy_table_dev", "oakgpu_party_table_last_misses", "oakgpu_party_table_rows", "oakgpu_party_table_width", "oakgpu_party_key", "oakgpu_party_variant",
     "oakgpu_set_search_party_table", "oakgpu_search_party_table_stats", "oakgpu_leaf_eval_table", "oakgpu_leaf_eval_policy_table",
@@ -75,6 +77,23 @@ class EncodedFrames(C.Structure):     # oakgpu_encoded_frames: one pointer per t
 
 class CorpusStats(C.Structure):       # oakgpu_corpus_stats
     _fields_ = [("records", C.c_uint32), ("malformed", C.c_uint32), ("frames", C.c_uint64), ("stopped_at", C.c_size_t)]
+
+
+class CorpusEval(C.Structure):        # oakgpu_corpus_eval: one nullable pointer per tensor, device or host as the call says
+    _fields_ = [(name, C.c_void_p) for name in ("value", "policy_logit", "policy", "k", "choices", "status", "where")]
+
+
+class LossParams(C.Structure):        # oakgpu_loss_params
+    _fields_ = [("wn", C.c_float), ("we", C.c_float), ("ws", C.c_float), ("pn", C.c_float), ("min_iterations", C.c_uint32)]
+
+
+class CorpusTerms(C.Structure):       # oakgpu_corpus_terms
+    _fields_ = [(name, C.c_void_p) for name in ("sq_err", "ce", "excluded", "record_sums", "record_counts")]
+
+
+class CorpusLosses(C.Structure):      # oakgpu_corpus_losses
+    _fields_ = [("sq_err", C.c_double), ("ce1", C.c_double), ("ce2", C.c_double), ("rows", C.c_uint64), ("excluded", C.c_uint64), ("failed", C.c_uint64),
+                ("mse", C.c_double), ("ce_p1", C.c_double), ("ce_p2", C.c_double)]
 
 
 # include/pkmn.h: the libpkmn-named single-battle ABI (batch-of-one wrappers, pkmn_shim.hip)
@@ -179,6 +198,14 @@ def load():
     lib.oakgpu_encode_battles_dev.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
     lib.oakgpu_frames_encode.argtypes = [vp, vp, vp, u32, C.POINTER(EncodedFrames), C.POINTER(u32)]
     lib.oakgpu_frames_sample.argtypes = [vp, vp, u32, u64, u32, u32, vp, C.POINTER(EncodedFrames), C.POINTER(u32)]
+    lib.oakgpu_corpus_frame_bases.argtypes = [vp, vp]
+    lib.oakgpu_corpus_chunks.argtypes = [vp, vp, u32, u32, vp, u32, C.POINTER(u32)]
+    lib.oakgpu_corpus_states_dev.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.oakgpu_corpus_states.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.oakgpu_corpus_inference_dev.argtypes = [vp, vp, vp, u32, u32, u32, C.POINTER(CorpusEval)]
+    lib.oakgpu_corpus_loss_dev.argtypes = [vp, vp, vp, u32, u32, u32, C.POINTER(LossParams), C.POINTER(CorpusEval), C.POINTER(CorpusTerms)]
+    lib.oakgpu_corpus_inference.argtypes = [vp, vp, vp, u32, u32, u32, C.POINTER(CorpusEval)]
+    lib.oakgpu_corpus_evaluate.argtypes = [vp, vp, vp, C.POINTER(LossParams), u32, C.POINTER(CorpusLosses), C.POINTER(CorpusLosses)]
     lib.oakgpu_selfplay_game.argtypes = [vp, vp, vp, u64, C.POINTER(SelfplayParams), vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(u32),
                                          C.POINTER(C.c_uint8)]
     lib.oakgpu_selfplay_games.argtypes = [C.POINTER(vp), vp, vp, C.POINTER(u64), C.POINTER(SelfplayParams), u32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t),

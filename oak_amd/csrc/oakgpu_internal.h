@@ -2,6 +2,8 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <vector>
+#include "../../include/oakgpu.h"
 struct oakgpu_ctx;
 int oakgpu_fail_hip(int hip_error, const char *what); // records hipGetErrorString, returns the code
 int oakgpu_fail_msg(const char *what);                 // records the message, returns -1
@@ -58,3 +60,28 @@ extern "C" int oakgpu_party_table_is_for(const oakgpu_party_table *table, const 
 void oakgpu_set_thread_search_threads(int threads);
 // Cores the process may really use (affinity mask capped by the cgroup CPU quota; OAKGPU_SEARCH_CORES overrides): search_host.hip.
 unsigned oakgpu_usable_cores();
+// A resident `.battle.data` corpus (trainframes.hip creates and frees it; corpuseval.hip evaluates it chunk by chunk)
+struct oakgpu_corpus {
+  oakgpu_ctx *ctx = nullptr;
+  uint32_t n = 0;
+  oakgpu_corpus_stats info{};
+  uint8_t *records = nullptr, *malformed = nullptr, *aligned = nullptr, *first = nullptr;
+  uint64_t *offsets = nullptr;
+  uint16_t *frames = nullptr;
+  std::vector<uint16_t> h_frames;
+  std::vector<uint8_t> h_malformed;
+  // workspace of a batch of picks: grow-only
+  uint32_t capacity = 0;
+  uint32_t *picks = nullptr, *order = nullptr, *meta = nullptr, *heads = nullptr;
+  uint32_t resident_waves = 0; // what the device holds of k_frames_pick: four waves per SIMD
+  uint8_t *snap = nullptr;
+  // sampling: valid-frame counts per min_iterations, eligible lists per (min_iterations, max_battle_length)
+  struct Valid { uint32_t min_iterations; uint32_t *d; std::vector<uint32_t> h; };
+  struct Eligible { uint32_t min_iterations, max_battle_length, count; uint32_t *d; const uint32_t *valid; };
+  static constexpr size_t MAX_CACHED = 16; // eligible lists kept; one more filter pair empties both caches
+  std::vector<Valid> valids;
+  std::vector<Eligible> eligibles;
+  // corpuseval.hip's workspace of a chunk of rows (freed through eval_free; the stream must be idle)
+  void *eval = nullptr;
+  void (*eval_free)(void *) = nullptr;
+};

@@ -8,6 +8,8 @@
 //           p{1,2}_{prior,empirical,nash}[9]}                                             :494-574
 //   search(input, heap, agent, output = Output()) -> Output                               :575-583
 //   cpp_inference(record, network_path, discrete, budget) -> value / policy_logit / policy :331-392, 709
+//   corpus_inference(paths_or_bytes, network_path, discrete) -> the same three fields for EVERY frame of many records at once
+//           (+ k, status, where, picks): one walk per record and one evaluator call per chunk of rows (oakgpu_corpus_inference)
 //   solve_matrix(row_payoff, discretize_factor) -> (p1, p2, value)                        :394-426, 711
 //   read_battle_data(path) -> [(bytes, frame_count), ...]                                 :43-71, 713
 //   network hyper-parameter constants                                                     :586-596
@@ -431,6 +433,60 @@ PYBIND11_MODULE(pyoak, m) {
         return d;
       },
       py::arg("record"), py::arg("network_path"), py::arg("discrete") = false, py::arg("budget") = "0");
+
+  m.def(
+      "corpus_inference",
+      [](py::object paths_or_bytes, const std::string &network_path, bool discrete) {
+        // cpp_inference's value / policy_logit / policy for every frame of every record, through the corpus calls of include/oakgpu.h:
+        // row bases[r] + f is frame f of record r (picks lists them); status / where as in EncodedBattleFrames
+        std::vector<uint8_t> all;
+        if (py::isinstance<py::bytes>(paths_or_bytes)) {
+          const std::string b = paths_or_bytes.cast<std::string>();
+          all.assign(b.begin(), b.end());
+        } else {
+          for (const std::string &path : paths_or_bytes.cast<std::vector<std::string>>()) {
+            const std::vector<char> bytes = read_file(path, "corpus_inference");
+            uint32_t n = 0;
+            size_t stop = 0; // (bytes behind a record whose length cannot be trusted are left out, so that the next file's records follow)
+            check(oakgpu_replay_index((const uint8_t *)bytes.data(), bytes.size(), nullptr, nullptr, nullptr, 0, &n, &stop));
+            all.insert(all.end(), bytes.begin(), bytes.begin() + (std::ptrdiff_t)stop);
+          }
+        }
+        std::lock_guard<std::mutex> lock(g_ctx_mu);
+        oakgpu_corpus *corpus = nullptr;
+        oakgpu_net *net = nullptr;
+        check(oakgpu_corpus_create(context(), all.data(), all.size(), &corpus));
+        oakgpu_corpus_stats st{};
+        int rc = oakgpu_corpus_info(corpus, &st);
+        const py::ssize_t rows = rc ? 0 : (py::ssize_t)st.frames;
+        py::array_t<float> value({rows, (py::ssize_t)1}), logit({rows, (py::ssize_t)2, (py::ssize_t)9}), policy({rows, (py::ssize_t)2, (py::ssize_t)9});
+        py::array_t<uint8_t> k({rows, (py::ssize_t)2}), status(rows);
+        py::array_t<uint32_t> where(rows), picks({rows, (py::ssize_t)2});
+        if (!rc) rc = discrete ? oakgpu_net_load_discrete(context(), network_path.c_str(), &net) : oakgpu_net_load(context(), network_path.c_str(), &net);
+        if (!rc) {
+          const oakgpu_corpus_eval out{value.mutable_data(), logit.mutable_data(), policy.mutable_data(), k.mutable_data(), nullptr, status.mutable_data(),
+                                       where.mutable_data()};
+          rc = oakgpu_corpus_inference(context(), net, corpus, 0, st.records, 0, &out);
+        }
+        std::vector<uint64_t> bases((size_t)st.records + 1);
+        if (!rc) rc = oakgpu_corpus_frame_bases(corpus, bases.data());
+        if (net) oakgpu_net_free(context(), net);
+        oakgpu_corpus_destroy(corpus);
+        check(rc);
+        uint32_t *pk = picks.mutable_data();
+        for (uint32_t r = 0; r < st.records; ++r)
+          for (uint64_t row = bases[r]; row < bases[r + 1]; ++row) { pk[2 * row] = r; pk[2 * row + 1] = (uint32_t)(row - bases[r]); }
+        py::dict d;
+        d["value"] = value;
+        d["policy_logit"] = logit;
+        d["policy"] = policy;
+        d["k"] = k;
+        d["status"] = status;
+        d["where"] = where;
+        d["picks"] = picks;
+        return d;
+      },
+      py::arg("paths_or_bytes"), py::arg("network_path"), py::arg("discrete") = false);
 
   m.def(
       "solve_matrix",

@@ -457,27 +457,7 @@ __global__ __launch_bounds__(256) void k_frames_count_ok(const uint8_t *status, 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return oakgpu_fail_hip((int)_e, #x); } while (0)
 
-struct oakgpu_corpus {
-  oakgpu_ctx *ctx = nullptr;
-  uint32_t n = 0;
-  oakgpu_corpus_stats info{};
-  uint8_t *records = nullptr, *malformed = nullptr, *aligned = nullptr, *first = nullptr;
-  uint64_t *offsets = nullptr;
-  uint16_t *frames = nullptr;
-  std::vector<uint16_t> h_frames;
-  std::vector<uint8_t> h_malformed;
-  // workspace of a batch of picks: grow-only
-  uint32_t capacity = 0;
-  uint32_t *picks = nullptr, *order = nullptr, *meta = nullptr, *heads = nullptr;
-  uint32_t resident_waves = 0; // what the device holds of k_frames_pick: four waves per SIMD
-  uint8_t *snap = nullptr;
-  // sampling: valid-frame counts per min_iterations, eligible lists per (min_iterations, max_battle_length)
-  struct Valid { uint32_t min_iterations; uint32_t *d; std::vector<uint32_t> h; };
-  struct Eligible { uint32_t min_iterations, max_battle_length, count; uint32_t *d; const uint32_t *valid; };
-  static constexpr size_t MAX_CACHED = 16; // eligible lists kept; one more filter pair empties both caches
-  std::vector<Valid> valids;
-  std::vector<Eligible> eligibles;
-};
+// (struct oakgpu_corpus: oakgpu_internal.h -- corpuseval.hip walks the same corpus)
 
 namespace {
 
@@ -499,6 +479,7 @@ void corpus_free(oakgpu_corpus *k) {
                   (void *)k->order, (void *)k->meta, (void *)k->snap, (void *)k->heads})
     if (p) (void)hipFree(p);
   cache_free(k);
+  if (k->eval && k->eval_free) k->eval_free(k->eval);
   delete k;
 }
 

@@ -7,7 +7,12 @@ row is written down.  The records are uploaded once (FrameCorpus); a batch is re
     enc = EncodedBattleFrames(4096, "cuda:0")          # torch tensors with the reference's attribute names and shapes
     ok = corpus.sample(enc, seed=step, max_battle_length=0, min_iterations=1)
 
-With device=None the tensors are numpy arrays and the calls go through the staged host-pointer entry points."""
+With device=None the tensors are numpy arrays and the calls go through the staged host-pointer entry points.
+
+Scoring a network on every frame of a corpus (k_frames_expand, k_corpus_terms, k_corpus_record_sums in oak_amd/csrc/corpuseval.hip):
+
+    out = corpus.inference(net)                        # value [F,1], policy_logit [F,2,9], policy [F,2,9], k, status, where, picks
+    losses = corpus.evaluate(net, 0.0, 0.5, 0.5, 0.5)  # mse, ce_p1, ce_p2, rows, excluded, failed"""
 import ctypes as C
 
 import numpy as np
@@ -61,6 +66,44 @@ class EncodedBattleFrames:
                 t.fill(0)
             else:
                 (t.view(torch.int32) if t.dtype == torch.uint32 else t).zero_()
+
+
+# name -> (shape behind the row axis, dtype): the reference's OutputBuffer fields (py/battle/output.h), then k / choices / status / where
+EVAL_FIELDS = {"value": ((1,), "float32"), "policy_logit": ((2, 9), "float32"), "policy": ((2, 9), "float32"), "k": ((2,), "uint8"),
+               "choices": ((2, 9), "uint8"), "status": ((), "uint8"), "where": ((), "uint32")}
+STATE_FIELDS = {"battles": ((384,), "uint8"), "durations": ((8,), "uint8"), "results": ((), "uint8"), "p1_choices": ((9,), "uint8"),
+                "p1_counts": ((), "uint8"), "p2_choices": ((9,), "uint8"), "p2_counts": ((), "uint8"), "status": ((), "uint8"), "where": ((), "uint32")}
+
+
+class CorpusOutput:
+    """`size` rows of a corpus evaluation: value [F,1], policy_logit [F,2,9], policy [F,2,9] (the reference's OutputBuffer names and
+    shapes), k [F,2], choices [F,2,9], status [F], where [F], and picks [F,2] (record, frame) filled on the host."""
+
+    def __init__(self, size, device=None):
+        self.size, self.device = int(size), device
+        if device is None:
+            for name, (tail, dtype) in EVAL_FIELDS.items():
+                setattr(self, name, np.zeros((self.size,) + tail, dtype=dtype))
+        else:
+            import torch
+            for name, (tail, dtype) in EVAL_FIELDS.items():
+                if dtype == "uint32":
+                    t = torch.zeros((self.size,) + tail, dtype=torch.int32, device=device).view(torch.uint32)
+                else:
+                    t = torch.zeros((self.size,) + tail, dtype=getattr(torch, dtype), device=device)
+                setattr(self, name, t)
+        self.picks = np.zeros((self.size, 2), dtype=np.uint32)
+
+    def _ptr(self, t):
+        return t.ctypes.data if self.device is None else t.data_ptr()
+
+    def pointers(self, row=0):
+        """The oakgpu_corpus_eval of these tensors from row `row` on."""
+        def at(name):
+            t = getattr(self, name)
+            tail, dtype = EVAL_FIELDS[name]
+            return self._ptr(t) + row * int(np.prod(tail, dtype=np.int64)) * np.dtype(dtype).itemsize
+        return _lib.CorpusEval(**{name: at(name) for name in EVAL_FIELDS})
 
 
 class _Bracket:
@@ -152,6 +195,76 @@ class FrameCorpus:
         with _Bracket(self.ctx, enc):
             _lib.check(lib.oakgpu_frames_sample_dev(self.ctx.handle, self.handle, *args))
         return int((enc.status[:n] == 0).sum())
+
+
+    # ---- every frame of the corpus --------------------------------------------------------------------------------------------
+    def frame_bases(self):
+        """uint64[records + 1]: record r owns rows bases[r] .. bases[r+1]-1 (a malformed record owns none)."""
+        bases = np.zeros(self.info()["records"] + 1, dtype=np.uint64)
+        _lib.check(self.ctx.lib.oakgpu_corpus_frame_bases(self.handle, bases.ctypes.data))
+        return bases
+
+    def chunks(self, chunk_rows=0, first=0, n=None):
+        """The record ranges an evaluation with chunk_rows walks: list of (first record, records) covering records first .. first+n-1."""
+        bases = self.frame_bases()
+        n = len(bases) - 1 - first if n is None else int(n)
+        frames = np.diff(bases)[first:first + n]
+        if len(frames) and int(frames.max()) > 0xFFFF:
+            raise _lib.OakGpuError("a record holds at most 65,535 frames")
+        frames = np.ascontiguousarray(frames, dtype=np.uint16)
+        count = C.c_uint32(0)
+        lib = self.ctx.lib
+        _lib.check(lib.oakgpu_corpus_chunks(frames.ctypes.data, None, n, int(chunk_rows), None, 0, C.byref(count)))
+        firsts = np.zeros(count.value + 1, dtype=np.uint32)
+        _lib.check(lib.oakgpu_corpus_chunks(frames.ctypes.data, None, n, int(chunk_rows), firsts.ctypes.data, len(firsts), C.byref(count)))
+        return [(first + int(firsts[i]), int(firsts[i + 1] - firsts[i])) for i in range(count.value)]
+
+    def states(self, first, n, rows_capacity=None):
+        """The state in front of every frame of records first .. first+n-1 (numpy, by name: STATE_FIELDS).  rows_capacity: what the
+        arrays may hold (default: exactly the rows of the range)."""
+        bases = self.frame_bases()
+        rows = int(bases[first + n] - bases[first]) if first + n < len(bases) else 0
+        cap = rows if rows_capacity is None else int(rows_capacity)
+        out = {name: np.zeros((min(rows, cap),) + tail, dtype=dtype) for name, (tail, dtype) in STATE_FIELDS.items()}
+        _lib.check(self.ctx.lib.oakgpu_corpus_states(self.ctx.handle, self.handle, int(first), int(n), cap, *[out[name].ctypes.data for name in STATE_FIELDS]))
+        return out
+
+    def inference(self, net, records=None, chunk_rows=0, device=None):
+        """The network on every frame of the corpus, or of records = (first, n): a CorpusOutput (numpy, or torch tensors on `device`)."""
+        bases = self.frame_bases()
+        first, n = (0, len(bases) - 1) if records is None else (int(records[0]), int(records[1]))
+        if first + n > len(bases) - 1:
+            raise _lib.OakGpuError("inference: records %d .. %d are not all in the corpus" % (first, first + n))
+        rows = int(bases[first + n] - bases[first])
+        out = CorpusOutput(rows, device)
+        frames = np.diff(bases)[first:first + n].astype(np.int64)
+        out.picks[:, 0] = np.repeat(np.arange(first, first + n, dtype=np.int64), frames)
+        out.picks[:, 1] = np.arange(rows, dtype=np.int64) - np.repeat(bases[first:first + n].astype(np.int64) - int(bases[first]), frames)
+        lib = self.ctx.lib
+        if device is None:
+            ptrs = out.pointers()
+            _lib.check(lib.oakgpu_corpus_inference(self.ctx.handle, net.handle, self.handle, first, n, int(chunk_rows), C.byref(ptrs)))
+            return out
+        with _Bracket(self.ctx, out):
+            for f, k in self.chunks(chunk_rows, first, n):
+                row, crows = int(bases[f] - bases[first]), int(bases[f + k] - bases[f])
+                ptrs = out.pointers(row)
+                _lib.check(lib.oakgpu_corpus_inference_dev(self.ctx.handle, net.handle, self.handle, f, k, crows, C.byref(ptrs)))
+        return out
+
+    def evaluate(self, net, value_nash_weight, value_empirical_weight, value_score_weight, p_nash_weight, min_iterations=1, chunk_rows=0,
+                 per_record=False):
+        """battle.py's loss terms over the whole corpus: {"mse", "ce_p1", "ce_p2", "sq_err", "ce1", "ce2" (the sums), "rows", "excluded"
+        (for their iterations), "failed" (rows that are not OK)}; per_record=True adds "records": the same per record."""
+        p = _lib.LossParams(float(value_nash_weight), float(value_empirical_weight), float(value_score_weight), float(p_nash_weight), int(min_iterations))
+        total = _lib.CorpusLosses()
+        per = (_lib.CorpusLosses * max(self.info()["records"], 1))() if per_record else None
+        _lib.check(self.ctx.lib.oakgpu_corpus_evaluate(self.ctx.handle, net.handle, self.handle, C.byref(p), int(chunk_rows), C.byref(total), per))
+        as_dict = lambda l: {name: getattr(l, name) for name, _ in _lib.CorpusLosses._fields_}
+        out = as_dict(total)
+        if per_record:
+            out["records"] = [as_dict(per[r]) for r in range(self.info()["records"])]
+        return out
 
 
 def encode_battles(ctx, battles, durations, results, enc):

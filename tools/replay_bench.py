@@ -64,6 +64,7 @@ def play_corpus(ctx, n_games, seed=1, ghost_frac=0.02, record_choices=True):
         m = live.numel()
         ch = [torch.empty((m, 9), dtype=u8, device=dev) for _ in range(2)]
         cn = [torch.empty((m,), dtype=u8, device=dev) for _ in range(2)]
+        torch.cuda.synchronize()   # (the context's stream does not wait for torch's: the gathers above must have landed)
         for pl in range(2):
             _lib.check(lib.oakgpu_choices_dev(h, P(lb), P(lr), pl, P(ch[pl]), P(cn[pl]), m))
         ctx.synchronize()
