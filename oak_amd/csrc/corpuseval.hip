@@ -2,8 +2,8 @@
 // include/oakgpu.h; the reference's per-record form is pyoak.cpp_inference, cpp/src/pyoak.cc:331-392).
 //
 //   k_chunk_order        : the records of a chunk -> lane order, longest first (one workgroup, counting sort by frame count)
-//   k_frames_expand      : one lane per record, k_frames_pick's walk on the register engine with EVERY frame written: the state in
-//                          front of frame f goes to row base[r] - base[first] + f of the chunk.  The 384-byte battles are staged in
+//   k_frames_expand      : one lane per record, the replay check's walk on the register engine (record_walk.hpp) with EVERY frame
+//                          written: the state in front of frame f goes to row base[r] - base[first] + f of the chunk.  The 384-byte battles are staged in
 //                          LDS and the wave writes whole rows (24 lanes x 16 B each) instead of one lane writing 16-byte pieces
 //                          384 bytes apart.
 //   k_corpus_terms       : one lane per row: softmax policies, the squared value error and both sides' cross-entropy terms of
@@ -20,42 +20,19 @@
 #include "../../include/oakgpu.h"
 #include "gen1_device.hpp"
 #include "gen1_regs.hpp"
+#include "record_walk.hpp"
 #include "oakgpu_internal.h"
 
 namespace oak {
 namespace ce {
 
-constexpr int TABLE_PAD = (TABLE_LDS_BYTES + 15) & ~15;
-constexpr uint32_t STATUS_PENDING = 0xFF, ROW_NONE = 0xFFFFFFFFu;
-constexpr int STAGE_STRIDE = 100; // words per staged battle: 96 + 4 (16-byte aligned rows that spread over the banks)
+using namespace walk;
 
-__device__ __forceinline__ uint32_t load_u32(const uint8_t *p) { // (frames sit at any byte of the file)
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-__device__ __forceinline__ uint32_t load_u16(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
+constexpr uint32_t ROW_NONE = 0xFFFFFFFFu;
 
-// ---- lane order of a chunk: frame count descending, so that the 64 games a wave walks are of similar length.  One workgroup; counts
-// past 1,023 share a bucket (the engine ends a game at turn 1,000).
+// ---- lane order of a chunk: frame count descending, longest game first (a malformed record has no frames)
 __global__ __launch_bounds__(1024) void k_chunk_order(const uint16_t *frames, const uint8_t *malformed, uint32_t n, uint32_t *order) {
-  __shared__ uint32_t hist[1024];
-  const uint32_t tid = threadIdx.x;
-  auto bucket = [&](uint32_t i) { return 1023u - (malformed[i] ? 0u : min((uint32_t)frames[i], 1023u)); };
-  hist[tid] = 0;
-  __syncthreads();
-  for (uint32_t i = tid; i < n; i += 1024) atomicAdd(&hist[bucket(i)], 1u);
-  __syncthreads();
-  const uint32_t own = hist[tid];
-  for (uint32_t off = 1; off < 1024; off <<= 1) {
-    const uint32_t v = tid >= off ? hist[tid - off] : 0;
-    __syncthreads();
-    hist[tid] += v;
-    __syncthreads();
-  }
-  const uint32_t start = hist[tid] - own;
-  __syncthreads();
-  hist[tid] = start;
-  __syncthreads();
-  for (uint32_t i = tid; i < n; i += 1024) order[atomicAdd(&hist[bucket(i)], 1u)] = i;
+  order_desc(n, order, [&](uint32_t i) { return malformed[i] ? 0u : (uint32_t)frames[i]; });
 }
 
 // ---- the walk --------------------------------------------------------------------------------------------------------------------
@@ -80,25 +57,14 @@ struct ExpandArgs {
 constexpr int EXPAND_COLD_BYTES = (sizeof(ExpandArgs) + 15) & ~15;
 constexpr int EXPAND_LDS_BYTES = 24 * 64 * 4 + TABLE_PAD + 64 * STAGE_STRIDE * 4 + 64 * 4 + EXPAND_COLD_BYTES;
 
-template <class P>
-__device__ __forceinline__ P cold_ptr_at(const lds_u32 *cold, size_t byte_off) { // a 64-bit pointer parked in LDS
-  return (P)((uint64_t)cold[byte_off / 4] | ((uint64_t)cold[byte_off / 4 + 1] << 32));
-}
-__device__ __forceinline__ bool member(uint32_t n, uint64_t lo, uint32_t hi, uint32_t c) { // c among the n choice bytes
-  bool in = false;
-#pragma unroll
-  for (uint32_t i = 0; i < OAKGPU_MAX_CHOICES; ++i) in |= i < n && (i < 8 ? (uint32_t)(lo >> (8 * i)) & 0xFF : hi) == c;
-  return in;
-}
 __device__ __forceinline__ void store_choices(uint8_t *dst, uint64_t lo, uint32_t hi) { // 9 bytes at any address
 #pragma unroll
   for (uint32_t i = 0; i < 8; ++i) dst[i] = (uint8_t)(lo >> (8 * i));
   dst[8] = (uint8_t)hi;
 }
 
-// One wave per workgroup, one record per lane; every loop turn each lane that still has a frame settles its row: in the replay check's
-// order the game has ended (EARLY_END), a legal-choice count differs (COUNT), a stored choice is not legal (ILLEGAL) -- from the
-// first failing frame on every row of the record carries that verdict and zeros -- else the state goes to the lane's LDS slot and its
+// One wave per workgroup, one record per lane; every loop turn each lane that still has a frame settles its row: the replay check
+// (frame_check) fails -- from the first failing frame on every row of the record carries that verdict and zeros -- else the state goes to the lane's LDS slot and its
 // small fields straight to their arrays, the wave copies the 64 slots out as whole rows, and the lane plays update(c1, c2).
 template <int WPS>
 __global__ __launch_bounds__(64, WPS) void k_frames_expand(ExpandArgs a_in) {
@@ -110,9 +76,7 @@ __global__ __launch_bounds__(64, WPS) void k_frames_expand(ExpandArgs a_in) {
   typedef OAK_LDS u32x4 lds_u128;
   lds_u32 *stage = (lds_u32 *)((lds_u8 *)smem + ER::PARTY_WORDS * 64 * 4 + TABLE_PAD);
   lds_u32 *srow = stage + 64 * STAGE_STRIDE; // the row each lane's slot goes to this turn
-  // the pointers are parked in LDS and read back where they are used (k_replay_records' reason: as kernel arguments they would hold
-  // SGPRs the turn-step's exec masks need)
-  lds_u32 *cold = srow + 64;
+  lds_u32 *cold = srow + 64; // the arguments, parked (cold_ptr_at)
   if (threadIdx.x < sizeof(ExpandArgs) / 4) cold[threadIdx.x] = ((const uint32_t *)&a_in)[threadIdx.x];
   __syncthreads();
 #define EA_PTR(field, type) cold_ptr_at<type>(cold, offsetof(ExpandArgs, field))
@@ -148,16 +112,9 @@ __global__ __launch_bounds__(64, WPS) void k_frames_expand(ExpandArgs a_in) {
     bool play = false;
     if (live) {
       row = row0 + k;
-      const uint32_t m = (mn & 15) + 1, nn = (mn >> 4) + 1;
       typename ER::Choices l1{0, 0, 0}, l2{0, 0, 0};
       if (verdict == STATUS_PENDING) {
-        if (res & 15) verdict = OAKGPU_REPLAY_EARLY_END;
-        else {
-          l1 = e.choices(e.S, (res >> 4) & 3); // (normalised frame: S = P1, F = P2)
-          l2 = e.choices(e.F, (res >> 6) & 3);
-          if (l1.n != m || l2.n != nn) verdict = OAKGPU_REPLAY_COUNT;
-          else if (!member(l1.n, l1.lo, l1.hi, c1) || !member(l2.n, l2.lo, l2.hi, c2)) verdict = OAKGPU_REPLAY_ILLEGAL;
-        }
+        verdict = frame_check(e, res, mn, c1, c2, l1, l2).status;
         if (verdict != STATUS_PENDING) vwhere = k;
       }
       const bool ok = verdict == STATUS_PENDING;
@@ -189,13 +146,7 @@ __global__ __launch_bounds__(64, WPS) void k_frames_expand(ExpandArgs a_in) {
       }
     }
     __syncthreads();
-    if (play) {
-      // the next frame's three bytes are loaded before this turn's update: the dependent load overlaps the turn-step
-      const uint32_t a1 = c1, a2 = c2;
-      fp += 11 + 4 * ((mn & 15) + 1 + (mn >> 4) + 1);
-      mn = fp[0]; c1 = fp[1]; c2 = fp[2];
-      res = e.update(a1, a2);
-    }
+    if (play) res = play_frame(e, fp, mn, c1, c2, true);
     ++k;
   }
 #undef EA_PTR
@@ -320,8 +271,6 @@ __global__ __launch_bounds__(64) void k_corpus_record_sums(const float *sq_err, 
 } // namespace oak
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-#define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return oakgpu_fail_hip((int)_e, #x); } while (0)
-
 namespace {
 
 constexpr uint32_t DEFAULT_CHUNK_ROWS = 65536;
@@ -346,11 +295,6 @@ void ws_free(void *p) { // (the stream is idle: corpus_free's callers have waite
   delete w;
 }
 
-template <class T>
-int dev_alloc(T *&p, size_t count) {
-  HIPCHK(hipMalloc((void **)&p, std::max<size_t>(count * sizeof(T), 16)));
-  return 0;
-}
 template <class T>
 int dev_grow(oakgpu_corpus *k, T *&p, uint32_t &cap, size_t per, uint32_t want) { // grow-only; an earlier chunk may still read the old block
   if (want <= cap && p) return 0;

@@ -23,15 +23,17 @@
 #include "../../include/oakgpu.h"
 #include "gen1_device.hpp"
 #include "gen1_regs.hpp"
+#include "record_walk.hpp"
 #include "oakgpu_internal.h"
 #include "fast_prng.hpp"
 
 namespace oak {
+using namespace walk; // the queue constants, cold_ptr_at and STAGE_STRIDE are record_walk.hpp's
 
 constexpr int BLOCK = 256;      // 4 waves: one per SIMD of a CU
 constexpr int STATE_WORDS = 96; // 384-byte battle
 constexpr int STATE_LDS_BYTES = STATE_WORDS * BLOCK * 4;
-constexpr int TABLE_LDS_PAD = (TABLE_LDS_BYTES + 15) & ~15;
+constexpr int TABLE_LDS_PAD = TABLE_PAD; // (record_walk.hpp; this file's older name for it)
 constexpr int ENGINE_LDS_BYTES = STATE_LDS_BYTES + TABLE_LDS_PAD;
 
 // The engine's tables (moves, species, type chart, boosts, reciprocals, effect descriptors: 3.4 KB) as ONE image in exactly
@@ -252,11 +254,6 @@ __global__ __launch_bounds__(BLK, 2) void k_rollout_regs(RolloutArgs a) {
 // launch with ZERO steps; the HBM traffic is worth 12).  Here the wave moves its 64 battles (24 KB, contiguous) between
 // global memory and LDS with fully coalesced 1 KB accesses, and the engine reads / writes the LDS copy through `gin`
 // (a generic pointer: the flat loads resolve to LDS).
-template <class P>
-__device__ __forceinline__ P cold_ptr_at(const lds_u32 *cold, size_t byte_off) { // a 64-bit pointer parked in LDS
-  return (P)((uint64_t)cold[byte_off / 4] | ((uint64_t)cold[byte_off / 4 + 1] << 32));
-}
-constexpr int STAGE_STRIDE = 100; // words per staged battle: 96 + 4 (16-byte aligned rows that spread over the banks)
 constexpr int STAGED_COLD_BYTES = 128; // the kernel arguments, parked (below)
 constexpr int STAGED_LDS_BYTES = 24 * 64 * 4 + TABLE_LDS_PAD + 64 * STAGE_STRIDE * 4 + STAGED_COLD_BYTES;
 __global__ __launch_bounds__(64, 2) void k_rollout_staged(RolloutArgs a) {
@@ -550,14 +547,7 @@ constexpr uint32_t LONG_STEPS = OAK_LONG_STEPS;
 #define OAK_PRIO_STILL 24
 #endif
 constexpr uint32_t PRIO_STILL = OAK_PRIO_STILL;
-#ifndef OAK_REFILL_EVERY
-#define OAK_REFILL_EVERY 8
-#endif
-#ifndef OAK_REFILL_LANES
-#define OAK_REFILL_LANES 16
-#endif
-constexpr uint32_t REFILL_EVERY = OAK_REFILL_EVERY, REFILL_LANES = OAK_REFILL_LANES; // free lanes refill every n-th iteration (a power of two), or at once when this many are free
-constexpr uint32_t QUEUE_HEADS = 8, QUEUE_HEAD_STRIDE = 64; // eight queue heads per round, 64 words (one 256-byte line) apart
+// (REFILL_EVERY / REFILL_LANES, with their OAK_REFILL_* overrides, and QUEUE_HEADS / QUEUE_HEAD_STRIDE: record_walk.hpp)
 template <int BLK, int WPS>
 __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, RoundArgs q_in) {
   extern __shared__ __align__(16) uint8_t smem[];
@@ -1262,8 +1252,9 @@ __global__ __launch_bounds__(64, 2) void k_tree_step_staged(TreeStepArgs a) {
 
 // ---- Replay check of `.battle.data` records (oakgpu_replay_records_dev; the contract is in include/oakgpu.h) ------------------
 // A replay turn is a rollout turn-step whose choices are read from the record instead of drawn, so the kernel is the queue kernel's
-// shape on the register engine: persistent lanes, one game each, refilled from eight queue heads when their game ends, the queue
-// ordered longest game first by the host.  Records stay in their on-disk layout; a battle can start at any byte, so k_replay_gather
+// shape on the register engine: persistent lanes, one game each, refilled from eight queue heads when their game ends (the queue and
+// the per-frame check are record_walk.hpp's), the queue ordered longest game first by the host.  Records stay in their on-disk
+// layout; a battle can start at any byte, so k_replay_gather
 // first copies every stored battle to a 16-byte aligned slot (the engine's dword loads and its immutable-data pointer `gin` read
 // it there) and derives the first request from it.
 struct ReplayArgs {
@@ -1300,8 +1291,7 @@ __global__ __launch_bounds__(256) void k_replay_gather(ReplayArgs a, const uint8
   }
   const uint8_t *src = a.records + a.offsets[rec] + 6; // u32 length, u16 frame count, then the battle
   uint32_t *dst = (uint32_t *)(a.aligned + (size_t)rec * 384);
-  for (uint32_t j = wl; j < 96; j += 64)
-    dst[j] = (uint32_t)src[4 * j] | ((uint32_t)src[4 * j + 1] << 8) | ((uint32_t)src[4 * j + 2] << 16) | ((uint32_t)src[4 * j + 3] << 24);
+  for (uint32_t j = wl; j < 96; j += 64) dst[j] = load_u32(src + 4 * j);
   if (wl == 0) { // PKMN::result(battle) (pkmn.h:235-272)
     bool alive[2] = {false, false}, fainted[2];
 #pragma unroll
@@ -1321,23 +1311,13 @@ __global__ __launch_bounds__(256) void k_replay_gather(ReplayArgs a, const uint8
   }
 }
 
-__device__ __forceinline__ bool replay_member(uint32_t n, uint64_t lo, uint32_t hi, uint32_t c) { // c among the n choice bytes
-  bool in = false;
-#pragma unroll
-  for (uint32_t i = 0; i < OAKGPU_MAX_CHOICES; ++i) in |= i < n && (i < 8 ? (uint32_t)(lo >> (8 * i)) & 0xFF : hi) == c;
-  return in;
-}
-
-constexpr uint32_t REPLAY_NONE = 0xFFFFFFFFu, REPLAY_DONE = 0xFFFFFFFEu;
 template <int WPS>
 __global__ __launch_bounds__(64, WPS) void k_replay_records(ReplayArgs a_in) {
   extern __shared__ __align__(16) uint8_t smem[];
   lds_u32 *party = (lds_u32 *)smem;
   using ER = EngineR<64, false>;
   Tables T = stage_default_tables((lds_u8 *)smem + ER::PARTY_WORDS * 64 * 4);
-  // the pointers are parked in LDS and read back on the cold paths (refill, verdict): k_rollout_queue's reason -- as kernel arguments
-  // they would hold SGPRs the turn-step's exec masks need
-  lds_u32 *cold = (lds_u32 *)((lds_u8 *)smem + ER::PARTY_WORDS * 64 * 4 + TABLE_LDS_PAD);
+  lds_u32 *cold = (lds_u32 *)((lds_u8 *)smem + ER::PARTY_WORDS * 64 * 4 + TABLE_LDS_PAD); // the arguments, parked (cold_ptr_at)
   if (threadIdx.x < sizeof(ReplayArgs) / 4) cold[threadIdx.x] = ((const uint32_t *)&a_in)[threadIdx.x];
   __syncthreads();
 #define RA_PTR(field, type) cold_ptr_at<type>(cold, offsetof(ReplayArgs, field))
@@ -1346,41 +1326,21 @@ __global__ __launch_bounds__(64, WPS) void k_replay_records(ReplayArgs a_in) {
   ER e;
   e.m = party + threadIdx.x;
   e.T = T;
-  uint32_t idx = REPLAY_NONE, r = 0, k = 0, nf = 0, mn = 0, c1 = 0, c2 = 0;
+  uint32_t idx = LANE_NONE, r = 0, k = 0, nf = 0, mn = 0, c1 = 0, c2 = 0;
   const uint8_t *fp = nullptr; // the next frame of this lane's record
-  // wave-uniform scalar state in one word: bits 8-10 the current queue head, 12-15 heads seen dry, 16-23 an iteration counter, bit 0 dry
-  uint32_t ust = (blockIdx.x & 7u) << 8;
+  uint32_t ust = queue_state(blockIdx.x);
   for (;;) {
-    const bool need = idx == REPLAY_NONE;
+    const bool need = idx == LANE_NONE;
     const uint64_t mask = __ballot(need);
     bool load = false;
-    ust = (ust & ~0xFF0000u) | ((ust + 0x10000u) & 0xFF0000u);
-    // refills in batches (k_rollout_queue's rule: every REFILL_EVERY-th iteration, or at once when REFILL_LANES lanes are free, or
-    // when no lane has a game) -- a refill is a returning atomic and dependent loads for the whole wave
-    if (mask && !(ust & 1u) && (((ust >> 16) & (REFILL_EVERY - 1)) == 0 || (uint32_t)__popcll(mask) >= REFILL_LANES || __ballot(idx < REPLAY_DONE) == 0)) {
-      uint64_t rem = mask;
+    if (refill_due(ust, mask, __ballot(idx < LANE_DONE) != 0)) {
       uint32_t my = 0;
-      bool got = false;
-      for (;;) { // head s hands out the queue positions s, s + 8, s + 16, ... (k_rollout_queue)
-        const uint32_t shard = (ust >> 8) & 7u, need_n = (uint32_t)__popcll(rem);
-        const uint32_t lim = n_live > shard ? (n_live - shard + 7u) >> 3 : 0u;
-        uint32_t base = 0;
-        if (wl == 0) base = atomicAdd(RA_PTR(heads, uint32_t *) + shard * QUEUE_HEAD_STRIDE, need_n);
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        const uint32_t avail = base < lim ? (lim - base < need_n ? lim - base : need_n) : 0u;
-        const uint32_t rank = (uint32_t)__popcll(rem & ((1ull << wl) - 1));
-        if (((rem >> wl) & 1) && rank < avail) { my = shard + ((base + rank) << 3); got = true; }
-        if (avail == need_n) break;
-        rem = __ballot(need && !got);
-        ust = (ust & ~(7u << 8)) | (((shard + 1u) & 7u) << 8);
-        ust += 1u << 12;
-        if (((ust >> 12) & 15u) >= 8u) { ust |= 1u; break; }
-      }
+      const bool got = queue_take(ust, cold, offsetof(ReplayArgs, heads), n_live, need, mask, wl, my);
       if (need) {
         if (got) { idx = RA_PTR(order, const uint32_t *)[my]; load = true; }
-        else idx = REPLAY_DONE;
+        else idx = LANE_DONE;
       }
-    } else if (mask && (ust & 1u) && need) idx = REPLAY_DONE;
+    } else if (need && queue_dry(ust)) idx = LANE_DONE;
     if (__ballot(load)) {
       if (load) {
         e.load_battle_global(RA_PTR(aligned, const uint8_t *) + (size_t)idx * 384, 0, 0); // zero durations (frames.h:57-59)
@@ -1391,41 +1351,32 @@ __global__ __launch_bounds__(64, WPS) void k_replay_records(ReplayArgs a_in) {
         if (nf) { mn = fp[0]; c1 = fp[1]; c2 = fp[2]; }
       }
     }
-    if (__ballot(idx != REPLAY_DONE) == 0) break;
-    if (idx < REPLAY_DONE) {
-      uint32_t status = 0xFF, player = 0, expected = 0, got = 0;
+    if (__ballot(idx != LANE_DONE) == 0) break;
+    if (idx < LANE_DONE) {
+      Verdict v{STATUS_PENDING, 0, 0, 0};
       if (k == nf) { // after the last frame
-        expected = RA_PTR(records, const uint8_t *)[RA_PTR(offsets, const uint64_t *)[idx] + 390];
-        status = r == expected ? OAKGPU_REPLAY_OK : OAKGPU_REPLAY_RESULT;
-        got = r;
+        v.expected = RA_PTR(records, const uint8_t *)[RA_PTR(offsets, const uint64_t *)[idx] + 390];
+        v.status = r == v.expected ? OAKGPU_REPLAY_OK : OAKGPU_REPLAY_RESULT;
+        v.got = r;
       } else if (r & 15) {
-        expected = RA_PTR(records, const uint8_t *)[RA_PTR(offsets, const uint64_t *)[idx] + 390];
-        status = OAKGPU_REPLAY_EARLY_END;
-        got = r;
+        v.expected = RA_PTR(records, const uint8_t *)[RA_PTR(offsets, const uint64_t *)[idx] + 390];
+        v.status = OAKGPU_REPLAY_EARLY_END;
+        v.got = r;
       } else {
-        const uint32_t m = (mn & 15) + 1, n = (mn >> 4) + 1;
-        const auto l1 = e.choices(e.S, (r >> 4) & 3); // (normalised frame: S = P1, F = P2)
-        const auto l2 = e.choices(e.F, (r >> 6) & 3);
-        if (l1.n != m) { status = OAKGPU_REPLAY_COUNT; player = 1; expected = m; got = l1.n; }
-        else if (l2.n != n) { status = OAKGPU_REPLAY_COUNT; player = 2; expected = n; got = l2.n; }
-        else if (!replay_member(l1.n, l1.lo, l1.hi, c1)) { status = OAKGPU_REPLAY_ILLEGAL; player = 1; expected = c1; got = l1.n; }
-        else if (!replay_member(l2.n, l2.lo, l2.hi, c2)) { status = OAKGPU_REPLAY_ILLEGAL; player = 2; expected = c2; got = l2.n; }
-        else {
-          // the next frame's three bytes are loaded before this turn's update: the dependent load overlaps the turn-step
-          const uint32_t a1 = c1, a2 = c2;
-          fp += 11 + 4 * (m + n);
-          if (k + 1 < nf) { mn = fp[0]; c1 = fp[1]; c2 = fp[2]; }
-          r = e.update(a1, a2);
+        typename ER::Choices l1, l2;
+        v = frame_check(e, r, mn, c1, c2, l1, l2);
+        if (v.status == STATUS_PENDING) {
+          r = play_frame(e, fp, mn, c1, c2, k + 1 < nf);
           ++k;
         }
       }
-      if (status != 0xFF) { // the verdict: report, state at the verdict, lane free
-        replay_report(RA_PTR(reports, uint32_t *), idx, k, status, player, expected, got);
+      if (v.status != STATUS_PENDING) { // the verdict: report, state at the verdict, lane free
+        replay_report(RA_PTR(reports, uint32_t *), idx, k, v.status, v.player, v.expected, v.got);
         uint8_t *bout = RA_PTR(battles_out, uint8_t *);
         if (bout) e.store_battle_global(bout + (size_t)idx * 384);
         uint32_t *dout = RA_PTR(durations_out, uint32_t *);
         if (dout) *(uint2 *)(dout + 2 * (size_t)idx) = make_uint2(e.S.dur, e.F.dur);
-        idx = REPLAY_NONE;
+        idx = LANE_NONE;
       }
     }
   }
@@ -1727,6 +1678,7 @@ void oakgpu_ctx_set_attachment(oakgpu_ctx *c, void *p, void (*dtor)(void *)) {
   c->attachment = p;
   c->attachment_dtor = dtor;
 }
+#undef HIPCHK // (oakgpu_internal.h's form: this file's errors go through its own fail())
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return fail(_e, #x); } while (0)
 
 // ---- host-buffer conveniences (PCIe-inclusive; never the benchmarked path) ------------------
@@ -2707,8 +2659,7 @@ static int replay_launch(oakgpu_ctx *c, const uint8_t *records, const uint64_t *
   const oak::ReplayArgs a{records, offsets, frames, d_order, aligned, first, (uint32_t *)reports, battles, durations, heads, n_live};
   hipLaunchKernelGGL(oak::k_replay_gather, dim3((n + 3) / 4), dim3(256), 0, c->stream, a, malformed, n);
   if (n_live) {
-    const uint32_t resident = (uint32_t)c->n_cu * 4u * 4u; // four waves per SIMD, as k_rollout_queue<64, 4>
-    const uint32_t waves = std::min((n_live + 63) / 64, resident);
+    const uint32_t waves = std::min((n_live + 63) / 64, oak::walk::resident_walk_waves(c->n_cu));
     hipLaunchKernelGGL((oak::k_replay_records<4>), dim3(waves), dim3(64), oak::REPLAY_LDS_BYTES, c->stream, a);
   }
   HIPCHK(hipGetLastError());

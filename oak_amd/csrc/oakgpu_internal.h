@@ -2,12 +2,21 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <algorithm>
 #include <vector>
+#include <hip/hip_runtime.h>
 #include "../../include/oakgpu.h"
 struct oakgpu_ctx;
 int oakgpu_fail_hip(int hip_error, const char *what); // records hipGetErrorString, returns the code
 int oakgpu_fail_msg(const char *what);                 // records the message, returns -1
 int oakgpu_ctx_device(const oakgpu_ctx *ctx);
+// A failed HIP call ends the calling function with its code, recorded (oakgpu.hip replaces this form by one through its own fail())
+#define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return oakgpu_fail_hip((int)_e, #x); } while (0)
+template <class T>
+int dev_alloc(T *&p, size_t count) { // hipMalloc of `count` elements (at least 16 bytes)
+  HIPCHK(hipMalloc((void **)&p, std::max<size_t>(count * sizeof(T), 16)));
+  return 0;
+}
 // One `.battle.data` record at the head of a buffer (selfplay.hip): OAKGPU_RECORD_OK, _MALFORMED (damaged inside its own length; *total
 // is trustworthy) or _STOP (the length field is not).  *msg: oakgpu_frames_read's message.  _length checks the header only.
 enum { OAKGPU_RECORD_OK = 0, OAKGPU_RECORD_MALFORMED = 1, OAKGPU_RECORD_STOP = 2 };

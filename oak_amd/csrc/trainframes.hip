@@ -3,8 +3,8 @@
 //   k_frames_valid   : one lane per record, frames with iterations >= min_iterations (cached per min_iterations by the corpus)
 //   k_frames_draw    : one lane per draw, pyoak.sample's rule with a fast_prng stream per draw -> picks (record, frame)
 //   k_frames_order   : picks -> lane order, longest prefix first (one workgroup, counting sort by frame)
-//   k_frames_pick    : persistent lanes fed from eight queue heads, one pick at a time: k_replay_records' walk on the register
-//                      engine up to the picked frame -> a snapshot
+//   k_frames_pick    : persistent lanes fed from eight queue heads, one pick at a time: the replay check's walk on the register
+//                      engine (record_walk.hpp) up to the picked frame -> a snapshot
 //                      (battle, durations, request, both choice lists, status)
 //   k_frames_requests: the same snapshot head for states the caller holds (oakgpu_encode_battles_dev)
 //   k_frames_encode  : one wave per row: the dense encoder rows built in LDS, streamed out; targets decoded from the frame bytes
@@ -19,17 +19,17 @@
 #include "../../include/oakgpu.h"
 #include "gen1_device.hpp"
 #include "gen1_regs.hpp"
+#include "record_walk.hpp"
 #include "oakgpu_internal.h"
 #include "encode_index.hpp"
 #include "fast_prng.hpp"
 
 namespace oak {
 namespace tf {
+using namespace walk;
 
-constexpr int TABLE_PAD = (TABLE_LDS_BYTES + 15) & ~15;
 constexpr uint32_t POKEMON_IN = 198, ACTIVE_IN = 229, POLICY_DIM = 315;
 constexpr uint32_t ROW_POKEMON = 2 * 6 * POKEMON_IN, ROW_ACTIVE = 2 * ACTIVE_IN; // floats per row
-constexpr uint32_t STATUS_PENDING = 0xFF;
 
 // A snapshot's head, 12 dwords (three 16-byte stores): [0] status | request << 8 | n1 << 16 | n2 << 24, [1] where, [2] [3] the
 // sides' duration words, [4] [5] P1's choice bytes 0..7, [6] [7] P2's, [8] choice byte 8 of P1 | of P2 << 8, [9] the frame's byte
@@ -50,12 +50,6 @@ __device__ __forceinline__ void store_meta_failed(uint32_t *meta, uint32_t slot,
   m[1] = make_uint4(0, 0, 0, 0);
   m[2] = make_uint4(0, 0, 0, 0);
 }
-
-__device__ __forceinline__ uint32_t load_u32(const uint8_t *p) { // (frames sit at any byte of the file)
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-__device__ __forceinline__ uint32_t load_u16(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-__device__ __forceinline__ uint32_t frame_bytes(uint32_t mn) { return 11 + 4 * ((mn & 15) + 1 + (mn >> 4) + 1); }
 
 // ---- sampling --------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_frames_valid(const uint8_t *records, const uint64_t *offsets, const uint16_t *frames, const uint8_t *malformed,
@@ -95,27 +89,9 @@ __global__ __launch_bounds__(256) void k_frames_draw(const uint8_t *records, con
   *(uint2 *)(picks + 2 * (size_t)i) = make_uint2(r, f);
 }
 
-// ---- lane order of a batch of picks: frame descending, so that the 64 prefixes a wave walks are of similar length.  One workgroup;
-// frames past 1,023 share a bucket (the engine ends a game at turn 1,000).
+// ---- lane order of a batch of picks: frame descending, longest prefix first
 __global__ __launch_bounds__(1024) void k_frames_order(const uint32_t *picks, uint32_t n, uint32_t *order) {
-  __shared__ uint32_t hist[1024];
-  const uint32_t tid = threadIdx.x;
-  hist[tid] = 0;
-  __syncthreads();
-  for (uint32_t i = tid; i < n; i += 1024) atomicAdd(&hist[1023u - min(picks[2 * (size_t)i + 1], 1023u)], 1u);
-  __syncthreads();
-  const uint32_t own = hist[tid];
-  for (uint32_t off = 1; off < 1024; off <<= 1) {
-    const uint32_t v = tid >= off ? hist[tid - off] : 0;
-    __syncthreads();
-    hist[tid] += v;
-    __syncthreads();
-  }
-  const uint32_t start = hist[tid] - own;
-  __syncthreads();
-  hist[tid] = start;
-  __syncthreads();
-  for (uint32_t i = tid; i < n; i += 1024) order[atomicAdd(&hist[1023u - min(picks[2 * (size_t)i + 1], 1023u)], 1u)] = i;
+  order_desc(n, order, [&](uint32_t i) { return picks[2 * (size_t)i + 1]; });
 }
 
 // ---- the walk --------------------------------------------------------------------------------------------------------------------
@@ -136,33 +112,16 @@ struct PickArgs {
 constexpr int PICK_COLD_BYTES = (sizeof(PickArgs) + 15) & ~15;
 constexpr int PICK_LDS_BYTES = 24 * 64 * 4 + TABLE_PAD + PICK_COLD_BYTES;
 
-template <class P>
-__device__ __forceinline__ P cold_ptr_at(const lds_u32 *cold, size_t byte_off) { // a 64-bit pointer parked in LDS
-  return (P)((uint64_t)cold[byte_off / 4] | ((uint64_t)cold[byte_off / 4 + 1] << 32));
-}
-__device__ __forceinline__ bool member(uint32_t n, uint64_t lo, uint32_t hi, uint32_t c) { // c among the n choice bytes
-  bool in = false;
-#pragma unroll
-  for (uint32_t i = 0; i < OAKGPU_MAX_CHOICES; ++i) in |= i < n && (i < 8 ? (uint32_t)(lo >> (8 * i)) & 0xFF : hi) == c;
-  return in;
-}
-
-// k_replay_records' shape: persistent lanes, one pick each, refilled from eight queue heads when their pick is settled; the queue is
-// k_frames_order's order, longest prefix first.  Per frame k of the pick's record, in the replay check's order: the game has ended
-// (EARLY_END), a legal-choice count differs (COUNT), a stored choice is not legal (ILLEGAL), else at k == f the snapshot, else
-// update(c1, c2).  The grid is the batch's waves up to what the device holds at four waves per SIMD.
-constexpr uint32_t REFILL_EVERY = 8, REFILL_LANES = 16; // free lanes refill every n-th iteration (a power of two), or at once when this many are free
-constexpr uint32_t QUEUE_HEADS = 8, QUEUE_HEAD_STRIDE = 64; // eight queue heads, 64 words (one 256-byte line) apart
-constexpr uint32_t PICK_NONE = 0xFFFFFFFFu, PICK_DONE = 0xFFFFFFFEu;
+// Persistent lanes, one pick each, refilled from the queue (record_walk.hpp) when their pick is settled; the queue is k_frames_order's
+// order, longest prefix first.  Per frame k of the pick's record: the replay check (frame_check), and on a playable frame at k == f
+// the snapshot, else the update.  The grid is the batch's waves up to what the device holds (resident_walk_waves).
 template <int WPS>
 __global__ __launch_bounds__(64, WPS) void k_frames_pick(PickArgs a_in) {
   extern __shared__ __align__(16) uint8_t smem[];
   lds_u32 *party = (lds_u32 *)smem;
   using ER = EngineR<64, false>;
   Tables T = stage_tables((lds_u8 *)smem + ER::PARTY_WORDS * 64 * 4, OAK_MOVE_WORDS, OAK_MOVE_MAXPP, OAK_SPECIES_W0, OAK_SPECIES_W1, OAK_TYPE_CHART, OAK_BOOSTS);
-  // the pointers are parked in LDS and read back on the cold paths (k_replay_records' reason: as kernel arguments they would hold
-  // SGPRs the turn-step's exec masks need)
-  lds_u32 *cold = (lds_u32 *)((lds_u8 *)smem + ER::PARTY_WORDS * 64 * 4 + TABLE_PAD);
+  lds_u32 *cold = (lds_u32 *)((lds_u8 *)smem + ER::PARTY_WORDS * 64 * 4 + TABLE_PAD); // the arguments, parked (cold_ptr_at)
   if (threadIdx.x < sizeof(PickArgs) / 4) cold[threadIdx.x] = ((const uint32_t *)&a_in)[threadIdx.x];
   __syncthreads();
 #define PA_PTR(field, type) cold_ptr_at<type>(cold, offsetof(PickArgs, field))
@@ -171,39 +130,21 @@ __global__ __launch_bounds__(64, WPS) void k_frames_pick(PickArgs a_in) {
   ER e;
   e.m = party + threadIdx.x;
   e.T = T;
-  uint32_t slot = PICK_NONE, f = 0, k = 0, res = 0, mn = 0, c1 = 0, c2 = 0; // slot: this lane's pick, or none yet / none left
+  uint32_t slot = LANE_NONE, f = 0, k = 0, res = 0, mn = 0, c1 = 0, c2 = 0; // slot: this lane's pick, or none yet / none left
   const uint8_t *fp = nullptr; // frame k of this lane's record
-  // wave-uniform scalar state in one word: bits 8-10 the current queue head, 12-15 heads seen dry, 16-23 an iteration counter, bit 0 dry
-  uint32_t ust = (blockIdx.x & 7u) << 8;
+  uint32_t ust = queue_state(blockIdx.x);
   for (;;) {
-    const bool need = slot == PICK_NONE;
+    const bool need = slot == LANE_NONE;
     const uint64_t mask = __ballot(need);
     bool load = false;
-    ust = (ust & ~0xFF0000u) | ((ust + 0x10000u) & 0xFF0000u);
-    if (mask && !(ust & 1u) && (((ust >> 16) & (REFILL_EVERY - 1)) == 0 || (uint32_t)__popcll(mask) >= REFILL_LANES || __ballot(slot < PICK_DONE) == 0)) {
-      uint64_t rem = mask;
+    if (refill_due(ust, mask, __ballot(slot < LANE_DONE) != 0)) {
       uint32_t my = 0;
-      bool got = false;
-      for (;;) { // head s hands out the queue positions s, s + 8, s + 16, ... (at most eight turns: a dry head is left for good)
-        const uint32_t shard = (ust >> 8) & 7u, need_n = (uint32_t)__popcll(rem);
-        const uint32_t lim = n > shard ? (n - shard + 7u) >> 3 : 0u;
-        uint32_t base = 0;
-        if (wl == 0) base = atomicAdd(PA_PTR(heads, uint32_t *) + shard * QUEUE_HEAD_STRIDE, need_n);
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        const uint32_t avail = base < lim ? (lim - base < need_n ? lim - base : need_n) : 0u;
-        const uint32_t rank = (uint32_t)__popcll(rem & ((1ull << wl) - 1));
-        if (((rem >> wl) & 1) && rank < avail) { my = shard + ((base + rank) << 3); got = true; }
-        if (avail == need_n) break;
-        rem = __ballot(need && !got);
-        ust = (ust & ~(7u << 8)) | (((shard + 1u) & 7u) << 8);
-        ust += 1u << 12;
-        if (((ust >> 12) & 15u) >= 8u) { ust |= 1u; break; }
-      }
+      const bool got = queue_take(ust, cold, offsetof(PickArgs, heads), n, need, mask, wl, my);
       if (need) {
-        if (got) { slot = PA_PTR(order, const uint32_t *)[my]; load = true; } // (my < n: below its head's limit)
-        else slot = PICK_DONE;
+        if (got) { slot = PA_PTR(order, const uint32_t *)[my]; load = true; }
+        else slot = LANE_DONE;
       }
-    } else if (mask && (ust & 1u) && need) slot = PICK_DONE;
+    } else if (need && queue_dry(ust)) slot = LANE_DONE;
     if (__ballot(load)) {
       if (load) { // the pick: settled here when it names no frame of a well-formed, finished game
         const uint2 pk = *(const uint2 *)(PA_PTR(picks, const uint32_t *) + 2 * (size_t)slot);
@@ -228,38 +169,29 @@ __global__ __launch_bounds__(64, WPS) void k_frames_pick(PickArgs a_in) {
         }
         if (status != STATUS_PENDING) {
           store_meta_failed(PA_PTR(meta, uint32_t *), slot, status, where);
-          slot = PICK_NONE;
+          slot = LANE_NONE;
         }
       }
     }
-    if (__ballot(slot != PICK_DONE) == 0) break;
-    if (slot < PICK_DONE) {
-      uint32_t status = STATUS_PENDING;
-      if (res & 15) status = OAKGPU_REPLAY_EARLY_END;
-      else {
-        const uint32_t m = (mn & 15) + 1, nn = (mn >> 4) + 1;
-        const auto l1 = e.choices(e.S, (res >> 4) & 3); // (normalised frame: S = P1, F = P2)
-        const auto l2 = e.choices(e.F, (res >> 6) & 3);
-        if (l1.n != m || l2.n != nn) status = OAKGPU_REPLAY_COUNT;
-        else if (!member(l1.n, l1.lo, l1.hi, c1) || !member(l2.n, l2.lo, l2.hi, c2)) status = OAKGPU_REPLAY_ILLEGAL;
-        else if (k == f) { // the picked frame: the snapshot
+    if (__ballot(slot != LANE_DONE) == 0) break;
+    if (slot < LANE_DONE) {
+      typename ER::Choices l1, l2;
+      const uint32_t status = frame_check(e, res, mn, c1, c2, l1, l2).status;
+      if (status == STATUS_PENDING) {
+        if (k == f) { // the picked frame: the snapshot
           const uint32_t r = PA_PTR(picks, const uint32_t *)[2 * (size_t)slot];
           const uint32_t rel = (uint32_t)(fp - (PA_PTR(records, const uint8_t *) + PA_PTR(offsets, const uint64_t *)[r]));
           e.store_battle_global(PA_PTR(snap, uint8_t *) + (size_t)slot * 384);
           store_meta(PA_PTR(meta, uint32_t *), slot, OAKGPU_REPLAY_OK, res, k, e.S.dur, e.F.dur, l1, l2, rel, r);
-          slot = PICK_NONE;
+          slot = LANE_NONE;
         } else {
-          // the next frame's three bytes are loaded before this turn's update: the dependent load overlaps the turn-step (k < f: it exists)
-          const uint32_t a1 = c1, a2 = c2;
-          fp += 11 + 4 * (m + nn);
-          mn = fp[0]; c1 = fp[1]; c2 = fp[2];
-          res = e.update(a1, a2);
+          res = play_frame(e, fp, mn, c1, c2, true); // (k < f: the next frame exists)
           ++k;
         }
       }
-      if (status != STATUS_PENDING) {
+      if (status != STATUS_PENDING) { // (behind the join, as k_replay_records' verdict)
         store_meta_failed(PA_PTR(meta, uint32_t *), slot, status, k);
-        slot = PICK_NONE;
+        slot = LANE_NONE;
       }
     }
   }
@@ -455,17 +387,9 @@ __global__ __launch_bounds__(256) void k_frames_count_ok(const uint8_t *status, 
 } // namespace oak
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-#define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return oakgpu_fail_hip((int)_e, #x); } while (0)
-
 // (struct oakgpu_corpus: oakgpu_internal.h -- corpuseval.hip walks the same corpus)
 
 namespace {
-
-template <class T>
-int dev_alloc(T *&p, size_t count) {
-  HIPCHK(hipMalloc((void **)&p, std::max<size_t>(count * sizeof(T), 16)));
-  return 0;
-}
 
 void cache_free(oakgpu_corpus *k) { // the sampling caches (the stream must be idle)
   for (auto &v : k->valids) if (v.d) (void)hipFree(v.d);
@@ -560,14 +484,14 @@ int oakgpu_corpus_create(oakgpu_ctx *c, const uint8_t *buffer, size_t size, oakg
   hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(c);
   int rc = 0;
   if (dev_alloc(k->records, stop) || dev_alloc(k->offsets, n) || dev_alloc(k->frames, n) || dev_alloc(k->malformed, n) || dev_alloc(k->aligned, (size_t)n * 384) ||
-      dev_alloc(k->first, n) || dev_alloc(scratch, (size_t)n * 2) || dev_alloc(k->heads, oak::tf::QUEUE_HEADS * oak::tf::QUEUE_HEAD_STRIDE))
+      dev_alloc(k->first, n) || dev_alloc(scratch, (size_t)n * 2) || dev_alloc(k->heads, oak::walk::QUEUE_HEADS * oak::walk::QUEUE_HEAD_STRIDE))
     rc = -1;
   int cus = 0;
   if (!rc) {
     const hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, oakgpu_ctx_device(c));
     if (e != hipSuccess || cus <= 0) rc = oakgpu_fail_hip((int)e, "oakgpu_corpus_create: hipDeviceGetAttribute");
   }
-  k->resident_waves = (uint32_t)std::max(cus, 1) * 4u * 4u;
+  k->resident_waves = oak::walk::resident_walk_waves(cus);
   auto up = [&](void *dst, const void *src, size_t bytes) {
     if (rc || !bytes) return;
     const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream);

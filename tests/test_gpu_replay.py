@@ -173,6 +173,49 @@ def test_reports_do_not_depend_on_the_batch(gpu_ctx):
     assert split == ref
 
 
+def _shortest_singles(gpu_ctx):
+    """The ~20 shortest games' records and the single-record replay of each (report fields, battle, durations)."""
+    if "short" not in _CORPUS:
+        games, recs = _oracle_corpus()
+        short = [recs[i] for i in sorted(range(len(recs)), key=lambda i: len(games[i][2]))[:20]]
+        singles = []
+        for r in short:
+            o = replay_check(gpu_ctx, r, want_states=True)
+            singles.append((tuple(int(o["reports"][f][0]) for f in ("frame", "status", "player", "expected", "got")),
+                            o["battles"][0].tobytes(), o["durations"][0].tobytes()))
+        _CORPUS["short"] = (short, singles)
+    return _CORPUS["short"]
+
+
+@pytest.mark.parametrize("n", [1, 7, 8, 9, 64, 65, 513])
+def test_queue_take_hands_every_record_out_once(gpu_ctx, n):
+    """The eight-head queue at its edges: fewer records than heads (heads whose limit is 0), a head that runs dry inside a take, a
+    queue longer than one take per head (513 = 8 x 64 + 1).  A take that drops a record leaves its report at the fill; one that hands
+    a record out twice or to the wrong lane shows as another record's report or state."""
+    from hipmem import Dev
+    from oak_amd import _lib
+    short, singles = _shortest_singles(gpu_ctx)
+    assert len({s[1] for s in singles}) == len(singles)                 # the games end in different states: a swap would show
+    blob = b"".join(short[i % len(short)] for i in range(n))
+    idx = replay_index(blob)
+    assert len(idx["offsets"]) == n and not idx["malformed"].any()
+    fill = 0xEE
+    raw = np.dtype([("frame", "<u4"), ("status", "u1"), ("player", "u1"), ("expected", "u1"), ("got", "u1")])
+    devs = [Dev(np.frombuffer(blob, np.uint8)), Dev(idx["offsets"]), Dev(idx["frames"]), Dev(idx["malformed"].astype(np.uint8)),
+            Dev(np.zeros(n, raw), fill=fill), Dev(np.zeros((n, 384), np.uint8), fill=fill), Dev(np.zeros((n, 8), np.uint8), fill=fill)]
+    try:
+        _lib.check(gpu_ctx.lib.oakgpu_replay_records_dev(gpu_ctx.handle, *(d.p for d in devs[:4]), n, *(d.p for d in devs[4:])))
+        gpu_ctx.synchronize()
+        rep, battles, durations = (d.host() for d in devs[4:])
+    finally:
+        for d in devs:
+            d.free()
+    assert not (rep.view(np.uint8).reshape(n, 8) == fill).all(1).any()  # every report was written
+    for i in range(n):
+        got = (tuple(int(rep[f][i]) for f in ("frame", "status", "player", "expected", "got")), battles[i].tobytes(), durations[i].tobytes())
+        assert got == singles[i % len(short)], i
+
+
 def test_scale_gpu_built_corpus_with_one_percent_damaged():
     """65,536 games built on the GPU as tools/replay_bench.py builds them, 1 % damaged: through tests/replay_scale_check.py in a child
     process -- the corpus is played with torch tensors, and torch must initialise the GPU before the library does."""

@@ -84,9 +84,9 @@ def test_every_frame_of_the_corpus_in_one_call(gpu_ctx):
     assert (k == 1).any() and (k == 9).any() and dup[:, :, :2].any() and (exp["iterations"] != 0).any() and (exp["nash_policies"] != 0).any()
 
 
-@pytest.mark.parametrize("n", [1, 7, 8, 9, 63, 64, 65, 257])
+@pytest.mark.parametrize("n", [1, 7, 8, 9, 63, 64, 65, 257, 513])
 def test_pick_counts(gpu_ctx, n):
-    """Fewer picks than a wave, the wave's edges, several waves; frame 0 and a record's last frame are among them."""
+    """Fewer picks than a wave, the wave's edges, several waves, more than one take per queue head (513 = 8 x 64 + 1); frame 0 and a record's last frame are among them."""
     games, recs, tref, corpus = _world(gpu_ctx)
     every = _all_picks(tref)
     rng = np.random.default_rng(n)
