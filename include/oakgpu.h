@@ -586,6 +586,55 @@ int oakgpu_corpus_inference(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_corpus *cor
 int oakgpu_corpus_evaluate(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_corpus *corpus, const oakgpu_loss_params *p, uint32_t chunk_rows,
                            oakgpu_corpus_losses *total, oakgpu_corpus_losses *per_record);
 
+/* ---- Batches of whole games between two policies, resident on the device: the reference's `vs` (cpp/src/vs.cc:107-408) in the one
+ * form that needs no tree,   vs --budget=0 --bandit=pucb-1.0 --policy-mode=p --p1-eval=A --p2-eval=B   -- with a zero budget a contextual
+ * bandit's Output carries only the root prior, the softmax of the policy head's legal logits (search/mcts.h:196-209), and mode `p` samples
+ * from it (util/policy.h:22-106): each side plays its network's raw policy.  n games start from the caller's states (as oakgpu_rollout_dev
+ * takes them) and run turn by turn -- oakgpu_tree_step_dev, oakgpu_leaf_eval_policy_dev, the pick -- until each has ended or made
+ * max_turns updates (result type 0 then, value 0.5).
+ *   Draws per game and turn, from the game's own fast_prng state (8 bytes, in / out):
+ *     both seats RANDOM: one uniform_64; c1 = p1_choices[seed % m], c2 = p2_choices[(seed >> 32) % n] -- the rollout kernels' rule, so such
+ *       a call equals oakgpu_rollout_dev with prep = 0 in every output byte;
+ *     otherwise seat p1 first, then seat p2: a POLICY seat with one legal choice draws nothing and plays it (vs.cc:258,273); a POLICY seat with
+ *       k > 1 draws one uniform (util/random.h:109-112) and takes sample_pdf of its policy (random.h:123-132); a RANDOM seat draws one
+ *       uniform_64 and plays choices[seed % k].
+ *   The policy of a POLICY seat over its k legal logits l, in the network's order: prior_i = expf(l_i) / sum with the sum in fp32 in index
+ *   order and the quotient in double (search/util/softmax.h:5-15 into Output's doubles); temp != 1: pow(x, temp), renormalised; entries below
+ *   `min` zeroed, renormalised (policy.h:70-95).  A policy zeroed entirely is the reference's "RuntimePolicy: zero policy, mode: p": refused
+ *   before anything is launched where that is known (min > 1); otherwise that game stops there with values_out = NaN and results_out = 0xFF, counts in
+ *   none of the four counters, and the call returns -1 with the lowest such game index in its message -- every other game's outputs are complete.
+ *   Outputs are indexed by the caller's game index and depend on nothing but the game: not on poll, compact_below, n or the rest of the batch.
+ * turns_out: updates made; values_out: 1 / 0 / 0.5 as the rollout's; battles_out / durations_out (nullable; battles_out 16-byte aligned): the
+ * final states; choice_log (nullable): n x log_turns x 2 bytes (c1, c2), game-major, the first log_turns turns of every game -- entries no
+ * game reaches are not written.  counts_out (host, nullable): wins, ties, losses of seat p1, games stopped at max_turns.
+ *   Schedule: finished rows are retired, and the host reads the live count, every `poll` turns; when the live share of the resident rows falls
+ * below compact_below the live rows are compacted (stable, into the other half of a double buffer) and the evaluator and the tree step run on
+ * the live prefix only.  The workspace belongs to the context.  The _dev call takes device arrays and returns with the games complete (it
+ * waits for the stream at every poll); the other takes host arrays. */
+#define OAKGPU_SEAT_RANDOM 0   /* the rollout kernel's rule */
+#define OAKGPU_SEAT_POLICY 1   /* the network's prior, RuntimePolicy mode "p" with budget 0 */
+typedef struct {
+  int32_t kind;                /* OAKGPU_SEAT_* */
+  oakgpu_net *net;             /* POLICY: required (fp32 or discrete handle, loaded on the context's device); RANDOM: ignored */
+  double temp, min;            /* RuntimePolicy::Options temp / min (util/policy.h:70-95); 0 / 0 mean 1 / 0 */
+} oakgpu_seat;
+typedef struct {
+  oakgpu_seat p1, p2;
+  uint32_t max_turns;          /* updates per game before it is stopped with result type 0 (0 = 1000) */
+  uint32_t poll;               /* host looks at the live count every `poll` turns (0 = 16) */
+  float compact_below;         /* compact the resident rows when live / rows falls below this (0 = 0.5; > 1 = at every poll; < 0 = never) */
+  uint32_t log_turns;          /* capacity of choice_log per game, 0 = no log */
+} oakgpu_policy_games_params;
+int oakgpu_policy_games_dev(oakgpu_ctx *ctx, const oakgpu_policy_games_params *params, const uint8_t *battles, const uint8_t *durations,
+                            const uint8_t *results_in, uint8_t *prng_state, uint32_t n, uint8_t *results_out, uint32_t *turns_out,
+                            float *values_out, uint8_t *battles_out, uint8_t *durations_out, uint8_t *choice_log, uint64_t counts_out[4]);
+int oakgpu_policy_games(oakgpu_ctx *ctx, const oakgpu_policy_games_params *params, const uint8_t *battles, const uint8_t *durations,
+                        const uint8_t *results_in, uint8_t *prng_state, uint32_t n, uint8_t *results_out, uint32_t *turns_out,
+                        float *values_out, uint8_t *battles_out, uint8_t *durations_out, uint8_t *choice_log, uint64_t counts_out[4]);
+/* Diagnostic: the schedule of the calling thread's last oakgpu_policy_games* call -- rows the evaluator and the tree step ran over, summed
+ * over the turns (the games' own need is the sum of turns_out); turns looped; compactions; polls. */
+int oakgpu_policy_games_last_stats(uint64_t out[4]);
+
 /* the compile-time engine switches this library was built with (DESIGN 0 order): MULTIHIT_ROLL_FIRST, PSYWAVE_SHOWDOWN,
  * COUNTER_SHOWDOWN, ACCURACY_LAST.  The default build reports 1, 1, 0, 0. */
 int oakgpu_engine_switches(int out[4]);

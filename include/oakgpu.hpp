@@ -14,10 +14,12 @@
 //   OakGPU::replay_check       <- the replay self-check of py/battle/frames.h:52-67, for a whole file at once
 //   OakGPU::FrameCorpus, EncodedFrames <- pyoak.sample + Py::Battle::EncodedFrames (pyoak.cc:111-245, py/battle/encoded-frames.h)
 //   OakGPU::FrameCorpus::inference / evaluate <- pyoak.cpp_inference over a whole corpus (pyoak.cc:331-392) and battle.py's loss terms
+//   OakGPU::PolicyGames        <- the per-game loop of `vs --budget=0 --bandit=pucb-1.0 --policy-mode=p` (vs.cc:107-408), a batch of games at once
 //   OakGPU::Exchange           <- the path's one collective: per-root means on the device + RCCL all-gather (no reference analogue)
 // Errors surface as std::runtime_error, like the reference's loaders (cpp/src/search.cc:81-146).
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
@@ -522,6 +524,71 @@ public:
 private:
   oakgpu_root_steps *rs_{};
   uint32_t roots_;
+};
+
+// Whole games between two policies, a batch resident on the device (oakgpu_policy_games*, include/oakgpu.h): the reference's `vs`
+// (cpp/src/vs.cc:107-408) with --budget=0 --bandit=pucb-1.0 --policy-mode=p, where each side samples its network's root prior.
+class PolicyGames {
+public:
+  struct Params {
+    const Network *p1 = nullptr, *p2 = nullptr; // nullptr: a RANDOM seat (the rollout's rule)
+    double p1_temp = 1, p1_min = 0, p2_temp = 1, p2_min = 0; // RuntimePolicy::Options (util/policy.h:8-12)
+    uint32_t max_turns = 1000, poll = 16;
+    float compact_below = 0.5f;
+    uint32_t log_turns = 0;
+  };
+  struct Result {
+    std::vector<uint8_t> result;      // final pkmn_result byte (type 0: stopped at max_turns)
+    std::vector<uint32_t> turns;      // updates made
+    std::vector<float> value;         // 1 / 0 / 0.5 for seat p1
+    std::vector<uint8_t> choice_log;  // n x log_turns x 2 (c1, c2); 0xFF where a game did not get
+    uint64_t wins = 0, ties = 0, losses = 0, stopped = 0;
+  };
+  PolicyGames(Context &ctx, const Params &params) : ctx_{ctx}, log_turns_{params.log_turns} {
+    p_.p1 = oakgpu_seat{params.p1 ? OAKGPU_SEAT_POLICY : OAKGPU_SEAT_RANDOM, params.p1 ? params.p1->get() : nullptr, params.p1_temp, params.p1_min};
+    p_.p2 = oakgpu_seat{params.p2 ? OAKGPU_SEAT_POLICY : OAKGPU_SEAT_RANDOM, params.p2 ? params.p2->get() : nullptr, params.p2_temp, params.p2_min};
+    p_.max_turns = params.max_turns;
+    p_.poll = params.poll;
+    p_.compact_below = params.compact_below;
+    p_.log_turns = params.log_turns;
+  }
+  // device pointers (n games; the outputs by game index, battles_out / durations_out / choice_log nullable); returns {wins, ties, losses, stopped}
+  std::array<uint64_t, 4> run_dev(const uint8_t *battles, const uint8_t *durations, const uint8_t *results_in, uint8_t *prng_state, uint32_t n,
+                                  uint8_t *results_out, uint32_t *turns_out, float *values_out, uint8_t *battles_out = nullptr,
+                                  uint8_t *durations_out = nullptr, uint8_t *choice_log = nullptr) {
+    std::array<uint64_t, 4> counts{};
+    check(oakgpu_policy_games_dev(ctx_.get(), &p_, battles, durations, results_in, prng_state, n, results_out, turns_out, values_out, battles_out,
+                                  durations_out, choice_log, counts.data()));
+    return counts;
+  }
+  // host form: the games start at `leaves`; device_rng holds one fast_prng state per game and is advanced; the leaves receive the final states
+  Result run(std::vector<Leaf> &leaves, std::vector<uint64_t> &device_rng) {
+    const uint32_t n = static_cast<uint32_t>(leaves.size());
+    if (device_rng.size() != n) throw std::runtime_error{"oakgpu: one RNG state per game required"};
+    std::vector<uint8_t> battles(size_t{n} * OAKGPU_BATTLE_SIZE), durations(size_t{n} * OAKGPU_DURATIONS_SIZE), results(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      std::memcpy(&battles[size_t{i} * OAKGPU_BATTLE_SIZE], leaves[i].battle, OAKGPU_BATTLE_SIZE);
+      std::memcpy(&durations[size_t{i} * OAKGPU_DURATIONS_SIZE], leaves[i].durations, OAKGPU_DURATIONS_SIZE);
+      results[i] = leaves[i].result;
+    }
+    Result out{std::vector<uint8_t>(n), std::vector<uint32_t>(n), std::vector<float>(n), std::vector<uint8_t>(size_t{n} * log_turns_ * 2, 0xFF)};
+    uint64_t counts[4] = {};
+    check(oakgpu_policy_games(ctx_.get(), &p_, battles.data(), durations.data(), results.data(), reinterpret_cast<uint8_t *>(device_rng.data()), n,
+                              out.result.data(), out.turns.data(), out.value.data(), battles.data(), durations.data(),
+                              log_turns_ ? out.choice_log.data() : nullptr, counts));
+    for (uint32_t i = 0; i < n; ++i) {
+      std::memcpy(leaves[i].battle, &battles[size_t{i} * OAKGPU_BATTLE_SIZE], OAKGPU_BATTLE_SIZE);
+      std::memcpy(leaves[i].durations, &durations[size_t{i} * OAKGPU_DURATIONS_SIZE], OAKGPU_DURATIONS_SIZE);
+      leaves[i].result = out.result[i];
+    }
+    out.wins = counts[0]; out.ties = counts[1]; out.losses = counts[2]; out.stopped = counts[3];
+    return out;
+  }
+
+private:
+  Context &ctx_;
+  oakgpu_policy_games_params p_{};
+  uint32_t log_turns_;
 };
 
 } // namespace OakGPU

@@ -30,6 +30,7 @@ SYMBOLS = [
     "oakgpu_party_table_create", "oakgpu_party_table_destroy", "oakgpu_party_table_fill_dev", "oakgpu_party_table_fill", "oakgpu_leaf_eval_table_dev",
     "oakgpu_leaf_eval_policy_table_dev", "oakgpu_party_table_last_misses", "oakgpu_party_table_rows", "oakgpu_party_table_width", "oakgpu_party_key", "oakgpu_party_variant",
     "oakgpu_set_search_party_table", "oakgpu_search_party_table_stats", "oakgpu_leaf_eval_table", "oakgpu_leaf_eval_policy_table",
+    "oakgpu_policy_games_dev", "oakgpu_policy_games", "oakgpu_policy_games_last_stats",
 ]
 
 
@@ -94,6 +95,15 @@ class CorpusTerms(C.Structure):       # oakgpu_corpus_terms
 class CorpusLosses(C.Structure):      # oakgpu_corpus_losses
     _fields_ = [("sq_err", C.c_double), ("ce1", C.c_double), ("ce2", C.c_double), ("rows", C.c_uint64), ("excluded", C.c_uint64), ("failed", C.c_uint64),
                 ("mse", C.c_double), ("ce_p1", C.c_double), ("ce_p2", C.c_double)]
+
+
+class Seat(C.Structure):              # oakgpu_seat
+    _fields_ = [("kind", C.c_int32), ("net", C.c_void_p), ("temp", C.c_double), ("min", C.c_double)]
+
+
+class PolicyGamesParams(C.Structure):  # oakgpu_policy_games_params
+    _fields_ = [("p1", Seat), ("p2", Seat), ("max_turns", C.c_uint32), ("poll", C.c_uint32), ("compact_below", C.c_float),
+                ("log_turns", C.c_uint32)]
 
 
 # include/pkmn.h: the libpkmn-named single-battle ABI (batch-of-one wrappers, pkmn_shim.hip)
@@ -260,6 +270,9 @@ def load():
     lib.oakgpu_search_party_table_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     lib.oakgpu_leaf_eval_table.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp]
     lib.oakgpu_leaf_eval_policy_table.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
+    lib.oakgpu_policy_games_dev.argtypes = [vp, C.POINTER(PolicyGamesParams), vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
+    lib.oakgpu_policy_games.argtypes = [vp, C.POINTER(PolicyGamesParams), vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
+    lib.oakgpu_policy_games_last_stats.argtypes = [vp]
     _lib = lib
     return lib
 

@@ -3221,6 +3221,7 @@ static int net_load_file(oakgpu_ctx *ctx, const char *path, bool discrete, oakgp
 int oakgpu_net_load(oakgpu_ctx *ctx, const char *path, oakgpu_net **out) { return net_load_file(ctx, path, false, out); }
 int oakgpu_net_load_discrete(oakgpu_ctx *ctx, const char *path, oakgpu_net **out) { return net_load_file(ctx, path, true, out); }
 int oakgpu_net_is_discrete(const oakgpu_net *net) { return net && net->discrete ? 1 : 0; }
+int oakgpu_net_device(const oakgpu_net *net) { return net ? net->device : -1; } // oakgpu_internal.h
 
 int oakgpu_net_set_main_precision(oakgpu_net *net, int mode) {
   if (net && net->discrete) { oakgpu_fail_msg("oakgpu_net_set_main_precision: the network is quantized (OAKGPU_MAIN_INT8)"); return -1; }

@@ -1621,6 +1621,7 @@ struct oakgpu_ctx {
   hipEvent_t tev[4];
   bool tev_valid;
   Block replay_ws{nullptr, 0};             // oakgpu_replay_records_dev: queue heads, queue order, first requests, aligned battles
+  Block games_ws{nullptr, 0};              // oakgpu_policy_games_dev (policyplay.hip): the resident rows, both halves, and the per-turn arrays
   void *attachment = nullptr;              // oakgpu_internal.h: the tree search's cached batch slots
   void (*attachment_dtor)(void *) = nullptr;
 };
@@ -1660,6 +1661,7 @@ void *oakgpu_ctx_workspace(oakgpu_ctx *c, int slot, size_t bytes) {
   if (slot % 3 == 2) c->ws2_owner = nullptr; // (whoever asks for the work-list block is about to write its head)
   return grow_block(c, c->ws[slot % 3], bytes ? bytes : 1);
 }
+void *oakgpu_ctx_games_workspace(oakgpu_ctx *c, size_t bytes) { return grow_block(c, c->games_ws, bytes ? bytes : 1); }
 void oakgpu_ctx_set_ws2_owner(oakgpu_ctx *c, const void *table) { c->ws2_owner = table; }
 const void *oakgpu_ctx_ws2_owner(const oakgpu_ctx *c) { return c->ws2_owner; }
 void oakgpu_ctx_count_search_table(oakgpu_ctx *c, uint64_t fills, uint64_t evals) { c->search_table_fills += fills; c->search_table_evals += evals; }
@@ -1824,6 +1826,7 @@ void oakgpu_destroy(oakgpu_ctx *c) {
   for (auto &b : c->stage) if (b.p) (void)hipFree(b.p);
   for (auto &b : c->ws) if (b.p) (void)hipFree(b.p);
   if (c->replay_ws.p) (void)hipFree(c->replay_ws.p);
+  if (c->games_ws.p) (void)hipFree(c->games_ws.p);
   if (c->tev_valid) for (auto &e : c->tev) (void)hipEventDestroy(e);
   if (c->h_table) {
     (void)hipHostFree(c->h_table);

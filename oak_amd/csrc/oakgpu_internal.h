@@ -27,6 +27,8 @@ int oakgpu_ctx_enter(oakgpu_ctx *ctx);                 // hipSetDevice(ctx->devi
 // Per-context device workspaces (slot 0: battle embeddings, 1: policy activations, 2: party-slot work list): grow-only, one per context = one
 // per stream, so two contexts evaluating the same network never share scratch memory.  nullptr on failure (error recorded).
 void *oakgpu_ctx_workspace(oakgpu_ctx *ctx, int slot, size_t bytes);
+// The whole-game loop's rows (policyplay.hip): one more grow-only block of the context, freed by oakgpu_destroy.  nullptr on failure.
+void *oakgpu_ctx_games_workspace(oakgpu_ctx *ctx, size_t bytes);
 // Staging buffers of the host-pointer entry points: a grow-only cache owned by the context (slot k of a call = the k-th
 // buffer it asks for).  A HostCall brackets one host-pointer call: its destructor synchronises the context's stream on
 // EVERY exit path, so no async copy to / from the caller's buffers is still in flight when the call returns.
@@ -64,6 +66,7 @@ const void *oakgpu_ctx_ws2_owner(const oakgpu_ctx *ctx);
 struct oakgpu_party_table;
 struct oakgpu_net;
 extern "C" int oakgpu_party_table_is_for(const oakgpu_party_table *table, const oakgpu_net *net);
+extern "C" int oakgpu_net_device(const oakgpu_net *net); // leafnet.hip: the device the weights live on (-1: null)
 // Host threads of the tree walks started by the CALLING thread (0 = the default rule): callers that run several searches side
 // by side -- oakgpu_search_many, oakgpu_selfplay_games -- give each its share of the cores.
 void oakgpu_set_thread_search_threads(int threads);

@@ -12,6 +12,8 @@
 //           (+ k, status, where, picks): one walk per record and one evaluator call per chunk of rows (oakgpu_corpus_inference)
 //   solve_matrix(row_payoff, discretize_factor) -> (p1, p2, value)                        :394-426, 711
 //   read_battle_data(path) -> [(bytes, frame_count), ...]                                 :43-71, 713
+//   policy_games(battles, durations, results, prng, p1_network, p2_network, ...) -> whole games between two networks' raw policies, the
+//           per-game loop of `vs --budget=0 --bandit=pucb-1.0 --policy-mode=p` (vs.cc:107-408) for a batch at once (oakgpu_policy_games)
 //   network hyper-parameter constants                                                     :586-596
 //   EncodedBattleFrames(size) {the reference's numpy fields + status, where, picks}, clear(), from_bytes(bytes, size)  py/battle/encoded-frames.h
 //   SampleIndexer() {get(path), prune(paths), size()}, sample(encoded_frames, indexer, threads, max_battle_length, min_iterations)  :73-245
@@ -526,6 +528,60 @@ PYBIND11_MODULE(pyoak, m) {
         return result;
       },
       py::arg("path"));
+
+  m.def(
+      "policy_games",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> battles, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> durations,
+         py::array_t<uint8_t, py::array::c_style | py::array::forcecast> results, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> prng,
+         const std::string &p1_network, const std::string &p2_network, bool p1_discrete, bool p2_discrete, double p1_temp, double p1_min, double p2_temp,
+         double p2_min, uint32_t max_turns, uint32_t poll, float compact_below, uint32_t log_turns) {
+        // n games from the given states, seat p1 against seat p2; an empty network path is a RANDOM seat (include/oakgpu.h)
+        const py::ssize_t n = results.size();
+        if (battles.size() != n * OAKGPU_BATTLE_SIZE || durations.size() != n * OAKGPU_DURATIONS_SIZE || prng.size() != n * 8)
+          throw std::runtime_error("policy_games: expecting battles [n, 384], durations [n, 8], results [n], prng [n, 8]");
+        std::lock_guard<std::mutex> lock(g_ctx_mu);
+        oakgpu_net *nets[2] = {nullptr, nullptr};
+        const std::string *paths[2] = {&p1_network, &p2_network};
+        const bool disc[2] = {p1_discrete, p2_discrete};
+        int rc = 0;
+        for (int s = 0; s < 2 && !rc; ++s) {
+          if (paths[s]->empty()) continue;
+          if (s == 1 && *paths[0] == *paths[1] && disc[0] == disc[1]) { nets[1] = nets[0]; continue; } // (one handle: one evaluator call per turn)
+          rc = disc[s] ? oakgpu_net_load_discrete(context(), paths[s]->c_str(), &nets[s]) : oakgpu_net_load(context(), paths[s]->c_str(), &nets[s]);
+        }
+        oakgpu_policy_games_params p{};
+        p.p1 = oakgpu_seat{nets[0] ? OAKGPU_SEAT_POLICY : OAKGPU_SEAT_RANDOM, nets[0], p1_temp, p1_min};
+        p.p2 = oakgpu_seat{nets[1] ? OAKGPU_SEAT_POLICY : OAKGPU_SEAT_RANDOM, nets[1], p2_temp, p2_min};
+        p.max_turns = max_turns; p.poll = poll; p.compact_below = compact_below; p.log_turns = log_turns;
+        py::array_t<uint8_t> results_out(n), prng_out({n, (py::ssize_t)8}), battles_out({n, (py::ssize_t)OAKGPU_BATTLE_SIZE}),
+            durations_out({n, (py::ssize_t)OAKGPU_DURATIONS_SIZE}), log({n, (py::ssize_t)log_turns, (py::ssize_t)2});
+        py::array_t<uint32_t> turns(n);
+        py::array_t<float> values(n);
+        std::memcpy(prng_out.mutable_data(), prng.data(), (size_t)n * 8);
+        std::fill_n(log.mutable_data(), log.size(), (uint8_t)0xFF);
+        uint64_t counts[4] = {0, 0, 0, 0};
+        if (!rc)
+          rc = oakgpu_policy_games(context(), &p, battles.data(), durations.data(), results.data(), prng_out.mutable_data(), (uint32_t)n, results_out.mutable_data(),
+                                   turns.mutable_data(), values.mutable_data(), battles_out.mutable_data(), durations_out.mutable_data(),
+                                   log_turns ? log.mutable_data() : nullptr, counts);
+        const std::string err = rc ? oakgpu_last_error() : "";
+        if (nets[1] && nets[1] != nets[0]) oakgpu_net_free(context(), nets[1]);
+        if (nets[0]) oakgpu_net_free(context(), nets[0]);
+        if (rc) throw std::runtime_error(err);
+        py::dict d;
+        d["results"] = results_out;
+        d["turns"] = turns;
+        d["values"] = values;
+        d["prng"] = prng_out;
+        d["battles"] = battles_out;
+        d["durations"] = durations_out;
+        d["log"] = log;
+        d["counts"] = py::make_tuple(counts[0], counts[1], counts[2], counts[3]);
+        return d;
+      },
+      py::arg("battles"), py::arg("durations"), py::arg("results"), py::arg("prng"), py::arg("p1_network") = "", py::arg("p2_network") = "",
+      py::arg("p1_discrete") = false, py::arg("p2_discrete") = false, py::arg("p1_temp") = 1.0, py::arg("p1_min") = 0.0, py::arg("p2_temp") = 1.0,
+      py::arg("p2_min") = 0.0, py::arg("max_turns") = 1000, py::arg("poll") = 16, py::arg("compact_below") = 0.0f, py::arg("log_turns") = 0);
 
   py::class_<EncodedBattleFrames>(m, "EncodedBattleFrames")
       .def(py::init<size_t>(), py::arg("size"))
