@@ -73,7 +73,7 @@ int oakgpu_set_queue_order(oakgpu_ctx *ctx, int on);
 int oakgpu_set_spread(oakgpu_ctx *ctx, int lanes);
 /* Long-playout migration inside a launch (mode 0 off, 1 = launches that saturate the device (default), 2 = every queue launch:
  * tests): a wave hands a playout that is still running after `long_steps` turn-steps (default 300; 99.5% end before 250) to
- * `adopters` dedicated waves (0 = one per two compute units), which from the first donation on hold only such playouts -- a dozen
+ * `adopters` dedicated waves (0 = one per four compute units), which from the first donation on hold only such playouts -- a dozen
  * per wave at the top priority of their SIMD -- so the 1,000-step chains that end a launch advance at a sparse wave's pace
  * long before the device drains.  State travels as the regrouping rounds' bit-exact image; results never depend on it.
  * Co-residency of the launch's waves is NOT required (other launches may share the device, e.g. a second context's group launch):
@@ -86,13 +86,19 @@ int oakgpu_set_migration(oakgpu_ctx *ctx, int mode, int long_steps, int adopters
  * hp stop changing at a median of turn-step 85, so they leave their full wave at ~step 135 instead of 300.  A heuristic about
  * WHO finishes a playout only; results never depend on it. */
 int oakgpu_set_migration_window(oakgpu_ctx *ctx, int window);
-/* The queue kernel takes a PROVEN frozen standstill -- both actives frozen (gen 1 never thaws by itself), neither side able to leave or
- * act, different speeds: a turn-step then draws nothing and changes nothing but the turn counter -- to its last turn-step in one go
- * (exact; tests/test_gpu_parity.py::test_frozen_standstill_skip_is_exact).  on = 0 plays every turn-step instead (A / B; also
- * OAKGPU_STANDSTILL_SKIP=0 at context creation).  Default 1.  The one-lane-per-playout kernels (k_rollout_regs, k_root_step) never skip. */
+/* The queue kernel takes a PROVEN inert standstill to its last turn-step in one go: each side is either frozen with no way out (gen 1
+ * never thaws by itself) or forced -- Rage-locked, or down to Struggle on its last Pokemon -- into a move the foe's types are immune
+ * to, and nothing else acts on either.  Every such turn-step changes nothing but the turn counter and battle.rng, by a constant 0..3
+ * draws (speed tie, full-paralysis rolls), which the skip applies as one jump of the generator (exact;
+ * tests/test_gpu_inert_standstill.py, tests/test_gpu_parity.py::test_frozen_standstill_skip_is_exact).  on = 0 plays every turn-step
+ * instead (A / B; also OAKGPU_STANDSTILL_SKIP=0 at context creation).  Default 1.  The one-lane-per-playout kernels (k_rollout_regs,
+ * k_root_step) never skip. */
 int oakgpu_set_standstill_skip(oakgpu_ctx *ctx, int on);
+/* Words of that block written by the queue kernel's standstill skip (cleared by every queue launch). */
+#define OAKGPU_CTL_FAST_FORWARDED 44 /* playouts whose inert standstill was taken in one go */
+#define OAKGPU_CTL_SKIPPED_STEPS 45  /* turn-steps those playouts skipped (they are part of steps_out) */
 /* Diagnostic (synchronises the stream): the 64 control words of the last queue launch -- [32] / [33]
- * the queue order's two counters, [40] donations, [41] adoptions, [42] bulk waves that left, [63] error bits (0 = none:
+ * the queue order's two counters, [40] donations, [41] adoptions, [42] bulk waves that left, [44] / [45] above, [63] error bits (0 = none:
  * 1 a ticket never arrived, 2 an adopter gave up waiting) -- STICKY: no launch clears them; oakgpu_synchronize reports a
  * non-zero word as a failed call and clears it, so the error of any launch since the last synchronize is seen, not only the
  * last launch's. */

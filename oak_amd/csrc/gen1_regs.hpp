@@ -1349,22 +1349,78 @@ struct EngineR {
     }
     return a;
   }
-  // Is this position a frozen-versus-frozen standstill whose every further turn-step is the same turn-step?  (k_rollout_queue
-  // skips all but the last of them.)  Both sides: request Move, status exactly FRZ, hp > 0, no Leech Seed and no binding volatile
-  // (the first drains a Pokemon that cannot move, the second is cleared by the turn's epilogue and would free the side's choices),
-  // and NO WAY OUT: either the active is the side's last Pokemon, or it is locked into its move (recharging, Rage, thrashing,
-  // charging, Bide: `legal` offers the forced move only, and none of these counters runs while before_move returns at the freeze
-  // check in front of them, so the lock never ends).  And speeds that differ (no tie draw).  Then update_frame does: select_move
-  // x 2 (a locked side: nothing; else clears the flinch bit and writes last selected move and last move index from the choice),
-  // an order decision that draws nothing, before_move x 2 -> `status & FRZ`: last used move = 0, done; no residual damage (FRZ
-  // excludes PSN / BRN, no Leech Seed), nobody faints; turn + 1, tie at 1,000.  Everything it writes is either the same every
-  // time or overwritten by the next turn-step before it is read.
-  __device__ __forceinline__ bool frozen_standstill(uint32_t result) const {
+  // Is this position an INERT standstill: is every further turn-step the same no-op, one that changes nothing but the turn counter,
+  // battle.rng by a constant number of draws, and fields the next turn-step overwrites before anything reads them?  Returns that
+  // number of draws per turn-step (0..3), or -1 when the position is not proven inert.  (k_rollout_queue skips all but the last of
+  // them.)  A proof over the engine's own code paths, not a comparison of states.
+  //   THE FRAME: both requests Move, 1 <= turn < 1000, both actives alive, no Leech Seed and no binding volatile on either side (the
+  // first drains a Pokemon that cannot act, the second ends before_move early and is cleared by the turn's epilogue).
+  //   Each side is inert in one of two ways (inert_side):
+  //   FROZEN -- status exactly FRZ (gen 1 never thaws by itself; FRZ excludes PSN / BRN: no residual damage) and NO WAY OUT: the
+  // active is the side's last Pokemon, or it is locked into its move (recharging, Rage, thrashing, charging, Bide: `legal` offers the
+  // forced move only, and none of these counters runs, because before_move returns at the freeze check in front of them).
+  // select_move does nothing for a locked side; for a free one it clears the flinch bit and writes last selected move and last move
+  // index from the choice -- both overwritten by the next turn-step's select_move; before_move: last used move = 0, done.
+  //   FORCED INTO A MOVE THAT CANNOT TOUCH THE FOE -- `legal` offers one forced choice, because of V_RAGE (select_move returns at
+  // once: the selected move stays) or because the side is on its last Pokemon with no usable move (Struggle: select_move writes
+  // last selected = Struggle, last move index = 0, every time).  Status none or PAR (no sleep counter, no residual).  before_move
+  // then passes every gate without a write: no flinch / recharging bit to clear, no disable counting (nor a disabled slot), no
+  // confusion, Bide, thrashing or binding counter; a PAR side rolls for full paralysis -- ONE draw -- and both outcomes are no-ops:
+  // paralysed, it clears volatile bits and the attacking / binding durations, which are required to be clear already, and leaves
+  // last used move, its counterable bit and last damage alone, so those must already hold what the other outcome writes (last used
+  // = the move, counterable 0, last damage 0).  Not paralysed, execute_selected runs the move: not charging and not a charge move
+  // (no volatile set), last used = the move, counterable = 0, NO PP (Rage: before_move says skip; Struggle: slot 0), not Metronome
+  // / Mirror Move / thrashing (draws, locks), Rage sets the V_RAGE bit that is already set; run_move: a damaging move that is
+  // neither fixed damage (those ignore the type chart), OHKO, Counter, nor Explode / Jump Kick (which hurt the user when they
+  // fail) and that is TYPE-IMMUNE against the foe's current types stops at `go == false`: last damage = 0, clear_binding (nothing
+  // to clear) -- no accuracy roll, no crit, no damage roll, no secondary.  post_action: nobody fainted, no residual.
+  //   DRAWS: one per PAR side of the second kind, and one for the speed tie -- drawn only when the speeds are equal and the Quick
+  // Attack / Counter tests of turn_prologue do not decide the order.  Those tests read the selected moves AFTER select_move: with a
+  // frozen side that still has a free choice they depend on the choice, so equal speeds are accepted only when both sides'
+  // selected moves are forced (locked, or Struggle); otherwise the speeds must differ, and then no order decision draws.  Who
+  // acts first changes nothing: neither action reads what the other writes.
+  __device__ __forceinline__ bool inert_side(const SideR &x, const SideR &y, uint32_t &sel, bool &sel_forced, bool &par) const {
     constexpr uint32_t locked = V_RECHARGING | V_RAGE | V_THRASHING | V_CHARGING | V_BIDE;
-    const bool stuckS = (S.misc & 63) == 1 || (S.vlo & locked) != 0, stuckF = (F.misc & 63) == 1 || (F.vlo & locked) != 0;
-    return result == mk_result(0, C_MOVE, C_MOVE) && turn >= 1 && turn < 1000 &&
-           status(S) == ST_FRZ && status(F) == ST_FRZ && stuckS && stuckF && (S.misc & 1) && (F.misc & 1) &&
-           ((S.vlo | F.vlo) & (V_BINDING | V_LEECHSEED)) == 0 && spe(S) != spe(F) && hp(S) > 0 && hp(F) > 0;
+    const uint32_t st = status(x);
+    const Legal L = legal(x, C_MOVE);
+    const bool struggle = !(x.vlo & (locked | V_BINDING)) && L.sw == 0 && L.mv == 0; // legal(): the forced Struggle (move, data 0)
+    sel = struggle ? (uint32_t)M_Struggle : last_sel(x); // the selected move after this turn-step's select_move, where it is forced
+    sel_forced = struggle || (x.vlo & locked) != 0;
+    par = false;
+    if (st == ST_FRZ) return (x.misc & 63) == 1 || (x.vlo & locked) != 0;
+    constexpr uint32_t busy = V_FLINCH | V_RECHARGING | V_CONFUSION | V_BIDE | V_THRASHING | V_CHARGING | V_INVULNERABLE | V_MULTIHIT | V_BINDING;
+    if ((st != 0 && st != ST_PAR) || !(struggle || (x.vlo & V_RAGE)) || (x.vlo & busy) != 0 || disable_left(x) != 0 || disable_move(x) != 0 ||
+        dget(x, 25, 3) != 0 || dget(x, 28, 3) != 0) return false;
+    const Move mv = move_data(sel);
+    const uint32_t eff = mv.effect(), ft = types(y);
+    const bool plain = mv.bp() != 0 && sel != M_Counter && eff != E_SpecialDamage && eff != E_SuperFang && eff != E_OHKO && eff != E_Charge &&
+                       eff != E_Metronome && eff != E_MirrorMove && eff != E_Thrashing && eff != E_Explode && eff != E_JumpKick;
+    const bool type_immune = chart(mv.type(), ft & 15) == 0 || chart(mv.type(), ft >> 4) == 0;
+    par = st == ST_PAR;
+    return plain && type_immune && last_used(x) == sel && lm_counterable(absp(x)) == 0 && (!par || last_damage == 0);
+  }
+  __device__ __forceinline__ int inert_standstill(uint32_t result) const {
+    if (!(result == mk_result(0, C_MOVE, C_MOVE) && turn >= 1 && turn < 1000 && (S.misc & 1) && (F.misc & 1) && hp(S) > 0 && hp(F) > 0 &&
+          ((S.vlo | F.vlo) & (V_BINDING | V_LEECHSEED)) == 0)) return -1;
+    uint32_t mS, mF;
+    bool fS, fF, pS, pF;
+    if (!inert_side(S, F, mS, fS, pS) || !inert_side(F, S, mF, fF, pF)) return -1;
+    bool tie = false;
+    if (spe(S) == spe(F)) {
+      if (!(fS && fF)) return -1;
+      tie = (mS == M_QuickAttack) == (mF == M_QuickAttack) && (mS == M_Counter) == (mF == M_Counter);
+    }
+    return (int)tie + (int)pS + (int)pF;
+  }
+  // battle.rng after n more draws: the LCG's n-fold composition by squaring (x -> A x + C composed with itself is x -> A^2 x + (A + 1) C)
+  __device__ __forceinline__ void rng_jump(uint32_t n) {
+    uint64_t accA = 1, accC = 0, curA = 0x5D588B656C078965ull, curC = 0x0000000000269EC3ull;
+    for (; n; n >>= 1) {
+      if (n & 1) { accA *= curA; accC = accC * curA + curC; }
+      curC *= curA + 1;
+      curA *= curA;
+    }
+    rng = accA * rng + accC;
   }
   // one random-policy turn-step of the rollout (choices x2 + update), frame-agnostic
   __device__ __forceinline__ uint32_t random_step(uint32_t result, uint32_t hi, uint32_t lo) {

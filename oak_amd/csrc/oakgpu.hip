@@ -433,7 +433,8 @@ struct RoundArgs {
   uint32_t n_adopters;      // 0 = off; waves [0, n_adopters) adopt
   uint32_t long_steps;      // bits 0-15: a bulk wave donates a playout that is still running after this many turn-steps;
                             // bits 16-24: ... or whose actives' {slot, hp} have not changed for this many turn-steps (256: never)
-  uint32_t no_skip;         // 1: a proven frozen standstill is played turn by turn like everything else (oakgpu_set_standstill_skip: A/B)
+  uint32_t no_skip;         // 1: a proven inert standstill is played turn by turn like everything else (oakgpu_set_standstill_skip: A/B)
+  uint32_t *stats;          // words 44-45 of the context's control block: {playouts fast-forwarded, turn-steps skipped}
 };
 
 // One launch drains a GROUP of independent batches (oakgpu_rollout_group_dev): the queue hands out GLOBAL playout
@@ -738,22 +739,29 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
 #ifdef OAKGPU_TIMELINE
     tl_steps += (unsigned long long)__popcll(__ballot(playing));
 #endif
-    // A standstill that can be PROVEN: both actives FROZEN (gen 1 never thaws by itself), neither side able to leave (its last
-    // Pokemon, or locked into a move), nothing that acts on a Pokemon that cannot move (Leech Seed, binding) and different speeds.  Such a turn-step draws
-    // nothing from battle.rng (no speed tie), executes no move (before_move returns at the freeze check) and leaves every byte as
-    // it was except the turn counter and the fields the NEXT turn-step overwrites unconditionally -- last selected move, last
-    // move index, last used move = 0, the flinch bit -- see EngineR::frozen_standstill.  So all but the last of the remaining
-    // turn-steps are taken at once: turn and step count advance, the choice stream advances by its two draws per turn-step, and
-    // the last turn-step runs for real (it writes those fields and, at turn 1,000, the tie).  These are the stalemates the queue
-    // order cannot see in the teams (round 4: 1-5 per 1.31 M playouts, started anywhere in the queue, each ~950 dependent
-    // turn-steps at a lone lane's 4.7 us: the launches they ended took 16.4-16.6 ms instead of 14.7-14.9).  Exact, not a
-    // heuristic: tests/test_gpu_parity.py holds it to the oracle, which plays every turn.
-    if (playing && stale >= (8u << 24) && !(ust & U_NO_SKIP) && e.frozen_standstill(result)) {
+    // A standstill that can be PROVEN (EngineR::inert_standstill): each side is either FROZEN with no way out (gen 1 never thaws by
+    // itself) or FORCED -- Rage-locked, or down to Struggle on its last Pokemon -- into a move the foe's types are immune to, and
+    // nothing acts on a Pokemon that cannot act (no Leech Seed, no binding).  Such a turn-step executes no move beyond its type
+    // check, spends no PP, and leaves every byte as it was except the turn counter, battle.rng -- by a CONSTANT number c of draws:
+    // the speed tie of equal speeds and a paralysed side's full-paralysis roll, both outcomes of which are no-ops -- and the fields
+    // the NEXT turn-step overwrites before anything reads them.  So all but the last of the remaining turn-steps are taken at
+    // once: turn and step count advance, the choice stream advances by its two draws per turn-step, battle.rng jumps c draws per
+    // turn-step ahead, and the last turn-step runs for real (it writes last selected / used move, last damage 0, the counterable
+    // bits and, at turn 1,000, the tie).  These are the launch's stalemates -- Rage or Struggle against a Ghost, a frozen Ghost --
+    // ~1,100 of 1.31 M playouts, each otherwise ~850 dependent turn-steps on an adopter.  Exact, not a heuristic:
+    // tests/test_gpu_inert_standstill.py and tests/test_gpu_parity.py hold it to the oracle, which plays every turn.  The `stale`
+    // gate keeps ordinary lanes from ever evaluating the predicate.
+    if (playing && stale >= (8u << 24) && !(ust & U_NO_SKIP)) {
+      const int draws = e.inert_standstill(result);
       const uint32_t by_steps = max_steps - steps, by_turn = 1000u - e.turn;
       const uint32_t skip = (by_steps < by_turn ? by_steps : by_turn) - 1u; // (both >= 1 while playing)
-      for (uint32_t k = 0; k < skip; ++k) { (void)g.next32(); (void)g.next32(); }
-      e.turn += skip;
-      steps += skip;
+      if (draws >= 0 && skip != 0) {
+        for (uint32_t k = 0; k < skip; ++k) { (void)g.next32(); (void)g.next32(); }
+        e.rng_jump((uint32_t)draws * skip);
+        e.turn += skip;
+        steps += skip;
+        atomicAdd((unsigned long long *)COLD_Q(stats, uint32_t *), 1ull | ((unsigned long long)skip << 32)); // {playouts, turn-steps}: one atomic
+      }
     }
     if (playing) {
       const uint32_t hi = g.next32(), lo = g.next32(); // uniform_64 = hi << 32 | lo
@@ -1600,12 +1608,12 @@ struct oakgpu_ctx {
   int tail_lanes;         //      lanes per wave of that dispatch that take playouts (0 = all 64)
   int migrate;            // long-playout migration (k_rollout_queue): 0 off, 1 (default) for launches that saturate the device, 2 always
   int migrate_steps;      //   a bulk wave donates a playout still running after this many turn-steps (default 300)
-  int migrate_adopters;   //   adopter waves (0 = one per two CUs)
+  int migrate_adopters;   //   adopter waves (0 = one per four CUs)
   int migrate_window;     //   ... or whose actives' {slot, hp} stood still for this many turn-steps (0 = off, at most 255)
   int migrate_used;       //   the last queue launch ran with migration: oakgpu_synchronize reports its error word
   int spread_lanes;       // launches that do not fill the device: lanes per wave that take playouts (-1 automatic, 0 / 64 = all)
   int queue_order;        // 1 (default): a saturated launch hands its playouts out likely-longest first (k_queue_order)
-  int standstill_skip;    // 1 (default): the queue kernel takes a PROVEN frozen standstill to its last turn-step in one go (exact); 0: plays every turn
+  int standstill_skip;    // 1 (default): the queue kernel takes a PROVEN inert standstill to its last turn-step in one go (exact); 0: plays every turn
   uint32_t *d_order;      // total entries
   size_t order_n;
   int n_cu;               // compute units of the device
@@ -2034,7 +2042,10 @@ static int launch_group(oakgpu_ctx *c, const oak::BatchDesc *descs, uint32_t cou
   // for most of its life (a group of batches) runs as a single dispatch (measured: DESIGN.md 3)
   // ... and so does a launch capped at a few steps (stepping a resident batch turn by turn): there is no tail to regroup
   const bool tail_pack = saturated && c->tail_below > 0 && max_steps > 64;
-  const uint32_t adopters = (uint32_t)(c->migrate_adopters > 0 ? c->migrate_adopters : (c->n_cu + 1) / 2); // measured best: one per two CUs
+  // (one per FOUR CUs since the stalemate chains are fast-forwarded instead of played: the adopters hold ~700 live long playouts per
+  // 1.31 M instead of ~1,800, and every adopter is a wave that takes no bulk work once donations exist.  Measured on the driver
+  // command, profiles/r13_drain.json: 16 / 32 / 64 / 96 / 128 adopters 8.42 / 8.89 / 9.00 / 8.84 / 8.90 G at the median of four runs)
+  const uint32_t adopters = (uint32_t)(c->migrate_adopters > 0 ? c->migrate_adopters : (c->n_cu + 3) / 4);
   // long-playout migration (k_rollout_queue) replaces the regrouping rounds where it applies: a single dispatch
   const bool migrate = !tail_pack && max_steps > (uint32_t)c->migrate_steps && waves > adopters &&
                        (c->migrate == 2 || (c->migrate == 1 && saturated && max_steps >= 500));
@@ -2074,6 +2085,7 @@ static int launch_group(oakgpu_ctx *c, const oak::BatchDesc *descs, uint32_t cou
     q.order = r == 0 ? order : nullptr;
     q.long_steps = (uint32_t)(c->migrate_steps > 0xFFFF ? 0xFFFF : c->migrate_steps) | (uint32_t)(c->migrate_window > 0 ? c->migrate_window : 256) << 16;
     q.no_skip = c->standstill_skip ? 0u : 1u;
+    q.stats = c->d_queue + OAKGPU_CTL_FAST_FORWARDED;
     if (migrate) { q.adopt_ctl = c->d_queue + 40; q.adopt_list = lists[0]; q.n_adopters = adopters; }
     q.list_in = r ? lists[(r - 1) & 1] : nullptr;
     q.n_in = r ? c->d_queue + 2 * r - 1 : nullptr; // = count_out of round r - 1

@@ -91,11 +91,11 @@ class Context:
         return fills.value, evals.value
 
     def set_standstill_skip(self, on=True):
-        """The queue kernel's exact fast-forward of proven frozen standstills (oakgpu_set_standstill_skip); results never change."""
+        """The queue kernel's exact fast-forward of proven inert standstills (oakgpu_set_standstill_skip); results never change."""
         _lib.check(self.lib.oakgpu_set_standstill_skip(self.handle, 1 if on else 0))
 
     def queue_counters(self):
-        """The 64 control words of the last queue launch (oakgpu_get_queue_counters): [40] donations, [41] adoptions, [63] sticky error bits."""
+        """The 64 control words of the last queue launch (oakgpu_get_queue_counters): [40] donations, [41] adoptions, [44] playouts fast-forwarded, [45] turn-steps skipped, [63] sticky error bits."""
         out = np.zeros(64, dtype=np.uint32)
         _lib.check(self.lib.oakgpu_get_queue_counters(self.handle, out.ctypes.data_as(C.c_void_p)))
         return out

@@ -1,7 +1,7 @@
 """Manual GPU tool: the wave timeline of the bench's TIMED group launch (profile build with -DOAKGPU_TIMELINE).  bench.py runs a set-up
 pass over its 20 batches and 5 warm-up batches in front of the timed 20, and the per-lane choice streams continue from pass to pass, so
 the timed launch plays OTHER playouts than a fresh launch of the same battles (tools/timeline.py): this replays exactly that sequence.
-usage: bench_timeline.py <lib.so> [reps]"""
+usage: bench_timeline.py <lib.so> [reps] [adopter waves of that build: default one per four CUs = 64; 128 up to round 12]"""
 import ctypes as C
 import os
 import sys
@@ -33,7 +33,7 @@ for k in range(G):
     descs[k] = _lib.RolloutBatch(battles[k].data_ptr(), durations[k].data_ptr(), rin[k].data_ptr(), prng[k].data_ptr(), n, rout[k].data_ptr(),
                                  steps[k].data_ptr(), values[k].data_ptr(), None, None)
 torch.cuda.synchronize()
-na = 128
+na = int(sys.argv[3]) if len(sys.argv) > 3 else int(os.environ.get("OAKGPU_MIGRATE_ADOPTERS", "0")) or 64
 lib.oakgpu_timeline.argtypes = [C.c_void_p, C.c_int]
 for rep in range(REPS):
     prng.copy_(prng0)
@@ -53,6 +53,6 @@ for rep in range(REPS):
     last = np.argsort(end)[-4:]
     c = np.zeros(64, dtype=np.uint32)
     _lib.check(lib.oakgpu_get_queue_counters(h, c.ctypes.data_as(C.c_void_p)))
-    print("rep %d: launch %.3f ms  dry %.0f us  bulk exit p99 %.0f max %.0f  adopters max %.0f  donations %d  last waves: %s" % (
-        rep, a.elapsed_time(b), np.median(dry[dry > 0]), np.percentile(end[na:], 99), end[na:].max(), end[:na].max(), int(c[40]),
+    print("rep %d: launch %.3f ms  dry %.0f us  bulk exit p99 %.0f max %.0f  adopters max %.0f  donations %d  fast-forwarded %d playouts / %d turn-steps  last waves: %s" % (
+        rep, a.elapsed_time(b), np.median(dry[dry > 0]), np.percentile(end[na:], 99), end[na:].max(), end[:na].max(), int(c[40]), int(c[44]), int(c[45]),
         " ".join("w%d@%.0f(%d steps)" % (w, end[w], tl[w, 4]) for w in last)), flush=True)
