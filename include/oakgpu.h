@@ -292,6 +292,11 @@ typedef struct {
 int oakgpu_search_agent(oakgpu_ctx *ctx, const uint8_t *battle, const uint8_t *durations, uint8_t result, const oakgpu_agent *agent,
                         uint32_t batch, uint64_t seed, oakgpu_search_output *out);
 void oakgpu_agent_networks_clear(oakgpu_ctx *ctx);
+/* The parser of oakgpu_search_agent* alone: the Agent's strings -> *params (batch as above, seed as given) and *net (the agent's
+ * network, loaded once per device and kept; NULL for "mc" / "fp"), with the same error texts.  For callers that run the search
+ * themselves, e.g. the forest search below. */
+int oakgpu_agent_params(oakgpu_ctx *ctx, const oakgpu_agent *agent, uint32_t batch, uint64_t seed, oakgpu_search_params *params,
+                        oakgpu_net **net);
 
 /* Diagnostic (no GPU involved): ONE player's bandit of the search above replayed for `steps` rounds -- select, then
  * update with values[t] -- so its arithmetic can be compared with the reference's bandit headers.  kind as in
@@ -310,6 +315,9 @@ int oakgpu_bandit_select_run(int kind, float c, float alpha, uint32_t k, const f
 int oakgpu_search(oakgpu_ctx *ctx, oakgpu_net *net /* nullable for eval = 0 */, const uint8_t *battle /* 384 */,
                   const uint8_t *durations /* 8 */, uint8_t result, const oakgpu_search_params *params,
                   oakgpu_search_output *out);
+/* Diagnostic (synchronises the search's stream): the continuing fast_prng state of lane 0 of the first batch slot of the LAST search on
+ * this context -- with batch = 1 the one stream that search drew from (what a tree of the forest search below must end on). */
+int oakgpu_search_stream(oakgpu_ctx *ctx, uint64_t *state);
 
 /* ---- RuntimeSearch::Heap (util/search.h:17-32, search.cc:17-58) and the resumable form of Search::run.
  * A heap keeps the tree of a search -- every node's bandit statistics -- between searches:
@@ -365,6 +373,79 @@ int oakgpu_search_many(oakgpu_ctx *const *ctxs, oakgpu_net *net, oakgpu_heap *co
 int oakgpu_search_agent_heap(oakgpu_ctx *ctx, oakgpu_heap *heap, const uint8_t *battle, const uint8_t *durations, uint8_t result,
                              const oakgpu_agent *agent, uint32_t batch, uint64_t seed, const oakgpu_search_output *previous,
                              oakgpu_search_output *out);
+
+/* ---- the forest search: n independent searches at once, ONE LANE PER TREE, every tree resident on the device (forest.hip).
+ * Where oakgpu_search parallelises inside one tree (a batch of descents, virtual loss, a host tree), this parallelises across trees:
+ * each tree runs the reference's strictly sequential iteration (mcts.h:250-447, no virtual loss) and the n trees advance in lockstep,
+ * so every kernel of an iteration -- root prep, tree step, leaf evaluation, back-up -- runs over n rows.  The form a game loop needs:
+ * thousands of positions, one small-budget search each.
+ *   Semantics.  Tree g of a call is the search oakgpu_search(ctx, net, battles + 384 g, durations + 8 g, results[g], {params with seed =
+ *   seeds[g], batch = 1}) runs, iteration for iteration; per iteration, in order: (1) root prep, oakgpu_rollout_dev(max_steps 0, prep 1)
+ *   on the tree's own fast_prng stream, whose state starts as the first splitmix64 output of seeds[g], | 1; (2) Bandit select, then visit,
+ *   for both players; (3) oakgpu_tree_step_dev with root_rolls at depth 0 and other_rolls below; (4) the walk goes on while the edge is
+ *   not terminal (a terminal edge ends it with the value of the result byte) and the child of (parent, i, j, 16-byte observation) --
+ *   created when new -- is initialised and above max_depth; (5) else the leaf is evaluated as oakgpu_search evaluates it, over ALL n
+ *   rows, finished ones included, so every stream advances as in the single search; (6) init (+ priors from the logits) at a node's first
+ *   evaluation; (7) update along the path; (8) root matrices: ++visits, value += the P1 value, in double.
+ *   Arithmetic.  The bandits are bandit.hpp's, compiled for the device without contraction; UCB trees equal the host search bit for bit in
+ *   every output.  PUCB priors use the device's expf where the host search uses the host's: a PUCB tree may differ from the host search and
+ *   is held to its own trace instead (tests/forest_ref.py).
+ *   Supported: bandit 0 (UCB) and 1 (PUCB, a forest created `contextual`, eval = 1); eval 0 / 1 / 2; integer budgets; fp32 and discrete
+ *   network handles.  Refused by name before any launch (oakgpu_forest_check): time budgets, matrix_ucb, UCB1 / Exp3 / PExp3,
+ *   iterations == 0 or > max_iterations, n > max_trees, a terminal root, a trace with trace_levels < max_depth.
+ *   Capacity.  A tree owns an arena of max_iterations + 1 nodes (an iteration creates at most one) and an open-addressing edge table of
+ *   at least twice as many slots; nothing grows during a call.  A full arena or table (impossible within the limits above) sets a sticky
+ *   error word: the lane stops, the call returns -1.
+ *   Outputs (oakgpu_forest_outputs: device arrays, all required): per tree m, n and the choice lists, the root matrices, iterations,
+ *   nodes, total_depth, initial_value and root logits / priors (PUCB; else 0), and the tree's continuing fast_prng state.
+ *   Trace (nullable; tests): n x iterations records, record (g, t) at byte (g * iterations + t) * OAKGPU_FOREST_TRACE_BYTES(trace_levels):
+ *   an oakgpu_forest_trace_head, then trace_levels oakgpu_forest_trace_level entries of which the first `levels` are meaningful (the rest 0).
+ *   Node ids count a tree's nodes in creation order, the root is 0.
+ * The calls: _create allocates the arenas on the context's device (the context must outlive the forest; all work runs on its stream);
+ * _search_dev takes device arrays and returns with the search complete (the host reads a 4-byte live count per tree level);
+ * _search takes host arrays, fills one oakgpu_search_output per tree as oakgpu_search does (process_output's empirical fields; the exact
+ * Nash solve only with solve_nash, else those fields are 0; duration_us = the whole call's), streams_out (nullable) n x u64, trace
+ * (nullable) a host buffer; _nodes reads `count` node records of one tree of the LAST call, from node `first`, into host memory;
+ * _check is the host-only validation both searches run first (results: host bytes, nullable = not checked). */
+typedef struct oakgpu_forest oakgpu_forest;
+typedef struct {
+  uint8_t *m, *n;                       /* n trees each */
+  uint8_t *p1_choices, *p2_choices;     /* n x 9 */
+  uint64_t *visit_matrix;               /* n x 81, [i * 9 + j] */
+  double *value_matrix;                 /* n x 81 */
+  uint64_t *iterations, *nodes, *total_depth;
+  double *initial_value;
+  double *p1_logit, *p2_logit, *p1_prior, *p2_prior; /* n x 9 */
+  uint64_t *stream;                     /* n: fast_prng state after the last iteration */
+} oakgpu_forest_outputs;
+typedef struct { float scores[9], priors[9]; uint32_t visits[9]; uint8_t k, pad[3]; } oakgpu_forest_bandit; /* k = 0: not initialised */
+typedef struct { oakgpu_forest_bandit p1, p2; } oakgpu_forest_node;
+typedef struct {
+  uint32_t levels;        /* tree levels walked = joint actions applied */
+  uint32_t leaf;          /* node the walk stopped at to evaluate; OAKGPU_FOREST_NO_NODE after a terminal edge */
+  uint8_t initialised;    /* 1: the leaf was initialised in this iteration */
+  uint8_t result_type;    /* result byte & 15 of the last edge: 0 = not terminal */
+  uint8_t pad[2];
+  float value;            /* the P1 value backed up */
+  float logits[18];       /* PUCB, initialised = 1: the leaf's p1 / p2 logits (9 each); else 0 */
+} oakgpu_forest_trace_head;
+typedef struct { uint32_t node; uint8_t i, j, pad[2]; } oakgpu_forest_trace_level;
+#define OAKGPU_FOREST_NO_NODE 0xFFFFFFFFu
+#define OAKGPU_FOREST_TRACE_BYTES(levels) (sizeof(oakgpu_forest_trace_head) + (size_t)(levels) * sizeof(oakgpu_forest_trace_level))
+int oakgpu_forest_create(oakgpu_ctx *ctx, uint32_t max_trees, uint32_t max_iterations, int contextual, oakgpu_forest **out);
+void oakgpu_forest_destroy(oakgpu_ctx *ctx, oakgpu_forest *forest); /* waits for ctx's stream; ctx == NULL (the context is gone): for the device */
+int oakgpu_forest_check(uint32_t max_trees, uint32_t max_iterations, int contextual, const oakgpu_search_params *params, int has_net,
+                        uint32_t n, const uint8_t *results, int has_trace, uint32_t trace_levels);
+int oakgpu_forest_search_dev(oakgpu_forest *forest, oakgpu_net *net, const oakgpu_search_params *params, const uint8_t *battles,
+                             const uint8_t *durations, const uint8_t *results, const uint64_t *seeds, uint32_t n,
+                             const oakgpu_forest_outputs *dev_out, void *trace, uint32_t trace_levels);
+int oakgpu_forest_search(oakgpu_forest *forest, oakgpu_net *net, const oakgpu_search_params *params, const uint8_t *battles,
+                         const uint8_t *durations, const uint8_t *results, const uint64_t *seeds, uint32_t n, oakgpu_search_output *out,
+                         int solve_nash, uint64_t *streams_out, void *trace, uint32_t trace_levels);
+int oakgpu_forest_nodes(oakgpu_forest *forest, uint32_t tree, uint32_t first, uint32_t count, oakgpu_forest_node *out);
+/* Diagnostic: the schedule of the forest's last call -- iterations run, tree levels stepped (= tree-step launches), kernel launches
+ * made (prep, steps, level kernels, evaluations, back-ups; an evaluation counts as one), host reads of the live count. */
+int oakgpu_forest_last_stats(const oakgpu_forest *forest, uint64_t out[4]);
 
 /* ---- the path's one exchange step: per-root pre-reduction on the device + RCCL all-gather over xGMI.
  * Root-parallel MCTS shards its roots contiguously over the GPUs of a node; each rank reduces its playouts' leaf values to

@@ -7,6 +7,7 @@
 //                                 value_policy_inference(b, d, m, n, c1, c2, p1, p2) that MCTS::Search::run calls (mcts.h:196-209,401-422)
 //   OakGPU::BatchedMonteCarlo  <- MCTS::MonteCarlo (mcts.h:21-23) + init_stats_and_rollout (mcts.h:448-496), batched
 //   OakGPU::TreeSearch         <- MCTS::Search::run (mcts.h:154-247): Node heap + the five joint bandits, leaves batched on the GPU
+//   OakGPU::SearchForest       <- MCTS::Search::run for many positions at once: one GPU lane per tree, the trees resident on the device
 //   OakGPU::run                <- RuntimeSearch::run (util/search.h:66, search.cc:150-313): the Agent's strings pick everything
 //   OakGPU::solve_matrix       <- LRSNash::solve_fast as called at mcts.h:643-649 / pyoak.cc:394-426 (exact)
 //   OakGPU::SharedDeviceRollout<- benchmark.cc:23-31: n playouts from one root driven by ONE sequential std::mt19937
@@ -301,6 +302,52 @@ inline oakgpu_search_output run(Context &ctx, const Leaf &input, const Agent &ag
   check(oakgpu_search_agent_heap(ctx.get(), heap ? heap->get() : nullptr, input.battle, input.durations, input.result, &a, batch, seed, previous, &out));
   return out;
 }
+
+// The forest search (include/oakgpu.h: oakgpu_forest_*): up to max_trees searches at once, one GPU lane per tree, every tree resident
+// on the device; tree g is TreeSearch::run(roots[g], {params, seed = seeds[g], batch = 1}) iteration for iteration.  params.bandit 0 / 1
+// (1 needs contextual = true, eval = 1 and a network), params.eval 0 / 1 / 2; the Nash fields are solved only with solve_nash.
+class SearchForest {
+public:
+  SearchForest(Context &ctx, uint32_t max_trees, uint32_t max_iterations, bool contextual = false) : ctx_{ctx} {
+    check(oakgpu_forest_create(ctx.get(), max_trees, max_iterations, contextual ? 1 : 0, &f_));
+  }
+  ~SearchForest() { oakgpu_forest_destroy(ctx_.get(), f_); }
+  SearchForest(const SearchForest &) = delete;
+  SearchForest &operator=(const SearchForest &) = delete;
+  std::vector<oakgpu_search_output> search(const oakgpu_search_params &params, const std::vector<Leaf> &roots, const std::vector<uint64_t> &seeds,
+                                           Network *net = nullptr, bool solve_nash = false, std::vector<uint64_t> *streams = nullptr) {
+    if (seeds.size() != roots.size()) throw std::runtime_error{"oakgpu: SearchForest::search: one seed per root"};
+    const uint32_t n = (uint32_t)roots.size();
+    std::vector<uint8_t> b((size_t)n * OAKGPU_BATTLE_SIZE), d((size_t)n * OAKGPU_DURATIONS_SIZE), r(n);
+    for (uint32_t g = 0; g < n; ++g) {
+      std::memcpy(b.data() + (size_t)g * OAKGPU_BATTLE_SIZE, roots[g].battle, OAKGPU_BATTLE_SIZE);
+      std::memcpy(d.data() + (size_t)g * OAKGPU_DURATIONS_SIZE, roots[g].durations, OAKGPU_DURATIONS_SIZE);
+      r[g] = roots[g].result;
+    }
+    std::vector<oakgpu_search_output> out(n);
+    if (streams) streams->assign(n, 0);
+    check(oakgpu_forest_search(f_, net ? net->get() : nullptr, &params, b.data(), d.data(), r.data(), seeds.data(), n, out.data(), solve_nash ? 1 : 0,
+                               streams ? streams->data() : nullptr, nullptr, 0));
+    return out;
+  }
+  // the same over arrays the caller holds on the device (dev_out: device arrays too)
+  void search_dev(const oakgpu_search_params &params, const uint8_t *battles, const uint8_t *durations, const uint8_t *results, const uint64_t *seeds,
+                  uint32_t n, const oakgpu_forest_outputs &dev_out, Network *net = nullptr) {
+    check(oakgpu_forest_search_dev(f_, net ? net->get() : nullptr, &params, battles, durations, results, seeds, n, &dev_out, nullptr, 0));
+  }
+  // `count` node records of one tree of the last call, from node `first`, in creation order (the root is node 0)
+  std::vector<oakgpu_forest_node> nodes(uint32_t tree, uint32_t first, uint32_t count) {
+    std::vector<oakgpu_forest_node> out(count);
+    oakgpu_forest_node none;
+    check(oakgpu_forest_nodes(f_, tree, first, count, count ? out.data() : &none));
+    return out;
+  }
+  oakgpu_forest *get() const noexcept { return f_; }
+
+private:
+  Context &ctx_;
+  oakgpu_forest *f_{};
+};
 
 // Exact Nash equilibrium of an integer m x n (<= 9 x 9) matrix game, row player maximising: {p1, p2, value / discretize}.
 inline std::tuple<std::vector<double>, std::vector<double>, double> solve_matrix(const std::vector<int32_t> &payoffs, int m, int n,

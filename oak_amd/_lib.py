@@ -31,6 +31,8 @@ SYMBOLS = [
     "oakgpu_leaf_eval_policy_table_dev", "oakgpu_party_table_last_misses", "oakgpu_party_table_rows", "oakgpu_party_table_width", "oakgpu_party_key", "oakgpu_party_variant",
     "oakgpu_set_search_party_table", "oakgpu_search_party_table_stats", "oakgpu_leaf_eval_table", "oakgpu_leaf_eval_policy_table",
     "oakgpu_policy_games_dev", "oakgpu_policy_games", "oakgpu_policy_games_last_stats",
+    "oakgpu_forest_create", "oakgpu_forest_destroy", "oakgpu_forest_check", "oakgpu_forest_search_dev", "oakgpu_forest_search", "oakgpu_forest_nodes",
+    "oakgpu_forest_last_stats", "oakgpu_search_stream", "oakgpu_agent_params",
 ]
 
 
@@ -104,6 +106,28 @@ class Seat(C.Structure):              # oakgpu_seat
 class PolicyGamesParams(C.Structure):  # oakgpu_policy_games_params
     _fields_ = [("p1", Seat), ("p2", Seat), ("max_turns", C.c_uint32), ("poll", C.c_uint32), ("compact_below", C.c_float),
                 ("log_turns", C.c_uint32)]
+
+
+class ForestOutputs(C.Structure):     # oakgpu_forest_outputs: one device pointer per array
+    _fields_ = [(name, C.c_void_p) for name in ("m", "n", "p1_choices", "p2_choices", "visit_matrix", "value_matrix", "iterations", "nodes",
+                                                "total_depth", "initial_value", "p1_logit", "p2_logit", "p1_prior", "p2_prior", "stream")]
+
+
+class ForestBandit(C.Structure):      # oakgpu_forest_bandit
+    _fields_ = [("scores", C.c_float * 9), ("priors", C.c_float * 9), ("visits", C.c_uint32 * 9), ("k", C.c_uint8), ("pad", C.c_uint8 * 3)]
+
+
+class ForestNode(C.Structure):        # oakgpu_forest_node
+    _fields_ = [("p1", ForestBandit), ("p2", ForestBandit)]
+
+
+class ForestTraceHead(C.Structure):   # oakgpu_forest_trace_head
+    _fields_ = [("levels", C.c_uint32), ("leaf", C.c_uint32), ("initialised", C.c_uint8), ("result_type", C.c_uint8), ("pad", C.c_uint8 * 2),
+                ("value", C.c_float), ("logits", C.c_float * 18)]
+
+
+class ForestTraceLevel(C.Structure):  # oakgpu_forest_trace_level
+    _fields_ = [("node", C.c_uint32), ("i", C.c_uint8), ("j", C.c_uint8), ("pad", C.c_uint8 * 2)]
 
 
 # include/pkmn.h: the libpkmn-named single-battle ABI (batch-of-one wrappers, pkmn_shim.hip)
@@ -273,6 +297,16 @@ def load():
     lib.oakgpu_policy_games_dev.argtypes = [vp, C.POINTER(PolicyGamesParams), vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
     lib.oakgpu_policy_games.argtypes = [vp, C.POINTER(PolicyGamesParams), vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
     lib.oakgpu_policy_games_last_stats.argtypes = [vp]
+    lib.oakgpu_forest_create.argtypes = [vp, u32, u32, i32, C.POINTER(vp)]
+    lib.oakgpu_forest_destroy.argtypes = [vp, vp]
+    lib.oakgpu_forest_destroy.restype = None
+    lib.oakgpu_forest_check.argtypes = [u32, u32, i32, C.POINTER(SearchParams), i32, u32, vp, i32, u32]
+    lib.oakgpu_forest_search_dev.argtypes = [vp, vp, C.POINTER(SearchParams), vp, vp, vp, vp, u32, C.POINTER(ForestOutputs), vp, u32]
+    lib.oakgpu_forest_search.argtypes = [vp, vp, C.POINTER(SearchParams), vp, vp, vp, vp, u32, C.POINTER(SearchOutput), i32, vp, vp, u32]
+    lib.oakgpu_forest_nodes.argtypes = [vp, u32, u32, u32, C.POINTER(ForestNode)]
+    lib.oakgpu_forest_last_stats.argtypes = [vp, C.POINTER(u64 * 4)]
+    lib.oakgpu_search_stream.argtypes = [vp, C.POINTER(u64)]
+    lib.oakgpu_agent_params.argtypes = [vp, C.POINTER(Agent), u32, u64, C.POINTER(SearchParams), C.POINTER(vp)]
     _lib = lib
     return lib
 

@@ -18,6 +18,13 @@
 #include <emmintrin.h>
 #define OAK_BANDIT_SSE2 1
 #endif
+// init / set_logits / select / visit / update also run on the device (forest.hip: one lane walks one tree); the host's
+// instructions are unchanged -- the SSE path above is the host's alone
+#if defined(__HIPCC__)
+#define OAK_BANDIT_HD __host__ __device__
+#else
+#define OAK_BANDIT_HD
+#endif
 
 namespace oak_search {
 
@@ -29,7 +36,7 @@ struct Bandit {
   float priors[9];
   uint32_t visits[9];
   uint8_t k = 0;
-  void init(uint8_t kk, int kind) {
+  OAK_BANDIT_HD void init(uint8_t kk, int kind) {
     k = kk;
     for (int i = 0; i < 9; ++i) {
       priors[i] = kk ? 1.0f / kk : 0.0f;
@@ -38,9 +45,9 @@ struct Bandit {
       else { scores[i] = 0.5f; visits[i] = 1; }
     }
   }
-  bool is_init() const { return k != 0; }
+  OAK_BANDIT_HD bool is_init() const { return k != 0; }
   // network logits -> priors (PUCB::softmax_logits = softmax.h:5-15) or initial gains (PExp3::softmax_logits: logit / eta)
-  void set_logits(const BanditParams &P, const float *logits) {
+  OAK_BANDIT_HD void set_logits(const BanditParams &P, const float *logits) {
     if (P.kind == B_PUCB) {
       float sum = 0;
       for (int i = 0; i < k; ++i) { const float y = std::exp(logits[i]); priors[i] = y; sum += y; }
@@ -51,7 +58,7 @@ struct Bandit {
     }
   }
   // `uniform` is called once per sampled selection (Exp3 / PExp3 with k > 1): the device's uniform() in (0, 1)
-  template <class U> uint8_t select(const BanditParams &P, U &&uniform, float &prob) const {
+  template <class U> OAK_BANDIT_HD uint8_t select(const BanditParams &P, U &&uniform, float &prob) const {
     prob = 1.0f;
     if (k == 1) return 0;
     if (P.kind >= B_EXP3) {
@@ -181,8 +188,8 @@ struct Bandit {
     }
   }
   // the visit of the counting bandits is booked at selection time (virtual loss), their score at back-up time
-  void visit(const BanditParams &P, uint8_t i) { if (P.kind < B_EXP3) ++visits[i]; }
-  void update(const BanditParams &P, uint8_t i, float value, float prob) {
+  OAK_BANDIT_HD void visit(const BanditParams &P, uint8_t i) { if (P.kind < B_EXP3) ++visits[i]; }
+  OAK_BANDIT_HD void update(const BanditParams &P, uint8_t i, float value, float prob) {
     if (P.kind < B_EXP3) { scores[i] += value; return; }
     // (prob == 0: only with alpha = 0 and an underflowed softmax, where the reference divides by zero -- the smallest normal float instead)
     if ((scores[i] += (value - 0.5) / (prob > 0 ? prob : 1.17549435e-38f)) > 0) { // Exp3::update (the reference's 0.5 is a double literal): keep the largest gain at 0

@@ -369,6 +369,41 @@ PYBIND11_MODULE(pyoak, m) {
       py::arg("input"), py::arg("heap"), py::arg("agent"), py::arg("output") = Output{}, py::arg("batch") = 0, py::arg("seed") = py::none());
 
   m.def(
+      "search_forest",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> battles, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> durations,
+         py::array_t<uint8_t, py::array::c_style | py::array::forcecast> results, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> seeds,
+         Agent &agent) {
+        // not in pyoak: n positions searched at once, one GPU lane per tree (include/oakgpu.h: oakgpu_forest_search); output g is
+        // search(input g, Heap(), agent, batch = 1, seed = seeds[g]).  The Agent's strings go through search's own parser; what the
+        // forest does not run (time budgets, matrix_ucb, UCB1 / Exp3 / PExp3) is refused by name.
+        const size_t n = (size_t)results.size();
+        if ((size_t)battles.size() != n * OAKGPU_BATTLE_SIZE || (size_t)durations.size() != n * OAKGPU_DURATIONS_SIZE || (size_t)seeds.size() != n)
+          throw std::runtime_error("search_forest: battles n x 384, durations n x 8, results n, seeds n");
+        const oakgpu_agent a{agent.budget.c_str(), agent.bandit.c_str(), agent.eval.c_str(), agent.matrix_ucb.c_str(), agent.discrete, agent.table};
+        std::vector<Output> out(n);
+        std::vector<oakgpu_search_output> raw(n);
+        int rc = 0;
+        std::string err;
+        {
+          py::gil_scoped_release release;
+          std::lock_guard<std::mutex> lock(g_ctx_mu);
+          oakgpu_search_params P{};
+          oakgpu_net *net = nullptr;
+          oakgpu_forest *forest = nullptr;
+          rc = oakgpu_agent_params(context(), &a, 1, 0, &P, &net);
+          if (!rc) rc = oakgpu_forest_check((uint32_t)n, (uint32_t)std::min<uint64_t>(P.iterations, 0xFFFFFFFFu), P.bandit == 1, &P, net != nullptr, (uint32_t)n, results.data(), 0, 0);
+          if (!rc && n) rc = oakgpu_forest_create(context(), (uint32_t)n, (uint32_t)P.iterations, P.bandit == 1, &forest);
+          if (!rc && n) rc = oakgpu_forest_search(forest, net, &P, battles.data(), durations.data(), results.data(), seeds.data(), (uint32_t)n, raw.data(), 1, nullptr, nullptr, 0);
+          if (rc) err = oakgpu_last_error();
+          oakgpu_forest_destroy(context(), forest);
+        }
+        if (rc) throw std::runtime_error(err);
+        for (size_t g = 0; g < n; ++g) out[g].raw = raw[g];
+        return out;
+      },
+      py::arg("battles"), py::arg("durations"), py::arg("results"), py::arg("seeds"), py::arg("agent"));
+
+  m.def(
       "value_policy_inference",
       [](const Input &input, const std::string &network_path) {
         // NetworkImpl::value_policy_inference at one position (network.h:102-123), the way Search::run calls it for a fresh

@@ -1187,6 +1187,17 @@ int oakgpu_search_heap(oakgpu_ctx *ctx, oakgpu_net *net, oakgpu_heap *heap, cons
   return 0;
 }
 
+// Diagnostic: lane 0's continuing fast_prng state of the context's first batch slot -- with batch = 1 the one stream of the search
+int oakgpu_search_stream(oakgpu_ctx *ctx, uint64_t *state) {
+  if (!ctx || !state) return oakgpu_fail_msg("oakgpu_search_stream: null argument");
+  SearchScratch *scratch = (SearchScratch *)oakgpu_ctx_attachment(ctx);
+  if (!scratch || !scratch->slots[0].ctx || !scratch->slots[0].cap) return oakgpu_fail_msg("oakgpu_search_stream: no search has run on this context");
+  HIPRC(hipSetDevice(oakgpu_ctx_device(ctx)));
+  HIPRC(hipStreamSynchronize(scratch->slots[0].stream));
+  HIPRC(hipMemcpy(state, scratch->slots[0].d_prng, 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int oakgpu_search(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *battle, const uint8_t *durations, uint8_t result,
                   const oakgpu_search_params *prm, oakgpu_search_output *out) {
   if (prm && prm->iterations == 0 && prm->duration_us == 0) return oakgpu_fail_msg("oakgpu_search: give an iteration or a time budget");
@@ -1285,10 +1296,11 @@ extern "C" int oakgpu_search_many(oakgpu_ctx *const *ctxs, oakgpu_net *net, oakg
   return 0;
 }
 
-extern "C" int oakgpu_search_agent_heap(oakgpu_ctx *ctx, oakgpu_heap *heap, const uint8_t *battle, const uint8_t *durations, uint8_t result,
-                                        const oakgpu_agent *agent, uint32_t batch, uint64_t seed, const oakgpu_search_output *previous,
-                                        oakgpu_search_output *out) {
-  if (!ctx || !battle || !durations || !agent || !out) return oakgpu_fail_msg("oakgpu_search_agent: null argument");
+// The Agent's strings -> search parameters + the loaded network (nullptr unless eval is a network path): the parser of
+// oakgpu_search_agent*, also used by callers that run the search themselves (the forest search's pyoak face).
+extern "C" int oakgpu_agent_params(oakgpu_ctx *ctx, const oakgpu_agent *agent, uint32_t batch, uint64_t seed, oakgpu_search_params *params,
+                                   oakgpu_net **net_out) {
+  if (!ctx || !agent || !params || !net_out) return oakgpu_fail_msg("oakgpu_search_agent: null argument");
   oakgpu_search_params P{};
   P.root_rolls = 3; P.other_rolls = 1; // default_search (mcts.h:131)
   P.seed = seed;
@@ -1350,6 +1362,18 @@ extern "C" int oakgpu_search_agent_heap(oakgpu_ctx *ctx, oakgpu_heap *heap, cons
     }
     net = it->second;
   }
+  *params = P;
+  *net_out = net;
+  return 0;
+}
+
+extern "C" int oakgpu_search_agent_heap(oakgpu_ctx *ctx, oakgpu_heap *heap, const uint8_t *battle, const uint8_t *durations, uint8_t result,
+                                        const oakgpu_agent *agent, uint32_t batch, uint64_t seed, const oakgpu_search_output *previous,
+                                        oakgpu_search_output *out) {
+  if (!ctx || !battle || !durations || !agent || !out) return oakgpu_fail_msg("oakgpu_search_agent: null argument");
+  oakgpu_search_params P{};
+  oakgpu_net *net = nullptr;
+  if (int rc = oakgpu_agent_params(ctx, agent, batch, seed, &P, &net)) return rc;
   return oakgpu_search_heap(ctx, net, heap, battle, durations, result, &P, previous, out);
 }
 

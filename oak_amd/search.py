@@ -224,3 +224,138 @@ def tree_search(ctx, battle, durations, result, iterations=1 << 16, batch=4096, 
                                           battle.ctypes.data_as(C.c_void_p), durations.ctypes.data_as(C.c_void_p), int(result), C.byref(prm),
                                           prev, C.byref(res)))
     return _output_dict(res)
+
+
+def search_stream(ctx):
+    """The continuing fast_prng state of the last tree_search on `ctx` (lane 0 of its first batch slot; with batch = 1 its one stream)."""
+    s = C.c_uint64(0)
+    _lib.check(ctx.lib.oakgpu_search_stream(ctx.handle, C.byref(s)))
+    return int(s.value)
+
+
+TRACE_HEAD_BYTES = C.sizeof(_lib.ForestTraceHead)
+
+
+def trace_dtype(trace_levels):
+    """numpy dtype of one trace record of the forest search (include/oakgpu.h: oakgpu_forest_trace_head + trace_levels levels)."""
+    level = np.dtype([("node", "<u4"), ("i", "u1"), ("j", "u1"), ("pad", "u1", (2,))])
+    return np.dtype([("levels", "<u4"), ("leaf", "<u4"), ("initialised", "u1"), ("result_type", "u1"), ("pad", "u1", (2,)), ("value", "<f4"),
+                     ("logits", "<f4", (2, 9)), ("path", level, (int(trace_levels),))])
+
+
+class Forest:
+    """oakgpu_forest: the device arenas of `max_trees` trees of up to `max_iterations` iterations each (include/oakgpu.h); contextual =
+    room for the policy logits PUCB needs.  Kept between forest_search calls to save the allocation."""
+
+    def __init__(self, ctx, max_trees, max_iterations, contextual=False):
+        self.ctx, self.max_trees, self.max_iterations, self.contextual = ctx, int(max_trees), int(max_iterations), bool(contextual)
+        h = C.c_void_p()
+        _lib.check(ctx.lib.oakgpu_forest_create(ctx.handle, self.max_trees, self.max_iterations, int(self.contextual), C.byref(h)))
+        self.handle = h
+
+    def nodes(self, tree, first=0, count=None):
+        """Node records of one tree of the last call, in creation order (the root first): a list of ((k, scores, priors, visits) of p1, of p2)."""
+        if count is None:
+            count = self.node_count(tree) - first
+        buf = (_lib.ForestNode * max(count, 1))()
+        _lib.check(self.ctx.lib.oakgpu_forest_nodes(self.handle, int(tree), int(first), int(count), buf))
+        def side(b):
+            return (int(b.k), np.array(b.scores, dtype=np.float32), np.array(b.priors, dtype=np.float32), np.array(b.visits, dtype=np.uint32))
+        return [(side(buf[q].p1), side(buf[q].p2)) for q in range(count)]
+
+    def node_count(self, tree):
+        return int(self._counts[int(tree)])
+
+    def last_stats(self):
+        """(iterations, tree levels stepped, kernel launches, host reads of the live count) of the last call."""
+        out = (C.c_uint64 * 4)()
+        _lib.check(self.ctx.lib.oakgpu_forest_last_stats(self.handle, C.byref(out)))
+        return tuple(int(x) for x in out)
+
+    def close(self):
+        if self.handle:   # (a forest that outlived its context still frees its arenas: the library then waits for the device)
+            self.ctx.lib.oakgpu_forest_destroy(self.ctx.handle, self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_FOREST_TENSORS = (("m", "uint8", ()), ("n", "uint8", ()), ("p1_choices", "uint8", (9,)), ("p2_choices", "uint8", (9,)), ("visit_matrix", "int64", (9, 9)),
+                   ("value_matrix", "float64", (9, 9)), ("iterations", "int64", ()), ("nodes", "int64", ()), ("total_depth", "int64", ()),
+                   ("initial_value", "float64", ()), ("p1_logit", "float64", (9,)), ("p2_logit", "float64", (9,)), ("p1_prior", "float64", (9,)),
+                   ("p2_prior", "float64", (9,)), ("stream", "int64", ()))
+
+
+def forest_search(ctx, battles, durations, results, seeds, iterations, c=2.0, bandit="ucb", evaluator="mc", max_depth=0, root_rolls=3,
+                  other_rolls=1, solve_nash=False, trace_levels=0, forest=None):
+    """n searches at once, one GPU lane per tree, every tree on the device (include/oakgpu.h: oakgpu_forest_search*): tree g is
+    tree_search(ctx, battles[g], durations[g], results[g], iterations, batch=1, seed=seeds[g], ...) iteration for iteration.  bandit "ucb" |
+    "pucb"; evaluator "mc", "poke-engine" or a Network; forest: None (one made for this call) or a Forest to reuse.
+    numpy arrays in: a list of n dicts with tree_search's keys (nash fields only with solve_nash) plus "stream" (the tree's continuing
+    fast_prng state) and, with trace_levels > 0, "trace" (iterations records of trace_dtype(trace_levels)) and -- when the call made its own
+    forest -- "tree" (Forest.nodes of the tree: with a forest of the caller's, read them from it).
+    torch GPU tensors in (battles [n, 384], durations [n, 8], results [n] uint8; seeds [n] int64 bit patterns): a dict of tensors on that
+    device, one row per tree -- m, n, p1_choices, p2_choices, visit_matrix [n, 9, 9], value_matrix, iterations, nodes, total_depth,
+    initial_value, p1_logit, p2_logit, p1_prior, p2_prior, stream (int64 bit patterns), and "trace" (uint8 [n, iterations, record bytes])
+    with trace_levels > 0; nothing is copied to the host."""
+    use_net = not isinstance(evaluator, str)
+    prm = _lib.SearchParams(iterations=int(iterations), batch=1, ucb_c=float(c), bandit={"ucb": 0, "pucb": 1, "ucb1": 2, "exp3": 3, "pexp3": 4}[bandit],
+                            eval=1 if use_net else {"mc": 0, "poke-engine": 2}[evaluator], max_depth=int(max_depth), root_rolls=int(root_rolls),
+                            other_rolls=int(other_rolls), seed=0, matrix_ucb=0, mucb_delay=0, mucb_minimum=0, mucb_c=0.0, exp3_alpha=-1.0, duration_us=0)
+    net = evaluator.handle if use_net else None
+    on_device = hasattr(battles, "data_ptr")
+    n = int(battles.shape[0]) if on_device else len(np.asarray(results).reshape(-1))
+    own = forest is None
+    if own:
+        forest = Forest(ctx, max(n, 1), max(int(iterations), 1), contextual=bandit == "pucb")
+    rec = C.sizeof(_lib.ForestTraceHead) + int(trace_levels) * C.sizeof(_lib.ForestTraceLevel)
+    try:
+        if on_device:
+            import torch
+            dev = battles.device
+            battles, durations, results, seeds = battles.contiguous(), durations.contiguous(), results.contiguous(), seeds.contiguous()
+            out = {name: torch.zeros((n,) + tail, dtype=getattr(torch, dt), device=dev) for name, dt, tail in _FOREST_TENSORS}
+            trace = torch.zeros((n, int(iterations), rec), dtype=torch.uint8, device=dev) if trace_levels else None
+            ptrs = _lib.ForestOutputs(**{name: out[name].data_ptr() for name, _, _ in _FOREST_TENSORS})
+            mine, theirs = torch.cuda.ExternalStream(ctx.stream_ptr(), device=dev), torch.cuda.current_stream(dev)
+            mine.wait_stream(theirs)
+            _lib.check(ctx.lib.oakgpu_forest_search_dev(forest.handle, net, C.byref(prm), battles.data_ptr(), durations.data_ptr(), results.data_ptr(),
+                                                        seeds.data_ptr(), n, C.byref(ptrs), trace.data_ptr() if trace_levels else None, int(trace_levels)))
+            theirs.wait_stream(mine)
+            if trace_levels:
+                out["trace"] = trace
+            forest._counts = out["nodes"]
+            return out
+        battles = np.ascontiguousarray(battles, dtype=np.uint8).reshape(n, 384)
+        durations = np.ascontiguousarray(durations, dtype=np.uint8).reshape(n, 8)
+        results = np.ascontiguousarray(results, dtype=np.uint8).reshape(n)
+        seeds = np.ascontiguousarray(np.asarray(seeds).astype(np.uint64)).reshape(n)
+        outs = (_lib.SearchOutput * max(n, 1))()
+        streams = np.zeros(max(n, 1), np.uint64)
+        trace = np.zeros((n, int(iterations)), dtype=trace_dtype(trace_levels)) if trace_levels else None
+        _lib.check(ctx.lib.oakgpu_forest_search(forest.handle, net, C.byref(prm), battles.ctypes.data_as(C.c_void_p), durations.ctypes.data_as(C.c_void_p),
+                                                results.ctypes.data_as(C.c_void_p), seeds.ctypes.data_as(C.c_void_p), n, outs, int(bool(solve_nash)),
+                                                streams.ctypes.data_as(C.c_void_p), trace.ctypes.data_as(C.c_void_p) if trace_levels else None,
+                                                int(trace_levels)))
+        res = []
+        for g in range(n):   # (_output_dict keeps a reference to its raw struct: give each its own copy)
+            o = _lib.SearchOutput()
+            C.memmove(C.byref(o), C.byref(outs[g]), C.sizeof(_lib.SearchOutput))
+            d = _output_dict(o)
+            d["stream"] = int(streams[g])
+            if trace_levels:
+                d["trace"] = trace[g]
+            res.append(d)
+        forest._counts = [r["nodes"] for r in res]
+        if not own:
+            return res
+        for g, d in enumerate(res):   # the forest goes with the call: its trees are read out now
+            d["tree"] = forest.nodes(g) if trace_levels else None
+        return res
+    finally:
+        if own:
+            forest.close()
