@@ -98,7 +98,7 @@ int oakgpu_set_standstill_skip(oakgpu_ctx *ctx, int on);
 #define OAKGPU_CTL_FAST_FORWARDED 44 /* playouts whose inert standstill was taken in one go */
 #define OAKGPU_CTL_SKIPPED_STEPS 45  /* turn-steps those playouts skipped (they are part of steps_out) */
 /* Diagnostic (synchronises the stream): the 64 control words of the last queue launch -- [32] / [33]
- * the queue order's two counters, [40] donations, [41] adoptions, [42] bulk waves that left, [44] / [45] above, [63] error bits (0 = none:
+ * or [34] / [35] the queue order's two counters (launches take the pairs in turn: each clears the next one's), [40] donations, [41] adoptions, [42] bulk waves that left, [44] / [45] above, [63] error bits (0 = none:
  * 1 a ticket never arrived, 2 an adopter gave up waiting) -- STICKY: no launch clears them; oakgpu_synchronize reports a
  * non-zero word as a failed call and clears it, so the error of any launch since the last synchronize is seen, not only the
  * last launch's. */
@@ -137,7 +137,8 @@ int oakgpu_rollout(oakgpu_ctx *ctx, const uint8_t *battles, const uint8_t *durat
 /* Group launch: `count` (<= 64) independent batches drained by ONE launch through one playout queue, so the group has
  * a single tail instead of one per batch (root-parallel MCTS submits its roots' batches together).  Same per-batch
  * contract as oakgpu_rollout_dev (outputs may alias inputs; results never depend on the grouping); batches with
- * n == 0 are skipped.  oakgpu_rollout_dev is the group of one. */
+ * n == 0 are skipped.  oakgpu_rollout_dev is the group of one.  Call it for every launch: a group launch must not be replayed
+ * from a captured HIP graph (its kernel arguments carry per-launch host state -- the table slot, the adoption tickets' epoch). */
 typedef struct {
   const uint8_t *battles, *durations, *results_in;
   uint8_t *prng_state;
@@ -150,6 +151,10 @@ typedef struct {
 int oakgpu_rollout_group_dev(oakgpu_ctx *ctx, const oakgpu_rollout_batch *batches, uint32_t count, uint32_t max_steps,
                              int prep);
 int oakgpu_rollout_group(oakgpu_ctx *ctx, const oakgpu_rollout_batch *batches, uint32_t count, uint32_t max_steps, int prep);
+/* Diagnostic (tests): the queue order of oakgpu_set_queue_order alone, at any total, for HOST battles (of `batches` only .battles
+ * and .n are read; no batch may be empty): order_out receives sum(n) playout indices -- the `*suspects_out` playouts that a launch
+ * hands out first at the front, the others behind them.  Synchronises, and clears the control words like a launch. */
+int oakgpu_queue_order(oakgpu_ctx *ctx, const oakgpu_rollout_batch *batches, uint32_t count, uint32_t *order_out, uint32_t *suspects_out);
 
 /* ---- rollouts driven by a caller-supplied draw stream (a SHARED sequential device generator).
  * The reference's benchmark / search drive every playout from ONE std::mt19937 (benchmark.cc:24, search.cc:150), so

@@ -429,7 +429,8 @@ struct RoundArgs {
   const uint32_t *order;    // round 0, nullable: queue position -> playout (k_queue_order: the likely-long playouts first)
   // long-playout migration (below): control words {tail, head, bulk waves exited, error}, one list entry per donation
   uint32_t *adopt_ctl;
-  uint32_t *adopt_list;
+  uint64_t *adopt_list;     // tickets {playout + 1, epoch << 32}: written for THIS launch when the high word is `epoch` (no per-launch clearing)
+  uint32_t epoch;           // the context's count of migrating launches, never 0
   uint32_t n_adopters;      // 0 = off; waves [0, n_adopters) adopt
   uint32_t long_steps;      // bits 0-15: a bulk wave donates a playout that is still running after this many turn-steps;
                             // bits 16-24: ... or whose actives' {slot, hp} have not changed for this many turn-steps (256: never)
@@ -500,43 +501,68 @@ static __device__ unsigned long long g_timeline[5 * 16384];
 // fifth of the launch has most of them behind it.  So the playouts with a Ghost on either team go to the front of the queue
 // (order[] filled from the front), the others behind them (filled from the back).  Pure scheduling: results are indexed by
 // playout and never depend on it.
-__global__ __launch_bounds__(1024) void k_queue_order(GroupArgs g, uint32_t *order, uint32_t *counters) {
+// A group launch's control words are cleared by the launch's own first small kernel, on the context's stream (they were two fills
+// in front of every launch): words 0-62 of the control block but the pair at `keep` (word 63 is the sticky migration error word:
+// never cleared here), and every round's queue heads.
+constexpr uint32_t QUEUE_MAX_ROUNDS = 16;
+__device__ __forceinline__ void clear_launch_words(uint32_t *ctl, uint32_t *heads, uint32_t keep, uint32_t tid, uint32_t threads) {
+  for (uint32_t i = tid; i < 63; i += threads) if ((i & ~1u) != keep) ctl[i] = 0;
+  for (uint32_t i = tid; i < QUEUE_MAX_ROUNDS * QUEUE_HEADS; i += threads) heads[i * QUEUE_HEAD_STRIDE] = 0;
+}
+__global__ __launch_bounds__(256) void k_clear_launch_words(uint32_t *ctl, uint32_t *heads) { clear_launch_words(ctl, heads, 64, threadIdx.x, 256); }
+
+// Blocks of 256 threads, 1,024 playouts each (four per thread).  The kernel runs in front of a launch whose stream neighbour
+// saturates the device: a block is placed when ALL its waves fit on one compute unit, and sixteen-wave blocks waited for a whole
+// drained SIMD set while four waves fit wherever a few slots are free.  Block 0 also clears the launch's control words (above);
+// the two counters in use (control words `pair`, `pair` + 1) were cleared by the PREVIOUS launch's kernel, which used the other pair.
+constexpr uint32_t ORDER_BLOCK = 256, ORDER_PER_BLOCK = 1024;
+__global__ __launch_bounds__(ORDER_BLOCK) void k_queue_order(GroupArgs g, uint32_t *order, uint32_t *ctl, uint32_t *heads, uint32_t pair) {
+  constexpr uint32_t PER = ORDER_PER_BLOCK / ORDER_BLOCK, GROUPS = ORDER_PER_BLOCK / 64;
   __shared__ uint32_t starts[MAX_GROUP + 1];
-  __shared__ uint32_t wave_s[16], wave_o[16], base_s, base_o;
-  for (uint32_t i = threadIdx.x; i < g.count; i += 1024) starts[i] = g.table[i].start;
+  __shared__ uint32_t wave_s[GROUPS], wave_o[GROUPS], base_s, base_o;
+  if (blockIdx.x == 0) clear_launch_words(ctl, heads, pair, threadIdx.x, ORDER_BLOCK);
+  for (uint32_t i = threadIdx.x; i < g.count; i += ORDER_BLOCK) starts[i] = g.table[i].start;
   if (threadIdx.x == 0) starts[g.count] = 0xFFFFFFFFu;
   __syncthreads();
-  const uint32_t idx = blockIdx.x * 1024 + threadIdx.x, wl = threadIdx.x & 63, wib = threadIdx.x >> 6;
-  bool suspect = false;
-  if (idx < g.total) {
-    uint32_t lo = 0, hi = g.count;
-    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (starts[mid] <= idx) lo = mid; else hi = mid; }
-    const BatchDesc &bd = g.table[lo];
-    const uint32_t *b = (const uint32_t *)(bd.battles + (size_t)(idx - bd.start) * 384);
-    uint32_t w[12]; // the dword {status, species, types, level} of each of the 12 Pokemon: all twelve loads in flight together
+  const uint32_t wl = threadIdx.x & 63, wib = threadIdx.x >> 6;
+  uint64_t ms[PER], mo[PER];
 #pragma unroll
-    for (int k = 0; k < 12; ++k) w[k] = b[((k / 6) * SIDE_SZ + (k % 6) * PK_SZ + P_STATUS) / 4];
+  for (uint32_t j = 0; j < PER; ++j) { // playout j * 256 + thread of the block's 1,024: every wave instruction reads 64 consecutive playouts
+    const uint32_t idx = blockIdx.x * ORDER_PER_BLOCK + j * ORDER_BLOCK + threadIdx.x;
+    bool suspect = false;
+    if (idx < g.total) {
+      uint32_t lo = 0, hi = g.count;
+      while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (starts[mid] <= idx) lo = mid; else hi = mid; }
+      const BatchDesc &bd = g.table[lo];
+      const uint32_t *b = (const uint32_t *)(bd.battles + (size_t)(idx - bd.start) * 384);
+      uint32_t w[12]; // the dword {status, species, types, level} of each of the 12 Pokemon: all twelve loads in flight together
 #pragma unroll
-    for (int k = 0; k < 12; ++k) {
-      const uint32_t sp = (w[k] >> 8) & 0xFF, ty = (w[k] >> 16) & 0xFF;
-      suspect |= sp != 0 && ((ty & 15) == T_Ghost || (ty >> 4) == T_Ghost || sp == 132 /* Ditto: Transform into a stalemate */);
+      for (int k = 0; k < 12; ++k) w[k] = b[((k / 6) * SIDE_SZ + (k % 6) * PK_SZ + P_STATUS) / 4];
+#pragma unroll
+      for (int k = 0; k < 12; ++k) {
+        const uint32_t sp = (w[k] >> 8) & 0xFF, ty = (w[k] >> 16) & 0xFF;
+        suspect |= sp != 0 && ((ty & 15) == T_Ghost || (ty >> 4) == T_Ghost || sp == 132 /* Ditto: Transform into a stalemate */);
+      }
     }
+    ms[j] = __ballot(suspect);
+    mo[j] = __ballot(idx < g.total && !suspect);
+    if (wl == 0) { wave_s[j * (ORDER_BLOCK / 64) + wib] = (uint32_t)__popcll(ms[j]); wave_o[j * (ORDER_BLOCK / 64) + wib] = (uint32_t)__popcll(mo[j]); }
   }
   // one pair of atomics per 1,024 playouts (a pair per wave: 41,000 atomics on two addresses took longer than the loads)
-  const uint64_t ms = __ballot(suspect), mo = __ballot(idx < g.total && !suspect);
-  if (wl == 0) { wave_s[wib] = (uint32_t)__popcll(ms); wave_o[wib] = (uint32_t)__popcll(mo); }
   __syncthreads();
   if (threadIdx.x == 0) {
     uint32_t ts = 0, to = 0;
-    for (int q = 0; q < 16; ++q) { const uint32_t a = wave_s[q], c = wave_o[q]; wave_s[q] = ts; wave_o[q] = to; ts += a; to += c; }
-    base_s = ts ? atomicAdd(counters + 0, ts) : 0;
-    base_o = to ? atomicAdd(counters + 1, to) : 0;
+    for (uint32_t q = 0; q < GROUPS; ++q) { const uint32_t a = wave_s[q], c = wave_o[q]; wave_s[q] = ts; wave_o[q] = to; ts += a; to += c; }
+    base_s = ts ? atomicAdd(ctl + pair, ts) : 0;
+    base_o = to ? atomicAdd(ctl + pair + 1, to) : 0;
   }
   __syncthreads();
-  if (idx < g.total) {
-    const uint64_t below = (1ull << wl) - 1;
-    if (suspect) order[base_s + wave_s[wib] + (uint32_t)__popcll(ms & below)] = idx;
-    else order[g.total - 1 - (base_o + wave_o[wib] + (uint32_t)__popcll(mo & below))] = idx;
+  const uint64_t below = (1ull << wl) - 1;
+#pragma unroll
+  for (uint32_t j = 0; j < PER; ++j) {
+    const uint32_t idx = blockIdx.x * ORDER_PER_BLOCK + j * ORDER_BLOCK + threadIdx.x, grp = j * (ORDER_BLOCK / 64) + wib;
+    if ((ms[j] >> wl) & 1) order[base_s + wave_s[grp] + (uint32_t)__popcll(ms[j] & below)] = idx;
+    else if ((mo[j] >> wl) & 1) order[g.total - 1 - (base_o + wave_o[grp] + (uint32_t)__popcll(mo[j] & below))] = idx;
   }
 }
 
@@ -653,9 +679,14 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
       const bool take = need && rank < k;
       uint32_t got = 0;
       if (take && h + rank < COLD_GU(total)) { // (tickets live in [0, total): one per donation at most)
-        const uint32_t *slot = COLD_Q(adopt_list, const uint32_t *) + h + rank;
+        // a ticket is one 64-bit word {playout + 1, this launch's epoch}: whatever an earlier launch left in the slot carries another
+        // epoch and reads as "not written yet", so no launch clears the list (it was a pass over total x 4 bytes in front of every launch)
+        const uint64_t *slot = COLD_Q(adopt_list, const uint64_t *) + h + rank;
+        const uint32_t epoch = COLD_QU(epoch);
         uint32_t spins = 0;
-        while ((got = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0 && ++spins < SPIN_CAP) __builtin_amdgcn_s_sleep(2);
+        uint64_t tk;
+        while ((uint32_t)((tk = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 32) != epoch && ++spins < SPIN_CAP) __builtin_amdgcn_s_sleep(2);
+        if ((uint32_t)(tk >> 32) == epoch) got = (uint32_t)tk;
         if (!got) atomicOr(ctl + ERR_WORD, 1u); // (a ticket that never arrived: reported, the playout is lost -- the tests would see it)
       }
       if (k) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); // the donors' images, step counts and PRNG states
@@ -816,7 +847,8 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
       if (wl == leader) base = atomicAdd(ctl + 0, (uint32_t)__popcll(dm));
       base = (uint32_t)__builtin_amdgcn_readlane((int)base, (int)leader);
       if (lng) {
-        __hip_atomic_store(COLD_Q(adopt_list, uint32_t *) + base + (uint32_t)__popcll(dm & ((1ull << wl) - 1)), idx + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(COLD_Q(adopt_list, uint64_t *) + base + (uint32_t)__popcll(dm & ((1ull << wl) - 1)), (uint64_t)(idx + 1) | ((uint64_t)COLD_QU(epoch) << 32),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         idx = NONE; // the lane is free again
       }
     }
@@ -1616,6 +1648,9 @@ struct oakgpu_ctx {
   int standstill_skip;    // 1 (default): the queue kernel takes a PROVEN inert standstill to its last turn-step in one go (exact); 0: plays every turn
   uint32_t *d_order;      // total entries
   size_t order_n;
+  uint32_t order_pair = 0;      // k_queue_order's two counters: control words 32-33 and 34-35 in turn (each launch clears the next one's)
+  uint32_t ticket_epoch = 0;    // migrating launches of this context: tags the adoption tickets (RoundArgs::epoch)
+  bool tickets_dirty = true;    // the ticket list holds something else (fresh scratch, a regrouping round's lists): ONE clearing, then epochs again
   int n_cu;               // compute units of the device
   static constexpr int TABLE_SLOTS = 8;
   void *h_table, *d_table; // batch tables of the group launches: pinned host ring -> device ring
@@ -1994,13 +2029,13 @@ static inline uint32_t grid_for(uint32_t n) { return (n + oak::BLOCK - 1) / oak:
 // ---- group launch of the queue kernel --------------------------------------------------------------------------
 // The batch table travels through a small ring of pinned host slots -> device slots (async copy on the context's
 // stream; a slot is reused only after the event behind its previous copy has completed).
-static int launch_group(oakgpu_ctx *c, const oak::BatchDesc *descs, uint32_t count, uint32_t total, uint32_t max_steps, int prep) {
-  HIPCHK(hipSetDevice(c->device));
+// The control block, the queue heads and the batch-table ring of the group launches; the batch table of this launch on its way to
+// the device (async copy on the context's stream; a slot is reused only after the event behind its previous copy has completed).
+static int stage_group_table(oakgpu_ctx *c, const oak::BatchDesc *descs, uint32_t count, oak::BatchDesc **dt_out) {
   // (the first clearing covers the sticky word too, ON THE CONTEXT'S STREAM: a hipMemset on the NULL stream is not ordered with a
   // non-blocking stream and could land in the middle of the first launch -- queue heads zeroed under a running kernel)
   if (!c->d_queue) { HIPCHK(hipMalloc((void **)&c->d_queue, 256)); HIPCHK(hipMemsetAsync(c->d_queue, 0, 256, c->stream)); }
-  constexpr int MAX_ROUNDS = 16;
-  constexpr size_t HEADS_BYTES = (size_t)MAX_ROUNDS * oak::QUEUE_HEADS * oak::QUEUE_HEAD_STRIDE * 4;
+  constexpr size_t HEADS_BYTES = (size_t)oak::QUEUE_MAX_ROUNDS * oak::QUEUE_HEADS * oak::QUEUE_HEAD_STRIDE * 4;
   if (!c->d_heads) HIPCHK(hipMalloc((void **)&c->d_heads, HEADS_BYTES));
   if (!c->h_table) {
     HIPCHK(hipHostMalloc((void **)&c->h_table, sizeof(oak::BatchDesc) * oak::MAX_GROUP * oakgpu_ctx::TABLE_SLOTS, hipHostMallocDefault));
@@ -2013,8 +2048,28 @@ static int launch_group(oakgpu_ctx *c, const oak::BatchDesc *descs, uint32_t cou
   memcpy(ht, descs, sizeof(oak::BatchDesc) * count);
   HIPCHK(hipMemcpyAsync(dt, ht, sizeof(oak::BatchDesc) * count, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipEventRecord(c->table_ev[slot], c->stream));
-  HIPCHK(hipMemsetAsync(c->d_queue, 0, 252, c->stream)); // (word 63 is the sticky migration error word: never cleared here)
-  HIPCHK(hipMemsetAsync(c->d_heads, 0, HEADS_BYTES, c->stream));
+  *dt_out = dt;
+  return 0;
+}
+
+// k_queue_order on the context's stream (it clears the launch's control words on its way); the order goes to c->d_order
+static int launch_queue_order(oakgpu_ctx *c, const oak::GroupArgs &g) {
+  if (c->order_n < g.total) {
+    if (c->d_order) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(c->d_order)); c->d_order = nullptr; }
+    HIPCHK(hipMalloc((void **)&c->d_order, (size_t)g.total * 4));
+    c->order_n = g.total;
+  }
+  const uint32_t pair = 32u + 2u * c->order_pair;
+  c->order_pair ^= 1u;
+  hipLaunchKernelGGL(oak::k_queue_order, dim3((g.total + oak::ORDER_PER_BLOCK - 1) / oak::ORDER_PER_BLOCK), dim3(oak::ORDER_BLOCK), 0, c->stream, g, c->d_order,
+                     c->d_queue, c->d_heads, pair);
+  return 0;
+}
+
+static int launch_group(oakgpu_ctx *c, const oak::BatchDesc *descs, uint32_t count, uint32_t total, uint32_t max_steps, int prep) {
+  HIPCHK(hipSetDevice(c->device));
+  oak::BatchDesc *dt = nullptr;
+  if (int r = stage_group_table(c, descs, count, &dt)) return r;
   // grid: at least `playouts_per_lane` playouts per lane, and never more waves than the device keeps resident
   const uint32_t n64 = (total + 63) / 64;
   uint32_t waves = (n64 + c->playouts_per_lane - 1) / c->playouts_per_lane;
@@ -2061,6 +2116,7 @@ static int launch_group(oakgpu_ctx *c, const oak::BatchDesc *descs, uint32_t cou
     if (c->d_scratch) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(c->d_scratch)); c->d_scratch = nullptr; }
     HIPCHK(hipMalloc((void **)&c->d_scratch, (size_t)total * (384 + 8 + 4 + 4) + (((size_t)total + 15) & ~(size_t)15)));
     c->scratch_n = total;
+    c->tickets_dirty = true;
   }
   const size_t lq = 24 * 64 * 4 + oak::TABLE_LDS_PAD + oak::COLD_LDS_BYTES;
   uint8_t *sb = c->d_scratch, *sd = sb ? sb + (size_t)c->scratch_n * 384 : nullptr;
@@ -2070,23 +2126,28 @@ static int launch_group(oakgpu_ctx *c, const oak::BatchDesc *descs, uint32_t cou
   const oak::GroupArgs g{dt, count, total, max_steps, prep};
   const uint32_t *order = nullptr;
   if (c->queue_order && max_steps > 250 && total >= 8192) { // (a few thousand playouts have no queue to speak of: they all start at once)
-    if (c->order_n < total) {
-      if (c->d_order) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(c->d_order)); c->d_order = nullptr; }
-      HIPCHK(hipMalloc((void **)&c->d_order, (size_t)total * 4));
-      c->order_n = total;
-    }
-    hipLaunchKernelGGL(oak::k_queue_order, dim3((total + 1023) / 1024), dim3(1024), 0, c->stream, g, c->d_order, c->d_queue + 32);
+    if (int r = launch_queue_order(c, g)) return r;
     order = c->d_order;
+  } else {
+    hipLaunchKernelGGL(oak::k_clear_launch_words, dim3(1), dim3(256), 0, c->stream, c->d_queue, c->d_heads);
   }
-  if (migrate) HIPCHK(hipMemsetAsync(lists[0], 0, (size_t)total * 4, c->stream)); // the adoption tickets (one per donation at most)
-  if (migrate) c->migrate_used = 1; // (sticky, like the device word: back-to-back launches keep an earlier launch's error)
+  // the adoption tickets (one per donation at most) are tagged with the launch's epoch, so a launch clears nothing -- but for the
+  // first use of the list, a regrouping launch's lists in the same memory, and the epoch's wrap to 0 after 2^32 launches
+  if (migrate) {
+    if (++c->ticket_epoch == 0 || c->tickets_dirty) {
+      HIPCHK(hipMemsetAsync(lists[0], 0, (size_t)c->scratch_n * 8, c->stream));
+      if (c->ticket_epoch == 0) c->ticket_epoch = 1;
+      c->tickets_dirty = false;
+    }
+    c->migrate_used = 1; // (sticky, like the device word: back-to-back launches keep an earlier launch's error)
+  } else if (rounds > 1) c->tickets_dirty = true;
   for (int r = 0; r < rounds; ++r) {
     oak::RoundArgs q{};
     q.order = r == 0 ? order : nullptr;
     q.long_steps = (uint32_t)(c->migrate_steps > 0xFFFF ? 0xFFFF : c->migrate_steps) | (uint32_t)(c->migrate_window > 0 ? c->migrate_window : 256) << 16;
     q.no_skip = c->standstill_skip ? 0u : 1u;
     q.stats = c->d_queue + OAKGPU_CTL_FAST_FORWARDED;
-    if (migrate) { q.adopt_ctl = c->d_queue + 40; q.adopt_list = lists[0]; q.n_adopters = adopters; }
+    if (migrate) { q.adopt_ctl = c->d_queue + 40; q.adopt_list = (uint64_t *)lists[0]; q.epoch = c->ticket_epoch; q.n_adopters = adopters; } // (one round: both lists' memory)
     q.list_in = r ? lists[(r - 1) & 1] : nullptr;
     q.n_in = r ? c->d_queue + 2 * r - 1 : nullptr; // = count_out of round r - 1
     q.list_out = lists[r & 1];
@@ -2101,6 +2162,41 @@ static int launch_group(oakgpu_ctx *c, const oak::BatchDesc *descs, uint32_t cou
   }
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+// Diagnostic (tests): k_queue_order alone, at ANY total, on host battles -- the order a group launch of these batches would hand its
+// playouts out in, and how many of them it put in front.  Synchronises; clears the control words like a launch.
+int oakgpu_queue_order(oakgpu_ctx *c, const oakgpu_rollout_batch *batches, uint32_t count, uint32_t *order_out, uint32_t *suspects_out) {
+  if (!c || !batches || !order_out || count == 0 || count > (uint32_t)oak::MAX_GROUP) return bad("oakgpu_queue_order: bad argument");
+  HIPCHK(hipSetDevice(c->device));
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < count; ++i) { if (!batches[i].battles || batches[i].n == 0) return bad("oakgpu_queue_order: empty batch"); total += batches[i].n; }
+  if (total >= 0xFFFFFFF0ull) return bad("oakgpu_queue_order: more than 2^32 playouts");
+  uint8_t *d_battles = nullptr;
+  HIPCHK(hipMalloc((void **)&d_battles, (size_t)total * 384));
+  oak::BatchDesc descs[oak::MAX_GROUP] = {};
+  uint32_t start = 0;
+  int rc = 0;
+  for (uint32_t i = 0; i < count && !rc; ++i) {
+    descs[i].battles = d_battles + (size_t)start * 384;
+    descs[i].start = start;
+    descs[i].n = batches[i].n;
+    if (hipMemcpyAsync(d_battles + (size_t)start * 384, batches[i].battles, (size_t)batches[i].n * 384, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = bad("oakgpu_queue_order: copy");
+    start += batches[i].n;
+  }
+  oak::BatchDesc *dt = nullptr;
+  if (!rc) rc = stage_group_table(c, descs, count, &dt);
+  uint32_t pair = 32u + 2u * c->order_pair; // (the pair launch_queue_order is about to use)
+  if (!rc) rc = launch_queue_order(c, oak::GroupArgs{dt, count, (uint32_t)total, 1000u, 0});
+  if (!rc && hipGetLastError() != hipSuccess) rc = bad("oakgpu_queue_order: launch");
+  if (!rc && hipMemcpyAsync(order_out, c->d_order, (size_t)total * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = bad("oakgpu_queue_order: copy back");
+  uint32_t suspects = 0;
+  if (!rc && hipMemcpyAsync(&suspects, c->d_queue + pair, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = bad("oakgpu_queue_order: copy back");
+  hipError_t se = hipStreamSynchronize(c->stream);
+  (void)hipFree(d_battles);
+  if (!rc && se != hipSuccess) return fail(se, "oakgpu_queue_order");
+  if (suspects_out) *suspects_out = suspects;
+  return rc;
 }
 
 static int launch_single(oakgpu_ctx *c, const oak::RolloutArgs &a) { // one lane per playout, no queue

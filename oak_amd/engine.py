@@ -90,6 +90,18 @@ class Context:
         _lib.check(self.lib.oakgpu_search_party_table_stats(self.handle, C.byref(fills), C.byref(evals)))
         return fills.value, evals.value
 
+    def queue_order(self, battles_per_batch):
+        """(order, suspects) of a group launch of these host battle arrays (oakgpu_queue_order, a diagnostic): the playout indices in
+        the order the queue hands them out, the first `suspects` of them the likely-long ones."""
+        bs = [_u8(b) for b in battles_per_batch]
+        descs = (_lib.RolloutBatch * len(bs))()
+        for k, b in enumerate(bs):
+            descs[k].battles, descs[k].n = b.ctypes.data, b.shape[0]
+        order = np.zeros(sum(b.shape[0] for b in bs), dtype=np.uint32)
+        suspects = C.c_uint32(0)
+        _lib.check(self.lib.oakgpu_queue_order(self.handle, descs, len(bs), _p(order), C.byref(suspects)))
+        return order, suspects.value
+
     def set_standstill_skip(self, on=True):
         """The queue kernel's exact fast-forward of proven inert standstills (oakgpu_set_standstill_skip); results never change."""
         _lib.check(self.lib.oakgpu_set_standstill_skip(self.handle, 1 if on else 0))
