@@ -62,12 +62,16 @@ struct SiteScope {
 #define OAK_SCOPE(id) SiteScope oak_scope_##id(id)
 #define OAK_T0(v) long long v = clock64()
 #define OAK_T1(id, v) site_add(id, clock64() - v)
+#define OAK_T1K(id, v) site_add(id + prof_k, clock64() - v) // ... under the site of the turn's k-th pass through the action code
+#define OAK_SET_K(eng, k) (eng).prof_k = (int)(k)
 #define OAK_PROF_ZERO() site_zero()
 #define OAK_PROF_FLUSH() site_flush()
 #else
 #define OAK_SCOPE(id)
 #define OAK_T0(v)
 #define OAK_T1(id, v)
+#define OAK_T1K(id, v)
+#define OAK_SET_K(eng, k)
 #define OAK_PROF_ZERO()
 #define OAK_PROF_FLUSH()
 #endif
@@ -75,7 +79,7 @@ struct SiteScope {
 enum { PS_REFILL = 0, PS_STEP, PS_LEGAL_DRAW, PS_ORDER, PS_EXEC_MOVE, PS_SWITCH_IN, PS_BEFORE_MOVE, PS_EXEC_SELECTED_PRE,
        PS_RUN_MOVE, PS_GATES_HIT, PS_STATUS_BODIES, PS_DAMAGE, PS_SECONDARY_APPLY, PS_FAINT_RESIDUAL, PS_PUBLISH,
        PS_CALC_DAMAGE, PS_APPLY_HITS, PS_DAMAGE_TAIL, PS_HEAVY, PS_H_CONVERSION, PS_H_HAZE, PS_H_HEAL, PS_H_MIMIC,
-       PS_H_POISON, PS_H_SUBSTITUTE, PS_H_TRANSFORM, PS_H_BIDE, PS_H_SLEEP, PS_H_DISABLE, PS_COUNT };
+       PS_H_POISON, PS_H_SUBSTITUTE, PS_H_TRANSFORM, PS_H_BIDE, PS_H_SLEEP, PS_H_DISABLE, PS_EXEC_MOVE_K0, PS_EXEC_MOVE_K1, PS_COUNT };
 
 struct SideR {
   uint32_t a0, a1, a2; // active: hp|atk<<16, def|spe<<16, spc|species<<16|types<<24
@@ -110,6 +114,9 @@ struct EngineR {
   Tables T;
   SideR S, F; // mover / target frame
   uint64_t actS, actF; // chance actions (TRACK_ACTIONS only)
+#ifdef OAKGPU_SITE_PROFILE
+  int prof_k = 0;      // which of the turn's passes through the action code is running (wave-uniform)
+#endif
   uint64_t rng;
   uint32_t turn, last_damage;
   uint32_t lm; // last_moves: index0 | counterable0<<8 | index1<<16 | counterable1<<24 (absolute players)
@@ -1196,6 +1203,7 @@ struct EngineR {
     if (r == BM_ERR) return mk_result(R_ERROR, 0, 0);
     if (r != BM_DONE) execute_selected(mslot, r == BM_SKIP_CAN, r == BM_SKIP_PP);
     OAK_T1(PS_EXEC_MOVE, t_em);
+    OAK_T1K(PS_EXEC_MOVE_K0, t_em);
     return post_action(choice, replace, true);
   }
 
@@ -1262,6 +1270,17 @@ struct EngineR {
     if constexpr (TRACK_ACTIONS) { uint64_t t = actS; actS = actF; actF = t; }
   }
 
+  // A turn in pieces, for a caller that drives it one action at a time (k_rollout_queue lets a lane's second action wait for the
+  // wave's next pass through the action code): turn_prologue above; act = this lane's pending action `pc` (act_move / act_cheap),
+  // hand_over = the other side becomes the actor and `pc` / `qc` change places -- the turn goes on while the result is 0 and the
+  // new `pc` is no pass; turn_finish = the turn's end.  update_frame is these in a row.
+  __device__ __forceinline__ uint32_t act(uint32_t choice) { return (choice & 3) == C_MOVE ? act_move(choice) : act_cheap(choice); }
+  __device__ __forceinline__ void hand_over(uint32_t &pc, uint32_t &qc) {
+    next_actor();
+    const uint32_t t = pc; pc = qc; qc = t;
+  }
+  __device__ __forceinline__ uint32_t turn_finish(uint32_t r) { return r ? r : turn_epilogue(); }
+
   __device__ uint32_t update_frame(uint32_t cS, uint32_t cF) {
     uint32_t pc = 0, qc = 0;
     uint32_t r = turn_prologue(cS, cF, pc, qc);
@@ -1272,13 +1291,13 @@ struct EngineR {
     // copy the whole engine state at each merge point.
 #pragma unroll 1
     for (int k = 0; k < 2; ++k) {
-      r = (pc & 3) == C_MOVE ? act_move(pc) : act_cheap(pc);
+      OAK_SET_K(*this, k);
+      r = act(pc);
       const bool last = r != 0 || (qc & 3) == C_PASS;
-      next_actor();
-      const uint32_t t = pc; pc = qc; qc = t;
+      hand_over(pc, qc);
       if (last) break;
     }
-    return r ? r : turn_epilogue();
+    return turn_finish(r);
   }
   // normalised-frame form (S = P1, F = P2 before and after)
   __device__ __forceinline__ uint32_t update(uint32_t c1, uint32_t c2) {
@@ -1423,14 +1442,18 @@ struct EngineR {
     rng = accA * rng + accC;
   }
   // one random-policy turn-step of the rollout (choices x2 + update), frame-agnostic
-  __device__ __forceinline__ uint32_t random_step(uint32_t result, uint32_t hi, uint32_t lo) {
-    OAK_SCOPE(PS_STEP);
-    OAK_T0(t_ld);
+  __device__ __forceinline__ void random_choices(uint32_t result, uint32_t hi, uint32_t lo, uint32_t &cS, uint32_t &cF) const {
     const bool s_p1 = absp(S) == 0;
     const uint32_t req1 = (result >> 4) & 3, req2 = (result >> 6) & 3;
     const Legal LS = legal(S, s_p1 ? req1 : req2), LF = legal(F, s_p1 ? req2 : req1);
-    const uint32_t cS = nth_choice(LS, draw_index(s_p1, hi, lo, LS.n));
-    const uint32_t cF = nth_choice(LF, draw_index(!s_p1, hi, lo, LF.n));
+    cS = nth_choice(LS, draw_index(s_p1, hi, lo, LS.n));
+    cF = nth_choice(LF, draw_index(!s_p1, hi, lo, LF.n));
+  }
+  __device__ __forceinline__ uint32_t random_step(uint32_t result, uint32_t hi, uint32_t lo) {
+    OAK_SCOPE(PS_STEP);
+    OAK_T0(t_ld);
+    uint32_t cS, cF;
+    random_choices(result, hi, lo, cS, cF);
     OAK_T1(PS_LEGAL_DRAW, t_ld);
     return update_frame(cS, cF);
   }

@@ -436,6 +436,7 @@ struct RoundArgs {
                             // bits 16-24: ... or whose actives' {slot, hp} have not changed for this many turn-steps (256: never)
   uint32_t no_skip;         // 1: a proven inert standstill is played turn by turn like everything else (oakgpu_set_standstill_skip: A/B)
   uint32_t *stats;          // words 44-45 of the context's control block: {playouts fast-forwarded, turn-steps skipped}
+  uint32_t move_carry;      // 0..64 (oakgpu_set_move_carry): a turn's second action waits for the wave's next action pass unless this many lanes want it now
 };
 
 // One launch drains a GROUP of independent batches (oakgpu_rollout_group_dev): the queue hands out GLOBAL playout
@@ -610,6 +611,8 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
   if (!IS_RESUME && COLD_GU(prep) != 0) ust |= U_PREP;
   ust |= (blockIdx.x & 7u) << 8; // the queue head this wave starts at
   if (COLD_QU(no_skip) != 0) ust |= U_NO_SKIP;
+  // bits 24-31: the move-carry threshold (below).  A resume or tail round and a launch spread over part of its lanes never carry.
+  if (!IS_RESUME && COLD_QU(lanes) == 0) ust |= (COLD_QU(move_carry) & 0xFFu) << 24;
   ER e;
   e.m = party + tid;
   e.T = T;
@@ -766,9 +769,24 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
       }
     }
     if (__ballot(idx != DONE) == 0) break;
+    // MOVE CARRY.  A turn is up to two actions, and the wave walks ONE copy of the action code once per action.  A switch goes before
+    // a move, so the first walk holds the move pipeline for the move + move lanes alone and the second for them and the switch + move
+    // lanes together: two trips through before_move / execute_selected / run_move per turn-step, each for well under half of the wave.
+    // The lanes are independent playouts, so a lane's second action may as well wait for the wave's NEXT walk, where it runs beside
+    // the other lanes' first actions.  Such a lane is in MID-TURN: T_PEND and its pending choice byte sit in the free bits of `result`
+    // (whose low byte is 0 then: it reads as playing), it skips the turn's start in the next iteration, and its step count, `stale`
+    // and everything that retires, parks or refills a lane wait for the turn's end.  Per lane the engine operations and draws are the
+    // same sequence as ever.  The first trip through the move pipeline takes every pending move (a switch in front of a move has
+    // run by then).  The second trip takes what is still pending -- if at least `carry_below` (ust bits
+    // 24-31; 0 = always, the schedule without carrying) lanes want it, or if the wave FLUSHES: it is dry or an adopter that adopts
+    // (resume, tail and spread launches have carry_below 0).  So a wave that can suspend, a wave that leaves and every lane that
+    // is written out stands at a turn boundary: the drain, the adopters and the images are what they were.
+    constexpr uint32_t T_PEND = 0x100u, T_DONE = 0x200u; // during the walks the low byte of `result` is the turn's result so far
+    const bool mid = (result & T_PEND) != 0;
     bool playing = idx != DONE && idx != NONE && (result & 15) == 0 && steps < max_steps; // (NONE: an adopter's lane that waits)
+    const bool start = playing && !mid;
 #ifdef OAKGPU_TIMELINE
-    tl_steps += (unsigned long long)__popcll(__ballot(playing));
+    tl_steps += (unsigned long long)__popcll(__ballot(start));
 #endif
     // A standstill that can be PROVEN (EngineR::inert_standstill): each side is either FROZEN with no way out (gen 1 never thaws by
     // itself) or FORCED -- Rage-locked, or down to Struggle on its last Pokemon -- into a move the foe's types are immune to, and
@@ -782,7 +800,7 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
     // ~1,100 of 1.31 M playouts, each otherwise ~850 dependent turn-steps on an adopter.  Exact, not a heuristic:
     // tests/test_gpu_inert_standstill.py and tests/test_gpu_parity.py hold it to the oracle, which plays every turn.  The `stale`
     // gate keeps ordinary lanes from ever evaluating the predicate.
-    if (playing && stale >= (8u << 24) && !(ust & U_NO_SKIP)) {
+    if (start && stale >= (8u << 24) && !(ust & U_NO_SKIP)) {
       const int draws = e.inert_standstill(result);
       const uint32_t by_steps = max_steps - steps, by_turn = 1000u - e.turn;
       const uint32_t skip = (by_steps < by_turn ? by_steps : by_turn) - 1u; // (both >= 1 while playing)
@@ -794,13 +812,49 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
         atomicAdd((unsigned long long *)COLD_Q(stats, uint32_t *), 1ull | ((unsigned long long)skip << 32)); // {playouts, turn-steps}: one atomic
       }
     }
-    if (playing) {
-      const uint32_t hi = g.next32(), lo = g.next32(); // uniform_64 = hi << 32 | lo
-      result = e.random_step(result, hi, lo);
-      ++steps;
-      playing = (result & 15) == 0 && steps < max_steps;
-      const uint32_t sg = ((e.S.p4 ^ e.F.p4) >> 16) | (((e.S.o0 + e.F.o0) & 0xFFu) << 16);
-      stale = sg != (stale & 0xFFFFFFu) ? sg : stale + (stale < 0xFF000000u ? 0x01000000u : 0u);
+    {
+      OAK_SCOPE(PS_STEP);
+      // (the pending choice byte lives in bits 16-23 of `result` and the one after it in bits 24-31, during the walks as between
+      // iterations: a lane in mid-turn comes in with T_PEND, its last action and nothing behind it)
+      if (start) { // the turn's start: two draws of the choice stream, both sides' choices, who acts first
+        OAK_T0(t_ld);
+        const uint32_t hi = g.next32(), lo = g.next32(); // uniform_64 = hi << 32 | lo
+        uint32_t cS, cF, pc = 0, qc = 0;
+        e.random_choices(result, hi, lo, cS, cF);
+        OAK_T1(PS_LEGAL_DRAW, t_ld);
+        const uint32_t r = e.turn_prologue(cS, cF, pc, qc);
+        result = r ? (r | T_DONE) : (T_PEND | (pc << 16) | (qc << 24)); // (turn 0 sends both leads out and is over)
+      }
+      // ONE copy of the action code, walked up to three times.  A wave that carries walks it first for the lanes whose pending action
+      // is cheap (a switch, a pass) -- so that a switch + move turn has its move ready for the next walk --, then for every pending
+      // action: the one trip through the move pipeline that every iteration makes.  The third walk is the second trip, for what is
+      // still pending (move + move turns): only if `carry_below` lanes want it.  A wave that does not carry (threshold 0, or a
+      // flush) skips the first walk and always takes the third: the schedule of update_frame.
+      const bool carrying = (ust >> 24) != 0 && !(ust & (U_DRY | U_ADOPTING)); // wave-uniform
+#pragma unroll 1
+      for (uint32_t walk = carrying ? 0u : 1u;; ++walk) {
+        const uint32_t c = (result >> 16) & 0xFFu;
+        if ((result & T_PEND) && (walk != 0 || (c & 3) != C_MOVE)) {
+          OAK_SET_K(e, walk ? walk - 1 : 0);
+          const uint32_t r = e.act(c);
+          e.next_actor();
+          const uint32_t next = T_PEND | ((result >> 8) & 0xFF0000u); // the action behind it moves up; none: a pass
+          result = (r != 0 || ((next >> 16) & 3) == C_PASS) ? (r | T_DONE) : next;
+        }
+        if (walk == 2) break;
+        if (walk == 1) {
+          const uint32_t want = (uint32_t)__popcll(__ballot((result & T_PEND) != 0));
+          if (want == 0 || (carrying && want < (ust >> 24))) break;
+        }
+      }
+      // (a lane that is still pending is carried as it stands: low byte 0, still playing)
+      if (result & T_DONE) { // the turn's end, and what belongs to a turn boundary
+        result = e.turn_finish(result & 0xFFu);
+        ++steps;
+        playing = (result & 15) == 0 && steps < max_steps;
+        const uint32_t sg = ((e.S.p4 ^ e.F.p4) >> 16) | (((e.S.o0 + e.F.o0) & 0xFFu) << 16);
+        stale = sg != (stale & 0xFFFFFFu) ? sg : stale + (stale < 0xFF000000u ? 0x01000000u : 0u);
+      }
     }
     // a wave that holds a playout far beyond the usual length (99.5% end before 250 turn-steps) is on the launch's critical
     // path -- a 1000-step chain: it goes first on its SIMD (an adopter as soon as it adopts)
@@ -815,7 +869,7 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
     // wave-uniform: the queue is dry and too few lanes are still playing -> hand them to the next round
     const uint64_t still = __ballot(playing);
     const bool suspend = IS_DRY && still != 0 && (uint32_t)__popcll(still) < suspend_below;
-    const bool lng = n_adopt != 0 && !IS_ADOPTER && playing && (steps >= (long_steps & 0xFFFFu) || (stale >> 24) >= (long_steps >> 16)); // a bulk wave's long (or standing-still) playout: to the adopters
+    const bool lng = n_adopt != 0 && !IS_ADOPTER && playing && !(result & T_PEND) && (steps >= (long_steps & 0xFFFFu) || (stale >> 24) >= (long_steps >> 16)); // a bulk wave's long (or standing-still) playout: to the adopters
     if (idx != DONE && idx != NONE && (!playing || suspend || lng)) { // retire the lane: publish a finished playout / park a suspended or donated one
       OAK_SCOPE(PS_PUBLISH);
       const bool fin = !playing;
@@ -1646,6 +1700,7 @@ struct oakgpu_ctx {
   int spread_lanes;       // launches that do not fill the device: lanes per wave that take playouts (-1 automatic, 0 / 64 = all)
   int queue_order;        // 1 (default): a saturated launch hands its playouts out likely-longest first (k_queue_order)
   int standstill_skip;    // 1 (default): the queue kernel takes a PROVEN inert standstill to its last turn-step in one go (exact); 0: plays every turn
+  int move_carry;         // 0..64 (oakgpu_set_move_carry): the queue kernel's move carry, 0 = a turn's two actions in one wave iteration
   uint32_t *d_order;      // total entries
   size_t order_n;
   uint32_t order_pair = 0;      // k_queue_order's two counters: control words 32-33 and 34-35 in turn (each launch clears the next one's)
@@ -1829,6 +1884,8 @@ int oakgpu_create(oakgpu_ctx **out, int device) {
   if (const char *env = getenv("OAKGPU_QUEUE_ORDER")) c->queue_order = atoi(env) != 0;
   c->standstill_skip = 1;
   if (const char *env = getenv("OAKGPU_STANDSTILL_SKIP")) c->standstill_skip = atoi(env) != 0;
+  c->move_carry = OAKGPU_MOVE_CARRY_DEFAULT;
+  if (const char *env = getenv("OAKGPU_MOVE_CARRY")) c->move_carry = atoi(env) < 0 ? 0 : atoi(env) > 64 ? 64 : atoi(env);
   c->migrate = 1;
   c->migrate_steps = 300;
   c->migrate_adopters = 0;
@@ -1941,6 +1998,12 @@ int oakgpu_set_spread(oakgpu_ctx *c, int lanes) {
 int oakgpu_set_standstill_skip(oakgpu_ctx *c, int on) {
   if (!c) return bad("null ctx");
   c->standstill_skip = on != 0;
+  return 0;
+}
+
+int oakgpu_set_move_carry(oakgpu_ctx *c, int below) {
+  if (!c || below < 0 || below > 64) return bad("oakgpu_set_move_carry: below must be 0 (off) .. 64 lanes");
+  c->move_carry = below;
   return 0;
 }
 
@@ -2146,6 +2209,7 @@ static int launch_group(oakgpu_ctx *c, const oak::BatchDesc *descs, uint32_t cou
     q.order = r == 0 ? order : nullptr;
     q.long_steps = (uint32_t)(c->migrate_steps > 0xFFFF ? 0xFFFF : c->migrate_steps) | (uint32_t)(c->migrate_window > 0 ? c->migrate_window : 256) << 16;
     q.no_skip = c->standstill_skip ? 0u : 1u;
+    q.move_carry = (uint32_t)c->move_carry;
     q.stats = c->d_queue + OAKGPU_CTL_FAST_FORWARDED;
     if (migrate) { q.adopt_ctl = c->d_queue + 40; q.adopt_list = (uint64_t *)lists[0]; q.epoch = c->ticket_epoch; q.n_adopters = adopters; } // (one round: both lists' memory)
     q.list_in = r ? lists[(r - 1) & 1] : nullptr;

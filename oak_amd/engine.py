@@ -102,6 +102,11 @@ class Context:
         _lib.check(self.lib.oakgpu_queue_order(self.handle, descs, len(bs), _p(order), C.byref(suspects)))
         return order, suspects.value
 
+    def set_move_carry(self, below=0):
+        """A turn's second action waits for the wave's next action pass unless `below` lanes want it now (oakgpu_set_move_carry;
+        0 = off, at most 64); results never change."""
+        _lib.check(self.lib.oakgpu_set_move_carry(self.handle, int(below)))
+
     def set_standstill_skip(self, on=True):
         """The queue kernel's exact fast-forward of proven inert standstills (oakgpu_set_standstill_skip); results never change."""
         _lib.check(self.lib.oakgpu_set_standstill_skip(self.handle, 1 if on else 0))

@@ -6,7 +6,7 @@ from oak_amd.engine import Context
 ctx = Context(0); lib, h = ctx.lib, ctx.handle
 dev = torch.device('cuda', 0)
 stream = torch.cuda.current_stream(dev); ctx.set_stream(stream.cuda_stream); ctx.ensure_ou_pools()
-n = 65536; u8 = torch.uint8
+n = int(os.environ.get('N', 65536)); u8 = torch.uint8  # (N=1310720: a launch that fills the device, the driver command's size)
 T = lambda *s, dt=u8: torch.empty(s, dtype=dt, device=dev)
 battles, durations, prng, rin, rout = T(n, 384), T(n, 8), T(n, 8), T(n), T(n)
 steps, values = T(n, dt=torch.int32), T(n, dt=torch.float32)

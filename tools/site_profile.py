@@ -20,7 +20,7 @@ from oak_amd.engine import Context  # noqa: E402
 NAMES = ["refill", "step", "legal_draw", "order", "exec_move", "switch_in", "before_move", "exec_selected_pre",
          "run_move", "gates_hit", "status_bodies", "damage", "secondary_apply", "faint_residual", "publish",
          "calc_damage", "apply_hits", "damage_tail", "heavy_switch", "h_conversion", "h_haze", "h_heal", "h_mimic", "h_poison",
-         "h_substitute", "h_transform", "h_bide", "h_sleep", "h_disable"]
+         "h_substitute", "h_transform", "h_bide", "h_sleep", "h_disable", "exec_move_k0", "exec_move_k1"]
 ctx = Context(0)
 lib, h = ctx.lib, ctx.handle
 dev = torch.device("cuda", 0)
@@ -50,7 +50,8 @@ for i, nm in enumerate(NAMES):
     passes, lanes, cyc, lanecyc = buf[4 * i:4 * i + 4]
     rows.append({"region": nm, "passes": passes, "lanes_per_pass": lanes / max(passes, 1), "cycles_per_pass": cyc / max(passes, 1),
                  "share_of_step_cycles": cyc / max(step_cycles, 1), "simt_eff": lanecyc / max(64 * cyc, 1)})
-print(json.dumps({"turn_steps": total_steps, "n": n, "rows": rows}))
+print(json.dumps({"turn_steps": total_steps, "n": n, "move_carry": os.environ.get("OAKGPU_MOVE_CARRY"), "launch_ms": ev0.elapsed_time(ev1),
+                  "exec_move_passes_per_turn_step_pass": buf[4 * 4] / max(buf[1 * 4], 1), "rows": rows}))
 for r in rows:
     print("%-18s passes %10d  lanes/pass %5.1f  cyc/pass %8.0f  share %6.3f  eff %5.3f" % (
         r["region"], r["passes"], r["lanes_per_pass"], r["cycles_per_pass"], r["share_of_step_cycles"], r["simt_eff"]), file=sys.stderr)
