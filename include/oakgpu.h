@@ -113,13 +113,8 @@ int oakgpu_set_move_carry(oakgpu_ctx *ctx, int below);
  * non-zero word as a failed call and clears it, so the error of any launch since the last synchronize is seen, not only the
  * last launch's. */
 int oakgpu_get_queue_counters(oakgpu_ctx *ctx, uint32_t *out64);
-/* Rollout engine (results never depend on it; both are bit-identical): 2 = register-resident engine, one wave per
- * workgroup, queue refill (default); 1 = LDS-resident engine (first implementation, kept as a second opinion on the
- * transcription: it is what oakgpu_update* / _choices* / the tree step run, and tests/test_gpu_parity.py holds its
- * rollouts to the oracle too), one launch per batch.  (Round 2-4's engine 3, 256-lane workgroups that re-binned
- * their playouts by action class through LDS before each action slot, lost to engine 2 by 8-12 % and was removed in round 5:
- * DESIGN_HISTORY.md.) */
-int oakgpu_set_rollout_engine(oakgpu_ctx *ctx, int engine);
+/* One engine runs everything in this header: the register-resident one (oak_amd/csrc/gen1_regs.hpp), held to the CPU oracle byte for
+ * byte by tests/.  (The LDS-resident engine written first, and the setter that selected it for rollouts, are gone: DESIGN_HISTORY.md.) */
 int oakgpu_device_count(void);
 
 /* ---- rollout: replaces MCTS::Search::init_stats_and_rollout (search/mcts.h:448-496) and,
@@ -191,6 +186,8 @@ int oakgpu_rollout_shared_device(oakgpu_ctx *ctx, const uint8_t *battle, const u
 
 /* ---- batched pkmn_gen1_battle_update (call sites mcts.h:278,350,463,479; wrapper
  * libpkmn/pkmn.h:106-139).  In place on battles; durations in/out (chance options);
+ * device battles of the _dev forms of this call, oakgpu_choices, oakgpu_init_battles and oakgpu_random_ou_battles: on a 4-byte boundary
+ * at least (16-byte aligned battles, as hipMalloc gives them, move in 16-byte pieces, others in dwords);
  * actions (nullable) receives the 16-byte chance-actions key of each update (mcts.h:93-98);
  * overrides (nullable, n x 16) are the calc damage-roll overrides (mcts.h:575-588). */
 int oakgpu_update_dev(oakgpu_ctx *ctx, uint8_t *battles, const uint8_t *c1, const uint8_t *c2,
@@ -220,9 +217,9 @@ int oakgpu_poke_engine_eval(oakgpu_ctx *ctx, const uint8_t *battles, uint32_t n,
  * report result, the 16-byte observation key (pkmn_gen1_battle_options_chance_actions; tree edge key,
  * mcts.h:93-98,359) and BOTH players' legal choices in the new state (n x 9 + n counts each; counts are 0
  * for terminal results).  rolls in {1, 2, 3, 20, 39}: damage-roll clamping of battle_options_set
- * (mcts.h:569-604; 39 = off), override bytes derived from the last two bytes of battle.rng.  Since round 5 the level runs on the
- * register-resident engine (k_tree_step_staged; 16-byte aligned battles, else -- or with OAKGPU_TREE_STEP=lds in the environment -- on the
- * LDS-resident engine's k_tree_step); both are held to the oracle byte for byte (tests/tree_step_check.py, test_gpu_move_coverage.py). */
+ * (mcts.h:569-604; 39 = off), override bytes derived from the last two bytes of battle.rng.  The level runs on the register-resident engine
+ * (k_tree_step_staged): 16-byte aligned battles move through it in 16-byte pieces, battles on a 4-byte boundary in dwords; both forms
+ * are held to the oracle byte for byte (tests/tree_step_check.py, test_gpu_move_coverage.py). */
 int oakgpu_tree_step_dev(oakgpu_ctx *ctx, uint8_t *battles, uint8_t *durations, uint8_t *results, const uint8_t *c1,
                          const uint8_t *c2, uint32_t n, uint32_t rolls, uint8_t *actions, uint8_t *p1_choices,
                          uint8_t *p1_counts, uint8_t *p2_choices, uint8_t *p2_counts);

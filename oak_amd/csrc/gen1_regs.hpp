@@ -1,8 +1,8 @@
-// oak_amd/csrc/gen1_regs.hpp -- register-resident gen-1 turn resolution for the rollout kernel.
+// oak_amd/csrc/gen1_regs.hpp -- register-resident gen-1 turn resolution: the engine every kernel runs
+// (encodings, layout and tables: gen1_device.hpp; the CPU oracle is what it is held to, byte for byte).
 //
-// Same semantics as gen1_device.hpp (and bit-identical results), different data placement:
-// with one wave per SIMD every LDS round trip (~64-128 cycles) is exposed, and the LDS-resident
-// engine makes ~150 of them per turn-step.  Here everything a turn touches lives in VGPRs:
+// With one wave per SIMD every LDS round trip (~64-128 cycles) is exposed, and an engine that keeps the
+// battle in LDS makes ~150 of them per turn-step.  Here everything a turn touches lives in VGPRs:
 //   * per side (struct SideR): the 32-byte active block, a cached copy of the stored (party)
 //     Pokemon behind it, the order bytes + last selected/used move, the chance durations word
 //     and a 6-bit "alive" mask (so legal-choice enumeration and faint checks need no memory);
@@ -110,7 +110,7 @@ __device__ __forceinline__ void cswap_sides(bool c, SideR &a, SideR &b) {
 // data is read with ds_read; as a generic pointer (flat loads that resolve to LDS) the staged kernel carried 44-54 spilled SGPRs.
 template <int STRIDE, bool TRACK_ACTIONS, bool GIN_LDS = false>
 struct EngineR {
-  lds_u32 *m; // party storage (lane-interleaved LDS, same addressing as Engine)
+  lds_u32 *m; // party storage (lane-interleaved LDS: dword w of this lane at m[w * STRIDE])
   Tables T;
   SideR S, F; // mover / target frame
   uint64_t actS, actF; // chance actions (TRACK_ACTIONS only)
@@ -727,7 +727,7 @@ struct EngineR {
   // effect-specific part only computes small decisions (gates, parameters) and all lanes meet at ONE
   // accuracy site, ONE secondary-roll site, ONE status site, ONE confusion site, ONE stat-stage site.
   // Per-lane RNG order is unchanged (accuracy -> effect rolls -> crit -> damage -> counts -> secondary
-  // chance -> secondary duration), so results stay bit-identical to gen1_device.hpp and the oracle.
+  // chance -> secondary duration), so results stay bit-identical to the oracle.
   __device__ void run_move(uint32_t mslot) {
     OAK_SCOPE(PS_RUN_MOVE);
     OAK_T0(t_g);

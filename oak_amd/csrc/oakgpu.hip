@@ -1,9 +1,9 @@
 // oak_amd/csrc/oakgpu.hip -- HIP kernels (gfx950) + the C ABI of include/oakgpu.h.
 //
-// K1  k_rollout   : batched random playouts (replaces cpp/include/search/mcts.h:448-496 and
-//                   the per-iteration prep of mcts.h:250-263): one lane per playout, the
-//                   384-byte battle resident in LDS (lane-interleaved) for the whole playout,
-//                   tables in LDS, choice RNG (fast_prng) and durations in registers.
+// K1  k_rollout_* : batched random playouts (replaces cpp/include/search/mcts.h:448-496 and
+//                   the per-iteration prep of mcts.h:250-263): one lane per playout on the
+//                   register-resident engine (gen1_regs.hpp), party slots and tables in LDS,
+//                   choice RNG (fast_prng) and durations in registers.
 //     k_update    : batched pkmn_gen1_battle_update (+ chance durations / actions / calc).
 //     k_choices   : batched pkmn_gen1_battle_choices.
 //     k_init      : batched PKMN::battle (cpp/include/libpkmn/init.h:90-154) + opening update.
@@ -18,6 +18,7 @@
 #include <random>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/oakgpu.h"
@@ -30,11 +31,8 @@
 namespace oak {
 using namespace walk; // the queue constants, cold_ptr_at and STAGE_STRIDE are record_walk.hpp's
 
-constexpr int BLOCK = 256;      // 4 waves: one per SIMD of a CU
 constexpr int STATE_WORDS = 96; // 384-byte battle
-constexpr int STATE_LDS_BYTES = STATE_WORDS * BLOCK * 4;
 constexpr int TABLE_LDS_PAD = TABLE_PAD; // (record_walk.hpp; this file's older name for it)
-constexpr int ENGINE_LDS_BYTES = STATE_LDS_BYTES + TABLE_LDS_PAD;
 
 // The engine's tables (moves, species, type chart, boosts, reciprocals, effect descriptors: 3.4 KB) as ONE image in exactly
 // their LDS layout, built once per device by k_build_table_image (oakgpu_create).  A kernel's prologue is then a straight
@@ -69,65 +67,6 @@ __device__ __forceinline__ Tables stage_default_tables(lds_u8 *lds) {
   return tables_at(lds);
 }
 
-// AoS (n x 384 B, 4-byte aligned) <-> lane-interleaved LDS, whole workgroup cooperating.
-template <int BLK = BLOCK>
-__device__ __forceinline__ void load_state(lds_u32 *state, const uint8_t *battles, uint32_t base, uint32_t count) {
-  const uint32_t *src = (const uint32_t *)battles + (size_t)base * STATE_WORDS;
-  for (uint32_t i = threadIdx.x; i < count * STATE_WORDS; i += BLK) {
-    uint32_t b = i / STATE_WORDS, w = i - b * STATE_WORDS;
-    state[w * BLK + b] = src[i];
-  }
-}
-template <int BLK = BLOCK>
-__device__ __forceinline__ void store_state(const lds_u32 *state, uint8_t *battles, uint32_t base, uint32_t count) {
-  uint32_t *dst = (uint32_t *)battles + (size_t)base * STATE_WORDS;
-  for (uint32_t i = threadIdx.x; i < count * STATE_WORDS; i += BLK) {
-    uint32_t b = i / STATE_WORDS, w = i - b * STATE_WORDS;
-    dst[i] = state[w * BLK + b];
-  }
-}
-
-__device__ __forceinline__ uint32_t mod64_small(uint32_t hi, uint32_t lo, uint32_t m) {
-  // (hi * 2^32 + lo) % m for small m, 32-bit ops only
-  uint32_t two32 = (0xFFFFFFFFu % m + 1) % m;
-  return ((hi % m) * two32 + (lo % m)) % m;
-}
-
-// ---- MCTS::randomize_hidden_variables (cpp/include/search/durations.h:25-97) ---------------
-template <class E>
-__device__ void randomize_hidden(E &e) {
-  // rows of the reference's 4 x 40 binding table as run lengths: {15,15,6,4} {24,8,8} {20,20} {40}
-  const uint32_t hi = e.r32(B_RNG + 4), lo = e.r32(B_RNG);
-  for (int s = 0; s < 2; ++s) {
-    const int so = s * SIDE_SZ;
-    const uint32_t d = e.dur_of(s);
-    const uint32_t confusion = (d >> 18) & 7, disable = (d >> 21) & 15, attacking = (d >> 25) & 7, binding = (d >> 28) & 7;
-    if (confusion) {
-      uint32_t one = confusion == 1;
-      uint32_t max = (6 - (confusion + one)) & 0xFF;
-      e.set_conf_left(so, (mod64_small(hi, lo, max) + 1 + one) & 0xFF);
-    }
-    if (disable) e.set_disable_left(so, (mod64_small(hi, lo, (9 - disable) & 0xFF) + 1) & 0xFF);
-    if (attacking && (e.vlo(so) & (V_BIDE | V_THRASHING)))
-      e.set_attacks(so, attacking == 3 ? 1u : 4u - (attacking + mod64_small(hi, lo, 2)));
-    if (binding) {
-      uint32_t idx = mod64_small(hi, lo, 40), a;
-      if (binding == 1) a = idx < 15 ? 1 : idx < 30 ? 2 : idx < 36 ? 3 : 4;
-      else if (binding == 2) a = idx < 24 ? 1 : idx < 32 ? 2 : 3;
-      else if (binding == 3) a = idx < 20 ? 1 : 2;
-      else a = 1;
-      e.set_attacks(so, a);
-    }
-    for (int i = 0; i < 6; ++i) {
-      uint32_t sleep = (d >> (3 * i)) & 7;
-      if (!sleep) continue;
-      int pk = so + PK_SZ * ((int)e.r8(so + O_ORDER + i) - 1);
-      uint32_t st = e.r8(pk + P_STATUS);
-      if ((st & 7) && !(st & 0x80)) e.w8(pk + P_STATUS, (st & 0xF8) | ((mod64_small(hi, lo, (8 - sleep) & 0xFF) + 1) & 0xFF));
-    }
-  }
-}
-
 // ---- K1: random playouts -------------------------------------------------------------------
 struct RolloutArgs {
   const uint8_t *battles;
@@ -143,65 +82,8 @@ struct RolloutArgs {
   uint8_t *durations_out;
 };
 
-template <int BLK>
-__global__ __launch_bounds__(BLK) void k_rollout(RolloutArgs a) {
-  extern __shared__ __align__(16) uint8_t smem[];
-  lds_u32 *state = (lds_u32 *)smem;
-  Tables T = stage_default_tables((lds_u8 *)smem + STATE_WORDS * BLK * 4);
-  const uint32_t base = blockIdx.x * BLK;
-  const uint32_t count = min((uint32_t)BLK, a.n - base);
-  load_state<BLK>(state, a.battles, base, count);
-  __syncthreads();
-  const uint32_t tid = threadIdx.x, lane = base + tid;
-  if (tid < count) {
-    Engine<BLK, false> e;
-    e.m = state + tid;
-    e.T = T;
-    const uint32_t *dsrc = (const uint32_t *)a.durations + 2 * (size_t)lane;
-    e.dur64 = (uint64_t)dsrc[0] | ((uint64_t)dsrc[1] << 32);
-    e.over16 = 0;
-    FastPrng g;
-    const uint32_t *psrc = (const uint32_t *)a.prng + 2 * (size_t)lane;
-    g.s0 = psrc[0];
-    g.s1 = psrc[1];
-    if (a.prep) { // mcts.h:254-259
-      uint32_t hi = g.next32(), lo = g.next32();
-      e.w32(B_RNG, lo);
-      e.w32(B_RNG + 4, hi);
-      randomize_hidden(e);
-    }
-    uint32_t result = a.results_in[lane];
-    uint32_t steps = 0;
-    while ((result & 15) == 0 && steps < a.max_steps) {
-      const uint32_t hi = g.next32(), lo = g.next32(); // uniform_64 = hi << 32 | lo
-      auto c1s = e.choices(0, (result >> 4) & 3);
-      const uint32_t c1 = c1s.get(mod64_small(hi, lo, c1s.n));
-      auto c2s = e.choices(1, (result >> 6) & 3);
-      const uint32_t c2 = c2s.get(hi % c2s.n);
-      result = e.update(c1, c2);
-      ++steps;
-    }
-    a.results_out[lane] = (uint8_t)result;
-    a.steps_out[lane] = steps;
-    const uint32_t t = result & 15;
-    a.values_out[lane] = t == R_WIN ? 1.0f : t == R_LOSE ? 0.0f : 0.5f;
-    uint32_t *pdst = (uint32_t *)a.prng + 2 * (size_t)lane;
-    pdst[0] = g.s0;
-    pdst[1] = g.s1;
-    if (a.durations_out) {
-      uint32_t *ddst = (uint32_t *)a.durations_out + 2 * (size_t)lane;
-      ddst[0] = e.dur_of(0);
-      ddst[1] = e.dur_of(1);
-    }
-  }
-  if (a.battles_out) {
-    __syncthreads();
-    store_state<BLK>(state, a.battles_out, base, count);
-  }
-}
-
-// ---- K1 (register-resident engine, gen1_regs.hpp): same contract as k_rollout.  LDS holds only
-// the party slots (72 dwords per lane) + one table image per workgroup, so 8 waves fit on a CU.
+// ---- K1, one lane per playout and no queue (oakgpu_rollout_dev's contract).  LDS holds only
+// the party slots (24 dwords per lane) + one table image per workgroup, so 8 waves fit on a CU.
 template <int BLK>
 __global__ __launch_bounds__(BLK, 2) void k_rollout_regs(RolloutArgs a) {
   extern __shared__ __align__(16) uint8_t smem[];
@@ -256,31 +138,74 @@ __global__ __launch_bounds__(BLK, 2) void k_rollout_regs(RolloutArgs a) {
 // (a generic pointer: the flat loads resolve to LDS).
 constexpr int STAGED_COLD_BYTES = 128; // the kernel arguments, parked (below)
 constexpr int STAGED_LDS_BYTES = 24 * 64 * 4 + TABLE_LDS_PAD + 64 * STAGE_STRIDE * 4 + STAGED_COLD_BYTES;
+// The staged kernels' LDS, in order: the engine's party slots, the tables, the wave's 64 staged rows, the parked arguments.
+__device__ __forceinline__ lds_u32 *staged_rows(uint8_t *smem) { return (lds_u32 *)((lds_u8 *)smem + 24 * 64 * 4 + TABLE_LDS_PAD); }
+// Pointer arguments are parked in LDS across the turn loop, like k_rollout_queue's cold arguments (read back with cold_ptr_at): as
+// kernel arguments they held ~20 SGPRs the loop's nested exec masks need (54 spilled SGPRs, a v_writelane / v_readlane pair each, in
+// a kernel that runs ONE turn-step per launch in BASELINE configs[2])
+template <class Args>
+__device__ __forceinline__ lds_u32 *park_args(lds_u32 *stage, const Args &a) {
+  static_assert(sizeof(Args) <= STAGED_COLD_BYTES, "parked arguments fit");
+  lds_u32 *cold = stage + 64 * STAGE_STRIDE;
+  if (threadIdx.x < sizeof(Args) / 4) cold[threadIdx.x] = ((const uint32_t *)&a)[threadIdx.x];
+  return cold;
+}
+// The wave's `cnt` battles, from battle `base` on, between global memory and the staged rows, 24 pieces per lane and trip: piece i is
+// piece i % P of battle i / P.  DWORDS = false moves 16-byte pieces in one trip (battles 16-byte aligned); DWORDS = true moves dwords in
+// four (all 96 in flight at once spilled the update kernels), for the entry points that take battles at any 4-byte boundary.  A barrier
+// belongs behind stage_in and in front of stage_out.
+template <bool DWORDS>
+struct StagePiece {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  typedef std::conditional_t<DWORDS, uint32_t, u32x4> type;
+  static constexpr uint32_t P = 384 / sizeof(type), WORDS = sizeof(type) / 4; // pieces per battle, words per piece
+};
+template <bool DWORDS = false>
+__device__ __forceinline__ void stage_in(lds_u32 *stage, const uint8_t *battles, uint32_t base, uint32_t cnt) {
+  using SP = StagePiece<DWORDS>;
+  typedef typename SP::type piece;
+  const piece *src = (const piece *)(battles + (size_t)base * 384);
+  const uint32_t tid = threadIdx.x;
+#pragma unroll 1
+  for (uint32_t q = 0; q < SP::P; q += 24) {
+    piece t[24];
+#pragma unroll
+    for (uint32_t k = 0; k < 24; ++k) { const uint32_t i = (q + k) * 64 + tid; t[k] = src[i < cnt * SP::P ? i : 0]; }
+#pragma unroll
+    for (uint32_t k = 0; k < 24; ++k) { const uint32_t i = (q + k) * 64 + tid, b = i / SP::P, w = i - b * SP::P; *(OAK_LDS piece *)(stage + b * STAGE_STRIDE + SP::WORDS * w) = t[k]; }
+  }
+}
+template <bool DWORDS = false>
+__device__ __forceinline__ void stage_out(const lds_u32 *stage, uint8_t *battles, uint32_t base, uint32_t cnt) {
+  using SP = StagePiece<DWORDS>;
+  typedef typename SP::type piece;
+  piece *dst = (piece *)(battles + (size_t)base * 384);
+  const uint32_t tid = threadIdx.x;
+  // (opaque: the bounds tests here are the ones of stage_in, and the compiler kept their 24 lane masks -- 48 SGPRs -- alive across the
+  // whole turn loop to reuse them: 44 of k_rollout_staged's 46 spilled SGPRs)
+  uint32_t cnt_out = cnt;
+  asm volatile("" : "+s"(cnt_out));
+#pragma unroll 1
+  for (uint32_t q = 0; q < SP::P; q += 24) {
+#pragma unroll
+    for (uint32_t k = 0; k < 24; ++k) {
+      const uint32_t i = (q + k) * 64 + tid, b = i / SP::P, w = i - b * SP::P;
+      if (i < cnt_out * SP::P) dst[i] = *(const OAK_LDS piece *)(stage + b * STAGE_STRIDE + SP::WORDS * w);
+    }
+  }
+}
+
 __global__ __launch_bounds__(64, 2) void k_rollout_staged(RolloutArgs a) {
   extern __shared__ __align__(16) uint8_t smem[];
   lds_u32 *party = (lds_u32 *)smem;
   using ER = EngineR<64, false, true>;
   Tables T = stage_default_tables((lds_u8 *)smem + ER::PARTY_WORDS * 64 * 4);
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  typedef OAK_LDS u32x4 lds_u128;
-  lds_u32 *stage = (lds_u32 *)((lds_u8 *)smem + ER::PARTY_WORDS * 64 * 4 + TABLE_LDS_PAD);
-  // the output pointers are parked in LDS across the turn loop, like k_rollout_queue's cold arguments: as kernel arguments they held
-  // ~20 SGPRs the loop's nested exec masks need (54 spilled SGPRs, a v_writelane / v_readlane pair each, in a kernel that runs ONE
-  // turn-step per launch in BASELINE configs[2])
-  static_assert(sizeof(RolloutArgs) <= STAGED_COLD_BYTES, "parked arguments fit");
-  lds_u32 *cold = stage + 64 * STAGE_STRIDE;
-  if (threadIdx.x < sizeof(RolloutArgs) / 4) cold[threadIdx.x] = ((const uint32_t *)&a)[threadIdx.x];
+  lds_u32 *stage = staged_rows(smem);
+  lds_u32 *cold = park_args(stage, a);
 #define SA_PTR(field, type) cold_ptr_at<type>(cold, offsetof(RolloutArgs, field))
   const uint32_t tid = threadIdx.x, base = blockIdx.x * 64, lane = base + tid;
   const uint32_t cnt = a.n - base < 64 ? a.n - base : 64; // battles of this wave
-  {
-    const u32x4 *src = (const u32x4 *)(a.battles + (size_t)base * 384);
-    u32x4 t[24];
-#pragma unroll
-    for (int k = 0; k < 24; ++k) { const uint32_t i = k * 64 + tid; t[k] = src[i < cnt * 24 ? i : 0]; } // float4 i = battle i / 24, piece i % 24
-#pragma unroll
-    for (int k = 0; k < 24; ++k) { const uint32_t i = k * 64 + tid, b = i / 24, w = i - b * 24; *(lds_u128 *)(stage + b * STAGE_STRIDE + 4 * w) = t[k]; }
-  }
+  stage_in(stage, a.battles, base, cnt);
   __syncthreads();
   uint32_t result = 0, steps = 0;
   FastPrng g;
@@ -326,16 +251,7 @@ __global__ __launch_bounds__(64, 2) void k_rollout_staged(RolloutArgs a) {
   uint8_t *bout = SA_PTR(battles_out, uint8_t *);
   if (!bout) return;
   __syncthreads();
-  u32x4 *dst = (u32x4 *)(bout + (size_t)base * 384);
-  // (opaque: the 24 bounds tests here are the ones of the staging loop at the top, and the compiler kept their 24 lane masks -- 48
-  // SGPRs -- alive across the whole turn loop to reuse them: 44 of the kernel's 46 spilled SGPRs)
-  uint32_t cnt_out = cnt;
-  asm volatile("" : "+s"(cnt_out));
-#pragma unroll
-  for (int k = 0; k < 24; ++k) {
-    const uint32_t i = k * 64 + tid, b = i / 24, w = i - b * 24;
-    if (i < cnt_out * 24) dst[i] = *(const lds_u128 *)(stage + b * STAGE_STRIDE + 4 * w);
-  }
+  stage_out(stage, bout, base, cnt);
 #undef SA_PTR
 }
 
@@ -1161,55 +1077,73 @@ __global__ __launch_bounds__(256) void k_root_step_report(const unsigned long lo
   }
 }
 
-// ---- batched single update -------------------------------------------------------------------
-__global__ __launch_bounds__(BLOCK) void k_update(uint8_t *battles, const uint8_t *c1, const uint8_t *c2,
-                                                  uint8_t *durations, uint8_t *actions, const uint8_t *overrides,
-                                                  uint32_t n, uint8_t *results) {
+// ---- the libpkmn boundary: k_update, k_choices, k_init, k_random_ou ---------------------------------------------------------------
+// One wave per workgroup on the register engine, its battles staged like k_rollout_staged's (STAGED_LDS_BYTES); DWORDS as stage_in's.
+// This is one wave's LDS and its share of the batch.
+struct BoundaryWave {
+  using ER = EngineR<64, true, true>;
+  lds_u32 *party, *stage;
+  Tables T;
+  uint32_t tid, base, lane, cnt;
+  __device__ __forceinline__ BoundaryWave(uint8_t *smem, uint32_t n, bool tables = true) {
+    party = (lds_u32 *)smem;
+    stage = staged_rows(smem);
+    T = tables ? stage_default_tables((lds_u8 *)smem + ER::PARTY_WORDS * 64 * 4) : Tables{};
+    tid = threadIdx.x, base = blockIdx.x * 64, lane = base + tid;
+    cnt = n - base < 64 ? n - base : 64;
+  }
+  __device__ __forceinline__ uint8_t *row() const { return (uint8_t *)(stage + tid * STAGE_STRIDE); } // (EngineR takes the address space back: gin_t)
+  __device__ __forceinline__ ER engine() const { ER e; e.m = party + tid; e.T = T; return e; }
+};
+
+// batched pkmn_gen1_battle_update: k_tree_step_staged's update half, with the caller's override bytes
+template <bool DWORDS>
+__global__ __launch_bounds__(64, 2) void k_update(uint8_t *battles, const uint8_t *c1, const uint8_t *c2, uint8_t *durations, uint8_t *actions,
+                                                  const uint8_t *overrides, uint32_t n, uint8_t *results) {
   extern __shared__ __align__(16) uint8_t smem[];
-  lds_u32 *state = (lds_u32 *)smem;
-  Tables T = stage_default_tables((lds_u8 *)smem + STATE_LDS_BYTES);
-  const uint32_t base = blockIdx.x * BLOCK;
-  const uint32_t count = min((uint32_t)BLOCK, n - base);
-  load_state(state, battles, base, count);
+  const BoundaryWave w(smem, n);
+  // the lane's small inputs are asked for in front of the staging: their round trip runs beside it (a batch of one is all latency)
+  const bool live = w.tid < w.cnt;
+  uint32_t *d = (uint32_t *)durations + 2 * (size_t)w.lane;
+  uint32_t d0 = 0, d1 = 0, pc1 = 0, pc2 = 0, over1 = 0, over2 = 0;
+  if (live) {
+    d0 = d[0], d1 = d[1], pc1 = c1[w.lane], pc2 = c2[w.lane];
+    if (overrides) over1 = overrides[(size_t)w.lane * 16], over2 = overrides[(size_t)w.lane * 16 + 8];
+  }
+  stage_in<DWORDS>(w.stage, battles, w.base, w.cnt);
   __syncthreads();
-  const uint32_t tid = threadIdx.x, lane = base + tid;
-  if (tid < count) {
-    Engine<BLOCK, true> e;
-    e.m = state + tid;
-    e.T = T;
-    uint32_t *d = (uint32_t *)durations + 2 * (size_t)lane;
-    e.dur64 = (uint64_t)d[0] | ((uint64_t)d[1] << 32);
-    e.over16 = overrides ? (uint32_t)overrides[(size_t)lane * 16] | ((uint32_t)overrides[(size_t)lane * 16 + 8] << 8) : 0;
-    e.act0 = e.act1 = 0;
-    results[lane] = (uint8_t)e.update(c1[lane], c2[lane]);
-    d[0] = e.dur_of(0);
-    d[1] = e.dur_of(1);
+  if (live) {
+    auto e = w.engine();
+    e.load_battle_global(w.row(), d0, d1);
+    e.S.misc |= over1 << 16;
+    e.F.misc |= over2 << 16;
+    results[w.lane] = (uint8_t)e.update(pc1, pc2);
+    d[0] = e.S.dur;
+    d[1] = e.F.dur;
     if (actions) {
-      uint64_t *ad = (uint64_t *)actions + 2 * (size_t)lane;
-      ad[0] = e.act0;
-      ad[1] = e.act1;
+      uint64_t *ad = (uint64_t *)actions + 2 * (size_t)w.lane;
+      ad[0] = e.actS;
+      ad[1] = e.actF;
     }
+    e.store_battle_global(w.row());
   }
   __syncthreads();
-  store_state(state, battles, base, count);
+  stage_out<DWORDS>(w.stage, battles, w.base, w.cnt);
 }
 
-__global__ __launch_bounds__(BLOCK) void k_choices(const uint8_t *battles, const uint8_t *results, int player,
-                                                   uint8_t *out, uint8_t *counts, uint32_t n) {
+template <bool DWORDS>
+__global__ __launch_bounds__(64, 2) void k_choices(const uint8_t *battles, const uint8_t *results, int player, uint8_t *out, uint8_t *counts, uint32_t n) {
   extern __shared__ __align__(16) uint8_t smem[];
-  lds_u32 *state = (lds_u32 *)smem;
-  const uint32_t base = blockIdx.x * BLOCK;
-  const uint32_t count = min((uint32_t)BLOCK, n - base);
-  load_state(state, battles, base, count);
+  const BoundaryWave w(smem, n, false); // (choices reads no table)
+  const uint32_t r = w.tid < w.cnt ? results[w.lane] : 0u; // (in front of the staging, as in k_update)
+  stage_in<DWORDS>(w.stage, battles, w.base, w.cnt);
   __syncthreads();
-  const uint32_t tid = threadIdx.x, lane = base + tid;
-  if (tid < count) {
-    Engine<BLOCK, false> e;
-    e.m = state + tid;
-    const uint32_t r = results[lane];
-    auto c = e.choices(player, player == 0 ? (r >> 4) & 3 : (r >> 6) & 3);
-    counts[lane] = (uint8_t)c.n;
-    for (uint32_t i = 0; i < OAKGPU_MAX_CHOICES; ++i) out[(size_t)lane * OAKGPU_MAX_CHOICES + i] = i < c.n ? (uint8_t)c.get(i) : 0;
+  if (w.tid < w.cnt) {
+    auto e = w.engine();
+    e.load_battle_global(w.row(), 0, 0); // (nor a duration)
+    const auto c = e.choices(player ? e.F : e.S, player == 0 ? (r >> 4) & 3 : (r >> 6) & 3);
+    counts[w.lane] = (uint8_t)c.n;
+    for (uint32_t i = 0; i < OAKGPU_MAX_CHOICES; ++i) out[(size_t)w.lane * OAKGPU_MAX_CHOICES + i] = i < c.n ? (uint8_t)c.get(i) : 0;
   }
 }
 
@@ -1223,83 +1157,28 @@ __device__ __forceinline__ uint32_t roll_byte(uint32_t rolls, uint32_t seed) {
   if (rolls == 1) return 236;
   return 217 + (38 / (rolls - 1)) * (seed % rolls);
 }
-__global__ __launch_bounds__(BLOCK) void k_tree_step(uint8_t *battles, uint8_t *durations, uint8_t *results, const uint8_t *c1,
-                                                     const uint8_t *c2, uint32_t n, uint32_t rolls, uint8_t *actions,
-                                                     uint8_t *ch1, uint8_t *cnt1, uint8_t *ch2, uint8_t *cnt2) {
-  extern __shared__ __align__(16) uint8_t smem[];
-  lds_u32 *state = (lds_u32 *)smem;
-  Tables T = stage_default_tables((lds_u8 *)smem + STATE_LDS_BYTES);
-  const uint32_t base = blockIdx.x * BLOCK;
-  const uint32_t count = min((uint32_t)BLOCK, n - base);
-  load_state(state, battles, base, count);
-  __syncthreads();
-  const uint32_t tid = threadIdx.x, lane = base + tid;
-  if (tid < count && c1[lane] != 0xFF) {
-    Engine<BLOCK, true> e;
-    e.m = state + tid;
-    e.T = T;
-    uint32_t *d = (uint32_t *)durations + 2 * (size_t)lane;
-    e.dur64 = (uint64_t)d[0] | ((uint64_t)d[1] << 32);
-    e.over16 = 0;
-    if (rolls != 39) {
-      const uint32_t hi = e.r32(B_RNG + 4);
-      e.over16 = roll_byte(rolls, (hi >> 16) & 0xFF) | (roll_byte(rolls, hi >> 24) << 8);
-    }
-    e.act0 = e.act1 = 0;
-    const uint32_t r = e.update(c1[lane], c2[lane]);
-    results[lane] = (uint8_t)r;
-    d[0] = e.dur_of(0);
-    d[1] = e.dur_of(1);
-    uint64_t *ad = (uint64_t *)actions + 2 * (size_t)lane;
-    ad[0] = e.act0;
-    ad[1] = e.act1;
-#pragma unroll 1
-    for (int pl = 0; pl < 2; ++pl) {
-      auto c = e.choices(pl, pl == 0 ? (r >> 4) & 3 : (r >> 6) & 3);
-      uint8_t *out = (pl ? ch2 : ch1) + (size_t)lane * OAKGPU_MAX_CHOICES;
-      (pl ? cnt2 : cnt1)[lane] = (r & 15) ? 0 : (uint8_t)c.n;
-      for (uint32_t i = 0; i < OAKGPU_MAX_CHOICES; ++i) out[i] = i < c.n ? (uint8_t)c.get(i) : 0;
-    }
-  }
-  __syncthreads();
-  store_state(state, battles, base, count);
-}
-
-// Round 5: the same tree level on the REGISTER-resident engine, staged like k_rollout_staged -- one wave per workgroup, its 64
-// battles moved between global memory and LDS with coalesced 1-KB accesses, 35 KB of LDS (four workgroups per CU) instead of
-// k_tree_step's 100 KB workgroup of four waves whose every field access is an LDS round trip.  A search level is a launch of
-// 4-32 k lanes that does not fill the device: its time is the latency of ONE wave's turn-step, which is what the register engine
-// halves (6.4 us for a dense lone wave).  Chance actions (EngineR<.., TRACK_ACTIONS>) and the damage-roll clamp (the override byte
-// in SideR::misc) are the register engine's own; outputs are byte for byte k_tree_step's (tests/test_gpu_parity.py:
-// test_tree_step_levels_match_the_oracle runs both against the oracle).
+// Staged like k_rollout_staged: one wave per workgroup, its 64 battles moved between global memory and LDS with coalesced 1-KB
+// accesses, 35 KB of LDS (four workgroups per CU).  A search level is a launch of 4-32 k lanes that does not fill the device: its
+// time is the latency of ONE wave's turn-step (6.4 us for a dense lone wave).  Chance actions (EngineR<.., TRACK_ACTIONS>) and the
+// damage-roll clamp (the override byte in SideR::misc) are the register engine's own.  DWORDS as stage_in's.
 struct TreeStepArgs {
   uint8_t *battles, *durations, *results;
   const uint8_t *c1, *c2;
   uint8_t *actions, *ch1, *cnt1, *ch2, *cnt2;
   uint32_t n, rolls;
 };
+template <bool DWORDS>
 __global__ __launch_bounds__(64, 2) void k_tree_step_staged(TreeStepArgs a) {
   extern __shared__ __align__(16) uint8_t smem[];
   lds_u32 *party = (lds_u32 *)smem;
   using ER = EngineR<64, true, true>;
   Tables T = stage_default_tables((lds_u8 *)smem + ER::PARTY_WORDS * 64 * 4);
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  typedef OAK_LDS u32x4 lds_u128;
-  lds_u32 *stage = (lds_u32 *)((lds_u8 *)smem + ER::PARTY_WORDS * 64 * 4 + TABLE_LDS_PAD);
-  static_assert(sizeof(TreeStepArgs) <= STAGED_COLD_BYTES, "parked arguments fit");
-  lds_u32 *cold = stage + 64 * STAGE_STRIDE; // the pointers are parked in LDS across the turn-step (k_rollout_staged: the SGPRs they would hold are needed for exec masks)
-  if (threadIdx.x < sizeof(TreeStepArgs) / 4) cold[threadIdx.x] = ((const uint32_t *)&a)[threadIdx.x];
+  lds_u32 *stage = staged_rows(smem);
+  lds_u32 *cold = park_args(stage, a); // (k_rollout_staged: the SGPRs the pointers would hold across the turn-step are needed for exec masks)
 #define TS_PTR(field, type) cold_ptr_at<type>(cold, offsetof(TreeStepArgs, field))
   const uint32_t tid = threadIdx.x, base = blockIdx.x * 64, lane = base + tid;
   const uint32_t cnt = a.n - base < 64 ? a.n - base : 64; // battles of this wave
-  {
-    const u32x4 *src = (const u32x4 *)(a.battles + (size_t)base * 384);
-    u32x4 t[24];
-#pragma unroll
-    for (int k = 0; k < 24; ++k) { const uint32_t i = k * 64 + tid; t[k] = src[i < cnt * 24 ? i : 0]; }
-#pragma unroll
-    for (int k = 0; k < 24; ++k) { const uint32_t i = k * 64 + tid, b = i / 24, w = i - b * 24; *(lds_u128 *)(stage + b * STAGE_STRIDE + 4 * w) = t[k]; }
-  }
+  stage_in<DWORDS>(stage, a.battles, base, cnt);
   __syncthreads();
   const uint32_t n_all = (uint32_t)__builtin_amdgcn_readfirstlane((int)cold[offsetof(TreeStepArgs, n) / 4]);
   const uint32_t rolls = (uint32_t)__builtin_amdgcn_readfirstlane((int)cold[offsetof(TreeStepArgs, rolls) / 4]);
@@ -1333,14 +1212,7 @@ __global__ __launch_bounds__(64, 2) void k_tree_step_staged(TreeStepArgs a) {
     e.store_battle_global((uint8_t *)(stage + tid * STAGE_STRIDE));
   }
   __syncthreads();
-  u32x4 *dst = (u32x4 *)(TS_PTR(battles, uint8_t *) + (size_t)base * 384);
-  uint32_t cnt_out = cnt;
-  asm volatile("" : "+s"(cnt_out)); // (opaque: k_rollout_staged -- the bounds tests' lane masks would otherwise live across the turn-step)
-#pragma unroll
-  for (int k = 0; k < 24; ++k) {
-    const uint32_t i = k * 64 + tid, b = i / 24, w = i - b * 24;
-    if (i < cnt_out * 24) dst[i] = *(const lds_u128 *)(stage + b * STAGE_STRIDE + 4 * w);
-  }
+  stage_out<DWORDS>(stage, TS_PTR(battles, uint8_t *), base, cnt);
 #undef TS_PTR
 }
 
@@ -1578,55 +1450,66 @@ __device__ void init_from_teams(E &e, const uint8_t *teams /* 60 B, this lane */
   e.w32(B_RNG, seed_lo);
   e.w32(B_RNG + 4, seed_hi);
 }
-
-__global__ __launch_bounds__(BLOCK) void k_init(const uint8_t *teams, const uint64_t *seeds, uint32_t n, int first_update,
-                                                uint8_t *battles, uint8_t *durations, uint8_t *results) {
-  extern __shared__ __align__(16) uint8_t smem[];
-  lds_u32 *state = (lds_u32 *)smem;
-  Tables T = stage_default_tables((lds_u8 *)smem + STATE_LDS_BYTES);
-  __syncthreads();
-  const uint32_t base = blockIdx.x * BLOCK;
-  const uint32_t count = min((uint32_t)BLOCK, n - base);
-  const uint32_t tid = threadIdx.x, lane = base + tid;
-  if (tid < count) {
-    Engine<BLOCK, false> e;
-    e.m = state + tid;
-    e.T = T;
-    e.dur64 = 0;
-    e.over16 = 0;
-    const uint64_t sd = seeds[lane];
-    init_from_teams(e, teams + (size_t)lane * OAKGPU_TEAMS_SIZE, (uint32_t)sd, (uint32_t)(sd >> 32));
-    uint32_t r = mk_result(0, C_MOVE, C_MOVE);
-    if (first_update) r = e.update(0, 0);
-    if (results) results[lane] = (uint8_t)r;
-    if (durations) {
-      uint32_t *d = (uint32_t *)durations + 2 * (size_t)lane;
-      d[0] = e.dur_of(0);
-      d[1] = e.dur_of(1);
-    }
+// what init_from_teams writes through: this lane's staged row (bytes and dwords only: the engine reads the row as dwords)
+struct RowWriter {
+  lds_u8 *row;
+  Tables T;
+  __device__ __forceinline__ void w8(int off, uint32_t v) { row[off] = (uint8_t)v; }
+  __device__ __forceinline__ void w16(int off, uint32_t v) { w8(off, v); w8(off + 1, v >> 8); }
+  __device__ __forceinline__ void w32(int off, uint32_t v) { *(lds_u32 *)(row + off) = v; }
+};
+// A lane's new battle from its teams into its staged row, the opening update if asked for, and the outputs (both nullable).  The
+// row is the lane's own: its LDS writes and the engine's reads stay in order without a barrier.
+__device__ __forceinline__ void open_battle(const BoundaryWave &w, const uint8_t *teams, uint32_t seed_lo, uint32_t seed_hi, bool first_update,
+                                            uint8_t *durations, uint8_t *results) {
+  RowWriter rw{(lds_u8 *)(w.stage + w.tid * STAGE_STRIDE), w.T};
+  init_from_teams(rw, teams, seed_lo, seed_hi);
+  uint32_t r = mk_result(0, C_MOVE, C_MOVE), d0 = 0, d1 = 0;
+  if (first_update) {
+    auto e = w.engine();
+    e.load_battle_global(w.row(), 0, 0);
+    r = e.update(0, 0);
+    e.store_battle_global(w.row());
+    d0 = e.S.dur;
+    d1 = e.F.dur;
   }
-  __syncthreads();
-  store_state(state, battles, base, count);
+  if (results) results[w.lane] = (uint8_t)r;
+  if (durations) {
+    uint32_t *d = (uint32_t *)durations + 2 * (size_t)w.lane;
+    d[0] = d0;
+    d[1] = d1;
+  }
 }
 
-__global__ __launch_bounds__(BLOCK) void k_random_ou(uint64_t seed0, uint32_t n, const uint8_t *legal, int n_legal,
-                                                     const uint8_t *pools, const uint8_t *sizes, uint8_t *battles,
-                                                     uint8_t *durations, uint8_t *prng, uint8_t *results) {
+template <bool DWORDS>
+__global__ __launch_bounds__(64, 2) void k_init(const uint8_t *teams, const uint64_t *seeds, uint32_t n, int first_update, uint8_t *battles,
+                                                uint8_t *durations, uint8_t *results) {
   extern __shared__ __align__(16) uint8_t smem[];
-  lds_u32 *state = (lds_u32 *)smem;
-  Tables T = stage_default_tables((lds_u8 *)smem + STATE_LDS_BYTES);
+  // the lane's seed and teams are asked for in front of the table copy: their round trip runs beside it (a batch of one is all latency)
+  const uint32_t lane = blockIdx.x * 64 + threadIdx.x;
+  uint64_t sd = 0;
+  uint8_t mine[OAKGPU_TEAMS_SIZE];
+  if (lane < n) {
+    sd = seeds[lane];
+#pragma unroll
+    for (int i = 0; i < OAKGPU_TEAMS_SIZE; ++i) mine[i] = teams[(size_t)lane * OAKGPU_TEAMS_SIZE + i];
+  }
+  const BoundaryWave w(smem, n);
   __syncthreads();
-  const uint32_t base = blockIdx.x * BLOCK;
-  const uint32_t count = min((uint32_t)BLOCK, n - base);
-  const uint32_t tid = threadIdx.x, lane = base + tid;
-  if (tid < count) {
-    Engine<BLOCK, false> e;
-    e.m = state + tid;
-    e.T = T;
-    e.dur64 = 0;
-    e.over16 = 0;
+  if (w.tid < w.cnt) open_battle(w, mine, (uint32_t)sd, (uint32_t)(sd >> 32), first_update != 0, durations, results);
+  __syncthreads();
+  stage_out<DWORDS>(w.stage, battles, w.base, w.cnt);
+}
+
+template <bool DWORDS>
+__global__ __launch_bounds__(64, 2) void k_random_ou(uint64_t seed0, uint32_t n, const uint8_t *legal, int n_legal, const uint8_t *pools,
+                                                     const uint8_t *sizes, uint8_t *battles, uint8_t *durations, uint8_t *prng, uint8_t *results) {
+  extern __shared__ __align__(16) uint8_t smem[];
+  const BoundaryWave w(smem, n);
+  __syncthreads();
+  if (w.tid < w.cnt) {
     FastPrng g;
-    g.seed(seed0 + lane);
+    g.seed(seed0 + w.lane);
     uint8_t teams[OAKGPU_TEAMS_SIZE];
     for (int i = 0; i < OAKGPU_TEAMS_SIZE; ++i) teams[i] = 0;
     for (int s = 0; s < 2; ++s)
@@ -1652,18 +1535,13 @@ __global__ __launch_bounds__(BLOCK) void k_random_ou(uint64_t seed0, uint32_t n,
         }
       }
     const uint32_t hi = g.next32(), lo = g.next32();
-    init_from_teams(e, teams, lo, hi);
-    const uint32_t r = e.update(0, 0);
-    results[lane] = (uint8_t)r;
-    uint32_t *d = (uint32_t *)durations + 2 * (size_t)lane;
-    d[0] = e.dur_of(0);
-    d[1] = e.dur_of(1);
-    uint32_t *pd = (uint32_t *)prng + 2 * (size_t)lane;
+    open_battle(w, teams, lo, hi, true, durations, results);
+    uint32_t *pd = (uint32_t *)prng + 2 * (size_t)w.lane;
     pd[0] = g.s0;
     pd[1] = g.s1;
   }
   __syncthreads();
-  store_state(state, battles, base, count);
+  stage_out<DWORDS>(w.stage, battles, w.base, w.cnt);
 }
 
 } // namespace oak
@@ -1675,7 +1553,6 @@ struct oakgpu_ctx {
   bool own_stream;
   uint8_t *d_legal, *d_pools, *d_sizes;
   int n_legal;
-  int rollout_engine; // 2 = register-resident (default), 1 = LDS-resident (a second implementation of the same engine: A/B)
   int playouts_per_lane; // > 1: persistent grid of n / this lanes with queue refill (k_rollout_queue)
   uint32_t *d_queue;      // 64 counters: suspended-playout counts of the regrouping rounds, queue-order counters, migration control block
   uint32_t *d_heads;      // the queue kernel's heads: MAX_ROUNDS rounds x 8 heads, each on a 256-byte line of its own
@@ -1801,19 +1678,29 @@ int oakgpu_device_count(void) {
 }
 
 static int set_lds_limits() {
-  HIPCHK(hipFuncSetAttribute((const void *)oak::k_rollout<64>, hipFuncAttributeMaxDynamicSharedMemorySize, oak::STATE_WORDS * 64 * 4 + oak::TABLE_LDS_PAD));
   HIPCHK(hipFuncSetAttribute((const void *)oak::k_rollout_regs<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 24 * 64 * 4 + oak::TABLE_LDS_PAD));
   HIPCHK(hipFuncSetAttribute((const void *)oak::k_rollout_staged, hipFuncAttributeMaxDynamicSharedMemorySize, oak::STAGED_LDS_BYTES));
   HIPCHK(hipFuncSetAttribute((const void *)oak::k_rollout_draws<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 24 * 64 * 4 + oak::TABLE_LDS_PAD));
   HIPCHK(hipFuncSetAttribute((const void *)oak::k_rollout_queue<64, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 24 * 64 * 4 + oak::TABLE_LDS_PAD + oak::COLD_LDS_BYTES));
-  HIPCHK(hipFuncSetAttribute((const void *)oak::k_update, hipFuncAttributeMaxDynamicSharedMemorySize, oak::ENGINE_LDS_BYTES));
-  HIPCHK(hipFuncSetAttribute((const void *)oak::k_choices, hipFuncAttributeMaxDynamicSharedMemorySize, oak::ENGINE_LDS_BYTES));
-  HIPCHK(hipFuncSetAttribute((const void *)oak::k_tree_step, hipFuncAttributeMaxDynamicSharedMemorySize, oak::ENGINE_LDS_BYTES));
-  HIPCHK(hipFuncSetAttribute((const void *)oak::k_tree_step_staged, hipFuncAttributeMaxDynamicSharedMemorySize, oak::STAGED_LDS_BYTES));
-  HIPCHK(hipFuncSetAttribute((const void *)oak::k_init, hipFuncAttributeMaxDynamicSharedMemorySize, oak::ENGINE_LDS_BYTES));
-  HIPCHK(hipFuncSetAttribute((const void *)oak::k_random_ou, hipFuncAttributeMaxDynamicSharedMemorySize, oak::ENGINE_LDS_BYTES));
+#define STAGED_LIMIT(kernel)                                                                                                           \
+  HIPCHK(hipFuncSetAttribute((const void *)oak::kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, oak::STAGED_LDS_BYTES)); \
+  HIPCHK(hipFuncSetAttribute((const void *)oak::kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, oak::STAGED_LDS_BYTES))
+  STAGED_LIMIT(k_update);
+  STAGED_LIMIT(k_choices);
+  STAGED_LIMIT(k_tree_step_staged);
+  STAGED_LIMIT(k_init);
+  STAGED_LIMIT(k_random_ou);
+#undef STAGED_LIMIT
   return 0;
 }
+
+// A staged kernel over n battles, one wave per 64: its 16-byte form, or its dword form when `battles` sits on a 4-byte boundary only.
+#define LAUNCH_STAGED(kernel, battles, n, ...)                                                                                          \
+  do {                                                                                                                                  \
+    if (((uintptr_t)(battles) & 15) == 0) hipLaunchKernelGGL(oak::kernel<false>, dim3(((n) + 63) / 64), dim3(64), oak::STAGED_LDS_BYTES, c->stream, __VA_ARGS__); \
+    else hipLaunchKernelGGL(oak::kernel<true>, dim3(((n) + 63) / 64), dim3(64), oak::STAGED_LDS_BYTES, c->stream, __VA_ARGS__);             \
+    HIPCHK(hipGetLastError());                                                                                                          \
+  } while (0)
 
 int oakgpu_create(oakgpu_ctx **out, int device) {
   if (!out) return bad("oakgpu_create: null out");
@@ -1902,8 +1789,6 @@ int oakgpu_create(oakgpu_ctx **out, int device) {
   if (const char *env = getenv("OAKGPU_ROUNDS")) c->rounds = atoi(env) < 1 ? 1 : atoi(env) > 8 ? 8 : atoi(env);
   if (const char *env = getenv("OAKGPU_SUSPEND_BELOW")) c->suspend_below = atoi(env) < 0 ? 0 : atoi(env) > 64 ? 64 : atoi(env);
   if (const char *env = getenv("OAKGPU_ROUND_SHRINK")) c->round_shrink = atoi(env) < 1 ? 1 : atoi(env);
-  c->rollout_engine = 2;
-  if (const char *env = getenv("OAKGPU_ROLLOUT_ENGINE")) c->rollout_engine = atoi(env) == 1 ? 1 : 2;
   hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e != hipSuccess) { delete c; return fail(e, "hipStreamCreate"); }
   *out = c;
@@ -1947,12 +1832,6 @@ int oakgpu_set_stream(oakgpu_ctx *c, void *hip_stream) {
 int oakgpu_set_playouts_per_lane(oakgpu_ctx *c, int k) {
   if (!c || k < 1) return bad("oakgpu_set_playouts_per_lane: bad argument");
   c->playouts_per_lane = k;
-  return 0;
-}
-
-int oakgpu_set_rollout_engine(oakgpu_ctx *c, int engine) {
-  if (!c || engine < 1 || engine > 2) return bad("oakgpu_set_rollout_engine: engine must be 1 (LDS-resident) or 2 (register-resident)");
-  c->rollout_engine = engine;
   return 0;
 }
 
@@ -2086,8 +1965,6 @@ extern "C" int oakgpu_timeline(unsigned long long *out, int waves) { // profile 
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(oak::g_timeline), sizeof(unsigned long long) * 5 * (size_t)waves) != hipSuccess;
 }
 #endif
-
-static inline uint32_t grid_for(uint32_t n) { return (n + oak::BLOCK - 1) / oak::BLOCK; }
 
 // ---- group launch of the queue kernel --------------------------------------------------------------------------
 // The batch table travels through a small ring of pinned host slots -> device slots (async copy on the context's
@@ -2265,16 +2142,11 @@ int oakgpu_queue_order(oakgpu_ctx *c, const oakgpu_rollout_batch *batches, uint3
 
 static int launch_single(oakgpu_ctx *c, const oak::RolloutArgs &a) { // one lane per playout, no queue
   const uint32_t n = a.n;
-  const size_t lds64 = oak::STATE_WORDS * 64 * 4 + oak::TABLE_LDS_PAD;
-  if (c->rollout_engine == 1) { // LDS-resident engine (gen1_device.hpp), kept for A/B and as a second implementation
-    hipLaunchKernelGGL(oak::k_rollout<64>, dim3((n + 63) / 64), dim3(64), lds64, c->stream, a);
-  } else {                      // register-resident engine (gen1_regs.hpp)
-    static const bool no_staged = getenv("OAKGPU_NO_STAGED") != nullptr; // (A/B)
-    if (a.max_steps <= 16 && !no_staged && ((uintptr_t)a.battles & 15) == 0 && (!a.battles_out || ((uintptr_t)a.battles_out & 15) == 0))
-      hipLaunchKernelGGL(oak::k_rollout_staged, dim3((n + 63) / 64), dim3(64), oak::STAGED_LDS_BYTES, c->stream, a);
-    else
-      hipLaunchKernelGGL(oak::k_rollout_regs<64>, dim3((n + 63) / 64), dim3(64), 24 * 64 * 4 + oak::TABLE_LDS_PAD, c->stream, a);
-  }
+  static const bool no_staged = getenv("OAKGPU_NO_STAGED") != nullptr; // (A/B)
+  if (a.max_steps <= 16 && !no_staged && ((uintptr_t)a.battles & 15) == 0 && (!a.battles_out || ((uintptr_t)a.battles_out & 15) == 0))
+    hipLaunchKernelGGL(oak::k_rollout_staged, dim3((n + 63) / 64), dim3(64), oak::STAGED_LDS_BYTES, c->stream, a);
+  else
+    hipLaunchKernelGGL(oak::k_rollout_regs<64>, dim3((n + 63) / 64), dim3(64), 24 * 64 * 4 + oak::TABLE_LDS_PAD, c->stream, a);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2301,7 +2173,7 @@ int oakgpu_rollout_group_dev(oakgpu_ctx *c, const oakgpu_rollout_batch *batches,
   // no queue: one launch per batch -- also for launches capped at a few turn-steps (stepping a resident batch turn by turn,
   // BASELINE configs[2]): there is no tail for a queue to fill, and twice the waves hide twice the latency (measured, one
   // turn-step of 65,536 battles: 61 us against 99 us; tools/onestep_latency.py)
-  if (c->rollout_engine == 1 || c->playouts_per_lane <= 1 || max_steps <= 16) {
+  if (c->playouts_per_lane <= 1 || max_steps <= 16) {
     HIPCHK(hipSetDevice(c->device));
     for (uint32_t i = 0; i < used; ++i) {
       const oak::BatchDesc &d = descs[i];
@@ -2553,9 +2425,7 @@ int oakgpu_update_dev(oakgpu_ctx *c, uint8_t *battles, const uint8_t *c1, const 
   if (n == 0) return 0;
   if (!battles || !c1 || !c2 || !durations || !results) return bad("oakgpu_update_dev: null required pointer");
   HIPCHK(hipSetDevice(c->device));
-  hipLaunchKernelGGL(oak::k_update, dim3(grid_for(n)), dim3(oak::BLOCK), oak::ENGINE_LDS_BYTES, c->stream, battles, c1, c2,
-                     durations, actions, overrides, n, results);
-  HIPCHK(hipGetLastError());
+  LAUNCH_STAGED(k_update, battles, n, battles, c1, c2, durations, actions, overrides, n, results);
   return 0;
 }
 
@@ -2565,9 +2435,7 @@ int oakgpu_choices_dev(oakgpu_ctx *c, const uint8_t *battles, const uint8_t *res
   if (n == 0) return 0;
   if (!battles || !results || !out || !counts || player < 0 || player > 1) return bad("oakgpu_choices_dev: bad argument");
   HIPCHK(hipSetDevice(c->device));
-  hipLaunchKernelGGL(oak::k_choices, dim3(grid_for(n)), dim3(oak::BLOCK), oak::ENGINE_LDS_BYTES, c->stream, battles, results,
-                     player, out, counts, n);
-  HIPCHK(hipGetLastError());
+  LAUNCH_STAGED(k_choices, battles, n, battles, results, player, out, counts, n);
   return 0;
 }
 
@@ -2580,14 +2448,8 @@ int oakgpu_tree_step_dev(oakgpu_ctx *c, uint8_t *battles, uint8_t *durations, ui
     return bad("oakgpu_tree_step_dev: null required pointer");
   if (!(rolls == 1 || rolls == 2 || rolls == 3 || rolls == 20 || rolls == 39)) return bad("oakgpu_tree_step_dev: rolls must be 1, 2, 3, 20 or 39");
   HIPCHK(hipSetDevice(c->device));
-  static const bool lds_engine = getenv("OAKGPU_TREE_STEP") && strcmp(getenv("OAKGPU_TREE_STEP"), "lds") == 0; // (A/B: the LDS-resident engine's kernel)
-  if (!lds_engine && ((uintptr_t)battles & 15) == 0 && ((uintptr_t)durations & 3) == 0 && ((uintptr_t)actions & 7) == 0) {
-    const oak::TreeStepArgs ta{battles, durations, results, c1, c2, actions, p1_choices, p1_counts, p2_choices, p2_counts, n, rolls};
-    hipLaunchKernelGGL(oak::k_tree_step_staged, dim3((n + 63) / 64), dim3(64), oak::STAGED_LDS_BYTES, c->stream, ta);
-  } else
-    hipLaunchKernelGGL(oak::k_tree_step, dim3(grid_for(n)), dim3(oak::BLOCK), oak::ENGINE_LDS_BYTES, c->stream, battles, durations,
-                       results, c1, c2, n, rolls, actions, p1_choices, p1_counts, p2_choices, p2_counts);
-  HIPCHK(hipGetLastError());
+  const oak::TreeStepArgs ta{battles, durations, results, c1, c2, actions, p1_choices, p1_counts, p2_choices, p2_counts, n, rolls};
+  LAUNCH_STAGED(k_tree_step_staged, battles, n, ta);
   return 0;
 }
 
@@ -2625,9 +2487,7 @@ int oakgpu_init_battles_dev(oakgpu_ctx *c, const uint8_t *teams, const uint64_t 
   if (n == 0) return 0;
   if (!teams || !seeds || !battles) return bad("oakgpu_init_battles_dev: null required pointer");
   HIPCHK(hipSetDevice(c->device));
-  hipLaunchKernelGGL(oak::k_init, dim3(grid_for(n)), dim3(oak::BLOCK), oak::ENGINE_LDS_BYTES, c->stream, teams, seeds, n,
-                     first_update, battles, durations, results);
-  HIPCHK(hipGetLastError());
+  LAUNCH_STAGED(k_init, battles, n, teams, seeds, n, first_update, battles, durations, results);
   return 0;
 }
 
@@ -2672,9 +2532,7 @@ int oakgpu_random_ou_battles_dev(oakgpu_ctx *c, uint64_t seed0, uint32_t n, uint
   if (n == 0) return 0;
   if (!battles || !durations || !prng_state || !results) return bad("oakgpu_random_ou_battles_dev: null pointer");
   HIPCHK(hipSetDevice(c->device));
-  hipLaunchKernelGGL(oak::k_random_ou, dim3(grid_for(n)), dim3(oak::BLOCK), oak::ENGINE_LDS_BYTES, c->stream, seed0, n,
-                     c->d_legal, c->n_legal, c->d_pools, c->d_sizes, battles, durations, prng_state, results);
-  HIPCHK(hipGetLastError());
+  LAUNCH_STAGED(k_random_ou, battles, n, seed0, n, c->d_legal, c->n_legal, c->d_pools, c->d_sizes, battles, durations, prng_state, results);
   return 0;
 }
 

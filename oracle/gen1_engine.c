@@ -50,8 +50,8 @@
 #include <string.h>
 
 /* The two roll-order choices above that pkmn/engine's -Dshowdown path settles by following Pokemon Showdown's own code (the
- * build of /root/reference/dev/libpkmn:9 IS -Dshowdown), as compile-time switches shared -- by name and default -- with the two
- * HIP engines (oak_amd/csrc/gen1_device.hpp); 0 restores rounds 1-3's behaviour in all three:
+ * build of /root/reference/dev/libpkmn:9 IS -Dshowdown), as compile-time switches shared -- by name and default -- with the
+ * HIP engine (oak_amd/csrc/gen1_device.hpp holds them, gen1_regs.hpp reads them); 0 restores rounds 1-3's behaviour in both:
  *   OAK_MULTIHIT_ROLL_FIRST  the multi-hit count is rolled behind the accuracy check, BEFORE crit / damage (Showdown
  *                            data/mods/gen1/scripts.ts tryMoveHit: `hits = this.battle.sample([2,2,2,3,3,3,4,5])`, then moveHit);
  *   OAK_PSYWAVE_SHOWDOWN     Psywave draws random(0, level * 3 / 2) and FAILS on 0 (data/mods/gen1/moves.ts psywave: "Desync

@@ -18,12 +18,14 @@ def hip():
 
 
 class Dev:
-    """A device copy of a numpy array (or an uninitialised buffer of its shape)."""
+    """A device copy of a numpy array (or an uninitialised buffer of its shape); `offset` bytes into a slightly larger allocation
+    (hipMalloc aligns to 256 bytes: the offset is the alignment the array gets)."""
 
-    def __init__(self, arr, fill=None):
+    def __init__(self, arr, fill=None, offset=0):
         self.shape, self.dtype, self.nbytes = arr.shape, arr.dtype, max(arr.nbytes, 4)
-        self.p = C.c_void_p()
-        assert hip().hipMalloc(C.byref(self.p), self.nbytes) == 0
+        self.base = C.c_void_p()
+        assert hip().hipMalloc(C.byref(self.base), self.nbytes + offset) == 0
+        self.p = C.c_void_p(self.base.value + offset)
         if fill is not None:
             assert hip().hipMemset(self.p, fill, self.nbytes) == 0
         else:
@@ -40,4 +42,4 @@ class Dev:
         return out
 
     def free(self):
-        hip().hipFree(self.p)
+        hip().hipFree(self.base)

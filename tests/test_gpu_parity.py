@@ -114,15 +114,108 @@ def test_stepwise_update_choices_actions(gpu_ctx):
 
 def test_tree_step_levels_match_the_oracle(gpu_ctx):
     """oakgpu_tree_step_dev (one search level: joint action, result, chance-action key, both players' next choices) over random
-    walks, finished lanes and every damage-roll clamp, every output byte against the oracle -- the default kernel (round 5: the
-    register-resident engine, staged) in this process, the LDS-resident engine's kernel in a child with OAKGPU_TREE_STEP=lds."""
-    import subprocess
+    walks, finished lanes and every damage-roll clamp, every output byte against the oracle -- with 16-byte aligned battles and with
+    battles on a 4-byte boundary only, the weakest alignment include/oakgpu.h allows (the kernel then stages dwords)."""
     import tree_step_check
     assert tree_step_check.run(gpu_ctx) > 20000
     assert tree_step_check.run(gpu_ctx, n=64 * 5 + 1, levels=12, seed0=0x7EE51000) > 1000      # a ragged last wave of one lane
-    env = dict(os.environ, OAKGPU_TREE_STEP="lds")
-    p = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tree_step_check.py"), "700", "25"], env=env, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0 and "kernel: lds" in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])
+    assert tree_step_check.run(gpu_ctx, n=64 * 2 + 1, levels=25, seed0=0x7EE52000, offset=4) > 1000
+
+
+@pytest.mark.parametrize("offset", [0, 4])
+@pytest.mark.parametrize("n", [1, 64, 65, 64 * 5 + 1])
+def test_boundary_entry_points_match_the_oracle(gpu_ctx, n, offset):
+    """oakgpu_random_ou_battles_dev, oakgpu_choices_dev, oakgpu_update_dev and oakgpu_init_battles_dev (one wave per 64 battles on the
+    register engine, battles staged through LDS) against the oracle, every output byte: a wave boundary and a ragged last wave of one
+    lane, battles 16-byte aligned (offset 0) and on a 4-byte boundary only (offset 4: the dword staging), every nullable argument null
+    and non-null, teams of one, five and six Pokemon."""
+    from hipmem import Dev
+    lib, h = gpu_ctx.lib, gpu_ctx.handle
+    P = lambda x: None if x is None else x.p
+
+    def call(f, *args):
+        assert f(h, *args) == 0, lib.oakgpu_last_error()
+        gpu_ctx.synchronize()
+
+    # random_ou_battles: battles, durations, prng and results of the oracle's generator
+    gpu_ctx.ensure_ou_pools()
+    seed0 = 0xB0DA0000 + 1000 * n
+    b, d, p, r = O.make_random_ou_batch(n, seed0=seed0)
+    db = Dev(np.zeros((n, 384), np.uint8), offset=offset)
+    dd, dp, dr = Dev(np.zeros((n, 8), np.uint8)), Dev(np.zeros((n, 8), np.uint8)), Dev(np.zeros(n, np.uint8))
+    call(lib.oakgpu_random_ou_battles_dev, seed0, n, P(db), P(dd), P(dp), P(dr))
+    assert (db.host() == b).all() and (dd.host() == d).all() and (dp.host() == p).all() and (dr.host() == r).all()
+
+    # choices of both players, then update in place: four steps, actions and overrides each null and non-null
+    dch, dcn = Dev(np.zeros((n, 9), np.uint8)), Dev(np.zeros(n, np.uint8))
+    dc1, dc2 = Dev(np.zeros(n, np.uint8)), Dev(np.zeros(n, np.uint8))
+    dact, dov = Dev(np.zeros((n, 16), np.uint8)), Dev(np.zeros((n, 16), np.uint8))
+    opts = [O.Options(d[i]) for i in range(n)]
+    rng = np.random.default_rng(n + offset)
+    for step in range(4):
+        assert ((r & 15) == 0).all()
+        picks = []
+        for pl in (0, 1):
+            call(lib.oakgpu_choices_dev, P(db), P(dr), pl, P(dch), P(dcn), n)
+            gch, gcn = dch.host(), dcn.host()
+            c = np.zeros(n, np.uint8)
+            for i in range(n):
+                o = O.choices(b[i], pl, (int(r[i]) >> (4 + 2 * pl)) & 3)
+                assert gcn[i] == len(o) and (gch[i, :len(o)] == o).all() and (gch[i, len(o):] == 0).all(), (step, pl, i)
+                c[i] = o[rng.integers(len(o))]
+            picks.append(c)
+        use_act, use_over = bool(step & 1), bool(step & 2)
+        over = np.zeros((n, 16), np.uint8)
+        over[:, 0], over[:, 8] = 217 + rng.integers(39, size=n), 236
+        dc1.put(picks[0])
+        dc2.put(picks[1])
+        dov.put(over)
+        dact.put(np.full((n, 16), 0xA5, np.uint8))
+        call(lib.oakgpu_update_dev, P(db), P(dc1), P(dc2), P(dd), P(dact) if use_act else None, P(dov) if use_over else None, n, P(dr))
+        for i in range(n):
+            opts[i].set(None, over[i] if use_over else None)
+            r[i] = O.update(b[i], int(picks[0][i]), int(picks[1][i]), opts[i])
+            d[i] = opts[i].durations
+        assert (dr.host() == r).all() and (dd.host() == d).all(), step
+        bad = np.nonzero((db.host() != b).any(axis=1))[0]
+        assert bad.size == 0, (step, int(bad[0]))
+        assert (dact.host() == (np.stack([o.actions for o in opts]) if use_act else 0xA5)).all(), step
+
+    # init_battles: lane i's teams by i % 3 -- P1 a single Pokemon, P2 five, both six (init_from_teams' empty slots)
+    from oak_amd import gamedata as G
+    legal, pools, sizes = G.ou_pools()
+    teams = np.zeros((n, 2, 6, 5), np.uint8)
+    for i in range(n):
+        for s in range(2):
+            sp = rng.choice(legal, 6, replace=False)
+            for k in range(6):
+                m = min(4, sizes[sp[k]])
+                teams[i, s, k, 0] = sp[k]
+                teams[i, s, k, 1:1 + m] = rng.choice(pools[sp[k], :sizes[sp[k]]], m, replace=False)
+        if i % 3 == 0:
+            teams[i, 0, 1:] = 0
+        elif i % 3 == 1:
+            teams[i, 1, 5] = 0
+    seeds = rng.integers(0, 2**63, n).astype(np.uint64)
+    dt, ds = Dev(teams.reshape(n, 60)), Dev(seeds)
+    for first_update in (0, 1):
+        ob = np.stack([O.init_battle(teams[i], int(seeds[i])) for i in range(n)])
+        od, orr = np.zeros((n, 8), np.uint8), np.full(n, 0x50, np.uint8)   # no update: both requests Move, durations clear
+        if first_update:
+            for i in range(n):
+                opt = O.Options()
+                orr[i] = O.update(ob[i], 0, 0, opt)
+                od[i] = opt.durations
+        for outputs in (False, True):
+            db.put(np.full((n, 384), 0xA5, np.uint8))
+            dd.put(np.full((n, 8), 0xA5, np.uint8))
+            dr.put(np.full(n, 0xA5, np.uint8))
+            call(lib.oakgpu_init_battles_dev, P(dt), P(ds), n, first_update, P(db), P(dd) if outputs else None, P(dr) if outputs else None)
+            bad = np.nonzero((db.host() != ob).any(axis=1))[0]
+            assert bad.size == 0, (first_update, outputs, int(bad[0]))
+            assert (dd.host() == (od if outputs else 0xA5)).all() and (dr.host() == (orr if outputs else 0xA5)).all(), (first_update, outputs)
+    for x in (db, dd, dp, dr, dch, dcn, dc1, dc2, dact, dov, dt, ds):
+        x.free()
 
 
 def test_init_battle_matches_oracle_and_golden(gpu_ctx):
@@ -631,32 +724,25 @@ def test_segment_mean_and_direct_rccl_all_gather(gpu_ctx):
     hip.hipFree(dr)
 
 
-def test_lds_resident_engine_rollouts_are_bit_identical(gpu_ctx):
-    """Engine 1 (k_rollout<64>: gen1_device.hpp's LDS-resident engine, written first and kept as a second implementation
-    of the same turn resolution) against the oracle: every output byte, with and without root prep, capped, ragged, and as
-    a group launch.  (The register-resident engine is what every other rollout test runs.)"""
-    try:
-        gpu_ctx.set_rollout_engine(1)
-        for n, max_steps, seed0 in ((3000, 1000, 0xB1A50000), (700, 23, 0xB1A51000), (9000, 1000, 0xB1A52000), (1, 1000, 0xB1A53000)):
-            b, d, p, r = O.make_random_ou_batch(n, seed0=seed0)
-            for prep in (False, True):
-                got = gpu_ctx.rollout(b, d, r, p, max_steps=max_steps, prep=prep, return_state=True)
-                ob, od, op = b.copy(), d.copy(), p.copy()
-                oout, osteps = O.rollout_batch(ob, od, r, op, max_steps=max_steps, prep=prep, threads=8)
-                assert (got["steps"] == osteps).all() and (got["results"] == oout).all(), (n, prep)
-                bad = np.nonzero((got["battles"] != ob).any(axis=1))[0]
-                assert bad.size == 0, (n, prep, int(bad[0]))
-                assert (got["durations"] == od).all() and (got["prng"] == op).all()
-        batches = [O.make_random_ou_batch(n, seed0=0xB1A60000 + 1000 * k) for k, n in enumerate((1200, 77, 2500))]
-        got = gpu_ctx.rollout_group([(b, d, r, p) for b, d, p, r in batches], return_state=True)
-        for (b, d, p, r), g in zip(batches, got):
+def test_rollout_shapes_with_final_state_are_bit_identical(gpu_ctx):
+    """The default engine's rollouts with the final state returned, against the oracle: every output byte, with and without root
+    prep, capped at 23 turn-steps (through the queue), ragged, a batch of one, and as a group launch."""
+    for n, max_steps, seed0 in ((3000, 1000, 0xB1A50000), (700, 23, 0xB1A51000), (9000, 1000, 0xB1A52000), (1, 1000, 0xB1A53000)):
+        b, d, p, r = O.make_random_ou_batch(n, seed0=seed0)
+        for prep in (False, True):
+            got = gpu_ctx.rollout(b, d, r, p, max_steps=max_steps, prep=prep, return_state=True)
             ob, od, op = b.copy(), d.copy(), p.copy()
-            oout, osteps = O.rollout_batch(ob, od, r, op, max_steps=1000, threads=8)
-            assert (g["steps"] == osteps).all() and (g["results"] == oout).all() and (g["battles"] == ob).all() and (g["prng"] == op).all()
-        with pytest.raises(RuntimeError, match="engine must be 1"):
-            gpu_ctx.set_rollout_engine(3)
-    finally:
-        gpu_ctx.set_rollout_engine(2)
+            oout, osteps = O.rollout_batch(ob, od, r, op, max_steps=max_steps, prep=prep, threads=8)
+            assert (got["steps"] == osteps).all() and (got["results"] == oout).all(), (n, prep)
+            bad = np.nonzero((got["battles"] != ob).any(axis=1))[0]
+            assert bad.size == 0, (n, prep, int(bad[0]))
+            assert (got["durations"] == od).all() and (got["prng"] == op).all()
+    batches = [O.make_random_ou_batch(n, seed0=0xB1A60000 + 1000 * k) for k, n in enumerate((1200, 77, 2500))]
+    got = gpu_ctx.rollout_group([(b, d, r, p) for b, d, p, r in batches], return_state=True)
+    for (b, d, p, r), g in zip(batches, got):
+        ob, od, op = b.copy(), d.copy(), p.copy()
+        oout, osteps = O.rollout_batch(ob, od, r, op, max_steps=1000, threads=8)
+        assert (g["steps"] == osteps).all() and (g["results"] == oout).all() and (g["battles"] == ob).all() and (g["prng"] == op).all()
 
 
 def test_group_launch_limits(gpu_ctx):

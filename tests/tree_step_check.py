@@ -1,7 +1,7 @@
 """One search level at a time through oakgpu_tree_step_dev against the oracle: every battle byte, durations, result, the 16-byte
 chance-action key and both players' legal choices, over random walks with finished lanes (0xFF) and all five damage-roll clamps.
-Run in-process by tests/test_gpu_parity.py (the default kernel: the register-resident engine, staged) and as a script in a child
-process with OAKGPU_TREE_STEP=lds (the LDS-resident engine's kernel) -- the switch is read once per process.
+Run in-process by tests/test_gpu_parity.py, with 16-byte aligned battles and with battles `offset` bytes into their allocation
+(the kernel's dword staging), and as a script.
 usage: python tests/tree_step_check.py [n] [levels]   (exit code 0 = every byte equal)"""
 import ctypes as C
 import os
@@ -20,12 +20,12 @@ def roll_byte(rolls, seed):   # mcts.h:569-604
     return 236 if rolls == 1 else 217 + (38 // (rolls - 1)) * (seed % rolls)
 
 
-def run(ctx, n=1500, levels=40, seed0=0x7EE50000):
+def run(ctx, n=1500, levels=40, seed0=0x7EE50000, offset=0):
     lib, h = ctx.lib, ctx.handle
     b, d, p, r = O.make_random_ou_batch(n, seed0=seed0)
     opts = [O.Options(d[i]) for i in range(n)]
     rng = np.random.default_rng(17)
-    db, dd, dr = Dev(b), Dev(d), Dev(r)
+    db, dd, dr = Dev(b, offset=offset), Dev(d), Dev(r)
     dc1, dc2 = Dev(np.zeros(n, np.uint8)), Dev(np.zeros(n, np.uint8))
     dact = Dev(np.zeros((n, 16), np.uint8))
     dch1, dch2 = Dev(np.zeros((n, 9), np.uint8)), Dev(np.zeros((n, 9), np.uint8))
@@ -81,4 +81,4 @@ if __name__ == "__main__":
     from oak_amd.engine import Context
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 1500
     levels = int(sys.argv[2]) if len(sys.argv) > 2 else 40
-    print("tree step levels checked against the oracle:", run(Context(0), n, levels), "lane-levels, kernel:", os.environ.get("OAKGPU_TREE_STEP", "staged"))
+    print("tree step levels checked against the oracle:", run(Context(0), n, levels), "lane-levels")

@@ -1,6 +1,6 @@
 """Manual GPU tool: large randomized GPU-vs-oracle parity soak (bit-exact final states) beyond the test suite's sizes.
-usage: parity_soak.py [batches] [playouts per batch] [engine].  Batches alternate between single launches and group
-launches of four (oakgpu_rollout_group), with and without root prep; engine 2 (register-resident, default) or 1 (LDS-resident).
+usage: parity_soak.py [batches] [playouts per batch].  Batches alternate between single launches and group
+launches of four (oakgpu_rollout_group), with and without root prep.
 Uses the CPU oracle as the checker, like the tests do."""
 import sys
 import time
@@ -15,8 +15,6 @@ from oak_amd.engine import Context  # noqa: E402
 batches = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 262144
 ctx = Context(0)
-if len(sys.argv) > 3:
-    ctx.set_rollout_engine(int(sys.argv[3]))
 bad = 0
 total_steps = 0
 t0 = time.time()
