@@ -770,6 +770,50 @@ int oakgpu_selfplay_games(oakgpu_ctx *const *ctxs, oakgpu_net *net, const uint8_
                           uint32_t n, int threads_per_game, uint8_t *buffers, size_t capacity_each, size_t *written, uint32_t *n_frames,
                           uint8_t *results);
 
+/* ---- self-play over the forest search: a batch of n games resident on one device, `.battle.data` out (forestplay.hip).
+ * Per turn: one oakgpu_forest_search_dev over the live games, one pick kernel, oakgpu_update_dev, retire + compact; at the end a pack
+ * kernel writes the finished CompressedFrames records as one contiguous byte stream, in game order.
+ *   Semantics.  Game g is oakgpu_selfplay_game(teams + 60 g, battle_seeds[g], {params with seed = seeds[g], search.batch = 1, keep_node
+ *   = 0}): oakgpu_init_battles_dev with the opening update (the record's stored battle); rng = seeds[g] ^ 0x9FB21C651E98DF25; while the
+ *   result is not terminal: search seed = splitmix64(rng), tree g of the forest search, process_output in double, get_policy for both
+ *   sides, i = sample_pdf(pol1), j = sample_pdf(pol2), the frame's update, oakgpu_update_dev with (c1, c2).  One text states the rule on
+ *   both sides (oak_amd/csrc/selfplay_pick.hpp); a UCB game's record equals the host loop's byte for byte, a PUCB game (device expf priors)
+ *   and any game with policy_temp != 1 (device pow) are held to the forest search's own outputs.  params->search.seed, search.batch and
+ *   keep_node are ignored / must be 0.
+ *   Game length.  A game that already holds max_battle_length frames (0 = 2,048) when another is due is dropped: status
+ *   OAKGPU_FSP_MAX_LENGTH, zero bytes in the stream, stored result unspecified; the call still returns 0.  A policy the minimum cut zeroes
+ *   entirely stops that game alone with OAKGPU_FSP_ZERO_POLICY and no record.
+ *   solve_nash = 1: the integer payoffs are formed on the device, solved on up to 16 host threads (oakgpu_solve_matrix's solver) and go
+ *   back up before the pick -- what oakgpu_forest_search(solve_nash = 1) computes.  0: the nash fields are stored as 0.
+ *   Refused before any launch (oakgpu_forest_selfplay_check; teams: host bytes, nullable = not checked): keep_node, an unknown mode
+ *   letter or 'b' or more than 8 words, policy_min > 1, an 'n' word without solve_nash, a team pair that fails
+ *   oakgpu_endless_battle_check (the lowest such game is named), and everything oakgpu_forest_check refuses.
+ *   Independence.  Game g's record, frame count, result and status depend on its own inputs and the parameters only.
+ * _dev takes device teams (n x 60), battle_seeds and seeds (n x u64) and returns with the games complete and the stream resident in
+ * the forest's workspace; _records copies the last call's stream (stream nullable: *bytes alone is the size query), offsets[n + 1],
+ * n_frames[n], results[n] and status[n] out -- to device memory with to_device != 0; every output nullable; the forest-less form takes host
+ * arrays.  _last_stats: turns looped, rows searched summed over turns, compactions, host reads of the live count.
+ * oakgpu_selfplay_pick_host (no GPU involved) is the pick rule alone on one root output: process_output's empirical fields, both
+ * policies, i, j, the advanced rng and the encoded update bytes (update: 83 bytes, nullable; nash / prior / choice arrays nullable = 0 /
+ * the index itself). */
+#define OAKGPU_FSP_OK 0
+#define OAKGPU_FSP_MAX_LENGTH 1
+#define OAKGPU_FSP_ZERO_POLICY 2
+int oakgpu_forest_selfplay_check(uint32_t max_trees, uint32_t max_iterations, int contextual, const oakgpu_selfplay_params *params, int has_net,
+                                 uint32_t n, const uint8_t *teams, int solve_nash);
+int oakgpu_forest_selfplay_dev(oakgpu_forest *forest, oakgpu_net *net, const oakgpu_selfplay_params *params, const uint8_t *teams,
+                               const uint64_t *battle_seeds, const uint64_t *seeds, uint32_t n, int solve_nash);
+int oakgpu_forest_selfplay_records(oakgpu_forest *forest, uint8_t *stream, size_t capacity, size_t *bytes, uint64_t *offsets, uint32_t *n_frames,
+                                   uint8_t *results, uint8_t *status, int to_device);
+int oakgpu_forest_selfplay(oakgpu_forest *forest, oakgpu_net *net, const oakgpu_selfplay_params *params, const uint8_t *teams,
+                           const uint64_t *battle_seeds, const uint64_t *seeds, uint32_t n, int solve_nash);
+int oakgpu_forest_selfplay_last_stats(const oakgpu_forest *forest, uint64_t out[4]);
+int oakgpu_selfplay_pick_host(uint32_t m, uint32_t n, const uint64_t *visit_matrix, const double *value_matrix, uint64_t iterations,
+                              const double *p1_nash, const double *p2_nash, double nash_value, const double *p1_prior, const double *p2_prior,
+                              const uint8_t *p1_choices, const uint8_t *p2_choices, const char *policy_mode, double policy_temp,
+                              double policy_min, uint64_t *rng, double *empirical_value, double *p1_empirical, double *p2_empirical,
+                              double *p1_policy, double *p2_policy, int32_t *i_out, int32_t *j_out, uint8_t *update, uint32_t *update_len);
+
 /* ---- batched PKMN::battle(p1, p2, seed) (pkmn.h:50-57, init.h:90-154), level 100 sets.
  * teams: n x 60 bytes; seeds: n x u64; with first_update != 0 also performs the opening
  * update(battle, 0, 0) (benchmark.cc:29) and writes its result byte. */

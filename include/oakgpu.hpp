@@ -8,6 +8,7 @@
 //   OakGPU::BatchedMonteCarlo  <- MCTS::MonteCarlo (mcts.h:21-23) + init_stats_and_rollout (mcts.h:448-496), batched
 //   OakGPU::TreeSearch         <- MCTS::Search::run (mcts.h:154-247): Node heap + the five joint bandits, leaves batched on the GPU
 //   OakGPU::SearchForest       <- MCTS::Search::run for many positions at once: one GPU lane per tree, the trees resident on the device
+//   OakGPU::ForestSelfplay     <- the per-game loop of generate.cc:238-322 for a batch of games at once over the forest search, `.battle.data` out
 //   OakGPU::run                <- RuntimeSearch::run (util/search.h:66, search.cc:150-313): the Agent's strings pick everything
 //   OakGPU::solve_matrix       <- LRSNash::solve_fast as called at mcts.h:643-649 / pyoak.cc:394-426 (exact)
 //   OakGPU::SharedDeviceRollout<- benchmark.cc:23-31: n playouts from one root driven by ONE sequential std::mt19937
@@ -347,6 +348,41 @@ public:
 private:
   Context &ctx_;
   oakgpu_forest *f_{};
+};
+
+// Self-play over the forest search (include/oakgpu.h: oakgpu_forest_selfplay*): n games at once, resident on the device; game g is the
+// per-game loop of generate.cc:238-322 with batch = 1 and seed = seeds[g].  The records come back as one `.battle.data` byte stream in game
+// order (a dropped game -- status OAKGPU_FSP_MAX_LENGTH / _ZERO_POLICY -- has zero bytes), with offsets[n + 1] into it.
+class ForestSelfplay {
+public:
+  struct Result {
+    std::vector<uint8_t> stream;
+    std::vector<uint64_t> offsets;
+    std::vector<uint32_t> n_frames;
+    std::vector<uint8_t> results, status;
+    std::array<uint64_t, 4> stats{}; // turns looped, rows searched summed over turns, compactions, host reads
+  };
+  explicit ForestSelfplay(SearchForest &forest) : forest_{forest} {}
+  // teams: n x 60 bytes; params.search.seed / batch and params.seed are ignored, keep_node must be 0
+  Result play(const oakgpu_selfplay_params &params, const std::vector<uint8_t> &teams, const std::vector<uint64_t> &battle_seeds,
+              const std::vector<uint64_t> &seeds, Network *net = nullptr, bool solve_nash = true) {
+    const uint32_t n = (uint32_t)seeds.size();
+    if (teams.size() != (size_t)n * 60 || battle_seeds.size() != n) throw std::runtime_error{"oakgpu: ForestSelfplay::play: teams n x 60, one battle seed and one seed per game"};
+    check(oakgpu_forest_selfplay(forest_.get(), net ? net->get() : nullptr, &params, teams.data(), battle_seeds.data(), seeds.data(), n, solve_nash ? 1 : 0));
+    Result out;
+    size_t bytes = 0;
+    check(oakgpu_forest_selfplay_records(forest_.get(), nullptr, 0, &bytes, nullptr, nullptr, nullptr, nullptr, 0));
+    out.stream.resize(bytes);
+    out.offsets.assign((size_t)n + 1, 0); out.n_frames.assign(n, 0); out.results.assign(n, 0); out.status.assign(n, 0);
+    uint8_t none = 0;
+    check(oakgpu_forest_selfplay_records(forest_.get(), bytes ? out.stream.data() : &none, bytes, &bytes, out.offsets.data(), out.n_frames.data(),
+                                         out.results.data(), out.status.data(), 0));
+    check(oakgpu_forest_selfplay_last_stats(forest_.get(), out.stats.data()));
+    return out;
+  }
+
+private:
+  SearchForest &forest_;
 };
 
 // Exact Nash equilibrium of an integer m x n (<= 9 x 9) matrix game, row player maximising: {p1, p2, value / discretize}.

@@ -33,6 +33,8 @@ SYMBOLS = [
     "oakgpu_policy_games_dev", "oakgpu_policy_games", "oakgpu_policy_games_last_stats",
     "oakgpu_forest_create", "oakgpu_forest_destroy", "oakgpu_forest_check", "oakgpu_forest_search_dev", "oakgpu_forest_search", "oakgpu_forest_nodes",
     "oakgpu_forest_last_stats", "oakgpu_search_stream", "oakgpu_agent_params",
+    "oakgpu_forest_selfplay_check", "oakgpu_forest_selfplay_dev", "oakgpu_forest_selfplay_records", "oakgpu_forest_selfplay", "oakgpu_forest_selfplay_last_stats",
+    "oakgpu_selfplay_pick_host",
 ]
 
 
@@ -308,6 +310,13 @@ def load():
     lib.oakgpu_forest_last_stats.argtypes = [vp, C.POINTER(u64 * 4)]
     lib.oakgpu_search_stream.argtypes = [vp, C.POINTER(u64)]
     lib.oakgpu_agent_params.argtypes = [vp, C.POINTER(Agent), u32, u64, C.POINTER(SearchParams), C.POINTER(vp)]
+    lib.oakgpu_forest_selfplay_check.argtypes = [u32, u32, i32, C.POINTER(SelfplayParams), i32, u32, vp, i32]
+    lib.oakgpu_forest_selfplay_dev.argtypes = [vp, vp, C.POINTER(SelfplayParams), vp, vp, vp, u32, i32]
+    lib.oakgpu_forest_selfplay_records.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, vp, vp, i32]
+    lib.oakgpu_forest_selfplay.argtypes = [vp, vp, C.POINTER(SelfplayParams), vp, vp, vp, u32, i32]
+    lib.oakgpu_forest_selfplay_last_stats.argtypes = [vp, C.POINTER(u64 * 4)]
+    lib.oakgpu_selfplay_pick_host.argtypes = [u32, u32, vp, vp, u64, vp, vp, C.c_double, vp, vp, vp, vp, C.c_char_p, C.c_double, C.c_double, C.POINTER(u64),
+                                              C.POINTER(C.c_double), vp, vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.POINTER(u32)]
     _lib = lib
     return lib
 

@@ -35,6 +35,7 @@
 #include "oakgpu_internal.h"
 #include "bandit.hpp"
 #include "nash.hpp"
+#include "selfplay_pick.hpp"
 
 namespace {
 using namespace oak_search;
@@ -297,12 +298,17 @@ struct oakgpu_forest {
   uint8_t *stage = nullptr, *trace_stage = nullptr;
   size_t trace_stage_bytes = 0;
   uint64_t stats[4] = {0, 0, 0, 0};
+  // the game loop's workspace (forestplay.hip), freed with the forest
+  void *attachment = nullptr;
+  void (*attachment_free)(void *) = nullptr;
   template <class T> int get(T *&p, size_t count) {
     RC(dev_alloc(p, count));
     dev.push_back(p);
     return 0;
   }
   void release() {
+    if (attachment && attachment_free) attachment_free(attachment);
+    attachment = nullptr;
     for (void *p : dev) (void)hipFree(p);
     dev.clear();
     if (path_node) (void)hipFree(path_node);
@@ -331,6 +337,13 @@ void carve_outputs(uint8_t *p, size_t n, oakgpu_forest_outputs *o) {
 }
 size_t outputs_bytes(size_t n) { return OUT_BYTES * n + 16 * 16; }
 } // namespace
+
+oakgpu_ctx *oakgpu_forest_ctx(const oakgpu_forest *f) { return f->ctx; }
+void oakgpu_forest_limits(const oakgpu_forest *f, uint32_t *max_trees, uint32_t *max_iterations, int *contextual) {
+  *max_trees = f->max_trees; *max_iterations = f->max_iterations; *contextual = f->contextual ? 1 : 0;
+}
+void *oakgpu_forest_attachment(const oakgpu_forest *f) { return f->attachment; }
+void oakgpu_forest_set_attachment(oakgpu_forest *f, void *p, void (*dtor)(void *)) { f->attachment = p; f->attachment_free = dtor; }
 
 extern "C" {
 
@@ -557,21 +570,9 @@ int oakgpu_forest_search(oakgpu_forest *f, oakgpu_net *net, const oakgpu_search_
     memcpy(x.p1_prior, ho.p1_prior + (size_t)g * 9, 72); memcpy(x.p2_prior, ho.p2_prior + (size_t)g * 9, 72);
     x.duration_us = us;
     if (streams_out) streams_out[g] = ho.stream[g];
-    // MCTS::Search::process_output (mcts.h:620-659), as oakgpu_search runs it
-    double tv = 0;
+    // MCTS::Search::process_output (mcts.h:620-659), as oakgpu_search runs it (selfplay_pick.hpp, shared with the device game loop)
     int32_t M[81];
-    for (int i = 0; i < m; ++i)
-      for (int j = 0; j < nn; ++j) {
-        tv += x.value_matrix[i * 9 + j];
-        uint64_t v = x.visit_matrix[i * 9 + j];
-        x.p1_empirical[i] += (double)v;
-        x.p2_empirical[j] += (double)v;
-        v += !v;
-        M[i * nn + j] = (int32_t)(x.value_matrix[i * 9 + j] / (double)v * 256.0);
-      }
-    x.empirical_value = tv / (double)x.iterations;
-    for (int i = 0; i < m; ++i) x.p1_empirical[i] /= (double)(float)x.iterations;
-    for (int j = 0; j < nn; ++j) x.p2_empirical[j] /= (double)(float)x.iterations;
+    oak_pick::process_output(x.visit_matrix, x.value_matrix, m, nn, x.iterations, &x.empirical_value, x.p1_empirical, x.p2_empirical, M);
     double nv = 0;
     if (solve_nash && oak_nash::solve(M, m, nn, x.p1_nash, x.p2_nash, &nv)) x.nash_value = nv / 256.0;
   }

@@ -1,0 +1,642 @@
+// oak_amd/csrc/forestplay.hip -- self-play over the forest search: a batch of games resident on one device, `.battle.data` out (the
+// contract is in include/oakgpu.h; the per-game form is selfplay.hip's oakgpu_selfplay_game, generate.cc:238-322).
+//
+//   k_fsp_start    : row g is game g at frame 0: its stream, its counters
+//   k_fsp_retire   : one lane per row: a finished, dropped or stopped row scatters result, frame count, status and record length by game
+//                    index; how many rows of each block are still live
+//   k_fsp_offsets  : one workgroup: the exclusive prefix sums of those per-block counts, and their total = the live count the host reads
+//   k_fsp_compact  : the live rows, in order, into the other half of the double buffer -- and the turn prelude: the row's stream advances,
+//                    its first draw is the seed of the row's tree
+//   k_fsp_payoffs  : (solve_nash) the integer payoffs of process_output's exact Nash solve, for the host threads that solve them
+//   k_fsp_pick     : one lane per live row: selfplay_pick.hpp's rule over the m x n live cells of the root matrices, the joint choice for the
+//                    update, one fixed-size entry of the turn-major log
+//   k_fsp_lengths  : one workgroup: the exclusive scan of the record lengths in game order = the record bases
+//   k_fsp_pack_head: one wave per game: length, frame count, first battle, result byte
+//   k_fsp_pack_log : 16 lanes per log entry: the update's bytes to base[game] + 391 + cursor
+// Every kernel is a plain grid over rows, games or entries (the two scans: one workgroup); none waits for another block.  Between
+// compact and pick runs oakgpu_forest_search_dev over exactly the live rows (the forest refuses terminal roots), after pick
+// oakgpu_update_dev.  The pattern of retire / offsets / compact is policyplay.hip's, with this loop's own row.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/oakgpu.h"
+#include "oakgpu_internal.h"
+#include "nash.hpp"
+#include "selfplay_pick.hpp"
+
+namespace oak {
+namespace fsp {
+
+constexpr uint32_t DEAD = 0xFFFFFFFFu; // game index of a retired row
+constexpr uint32_t NO_ROW = 0xFFFFFFFFu;
+constexpr int BLOCK = 256;
+constexpr uint32_t HEAD_BYTES = 4 + 2 + 384 + 1; // a record in front of its updates
+constexpr uint32_t PAY_STRIDE = 82;              // 81 payoffs + (m | n << 8)
+
+// one entry of the turn-major log: which game, where in its record, how long, the encoded update
+struct LogEntry { uint32_t game, cursor, length; uint8_t bytes[84]; };
+static_assert(sizeof(LogEntry) == 96 && oak_pick::MAX_UPDATE_BYTES <= 84, "one log entry is 96 bytes");
+
+// one half of the double buffer: a row is its battle, durations, result byte, the joint choice between pick and the update, the stop flag
+// (OAKGPU_FSP_ZERO_POLICY), its game index, the game's stream, its frame count and the byte cursor within its record's updates
+struct Rows {
+  uint8_t *battles, *durations, *results, *c1, *c2, *flag;
+  uint32_t *game, *frames, *cursor;
+  uint64_t *rng;
+};
+
+__global__ __launch_bounds__(BLOCK) void k_fsp_start(Rows r, const uint64_t *seeds, uint32_t n) {
+  const uint32_t row = blockIdx.x * BLOCK + threadIdx.x;
+  if (row >= n) return;
+  r.game[row] = row;
+  r.frames[row] = 0;
+  r.cursor[row] = 0;
+  r.flag[row] = 0;
+  r.rng[row] = seeds[row] ^ oak_pick::GAME_STREAM_XOR;
+}
+
+struct RetireArgs {
+  Rows r;
+  uint8_t *results_out, *status_out; // by game index
+  uint32_t *frames_out, *length_out;
+  uint32_t *block_live;              // per block of BLOCK rows: rows still live after this pass
+  uint32_t rows, max_len;
+};
+
+__global__ __launch_bounds__(BLOCK) void k_fsp_retire(RetireArgs a) {
+  __shared__ uint32_t wave_live[BLOCK / 64];
+  const uint32_t tid = threadIdx.x, row = blockIdx.x * BLOCK + tid, lane = tid & 63;
+  const bool in = row < a.rows;
+  const uint32_t g = in ? a.r.game[row] : DEAD;
+  bool live = false;
+  if (g != DEAD) {
+    const uint32_t res = a.r.results[row], frames = a.r.frames[row];
+    // the host loop's order: a policy that was zeroed ends the game where it stood; a terminal result ends it; only then is another frame due
+    const uint32_t status = a.r.flag[row] ? (uint32_t)OAKGPU_FSP_ZERO_POLICY : (res & 15) != 0 ? (uint32_t)OAKGPU_FSP_OK : frames >= a.max_len ? (uint32_t)OAKGPU_FSP_MAX_LENGTH : DEAD;
+    if (status == DEAD) live = true;
+    else {
+      a.results_out[g] = (uint8_t)res;
+      a.frames_out[g] = frames;
+      a.status_out[g] = (uint8_t)status;
+      a.length_out[g] = status == OAKGPU_FSP_OK ? HEAD_BYTES + a.r.cursor[row] : 0u;
+      a.r.game[row] = DEAD;
+    }
+  }
+  const unsigned long long ml = __ballot(live);
+  if (lane == 0) wave_live[tid >> 6] = (uint32_t)__popcll(ml);
+  __syncthreads();
+  if (tid == 0) a.block_live[blockIdx.x] = wave_live[0] + wave_live[1] + wave_live[2] + wave_live[3];
+}
+
+// exclusive prefix sums of `count` dwords, 1,024 at a time (a wave scans its 64 by shuffles, the 16 wave totals are scanned by every lane);
+// out_total (nullable) receives the sum.  policyplay.hip's k_games_offsets with a total.
+__global__ __launch_bounds__(1024) void k_fsp_offsets(const uint32_t *in, uint32_t count, uint32_t *out, uint32_t *out_total) {
+  __shared__ uint32_t wave_total[16];
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  uint32_t carry = 0;
+  for (uint32_t base = 0; base < count; base += 1024) {
+    const uint32_t i = base + tid, own = i < count ? in[i] : 0;
+    uint32_t incl = own;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t up = __shfl_up(incl, d);
+      if ((int)lane >= d) incl += up;
+    }
+    if (lane == 63) wave_total[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < 16; ++w) { const uint32_t t = wave_total[w]; if (w < wave) before += t; all += t; }
+    if (i < count) out[i] = carry + before + incl - own;
+    carry += all;
+    __syncthreads();
+  }
+  if (tid == 0 && out_total) *out_total = carry;
+}
+
+// the same scan in 64 bits, over the record lengths in game order: offsets[g] = where game g's record starts, offsets[n] = the stream's size
+__global__ __launch_bounds__(1024) void k_fsp_lengths(const uint32_t *length, uint32_t n, unsigned long long *offsets) {
+  __shared__ unsigned long long wave_total[16];
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned long long carry = 0;
+  for (uint32_t base = 0; base < n; base += 1024) {
+    const uint32_t i = base + tid;
+    const unsigned long long own = i < n ? length[i] : 0;
+    unsigned long long incl = own;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned long long up = __shfl_up(incl, d);
+      if ((int)lane >= d) incl += up;
+    }
+    if (lane == 63) wave_total[wave] = incl;
+    __syncthreads();
+    unsigned long long before = 0, all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < 16; ++w) { const unsigned long long t = wave_total[w]; if (w < wave) before += t; all += t; }
+    if (i < n) offsets[i] = carry + before + incl - own;
+    carry += all;
+    __syncthreads();
+  }
+  if (tid == 0) offsets[n] = carry;
+}
+
+struct CompactArgs {
+  Rows from, to;
+  const uint32_t *block_offset;
+  uint64_t *tree_seed; // per compacted row: the seed of this turn's tree
+  uint32_t rows;
+};
+
+// Stable: a live row's place is its block's offset + the live rows in front of it in the block.  The 384-byte battles move as whole rows, 24
+// lanes x 16 bytes each, as policyplay.hip's k_games_compact moves them.  The turn prelude rides along: search seed = splitmix64(rng).
+__global__ __launch_bounds__(BLOCK) void k_fsp_compact(CompactArgs a) {
+  __shared__ uint32_t wave_total[BLOCK / 64];
+  __shared__ uint32_t place[BLOCK];
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const uint32_t tid = threadIdx.x, base = blockIdx.x * BLOCK, row = base + tid, lane = tid & 63, wave = tid >> 6;
+  const bool live = row < a.rows && a.from.game[row] != DEAD;
+  const unsigned long long m = __ballot(live);
+  const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+  if (lane == 0) wave_total[wave] = (uint32_t)__popcll(m);
+  __syncthreads();
+  uint32_t before = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < BLOCK / 64; ++w) if (w < wave) before += wave_total[w];
+  const uint32_t to = live ? a.block_offset[blockIdx.x] + before + prefix : NO_ROW;
+  place[tid] = to;
+  if (live) {
+    *((uint2 *)a.to.durations + to) = *((const uint2 *)a.from.durations + row);
+    a.to.results[to] = a.from.results[row];
+    a.to.flag[to] = 0;
+    a.to.game[to] = a.from.game[row];
+    a.to.frames[to] = a.from.frames[row];
+    a.to.cursor[to] = a.from.cursor[row];
+    uint64_t rng = a.from.rng[row];
+    a.tree_seed[to] = oak_pick::splitmix64(rng);
+    a.to.rng[to] = rng;
+  }
+  __syncthreads();
+  const u32x4 *src = (const u32x4 *)a.from.battles + (size_t)base * 24;
+  u32x4 *dst = (u32x4 *)a.to.battles;
+  const uint32_t in_block = a.rows - base < (uint32_t)BLOCK ? a.rows - base : (uint32_t)BLOCK;
+#pragma unroll 4
+  for (int q = 0; q < 24; ++q) {
+    const uint32_t i = q * BLOCK + tid, b = i / 24, w = i - b * 24;
+    if (b >= in_block) continue; // (rows past the end are not read)
+    const uint32_t t = place[b];
+    if (t != NO_ROW) dst[(size_t)t * 24 + w] = src[i];
+  }
+}
+
+struct PayoffArgs {
+  const uint8_t *m, *n;
+  const uint64_t *visit_matrix;
+  const double *value_matrix;
+  int32_t *pay; // rows x PAY_STRIDE
+  uint32_t rows;
+};
+
+__global__ __launch_bounds__(BLOCK) void k_fsp_payoffs(PayoffArgs a) {
+#pragma clang fp contract(off)
+  const uint32_t row = blockIdx.x * BLOCK + threadIdx.x;
+  if (row >= a.rows) return;
+  const uint32_t m = a.m[row], n = a.n[row];
+  const uint64_t *vis = a.visit_matrix + (size_t)row * 81;
+  const double *val = a.value_matrix + (size_t)row * 81;
+  int32_t *M = a.pay + (size_t)row * PAY_STRIDE;
+  for (uint32_t i = 0; i < m; ++i)
+    for (uint32_t j = 0; j < n; ++j) {
+      uint64_t v = vis[i * 9 + j];
+      v += !v;
+      M[i * n + j] = (int32_t)(val[i * 9 + j] / (double)v * 256.0);
+    }
+  M[81] = (int32_t)(m | n << 8);
+}
+
+struct PickArgs {
+  Rows r;
+  oakgpu_forest_outputs out;                 // the search's outputs, row-major over the live rows
+  const double *p1_nash, *p2_nash, *nash_value; // rows x 9, rows x 9, rows; null without solve_nash
+  LogEntry *log;                             // this turn's entries, one per row
+  oak_pick::PolicyMode mode;
+  double temp, minp;
+  uint32_t rows;
+};
+
+__global__ __launch_bounds__(BLOCK) void k_fsp_pick(PickArgs a) {
+  const uint32_t row = blockIdx.x * BLOCK + threadIdx.x;
+  if (row >= a.rows) return;
+  const int m = a.out.m[row], n = a.out.n[row];
+  double ev, e1[9], e2[9], n1[9], n2[9], r1[9], r2[9], pol1[9], pol2[9], nv = 0.0;
+  const uint64_t iterations = a.out.iterations[row];
+  oak_pick::process_output(a.out.visit_matrix + (size_t)row * 81, a.out.value_matrix + (size_t)row * 81, m, n, iterations, &ev, e1, e2, nullptr);
+  for (int q = 0; q < 9; ++q) {
+    n1[q] = a.p1_nash && q < m ? a.p1_nash[(size_t)row * 9 + q] : 0.0;
+    n2[q] = a.p2_nash && q < n ? a.p2_nash[(size_t)row * 9 + q] : 0.0;
+    r1[q] = q < m ? a.out.p1_prior[(size_t)row * 9 + q] : 0.0;
+    r2[q] = q < n ? a.out.p2_prior[(size_t)row * 9 + q] : 0.0;
+  }
+  if (a.nash_value) nv = a.nash_value[row];
+  LogEntry *entry = a.log + row;
+  entry->game = a.r.game[row];
+  entry->cursor = a.r.cursor[row];
+  uint8_t c1 = a.out.p1_choices[(size_t)row * 9], c2 = a.out.p2_choices[(size_t)row * 9];
+  uint32_t len = 0;
+  if (!oak_pick::get_policy(r1, e1, n1, m, a.mode, a.temp, a.minp, pol1) || !oak_pick::get_policy(r2, e2, n2, n, a.mode, a.temp, a.minp, pol2)) {
+    a.r.flag[row] = (uint8_t)OAKGPU_FSP_ZERO_POLICY; // the game stops here: its row takes a legal step and is retired with no record
+  } else {
+    uint64_t rng = a.r.rng[row];
+    const int i = oak_pick::sample_pdf(pol1, m, rng), j = oak_pick::sample_pdf(pol2, n, rng);
+    a.r.rng[row] = rng;
+    c1 = a.out.p1_choices[(size_t)row * 9 + i];
+    c2 = a.out.p2_choices[(size_t)row * 9 + j];
+    len = oak_pick::encode_update(entry->bytes, (uint32_t)m, (uint32_t)n, c1, c2, (uint32_t)iterations, ev, nv, e1, n1, e2, n2);
+    a.r.frames[row] += 1;
+    a.r.cursor[row] += len;
+  }
+  entry->length = len;
+  a.r.c1[row] = c1;
+  a.r.c2[row] = c2;
+}
+
+struct PackArgs {
+  const unsigned long long *offsets;
+  const uint32_t *frames, *length;
+  const uint8_t *results, *status, *first; // first: n x 384, the battles after the opening update
+  const LogEntry *log;
+  uint8_t *stream;
+  uint32_t n, entries;
+};
+
+// the fixed part of every kept record: u32 byte length, u16 frame count, the 384-byte battle, the result byte.  One wave per game; the
+// record starts at any byte, so the bytes go out one by one.
+__global__ __launch_bounds__(BLOCK) void k_fsp_pack_head(PackArgs a) {
+  const uint32_t g = blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (g >= a.n || a.status[g] != OAKGPU_FSP_OK) return;
+  uint8_t *dst = a.stream + a.offsets[g];
+  const uint32_t total = a.length[g], frames = a.frames[g];
+  const uint8_t *battle = a.first + (size_t)g * 384;
+  for (uint32_t i = lane; i < HEAD_BYTES; i += 64) {
+    uint8_t v;
+    if (i < 4) v = (uint8_t)(total >> (8 * i));
+    else if (i < 6) v = (uint8_t)(frames >> (8 * (i - 4)));
+    else if (i < 6 + 384) v = battle[i - 6];
+    else v = a.results[g];
+    dst[i] = v;
+  }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_fsp_pack_log(PackArgs a) {
+  const uint32_t e = blockIdx.x * (BLOCK / 16) + (threadIdx.x >> 4), lane = threadIdx.x & 15;
+  if (e >= a.entries) return;
+  const LogEntry &entry = a.log[e];
+  const uint32_t g = entry.game, len = entry.length;
+  if (g >= a.n || len == 0 || len > oak_pick::MAX_UPDATE_BYTES || a.status[g] != OAKGPU_FSP_OK) return; // (a dropped game's entries stay behind)
+  const uint32_t at = HEAD_BYTES + entry.cursor;
+  if (at + len > a.length[g]) return;
+  uint8_t *dst = a.stream + a.offsets[g] + at;
+  for (uint32_t i = lane; i < len; i += 16) dst[i] = entry.bytes[i];
+}
+
+} // namespace fsp
+} // namespace oak
+
+// ---- host ------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+using namespace oak::fsp;
+
+#define RC(x) do { int _r = (x); if (_r) return _r; } while (0)
+
+// the loop's workspace, attached to the forest and freed with it: everything sized by the batch is grow-only, the log grows by doubling
+// between turns, the stream is sized by the records
+struct Workspace {
+  std::vector<void *> dev;
+  uint32_t capacity = 0; // rows
+  Rows half[2] = {};
+  uint64_t *tree_seed = nullptr;
+  uint8_t *out_block = nullptr; // the search's outputs
+  int32_t *pay = nullptr;
+  double *nash = nullptr;       // rows x 9, rows x 9, rows
+  uint8_t *first = nullptr, *results_out = nullptr, *status_out = nullptr, *d_teams = nullptr;
+  uint32_t *frames_out = nullptr, *length_out = nullptr, *block_live = nullptr, *block_offset = nullptr, *ctl = nullptr;
+  uint64_t *d_seeds = nullptr; // the host-array call's staging: battle seeds, then seeds
+  unsigned long long *offsets = nullptr;
+  LogEntry *log = nullptr;
+  size_t log_capacity = 0;
+  uint8_t *stream = nullptr;
+  size_t stream_capacity = 0, stream_bytes = 0;
+  uint32_t last_n = 0;
+  bool have = false;
+  uint64_t stats[4] = {0, 0, 0, 0};
+  std::vector<int32_t> h_pay;
+  std::vector<double> h_nash;
+  void release() {
+    for (void *p : dev) (void)hipFree(p);
+    dev.clear();
+    if (log) (void)hipFree(log);
+    if (stream) (void)hipFree(stream);
+    log = nullptr; stream = nullptr; log_capacity = stream_capacity = 0; capacity = 0;
+  }
+  template <class T> int get(T *&p, size_t count) {
+    RC(dev_alloc(p, count));
+    dev.push_back(p);
+    return 0;
+  }
+};
+
+void workspace_free(void *p) {
+  Workspace *w = (Workspace *)p;
+  w->release();
+  delete w;
+}
+
+// bytes of one tree's outputs (forest.hip's staging block has the same arrays), every array 16-byte aligned for any n
+void carve_outputs(uint8_t *p, size_t n, oakgpu_forest_outputs *o) {
+  auto take = [&](size_t bytes_per) { uint8_t *q = p; p += ((bytes_per * n + 15) / 16) * 16; return q; };
+  o->visit_matrix = (uint64_t *)take(81 * 8); o->value_matrix = (double *)take(81 * 8);
+  o->iterations = (uint64_t *)take(8); o->nodes = (uint64_t *)take(8); o->total_depth = (uint64_t *)take(8);
+  o->initial_value = (double *)take(8);
+  o->p1_logit = (double *)take(72); o->p2_logit = (double *)take(72); o->p1_prior = (double *)take(72); o->p2_prior = (double *)take(72);
+  o->stream = (uint64_t *)take(8);
+  o->p1_choices = take(9); o->p2_choices = take(9); o->m = take(1); o->n = take(1);
+}
+constexpr size_t OUT_BYTES = 81 * 8 * 2 + 8 * 4 + 72 * 4 + 8 + 9 * 2 + 2;
+
+int workspace_for(oakgpu_forest *f, uint32_t n, Workspace **out) {
+  Workspace *w = (Workspace *)oakgpu_forest_attachment(f);
+  if (!w) {
+    w = new Workspace();
+    oakgpu_forest_set_attachment(f, w, workspace_free);
+  }
+  *out = w;
+  if (w->capacity >= n) return 0;
+  HIPCHK(hipStreamSynchronize((hipStream_t)oakgpu_ctx_stream(oakgpu_forest_ctx(f))));
+  for (void *p : w->dev) (void)hipFree(p);
+  w->dev.clear();
+  w->capacity = 0;
+  w->have = false;
+  const size_t T = n, blocks = (T + BLOCK - 1) / BLOCK;
+  for (int h = 0; h < 2; ++h) {
+    Rows &r = w->half[h];
+    RC(w->get(r.battles, T * 384)); RC(w->get(r.durations, T * 8)); RC(w->get(r.results, T)); RC(w->get(r.c1, T)); RC(w->get(r.c2, T)); RC(w->get(r.flag, T));
+    RC(w->get(r.game, T)); RC(w->get(r.frames, T)); RC(w->get(r.cursor, T)); RC(w->get(r.rng, T));
+  }
+  RC(w->get(w->tree_seed, T)); RC(w->get(w->out_block, OUT_BYTES * T + 16 * 16)); RC(w->get(w->pay, T * PAY_STRIDE)); RC(w->get(w->nash, T * 19));
+  RC(w->get(w->first, T * 384)); RC(w->get(w->results_out, T)); RC(w->get(w->status_out, T)); RC(w->get(w->d_teams, T * 60));
+  RC(w->get(w->frames_out, T)); RC(w->get(w->length_out, T)); RC(w->get(w->block_live, blocks)); RC(w->get(w->block_offset, blocks)); RC(w->get(w->ctl, 4));
+  RC(w->get(w->d_seeds, 2 * T)); RC(w->get(w->offsets, T + 1));
+  w->capacity = n;
+  return 0;
+}
+
+// the turn's payoffs on the host's threads, min(16, usable cores): p1 / p2 strategies and the value / 256; a matrix the solver refuses
+// keeps zeros, as oakgpu_forest_search leaves them
+void solve_rows(const int32_t *pay, uint32_t rows, double *nash) {
+  double *p1 = nash, *p2 = nash + (size_t)rows * 9, *nv = nash + (size_t)rows * 18;
+  auto work = [&](uint32_t lo, uint32_t hi) {
+    for (uint32_t r = lo; r < hi; ++r) {
+      const int32_t *M = pay + (size_t)r * PAY_STRIDE;
+      const int m = M[81] & 0xFF, n = (M[81] >> 8) & 0xFF;
+      double x[9] = {}, y[9] = {}, v = 0;
+      const bool ok = m >= 1 && m <= 9 && n >= 1 && n <= 9 && oak_nash::solve(M, m, n, x, y, &v);
+      for (int q = 0; q < 9; ++q) { p1[(size_t)r * 9 + q] = ok ? x[q] : 0.0; p2[(size_t)r * 9 + q] = ok ? y[q] : 0.0; }
+      nv[r] = ok ? v / 256.0 : 0.0;
+    }
+  };
+  const uint32_t threads = std::min<uint32_t>({16u, std::max(1u, oakgpu_usable_cores()), rows / 32 + 1});
+  if (threads <= 1) { work(0, rows); return; }
+  std::vector<std::thread> pool;
+  const uint32_t per = (rows + threads - 1) / threads;
+  for (uint32_t t = 0; t < threads; ++t) pool.emplace_back(work, std::min(rows, t * per), std::min(rows, (t + 1) * per));
+  for (auto &th : pool) th.join();
+}
+
+int fail_fmt(const char *fmt, unsigned a) {
+  char msg[256];
+  snprintf(msg, sizeof msg, fmt, a);
+  return oakgpu_fail_msg(msg);
+}
+
+} // namespace
+
+extern "C" {
+
+int oakgpu_forest_selfplay_check(uint32_t max_trees, uint32_t max_iterations, int contextual, const oakgpu_selfplay_params *prm, int has_net, uint32_t n,
+                                 const uint8_t *teams, int solve_nash) {
+  if (!prm) return oakgpu_fail_msg("oakgpu_forest_selfplay: null argument");
+  if (prm->keep_node != 0) return oakgpu_fail_msg("oakgpu_forest_selfplay: keep_node is not supported (every turn searches a fresh tree)");
+  oak_pick::PolicyMode mode;
+  const int bad = oak_pick::parse_policy_mode(prm->policy_mode, sizeof prm->policy_mode, &mode);
+  if (bad == 'b') return oakgpu_fail_msg("oakgpu_forest_selfplay: policy mode 'b' (beta) is not supported (util/policy.h:59-60 throws)");
+  if (bad > 0) return fail_fmt("oakgpu_forest_selfplay: unknown policy mode letter '%c' (words are e / n / x / p with optional weights, util/policy.h:22-98)", (unsigned)bad);
+  if (bad < 0) return oakgpu_fail_msg("oakgpu_forest_selfplay: more than 8 policy mode words");
+  if (!(prm->policy_min <= 1.0)) return oakgpu_fail_msg("oakgpu_forest_selfplay: RuntimePolicy: zero policy (policy_min above 1 zeroes every policy)");
+  if (!solve_nash)
+    for (uint32_t q = 0; q < mode.count; ++q)
+      if (mode.word[q].kind == oak_pick::W_NASH) return oakgpu_fail_msg("oakgpu_forest_selfplay: policy mode word 'n' needs solve_nash (the nash strategies are not computed)");
+  if (int rc = oakgpu_forest_check(max_trees, max_iterations, contextual, &prm->search, has_net, n, nullptr, 0, 0)) {
+    std::string msg = oakgpu_last_error();
+    const std::string from = "oakgpu_forest_search:";
+    if (msg.compare(0, from.size(), from) == 0) msg = "oakgpu_forest_selfplay: the forest search refuses:" + msg.substr(from.size());
+    oakgpu_fail_msg(msg.c_str());
+    return rc;
+  }
+  if (teams)
+    for (uint32_t g = 0; g < n; ++g)
+      if (oakgpu_endless_battle_check(teams + (size_t)g * 60))
+        return fail_fmt("oakgpu_forest_selfplay: game %u: EBC check failed (every match-up is Ghost against Ghost with no move that can hit a Ghost, generate.cc:127-152)", g);
+  return 0;
+}
+
+int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_selfplay_params *prm, const uint8_t *teams, const uint64_t *battle_seeds,
+                               const uint64_t *seeds, uint32_t n, int solve_nash) {
+  if (!f || !prm) return oakgpu_fail_msg("oakgpu_forest_selfplay: null argument");
+  uint32_t max_trees = 0, max_iterations = 0;
+  int contextual = 0;
+  oakgpu_forest_limits(f, &max_trees, &max_iterations, &contextual);
+  oakgpu_ctx *ctx = oakgpu_forest_ctx(f);
+  RC(oakgpu_ctx_enter(ctx));
+  hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(ctx);
+  if (n && (!teams || !battle_seeds || !seeds)) return oakgpu_fail_msg("oakgpu_forest_selfplay: null argument");
+  std::vector<uint8_t> h_teams((size_t)n * 60);
+  if (n) { // the endless battle check reads the teams on the host: one copy, before anything is launched
+    HIPCHK(hipMemcpyAsync(h_teams.data(), teams, h_teams.size(), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+  }
+  RC(oakgpu_forest_selfplay_check(max_trees, max_iterations, contextual, prm, net != nullptr, n, n ? h_teams.data() : nullptr, solve_nash));
+  Workspace *w = nullptr;
+  RC(workspace_for(f, std::max(n, 1u), &w));
+  w->have = false;
+  w->last_n = n;
+  w->stream_bytes = 0;
+  w->stats[0] = w->stats[1] = w->stats[2] = w->stats[3] = 0;
+  if (n == 0) { w->have = true; return 0; }
+  oak_pick::PolicyMode mode;
+  (void)oak_pick::parse_policy_mode(prm->policy_mode, sizeof prm->policy_mode, &mode);
+  const uint32_t max_len = prm->max_battle_length ? prm->max_battle_length : 2048;
+  oakgpu_search_params sp = prm->search;
+  sp.batch = 1; sp.seed = 0;
+  auto grid = [](uint32_t rows) { return dim3((rows + BLOCK - 1) / BLOCK); };
+
+  // the opening: PKMN::battle + update(0, 0); the battle after it is the record's stored one
+  int cur = 0;
+  uint32_t rows = n;
+  {
+    Rows &r = w->half[0];
+    RC(oakgpu_init_battles_dev(ctx, teams, battle_seeds, n, 1, r.battles, r.durations, r.results));
+    HIPCHK(hipMemcpyAsync(w->first, r.battles, (size_t)n * 384, hipMemcpyDeviceToDevice, stream));
+    hipLaunchKernelGGL(k_fsp_start, grid(n), dim3(BLOCK), 0, stream, r, seeds, n);
+    HIPCHK(hipGetLastError());
+  }
+  if (!w->log) {
+    const size_t want = std::max<size_t>((size_t)n * 16, 4096);
+    RC(dev_alloc(w->log, want));
+    w->log_capacity = want;
+  }
+  oakgpu_forest_outputs o;
+  size_t entries = 0;
+  for (uint64_t turn = 0;; ++turn) {
+    // retire what ended, compact the rest: the rows handed to the search are exactly the live games
+    const uint32_t blocks = (rows + BLOCK - 1) / BLOCK;
+    const RetireArgs ra{w->half[cur], w->results_out, w->status_out, w->frames_out, w->length_out, w->block_live, rows, max_len};
+    hipLaunchKernelGGL(k_fsp_retire, grid(rows), dim3(BLOCK), 0, stream, ra);
+    hipLaunchKernelGGL(k_fsp_offsets, dim3(1), dim3(1024), 0, stream, w->block_live, blocks, w->block_offset, w->ctl);
+    const CompactArgs ca{w->half[cur], w->half[cur ^ 1], w->block_offset, w->tree_seed, rows};
+    hipLaunchKernelGGL(k_fsp_compact, grid(rows), dim3(BLOCK), 0, stream, ca);
+    HIPCHK(hipGetLastError());
+    uint32_t live = 0;
+    HIPCHK(hipMemcpyAsync(&live, w->ctl, 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    ++w->stats[3];
+    ++w->stats[2];
+    cur ^= 1;
+    if (live > rows) return oakgpu_fail_msg("oakgpu_forest_selfplay: the live count grew (internal error)");
+    rows = live;
+    if (rows == 0) break;
+    if (turn > (uint64_t)max_len + 1) return oakgpu_fail_msg("oakgpu_forest_selfplay: a game outlived max_battle_length (internal error)");
+    Rows &r = w->half[cur];
+    ++w->stats[0];
+    w->stats[1] += rows;
+    if (entries + rows > w->log_capacity) { // the log follows the frames played: doubled between turns
+      const size_t want = std::max(w->log_capacity * 2, entries + rows);
+      LogEntry *bigger = nullptr;
+      RC(dev_alloc(bigger, want));
+      HIPCHK(hipMemcpyAsync(bigger, w->log, entries * sizeof(LogEntry), hipMemcpyDeviceToDevice, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      (void)hipFree(w->log);
+      w->log = bigger;
+      w->log_capacity = want;
+    }
+    carve_outputs(w->out_block, rows, &o);
+    RC(oakgpu_forest_search_dev(f, net, &sp, r.battles, r.durations, r.results, w->tree_seed, rows, &o, nullptr, 0));
+    double *d_p1 = nullptr, *d_p2 = nullptr, *d_nv = nullptr;
+    if (solve_nash) {
+      const PayoffArgs pa{o.m, o.n, o.visit_matrix, o.value_matrix, w->pay, rows};
+      hipLaunchKernelGGL(k_fsp_payoffs, grid(rows), dim3(BLOCK), 0, stream, pa);
+      HIPCHK(hipGetLastError());
+      w->h_pay.resize((size_t)rows * PAY_STRIDE);
+      w->h_nash.resize((size_t)rows * 19);
+      HIPCHK(hipMemcpyAsync(w->h_pay.data(), w->pay, w->h_pay.size() * 4, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      solve_rows(w->h_pay.data(), rows, w->h_nash.data());
+      HIPCHK(hipMemcpyAsync(w->nash, w->h_nash.data(), w->h_nash.size() * 8, hipMemcpyHostToDevice, stream));
+      d_p1 = w->nash; d_p2 = w->nash + (size_t)rows * 9; d_nv = w->nash + (size_t)rows * 18;
+    }
+    PickArgs pk{};
+    pk.r = r; pk.out = o; pk.p1_nash = d_p1; pk.p2_nash = d_p2; pk.nash_value = d_nv; pk.log = w->log + entries; pk.mode = mode;
+    pk.temp = prm->policy_temp > 0 ? prm->policy_temp : 1.0; pk.minp = prm->policy_min; pk.rows = rows;
+    hipLaunchKernelGGL(k_fsp_pick, grid(rows), dim3(BLOCK), 0, stream, pk);
+    HIPCHK(hipGetLastError());
+    entries += rows;
+    // PKMN::update(battle, c1, c2, options); durations <- options (generate.cc:319-322)
+    RC(oakgpu_update_dev(ctx, r.battles, r.c1, r.c2, r.durations, nullptr, nullptr, rows, r.results));
+    if (solve_nash) HIPCHK(hipStreamSynchronize(stream)); // (the strategies' host copy is reused next turn)
+  }
+
+  // pack: record bases in game order, the headers, the log's updates
+  hipLaunchKernelGGL(k_fsp_lengths, dim3(1), dim3(1024), 0, stream, w->length_out, n, w->offsets);
+  HIPCHK(hipGetLastError());
+  unsigned long long total = 0;
+  HIPCHK(hipMemcpyAsync(&total, w->offsets + n, 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (total > w->stream_capacity) {
+    if (w->stream) (void)hipFree(w->stream);
+    w->stream = nullptr; w->stream_capacity = 0;
+    RC(dev_alloc(w->stream, (size_t)total));
+    w->stream_capacity = (size_t)total;
+  }
+  if (total) {
+    const PackArgs pa{w->offsets, w->frames_out, w->length_out, w->results_out, w->status_out, w->first, w->log, w->stream, n, (uint32_t)entries};
+    if (entries > 0xFFFFFFFFull) return oakgpu_fail_msg("oakgpu_forest_selfplay: more than 2^32 frames in one call");
+    hipLaunchKernelGGL(k_fsp_pack_head, dim3((n + BLOCK / 64 - 1) / (BLOCK / 64)), dim3(BLOCK), 0, stream, pa);
+    if (entries) hipLaunchKernelGGL(k_fsp_pack_log, dim3((uint32_t)((entries + BLOCK / 16 - 1) / (BLOCK / 16))), dim3(BLOCK), 0, stream, pa);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamSynchronize(stream));
+  w->stream_bytes = (size_t)total;
+  w->have = true;
+  return 0;
+}
+
+int oakgpu_forest_selfplay_records(oakgpu_forest *f, uint8_t *stream_out, size_t capacity, size_t *bytes, uint64_t *offsets, uint32_t *n_frames, uint8_t *results,
+                                   uint8_t *status, int to_device) {
+  if (!f) return oakgpu_fail_msg("oakgpu_forest_selfplay_records: null argument");
+  Workspace *w = (Workspace *)oakgpu_forest_attachment(f);
+  if (!w || !w->have) return oakgpu_fail_msg("oakgpu_forest_selfplay_records: the forest holds no finished self-play call");
+  if (bytes) *bytes = w->stream_bytes;
+  if (stream_out && capacity < w->stream_bytes) return oakgpu_fail_msg("oakgpu_forest_selfplay_records: buffer too small");
+  oakgpu_ctx *ctx = oakgpu_forest_ctx(f);
+  RC(oakgpu_ctx_enter(ctx));
+  hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(ctx);
+  const hipMemcpyKind kind = to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const size_t n = w->last_n;
+  if (stream_out && w->stream_bytes) HIPCHK(hipMemcpyAsync(stream_out, w->stream, w->stream_bytes, kind, stream));
+  if (offsets) {
+    if (n) HIPCHK(hipMemcpyAsync(offsets, w->offsets, (n + 1) * 8, kind, stream));
+    else if (to_device) HIPCHK(hipMemsetAsync(offsets, 0, 8, stream));
+    else offsets[0] = 0;
+  }
+  if (n_frames && n) HIPCHK(hipMemcpyAsync(n_frames, w->frames_out, n * 4, kind, stream));
+  if (results && n) HIPCHK(hipMemcpyAsync(results, w->results_out, n, kind, stream));
+  if (status && n) HIPCHK(hipMemcpyAsync(status, w->status_out, n, kind, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  return 0;
+}
+
+int oakgpu_forest_selfplay(oakgpu_forest *f, oakgpu_net *net, const oakgpu_selfplay_params *prm, const uint8_t *teams, const uint64_t *battle_seeds,
+                           const uint64_t *seeds, uint32_t n, int solve_nash) {
+  if (!f || !prm || (n && (!teams || !battle_seeds || !seeds))) return oakgpu_fail_msg("oakgpu_forest_selfplay: null argument");
+  uint32_t max_trees = 0, max_iterations = 0;
+  int contextual = 0;
+  oakgpu_forest_limits(f, &max_trees, &max_iterations, &contextual);
+  RC(oakgpu_forest_selfplay_check(max_trees, max_iterations, contextual, prm, net != nullptr, n, teams, solve_nash));
+  oakgpu_ctx *ctx = oakgpu_forest_ctx(f);
+  RC(oakgpu_ctx_enter(ctx));
+  hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(ctx);
+  Workspace *w = nullptr;
+  RC(workspace_for(f, std::max(n, 1u), &w));
+  if (n) {
+    HIPCHK(hipMemcpyAsync(w->d_teams, teams, (size_t)n * 60, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(w->d_seeds, battle_seeds, (size_t)n * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(w->d_seeds + n, seeds, (size_t)n * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+  }
+  return oakgpu_forest_selfplay_dev(f, net, prm, w->d_teams, w->d_seeds, w->d_seeds + n, n, solve_nash);
+}
+
+int oakgpu_forest_selfplay_last_stats(const oakgpu_forest *f, uint64_t out[4]) {
+  if (!f || !out) return oakgpu_fail_msg("oakgpu_forest_selfplay_last_stats: null argument");
+  const Workspace *w = (const Workspace *)oakgpu_forest_attachment(f);
+  for (int q = 0; q < 4; ++q) out[q] = w ? w->stats[q] : 0;
+  return 0;
+}
+
+} // extern "C"

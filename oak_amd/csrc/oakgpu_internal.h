@@ -72,6 +72,13 @@ extern "C" int oakgpu_net_device(const oakgpu_net *net); // leafnet.hip: the dev
 void oakgpu_set_thread_search_threads(int threads);
 // Cores the process may really use (affinity mask capped by the cgroup CPU quota; OAKGPU_SEARCH_CORES overrides): search_host.hip.
 unsigned oakgpu_usable_cores();
+// forest.hip: what the game loop over the forest (forestplay.hip) needs of a forest -- its context, its limits, and one attachment (the
+// loop's workspace) that oakgpu_forest_destroy frees through `dtor` while the device is idle.
+struct oakgpu_forest;
+oakgpu_ctx *oakgpu_forest_ctx(const oakgpu_forest *forest);
+void oakgpu_forest_limits(const oakgpu_forest *forest, uint32_t *max_trees, uint32_t *max_iterations, int *contextual);
+void *oakgpu_forest_attachment(const oakgpu_forest *forest);
+void oakgpu_forest_set_attachment(oakgpu_forest *forest, void *p, void (*dtor)(void *));
 // A resident `.battle.data` corpus (trainframes.hip creates and frees it; corpuseval.hip evaluates it chunk by chunk)
 struct oakgpu_corpus {
   oakgpu_ctx *ctx = nullptr;

@@ -14,6 +14,8 @@
 //   read_battle_data(path) -> [(bytes, frame_count), ...]                                 :43-71, 713
 //   policy_games(battles, durations, results, prng, p1_network, p2_network, ...) -> whole games between two networks' raw policies, the
 //           per-game loop of `vs --budget=0 --bandit=pucb-1.0 --policy-mode=p` (vs.cc:107-408) for a batch at once (oakgpu_policy_games)
+//   selfplay_forest(teams, battle_seeds, seeds, agent, policy_mode, ...) -> n self-play games at once over the forest search, the per-game
+//           loop of `generate` (generate.cc:238-322) as one `.battle.data` byte stream (oakgpu_forest_selfplay)
 //   network hyper-parameter constants                                                     :586-596
 //   EncodedBattleFrames(size) {the reference's numpy fields + status, where, picks}, clear(), from_bytes(bytes, size)  py/battle/encoded-frames.h
 //   SampleIndexer() {get(path), prune(paths), size()}, sample(encoded_frames, indexer, threads, max_battle_length, min_iterations)  :73-245
@@ -402,6 +404,54 @@ PYBIND11_MODULE(pyoak, m) {
         return out;
       },
       py::arg("battles"), py::arg("durations"), py::arg("results"), py::arg("seeds"), py::arg("agent"));
+
+  m.def(
+      "selfplay_forest",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> teams, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> battle_seeds,
+         py::array_t<uint64_t, py::array::c_style | py::array::forcecast> seeds, Agent &agent, const std::string &policy_mode, double policy_temp,
+         double policy_min, uint32_t max_battle_length, bool solve_nash) {
+        // not in pyoak: the reference's `generate` loop for n games at once over the forest search (include/oakgpu.h:
+        // oakgpu_forest_selfplay); game g is the per-game loop with batch = 1 and seed = seeds[g].  Returns (stream bytes, offsets, n_frames,
+        // results, status).
+        const size_t n = (size_t)seeds.size();
+        if ((size_t)teams.size() != n * 60 || (size_t)battle_seeds.size() != n) throw std::runtime_error("selfplay_forest: teams n x 60, battle_seeds n, seeds n");
+        if (policy_mode.size() > 15) throw std::runtime_error("selfplay_forest: policy_mode: at most 15 characters");
+        const oakgpu_agent a{agent.budget.c_str(), agent.bandit.c_str(), agent.eval.c_str(), agent.matrix_ucb.c_str(), agent.discrete, agent.table};
+        std::string stream;
+        py::array_t<uint64_t> offsets(n + 1);
+        py::array_t<uint32_t> n_frames(n);
+        py::array_t<uint8_t> results(n), status(n);
+        int rc = 0;
+        std::string err;
+        {
+          py::gil_scoped_release release;
+          std::lock_guard<std::mutex> lock(g_ctx_mu);
+          oakgpu_selfplay_params P{};
+          oakgpu_net *net = nullptr;
+          oakgpu_forest *forest = nullptr;
+          rc = oakgpu_agent_params(context(), &a, 1, 0, &P.search, &net);
+          std::memcpy(P.policy_mode, policy_mode.c_str(), policy_mode.size() + 1);
+          P.policy_temp = policy_temp; P.policy_min = policy_min; P.max_battle_length = max_battle_length;
+          const uint32_t cap = (uint32_t)std::min<uint64_t>(P.search.iterations, 0xFFFFFFFFu);
+          if (!rc) rc = oakgpu_forest_selfplay_check((uint32_t)n, cap, P.search.bandit == 1, &P, net != nullptr, (uint32_t)n, teams.data(), solve_nash ? 1 : 0);
+          if (!rc && n) rc = oakgpu_forest_create(context(), (uint32_t)n, cap, P.search.bandit == 1, &forest);
+          if (!rc && n) rc = oakgpu_forest_selfplay(forest, net, &P, teams.data(), battle_seeds.data(), seeds.data(), (uint32_t)n, solve_nash ? 1 : 0);
+          size_t bytes = 0;
+          if (!rc && n) rc = oakgpu_forest_selfplay_records(forest, nullptr, 0, &bytes, nullptr, nullptr, nullptr, nullptr, 0);
+          if (!rc && n) {
+            stream.resize(bytes);
+            rc = oakgpu_forest_selfplay_records(forest, (uint8_t *)stream.data(), bytes, &bytes, offsets.mutable_data(), n_frames.mutable_data(),
+                                                results.mutable_data(), status.mutable_data(), 0);
+          }
+          if (rc) err = oakgpu_last_error();
+          oakgpu_forest_destroy(context(), forest);
+        }
+        if (rc) throw std::runtime_error(err);
+        if (!n) offsets.mutable_data()[0] = 0;
+        return py::make_tuple(py::bytes(stream), offsets, n_frames, results, status);
+      },
+      py::arg("teams"), py::arg("battle_seeds"), py::arg("seeds"), py::arg("agent"), py::arg("policy_mode") = "e", py::arg("policy_temp") = 1.0,
+      py::arg("policy_min") = 0.0, py::arg("max_battle_length") = 0, py::arg("solve_nash") = true);
 
   m.def(
       "value_policy_inference",

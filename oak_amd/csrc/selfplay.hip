@@ -25,25 +25,17 @@
 
 #include "../../include/oakgpu.h"
 #include "oakgpu_internal.h"
+#include "selfplay_pick.hpp"
 
 namespace {
 
-uint16_t compress_prob(double x) { // compress_probs<double, uint16_t> (compressed-frame.h:11-25)
-  const double v = x * 65535.0;
-  return v <= 0 ? 0 : v >= 65535.0 ? 65535 : (uint16_t)v;
-}
-size_t update_bytes(uint32_t m, uint32_t n) { return 1 + 2 + 4 + 2 * 2 + 2 * (m + n) * 2; } // Update::n_bytes_static (:77-82)
+using oak_pick::compress_prob;
+using oak_pick::update_bytes;
+using oak_pick::splitmix64;
+using oak_pick::sample_pdf;
 
 template <class T> void put(uint8_t *&p, T v) { memcpy(p, &v, sizeof v); p += sizeof v; }
 template <class T> T get(const uint8_t *&p) { T v; memcpy(&v, p, sizeof v); p += sizeof v; return v; }
-
-uint64_t splitmix64(uint64_t &x) {
-  uint64_t z = (x += 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-double uniform01(uint64_t &rng) { return (double)(splitmix64(rng) >> 11) * (1.0 / 9007199254740992.0); }
 
 // RuntimePolicy::get_policy (util/policy.h:22-98) for the modes the search output can feed: words of the mode string are
 // 'e' (empirical), 'n' (nash), 'x' (argmax of empirical), each optionally followed by a weight ("e0.9-x0.1"); then
@@ -51,38 +43,11 @@ double uniform01(uint64_t &rng) { return (double)(splitmix64(rng) >> 11) * (1.0 
 // w * prior AND THEN w * empirical: the reference's `case Mode::prior` has no `break` and falls into the empirical case
 // (policy.h:37-46), and a drop-in follows what the code does.  'b' (beta) throws in the reference (policy.h:59-60) and is
 // refused here, like an unknown mode character.
+// The string is parsed into words here; the arithmetic is selfplay_pick.hpp's, shared with the device game loop.
 bool get_policy(const double *prior, const double *empirical, const double *nash, int k, const char *mode, double temp, double minp, double *policy) {
-  for (int i = 0; i < 9; ++i) policy[i] = 0;
-  const std::string s(mode && *mode ? mode : "e");
-  size_t pos = 0;
-  while (pos <= s.size()) {
-    size_t end = s.find('-', pos);
-    if (end == std::string::npos) end = s.size();
-    const std::string word = s.substr(pos, end - pos);
-    pos = end + 1;
-    if (word.empty()) continue;
-    const double w = word.size() > 1 ? atof(word.c_str() + 1) : 1.0;
-    if (word[0] == 'p') { for (int i = 0; i < k; ++i) policy[i] += w * prior[i] + w * empirical[i]; }
-    else if (word[0] == 'e') { for (int i = 0; i < k; ++i) policy[i] += w * empirical[i]; }
-    else if (word[0] == 'n') { for (int i = 0; i < k; ++i) policy[i] += w * nash[i]; }
-    else if (word[0] == 'x') { policy[std::max_element(empirical, empirical + k) - empirical] += w; }
-    else return false;
-  }
-  if (temp != 1) {
-    double sum = 0;
-    for (int i = 0; i < 9; ++i) { policy[i] = std::pow(policy[i], temp); sum += policy[i]; }
-    for (int i = 0; i < 9; ++i) policy[i] /= sum;
-  }
-  double sum = 0;
-  for (int i = 0; i < 9; ++i) { if (policy[i] < minp) policy[i] = 0; sum += policy[i]; }
-  if (!(sum > 0)) return false;
-  for (int i = 0; i < 9; ++i) policy[i] /= sum;
-  return true;
-}
-int sample_pdf(const double *p, int k, uint64_t &rng) { // device.sample_pdf (util/random.h:40-49)
-  double u = uniform01(rng);
-  for (int i = 0; i < k; ++i) { u -= p[i]; if (u <= 0) return i; }
-  return 0;
+  oak_pick::PolicyMode words;
+  if (oak_pick::parse_policy_mode(mode, 64, &words)) { for (int i = 0; i < 9; ++i) policy[i] = 0; return false; }
+  return oak_pick::get_policy(prior, empirical, nash, k, words, temp, minp, policy);
 }
 
 // endless_battle_check (generate.cc:127-152): with ebc=false a battle of Ghosts that cannot hurt each other never ends before turn 1,000.
@@ -344,6 +309,35 @@ int oakgpu_selfplay_games(oakgpu_ctx *const *ctxs, oakgpu_net *net, const uint8_
   for (auto &t : th) t.join();
   for (uint32_t g = 0; g < n; ++g)
     if (rc[g]) return oakgpu_fail_msg(("oakgpu_selfplay_games: game " + std::to_string(g) + ": " + err[g]).c_str());
+  return 0;
+}
+
+// Diagnostic (no GPU involved): one turn's pick from a root output, by selfplay_pick.hpp's rule -- the text the device game loop compiles.
+int oakgpu_selfplay_pick_host(uint32_t m, uint32_t n, const uint64_t *visit_matrix, const double *value_matrix, uint64_t iterations, const double *p1_nash,
+                              const double *p2_nash, double nash_value, const double *p1_prior, const double *p2_prior, const uint8_t *p1_choices,
+                              const uint8_t *p2_choices, const char *policy_mode, double policy_temp, double policy_min, uint64_t *rng,
+                              double *empirical_value, double *p1_empirical, double *p2_empirical, double *p1_policy, double *p2_policy, int32_t *i_out,
+                              int32_t *j_out, uint8_t *update, uint32_t *update_len) {
+  if (!visit_matrix || !value_matrix || !rng || !empirical_value || !p1_empirical || !p2_empirical || !p1_policy || !p2_policy || !i_out || !j_out)
+    return oakgpu_fail_msg("oakgpu_selfplay_pick_host: null argument");
+  if (m < 1 || m > 9 || n < 1 || n > 9) return oakgpu_fail_msg("oakgpu_selfplay_pick_host: m, n must be in 1..9");
+  oak_pick::PolicyMode words;
+  if (oak_pick::parse_policy_mode(policy_mode, 63, &words))
+    return oakgpu_fail_msg("oakgpu_selfplay_pick_host: policy mode must be built from e / n / x / p words, 8 at the most (util/policy.h:22-98)");
+  const double zero[9] = {};
+  const double *n1 = p1_nash ? p1_nash : zero, *n2 = p2_nash ? p2_nash : zero, *r1 = p1_prior ? p1_prior : zero, *r2 = p2_prior ? p2_prior : zero;
+  oak_pick::process_output(visit_matrix, value_matrix, (int)m, (int)n, iterations, empirical_value, p1_empirical, p2_empirical, nullptr);
+  const double temp = policy_temp > 0 ? policy_temp : 1.0;
+  if (!oak_pick::get_policy(r1, p1_empirical, n1, (int)m, words, temp, policy_min, p1_policy) ||
+      !oak_pick::get_policy(r2, p2_empirical, n2, (int)n, words, temp, policy_min, p2_policy))
+    return oakgpu_fail_msg("oakgpu_selfplay_pick_host: RuntimePolicy: zero policy (the minimum-probability cut left nothing)");
+  const int i = sample_pdf(p1_policy, (int)m, *rng), j = sample_pdf(p2_policy, (int)n, *rng);
+  *i_out = i; *j_out = j;
+  if (update) {
+    const uint32_t len = oak_pick::encode_update(update, m, n, p1_choices ? p1_choices[i] : (uint8_t)i, p2_choices ? p2_choices[j] : (uint8_t)j, (uint32_t)iterations,
+                                                 *empirical_value, nash_value, p1_empirical, n1, p2_empirical, n2);
+    if (update_len) *update_len = len;
+  }
   return 0;
 }
 

@@ -113,6 +113,124 @@ def selfplay_games(ctxs, teams, battle_seeds, seeds, iterations=1 << 12, batch=1
     return [(out[g, :written[g]].tobytes(), int(frames[g]), int(result[g])) for g in range(n)]
 
 
+# ---- self-play over the forest search (oakgpu_forest_selfplay*; the rules are in include/oakgpu.h) -------------------------------------
+FSP_STATUS = ("OK", "MAX_LENGTH", "ZERO_POLICY")
+
+
+def _selfplay_params(iterations, bandit, c, evaluator, policy_mode, policy_temp, policy_min, max_battle_length, root_rolls, other_rolls, max_depth):
+    use_net = not isinstance(evaluator, str)
+    prm = _lib.SelfplayParams()
+    prm.search = _lib.SearchParams(iterations=int(iterations), batch=1, ucb_c=float(c), bandit={"ucb": 0, "pucb": 1, "ucb1": 2, "exp3": 3, "pexp3": 4}[bandit],
+                                   eval=1 if use_net else {"mc": 0, "poke-engine": 2}[evaluator], max_depth=int(max_depth), root_rolls=int(root_rolls),
+                                   other_rolls=int(other_rolls), seed=0, matrix_ucb=0, mucb_delay=0, mucb_minimum=0, mucb_c=0.0, exp3_alpha=-1.0,
+                                   duration_us=0)
+    mode = policy_mode.encode()
+    if len(mode) > 15:
+        raise ValueError("policy_mode: at most 15 characters")
+    prm.policy_mode = mode
+    prm.policy_temp, prm.policy_min = float(policy_temp), float(policy_min)
+    prm.max_battle_length, prm.seed, prm.keep_node = int(max_battle_length), 0, 0
+    return prm
+
+
+def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="ucb", evaluator="mc", policy_mode="e", policy_temp=1.0,
+                    policy_min=0.0, max_battle_length=0, root_rolls=3, other_rolls=1, max_depth=0, forest=None, solve_nash=True, stats=None):
+    """n self-play games at once over the forest search, resident on the GPU (oakgpu_forest_selfplay*): game g is selfplay_game(ctx,
+    teams[g], battle_seeds[g], batch=1, seed=seeds[g], ...).  teams uint8[n, 2, 6, 5]; forest: None (one made for this call) or a
+    search.Forest to reuse; stats: optional dict that receives turns, rows searched, compactions and host reads.
+    numpy arrays in: (stream bytes, offsets uint64[n + 1], n_frames uint32[n], results uint8[n], status uint8[n]) -- the stream is the
+    kept games' records in game order, a dropped game (status MAX_LENGTH / ZERO_POLICY, see FSP_STATUS) has zero bytes.
+    torch GPU tensors in (teams uint8 [n, 60]; battle_seeds, seeds int64 bit patterns): the same five as tensors on that device; nothing
+    but the stream's size is copied to the host."""
+    from .search import Forest
+    use_net = not isinstance(evaluator, str)
+    prm = _selfplay_params(iterations, bandit, c, evaluator, policy_mode, policy_temp, policy_min, max_battle_length, root_rolls, other_rolls, max_depth)
+    net = evaluator.handle if use_net else None
+    on_device = hasattr(teams, "data_ptr")
+    n = int(teams.shape[0]) if on_device else len(np.asarray(seeds).reshape(-1))
+    own = forest is None
+    if own:
+        forest = Forest(ctx, max(n, 1), max(int(iterations), 1), contextual=bandit == "pucb")
+    lib = ctx.lib
+    try:
+        size = C.c_size_t(0)
+        if on_device:
+            import torch
+            dev = teams.device
+            teams, battle_seeds, seeds = teams.contiguous().view(n, 60), battle_seeds.contiguous(), seeds.contiguous()
+            mine, theirs = torch.cuda.ExternalStream(ctx.stream_ptr(), device=dev), torch.cuda.current_stream(dev)
+            mine.wait_stream(theirs)
+            _lib.check(lib.oakgpu_forest_selfplay_dev(forest.handle, net, C.byref(prm), teams.data_ptr(), battle_seeds.data_ptr(), seeds.data_ptr(), n,
+                                                      int(bool(solve_nash))))
+            _lib.check(lib.oakgpu_forest_selfplay_records(forest.handle, None, 0, C.byref(size), None, None, None, None, 1))
+            stream = torch.zeros(max(size.value, 1), dtype=torch.uint8, device=dev)
+            offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            n_frames = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+            results, status = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev), torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+            _lib.check(lib.oakgpu_forest_selfplay_records(forest.handle, stream.data_ptr(), size.value, C.byref(size), offsets.data_ptr(),
+                                                          n_frames.data_ptr(), results.data_ptr(), status.data_ptr(), 1))
+            theirs.wait_stream(mine)
+            out = (stream[:size.value], offsets, n_frames[:n], results[:n], status[:n])
+        else:
+            t = np.ascontiguousarray(teams, dtype=np.uint8).reshape(n, 60)
+            bs = np.ascontiguousarray(np.asarray(battle_seeds).astype(np.uint64)).reshape(n)
+            sd = np.ascontiguousarray(np.asarray(seeds).astype(np.uint64)).reshape(n)
+            vp = lambda a: a.ctypes.data_as(C.c_void_p)
+            _lib.check(lib.oakgpu_forest_selfplay(forest.handle, net, C.byref(prm), vp(t), vp(bs), vp(sd), n, int(bool(solve_nash))))
+            _lib.check(lib.oakgpu_forest_selfplay_records(forest.handle, None, 0, C.byref(size), None, None, None, None, 0))
+            stream = np.zeros(max(size.value, 1), np.uint8)
+            offsets, n_frames = np.zeros(n + 1, np.uint64), np.zeros(max(n, 1), np.uint32)
+            results, status = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+            _lib.check(lib.oakgpu_forest_selfplay_records(forest.handle, vp(stream), size.value, C.byref(size), vp(offsets), vp(n_frames), vp(results),
+                                                          vp(status), 0))
+            out = (stream[:size.value].tobytes(), offsets, n_frames[:n], results[:n], status[:n])
+        if stats is not None:
+            st = (C.c_uint64 * 4)()
+            _lib.check(lib.oakgpu_forest_selfplay_last_stats(forest.handle, C.byref(st)))
+            stats.update(turns=int(st[0]), rows=int(st[1]), compactions=int(st[2]), host_reads=int(st[3]))
+        return out
+    finally:
+        if own:
+            forest.close()
+
+
+def forest_selfplay_check(max_trees, max_iterations, contextual, iterations, n=1, teams=None, c=2.0, bandit="ucb", evaluator="mc", policy_mode="e",
+                          policy_temp=1.0, policy_min=0.0, max_battle_length=0, root_rolls=3, other_rolls=1, max_depth=0, solve_nash=True,
+                          has_net=False, keep_node=False, matrix_ucb=0, duration_us=0):
+    """oakgpu_forest_selfplay_check alone (host only, no GPU): raises OakGpuError with the refusal's message.  evaluator "mc" | "poke-engine" |
+    "net" (with has_net saying whether a network is given)."""
+    prm = _selfplay_params(iterations, bandit, c, "mc" if evaluator == "net" else evaluator, policy_mode, policy_temp, policy_min, max_battle_length,
+                           root_rolls, other_rolls, max_depth)
+    if evaluator == "net":
+        prm.search.eval = 1
+    prm.keep_node, prm.search.matrix_ucb, prm.search.duration_us = int(bool(keep_node)), int(matrix_ucb), int(duration_us)
+    t = None if teams is None else np.ascontiguousarray(teams, dtype=np.uint8).reshape(n, 60)
+    _lib.check(_lib.load().oakgpu_forest_selfplay_check(int(max_trees), int(max_iterations), int(bool(contextual)), C.byref(prm), int(bool(has_net)), int(n),
+                                                        None if t is None else t.ctypes.data_as(C.c_void_p), int(bool(solve_nash))))
+
+
+def selfplay_pick_host(m, n, visit_matrix, value_matrix, iterations, rng, p1_nash=None, p2_nash=None, nash_value=0.0, p1_prior=None, p2_prior=None,
+                       p1_choices=None, p2_choices=None, policy_mode="e", policy_temp=1.0, policy_min=0.0):
+    """oakgpu_selfplay_pick_host (no GPU): one turn's pick from a root output by the rule the device game loop compiles.  visit_matrix uint64
+    [9, 9], value_matrix float64 [9, 9]; rng: the game's stream state.  Returns a dict: empirical_value, p1_empirical, p2_empirical, p1_policy,
+    p2_policy (float64[9]), i, j, rng (advanced), update (bytes).  Raises OakGpuError for a zeroed policy or a bad mode."""
+    lib = _lib.load()
+    vis = np.ascontiguousarray(visit_matrix, dtype=np.uint64).reshape(81)
+    val = np.ascontiguousarray(value_matrix, dtype=np.float64).reshape(81)
+    opt = lambda a, dt: None if a is None else np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=dt).reshape(-1), np.zeros(9, dt)])[:9])
+    arrs = [opt(p1_nash, np.float64), opt(p2_nash, np.float64), opt(p1_prior, np.float64), opt(p2_prior, np.float64), opt(p1_choices, np.uint8),
+            opt(p2_choices, np.uint8)]
+    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    state, ev, i, j, ulen = C.c_uint64(int(rng)), C.c_double(0), C.c_int32(0), C.c_int32(0), C.c_uint32(0)
+    e1, e2, q1, q2 = (np.zeros(9) for _ in range(4))
+    upd = np.zeros(83, np.uint8)
+    _lib.check(lib.oakgpu_selfplay_pick_host(int(m), int(n), vp(vis), vp(val), int(iterations), vp(arrs[0]), vp(arrs[1]), float(nash_value), vp(arrs[2]),
+                                             vp(arrs[3]), vp(arrs[4]), vp(arrs[5]), policy_mode.encode(), float(policy_temp), float(policy_min),
+                                             C.byref(state), C.byref(ev), vp(e1), vp(e2), vp(q1), vp(q2), C.byref(i), C.byref(j), vp(upd), C.byref(ulen)))
+    return {"empirical_value": ev.value, "p1_empirical": e1, "p2_empirical": e2, "p1_policy": q1, "p2_policy": q2, "i": i.value, "j": j.value,
+            "rng": state.value, "update": upd[:ulen.value].tobytes()}
+
+
 # ---- replay check of `.battle.data` records on the GPU (oakgpu_replay_records; the rules are in include/oakgpu.h) ----------------
 REPLAY_STATUS = ("OK", "COUNT", "ILLEGAL", "EARLY_END", "RESULT", "MALFORMED")
 REPORT_DTYPE = np.dtype([("status", np.uint8), ("player", np.uint8), ("frame", np.uint32), ("expected", np.uint8), ("got", np.uint8),

@@ -1,0 +1,115 @@
+"""The reference's `generate` as a command over the device game loop (oak_amd.frames.forest_selfplay: whole batches of self-play games
+resident on the GPU, one forest search per turn, oak_amd/csrc/forestplay.hip): play --games games and write their records as `.battle.data`
+files under --out.
+
+  python tools/generate_battle_data.py --out DIR [--games N] [--batch B] [--teams FILE] [--budget K] [--bandit ucb-2.0 | pucb-1.5]
+         [--eval mc | fp | NET.battle.net] [--discrete] [--policy-mode e] [--policy-temp 1] [--policy-min 0] [--max-battle-length L]
+         [--no-nash] [--seed S] [--file-mb 8]
+
+--teams FILE: JSON {"teams": [[[species, move, move, move, move] x 6] ...]} by name, the layout of tests/golden/ou_sample_teams.json (the
+default: the reference's 16 sample teams); each game draws its two teams from the file with --seed's generator, a pair that fails the
+endless battle check is drawn again (generate.cc:222-225).  --batch games are resident at a time (one forest of that many trees).  A file
+is closed once it holds --file-mb MiB of whole records; names are <seed>_<index>.battle.data.  A game that reaches --max-battle-length
+frames is dropped, as generate drops it.  Prints games, frames, dropped games and seconds."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def draw_games(team_bytes, n, rng):
+    """teams uint8[n, 60], battle seeds and policy seeds of n games; pairs the endless battle check refuses are drawn again."""
+    import ctypes as C
+    from oak_amd import _lib
+    lib = _lib.load()
+    teams = np.zeros((n, 60), np.uint8)
+    for g in range(n):
+        while True:
+            i, j = rng.integers(0, len(team_bytes), 2)
+            pair = np.ascontiguousarray(np.concatenate([team_bytes[i].reshape(30), team_bytes[j].reshape(30)]))
+            if not lib.oakgpu_endless_battle_check(pair.ctypes.data_as(C.c_void_p)):
+                break
+        teams[g] = pair
+    return teams, rng.integers(0, 1 << 63, n, dtype=np.uint64), rng.integers(0, 1 << 63, n, dtype=np.uint64)
+
+
+def main():
+    from policy_match import team_bytes
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--games", type=int, default=4096)
+    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--teams", default=os.path.join(ROOT, "tests", "golden", "ou_sample_teams.json"))
+    ap.add_argument("--budget", type=int, default=256)
+    ap.add_argument("--bandit", default="ucb-2.0")
+    ap.add_argument("--eval", default="fp")
+    ap.add_argument("--discrete", action="store_true")
+    ap.add_argument("--policy-mode", default="e")
+    ap.add_argument("--policy-temp", type=float, default=1.0)
+    ap.add_argument("--policy-min", type=float, default=0.0)
+    ap.add_argument("--max-battle-length", type=int, default=0)
+    ap.add_argument("--no-nash", action="store_true")
+    ap.add_argument("--seed", type=int, default=0x0A4B)
+    ap.add_argument("--file-mb", type=float, default=8.0)
+    a = ap.parse_args()
+    name, _, c = a.bandit.partition("-")
+    if name not in ("ucb", "pucb"):
+        sys.exit("--bandit: ucb-<c> or pucb-<c> (the forest search runs no other)")
+    from oak_amd.engine import Context, Network
+    from oak_amd.frames import forest_selfplay
+    from oak_amd.search import Forest
+    ctx = Context(0)
+    evaluator = {"mc": "mc", "": "mc", "fp": "poke-engine"}.get(a.eval)
+    net = None
+    if evaluator is None:
+        evaluator = net = Network(ctx, path=a.eval, discrete=a.discrete)
+    pool = team_bytes(a.teams)
+    rng = np.random.default_rng(a.seed)
+    os.makedirs(a.out, exist_ok=True)
+    batch = max(1, min(a.batch, a.games))
+    forest = Forest(ctx, batch, a.budget, contextual=name == "pucb")
+    limit = int(a.file_mb * (1 << 20))
+    played = frames = dropped = files = 0
+    pending = []
+    t0 = time.perf_counter()
+
+    def flush(everything):
+        nonlocal files, pending
+        while pending and (everything or sum(map(len, pending)) >= limit):
+            size, k = 0, 0
+            while k < len(pending) and (k == 0 or size + len(pending[k]) <= limit):
+                size += len(pending[k])
+                k += 1
+            with open(os.path.join(a.out, "%d_%d.battle.data" % (a.seed, files)), "wb") as f:
+                f.write(b"".join(pending[:k]))
+            files += 1
+            pending = pending[k:]
+
+    while played < a.games:
+        n = min(batch, a.games - played)
+        teams, battle_seeds, seeds = draw_games(pool, n, rng)
+        stream, offsets, n_frames, results, status = forest_selfplay(
+            ctx, teams, battle_seeds, seeds, a.budget, c=float(c or 2.0), bandit=name, evaluator=evaluator, policy_mode=a.policy_mode,
+            policy_temp=a.policy_temp, policy_min=a.policy_min, max_battle_length=a.max_battle_length, forest=forest, solve_nash=not a.no_nash)
+        kept = status == 0
+        pending += [stream[int(offsets[g]):int(offsets[g + 1])] for g in range(n) if kept[g]]
+        played, frames, dropped = played + n, frames + int(n_frames[kept].sum()), dropped + int((~kept).sum())
+        flush(False)
+    flush(True)
+    s = time.perf_counter() - t0
+    print("games: %d, frames: %d, dropped: %d, files: %d, seconds: %.2f (%.1f games/s, %.0f frames/s)" % (played - dropped, frames, dropped, files, s,
+                                                                                                       (played - dropped) / s, frames / s))
+    forest.close()
+    if net is not None:
+        net.close()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
