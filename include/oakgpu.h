@@ -814,6 +814,79 @@ int oakgpu_selfplay_pick_host(uint32_t m, uint32_t n, const uint64_t *visit_matr
                               double policy_min, uint64_t *rng, double *empirical_value, double *p1_empirical, double *p2_empirical,
                               double *p1_policy, double *p2_policy, int32_t *i_out, int32_t *j_out, uint8_t *update, uint32_t *update_len);
 
+/* ---- matches between two SEARCH agents over the forest search: the reference's `vs` with a budget (cpp/src/vs.cc:230-345), a batch of n
+ * games resident on one device (forestmatch.hip).  Seat p1 and seat p2 are independent agents: each has its own oakgpu_search_params
+ * (bandit, budget, evaluator), its own network and its own RuntimePolicy options; each searches for itself and plays its own side's move.
+ *   Semantics.  Game g starts from battles + 384 g, durations + 8 g, results_in[g] (as oakgpu_policy_games_dev takes them) and seeds[g].
+ *   A game whose input result is terminal is retired at once: results_out[g] = results_in[g], turns_out[g] = 0, status OK.  Otherwise
+ *   rng = seeds[g] ^ 0x9FB21C651E98DF25 and, while the result is not terminal and fewer than max_turns updates were made, per turn:
+ *   (1) m, n = the legal choice counts of p1, p2.  (2) Seeds, seat p1 first, then seat p2: a seat with more than one choice draws its tree
+ *   seed as one splitmix64(rng); a seat with exactly one choice draws nothing and is NOT searched (vs.cc:258,273).  (3) Seat p1's search
+ *   is one oakgpu_forest_search_dev with p1's parameters (batch = 1, seed ignored) and net over exactly the live rows with m > 1, gathered
+ *   into a contiguous buffer in row order; then seat p2's over the rows with n > 1; a seat without rows makes no call.  Tree k of a call
+ *   is the standalone search of that state with that seed.  (4) solve_nash != 0: the exact Nash solve of every searched row's payoffs, as
+ *   oakgpu_forest_selfplay does it (device payoffs, host threads, upload).  (5) Pick, seat p1 first, then seat p2, each from ITS OWN
+ *   search's output: process_output in double, get_policy for that seat's side with that seat's {policy_mode, policy_temp, policy_min},
+ *   index = sample_pdf(policy, rng), the choice at that index; ev = the output's empirical_value (P1's point of view for both seats).  An
+ *   unsearched seat plays its one choice, draws nothing, ev = 0.  The rule is selfplay_pick.hpp's text without contraction; pow
+ *   (policy_temp != 1) and expf (PUCB priors) are the device's.  (6) Early stop (vs.cc:263,287,300; early_stop = 0: off): a searched seat's
+ *   sign is s = +1 when t >= 1, -1 when t <= -1, else 0, with t = (log(ev) - log(1 - ev)) / early_stop in double (ev = 1 / 0 give +-inf
+ *   and so +-1; the reference's int cast is undefined there and equals this wherever it is defined); an unsearched seat has s = 0.
+ *   s1 * s2 > 0 ends the game BEFORE the update: result byte 1 (Win) for s1 > 0, else 2 (Lose), status EARLY_STOP, the turn not counted in
+ *   turns_out.  (7) A policy the minimum cut zeroes entirely stops that game alone: status ZERO_POLICY, result 0xFF, no counter, no log
+ *   record for that turn, and when it was seat p1's then seat p2 draws nothing; the call still returns 0.  (8) Otherwise
+ *   oakgpu_update_dev with (c1, c2).  A game cut at max_turns (0 = 1,000) has status MAX_TURNS and its last result byte (type 0).
+ *   Independence.  Game g's outputs depend on its own inputs and the parameters only -- not on n, its neighbours, the compaction, the
+ *   forest's capacity or earlier calls.
+ *   Outputs, by game index (device arrays in _dev, all nullable): results_out n bytes, turns_out n x u32 (updates made), status_out n
+ *   bytes (OAKGPU_FM_*), turn_log n x log_turns records of 24 bytes {u8 c1, c2, m, n; u32 0; double ev_p1, ev_p2} -- record (g, t) is the
+ *   game's t-th turn, entries no game reaches are not written, the early-stop turn writes c1 = c2 = 0; counts_out (host, nullable): wins,
+ *   ties, losses of seat p1 (early stops included), games stopped at max_turns.
+ *   Schedule.  Per turn: oakgpu_choices_dev for both sides over the resident rows, retire by scatter on game index, the compaction into the
+ *   other half of a double buffer (the choice counts ride along), and ONE prelude kernel (streams, both seats' tree seeds, both row lists by
+ *   a stable prefix sum) that leaves one 12-byte record -- live rows, p1 rows, p2 rows -- which is the loop's single host read per turn (the forest
+ *   search and the Nash solve read what they read by themselves); per seat a gather (393 bytes per row, the battle in 16-byte pieces),
+ *   the search, the pick scattered back by row list; one kernel for the early stop and the log; the update.  The two seats' searches run
+ *   one after the other on the same forest; the workspace belongs to the forest.
+ *   Refused by name before any launch (oakgpu_forest_match_check, host only): for either seat everything oakgpu_forest_check refuses --
+ *   time budgets, matrix_ucb, UCB1 / Exp3 / PExp3, iterations 0 or above max_iterations, PUCB on a non-contextual forest, a network
+ *   evaluator without a net -- n above max_trees, an unknown mode letter or 'b' or more than 8 words, policy_min > 1, an 'n' word without
+ *   solve_nash, early_stop < 0 or NaN.  There are no keep_node-style options.
+ * _dev takes device arrays (battles 16-byte aligned) and returns with the games complete; the other form takes host arrays.
+ * _last_stats: turns looped, p1 rows searched, p2 rows searched (summed over the turns), host reads of the per-turn record.
+ * oakgpu_match_pick_host (no GPU involved) is ONE seat's pick and early-stop sign from one root output: side 0 / 1, the root matrices and
+ * iterations, that side's nash and prior (nullable = 0), the seat's mode / temp / min, early_stop, rng in and out -> policy[9], index, ev,
+ * sign.  A zeroed policy fails ("zero policy"). */
+#define OAKGPU_FM_OK 0
+#define OAKGPU_FM_MAX_TURNS 1
+#define OAKGPU_FM_ZERO_POLICY 2
+#define OAKGPU_FM_EARLY_STOP 3
+typedef struct {
+  oakgpu_search_params search; /* batch and seed are ignored (1, the turn's draw) */
+  oakgpu_net *net;             /* required for eval = 1 / PUCB, else ignored */
+  char policy_mode[16];
+  double policy_temp, policy_min; /* policy_temp <= 0 means 1 */
+} oakgpu_match_seat;
+typedef struct {
+  oakgpu_match_seat p1, p2;
+  uint32_t max_turns;          /* updates per game before it is stopped (0 = 1000) */
+  double early_stop;           /* 0 = off; the reference's default is 10.0 */
+  uint32_t log_turns;          /* capacity of turn_log per game, 0 = no log */
+  int32_t solve_nash;
+} oakgpu_forest_match_params;
+typedef struct { uint8_t c1, c2, m, n; uint32_t zero; double ev_p1, ev_p2; } oakgpu_match_turn;
+int oakgpu_forest_match_check(uint32_t max_trees, uint32_t max_iterations, int contextual, const oakgpu_forest_match_params *params, uint32_t n);
+int oakgpu_forest_match_dev(oakgpu_forest *forest, const oakgpu_forest_match_params *params, const uint8_t *battles, const uint8_t *durations,
+                            const uint8_t *results_in, const uint64_t *seeds, uint32_t n, uint8_t *results_out, uint32_t *turns_out,
+                            uint8_t *status_out, oakgpu_match_turn *turn_log, uint64_t counts_out[4]);
+int oakgpu_forest_match(oakgpu_forest *forest, const oakgpu_forest_match_params *params, const uint8_t *battles, const uint8_t *durations,
+                        const uint8_t *results_in, const uint64_t *seeds, uint32_t n, uint8_t *results_out, uint32_t *turns_out,
+                        uint8_t *status_out, oakgpu_match_turn *turn_log, uint64_t counts_out[4]);
+int oakgpu_forest_match_last_stats(const oakgpu_forest *forest, uint64_t out[4]);
+int oakgpu_match_pick_host(int side, uint32_t m, uint32_t n, const uint64_t *visit_matrix, const double *value_matrix, uint64_t iterations,
+                           const double *nash, const double *prior, const char *policy_mode, double policy_temp, double policy_min,
+                           double early_stop, uint64_t *rng, double *policy, int32_t *index, double *empirical_value, int32_t *sign);
+
 /* ---- batched PKMN::battle(p1, p2, seed) (pkmn.h:50-57, init.h:90-154), level 100 sets.
  * teams: n x 60 bytes; seeds: n x u64; with first_update != 0 also performs the opening
  * update(battle, 0, 0) (benchmark.cc:29) and writes its result byte. */

@@ -9,6 +9,7 @@
 //   OakGPU::TreeSearch         <- MCTS::Search::run (mcts.h:154-247): Node heap + the five joint bandits, leaves batched on the GPU
 //   OakGPU::SearchForest       <- MCTS::Search::run for many positions at once: one GPU lane per tree, the trees resident on the device
 //   OakGPU::ForestSelfplay     <- the per-game loop of generate.cc:238-322 for a batch of games at once over the forest search, `.battle.data` out
+//   OakGPU::ForestMatch        <- the per-game loop of vs.cc:230-345 with a budget: two search agents, a batch of games at once over the forest search
 //   OakGPU::run                <- RuntimeSearch::run (util/search.h:66, search.cc:150-313): the Agent's strings pick everything
 //   OakGPU::solve_matrix       <- LRSNash::solve_fast as called at mcts.h:643-649 / pyoak.cc:394-426 (exact)
 //   OakGPU::SharedDeviceRollout<- benchmark.cc:23-31: n playouts from one root driven by ONE sequential std::mt19937
@@ -378,6 +379,44 @@ public:
     check(oakgpu_forest_selfplay_records(forest_.get(), bytes ? out.stream.data() : &none, bytes, &bytes, out.offsets.data(), out.n_frames.data(),
                                          out.results.data(), out.status.data(), 0));
     check(oakgpu_forest_selfplay_last_stats(forest_.get(), out.stats.data()));
+    return out;
+  }
+
+private:
+  SearchForest &forest_;
+};
+
+// Matches between two search agents over the forest search (include/oakgpu.h: oakgpu_forest_match*): n games at once, resident on the
+// device, from the caller's states; seat p1 and seat p2 each search with their own parameters and network and play their own side's
+// move -- the per-game loop of vs.cc:230-345 with a budget.  status: OAKGPU_FM_*; log: n x params.log_turns records, game-major, 0xFF
+// bytes where no game came.
+class ForestMatch {
+public:
+  struct Result {
+    std::vector<uint8_t> results, status;
+    std::vector<uint32_t> turns;
+    std::vector<oakgpu_match_turn> log;
+    std::array<uint64_t, 4> counts{}; // wins, ties, losses of seat p1 (early stops included), stopped at max_turns
+    std::array<uint64_t, 4> stats{};  // turns looped, p1 rows searched, p2 rows searched, host reads of the per-turn record
+  };
+  explicit ForestMatch(SearchForest &forest) : forest_{forest} {}
+  // params.p1 / p2 .net: the seats' network handles (Network::get()) or null; one seed per start state
+  Result play(const oakgpu_forest_match_params &params, const std::vector<Leaf> &starts, const std::vector<uint64_t> &seeds) {
+    if (seeds.size() != starts.size()) throw std::runtime_error{"oakgpu: ForestMatch::play: one seed per start state"};
+    const uint32_t n = (uint32_t)starts.size();
+    std::vector<uint8_t> b((size_t)n * OAKGPU_BATTLE_SIZE), d((size_t)n * OAKGPU_DURATIONS_SIZE), r(n);
+    for (uint32_t g = 0; g < n; ++g) {
+      std::memcpy(b.data() + (size_t)g * OAKGPU_BATTLE_SIZE, starts[g].battle, OAKGPU_BATTLE_SIZE);
+      std::memcpy(d.data() + (size_t)g * OAKGPU_DURATIONS_SIZE, starts[g].durations, OAKGPU_DURATIONS_SIZE);
+      r[g] = starts[g].result;
+    }
+    Result out;
+    out.results.assign(n, 0); out.status.assign(n, 0); out.turns.assign(n, 0);
+    out.log.resize((size_t)n * params.log_turns);
+    if (!out.log.empty()) std::memset(out.log.data(), 0xFF, out.log.size() * sizeof(oakgpu_match_turn));
+    check(oakgpu_forest_match(forest_.get(), &params, b.data(), d.data(), r.data(), seeds.data(), n, out.results.data(), out.turns.data(), out.status.data(),
+                              out.log.empty() ? nullptr : out.log.data(), out.counts.data()));
+    check(oakgpu_forest_match_last_stats(forest_.get(), out.stats.data()));
     return out;
   }
 

@@ -35,6 +35,7 @@ SYMBOLS = [
     "oakgpu_forest_last_stats", "oakgpu_search_stream", "oakgpu_agent_params",
     "oakgpu_forest_selfplay_check", "oakgpu_forest_selfplay_dev", "oakgpu_forest_selfplay_records", "oakgpu_forest_selfplay", "oakgpu_forest_selfplay_last_stats",
     "oakgpu_selfplay_pick_host",
+    "oakgpu_forest_match_check", "oakgpu_forest_match_dev", "oakgpu_forest_match", "oakgpu_forest_match_last_stats", "oakgpu_match_pick_host",
 ]
 
 
@@ -108,6 +109,20 @@ class Seat(C.Structure):              # oakgpu_seat
 class PolicyGamesParams(C.Structure):  # oakgpu_policy_games_params
     _fields_ = [("p1", Seat), ("p2", Seat), ("max_turns", C.c_uint32), ("poll", C.c_uint32), ("compact_below", C.c_float),
                 ("log_turns", C.c_uint32)]
+
+
+class MatchSeat(C.Structure):         # oakgpu_match_seat
+    _fields_ = [("search", SearchParams), ("net", C.c_void_p), ("policy_mode", C.c_char * 16), ("policy_temp", C.c_double), ("policy_min", C.c_double)]
+
+
+class ForestMatchParams(C.Structure):  # oakgpu_forest_match_params
+    _fields_ = [("p1", MatchSeat), ("p2", MatchSeat), ("max_turns", C.c_uint32), ("early_stop", C.c_double), ("log_turns", C.c_uint32),
+                ("solve_nash", C.c_int32)]
+
+
+class MatchTurn(C.Structure):         # oakgpu_match_turn
+    _fields_ = [("c1", C.c_uint8), ("c2", C.c_uint8), ("m", C.c_uint8), ("n", C.c_uint8), ("zero", C.c_uint32), ("ev_p1", C.c_double),
+                ("ev_p2", C.c_double)]
 
 
 class ForestOutputs(C.Structure):     # oakgpu_forest_outputs: one device pointer per array
@@ -317,6 +332,12 @@ def load():
     lib.oakgpu_forest_selfplay_last_stats.argtypes = [vp, C.POINTER(u64 * 4)]
     lib.oakgpu_selfplay_pick_host.argtypes = [u32, u32, vp, vp, u64, vp, vp, C.c_double, vp, vp, vp, vp, C.c_char_p, C.c_double, C.c_double, C.POINTER(u64),
                                               C.POINTER(C.c_double), vp, vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.POINTER(u32)]
+    lib.oakgpu_forest_match_check.argtypes = [u32, u32, i32, C.POINTER(ForestMatchParams), u32]
+    lib.oakgpu_forest_match_dev.argtypes = [vp, C.POINTER(ForestMatchParams), vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+    lib.oakgpu_forest_match.argtypes = [vp, C.POINTER(ForestMatchParams), vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+    lib.oakgpu_forest_match_last_stats.argtypes = [vp, C.POINTER(u64 * 4)]
+    lib.oakgpu_match_pick_host.argtypes = [i32, u32, u32, vp, vp, u64, vp, vp, C.c_char_p, C.c_double, C.c_double, C.c_double, C.POINTER(u64), vp,
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     _lib = lib
     return lib
 

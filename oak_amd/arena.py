@@ -3,6 +3,9 @@
   policy_games(ctx, seats, ...)  <- the per-game loop of the reference's `vs` (cpp/src/vs.cc:107-408) in the form that needs no tree:
                                     vs --budget=0 --bandit=pucb-1.0 --policy-mode=p --p1-eval=A --p2-eval=B
   match(ctx, net_a, net_b, ...)  <- its outer loop (vs.cc:355-377) and its report (vs.cc:66-68,424-427): W D L, score, Elo difference
+  search_games(ctx, seats, ...)  <- the per-game loop with a budget (vs.cc:230-345): both seats SEARCH, each with its own agent, on the
+                                    forest search (include/oakgpu.h: oakgpu_forest_match*)
+  search_match(ctx, a, b, ...)   <- the outer loop and the report for two search agents
 
 Nothing here computes on the CPU but the bookkeeping of a finished batch."""
 import contextlib
@@ -94,6 +97,196 @@ def last_stats(ctx):
     out = (C.c_uint64 * 4)()
     _lib.check(ctx.lib.oakgpu_policy_games_last_stats(out))
     return dict(zip(("row_turns", "turns", "compactions", "polls"), (int(x) for x in out)))
+
+
+# ---- matches between two SEARCH agents over the forest search (oakgpu_forest_match*; the rules are in include/oakgpu.h) -----------------
+FM_STATUS = ("OK", "MAX_TURNS", "ZERO_POLICY", "EARLY_STOP")
+TURN_DTYPE = np.dtype([("c1", "u1"), ("c2", "u1"), ("m", "u1"), ("n", "u1"), ("zero", "<u4"), ("ev_p1", "<f8"), ("ev_p2", "<f8")])   # oakgpu_match_turn
+_BANDITS = {"ucb": 0, "pucb": 1, "ucb1": 2, "exp3": 3, "pexp3": 4}
+
+
+def _match_seat(s):
+    """A search seat from a dict: iterations, bandit "ucb" | "pucb", c, evaluator "mc" | "poke-engine" | a Network, policy_mode, policy_temp,
+    policy_min, max_depth, root_rolls, other_rolls (has_net / matrix_ucb / duration_us: for the check alone)."""
+    ev = s.get("evaluator", "mc")
+    use_net = not isinstance(ev, str)
+    seat = _lib.MatchSeat()
+    seat.search = _lib.SearchParams(iterations=int(s["iterations"]), batch=1, ucb_c=float(s.get("c", 2.0)), bandit=_BANDITS[s.get("bandit", "ucb")],
+                                    eval=1 if use_net or ev == "net" else {"mc": 0, "poke-engine": 2}[ev], max_depth=int(s.get("max_depth", 0)),
+                                    root_rolls=int(s.get("root_rolls", 3)), other_rolls=int(s.get("other_rolls", 1)), seed=0,
+                                    matrix_ucb=int(s.get("matrix_ucb", 0)), mucb_delay=0, mucb_minimum=0, mucb_c=0.0, exp3_alpha=-1.0,
+                                    duration_us=int(s.get("duration_us", 0)))
+    seat.net = getattr(ev, "handle", None) if use_net else (C.c_void_p(1) if s.get("has_net") else None)
+    mode = s.get("policy_mode", "e").encode()
+    if len(mode) > 15:
+        raise ValueError("policy_mode: at most 15 characters")
+    seat.policy_mode = mode
+    seat.policy_temp, seat.policy_min = float(s.get("policy_temp", 1.0)), float(s.get("policy_min", 0.0))
+    return seat
+
+
+def _match_params(seats, max_turns, early_stop, log_turns, solve_nash):
+    return _lib.ForestMatchParams(_match_seat(seats[0]), _match_seat(seats[1]), int(max_turns), float(early_stop), int(log_turns), int(bool(solve_nash)))
+
+
+def forest_match_check(max_trees, max_iterations, contextual, seats, n=1, max_turns=0, early_stop=0.0, solve_nash=True):
+    """oakgpu_forest_match_check alone (host only, no GPU): raises OakGpuError with the refusal's message.  A seat's evaluator may be "net"
+    here, with has_net saying whether a network is given."""
+    p = _match_params(seats, max_turns, early_stop, 0, solve_nash)
+    _lib.check(_lib.load().oakgpu_forest_match_check(int(max_trees), int(max_iterations), int(bool(contextual)), C.byref(p), int(n)))
+
+
+def match_pick_host(side, m, n, visit_matrix, value_matrix, iterations, rng, nash=None, prior=None, policy_mode="e", policy_temp=1.0, policy_min=0.0,
+                    early_stop=0.0):
+    """oakgpu_match_pick_host (no GPU): ONE seat's pick and early-stop sign from one root output.  side 0 / 1; nash / prior: that side's.
+    Returns a dict: policy float64[9], index, empirical_value, sign, rng (advanced).  Raises OakGpuError for a zeroed policy or a bad mode."""
+    vis = np.ascontiguousarray(visit_matrix, dtype=np.uint64).reshape(81)
+    val = np.ascontiguousarray(value_matrix, dtype=np.float64).reshape(81)
+    opt = lambda a: None if a is None else np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=np.float64).reshape(-1), np.zeros(9)])[:9])
+    na, pr = opt(nash), opt(prior)
+    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    state, ev, idx, sign = C.c_uint64(int(rng)), C.c_double(0), C.c_int32(0), C.c_int32(0)
+    pol = np.zeros(9)
+    _lib.check(_lib.load().oakgpu_match_pick_host(int(side), int(m), int(n), vp(vis), vp(val), int(iterations), vp(na), vp(pr), policy_mode.encode(),
+                                                  float(policy_temp), float(policy_min), float(early_stop), C.byref(state), vp(pol), C.byref(idx), C.byref(ev),
+                                                  C.byref(sign)))
+    return {"policy": pol, "index": idx.value, "empirical_value": ev.value, "sign": sign.value, "rng": state.value}
+
+
+def search_games(ctx, seats, battles, durations, results, seeds, forest=None, max_turns=1000, early_stop=0.0, log_turns=0, solve_nash=True, stats=None):
+    """n whole games from the given states between two SEARCH agents on the forest search (oakgpu_forest_match*): seats = (p1, p2), each a
+    dict as _match_seat takes it; seeds uint64[n], one per game.  forest: None (one made for this call, contextual when a seat is PUCB)
+    or a search.Forest to reuse; stats: optional dict that receives turns, p1_rows, p2_rows, host_reads.
+
+    numpy arrays in -> numpy arrays out; torch tensors on the GPU in (seeds int64 bit patterns) -> torch tensors out, nothing leaves the
+    device but the counters.  Returns a dict: results uint8[n], turns uint32[n] (int32 for torch), status uint8[n] (FM_STATUS), counts =
+    (wins, ties, losses of seat p1 with early stops, stopped at max_turns), log: TURN_DTYPE [n, log_turns] prefilled with 0xFF bytes
+    (torch: uint8 [n, log_turns, 24]); None without log_turns."""
+    from .search import Forest
+    p = _match_params(seats, max_turns, early_stop, log_turns, solve_nash)
+    counts = (C.c_uint64 * 4)()
+    on_device = not isinstance(battles, np.ndarray) and hasattr(battles, "data_ptr")
+    n = int(battles.shape[0]) if on_device else len(np.asarray(results).reshape(-1))
+    own = forest is None
+    if own:
+        forest = Forest(ctx, max(n, 1), max(int(seats[0]["iterations"]), int(seats[1]["iterations"]), 1),
+                        contextual="pucb" in (seats[0].get("bandit"), seats[1].get("bandit")))
+    try:
+        if not on_device:
+            battles = np.ascontiguousarray(battles, dtype=np.uint8).reshape(n, 384)
+            durations = np.ascontiguousarray(durations, dtype=np.uint8).reshape(n, 8)
+            results = np.ascontiguousarray(results, dtype=np.uint8).reshape(n)
+            seeds = np.ascontiguousarray(np.asarray(seeds).astype(np.uint64)).reshape(n)
+            out = dict(results=np.zeros(n, np.uint8), turns=np.zeros(n, np.uint32), status=np.zeros(n, np.uint8),
+                       log=np.frombuffer(bytearray(b"\xff" * (n * log_turns * 24)), dtype=TURN_DTYPE).reshape(n, log_turns) if log_turns else None)
+            ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+            rc = ctx.lib.oakgpu_forest_match(forest.handle, C.byref(p), ptr(battles), ptr(durations), ptr(results), ptr(seeds), n, ptr(out["results"]),
+                                             ptr(out["turns"]), ptr(out["status"]), ptr(out["log"]), counts)
+        else:
+            import torch
+            dev = battles.device
+            u8 = lambda t, shape: t.to(device=dev, dtype=torch.uint8).reshape(shape).contiguous()
+            battles, durations, results, seeds = u8(battles, (n, 384)), u8(durations, (n, 8)), u8(results, (n,)), seeds.contiguous()
+            new = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)
+            out = dict(results=new((n,), torch.uint8), turns=new((n,), torch.int32), status=new((n,), torch.uint8),
+                       log=torch.full((n, log_turns, 24), 0xFF, dtype=torch.uint8, device=dev) if log_turns else None)
+            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+            with _ordered(ctx, dev):
+                rc = ctx.lib.oakgpu_forest_match_dev(forest.handle, C.byref(p), ptr(battles), ptr(durations), ptr(results), ptr(seeds), n, ptr(out["results"]),
+                                                     ptr(out["turns"]), ptr(out["status"]), ptr(out["log"]), counts)
+        _lib.check(rc)
+        out["counts"] = tuple(int(x) for x in counts)
+        if stats is not None:
+            st = (C.c_uint64 * 4)()
+            _lib.check(ctx.lib.oakgpu_forest_match_last_stats(forest.handle, C.byref(st)))
+            stats.update(turns=int(st[0]), p1_rows=int(st[1]), p2_rows=int(st[2]), host_reads=int(st[3]))
+        return out
+    finally:
+        if own:
+            forest.close()
+
+
+def search_match(ctx, agent_a, agent_b, teams, games, seed, mirror=False, max_turns=1000, early_stop=10.0, solve_nash=True, return_games=False):
+    """`games` matches between search agents A and B (dicts as _match_seat takes them; an evaluator may also be a `.battle.net` path, loaded
+    for the call, "discrete": True choosing the int8 form) as vs.cc:355-377 plays them: per match two teams drawn from `teams` (uint8
+    [T, 6, 5]; one team for both sides with mirror), played in both seatings with the agents swapped unless mirror is set.  A drawn pair
+    that fails the endless-battle check (oakgpu_endless_battle_check, on the host) is drawn again.  Every seating is one search_games batch.
+
+    Returns a dict from A's point of view: W, D, L, games, score, elo, early_stops, stopped (games cut at max_turns: counted as draws), and
+    zero_policy (games a zeroed policy stopped: counted nowhere else); with return_games the per-seating inputs and outputs."""
+    import torch
+    lib = _lib.load()
+    teams = np.ascontiguousarray(teams, dtype=np.uint8).reshape(-1, 6, 5)
+    rng = np.random.default_rng(int(seed))
+    pairs = int(games)
+    pick = np.zeros((pairs, 2), np.int64)
+    for g in range(pairs):
+        for _ in range(1000):
+            pick[g] = rng.integers(0, teams.shape[0], size=2)
+            if mirror:
+                pick[g, 1] = pick[g, 0]
+            both = np.ascontiguousarray(np.concatenate([teams[pick[g, 0]].reshape(30), teams[pick[g, 1]].reshape(30)]))
+            if not lib.oakgpu_endless_battle_check(both.ctypes.data_as(C.c_void_p)):
+                break
+        else:
+            raise _lib.OakGpuError("search_match: every drawn team pair fails the endless-battle check")
+    seatings = 1 if mirror else 2
+    battle_seeds = rng.integers(1, 2 ** 63, size=(seatings, pairs), dtype=np.uint64)
+    streams = rng.integers(1, 2 ** 63, size=(seatings, pairs), dtype=np.uint64)
+    loaded = {}
+
+    def agent_of(a):
+        a = dict(a)
+        ev = a.get("evaluator", "mc")
+        if isinstance(ev, str) and ev not in ("mc", "poke-engine"):
+            key = (ev, bool(a.get("discrete")))
+            if key not in loaded:
+                loaded[key] = Network(ctx, path=ev, discrete=key[1])
+            a["evaluator"] = loaded[key]
+        return a
+
+    forest = None
+    try:
+        from .search import Forest
+        a, b = agent_of(agent_a), agent_of(agent_b)
+        forest = Forest(ctx, max(pairs, 1), max(int(a["iterations"]), int(b["iterations"]), 1), contextual="pucb" in (a.get("bandit"), b.get("bandit")))
+        dev = torch.device("cuda", ctx.device)
+        both = np.ascontiguousarray(np.stack([teams[pick[:, 0]], teams[pick[:, 1]]], axis=1).reshape(pairs, 60))
+        d_teams = torch.from_numpy(both).to(dev)
+        w = d = l = stopped = early = zeroed = 0
+        played = []
+        for s in range(seatings):
+            d_seeds = torch.from_numpy(battle_seeds[s].view(np.int64)).to(dev)
+            bt = torch.empty((pairs, 384), dtype=torch.uint8, device=dev)
+            du = torch.empty((pairs, 8), dtype=torch.uint8, device=dev)
+            rs = torch.empty((pairs,), dtype=torch.uint8, device=dev)
+            with _ordered(ctx, dev):
+                _lib.check(ctx.lib.oakgpu_init_battles_dev(ctx.handle, C.c_void_p(d_teams.data_ptr()), C.c_void_p(d_seeds.data_ptr()), pairs, 1,
+                                                           C.c_void_p(bt.data_ptr()), C.c_void_p(du.data_ptr()), C.c_void_p(rs.data_ptr())))
+            out = search_games(ctx, (a, b) if s == 0 else (b, a), bt, du, rs, torch.from_numpy(streams[s].view(np.int64)).to(dev), forest=forest,
+                               max_turns=max_turns, early_stop=early_stop, solve_nash=solve_nash)
+            wins, ties, losses, cut = out["counts"]
+            w += wins if s == 0 else losses
+            l += losses if s == 0 else wins
+            d += ties + cut
+            stopped += cut
+            status = out["status"].cpu().numpy()
+            early += int((status == 3).sum())
+            zeroed += int((status == 2).sum())
+            if return_games:
+                played.append(dict(a_is_p1=s == 0, teams=pick.copy(), battle_seeds=battle_seeds[s].copy(), streams=streams[s].copy(),
+                                   results=out["results"].cpu().numpy(), turns=out["turns"].cpu().numpy(), status=status, counts=out["counts"]))
+    finally:
+        if forest is not None:
+            forest.close()
+        for net in loaded.values():
+            net.close()
+    total = w + d + l
+    score = (w + 0.5 * d) / total if total else 0.5
+    res = dict(W=w, D=d, L=l, games=total, score=score, elo=elo_difference(score), early_stops=early, stopped=stopped, zero_policy=zeroed)
+    if return_games:
+        res["seatings"] = played
+    return res
 
 
 def elo_difference(score):

@@ -301,6 +301,9 @@ struct oakgpu_forest {
   // the game loop's workspace (forestplay.hip), freed with the forest
   void *attachment = nullptr;
   void (*attachment_free)(void *) = nullptr;
+  // the match loop's (forestmatch.hip), likewise
+  void *match_attachment = nullptr;
+  void (*match_attachment_free)(void *) = nullptr;
   template <class T> int get(T *&p, size_t count) {
     RC(dev_alloc(p, count));
     dev.push_back(p);
@@ -309,6 +312,8 @@ struct oakgpu_forest {
   void release() {
     if (attachment && attachment_free) attachment_free(attachment);
     attachment = nullptr;
+    if (match_attachment && match_attachment_free) match_attachment_free(match_attachment);
+    match_attachment = nullptr;
     for (void *p : dev) (void)hipFree(p);
     dev.clear();
     if (path_node) (void)hipFree(path_node);
@@ -344,6 +349,8 @@ void oakgpu_forest_limits(const oakgpu_forest *f, uint32_t *max_trees, uint32_t 
 }
 void *oakgpu_forest_attachment(const oakgpu_forest *f) { return f->attachment; }
 void oakgpu_forest_set_attachment(oakgpu_forest *f, void *p, void (*dtor)(void *)) { f->attachment = p; f->attachment_free = dtor; }
+void *oakgpu_forest_match_attachment(const oakgpu_forest *f) { return f->match_attachment; }
+void oakgpu_forest_set_match_attachment(oakgpu_forest *f, void *p, void (*dtor)(void *)) { f->match_attachment = p; f->match_attachment_free = dtor; }
 
 extern "C" {
 

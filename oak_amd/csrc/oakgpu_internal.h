@@ -79,6 +79,9 @@ oakgpu_ctx *oakgpu_forest_ctx(const oakgpu_forest *forest);
 void oakgpu_forest_limits(const oakgpu_forest *forest, uint32_t *max_trees, uint32_t *max_iterations, int *contextual);
 void *oakgpu_forest_attachment(const oakgpu_forest *forest);
 void oakgpu_forest_set_attachment(oakgpu_forest *forest, void *p, void (*dtor)(void *));
+// a second one of the same kind for the match loop (forestmatch.hip), so that one forest serves self-play and matches in turn
+void *oakgpu_forest_match_attachment(const oakgpu_forest *forest);
+void oakgpu_forest_set_match_attachment(oakgpu_forest *forest, void *p, void (*dtor)(void *));
 // A resident `.battle.data` corpus (trainframes.hip creates and frees it; corpuseval.hip evaluates it chunk by chunk)
 struct oakgpu_corpus {
   oakgpu_ctx *ctx = nullptr;

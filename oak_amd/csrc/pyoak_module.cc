@@ -16,7 +16,9 @@
 //           per-game loop of `vs --budget=0 --bandit=pucb-1.0 --policy-mode=p` (vs.cc:107-408) for a batch at once (oakgpu_policy_games)
 //   selfplay_forest(teams, battle_seeds, seeds, agent, policy_mode, ...) -> n self-play games at once over the forest search, the per-game
 //           loop of `generate` (generate.cc:238-322) as one `.battle.data` byte stream (oakgpu_forest_selfplay)
-//   network hyper-parameter constants                                                     :586-596
+//   match_forest(battles, durations, results, seeds, agent_p1, agent_p2, policy_p1, policy_p2, ...) -> n games between two SEARCH agents at
+//           once over the forest search, the per-game loop of `vs` with a budget (vs.cc:230-345) (oakgpu_forest_match)
+//   network hyper-parameter constants                                                    :586-596
 //   EncodedBattleFrames(size) {the reference's numpy fields + status, where, picks}, clear(), from_bytes(bytes, size)  py/battle/encoded-frames.h
 //   SampleIndexer() {get(path), prune(paths), size()}, sample(encoded_frames, indexer, threads, max_battle_length, min_iterations)  :73-245
 // Every battle operation goes through the C ABI (GPU); this file holds no battle arithmetic.  The battle training-data loader
@@ -452,6 +454,59 @@ PYBIND11_MODULE(pyoak, m) {
       },
       py::arg("teams"), py::arg("battle_seeds"), py::arg("seeds"), py::arg("agent"), py::arg("policy_mode") = "e", py::arg("policy_temp") = 1.0,
       py::arg("policy_min") = 0.0, py::arg("max_battle_length") = 0, py::arg("solve_nash") = true);
+
+  m.def(
+      "match_forest",
+      [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> battles, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> durations,
+         py::array_t<uint8_t, py::array::c_style | py::array::forcecast> results, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> seeds,
+         Agent &agent_p1, Agent &agent_p2, const std::string &policy_p1, const std::string &policy_p2, double temp_p1, double temp_p2, double min_p1,
+         double min_p2, uint32_t max_turns, double early_stop, uint32_t log_turns, bool solve_nash) {
+        // not in pyoak: the reference's `vs` loop with a budget for n games at once over the forest search (include/oakgpu.h:
+        // oakgpu_forest_match); each seat's Agent strings go through search's own parser.  Returns a dict: results, turns, status, log
+        // (uint8 [n, log_turns, 24], 0xFF where no game came), counts (wins, ties, losses of seat p1, stopped at max_turns).
+        const size_t n = (size_t)results.size();
+        if ((size_t)battles.size() != n * OAKGPU_BATTLE_SIZE || (size_t)durations.size() != n * OAKGPU_DURATIONS_SIZE || (size_t)seeds.size() != n)
+          throw std::runtime_error("match_forest: battles n x 384, durations n x 8, results n, seeds n");
+        if (policy_p1.size() > 15 || policy_p2.size() > 15) throw std::runtime_error("match_forest: policy mode: at most 15 characters");
+        const oakgpu_agent a1{agent_p1.budget.c_str(), agent_p1.bandit.c_str(), agent_p1.eval.c_str(), agent_p1.matrix_ucb.c_str(), agent_p1.discrete, agent_p1.table};
+        const oakgpu_agent a2{agent_p2.budget.c_str(), agent_p2.bandit.c_str(), agent_p2.eval.c_str(), agent_p2.matrix_ucb.c_str(), agent_p2.discrete, agent_p2.table};
+        py::array_t<uint8_t> res(n), status(n);
+        py::array_t<uint32_t> turns(n);
+        py::array_t<uint8_t> log(std::vector<py::ssize_t>{(py::ssize_t)n, (py::ssize_t)log_turns, (py::ssize_t)sizeof(oakgpu_match_turn)});
+        std::memset(log.mutable_data(), 0xFF, (size_t)log.size());
+        uint64_t counts[4] = {0, 0, 0, 0};
+        int rc = 0;
+        std::string err;
+        {
+          py::gil_scoped_release release;
+          std::lock_guard<std::mutex> lock(g_ctx_mu);
+          oakgpu_forest_match_params P{};
+          oakgpu_forest *forest = nullptr;
+          rc = oakgpu_agent_params(context(), &a1, 1, 0, &P.p1.search, &P.p1.net);
+          if (!rc) rc = oakgpu_agent_params(context(), &a2, 1, 0, &P.p2.search, &P.p2.net);
+          std::memcpy(P.p1.policy_mode, policy_p1.c_str(), policy_p1.size() + 1);
+          std::memcpy(P.p2.policy_mode, policy_p2.c_str(), policy_p2.size() + 1);
+          P.p1.policy_temp = temp_p1; P.p2.policy_temp = temp_p2; P.p1.policy_min = min_p1; P.p2.policy_min = min_p2;
+          P.max_turns = max_turns; P.early_stop = early_stop; P.log_turns = log_turns; P.solve_nash = solve_nash ? 1 : 0;
+          const uint32_t cap = (uint32_t)std::min<uint64_t>(std::max(P.p1.search.iterations, P.p2.search.iterations), 0xFFFFFFFFu);
+          const int contextual = P.p1.search.bandit == 1 || P.p2.search.bandit == 1;
+          if (!rc) rc = oakgpu_forest_match_check((uint32_t)n, cap, contextual, &P, (uint32_t)n);
+          if (!rc && n) rc = oakgpu_forest_create(context(), (uint32_t)n, cap, contextual, &forest);
+          if (!rc && n)
+            rc = oakgpu_forest_match(forest, &P, battles.data(), durations.data(), results.data(), seeds.data(), (uint32_t)n, res.mutable_data(), turns.mutable_data(),
+                                     status.mutable_data(), log_turns ? (oakgpu_match_turn *)log.mutable_data() : nullptr, counts);
+          if (rc) err = oakgpu_last_error();
+          oakgpu_forest_destroy(context(), forest);
+        }
+        if (rc) throw std::runtime_error(err);
+        py::dict out;
+        out["results"] = res; out["turns"] = turns; out["status"] = status; out["log"] = log;
+        out["counts"] = py::make_tuple(counts[0], counts[1], counts[2], counts[3]);
+        return out;
+      },
+      py::arg("battles"), py::arg("durations"), py::arg("results"), py::arg("seeds"), py::arg("agent_p1"), py::arg("agent_p2"), py::arg("policy_p1") = "e",
+      py::arg("policy_p2") = "e", py::arg("temp_p1") = 1.0, py::arg("temp_p2") = 1.0, py::arg("min_p1") = 0.0, py::arg("min_p2") = 0.0,
+      py::arg("max_turns") = 1000, py::arg("early_stop") = 0.0, py::arg("log_turns") = 0, py::arg("solve_nash") = true);
 
   m.def(
       "value_policy_inference",
