@@ -459,6 +459,51 @@ int oakgpu_forest_nodes(oakgpu_forest *forest, uint32_t tree, uint32_t first, ui
  * made (prep, steps, level kernels, evaluations, back-ups; an evaluation counts as one), host reads of the live count. */
 int oakgpu_forest_last_stats(const oakgpu_forest *forest, uint64_t out[4]);
 
+/* ---- kept forests: a tree goes on into the next turn (generate's --keep-node: generate.cc:324-333, Heap::update in search.cc:27-52).
+ * oakgpu_forest_create_kept makes a forest whose trees hold keep_arena nodes each (>= max_iterations + 1; 0 = 4 * max_iterations + 1) and
+ * whose node arenas and edge tables exist TWICE, front and back; the slot count follows from keep_arena by the plain forest's rule (the
+ * power of two >= max(16, 2 * keep_arena)).  Device memory per tree, beside the per-tree rows every forest has:
+ *     2 * (keep_arena * 224 + slots * 32) bytes           (oakgpu_forest_kept_tree_bytes; 0 for refused arguments)
+ *   plus 4 * keep_arena for the advance's map.  A failed allocation names the bytes asked for.  Such a forest serves every call of a plain
+ *   one unchanged; a plain forest answers the calls below with a refusal that says it was created without keep.
+ * oakgpu_forest_advance_dev(forest, i, j, obs, src_tree, n_new, kept_out), all device pointers (src_tree nullable = the same row): new
+ *   tree t continues tree src_tree[t] of the last call along the played cell (i[t], j[t]) and the update's 16-byte observation obs + 16 t
+ *   (oakgpu_update_dev's `actions`) -- ONE launch, one wave per new tree, that re-roots the tree and moves it to its new row; it reads the
+ *   front copy, writes the back copy, and the two swap.  The rule per tree is oakgpu_heap_update's: a source that was never searched or
+ *   whose root was never initialised, or a cell / observation no iteration took: nothing is kept, kept_out[t] = 0, the new tree is empty
+ *   with an uninitialised root.  Otherwise the child becomes node 0 and its whole subtree is kept, bandits byte for byte, node ids still
+ *   in creation order, kept_out[t] = 1 -- also when the child itself is uninitialised: the next search then initialises it, priors
+ *   included.  The tree's fast_prng word stays in its old row: every search reseeds it.  src_tree values need not be distinct.
+ *   Capacity: a kept subtree that leaves fewer than max_iterations free nodes (kept + max_iterations > keep_arena) is DROPPED to an empty
+ *   tree, kept_out[t] = 0, and counted (oakgpu_forest_keep_stats).  This is the one place where the device departs from the host's
+ *   oakgpu_heap_update, whose heap is unbounded; with the default keep_arena it takes a subtree of more than 3 * max_iterations nodes.
+ * oakgpu_forest_search_kept_dev / _search_kept take oakgpu_forest_search_dev's / _search's arguments and go on in the trees the forest
+ *   holds (after an advance, or after an earlier search), as oakgpu_search_heap does on a heap (mcts.h:185-212): an initialised root whose
+ *   choice counts are the position's is left alone with all its nodes -- initial_value, root logits and priors of the outputs are then 0, no
+ *   root inference having run, so policy mode `p` sees a zero prior as in the reference; an uninitialised root (also: a tree beyond those
+ *   the last advance wrote) starts as in oakgpu_forest_search_dev; an initialised root with OTHER counts (OAKGPU_E_ROOT_MISMATCH on the
+ *   host) has its tree cleared and starts afresh, flagged in a per-tree byte (oakgpu_forest_mismatch: the last kept search's n bytes, to
+ *   host or device memory).  `iterations`, the root matrices and total_depth are this call's alone; `nodes` counts the kept ones too.
+ * oakgpu_forest_keep_stats: out = { keep_arena, slots per tree, advance launches, trees dropped } since the forest was made. */
+#define OAKGPU_FOREST_KEPT 2 /* or-ed into `contextual` of oakgpu_forest_selfplay_check: the limits are a kept forest's */
+int oakgpu_forest_create_kept(oakgpu_ctx *ctx, uint32_t max_trees, uint32_t max_iterations, int contextual, uint32_t keep_arena, oakgpu_forest **out);
+int oakgpu_forest_create_kept_check(uint32_t max_trees, uint32_t max_iterations, uint32_t keep_arena); /* host only */
+uint64_t oakgpu_forest_kept_tree_bytes(uint32_t max_iterations, uint32_t keep_arena);
+int oakgpu_forest_advance_dev(oakgpu_forest *forest, const uint8_t *i, const uint8_t *j, const uint8_t *obs, const uint32_t *src_tree, uint32_t n_new,
+                              uint8_t *kept_out);
+int oakgpu_forest_advance(oakgpu_forest *forest, const uint8_t *i, const uint8_t *j, const uint8_t *obs, const uint32_t *src_tree, uint32_t n_new,
+                          uint8_t *kept_out); /* host arrays */
+int oakgpu_forest_search_kept_dev(oakgpu_forest *forest, oakgpu_net *net, const oakgpu_search_params *params, const uint8_t *battles,
+                                  const uint8_t *durations, const uint8_t *results, const uint64_t *seeds, uint32_t n,
+                                  const oakgpu_forest_outputs *dev_out, void *trace, uint32_t trace_levels);
+int oakgpu_forest_search_kept(oakgpu_forest *forest, oakgpu_net *net, const oakgpu_search_params *params, const uint8_t *battles,
+                              const uint8_t *durations, const uint8_t *results, const uint64_t *seeds, uint32_t n, oakgpu_search_output *out,
+                              int solve_nash, uint64_t *streams_out, void *trace, uint32_t trace_levels);
+int oakgpu_forest_keep_stats(oakgpu_forest *forest, uint64_t out[4]);
+int oakgpu_forest_mismatch(oakgpu_forest *forest, uint8_t *out, uint32_t n, int to_device);
+/* the node counts of the first n trees the forest's last call (a search or an advance) left, to host or device memory; any forest */
+int oakgpu_forest_node_counts(oakgpu_forest *forest, uint32_t *out, uint32_t n, int to_device);
+
 /* ---- the path's one exchange step: per-root pre-reduction on the device + RCCL all-gather over xGMI.
  * Root-parallel MCTS shards its roots contiguously over the GPUs of a node; each rank reduces its playouts' leaf values to
  * one mean per root (oakgpu_segment_mean_dev: out[s] = mean(values[s * per_segment .. (s + 1) * per_segment))) and ONE
@@ -778,14 +823,14 @@ int oakgpu_selfplay_games(oakgpu_ctx *const *ctxs, oakgpu_net *net, const uint8_
  *   result is not terminal: search seed = splitmix64(rng), tree g of the forest search, process_output in double, get_policy for both
  *   sides, i = sample_pdf(pol1), j = sample_pdf(pol2), the frame's update, oakgpu_update_dev with (c1, c2).  One text states the rule on
  *   both sides (oak_amd/csrc/selfplay_pick.hpp); a UCB game's record equals the host loop's byte for byte, a PUCB game (device expf priors)
- *   and any game with policy_temp != 1 (device pow) are held to the forest search's own outputs.  params->search.seed, search.batch and
- *   keep_node are ignored / must be 0.
+ *   and any game with policy_temp != 1 (device pow) are held to the forest search's own outputs.  params->search.seed and search.batch
+ *   are ignored; keep_node must be 0 on a plain forest (see below for a kept one).
  *   Game length.  A game that already holds max_battle_length frames (0 = 2,048) when another is due is dropped: status
  *   OAKGPU_FSP_MAX_LENGTH, zero bytes in the stream, stored result unspecified; the call still returns 0.  A policy the minimum cut zeroes
  *   entirely stops that game alone with OAKGPU_FSP_ZERO_POLICY and no record.
  *   solve_nash = 1: the integer payoffs are formed on the device, solved on up to 16 host threads (oakgpu_solve_matrix's solver) and go
  *   back up before the pick -- what oakgpu_forest_search(solve_nash = 1) computes.  0: the nash fields are stored as 0.
- *   Refused before any launch (oakgpu_forest_selfplay_check; teams: host bytes, nullable = not checked): keep_node, an unknown mode
+ *   Refused before any launch (oakgpu_forest_selfplay_check; teams: host bytes, nullable = not checked): keep_node on a plain forest, an unknown mode
  *   letter or 'b' or more than 8 words, policy_min > 1, an 'n' word without solve_nash, a team pair that fails
  *   oakgpu_endless_battle_check (the lowest such game is named), and everything oakgpu_forest_check refuses.
  *   Independence.  Game g's record, frame count, result and status depend on its own inputs and the parameters only.
@@ -808,6 +853,16 @@ int oakgpu_forest_selfplay_records(oakgpu_forest *forest, uint8_t *stream, size_
 int oakgpu_forest_selfplay(oakgpu_forest *forest, oakgpu_net *net, const oakgpu_selfplay_params *params, const uint8_t *teams,
                            const uint64_t *battle_seeds, const uint64_t *seeds, uint32_t n, int solve_nash);
 int oakgpu_forest_selfplay_last_stats(const oakgpu_forest *forest, uint64_t out[4]);
+/* keep_node = 1 on a kept forest (oakgpu_forest_create_kept; `contextual | OAKGPU_FOREST_KEPT` in _check): the game's tree goes on from turn
+ * to turn as oakgpu_selfplay_game's heap does (generate.cc:324-333).  The pick leaves the played cell in the row, oakgpu_update_dev its
+ * observation; the next turn's compaction hands its source-row list to ONE oakgpu_forest_advance_dev, which re-roots every live tree and
+ * moves it with its row (no new host read), and the turn's search is oakgpu_forest_search_kept_dev; a retired row has no successor.  Per
+ * game, nodes_kept counts the advances that kept a subtree, minus 1 per root mismatch but never below 0 (selfplay.hip:250-256,275), gathered
+ * by game index with the other per-game results and read once at the end (_nodes_kept: n x u32, zeros after a call without keep_node).
+ * A game is the host loop's game with keep_node = 1 as long as no tree is dropped for want of room (see oakgpu_forest_advance_dev), which
+ * _keep_stats reports: out = { sum of nodes_kept, trees dropped, root mismatches, nodes carried into the turns' searches } of the last call. */
+int oakgpu_forest_selfplay_nodes_kept(oakgpu_forest *forest, uint32_t *nodes_kept, int to_device);
+int oakgpu_forest_selfplay_keep_stats(const oakgpu_forest *forest, uint64_t out[4]);
 int oakgpu_selfplay_pick_host(uint32_t m, uint32_t n, const uint64_t *visit_matrix, const double *value_matrix, uint64_t iterations,
                               const double *p1_nash, const double *p2_nash, double nash_value, const double *p1_prior, const double *p2_prior,
                               const uint8_t *p1_choices, const uint8_t *p2_choices, const char *policy_mode, double policy_temp,

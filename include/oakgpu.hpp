@@ -308,16 +308,20 @@ inline oakgpu_search_output run(Context &ctx, const Leaf &input, const Agent &ag
 // The forest search (include/oakgpu.h: oakgpu_forest_*): up to max_trees searches at once, one GPU lane per tree, every tree resident
 // on the device; tree g is TreeSearch::run(roots[g], {params, seed = seeds[g], batch = 1}) iteration for iteration.  params.bandit 0 / 1
 // (1 needs contextual = true, eval = 1 and a network), params.eval 0 / 1 / 2; the Nash fields are solved only with solve_nash.
+// keep_arena != NO_KEEP makes a kept forest (oakgpu_forest_create_kept: that many nodes a tree, 0 = 4 * max_iterations + 1): its trees go
+// on from call to call -- advance() is Heap::update of every tree, search(..., keep = true) the search on the kept trees.
 class SearchForest {
 public:
-  SearchForest(Context &ctx, uint32_t max_trees, uint32_t max_iterations, bool contextual = false) : ctx_{ctx} {
-    check(oakgpu_forest_create(ctx.get(), max_trees, max_iterations, contextual ? 1 : 0, &f_));
+  static constexpr uint32_t NO_KEEP = 0xFFFFFFFFu;
+  SearchForest(Context &ctx, uint32_t max_trees, uint32_t max_iterations, bool contextual = false, uint32_t keep_arena = NO_KEEP) : ctx_{ctx} {
+    if (keep_arena == NO_KEEP) check(oakgpu_forest_create(ctx.get(), max_trees, max_iterations, contextual ? 1 : 0, &f_));
+    else check(oakgpu_forest_create_kept(ctx.get(), max_trees, max_iterations, contextual ? 1 : 0, keep_arena, &f_));
   }
   ~SearchForest() { oakgpu_forest_destroy(ctx_.get(), f_); }
   SearchForest(const SearchForest &) = delete;
   SearchForest &operator=(const SearchForest &) = delete;
   std::vector<oakgpu_search_output> search(const oakgpu_search_params &params, const std::vector<Leaf> &roots, const std::vector<uint64_t> &seeds,
-                                           Network *net = nullptr, bool solve_nash = false, std::vector<uint64_t> *streams = nullptr) {
+                                           Network *net = nullptr, bool solve_nash = false, std::vector<uint64_t> *streams = nullptr, bool keep = false) {
     if (seeds.size() != roots.size()) throw std::runtime_error{"oakgpu: SearchForest::search: one seed per root"};
     const uint32_t n = (uint32_t)roots.size();
     std::vector<uint8_t> b((size_t)n * OAKGPU_BATTLE_SIZE), d((size_t)n * OAKGPU_DURATIONS_SIZE), r(n);
@@ -328,9 +332,27 @@ public:
     }
     std::vector<oakgpu_search_output> out(n);
     if (streams) streams->assign(n, 0);
-    check(oakgpu_forest_search(f_, net ? net->get() : nullptr, &params, b.data(), d.data(), r.data(), seeds.data(), n, out.data(), solve_nash ? 1 : 0,
-                               streams ? streams->data() : nullptr, nullptr, 0));
+    check((keep ? oakgpu_forest_search_kept : oakgpu_forest_search)(f_, net ? net->get() : nullptr, &params, b.data(), d.data(), r.data(), seeds.data(), n,
+                                                                    out.data(), solve_nash ? 1 : 0, streams ? streams->data() : nullptr, nullptr, 0));
     return out;
+  }
+  // Heap::update of every tree and its move to another row (a kept forest): new tree t continues tree src[t] (src empty: tree t) along the
+  // played cell (i[t], j[t]) and the update's 16-byte observation obs[16 t ..]; returns 1 per tree whose child is the root now, 0 = nothing kept
+  std::vector<uint8_t> advance(const std::vector<uint8_t> &i, const std::vector<uint8_t> &j, const std::vector<uint8_t> &obs, const std::vector<uint32_t> &src = {}) {
+    const uint32_t n = (uint32_t)i.size();
+    if (j.size() != n || obs.size() != (size_t)n * 16 || (!src.empty() && src.size() != n)) throw std::runtime_error{"oakgpu: SearchForest::advance: i, j, src n each, obs n x 16"};
+    std::vector<uint8_t> kept((size_t)n + 1, 0);
+    check(oakgpu_forest_advance(f_, i.data(), j.data(), obs.data(), src.empty() ? nullptr : src.data(), n, kept.data()));
+    kept.resize(n);
+    return kept;
+  }
+  // the same over device arrays (src_tree nullable), kept_out on the device too
+  void advance_dev(const uint8_t *i, const uint8_t *j, const uint8_t *obs, const uint32_t *src_tree, uint32_t n_new, uint8_t *kept_out) {
+    check(oakgpu_forest_advance_dev(f_, i, j, obs, src_tree, n_new, kept_out));
+  }
+  void search_kept_dev(const oakgpu_search_params &params, const uint8_t *battles, const uint8_t *durations, const uint8_t *results, const uint64_t *seeds,
+                       uint32_t n, const oakgpu_forest_outputs &dev_out, Network *net = nullptr) {
+    check(oakgpu_forest_search_kept_dev(f_, net ? net->get() : nullptr, &params, battles, durations, results, seeds, n, &dev_out, nullptr, 0));
   }
   // the same over arrays the caller holds on the device (dev_out: device arrays too)
   void search_dev(const oakgpu_search_params &params, const uint8_t *battles, const uint8_t *durations, const uint8_t *results, const uint64_t *seeds,
@@ -362,9 +384,11 @@ public:
     std::vector<uint32_t> n_frames;
     std::vector<uint8_t> results, status;
     std::array<uint64_t, 4> stats{}; // turns looped, rows searched summed over turns, compactions, host reads
+    std::vector<uint32_t> nodes_kept;      // params.keep_node: per game, the updates that found their child (oakgpu_selfplay_params::nodes_kept); else zeros
+    std::array<uint64_t, 4> keep_stats{};  // params.keep_node: sum of nodes_kept, trees dropped for want of room, root mismatches, nodes carried in
   };
   explicit ForestSelfplay(SearchForest &forest) : forest_{forest} {}
-  // teams: n x 60 bytes; params.search.seed / batch and params.seed are ignored, keep_node must be 0
+  // teams: n x 60 bytes; params.search.seed / batch and params.seed are ignored; keep_node = 1 needs a forest made with keep_arena
   Result play(const oakgpu_selfplay_params &params, const std::vector<uint8_t> &teams, const std::vector<uint64_t> &battle_seeds,
               const std::vector<uint64_t> &seeds, Network *net = nullptr, bool solve_nash = true) {
     const uint32_t n = (uint32_t)seeds.size();
@@ -379,6 +403,10 @@ public:
     check(oakgpu_forest_selfplay_records(forest_.get(), bytes ? out.stream.data() : &none, bytes, &bytes, out.offsets.data(), out.n_frames.data(),
                                          out.results.data(), out.status.data(), 0));
     check(oakgpu_forest_selfplay_last_stats(forest_.get(), out.stats.data()));
+    out.nodes_kept.assign((size_t)n + 1, 0);
+    check(oakgpu_forest_selfplay_nodes_kept(forest_.get(), out.nodes_kept.data(), 0));
+    out.nodes_kept.resize(n);
+    check(oakgpu_forest_selfplay_keep_stats(forest_.get(), out.keep_stats.data()));
     return out;
   }
 

@@ -36,6 +36,9 @@ SYMBOLS = [
     "oakgpu_forest_selfplay_check", "oakgpu_forest_selfplay_dev", "oakgpu_forest_selfplay_records", "oakgpu_forest_selfplay", "oakgpu_forest_selfplay_last_stats",
     "oakgpu_selfplay_pick_host",
     "oakgpu_forest_match_check", "oakgpu_forest_match_dev", "oakgpu_forest_match", "oakgpu_forest_match_last_stats", "oakgpu_match_pick_host",
+    "oakgpu_forest_create_kept", "oakgpu_forest_create_kept_check", "oakgpu_forest_kept_tree_bytes", "oakgpu_forest_advance_dev", "oakgpu_forest_advance",
+    "oakgpu_forest_search_kept_dev", "oakgpu_forest_search_kept", "oakgpu_forest_keep_stats", "oakgpu_forest_mismatch", "oakgpu_forest_node_counts",
+    "oakgpu_forest_selfplay_nodes_kept", "oakgpu_forest_selfplay_keep_stats",
 ]
 
 
@@ -323,6 +326,17 @@ def load():
     lib.oakgpu_forest_search.argtypes = [vp, vp, C.POINTER(SearchParams), vp, vp, vp, vp, u32, C.POINTER(SearchOutput), i32, vp, vp, u32]
     lib.oakgpu_forest_nodes.argtypes = [vp, u32, u32, u32, C.POINTER(ForestNode)]
     lib.oakgpu_forest_last_stats.argtypes = [vp, C.POINTER(u64 * 4)]
+    lib.oakgpu_forest_create_kept.argtypes = [vp, u32, u32, i32, u32, C.POINTER(vp)]
+    lib.oakgpu_forest_create_kept_check.argtypes = [u32, u32, u32]
+    lib.oakgpu_forest_kept_tree_bytes.argtypes = [u32, u32]
+    lib.oakgpu_forest_kept_tree_bytes.restype = u64
+    lib.oakgpu_forest_advance_dev.argtypes = [vp, vp, vp, vp, vp, u32, vp]
+    lib.oakgpu_forest_advance.argtypes = [vp, vp, vp, vp, vp, u32, vp]
+    lib.oakgpu_forest_search_kept_dev.argtypes = lib.oakgpu_forest_search_dev.argtypes
+    lib.oakgpu_forest_search_kept.argtypes = lib.oakgpu_forest_search.argtypes
+    lib.oakgpu_forest_keep_stats.argtypes = [vp, C.POINTER(u64 * 4)]
+    lib.oakgpu_forest_mismatch.argtypes = [vp, vp, u32, i32]
+    lib.oakgpu_forest_node_counts.argtypes = [vp, vp, u32, i32]
     lib.oakgpu_search_stream.argtypes = [vp, C.POINTER(u64)]
     lib.oakgpu_agent_params.argtypes = [vp, C.POINTER(Agent), u32, u64, C.POINTER(SearchParams), C.POINTER(vp)]
     lib.oakgpu_forest_selfplay_check.argtypes = [u32, u32, i32, C.POINTER(SelfplayParams), i32, u32, vp, i32]
@@ -330,6 +344,8 @@ def load():
     lib.oakgpu_forest_selfplay_records.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, vp, vp, i32]
     lib.oakgpu_forest_selfplay.argtypes = [vp, vp, C.POINTER(SelfplayParams), vp, vp, vp, u32, i32]
     lib.oakgpu_forest_selfplay_last_stats.argtypes = [vp, C.POINTER(u64 * 4)]
+    lib.oakgpu_forest_selfplay_nodes_kept.argtypes = [vp, vp, i32]
+    lib.oakgpu_forest_selfplay_keep_stats.argtypes = [vp, C.POINTER(u64 * 4)]
     lib.oakgpu_selfplay_pick_host.argtypes = [u32, u32, vp, vp, u64, vp, vp, C.c_double, vp, vp, vp, vp, C.c_char_p, C.c_double, C.c_double, C.POINTER(u64),
                                               C.POINTER(C.c_double), vp, vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.POINTER(u32)]
     lib.oakgpu_forest_match_check.argtypes = [u32, u32, i32, C.POINTER(ForestMatchParams), u32]

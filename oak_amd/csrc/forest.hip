@@ -19,6 +19,15 @@
 // k_forest_level(d), which resolves the edge just taken, selects at the child of a continuing lane (c1 / c2 = 0xFF for a finished
 // one) and appends to the lane's path; the host reads that level's 4-byte live count and stops at 0.  Then the evaluator over all n
 // rows and k_forest_backup: init (+ priors) of a new leaf, update along the path, the root matrices, the trace record.
+//
+// Kept forests (oakgpu_forest_create_kept; generate's --keep-node, Heap::update in search.cc:27-52).  Such a forest owns its node arenas
+// and edge tables twice, front and back, with `arena` = keep_arena nodes per tree.  k_forest_advance, one wave per NEW tree t, reads tree
+// src_tree[t] of the front copy and writes tree t of the back copy: the child along the played (i, j, observation) becomes node 0, its
+// subtree is kept byte for byte, the rest is left behind; then front and back swap.  A node id is its creation order and a child is
+// created after its parent, so once every node's parent is known (one scan of the tree's own table for live stamps) "is in the subtree"
+// resolves in one ascending pass over ids, 64 at a time; the new id of a kept node is the count of kept nodes below it.  The kept edges
+// are re-inserted with renumbered ends under a new stamp.  The kept form of the search (k_forest_begin with keep = 1) leaves an
+// initialised root with the position's choice counts alone and runs on under the stamp the advance wrote.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -46,6 +55,7 @@ static_assert(offsetof(Bandit, priors) == offsetof(oakgpu_forest_bandit, priors)
               offsetof(Bandit, k) == offsetof(oakgpu_forest_bandit, k), "oakgpu_forest_bandit mirrors Bandit");
 struct FEdge { uint64_t obs0, obs1; uint32_t parent, child; uint8_t i, j; uint16_t gen; };
 static_assert(sizeof(FEdge) == 32, "one edge slot is 32 bytes");
+static_assert(offsetof(FEdge, i) == 24 && offsetof(FEdge, j) == 25 && offsetof(FEdge, gen) == 26, "i, j and the stamp share the slot's dword 6");
 static_assert(sizeof(oakgpu_forest_trace_head) == 88 && sizeof(oakgpu_forest_trace_level) == 8, "trace record layout");
 
 enum : uint8_t { ST_WALK = 0, ST_TERMINAL = 1, ST_LEAF = 2, ST_DEAD = 3 };
@@ -159,10 +169,17 @@ struct BeginArgs {
   uint64_t *total_depth;
   BanditParams P;
   oakgpu_forest_outputs out;
+  // the kept form (keep = 1): trees below `valid` hold what the last advance or kept search left; the tree's table, to clear after a mismatch
+  uint32_t keep, valid, slots, gen;
+  FEdge *edges;
+  uint8_t *mismatch;   // per tree: 1 = an initialised root with other choice counts than the position's (OAKGPU_E_ROOT_MISMATCH on the host)
+  uint32_t *carried;   // per tree: nodes the call started with (0 = a fresh tree)
 };
 
 // Start of a call: the tree's stream (search_host.hip: slot 0, lane 0 -- the first splitmix64 output of the seed, never zero), the
-// root's stats.init(m, n) + priors (mcts.h:177-210), the zeroed outputs.
+// root's stats.init(m, n) + priors (mcts.h:177-210), the zeroed outputs.  The kept form (mcts.h:185-212, search_host.hip's heap): an
+// initialised root with the position's m and n stays as it is with all its nodes, and the call's initial_value, logits and priors are
+// zeros (no root inference ran); a root with other counts starts afresh after the lane has cleared its own tree's live slots.
 __global__ __launch_bounds__(FBLOCK) void k_forest_begin(BeginArgs a) {
   const uint32_t lane = blockIdx.x * FBLOCK + threadIdx.x;
   if (lane >= a.n) return;
@@ -172,9 +189,26 @@ __global__ __launch_bounds__(FBLOCK) void k_forest_begin(BeginArgs a) {
   a.prng[lane] = (z ^ (z >> 31)) | 1;
   const uint8_t m = a.root_cnt1[lane], n = a.root_cnt2[lane];
   FNode &root = a.nodes[(size_t)lane * a.arena];
-  root.p1.init(m, a.P.kind);
-  root.p2.init(n, a.P.kind);
-  a.n_nodes[lane] = 1;
+  bool fresh = true;
+  if (a.keep) {
+    uint8_t other = 0;
+    uint32_t had = 0;
+    if (lane < a.valid && a.n_nodes[lane] != 0 && root.p1.is_init()) {
+      if (root.p1.k == m && root.p2.k == n) { fresh = false; had = a.n_nodes[lane]; }
+      else {
+        other = 1;
+        FEdge *tab = a.edges + (size_t)lane * a.slots;
+        for (uint32_t s = 0; s < a.slots; ++s) if (tab[s].gen == (uint16_t)a.gen) tab[s].gen = 0;
+      }
+    }
+    a.mismatch[lane] = other;
+    a.carried[lane] = had;
+  }
+  if (fresh) {
+    root.p1.init(m, a.P.kind);
+    root.p2.init(n, a.P.kind);
+    a.n_nodes[lane] = 1;
+  }
   a.status[lane] = ST_WALK;
   a.total_depth[lane] = 0;
   a.out.m[lane] = m; a.out.n[lane] = n;
@@ -183,7 +217,7 @@ __global__ __launch_bounds__(FBLOCK) void k_forest_begin(BeginArgs a) {
   double *lg[2] = {a.out.p1_logit + (size_t)lane * 9, a.out.p2_logit + (size_t)lane * 9}, *pr[2] = {a.out.p1_prior + (size_t)lane * 9, a.out.p2_prior + (size_t)lane * 9};
   for (int s = 0; s < 2; ++s) for (int q = 0; q < 9; ++q) { lg[s][q] = 0.0; pr[s][q] = 0.0; }
   a.out.initial_value[lane] = 0.0;
-  if (a.pucb) {
+  if (a.pucb && fresh) {
     const float *l[2] = {a.l1 + (size_t)lane * 9, a.l2 + (size_t)lane * 9};
     root.p1.set_logits(a.P, l[0]);
     root.p2.set_logits(a.P, l[1]);
@@ -273,6 +307,132 @@ __global__ __launch_bounds__(FBLOCK) void k_forest_finish(uint32_t n, uint64_t i
   out.stream[lane] = prng[lane];
 }
 
+struct AdvanceArgs {
+  const FNode *src_nodes;      // the front copy: read only
+  const FEdge *src_edges;
+  const uint32_t *src_n_nodes;
+  FNode *dst_nodes;            // the back copy: tree t is written by wave t alone
+  FEdge *dst_edges;
+  uint32_t *dst_n_nodes;
+  uint32_t *map;               // [new tree][arena]: a node's parent, then its new id (NONE = left behind)
+  const uint8_t *i, *j, *obs;  // per new tree: the played cell and the update's 16-byte observation
+  const uint32_t *src_tree;    // per new tree: the front tree it continues; null = the same row
+  uint8_t *kept_out;
+  uint32_t *dropped;           // trees dropped for want of room, since the forest was made
+  uint32_t arena, slots, gen_old, gen_new, n_new, valid, max_iterations;
+};
+
+// Heap::update(i, j, obs) of every tree (search.cc:27-52; oakgpu_heap_update's rule), and the move to another row: one wave per new tree.
+// Every loop is bounded by `slots`, `arena` or 64; the only atomics are the wave's own claims of slots in its own back table (and the
+// drop counter, when a tree is dropped).
+__global__ __launch_bounds__(64) void k_forest_advance(AdvanceArgs a) {
+  const uint32_t t = blockIdx.x, lane = threadIdx.x;
+  if (t >= a.n_new) return;
+  FNode *dn = a.dst_nodes + (size_t)t * a.arena;
+  FEdge *dt = a.dst_edges + (size_t)t * a.slots;
+  const uint32_t src = a.src_tree ? a.src_tree[t] : t;
+  uint32_t nn = src < a.valid ? a.src_n_nodes[src] : 0; // 0: never searched
+  if (nn > a.arena) nn = a.arena;
+  const size_t from = src < a.valid ? src : 0;
+  const FNode *sn = a.src_nodes + from * a.arena;
+  const FEdge *st = a.src_edges + from * a.slots;
+  const uint32_t mask = a.slots - 1;
+  const uint16_t live = (uint16_t)a.gen_old, stamp = (uint16_t)a.gen_new;
+  uint32_t child = NONE;
+  if (nn != 0 && sn[0].p1.k != 0) { // the edge (root, i, j, obs), every lane the same probes
+    const uint32_t i = a.i[t], j = a.j[t];
+    uint64_t o0, o1;
+    memcpy(&o0, a.obs + (size_t)t * 16, 8);
+    memcpy(&o1, a.obs + (size_t)t * 16 + 8, 8);
+    uint32_t s = (uint32_t)edge_hash(0, i, j, o0, o1) & mask;
+    for (uint32_t probe = 0; probe < a.slots; ++probe, s = (s + 1) & mask) {
+      const FEdge &e = st[s];
+      if (e.gen != live) break;
+      if (e.parent == 0 && e.i == i && e.j == j && e.obs0 == o0 && e.obs1 == o1) { child = e.child; break; }
+    }
+    if (child == 0 || child >= nn) child = NONE;
+  }
+  child = __builtin_amdgcn_readfirstlane(child); // (the same in every lane: the barriers below are reached by all or none)
+  uint32_t kept = 0;
+  if (child != NONE) {
+    uint32_t *map = a.map + (size_t)t * a.arena;
+    for (uint32_t id = lane; id < nn; id += 64) map[id] = NONE;
+    __syncthreads();
+    for (uint32_t s = lane; s < a.slots; s += 64) { // every node but the root is the child of exactly one live edge
+      const FEdge &e = st[s];
+      if (e.gen == live && e.child < nn) map[e.child] = e.parent;
+    }
+    __syncthreads();
+    // ascending over ids from the child on, 64 at a time: kept = the parent is kept.  A parent in an earlier chunk is read from the map (it
+    // holds new ids there already); a parent in the same chunk sits in a lower lane and is reached by pointer jumping, 6 rounds for 64 lanes.
+    for (uint32_t base = child; base < nn; base += 64) {
+      const uint32_t id = base + lane;
+      const bool in = id < nn;
+      const uint32_t p = in ? map[id] : NONE;
+      int state = 0; // 0 left behind, 1 kept, 2 waits for a lower lane
+      uint32_t anc = 0;
+      if (in) {
+        if (id == child) state = 1;
+        else if (p == NONE || p < child || p >= id) state = 0;
+        else if (p == child) state = 1;
+        else if (p < base) state = map[p] != NONE;
+        else { state = 2; anc = p - base; }
+      }
+#pragma unroll
+      for (int r = 0; r < 6; ++r) {
+        const int s2 = __shfl(state, (int)anc);
+        const uint32_t a2 = __shfl(anc, (int)anc);
+        if (state == 2) { if (s2 != 2) state = s2; else anc = a2; }
+      }
+      const bool k = state == 1;
+      const unsigned long long m = __ballot(k);
+      const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+      if (in) map[id] = k ? kept + below : NONE;
+      kept += (uint32_t)__popcll(m);
+      __syncthreads();
+    }
+  }
+  // room for a whole call below the kept nodes, or the tree is dropped (the host's heap is unbounded: the one departure from it)
+  const bool drop = child != NONE && (uint64_t)kept + a.max_iterations > a.arena;
+  const bool keep = child != NONE && !drop;
+  if (keep) {
+    const uint32_t *map = a.map + (size_t)t * a.arena;
+    for (uint32_t base = child; base < nn; base += 64) { // the records, 14 x 16 bytes each, 64 nodes a round
+      const uint32_t id = base + lane;
+      const uint32_t to = id < nn ? map[id] : NONE;
+#pragma unroll 2
+      for (uint32_t q = 0; q < 14; ++q) {
+        const uint32_t idx = q * 64 + lane, node = idx / 14, part = idx - node * 14;
+        const uint32_t dst = __shfl(to, (int)node);
+        if (dst != NONE) ((uint4 *)(dn + dst))[part] = ((const uint4 *)(sn + base + node))[part];
+      }
+    }
+    for (uint32_t s0 = lane; s0 < a.slots; s0 += 64) { // the edges between kept nodes, renumbered, under the new stamp
+      const FEdge e = st[s0];
+      if (e.gen != live || e.child >= nn || e.child <= child || e.parent < child || e.parent >= e.child) continue;
+      const uint32_t nc = map[e.child], np = map[e.parent];
+      if (nc == NONE || np == NONE) continue;
+      const uint32_t word = (uint32_t)e.i | (uint32_t)e.j << 8 | (uint32_t)stamp << 16; // i, j, gen: one dword of the slot, claimed as one
+      uint32_t s = (uint32_t)edge_hash(np, e.i, e.j, e.obs0, e.obs1) & mask;
+      for (uint32_t probe = 0; probe < a.slots; ++probe, s = (s + 1) & mask) {
+        uint32_t *w = (uint32_t *)(dt + s) + offsetof(FEdge, i) / 4;
+        const uint32_t seen = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((uint16_t)(seen >> 16) == stamp) continue; // taken by another lane of this wave
+        if (atomicCAS(w, seen, word) != seen) continue; // lost the slot to one
+        FEdge &d = dt[s];
+        d.obs0 = e.obs0; d.obs1 = e.obs1; d.parent = np; d.child = nc;
+        break;
+      }
+    }
+  }
+  if (lane == 0) {
+    if (!keep) { dn[0].p1.k = 0; dn[0].p2.k = 0; } // `node = {}`: an empty tree, the next search initialises its root
+    a.dst_n_nodes[t] = keep ? kept : 1;
+    a.kept_out[t] = keep ? 1 : 0;
+    if (drop) atomicAdd(a.dropped, 1u);
+  }
+}
+
 #define RC(x) do { int _r = (x); if (_r) return _r; } while (0)
 } // namespace
 
@@ -298,6 +458,15 @@ struct oakgpu_forest {
   uint8_t *stage = nullptr, *trace_stage = nullptr;
   size_t trace_stage_bytes = 0;
   uint64_t stats[4] = {0, 0, 0, 0};
+  // a kept forest (oakgpu_forest_create_kept): the back copy of arenas, tables and node counts that k_forest_advance writes and that then
+  // becomes the front (nodes / edges / n_nodes above); `valid` = the trees of the front copy that hold what a call left
+  bool kept = false;
+  FNode *nodes_back = nullptr;
+  FEdge *edges_back = nullptr;
+  uint32_t *n_nodes_back = nullptr, *map = nullptr, *carried = nullptr, *dropped = nullptr, *adv_src = nullptr;
+  uint8_t *mismatch = nullptr, *adv_in = nullptr;
+  uint32_t valid = 0;
+  uint64_t advances = 0;
   // the game loop's workspace (forestplay.hip), freed with the forest
   void *attachment = nullptr;
   void (*attachment_free)(void *) = nullptr;
@@ -347,6 +516,10 @@ oakgpu_ctx *oakgpu_forest_ctx(const oakgpu_forest *f) { return f->ctx; }
 void oakgpu_forest_limits(const oakgpu_forest *f, uint32_t *max_trees, uint32_t *max_iterations, int *contextual) {
   *max_trees = f->max_trees; *max_iterations = f->max_iterations; *contextual = f->contextual ? 1 : 0;
 }
+int oakgpu_forest_is_kept(const oakgpu_forest *f) { return f->kept ? 1 : 0; }
+void oakgpu_forest_keep_arrays(const oakgpu_forest *f, const uint8_t **mismatch, const uint32_t **carried, const uint32_t **dropped) {
+  *mismatch = f->mismatch; *carried = f->carried; *dropped = f->dropped;
+}
 void *oakgpu_forest_attachment(const oakgpu_forest *f) { return f->attachment; }
 void oakgpu_forest_set_attachment(oakgpu_forest *f, void *p, void (*dtor)(void *)) { f->attachment = p; f->attachment_free = dtor; }
 void *oakgpu_forest_match_attachment(const oakgpu_forest *f) { return f->match_attachment; }
@@ -381,18 +554,49 @@ int oakgpu_forest_check(uint32_t max_trees, uint32_t max_iterations, int context
   return 0;
 }
 
-int oakgpu_forest_create(oakgpu_ctx *ctx, uint32_t max_trees, uint32_t max_iterations, int contextual, oakgpu_forest **out) {
-  if (!ctx || !out) return oakgpu_fail_msg("oakgpu_forest_create: null argument");
-  if (max_trees == 0 || max_iterations == 0 || max_iterations > (1u << 24)) return oakgpu_fail_msg("oakgpu_forest_create: max_trees >= 1, max_iterations in 1..2^24");
+static uint32_t forest_slots(uint32_t arena) {
+  uint32_t slots = 16;
+  while (slots < 2 * arena) slots *= 2;
+  return slots;
+}
+
+uint64_t oakgpu_forest_kept_tree_bytes(uint32_t max_iterations, uint32_t keep_arena) {
+  if (max_iterations == 0 || max_iterations > (1u << 24)) return 0;
+  if (keep_arena == 0) keep_arena = 4 * max_iterations + 1;
+  if (keep_arena < max_iterations + 1 || keep_arena > (1u << 27)) return 0;
+  return 2 * ((uint64_t)keep_arena * sizeof(FNode) + (uint64_t)forest_slots(keep_arena) * sizeof(FEdge));
+}
+
+// both creates: arena = 0 makes the plain forest (max_iterations + 1 nodes a tree, one copy), else a kept one of `arena` nodes a tree, two copies
+static int forest_make(const char *who, oakgpu_ctx *ctx, uint32_t max_trees, uint32_t max_iterations, int contextual, uint32_t keep_arena, oakgpu_forest **out) {
   RC(oakgpu_ctx_enter(ctx));
   oakgpu_forest *f = new oakgpu_forest();
   f->ctx = ctx; f->device = oakgpu_ctx_device(ctx); f->max_trees = max_trees; f->max_iterations = max_iterations; f->contextual = contextual != 0;
-  f->arena = max_iterations + 1;
-  f->slots = 16;
-  while (f->slots < 2 * f->arena) f->slots *= 2;
+  f->kept = keep_arena != 0;
+  f->arena = f->kept ? keep_arena : max_iterations + 1;
+  f->slots = forest_slots(f->arena);
   const size_t T = max_trees;
+  auto trees = [&]() -> int { // the arenas and tables; a kept forest's failure names what was asked for
+    if (!f->kept) { RC(f->get(f->nodes, T * f->arena)); RC(f->get(f->edges, T * f->slots)); return 0; }
+    const int rc = [&]() -> int {
+      RC(f->get(f->nodes, T * f->arena)); RC(f->get(f->edges, T * f->slots)); RC(f->get(f->nodes_back, T * f->arena)); RC(f->get(f->edges_back, T * f->slots));
+      RC(f->get(f->map, T * f->arena));
+      return 0;
+    }();
+    if (rc) {
+      const unsigned long long per = oakgpu_forest_kept_tree_bytes(max_iterations, keep_arena) + (unsigned long long)f->arena * 4;
+      char msg[320];
+      snprintf(msg, sizeof msg, "%s: out of device memory: %u trees of %u nodes ask for %llu bytes (%llu a tree: two copies of %u x 224-byte nodes and %u x 32-byte slots, and the advance's map)",
+               who, max_trees, f->arena, per * T, per, f->arena, f->slots);
+      return oakgpu_fail_msg(msg);
+    }
+    RC(f->get(f->n_nodes_back, T)); RC(f->get(f->carried, T)); RC(f->get(f->dropped, 4)); RC(f->get(f->adv_src, T)); RC(f->get(f->mismatch, T)); RC(f->get(f->adv_in, T * 19));
+    HIPCHK(hipMemset(f->edges_back, 0, T * f->slots * sizeof(FEdge)));
+    HIPCHK(hipMemset(f->n_nodes_back, 0, T * 4)); HIPCHK(hipMemset(f->dropped, 0, 16)); HIPCHK(hipMemset(f->mismatch, 0, T));
+    return 0;
+  };
   auto all = [&]() -> int {
-    RC(f->get(f->nodes, T * f->arena)); RC(f->get(f->edges, T * f->slots));
+    RC(trees());
     RC(f->get(f->b, T * 384)); RC(f->get(f->d, T * 8)); RC(f->get(f->r, T)); RC(f->get(f->c1, T)); RC(f->get(f->c2, T)); RC(f->get(f->act, T * 16));
     RC(f->get(f->ch1, T * 9)); RC(f->get(f->cnt1, T)); RC(f->get(f->ch2, T * 9)); RC(f->get(f->cnt2, T)); RC(f->get(f->rout, T));
     RC(f->get(f->root_ch1, T * 9)); RC(f->get(f->root_cnt1, T)); RC(f->get(f->root_ch2, T * 9)); RC(f->get(f->root_cnt2, T)); RC(f->get(f->status, T));
@@ -401,11 +605,31 @@ int oakgpu_forest_create(oakgpu_ctx *ctx, uint32_t max_trees, uint32_t max_itera
     if (f->contextual) { RC(f->get(f->l1, T * 9)); RC(f->get(f->l2, T * 9)); }
     HIPCHK(hipHostMalloc((void **)&f->h_live, 16, hipHostMallocDefault));
     HIPCHK(hipMemset(f->edges, 0, T * f->slots * sizeof(FEdge))); // stamp 0 = free; calls stamp from 1
+    if (f->kept) HIPCHK(hipMemset(f->n_nodes, 0, T * 4));
     return 0;
   };
   if (int rc = all()) { f->release(); delete f; return rc; }
   *out = f;
   return 0;
+}
+
+int oakgpu_forest_create(oakgpu_ctx *ctx, uint32_t max_trees, uint32_t max_iterations, int contextual, oakgpu_forest **out) {
+  if (!ctx || !out) return oakgpu_fail_msg("oakgpu_forest_create: null argument");
+  if (max_trees == 0 || max_iterations == 0 || max_iterations > (1u << 24)) return oakgpu_fail_msg("oakgpu_forest_create: max_trees >= 1, max_iterations in 1..2^24");
+  return forest_make("oakgpu_forest_create", ctx, max_trees, max_iterations, contextual, 0, out);
+}
+
+int oakgpu_forest_create_kept_check(uint32_t max_trees, uint32_t max_iterations, uint32_t keep_arena) {
+  if (max_trees == 0 || max_iterations == 0 || max_iterations > (1u << 24)) return oakgpu_fail_msg("oakgpu_forest_create_kept: max_trees >= 1, max_iterations in 1..2^24");
+  if (keep_arena != 0 && keep_arena < max_iterations + 1) return oakgpu_fail_msg("oakgpu_forest_create_kept: keep_arena must be at least max_iterations + 1 (0 = 4 * max_iterations + 1)");
+  if (keep_arena > (1u << 27)) return oakgpu_fail_msg("oakgpu_forest_create_kept: keep_arena above 2^27");
+  return 0;
+}
+
+int oakgpu_forest_create_kept(oakgpu_ctx *ctx, uint32_t max_trees, uint32_t max_iterations, int contextual, uint32_t keep_arena, oakgpu_forest **out) {
+  if (!ctx || !out) return oakgpu_fail_msg("oakgpu_forest_create_kept: null argument");
+  RC(oakgpu_forest_create_kept_check(max_trees, max_iterations, keep_arena));
+  return forest_make("oakgpu_forest_create_kept", ctx, max_trees, max_iterations, contextual, keep_arena ? keep_arena : 4 * max_iterations + 1, out);
 }
 
 void oakgpu_forest_destroy(oakgpu_ctx *ctx, oakgpu_forest *f) {
@@ -424,9 +648,11 @@ int oakgpu_forest_last_stats(const oakgpu_forest *f, uint64_t out[4]) {
   return 0;
 }
 
-int oakgpu_forest_search_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_search_params *prm, const uint8_t *battles, const uint8_t *durations,
-                             const uint8_t *results, const uint64_t *seeds, uint32_t n, const oakgpu_forest_outputs *o, void *trace, uint32_t trace_levels) {
+// the body of both device searches: keep = the kept form (an initialised root goes on; the stamp is the one the advance wrote)
+static int forest_search_body(oakgpu_forest *f, oakgpu_net *net, const oakgpu_search_params *prm, const uint8_t *battles, const uint8_t *durations,
+                              const uint8_t *results, const uint64_t *seeds, uint32_t n, const oakgpu_forest_outputs *o, void *trace, uint32_t trace_levels, bool keep) {
   if (!f || !prm || !battles || !durations || !results || !seeds || !o) return oakgpu_fail_msg("oakgpu_forest_search: null argument");
+  if (keep && !f->kept) return oakgpu_fail_msg("oakgpu_forest_search_kept: the forest was created without keep (oakgpu_forest_create_kept makes one that keeps its trees)");
   if (!o->m || !o->n || !o->p1_choices || !o->p2_choices || !o->visit_matrix || !o->value_matrix || !o->iterations || !o->nodes || !o->total_depth ||
       !o->initial_value || !o->p1_logit || !o->p2_logit || !o->p1_prior || !o->p2_prior || !o->stream)
     return oakgpu_fail_msg("oakgpu_forest_search: every output array is required");
@@ -456,9 +682,13 @@ int oakgpu_forest_search_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_sea
     RC(dev_alloc(f->path_node, (size_t)f->max_trees * max_depth)); RC(dev_alloc(f->path_i, (size_t)f->max_trees * max_depth)); RC(dev_alloc(f->path_j, (size_t)f->max_trees * max_depth));
     f->path_levels = max_depth;
   }
-  if (++f->gen > 0xFFFFu) { // the stamp wrapped: one real clear
-    HIPCHK(hipMemsetAsync(f->edges, 0, (size_t)f->max_trees * f->slots * sizeof(FEdge), stream));
-    f->gen = 1;
+  if (!keep || f->gen == 0) {
+    if (++f->gen > 0xFFFFu) { // the stamp wrapped: one real clear, of both copies
+      HIPCHK(hipMemsetAsync(f->edges, 0, (size_t)f->max_trees * f->slots * sizeof(FEdge), stream));
+      if (f->edges_back) HIPCHK(hipMemsetAsync(f->edges_back, 0, (size_t)f->max_trees * f->slots * sizeof(FEdge), stream));
+      f->gen = 1;
+    }
+    f->valid = 0; // every tree of the new stamp is empty
   }
   f->last_n = 0;
   const dim3 grid((n + FBLOCK - 1) / FBLOCK), block(FBLOCK);
@@ -475,6 +705,7 @@ int oakgpu_forest_search_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_sea
     a.root_cnt1 = f->root_cnt1; a.root_cnt2 = f->root_cnt2; a.root_ch1 = f->root_ch1; a.root_ch2 = f->root_ch2;
     a.values = f->values; a.l1 = f->l1; a.l2 = f->l2; a.prng = f->prng; a.n_nodes = f->n_nodes; a.status = f->status; a.total_depth = f->total_depth;
     a.P = BP; a.out = *o;
+    a.keep = keep; a.valid = f->valid; a.slots = f->slots; a.gen = f->gen; a.edges = f->edges; a.mismatch = f->mismatch; a.carried = f->carried;
     hipLaunchKernelGGL(k_forest_begin, grid, block, 0, stream, a);
     HIPCHK(hipGetLastError());
   }
@@ -527,15 +758,28 @@ int oakgpu_forest_search_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_sea
   HIPCHK(hipStreamSynchronize(stream));
   f->stats[0] = iterations; f->stats[1] = levels_stepped; f->stats[2] = launches; f->stats[3] = polls;
   f->last_n = n;
+  f->valid = keep ? std::max(f->valid, n) : n;
   if (f->h_live[1] & ERR_ARENA_FULL) return oakgpu_fail_msg("oakgpu_forest_search: a tree's node arena is full");
   if (f->h_live[1] & ERR_TABLE_FULL) return oakgpu_fail_msg("oakgpu_forest_search: a tree's edge table is full");
   return 0;
 }
 
-int oakgpu_forest_search(oakgpu_forest *f, oakgpu_net *net, const oakgpu_search_params *prm, const uint8_t *battles, const uint8_t *durations,
-                         const uint8_t *results, const uint64_t *seeds, uint32_t n, oakgpu_search_output *out, int solve_nash, uint64_t *streams_out,
-                         void *trace, uint32_t trace_levels) {
+int oakgpu_forest_search_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_search_params *prm, const uint8_t *battles, const uint8_t *durations,
+                             const uint8_t *results, const uint64_t *seeds, uint32_t n, const oakgpu_forest_outputs *o, void *trace, uint32_t trace_levels) {
+  return forest_search_body(f, net, prm, battles, durations, results, seeds, n, o, trace, trace_levels, false);
+}
+
+int oakgpu_forest_search_kept_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_search_params *prm, const uint8_t *battles, const uint8_t *durations,
+                                  const uint8_t *results, const uint64_t *seeds, uint32_t n, const oakgpu_forest_outputs *o, void *trace, uint32_t trace_levels) {
+  return forest_search_body(f, net, prm, battles, durations, results, seeds, n, o, trace, trace_levels, true);
+}
+
+// the body of both host-array searches
+static int forest_search_host(oakgpu_forest *f, oakgpu_net *net, const oakgpu_search_params *prm, const uint8_t *battles, const uint8_t *durations,
+                              const uint8_t *results, const uint64_t *seeds, uint32_t n, oakgpu_search_output *out, int solve_nash, uint64_t *streams_out,
+                              void *trace, uint32_t trace_levels, bool keep) {
   if (!f || !prm || !battles || !durations || !results || !seeds || !out) return oakgpu_fail_msg("oakgpu_forest_search: null argument");
+  if (keep && !f->kept) return oakgpu_fail_msg("oakgpu_forest_search_kept: the forest was created without keep (oakgpu_forest_create_kept makes one that keeps its trees)");
   RC(oakgpu_forest_check(f->max_trees, f->max_iterations, f->contextual, prm, net != nullptr, n, results, trace != nullptr, trace_levels));
   if (n == 0) return 0;
   const auto t0 = std::chrono::high_resolution_clock::now();
@@ -559,7 +803,7 @@ int oakgpu_forest_search(oakgpu_forest *f, oakgpu_net *net, const oakgpu_search_
   HIPCHK(hipStreamSynchronize(stream));
   oakgpu_forest_outputs o;
   carve_outputs(d_o, n, &o);
-  RC(oakgpu_forest_search_dev(f, net, prm, d_b, d_d, d_r, (const uint64_t *)d_s, n, &o, trace ? f->trace_stage : nullptr, trace_levels));
+  RC(forest_search_body(f, net, prm, d_b, d_d, d_r, (const uint64_t *)d_s, n, &o, trace ? f->trace_stage : nullptr, trace_levels, keep));
   std::vector<uint8_t> h(outputs_bytes(n));
   HIPCHK(hipMemcpy(h.data(), d_o, h.size(), hipMemcpyDeviceToHost));
   if (trace) HIPCHK(hipMemcpy(trace, f->trace_stage, trace_bytes, hipMemcpyDeviceToHost));
@@ -583,6 +827,102 @@ int oakgpu_forest_search(oakgpu_forest *f, oakgpu_net *net, const oakgpu_search_
     double nv = 0;
     if (solve_nash && oak_nash::solve(M, m, nn, x.p1_nash, x.p2_nash, &nv)) x.nash_value = nv / 256.0;
   }
+  return 0;
+}
+
+int oakgpu_forest_search(oakgpu_forest *f, oakgpu_net *net, const oakgpu_search_params *prm, const uint8_t *battles, const uint8_t *durations,
+                         const uint8_t *results, const uint64_t *seeds, uint32_t n, oakgpu_search_output *out, int solve_nash, uint64_t *streams_out,
+                         void *trace, uint32_t trace_levels) {
+  return forest_search_host(f, net, prm, battles, durations, results, seeds, n, out, solve_nash, streams_out, trace, trace_levels, false);
+}
+
+int oakgpu_forest_search_kept(oakgpu_forest *f, oakgpu_net *net, const oakgpu_search_params *prm, const uint8_t *battles, const uint8_t *durations,
+                              const uint8_t *results, const uint64_t *seeds, uint32_t n, oakgpu_search_output *out, int solve_nash, uint64_t *streams_out,
+                              void *trace, uint32_t trace_levels) {
+  return forest_search_host(f, net, prm, battles, durations, results, seeds, n, out, solve_nash, streams_out, trace, trace_levels, true);
+}
+
+// Heap::update of every tree, and the move to another row (k_forest_advance): reads the front copy, writes the back one, then the two swap
+int oakgpu_forest_advance_dev(oakgpu_forest *f, const uint8_t *i, const uint8_t *j, const uint8_t *obs, const uint32_t *src_tree, uint32_t n_new, uint8_t *kept_out) {
+  if (!f) return oakgpu_fail_msg("oakgpu_forest_advance: null argument");
+  if (!f->kept) return oakgpu_fail_msg("oakgpu_forest_advance: the forest was created without keep (oakgpu_forest_create_kept makes one that keeps its trees)");
+  if (n_new > f->max_trees) return oakgpu_fail_msg("oakgpu_forest_advance: n_new exceeds the forest's max_trees");
+  if (n_new && (!i || !j || !obs || !kept_out)) return oakgpu_fail_msg("oakgpu_forest_advance: null argument");
+  RC(oakgpu_ctx_enter(f->ctx));
+  hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(f->ctx);
+  const size_t table_bytes = (size_t)f->max_trees * f->slots * sizeof(FEdge);
+  const uint32_t gen_old = f->gen;
+  const bool wrapped = f->gen + 1 > 0xFFFFu; // the back copy is cleared before it is written, the front one once it has been read
+  if (wrapped) HIPCHK(hipMemsetAsync(f->edges_back, 0, table_bytes, stream));
+  f->gen = wrapped ? 1 : f->gen + 1;
+  if (n_new) {
+    AdvanceArgs a{};
+    a.src_nodes = f->nodes; a.src_edges = f->edges; a.src_n_nodes = f->n_nodes; a.dst_nodes = f->nodes_back; a.dst_edges = f->edges_back; a.dst_n_nodes = f->n_nodes_back;
+    a.map = f->map; a.i = i; a.j = j; a.obs = obs; a.src_tree = src_tree; a.kept_out = kept_out; a.dropped = f->dropped;
+    a.arena = f->arena; a.slots = f->slots; a.gen_old = gen_old; a.gen_new = f->gen; a.n_new = n_new; a.valid = f->valid; a.max_iterations = f->max_iterations;
+    hipLaunchKernelGGL(k_forest_advance, dim3(n_new), dim3(64), 0, stream, a);
+    HIPCHK(hipGetLastError());
+  }
+  if (wrapped) HIPCHK(hipMemsetAsync(f->edges, 0, table_bytes, stream));
+  std::swap(f->nodes, f->nodes_back); std::swap(f->edges, f->edges_back); std::swap(f->n_nodes, f->n_nodes_back);
+  f->valid = n_new;
+  f->last_n = n_new;
+  ++f->advances;
+  return 0;
+}
+
+int oakgpu_forest_advance(oakgpu_forest *f, const uint8_t *i, const uint8_t *j, const uint8_t *obs, const uint32_t *src_tree, uint32_t n_new, uint8_t *kept_out) {
+  if (!f) return oakgpu_fail_msg("oakgpu_forest_advance: null argument");
+  if (!f->kept) return oakgpu_fail_msg("oakgpu_forest_advance: the forest was created without keep (oakgpu_forest_create_kept makes one that keeps its trees)");
+  if (n_new > f->max_trees) return oakgpu_fail_msg("oakgpu_forest_advance: n_new exceeds the forest's max_trees");
+  if (n_new && (!i || !j || !obs || !kept_out)) return oakgpu_fail_msg("oakgpu_forest_advance: null argument");
+  RC(oakgpu_ctx_enter(f->ctx));
+  hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(f->ctx);
+  const size_t T = f->max_trees;
+  uint8_t *d_obs = f->adv_in, *d_i = d_obs + 16 * T, *d_j = d_i + T, *d_kept = d_j + T;
+  if (n_new) {
+    HIPCHK(hipMemcpyAsync(d_i, i, n_new, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_j, j, n_new, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_obs, obs, (size_t)n_new * 16, hipMemcpyHostToDevice, stream));
+    if (src_tree) HIPCHK(hipMemcpyAsync(f->adv_src, src_tree, (size_t)n_new * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+  }
+  RC(oakgpu_forest_advance_dev(f, d_i, d_j, d_obs, src_tree ? f->adv_src : nullptr, n_new, d_kept));
+  if (n_new) HIPCHK(hipMemcpyAsync(kept_out, d_kept, n_new, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  return 0;
+}
+
+int oakgpu_forest_keep_stats(oakgpu_forest *f, uint64_t out[4]) {
+  if (!f || !out) return oakgpu_fail_msg("oakgpu_forest_keep_stats: null argument");
+  if (!f->kept) return oakgpu_fail_msg("oakgpu_forest_keep_stats: the forest was created without keep (oakgpu_forest_create_kept makes one that keeps its trees)");
+  RC(oakgpu_ctx_enter(f->ctx));
+  hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(f->ctx);
+  uint32_t dropped = 0;
+  HIPCHK(hipMemcpyAsync(&dropped, f->dropped, 4, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  out[0] = f->arena; out[1] = f->slots; out[2] = f->advances; out[3] = dropped;
+  return 0;
+}
+
+int oakgpu_forest_node_counts(oakgpu_forest *f, uint32_t *out, uint32_t n, int to_device) {
+  if (!f || (n && !out)) return oakgpu_fail_msg("oakgpu_forest_node_counts: null argument");
+  if (n > f->last_n) return oakgpu_fail_msg("oakgpu_forest_node_counts: more trees than the forest's last call left");
+  RC(oakgpu_ctx_enter(f->ctx));
+  hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(f->ctx);
+  if (n) HIPCHK(hipMemcpyAsync(out, f->n_nodes, (size_t)n * 4, to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  return 0;
+}
+
+int oakgpu_forest_mismatch(oakgpu_forest *f, uint8_t *out, uint32_t n, int to_device) {
+  if (!f || (n && !out)) return oakgpu_fail_msg("oakgpu_forest_mismatch: null argument");
+  if (!f->kept) return oakgpu_fail_msg("oakgpu_forest_mismatch: the forest was created without keep (oakgpu_forest_create_kept makes one that keeps its trees)");
+  if (n > f->max_trees) return oakgpu_fail_msg("oakgpu_forest_mismatch: n exceeds the forest's max_trees");
+  RC(oakgpu_ctx_enter(f->ctx));
+  hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(f->ctx);
+  if (n) HIPCHK(hipMemcpyAsync(out, f->mismatch, n, to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
   return 0;
 }
 

@@ -13,6 +13,10 @@
 //   k_fsp_lengths  : one workgroup: the exclusive scan of the record lengths in game order = the record bases
 //   k_fsp_pack_head: one wave per game: length, frame count, first battle, result byte
 //   k_fsp_pack_log : 16 lanes per log entry: the update's bytes to base[game] + 391 + cursor
+// keep_node (a kept forest, oakgpu_forest_create_kept): the pick leaves the played cell (i, j) in the row and the update its observation; the
+// next turn's compaction carries them to the row's new place and lists each new row's source row, and ONE oakgpu_forest_advance_dev with
+// that list re-roots every tree and moves it along with its row; the search is then oakgpu_forest_search_kept_dev.  A retired row has no
+// successor.  The pick also keeps the row's nodes_kept count (selfplay.hip: + 1 per advance that kept, - 1 per root mismatch, never below 0).
 // Every kernel is a plain grid over rows, games or entries (the two scans: one workgroup); none waits for another block.  Between
 // compact and pick runs oakgpu_forest_search_dev over exactly the live rows (the forest refuses terminal roots), after pick
 // oakgpu_update_dev.  The pattern of retire / offsets / compact is policyplay.hip's, with this loop's own row.
@@ -47,11 +51,15 @@ struct Rows {
   uint8_t *battles, *durations, *results, *c1, *c2, *flag;
   uint32_t *game, *frames, *cursor;
   uint64_t *rng;
+  // keep_node: the played cell, the update's observation, and the game's counts so far (advances that kept, root mismatches, nodes carried in)
+  uint8_t *pi, *pj, *obs;
+  uint32_t *kept, *mism, *carry;
 };
 
-__global__ __launch_bounds__(BLOCK) void k_fsp_start(Rows r, const uint64_t *seeds, uint32_t n) {
+__global__ __launch_bounds__(BLOCK) void k_fsp_start(Rows r, const uint64_t *seeds, uint32_t n, int keep) {
   const uint32_t row = blockIdx.x * BLOCK + threadIdx.x;
   if (row >= n) return;
+  if (keep) { r.kept[row] = 0; r.mism[row] = 0; r.carry[row] = 0; }
   r.game[row] = row;
   r.frames[row] = 0;
   r.cursor[row] = 0;
@@ -65,6 +73,7 @@ struct RetireArgs {
   uint32_t *frames_out, *length_out;
   uint32_t *block_live;              // per block of BLOCK rows: rows still live after this pass
   uint32_t rows, max_len;
+  uint32_t *kept_out, *mism_out, *carry_out; // keep_node, by game index; else null
 };
 
 __global__ __launch_bounds__(BLOCK) void k_fsp_retire(RetireArgs a) {
@@ -83,6 +92,7 @@ __global__ __launch_bounds__(BLOCK) void k_fsp_retire(RetireArgs a) {
       a.frames_out[g] = frames;
       a.status_out[g] = (uint8_t)status;
       a.length_out[g] = status == OAKGPU_FSP_OK ? HEAD_BYTES + a.r.cursor[row] : 0u;
+      if (a.kept_out) { a.kept_out[g] = a.r.kept[row]; a.mism_out[g] = a.r.mism[row]; a.carry_out[g] = a.r.carry[row]; }
       a.r.game[row] = DEAD;
     }
   }
@@ -123,6 +133,11 @@ struct CompactArgs {
   const uint32_t *block_offset;
   uint64_t *tree_seed; // per compacted row: the seed of this turn's tree
   uint32_t rows;
+  // keep_node from the second turn on (else null): per compacted row, what oakgpu_forest_advance_dev takes -- the row (= tree) it came from,
+  // the cell played there, the observation
+  uint32_t *src_row;
+  uint8_t *adv_i, *adv_j, *adv_obs;
+  int keep; // keep_node: the game's counts move with the row
 };
 
 // Stable: a live row's place is its block's offset + the live rows in front of it in the block.  The 384-byte battles move as whole rows, 24
@@ -152,6 +167,12 @@ __global__ __launch_bounds__(BLOCK) void k_fsp_compact(CompactArgs a) {
     uint64_t rng = a.from.rng[row];
     a.tree_seed[to] = oak_pick::splitmix64(rng);
     a.to.rng[to] = rng;
+    if (a.src_row) {
+      a.src_row[to] = row;
+      a.adv_i[to] = a.from.pi[row]; a.adv_j[to] = a.from.pj[row];
+      *((u32x4 *)a.adv_obs + to) = *((const u32x4 *)a.from.obs + row);
+    }
+    if (a.keep) { a.to.kept[to] = a.from.kept[row]; a.to.mism[to] = a.from.mism[row]; a.to.carry[to] = a.from.carry[row]; }
   }
   __syncthreads();
   const u32x4 *src = (const u32x4 *)a.from.battles + (size_t)base * 24;
@@ -174,6 +195,10 @@ struct PickArgs {
   oak_pick::PolicyMode mode;
   double temp, minp;
   uint32_t rows;
+  // keep_node: the row keeps the played cell; from the second turn on (else null) the advance's results, the kept search's mismatch bytes and carried nodes
+  int keep;
+  const uint8_t *advanced, *mismatch;
+  const uint32_t *carried;
 };
 
 __global__ __launch_bounds__(BLOCK) void k_fsp_pick(PickArgs a) {
@@ -195,6 +220,7 @@ __global__ __launch_bounds__(BLOCK) void k_fsp_pick(PickArgs a) {
   entry->cursor = a.r.cursor[row];
   uint8_t c1 = a.out.p1_choices[(size_t)row * 9], c2 = a.out.p2_choices[(size_t)row * 9];
   uint32_t len = 0;
+  uint8_t pi = 0, pj = 0;
   if (!oak_pick::get_policy(r1, e1, n1, m, a.mode, a.temp, a.minp, pol1) || !oak_pick::get_policy(r2, e2, n2, n, a.mode, a.temp, a.minp, pol2)) {
     a.r.flag[row] = (uint8_t)OAKGPU_FSP_ZERO_POLICY; // the game stops here: its row takes a legal step and is retired with no record
   } else {
@@ -203,6 +229,7 @@ __global__ __launch_bounds__(BLOCK) void k_fsp_pick(PickArgs a) {
     a.r.rng[row] = rng;
     c1 = a.out.p1_choices[(size_t)row * 9 + i];
     c2 = a.out.p2_choices[(size_t)row * 9 + j];
+    pi = (uint8_t)i; pj = (uint8_t)j;
     len = oak_pick::encode_update(entry->bytes, (uint32_t)m, (uint32_t)n, c1, c2, (uint32_t)iterations, ev, nv, e1, n1, e2, n2);
     a.r.frames[row] += 1;
     a.r.cursor[row] += len;
@@ -210,6 +237,15 @@ __global__ __launch_bounds__(BLOCK) void k_fsp_pick(PickArgs a) {
   entry->length = len;
   a.r.c1[row] = c1;
   a.r.c2[row] = c2;
+  if (a.keep) {
+    a.r.pi[row] = pi; a.r.pj[row] = pj;
+    if (a.advanced) {
+      uint32_t kept = a.r.kept[row] + a.advanced[row];
+      if (a.mismatch[row]) { if (kept) --kept; a.r.mism[row] += 1; }
+      a.r.kept[row] = kept;
+      a.r.carry[row] += a.carried[row];
+    }
+  }
 }
 
 struct PackArgs {
@@ -282,6 +318,11 @@ struct Workspace {
   uint32_t last_n = 0;
   bool have = false;
   uint64_t stats[4] = {0, 0, 0, 0};
+  // keep_node: the advance's inputs and results per compacted row, the per-game counts, and the last call's totals
+  uint32_t *src_row = nullptr, *kept_out = nullptr, *mism_out = nullptr, *carry_out = nullptr;
+  uint8_t *adv_i = nullptr, *adv_j = nullptr, *adv_obs = nullptr, *advanced = nullptr;
+  bool kept_call = false;
+  uint64_t keep_stats[4] = {0, 0, 0, 0};
   std::vector<int32_t> h_pay;
   std::vector<double> h_nash;
   void release() {
@@ -322,6 +363,11 @@ int workspace_for(oakgpu_forest *f, uint32_t n, Workspace **out) {
     Rows &r = w->half[h];
     RC(w->get(r.battles, T * 384)); RC(w->get(r.durations, T * 8)); RC(w->get(r.results, T)); RC(w->get(r.c1, T)); RC(w->get(r.c2, T)); RC(w->get(r.flag, T));
     RC(w->get(r.game, T)); RC(w->get(r.frames, T)); RC(w->get(r.cursor, T)); RC(w->get(r.rng, T));
+    if (oakgpu_forest_is_kept(f)) { RC(w->get(r.pi, T)); RC(w->get(r.pj, T)); RC(w->get(r.obs, T * 16)); RC(w->get(r.kept, T)); RC(w->get(r.mism, T)); RC(w->get(r.carry, T)); }
+  }
+  if (oakgpu_forest_is_kept(f)) {
+    RC(w->get(w->src_row, T)); RC(w->get(w->kept_out, T)); RC(w->get(w->mism_out, T)); RC(w->get(w->carry_out, T));
+    RC(w->get(w->adv_i, T)); RC(w->get(w->adv_j, T)); RC(w->get(w->adv_obs, T * 16)); RC(w->get(w->advanced, T));
   }
   RC(w->get(w->tree_seed, T)); RC(w->get(w->out_block, OUT_BYTES * T + 16 * 16)); RC(w->get(w->pay, T * PAY_STRIDE)); RC(w->get(w->nash, T * 19));
   RC(w->get(w->first, T * 384)); RC(w->get(w->results_out, T)); RC(w->get(w->status_out, T)); RC(w->get(w->d_teams, T * 60));
@@ -344,7 +390,9 @@ extern "C" {
 int oakgpu_forest_selfplay_check(uint32_t max_trees, uint32_t max_iterations, int contextual, const oakgpu_selfplay_params *prm, int has_net, uint32_t n,
                                  const uint8_t *teams, int solve_nash) {
   if (!prm) return oakgpu_fail_msg("oakgpu_forest_selfplay: null argument");
-  if (prm->keep_node != 0) return oakgpu_fail_msg("oakgpu_forest_selfplay: keep_node is not supported (every turn searches a fresh tree)");
+  if (prm->keep_node != 0 && !(contextual & OAKGPU_FOREST_KEPT))
+    return oakgpu_fail_msg("oakgpu_forest_selfplay: keep_node is not supported on this forest (every turn searches a fresh tree): oakgpu_forest_create_kept makes one that keeps its trees");
+  contextual &= ~OAKGPU_FOREST_KEPT;
   oak_pick::PolicyMode mode;
   const int bad = oak_pick::parse_policy_mode(prm->policy_mode, sizeof prm->policy_mode, &mode);
   if (bad == 'b') return oakgpu_fail_msg("oakgpu_forest_selfplay: policy mode 'b' (beta) is not supported (util/policy.h:59-60 throws)");
@@ -383,10 +431,22 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
     HIPCHK(hipMemcpyAsync(h_teams.data(), teams, h_teams.size(), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
   }
+  if (oakgpu_forest_is_kept(f)) contextual |= OAKGPU_FOREST_KEPT;
   RC(oakgpu_forest_selfplay_check(max_trees, max_iterations, contextual, prm, net != nullptr, n, n ? h_teams.data() : nullptr, solve_nash));
+  const bool keep = prm->keep_node != 0;
   Workspace *w = nullptr;
   RC(workspace_for(f, std::max(n, 1u), &w));
   w->have = false;
+  w->kept_call = keep;
+  w->keep_stats[0] = w->keep_stats[1] = w->keep_stats[2] = w->keep_stats[3] = 0;
+  const uint8_t *d_mismatch = nullptr;
+  const uint32_t *d_carried = nullptr, *d_dropped = nullptr;
+  uint32_t dropped_before = 0;
+  if (keep) {
+    oakgpu_forest_keep_arrays(f, &d_mismatch, &d_carried, &d_dropped);
+    HIPCHK(hipMemcpyAsync(&dropped_before, d_dropped, 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+  }
   w->last_n = n;
   w->stream_bytes = 0;
   w->stats[0] = w->stats[1] = w->stats[2] = w->stats[3] = 0;
@@ -405,7 +465,7 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
     Rows &r = w->half[0];
     RC(oakgpu_init_battles_dev(ctx, teams, battle_seeds, n, 1, r.battles, r.durations, r.results));
     HIPCHK(hipMemcpyAsync(w->first, r.battles, (size_t)n * 384, hipMemcpyDeviceToDevice, stream));
-    hipLaunchKernelGGL(k_fsp_start, grid(n), dim3(BLOCK), 0, stream, r, seeds, n);
+    hipLaunchKernelGGL(k_fsp_start, grid(n), dim3(BLOCK), 0, stream, r, seeds, n, keep ? 1 : 0);
     HIPCHK(hipGetLastError());
   }
   if (!w->log) {
@@ -418,10 +478,12 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
   for (uint64_t turn = 0;; ++turn) {
     // retire what ended, compact the rest: the rows handed to the search are exactly the live games
     const uint32_t blocks = (rows + BLOCK - 1) / BLOCK;
-    const RetireArgs ra{w->half[cur], w->results_out, w->status_out, w->frames_out, w->length_out, w->block_live, rows, max_len};
+    const RetireArgs ra{w->half[cur], w->results_out, w->status_out, w->frames_out, w->length_out, w->block_live, rows, max_len,
+                        keep ? w->kept_out : nullptr, keep ? w->mism_out : nullptr, keep ? w->carry_out : nullptr};
     hipLaunchKernelGGL(k_fsp_retire, grid(rows), dim3(BLOCK), 0, stream, ra);
     hipLaunchKernelGGL(k_fsp_offsets, dim3(1), dim3(1024), 0, stream, w->block_live, blocks, w->block_offset, w->ctl);
-    const CompactArgs ca{w->half[cur], w->half[cur ^ 1], w->block_offset, w->tree_seed, rows};
+    const bool advance = keep && turn > 0; // the first turn's trees are new
+    const CompactArgs ca{w->half[cur], w->half[cur ^ 1], w->block_offset, w->tree_seed, rows, advance ? w->src_row : nullptr, w->adv_i, w->adv_j, w->adv_obs, keep ? 1 : 0};
     hipLaunchKernelGGL(k_fsp_compact, grid(rows), dim3(BLOCK), 0, stream, ca);
     HIPCHK(hipGetLastError());
     uint32_t live = 0;
@@ -448,7 +510,10 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
       w->log_capacity = want;
     }
     carve_outputs(w->out_block, rows, &o);
-    RC(oakgpu_forest_search_dev(f, net, &sp, r.battles, r.durations, r.results, w->tree_seed, rows, &o, nullptr, 0));
+    if (advance) { // every live game's tree: re-rooted at the child it played into, and moved to the game's new row
+      RC(oakgpu_forest_advance_dev(f, w->adv_i, w->adv_j, w->adv_obs, w->src_row, rows, w->advanced));
+      RC(oakgpu_forest_search_kept_dev(f, net, &sp, r.battles, r.durations, r.results, w->tree_seed, rows, &o, nullptr, 0));
+    } else RC(oakgpu_forest_search_dev(f, net, &sp, r.battles, r.durations, r.results, w->tree_seed, rows, &o, nullptr, 0));
     double *d_p1 = nullptr, *d_p2 = nullptr, *d_nv = nullptr;
     if (solve_nash) {
       const PayoffArgs pa{o.m, o.n, o.visit_matrix, o.value_matrix, w->pay, rows};
@@ -465,11 +530,13 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
     PickArgs pk{};
     pk.r = r; pk.out = o; pk.p1_nash = d_p1; pk.p2_nash = d_p2; pk.nash_value = d_nv; pk.log = w->log + entries; pk.mode = mode;
     pk.temp = prm->policy_temp > 0 ? prm->policy_temp : 1.0; pk.minp = prm->policy_min; pk.rows = rows;
+    pk.keep = keep ? 1 : 0;
+    if (advance) { pk.advanced = w->advanced; pk.mismatch = d_mismatch; pk.carried = d_carried; }
     hipLaunchKernelGGL(k_fsp_pick, grid(rows), dim3(BLOCK), 0, stream, pk);
     HIPCHK(hipGetLastError());
     entries += rows;
     // PKMN::update(battle, c1, c2, options); durations <- options (generate.cc:319-322)
-    RC(oakgpu_update_dev(ctx, r.battles, r.c1, r.c2, r.durations, nullptr, nullptr, rows, r.results));
+    RC(oakgpu_update_dev(ctx, r.battles, r.c1, r.c2, r.durations, keep ? r.obs : nullptr, nullptr, rows, r.results));
     if (solve_nash) HIPCHK(hipStreamSynchronize(stream)); // (the strategies' host copy is reused next turn)
   }
 
@@ -493,8 +560,43 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipStreamSynchronize(stream));
+  if (keep) { // the per-game counts, read once: the call's totals
+    std::vector<uint32_t> h((size_t)n * 3);
+    uint32_t dropped_after = 0;
+    HIPCHK(hipMemcpyAsync(h.data(), w->kept_out, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(h.data() + n, w->mism_out, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(h.data() + 2 * (size_t)n, w->carry_out, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(&dropped_after, d_dropped, 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    for (uint32_t g = 0; g < n; ++g) { w->keep_stats[0] += h[g]; w->keep_stats[2] += h[n + g]; w->keep_stats[3] += h[2 * (size_t)n + g]; }
+    w->keep_stats[1] = dropped_after - dropped_before;
+  }
   w->stream_bytes = (size_t)total;
   w->have = true;
+  return 0;
+}
+
+int oakgpu_forest_selfplay_nodes_kept(oakgpu_forest *f, uint32_t *nodes_kept, int to_device) {
+  if (!f || !nodes_kept) return oakgpu_fail_msg("oakgpu_forest_selfplay_nodes_kept: null argument");
+  Workspace *w = (Workspace *)oakgpu_forest_attachment(f);
+  if (!w || !w->have) return oakgpu_fail_msg("oakgpu_forest_selfplay_nodes_kept: the forest holds no finished self-play call");
+  oakgpu_ctx *ctx = oakgpu_forest_ctx(f);
+  RC(oakgpu_ctx_enter(ctx));
+  hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(ctx);
+  const size_t n = w->last_n;
+  if (n) {
+    if (w->kept_call) HIPCHK(hipMemcpyAsync(nodes_kept, w->kept_out, n * 4, to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+    else if (to_device) HIPCHK(hipMemsetAsync(nodes_kept, 0, n * 4, stream));
+    else memset(nodes_kept, 0, n * 4);
+  }
+  HIPCHK(hipStreamSynchronize(stream));
+  return 0;
+}
+
+int oakgpu_forest_selfplay_keep_stats(const oakgpu_forest *f, uint64_t out[4]) {
+  if (!f || !out) return oakgpu_fail_msg("oakgpu_forest_selfplay_keep_stats: null argument");
+  const Workspace *w = (const Workspace *)oakgpu_forest_attachment(f);
+  for (int q = 0; q < 4; ++q) out[q] = w ? w->keep_stats[q] : 0;
   return 0;
 }
 
@@ -529,6 +631,7 @@ int oakgpu_forest_selfplay(oakgpu_forest *f, oakgpu_net *net, const oakgpu_selfp
   uint32_t max_trees = 0, max_iterations = 0;
   int contextual = 0;
   oakgpu_forest_limits(f, &max_trees, &max_iterations, &contextual);
+  if (oakgpu_forest_is_kept(f)) contextual |= OAKGPU_FOREST_KEPT;
   RC(oakgpu_forest_selfplay_check(max_trees, max_iterations, contextual, prm, net != nullptr, n, teams, solve_nash));
   oakgpu_ctx *ctx = oakgpu_forest_ctx(f);
   RC(oakgpu_ctx_enter(ctx));

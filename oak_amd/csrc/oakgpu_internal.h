@@ -77,6 +77,10 @@ unsigned oakgpu_usable_cores();
 struct oakgpu_forest;
 oakgpu_ctx *oakgpu_forest_ctx(const oakgpu_forest *forest);
 void oakgpu_forest_limits(const oakgpu_forest *forest, uint32_t *max_trees, uint32_t *max_iterations, int *contextual);
+// a kept forest (oakgpu_forest_create_kept) and, for the game loop's pick kernel, its per-tree device arrays: the last kept search's mismatch
+// bytes and carried node counts, and the counter of dropped trees
+int oakgpu_forest_is_kept(const oakgpu_forest *forest);
+void oakgpu_forest_keep_arrays(const oakgpu_forest *forest, const uint8_t **mismatch, const uint32_t **carried, const uint32_t **dropped);
 void *oakgpu_forest_attachment(const oakgpu_forest *forest);
 void oakgpu_forest_set_attachment(oakgpu_forest *forest, void *p, void (*dtor)(void *));
 // a second one of the same kind for the match loop (forestmatch.hip), so that one forest serves self-play and matches in turn

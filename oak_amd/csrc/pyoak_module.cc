@@ -411,10 +411,11 @@ PYBIND11_MODULE(pyoak, m) {
       "selfplay_forest",
       [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> teams, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> battle_seeds,
          py::array_t<uint64_t, py::array::c_style | py::array::forcecast> seeds, Agent &agent, const std::string &policy_mode, double policy_temp,
-         double policy_min, uint32_t max_battle_length, bool solve_nash) {
+         double policy_min, uint32_t max_battle_length, bool solve_nash, bool keep_node, uint32_t keep_arena) {
         // not in pyoak: the reference's `generate` loop for n games at once over the forest search (include/oakgpu.h:
         // oakgpu_forest_selfplay); game g is the per-game loop with batch = 1 and seed = seeds[g].  Returns (stream bytes, offsets, n_frames,
-        // results, status).
+        // results, status); with keep_node (generate's --keep-node, on a kept forest of keep_arena nodes a tree, 0 = 4 * budget + 1) a sixth
+        // value, nodes_kept per game.
         const size_t n = (size_t)seeds.size();
         if ((size_t)teams.size() != n * 60 || (size_t)battle_seeds.size() != n) throw std::runtime_error("selfplay_forest: teams n x 60, battle_seeds n, seeds n");
         if (policy_mode.size() > 15) throw std::runtime_error("selfplay_forest: policy_mode: at most 15 characters");
@@ -423,20 +424,25 @@ PYBIND11_MODULE(pyoak, m) {
         py::array_t<uint64_t> offsets(n + 1);
         py::array_t<uint32_t> n_frames(n);
         py::array_t<uint8_t> results(n), status(n);
+        py::array_t<uint32_t> nodes_kept(n);
         int rc = 0;
         std::string err;
         {
           py::gil_scoped_release release;
           std::lock_guard<std::mutex> lock(g_ctx_mu);
           oakgpu_selfplay_params P{};
+          P.keep_node = keep_node ? 1 : 0;
           oakgpu_net *net = nullptr;
           oakgpu_forest *forest = nullptr;
           rc = oakgpu_agent_params(context(), &a, 1, 0, &P.search, &net);
           std::memcpy(P.policy_mode, policy_mode.c_str(), policy_mode.size() + 1);
           P.policy_temp = policy_temp; P.policy_min = policy_min; P.max_battle_length = max_battle_length;
           const uint32_t cap = (uint32_t)std::min<uint64_t>(P.search.iterations, 0xFFFFFFFFu);
-          if (!rc) rc = oakgpu_forest_selfplay_check((uint32_t)n, cap, P.search.bandit == 1, &P, net != nullptr, (uint32_t)n, teams.data(), solve_nash ? 1 : 0);
-          if (!rc && n) rc = oakgpu_forest_create(context(), (uint32_t)n, cap, P.search.bandit == 1, &forest);
+          if (!rc && keep_node) rc = oakgpu_forest_create_kept_check((uint32_t)std::max<size_t>(n, 1), cap, keep_arena);
+          if (!rc) rc = oakgpu_forest_selfplay_check((uint32_t)n, cap, (P.search.bandit == 1 ? 1 : 0) | (keep_node ? OAKGPU_FOREST_KEPT : 0), &P, net != nullptr, (uint32_t)n,
+                                                     teams.data(), solve_nash ? 1 : 0);
+          if (!rc && n) rc = keep_node ? oakgpu_forest_create_kept(context(), (uint32_t)n, cap, P.search.bandit == 1, keep_arena, &forest)
+                                       : oakgpu_forest_create(context(), (uint32_t)n, cap, P.search.bandit == 1, &forest);
           if (!rc && n) rc = oakgpu_forest_selfplay(forest, net, &P, teams.data(), battle_seeds.data(), seeds.data(), (uint32_t)n, solve_nash ? 1 : 0);
           size_t bytes = 0;
           if (!rc && n) rc = oakgpu_forest_selfplay_records(forest, nullptr, 0, &bytes, nullptr, nullptr, nullptr, nullptr, 0);
@@ -445,15 +451,17 @@ PYBIND11_MODULE(pyoak, m) {
             rc = oakgpu_forest_selfplay_records(forest, (uint8_t *)stream.data(), bytes, &bytes, offsets.mutable_data(), n_frames.mutable_data(),
                                                 results.mutable_data(), status.mutable_data(), 0);
           }
+          if (!rc && n && keep_node) rc = oakgpu_forest_selfplay_nodes_kept(forest, nodes_kept.mutable_data(), 0);
           if (rc) err = oakgpu_last_error();
           oakgpu_forest_destroy(context(), forest);
         }
         if (rc) throw std::runtime_error(err);
         if (!n) offsets.mutable_data()[0] = 0;
-        return py::make_tuple(py::bytes(stream), offsets, n_frames, results, status);
+        if (keep_node) return py::tuple(py::make_tuple(py::bytes(stream), offsets, n_frames, results, status, nodes_kept));
+        return py::tuple(py::make_tuple(py::bytes(stream), offsets, n_frames, results, status));
       },
       py::arg("teams"), py::arg("battle_seeds"), py::arg("seeds"), py::arg("agent"), py::arg("policy_mode") = "e", py::arg("policy_temp") = 1.0,
-      py::arg("policy_min") = 0.0, py::arg("max_battle_length") = 0, py::arg("solve_nash") = true);
+      py::arg("policy_min") = 0.0, py::arg("max_battle_length") = 0, py::arg("solve_nash") = true, py::arg("keep_node") = false, py::arg("keep_arena") = 0);
 
   m.def(
       "match_forest",

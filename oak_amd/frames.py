@@ -134,10 +134,14 @@ def _selfplay_params(iterations, bandit, c, evaluator, policy_mode, policy_temp,
 
 
 def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="ucb", evaluator="mc", policy_mode="e", policy_temp=1.0,
-                    policy_min=0.0, max_battle_length=0, root_rolls=3, other_rolls=1, max_depth=0, forest=None, solve_nash=True, stats=None):
+                    policy_min=0.0, max_battle_length=0, root_rolls=3, other_rolls=1, max_depth=0, forest=None, solve_nash=True, stats=None,
+                    keep_node=False, keep_arena=0):
     """n self-play games at once over the forest search, resident on the GPU (oakgpu_forest_selfplay*): game g is selfplay_game(ctx,
     teams[g], battle_seeds[g], batch=1, seed=seeds[g], ...).  teams uint8[n, 2, 6, 5]; forest: None (one made for this call) or a
     search.Forest to reuse; stats: optional dict that receives turns, rows searched, compactions and host reads.
+    keep_node: generate's --keep-node -- each game's tree goes on from turn to turn (a kept forest: one made with keep_arena nodes per tree,
+    0 = 4 * iterations + 1, or the caller's Forest(keep_arena=...)); a sixth value is then returned, nodes_kept uint32[n] (selfplay_game's
+    stats["nodes_kept"] per game), and stats also receives nodes_kept, dropped, mismatches and carried_nodes.
     numpy arrays in: (stream bytes, offsets uint64[n + 1], n_frames uint32[n], results uint8[n], status uint8[n]) -- the stream is the
     kept games' records in game order, a dropped game (status MAX_LENGTH / ZERO_POLICY, see FSP_STATUS) has zero bytes.
     torch GPU tensors in (teams uint8 [n, 60]; battle_seeds, seeds int64 bit patterns): the same five as tensors on that device; nothing
@@ -145,12 +149,13 @@ def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="
     from .search import Forest
     use_net = not isinstance(evaluator, str)
     prm = _selfplay_params(iterations, bandit, c, evaluator, policy_mode, policy_temp, policy_min, max_battle_length, root_rolls, other_rolls, max_depth)
+    prm.keep_node = 1 if keep_node else 0
     net = evaluator.handle if use_net else None
     on_device = hasattr(teams, "data_ptr")
     n = int(teams.shape[0]) if on_device else len(np.asarray(seeds).reshape(-1))
     own = forest is None
     if own:
-        forest = Forest(ctx, max(n, 1), max(int(iterations), 1), contextual=bandit == "pucb")
+        forest = Forest(ctx, max(n, 1), max(int(iterations), 1), contextual=bandit == "pucb", keep_arena=int(keep_arena) if keep_node else None)
     lib = ctx.lib
     try:
         size = C.c_size_t(0)
@@ -171,6 +176,12 @@ def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="
                                                           n_frames.data_ptr(), results.data_ptr(), status.data_ptr(), 1))
             theirs.wait_stream(mine)
             out = (stream[:size.value], offsets, n_frames[:n], results[:n], status[:n])
+            if keep_node:
+                kept = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+                mine.wait_stream(theirs)
+                _lib.check(lib.oakgpu_forest_selfplay_nodes_kept(forest.handle, kept.data_ptr(), 1))
+                theirs.wait_stream(mine)
+                out += (kept[:n],)
         else:
             t = np.ascontiguousarray(teams, dtype=np.uint8).reshape(n, 60)
             bs = np.ascontiguousarray(np.asarray(battle_seeds).astype(np.uint64)).reshape(n)
@@ -184,10 +195,17 @@ def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="
             _lib.check(lib.oakgpu_forest_selfplay_records(forest.handle, vp(stream), size.value, C.byref(size), vp(offsets), vp(n_frames), vp(results),
                                                           vp(status), 0))
             out = (stream[:size.value].tobytes(), offsets, n_frames[:n], results[:n], status[:n])
+            if keep_node:
+                kept = np.zeros(max(n, 1), np.uint32)
+                _lib.check(lib.oakgpu_forest_selfplay_nodes_kept(forest.handle, vp(kept), 0))
+                out += (kept[:n],)
         if stats is not None:
             st = (C.c_uint64 * 4)()
             _lib.check(lib.oakgpu_forest_selfplay_last_stats(forest.handle, C.byref(st)))
             stats.update(turns=int(st[0]), rows=int(st[1]), compactions=int(st[2]), host_reads=int(st[3]))
+            if keep_node:
+                _lib.check(lib.oakgpu_forest_selfplay_keep_stats(forest.handle, C.byref(st)))
+                stats.update(nodes_kept=int(st[0]), dropped=int(st[1]), mismatches=int(st[2]), carried_nodes=int(st[3]))
         return out
     finally:
         if own:
@@ -196,16 +214,16 @@ def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="
 
 def forest_selfplay_check(max_trees, max_iterations, contextual, iterations, n=1, teams=None, c=2.0, bandit="ucb", evaluator="mc", policy_mode="e",
                           policy_temp=1.0, policy_min=0.0, max_battle_length=0, root_rolls=3, other_rolls=1, max_depth=0, solve_nash=True,
-                          has_net=False, keep_node=False, matrix_ucb=0, duration_us=0):
+                          has_net=False, keep_node=False, matrix_ucb=0, duration_us=0, kept=False):
     """oakgpu_forest_selfplay_check alone (host only, no GPU): raises OakGpuError with the refusal's message.  evaluator "mc" | "poke-engine" |
-    "net" (with has_net saying whether a network is given)."""
+    "net" (with has_net saying whether a network is given); kept: the limits are a kept forest's (oakgpu_forest_create_kept)."""
     prm = _selfplay_params(iterations, bandit, c, "mc" if evaluator == "net" else evaluator, policy_mode, policy_temp, policy_min, max_battle_length,
                            root_rolls, other_rolls, max_depth)
     if evaluator == "net":
         prm.search.eval = 1
     prm.keep_node, prm.search.matrix_ucb, prm.search.duration_us = int(bool(keep_node)), int(matrix_ucb), int(duration_us)
     t = None if teams is None else np.ascontiguousarray(teams, dtype=np.uint8).reshape(n, 60)
-    _lib.check(_lib.load().oakgpu_forest_selfplay_check(int(max_trees), int(max_iterations), int(bool(contextual)), C.byref(prm), int(bool(has_net)), int(n),
+    _lib.check(_lib.load().oakgpu_forest_selfplay_check(int(max_trees), int(max_iterations), int(bool(contextual)) | (2 if kept else 0), C.byref(prm), int(bool(has_net)), int(n),
                                                         None if t is None else t.ctypes.data_as(C.c_void_p), int(bool(solve_nash))))
 
 

@@ -245,13 +245,67 @@ def trace_dtype(trace_levels):
 
 class Forest:
     """oakgpu_forest: the device arenas of `max_trees` trees of up to `max_iterations` iterations each (include/oakgpu.h); contextual =
-    room for the policy logits PUCB needs.  Kept between forest_search calls to save the allocation."""
+    room for the policy logits PUCB needs.  Kept between forest_search calls to save the allocation.
+    keep_arena: None = a plain forest; a node count per tree (0 = 4 * max_iterations + 1) = a kept forest (oakgpu_forest_create_kept),
+    whose trees go on from call to call: forest_search(..., keep=True) and advance()."""
 
-    def __init__(self, ctx, max_trees, max_iterations, contextual=False):
+    def __init__(self, ctx, max_trees, max_iterations, contextual=False, keep_arena=None):
         self.ctx, self.max_trees, self.max_iterations, self.contextual = ctx, int(max_trees), int(max_iterations), bool(contextual)
+        self.kept = keep_arena is not None
         h = C.c_void_p()
-        _lib.check(ctx.lib.oakgpu_forest_create(ctx.handle, self.max_trees, self.max_iterations, int(self.contextual), C.byref(h)))
+        if self.kept:
+            _lib.check(ctx.lib.oakgpu_forest_create_kept(ctx.handle, self.max_trees, self.max_iterations, int(self.contextual), int(keep_arena), C.byref(h)))
+        else:
+            _lib.check(ctx.lib.oakgpu_forest_create(ctx.handle, self.max_trees, self.max_iterations, int(self.contextual), C.byref(h)))
         self.handle = h
+
+    def advance(self, i, j, obs, src=None):
+        """Heap::update of every tree, and its move to another row (oakgpu_forest_advance*): new tree t continues tree src[t] (None: tree t)
+        of the last call along the played cell (i[t], j[t]) and the update's 16-byte observation obs[t].  Returns kept [n] uint8: 1 = the
+        child is the root now with its whole subtree, 0 = nothing kept (an empty tree).  torch GPU tensors in (uint8 i, j, obs [n, 16];
+        int32 src): a tensor out, nothing copied to the host."""
+        lib = self.ctx.lib
+        if hasattr(i, "data_ptr"):
+            import torch
+            n, dev = int(i.shape[0]), i.device
+            i, j, obs = i.contiguous(), j.contiguous(), obs.contiguous()
+            src = None if src is None else src.to(torch.int32).contiguous()
+            kept = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+            mine, theirs = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev), torch.cuda.current_stream(dev)
+            mine.wait_stream(theirs)
+            _lib.check(lib.oakgpu_forest_advance_dev(self.handle, i.data_ptr(), j.data_ptr(), obs.data_ptr(), None if src is None else src.data_ptr(), n,
+                                                     kept.data_ptr()))
+            theirs.wait_stream(mine)
+            self._counts = None
+            return kept[:n]
+        i = np.ascontiguousarray(i, dtype=np.uint8).reshape(-1)
+        n = len(i)
+        j = np.ascontiguousarray(j, dtype=np.uint8).reshape(n)
+        obs = np.ascontiguousarray(obs, dtype=np.uint8).reshape(n, 16)
+        src = None if src is None else np.ascontiguousarray(src, dtype=np.uint32).reshape(n)
+        kept = np.zeros(max(n, 1), np.uint8)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        _lib.check(lib.oakgpu_forest_advance(self.handle, vp(i), vp(j), vp(obs), None if src is None else vp(src), n, vp(kept)))
+        self._counts = None
+        return kept[:n]
+
+    def mismatch(self, n):
+        """The last kept search's per-tree bytes: 1 = the kept root had other choice counts than the position, the tree started afresh."""
+        out = np.zeros(max(int(n), 1), np.uint8)
+        _lib.check(self.ctx.lib.oakgpu_forest_mismatch(self.handle, out.ctypes.data_as(C.c_void_p), int(n), 0))
+        return out[:int(n)]
+
+    def node_counts(self, n):
+        """Node counts of the first n trees the last call (a search or an advance) left."""
+        out = np.zeros(max(int(n), 1), np.uint32)
+        _lib.check(self.ctx.lib.oakgpu_forest_node_counts(self.handle, out.ctypes.data_as(C.c_void_p), int(n), 0))
+        return out[:int(n)]
+
+    def keep_stats(self):
+        """(keep_arena, slots per tree, advance launches, trees dropped for want of room) since the forest was made."""
+        out = (C.c_uint64 * 4)()
+        _lib.check(self.ctx.lib.oakgpu_forest_keep_stats(self.handle, C.byref(out)))
+        return tuple(int(x) for x in out)
 
     def nodes(self, tree, first=0, count=None):
         """Node records of one tree of the last call, in creation order (the root first): a list of ((k, scores, priors, visits) of p1, of p2)."""
@@ -264,6 +318,8 @@ class Forest:
         return [(side(buf[q].p1), side(buf[q].p2)) for q in range(count)]
 
     def node_count(self, tree):
+        if getattr(self, "_counts", None) is None:   # (after an advance: ask for nodes with an explicit count)
+            raise ValueError("Forest.nodes: give a count (the node counts are those of the last search)")
         return int(self._counts[int(tree)])
 
     def last_stats(self):
@@ -291,10 +347,12 @@ _FOREST_TENSORS = (("m", "uint8", ()), ("n", "uint8", ()), ("p1_choices", "uint8
 
 
 def forest_search(ctx, battles, durations, results, seeds, iterations, c=2.0, bandit="ucb", evaluator="mc", max_depth=0, root_rolls=3,
-                  other_rolls=1, solve_nash=False, trace_levels=0, forest=None):
+                  other_rolls=1, solve_nash=False, trace_levels=0, forest=None, keep=False):
     """n searches at once, one GPU lane per tree, every tree on the device (include/oakgpu.h: oakgpu_forest_search*): tree g is
     tree_search(ctx, battles[g], durations[g], results[g], iterations, batch=1, seed=seeds[g], ...) iteration for iteration.  bandit "ucb" |
     "pucb"; evaluator "mc", "poke-engine" or a Network; forest: None (one made for this call) or a Forest to reuse.
+    keep=True (a Forest made with keep_arena): the kept form, oakgpu_forest_search_kept* -- every tree goes on where the forest's last call
+    or Forest.advance left it, as tree_search does on a heap; an initialised root is left alone and the outputs' priors are zeros.
     numpy arrays in: a list of n dicts with tree_search's keys (nash fields only with solve_nash) plus "stream" (the tree's continuing
     fast_prng state) and, with trace_levels > 0, "trace" (iterations records of trace_dtype(trace_levels)) and -- when the call made its own
     forest -- "tree" (Forest.nodes of the tree: with a forest of the caller's, read them from it).
@@ -323,7 +381,7 @@ def forest_search(ctx, battles, durations, results, seeds, iterations, c=2.0, ba
             ptrs = _lib.ForestOutputs(**{name: out[name].data_ptr() for name, _, _ in _FOREST_TENSORS})
             mine, theirs = torch.cuda.ExternalStream(ctx.stream_ptr(), device=dev), torch.cuda.current_stream(dev)
             mine.wait_stream(theirs)
-            _lib.check(ctx.lib.oakgpu_forest_search_dev(forest.handle, net, C.byref(prm), battles.data_ptr(), durations.data_ptr(), results.data_ptr(),
+            _lib.check((ctx.lib.oakgpu_forest_search_kept_dev if keep else ctx.lib.oakgpu_forest_search_dev)(forest.handle, net, C.byref(prm), battles.data_ptr(), durations.data_ptr(), results.data_ptr(),
                                                         seeds.data_ptr(), n, C.byref(ptrs), trace.data_ptr() if trace_levels else None, int(trace_levels)))
             theirs.wait_stream(mine)
             if trace_levels:
@@ -337,7 +395,7 @@ def forest_search(ctx, battles, durations, results, seeds, iterations, c=2.0, ba
         outs = (_lib.SearchOutput * max(n, 1))()
         streams = np.zeros(max(n, 1), np.uint64)
         trace = np.zeros((n, int(iterations)), dtype=trace_dtype(trace_levels)) if trace_levels else None
-        _lib.check(ctx.lib.oakgpu_forest_search(forest.handle, net, C.byref(prm), battles.ctypes.data_as(C.c_void_p), durations.ctypes.data_as(C.c_void_p),
+        _lib.check((ctx.lib.oakgpu_forest_search_kept if keep else ctx.lib.oakgpu_forest_search)(forest.handle, net, C.byref(prm), battles.ctypes.data_as(C.c_void_p), durations.ctypes.data_as(C.c_void_p),
                                                 results.ctypes.data_as(C.c_void_p), seeds.ctypes.data_as(C.c_void_p), n, outs, int(bool(solve_nash)),
                                                 streams.ctypes.data_as(C.c_void_p), trace.ctypes.data_as(C.c_void_p) if trace_levels else None,
                                                 int(trace_levels)))

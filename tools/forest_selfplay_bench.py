@@ -9,7 +9,10 @@ frames: every allocation and kernel load), then times ONE call with a host clock
 --rounds forest runs alternated with baseline runs (the baseline's runs are shared by the sizes of a workload); reported: the runs, the
 median, games/s and frames/s, the schedule counters, and -- at --nash-size -- one more forest run without the Nash solve, whose difference
 to the median is the host Nash solves' share of a call.  The share of the loop's own kernels is a separate rocprofv3 --kernel-trace
---stats run of `--child forest` (see --help of the child arguments), not made here.
+--stats run of `--child forest` (see --help of the child arguments), not made here.  --keep-node: the forest runs keep each game's tree
+between turns (a kept forest of --keep-arena nodes per tree, 0 = 4 * budget + 1); a run then also reports the keep-node ratio (updates that
+found their child / updates), the mean nodes carried into a turn's search, the trees dropped for want of room and the root mismatches; the
+cells are named <workload>+keep/<games>.  The baseline is not run with it.
 
   python tools/forest_selfplay_bench.py [--sizes 256,4096,65536] [--workloads pucb_default,ucb_fp] [--budget 256] [--rounds 3] [--out FILE]
 A run that is cut short keeps what it measured: --out is rewritten after every run, and a later run with the same --out goes on from it."""
@@ -48,8 +51,8 @@ def child(a):
     ev = w["eval"] if w["eval"] in ("mc", "poke-engine") else Network(ctx, path=os.path.join(ROOT, "tests", "golden", w["eval"]))
     teams, battle_seeds, seeds = draw(a.games, a.seed)
     if a.child == "forest":
-        forest = Forest(ctx, a.games, a.budget, contextual=w["bandit"] == "pucb")
-        kw = dict(c=w["c"], bandit=w["bandit"], evaluator=ev, policy_mode=w["mode"], forest=forest, solve_nash=not a.no_nash)
+        forest = Forest(ctx, a.games, a.budget, contextual=w["bandit"] == "pucb", keep_arena=a.keep_arena if a.keep_node else None)
+        kw = dict(c=w["c"], bandit=w["bandit"], evaluator=ev, policy_mode=w["mode"], forest=forest, solve_nash=not a.no_nash, keep_node=a.keep_node)
         forest_selfplay(ctx, teams, battle_seeds, seeds, a.budget, max_battle_length=2, **kw)
         ctx.synchronize()
         stats = {}
@@ -57,7 +60,11 @@ def child(a):
         out = forest_selfplay(ctx, teams, battle_seeds, seeds, a.budget, stats=stats, **kw)
         s = time.perf_counter() - t
         frames, kept = int(out[2][out[4] == 0].sum()), int((out[4] == 0).sum())
-        res = dict(form="forest", s=s, games=kept, frames=frames, dropped=a.games - kept, bytes=len(out[0]), solve_nash=not a.no_nash, **stats)
+        res = dict(form="forest", s=s, games=kept, frames=frames, dropped=a.games - kept, bytes=len(out[0]), solve_nash=not a.no_nash, keep_node=a.keep_node)
+        if a.keep_node:
+            res.update(keep_node_ratio=stats["nodes_kept"] / max(stats["rows"], 1), mean_kept_nodes_per_turn=stats["carried_nodes"] / max(stats["rows"], 1),
+                       trees_dropped=stats.pop("dropped"))
+        res.update(stats)
         forest.close()
     else:
         ctxs = [Context(0) for _ in range(16)]
@@ -75,10 +82,12 @@ def child(a):
     print("RESULT " + json.dumps(res), flush=True)
 
 
-def run_child(form, workload, games, budget, seed, no_nash=False, timeout=1100):
+def run_child(form, workload, games, budget, seed, no_nash=False, timeout=1100, keep_node=False, keep_arena=0):
     cmd = [sys.executable, os.path.abspath(__file__), "--child", form, "--workload", workload, "--games", str(games), "--budget", str(budget), "--seed", str(seed)]
     if no_nash:
         cmd.append("--no-nash")
+    if keep_node:
+        cmd += ["--keep-node", "--keep-arena", str(keep_arena)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
     lines = [x for x in out.stdout.splitlines() if x.startswith("RESULT ")]
     if out.returncode != 0 or not lines:
@@ -101,6 +110,8 @@ def main():
     ap.add_argument("--workload", default="ucb_fp")
     ap.add_argument("--games", type=int, default=256)
     ap.add_argument("--no-nash", action="store_true")
+    ap.add_argument("--keep-node", action="store_true")
+    ap.add_argument("--keep-arena", type=int, default=0)
     a = ap.parse_args()
     if a.child:
         return child(a)
@@ -125,20 +136,20 @@ def main():
     for workload in a.workloads.split(","):
         base = res["cells"].setdefault(workload + "/baseline", {"runs": []})
         for n in sizes:
-            cell = res["cells"].setdefault("%s/%d" % (workload, n), {"workload": workload, "games": n, "runs": []})
+            cell = res["cells"].setdefault("%s%s/%d" % (workload, "+keep" if a.keep_node else "", n), {"workload": workload, "games": n, "keep_node": a.keep_node, "runs": []})
             for k in range(a.rounds):
                 for which in (("forest", "baseline") if k % 2 == 0 else ("baseline", "forest")):
                     if late():
                         continue
                     if which == "forest" and len(cell["runs"]) <= k:
-                        cell["runs"].append(run_child("forest", workload, n, a.budget, a.seed))
+                        cell["runs"].append(run_child("forest", workload, n, a.budget, a.seed, keep_node=a.keep_node, keep_arena=a.keep_arena))
                         print("  %s N=%d forest run %d: %.2f s, %.1f games/s" % (workload, n, k, cell["runs"][-1]["s"], cell["runs"][-1]["games_per_s"]), file=sys.stderr, flush=True)
-                    if which == "baseline" and len(base["runs"]) <= k:
+                    if which == "baseline" and len(base["runs"]) <= k and not a.keep_node:
                         base["runs"].append(run_child("baseline", workload, a.baseline_games, a.budget, a.seed))
                         print("  %s baseline run %d: %.2f s, %.1f games/s" % (workload, k, base["runs"][-1]["s"], base["runs"][-1]["games_per_s"]), file=sys.stderr, flush=True)
                     save()
             if n == a.nash_size and "without_nash" not in cell and cell["runs"] and not late():
-                cell["without_nash"] = run_child("forest", workload, n, a.budget, a.seed, no_nash=True)
+                cell["without_nash"] = run_child("forest", workload, n, a.budget, a.seed, no_nash=True, keep_node=a.keep_node, keep_arena=a.keep_arena)
                 save()
             if cell["runs"]:
                 med = float(np.median([x["s"] for x in cell["runs"]]))
@@ -150,7 +161,7 @@ def main():
                     base.update(median_games_per_s=float(np.median([x["games_per_s"] for x in base["runs"]])), fastest_games_per_s=best)
                     cell["forest_median_beats_baseline_fastest"] = bool(cell["games_per_s"] > best)
             save()
-    claim = [res["cells"].get("%s/4096" % w, {}).get("forest_median_beats_baseline_fastest") for w in a.workloads.split(",")]
+    claim = [res["cells"].get("%s%s/4096" % (w, "+keep" if a.keep_node else ""), {}).get("forest_median_beats_baseline_fastest") for w in a.workloads.split(",")]
     res["claim"] = "at 4,096 games the forest loop's median games/s beats the baseline's fastest run: " + ", ".join(
         "%s: %s" % (w, "not measured" if c is None else c) for w, c in zip(a.workloads.split(","), claim))
     save()

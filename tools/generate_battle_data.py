@@ -4,13 +4,15 @@ files under --out.
 
   python tools/generate_battle_data.py --out DIR [--games N] [--batch B] [--teams FILE] [--budget K] [--bandit ucb-2.0 | pucb-1.5]
          [--eval mc | fp | NET.battle.net] [--discrete] [--policy-mode e] [--policy-temp 1] [--policy-min 0] [--max-battle-length L]
-         [--no-nash] [--seed S] [--file-mb 8]
+         [--no-nash] [--seed S] [--file-mb 8] [--keep-node [--keep-arena NODES]]
 
 --teams FILE: JSON {"teams": [[[species, move, move, move, move] x 6] ...]} by name, the layout of tests/golden/ou_sample_teams.json (the
 default: the reference's 16 sample teams); each game draws its two teams from the file with --seed's generator, a pair that fails the
 endless battle check is drawn again (generate.cc:222-225).  --batch games are resident at a time (one forest of that many trees).  A file
 is closed once it holds --file-mb MiB of whole records; names are <seed>_<index>.battle.data.  A game that reaches --max-battle-length
-frames is dropped, as generate drops it.  Prints games, frames, dropped games and seconds."""
+frames is dropped, as generate drops it.  --keep-node: each game's tree goes on into the next turn (generate.cc:324-333) on a kept forest
+of --keep-arena nodes per tree (0 = 4 * budget + 1); then the keep-node ratio is printed as generate prints it (updates that found their
+child / updates), with the trees dropped for want of room.  Prints games, frames, dropped games and seconds."""
 import argparse
 import os
 import sys
@@ -57,6 +59,8 @@ def main():
     ap.add_argument("--no-nash", action="store_true")
     ap.add_argument("--seed", type=int, default=0x0A4B)
     ap.add_argument("--file-mb", type=float, default=8.0)
+    ap.add_argument("--keep-node", action="store_true")
+    ap.add_argument("--keep-arena", type=int, default=0)
     a = ap.parse_args()
     name, _, c = a.bandit.partition("-")
     if name not in ("ucb", "pucb"):
@@ -73,9 +77,10 @@ def main():
     rng = np.random.default_rng(a.seed)
     os.makedirs(a.out, exist_ok=True)
     batch = max(1, min(a.batch, a.games))
-    forest = Forest(ctx, batch, a.budget, contextual=name == "pucb")
+    forest = Forest(ctx, batch, a.budget, contextual=name == "pucb", keep_arena=a.keep_arena if a.keep_node else None)
     limit = int(a.file_mb * (1 << 20))
     played = frames = dropped = files = 0
+    updates = updates_with_node = trees_dropped = 0
     pending = []
     t0 = time.perf_counter()
 
@@ -94,9 +99,13 @@ def main():
     while played < a.games:
         n = min(batch, a.games - played)
         teams, battle_seeds, seeds = draw_games(pool, n, rng)
+        stats = {}
         stream, offsets, n_frames, results, status = forest_selfplay(
             ctx, teams, battle_seeds, seeds, a.budget, c=float(c or 2.0), bandit=name, evaluator=evaluator, policy_mode=a.policy_mode,
-            policy_temp=a.policy_temp, policy_min=a.policy_min, max_battle_length=a.max_battle_length, forest=forest, solve_nash=not a.no_nash)
+            policy_temp=a.policy_temp, policy_min=a.policy_min, max_battle_length=a.max_battle_length, forest=forest, solve_nash=not a.no_nash,
+            keep_node=a.keep_node, stats=stats)[:5]
+        if a.keep_node:   # RuntimeData::update_with_node_counter / update_counter (generate.cc:412-416)
+            updates, updates_with_node, trees_dropped = updates + int(n_frames.sum()), updates_with_node + stats["nodes_kept"], trees_dropped + stats["dropped"]
         kept = status == 0
         pending += [stream[int(offsets[g]):int(offsets[g + 1])] for g in range(n) if kept[g]]
         played, frames, dropped = played + n, frames + int(n_frames[kept].sum()), dropped + int((~kept).sum())
@@ -105,6 +114,9 @@ def main():
     s = time.perf_counter() - t0
     print("games: %d, frames: %d, dropped: %d, files: %d, seconds: %.2f (%.1f games/s, %.0f frames/s)" % (played - dropped, frames, dropped, files, s,
                                                                                                        (played - dropped) / s, frames / s))
+    if a.keep_node:
+        print("keep node ratio: %g" % (updates_with_node / max(updates, 1)))
+        print("trees dropped for want of room: %d" % trees_dropped)
     forest.close()
     if net is not None:
         net.close()
