@@ -98,12 +98,19 @@ int oakgpu_set_standstill_skip(oakgpu_ctx *ctx, int on);
  * goes before a move, so both walks hold the move pipeline for well under half of the wave's lanes.  With below > 0 a lane's second
  * action waits for the wave's NEXT walk -- beside the other lanes' first actions of their next turn -- unless at least `below` lanes
  * of the wave want it now.  below = 0: off, both actions of a turn in one wave iteration; 1..64: carry (64: whenever any lane of
- * the wave has no second action to run).  Dry waves, adopting waves, resume / tail rounds and launches spread over part of their
- * lanes never carry, so every playout that is written out, parked or donated stands at a turn boundary.  Every playout executes
+ * the wave has no second action to run).  Dry waves (but see oakgpu_set_move_carry_dry), adopting waves, resume / tail rounds and
+ * launches spread over part of their lanes never carry, so every playout that is written out, parked or donated stands at a turn boundary.  Every playout executes
  * the same engine operations and draws in the same order: results never depend on it.  Range checked; applies to launches made
  * after the call (also OAKGPU_MOVE_CARRY at context creation).  Default OAKGPU_MOVE_CARRY_DEFAULT. */
 #define OAKGPU_MOVE_CARRY_DEFAULT 32
 int oakgpu_set_move_carry(oakgpu_ctx *ctx, int below);
+/* ... in DRY waves.  With below > 0 a bulk wave whose queue has run dry goes on carrying (at the threshold above) while at least
+ * `below` of its lanes play -- and no fewer than a regrouping or tail launch suspends at -- and runs the schedule without carrying
+ * below that; a wave flushes before it suspends, so every image is still a completed turn's.  below = 0: a dry wave never carries.
+ * Adopter waves never do.  No effect while oakgpu_set_move_carry is 0.  Results never depend on it.  Range checked; also
+ * OAKGPU_MOVE_CARRY_DRY at context creation.  Default OAKGPU_MOVE_CARRY_DRY_DEFAULT. */
+#define OAKGPU_MOVE_CARRY_DRY_DEFAULT 0
+int oakgpu_set_move_carry_dry(oakgpu_ctx *ctx, int below);
 /* Words of that block written by the queue kernel's standstill skip (cleared by every queue launch). */
 #define OAKGPU_CTL_FAST_FORWARDED 44 /* playouts whose inert standstill was taken in one go */
 #define OAKGPU_CTL_SKIPPED_STEPS 45  /* turn-steps those playouts skipped (they are part of steps_out) */

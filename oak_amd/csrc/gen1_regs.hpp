@@ -105,6 +105,12 @@ __device__ __forceinline__ void cswap_sides(bool c, SideR &a, SideR &b) {
   OAK_FOR_SIDE_FIELDS(X)
 #undef X
 }
+// the sides by PLAYER, whichever frame they stand in (c: the frame is flipped, a holds P2): copies for a reader that must leave a and b alone
+__device__ __forceinline__ void sides_by_player(bool c, const SideR &a, const SideR &b, SideR &p1, SideR &p2) {
+#define X(f) p1.f = c ? b.f : a.f; p2.f = c ? a.f : b.f;
+  OAK_FOR_SIDE_FIELDS(X)
+#undef X
+}
 
 // GIN_LDS: the lane's input battle lives in LDS (k_rollout_staged's staged copy) -- `gin` is then an LDS pointer and the immutable party
 // data is read with ds_read; as a generic pointer (flat loads that resolve to LDS) the staged kernel carried 44-54 spilled SGPRs.
@@ -329,7 +335,9 @@ struct EngineR {
     load_stored(F);
   }
   // registers + party LDS (+ immutable input fields) -> global AoS; frame must be normalised (S = P1, F = P2)
-  __device__ __forceinline__ void store_battle_global(uint8_t *battle384) {
+  __device__ __forceinline__ void store_battle_global(uint8_t *battle384) { store_battle_global(battle384, S, F); }
+  // ... from the sides by player (sides_by_player): the engine's own frame stays as it is (the party LDS takes the actives' mutable fields)
+  __device__ __forceinline__ void store_battle_global(uint8_t *battle384, const SideR &S, const SideR &F) {
     if (order0(S) != 0) writeback_stored(S);
     if (order0(F) != 0) writeback_stored(F);
     uint32_t *g = (uint32_t *)battle384;
@@ -1186,26 +1194,6 @@ struct EngineR {
     }
     return r;
   }
-  __device__ __forceinline__ uint32_t act_cheap(uint32_t choice) { // C_SWITCH or C_PASS
-    const bool replace = hp(S) == 0;
-    if ((choice & 3) == C_SWITCH) { OAK_SCOPE(PS_SWITCH_IN); switch_in(S, F, choice >> 2); }
-    return post_action(choice, replace, false);
-  }
-  __device__ __forceinline__ uint32_t act_move(uint32_t choice) { // C_MOVE
-    OAK_T0(t_em);
-    const bool replace = hp(S) == 0;
-    uint32_t mslot = choice >> 2;
-    if (last_sel(S) == M_Struggle) mslot = 0;
-    else if (mslot == 0) mslot = lm_index(absp(S));
-    OAK_T0(t_bm);
-    const int r = before_move();
-    OAK_T1(PS_BEFORE_MOVE, t_bm);
-    if (r == BM_ERR) return mk_result(R_ERROR, 0, 0);
-    if (r != BM_DONE) execute_selected(mslot, r == BM_SKIP_CAN, r == BM_SKIP_PP);
-    OAK_T1(PS_EXEC_MOVE, t_em);
-    OAK_T1K(PS_EXEC_MOVE_K0, t_em);
-    return post_action(choice, replace, true);
-  }
 
   // ---- pkmn_gen1_battle_update in FRAME terms: cS / cF are the choices of whoever currently sits in S / F
   // (absp() tells which player that is).  The frame is left wherever the turn ends -- callers that need
@@ -1255,7 +1243,9 @@ struct EngineR {
     }
     pc = f_first ? cF : cS;
     qc = f_first ? cS : cF;
-    cswap_sides(f_first, S, F);
+    // (lane-masked v_swap, in place: as two selects per field the new S comes out in the selects' temporaries, and a caller that keeps
+    // the state in a loop moves all 18 words back to where the loop holds them)
+    if (f_first) swap_sides(S, F);
     if constexpr (TRACK_ACTIONS) { uint64_t t = f_first ? actF : actS; actF = f_first ? actS : actF; actS = t; }
     OAK_T1(PS_ORDER, t_ord);
     return 0;
@@ -1271,10 +1261,29 @@ struct EngineR {
   }
 
   // A turn in pieces, for a caller that drives it one action at a time (k_rollout_queue lets a lane's second action wait for the
-  // wave's next pass through the action code): turn_prologue above; act = this lane's pending action `pc` (act_move / act_cheap),
+  // wave's next pass through the action code): turn_prologue above; act = this lane's pending action `pc` (a move, a switch or a pass),
   // hand_over = the other side becomes the actor and `pc` / `qc` change places -- the turn goes on while the result is 0 and the
   // new `pc` is no pass; turn_finish = the turn's end.  update_frame is these in a row.
-  __device__ __forceinline__ uint32_t act(uint32_t choice) { return (choice & 3) == C_MOVE ? act_move(choice) : act_cheap(choice); }
+  // act: ONE copy of post_action behind every kind of action.  (As act_move / act_cheap with a post_action each, a wave whose lanes
+  // held moves and switches walked the faint and residual checks twice, and the two returns met in a merge of the whole mover's side:
+  // 21 + 26 register moves around every walk of k_rollout_queue; round 18.)
+  __device__ __forceinline__ uint32_t act(uint32_t choice) {
+    const uint32_t hp0 = hp(S); // (the mover's hp before the action: 0 = it replaces a fainted Pokemon)
+    if ((choice & 3) == C_MOVE) {
+      OAK_T0(t_em);
+      uint32_t mslot = choice >> 2;
+      if (last_sel(S) == M_Struggle) mslot = 0;
+      else if (mslot == 0) mslot = lm_index(absp(S));
+      OAK_T0(t_bm);
+      const int r = before_move();
+      OAK_T1(PS_BEFORE_MOVE, t_bm);
+      if (r == BM_ERR) return mk_result(R_ERROR, 0, 0);
+      if (r != BM_DONE) execute_selected(mslot, r == BM_SKIP_CAN, r == BM_SKIP_PP);
+      OAK_T1(PS_EXEC_MOVE, t_em);
+      OAK_T1K(PS_EXEC_MOVE_K0, t_em);
+    } else if ((choice & 3) == C_SWITCH) { OAK_SCOPE(PS_SWITCH_IN); switch_in(S, F, choice >> 2); }
+    return post_action(choice, hp0 == 0, (choice & 3) == C_MOVE); // (from `choice` again: a lane mask kept across the move pipeline is two SGPRs)
+  }
   __device__ __forceinline__ void hand_over(uint32_t &pc, uint32_t &qc) {
     next_actor();
     const uint32_t t = pc; pc = qc; qc = t;

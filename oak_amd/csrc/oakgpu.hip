@@ -353,6 +353,7 @@ struct RoundArgs {
   uint32_t no_skip;         // 1: a proven inert standstill is played turn by turn like everything else (oakgpu_set_standstill_skip: A/B)
   uint32_t *stats;          // words 44-45 of the context's control block: {playouts fast-forwarded, turn-steps skipped}
   uint32_t move_carry;      // 0..64 (oakgpu_set_move_carry): a turn's second action waits for the wave's next action pass unless this many lanes want it now
+  uint32_t move_carry_dry;  // 0..64 (oakgpu_set_move_carry_dry): a dry bulk wave goes on carrying while at least this many of its lanes play; 0 = a dry wave never carries
 };
 
 // One launch drains a GROUP of independent batches (oakgpu_rollout_group_dev): the queue hands out GLOBAL playout
@@ -518,7 +519,7 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
 #define COLD_GU(field) COLD_U32(offsetof(ColdArgs, g) + offsetof(GroupArgs, field))
   // (wave-uniform booleans live as BITS of one scalar word: as `bool`s each is a 64-bit lane mask, two SGPRs, and the turn loop
   // has none to spare)
-  constexpr uint32_t U_RESUME = 1, U_PREP = 2, U_ADOPTER = 4, U_DRY = 8, U_ADOPTING = 16, U_ANY_PLAYING = 32, U_NO_SKIP = 64;
+  constexpr uint32_t U_RESUME = 1, U_PREP = 2, U_ADOPTER = 4, U_DRY = 8, U_ADOPTING = 16, U_ANY_PLAYING = 32, U_NO_SKIP = 64, U_CARRIED = 128, U_MIGRATE = 1u << 11;
   uint32_t ust = (COLD_QU(list_in) | COLD_U32(offsetof(ColdArgs, q) + offsetof(RoundArgs, list_in) + 4)) != 0 ? U_RESUME : 0u; // a later round: playouts come from the previous round's suspended list
 #define IS_RESUME ((ust & U_RESUME) != 0)
 #define IS_PREP ((ust & U_PREP) != 0)
@@ -551,9 +552,9 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
   // stop changing any hp at a median of turn-step 85 (p90 160) -- from then on they are the stalemates of k_queue_order's comment --
   // while an ordinary playout almost never goes 40 turn-steps without its actives' {slot, hp} changing.  `stale` = a 24-bit
   // signature of both actives (hp xor, slot sum: symmetric, the frame may be swapped) | the turn-steps it has stood still << 24.
-  const uint32_t n_adopt = COLD_QU(n_adopters), long_steps = COLD_QU(long_steps);
+  const uint32_t long_steps = COLD_QU(long_steps);
   uint32_t stale = 0;
-  if (n_adopt != 0 && blockIdx.x < n_adopt) ust |= U_ADOPTER;
+  { const uint32_t n_adopt = COLD_QU(n_adopters); if (n_adopt != 0) ust |= blockIdx.x < n_adopt ? U_MIGRATE | U_ADOPTER : U_MIGRATE; } // (the count itself is read where an adopter needs it)
 #define IS_ADOPTER ((ust & U_ADOPTER) != 0)
 #define IS_ADOPTING ((ust & U_ADOPTING) != 0) // adopter: a donation has been seen, no more playouts from the main queue
 #define ANY_PLAYING ((ust & U_ANY_PLAYING) != 0)
@@ -584,7 +585,7 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
           const uint32_t kk = t > hh ? min(t - hh, (uint32_t)__popcll(mask)) : 0u;
           if (!kk) {
             // every bulk wave has left (a wave's last donation is complete before it counts itself out) and nothing is waiting
-            if (__hip_atomic_load(ctl + 2, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - n_adopt &&
+            if (__hip_atomic_load(ctl + 2, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - COLD_QU(n_adopters) &&
                 __hip_atomic_load(ctl + 0, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == hh &&
                 __hip_atomic_load(ctl + 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == hh) closed |= 1;
             break;
@@ -694,7 +695,7 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
     // and everything that retires, parks or refills a lane wait for the turn's end.  Per lane the engine operations and draws are the
     // same sequence as ever.  The first trip through the move pipeline takes every pending move (a switch in front of a move has
     // run by then).  The second trip takes what is still pending -- if at least `carry_below` (ust bits
-    // 24-31; 0 = always, the schedule without carrying) lanes want it, or if the wave FLUSHES: it is dry or an adopter that adopts
+    // 24-31; 0 = always, the schedule without carrying) lanes want it, or if the wave FLUSHES: it is dry (and below its dry-carry threshold: U_CARRIED below) or an adopter that adopts
     // (resume, tail and spread launches have carry_below 0).  So a wave that can suspend, a wave that leaves and every lane that
     // is written out stands at a turn boundary: the drain, the adopters and the images are what they were.
     constexpr uint32_t T_PEND = 0x100u, T_DONE = 0x200u; // during the walks the low byte of `result` is the turn's result so far
@@ -746,9 +747,18 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
       // action: the one trip through the move pipeline that every iteration makes.  The third walk is the second trip, for what is
       // still pending (move + move turns): only if `carry_below` lanes want it.  A wave that does not carry (threshold 0, or a
       // flush) skips the first walk and always takes the third: the schedule of update_frame.
-      const bool carrying = (ust >> 24) != 0 && !(ust & (U_DRY | U_ADOPTING)); // wave-uniform
+      // (wave-uniform, kept as a bit of `ust` like the other flags: U_CARRIED = this iteration carries and may leave lanes in mid-turn)
+      if ((ust >> 24) != 0 && !(ust & (U_DRY | U_ADOPTING))) ust |= U_CARRIED; else ust &= ~U_CARRIED;
+      // (round 18: a dry BULK wave goes on carrying while at least `move_carry_dry` of its lanes play -- the host makes that no fewer than
+      // a regrouping or tail launch suspends at: a wave about to suspend flushes first.  The threshold is read where it is needed: a dry
+      // wave's iterations)
+      if ((ust >> 24) != 0 && IS_DRY && !IS_ADOPTER) {
+        const uint32_t dry_below = COLD_QU(move_carry_dry);
+        if (dry_below != 0 && (uint32_t)__popcll(__ballot(playing)) >= dry_below) ust |= U_CARRIED;
+      }
+#define CARRYING ((ust & U_CARRIED) != 0)
 #pragma unroll 1
-      for (uint32_t walk = carrying ? 0u : 1u;; ++walk) {
+      for (uint32_t walk = CARRYING ? 0u : 1u;; ++walk) {
         const uint32_t c = (result >> 16) & 0xFFu;
         if ((result & T_PEND) && (walk != 0 || (c & 3) != C_MOVE)) {
           OAK_SET_K(e, walk ? walk - 1 : 0);
@@ -760,7 +770,7 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
         if (walk == 2) break;
         if (walk == 1) {
           const uint32_t want = (uint32_t)__popcll(__ballot((result & T_PEND) != 0));
-          if (want == 0 || (carrying && want < (ust >> 24))) break;
+          if (want == 0 || (CARRYING && want < (ust >> 24))) break;
         }
       }
       // (a lane that is still pending is carried as it stands: low byte 0, still playing)
@@ -784,12 +794,17 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
     }
     // wave-uniform: the queue is dry and too few lanes are still playing -> hand them to the next round
     const uint64_t still = __ballot(playing);
-    const bool suspend = IS_DRY && still != 0 && (uint32_t)__popcll(still) < suspend_below;
-    const bool lng = n_adopt != 0 && !IS_ADOPTER && playing && !(result & T_PEND) && (steps >= (long_steps & 0xFFFFu) || (stale >> 24) >= (long_steps >> 16)); // a bulk wave's long (or standing-still) playout: to the adopters
+    // (a lane in mid-turn -- a dry wave that carried in this iteration -- has no image to park: the wave flushes in its next iteration, then suspends)
+    const bool suspend = IS_DRY && !(ust & U_CARRIED) && still != 0 && (uint32_t)__popcll(still) < suspend_below;
+    const bool lng = (ust & U_MIGRATE) != 0 && !IS_ADOPTER && playing && !(result & T_PEND) && (steps >= (long_steps & 0xFFFFu) || (stale >> 24) >= (long_steps >> 16)); // a bulk wave's long (or standing-still) playout: to the adopters
     if (idx != DONE && idx != NONE && (!playing || suspend || lng)) { // retire the lane: publish a finished playout / park a suspended or donated one
       OAK_SCOPE(PS_PUBLISH);
       const bool fin = !playing;
-      e.normalize();
+      // the image is written from COPIES of the sides by player: normalising `e` in place (lane-masked) made the whole engine state a
+      // value that differs between the two ways out of this branch, and the wave copied it to a second register set and back in
+      // every iteration (round 18); the engine's own frame stays where the turn left it -- a parked or finished lane's is dead
+      SideR P1, P2;
+      sides_by_player(ER::absp(e.S) != 0, e.S, e.F, P1, P2);
       const BatchDesc *bd = find_batch(cold, idx);
       const uint32_t k = idx - bd->start;
       if (fin) bd->results_out[k] = (uint8_t)result; else COLD_Q(sres, uint8_t *)[idx] = (uint8_t)result;
@@ -801,11 +816,11 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
       pdst[1] = g.s1;
       uint32_t *ddst = fin ? (bd->durations_out ? (uint32_t *)bd->durations_out + 2 * (size_t)k : nullptr) : COLD_Q(sd, uint32_t *) + 2 * (size_t)idx;
       if (ddst) {
-        ddst[0] = e.S.dur;
-        ddst[1] = e.F.dur;
+        ddst[0] = P1.dur;
+        ddst[1] = P2.dur;
       }
       uint8_t *bdst = fin ? (bd->battles_out ? bd->battles_out + (size_t)k * 384 : nullptr) : COLD_Q(sb, uint8_t *) + (size_t)idx * 384;
-      if (bdst) e.store_battle_global(bdst);
+      if (bdst) e.store_battle_global(bdst, P1, P2);
       idx = fin ? NONE : idx;
     }
     const uint64_t dm = __ballot(lng);
@@ -831,7 +846,7 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
       break;
     }
   }
-  if (n_adopt != 0 && !IS_ADOPTER && wl == 0) atomicAdd(COLD_Q(adopt_ctl, uint32_t *) + 2, 1u); // a bulk wave has left: it donates no more
+  if ((ust & U_MIGRATE) != 0 && !IS_ADOPTER && wl == 0) atomicAdd(COLD_Q(adopt_ctl, uint32_t *) + 2, 1u); // a bulk wave has left: it donates no more
   OAK_TL(2, wall_clock64());
 #ifdef OAKGPU_TIMELINE
   OAK_TL(4, tl_steps);
@@ -848,6 +863,7 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
 #undef IS_ADOPTER
 #undef IS_ADOPTING
 #undef ANY_PLAYING
+#undef CARRYING
 
 // ---- root-parallel search steps in SLICES (BASELINE configs[3]: 256 roots x 4,096 playouts per search step) -----------------
 // A search step of root-parallel MCTS hands every root `reps` fresh playouts (run_root_iteration's prep, mcts.h:250-263, then the
@@ -1578,6 +1594,7 @@ struct oakgpu_ctx {
   int queue_order;        // 1 (default): a saturated launch hands its playouts out likely-longest first (k_queue_order)
   int standstill_skip;    // 1 (default): the queue kernel takes a PROVEN inert standstill to its last turn-step in one go (exact); 0: plays every turn
   int move_carry;         // 0..64 (oakgpu_set_move_carry): the queue kernel's move carry, 0 = a turn's two actions in one wave iteration
+  int move_carry_dry;     // 0..64 (oakgpu_set_move_carry_dry): a dry bulk wave carries while at least this many lanes play, 0 = never
   uint32_t *d_order;      // total entries
   size_t order_n;
   uint32_t order_pair = 0;      // k_queue_order's two counters: control words 32-33 and 34-35 in turn (each launch clears the next one's)
@@ -1773,6 +1790,8 @@ int oakgpu_create(oakgpu_ctx **out, int device) {
   if (const char *env = getenv("OAKGPU_STANDSTILL_SKIP")) c->standstill_skip = atoi(env) != 0;
   c->move_carry = OAKGPU_MOVE_CARRY_DEFAULT;
   if (const char *env = getenv("OAKGPU_MOVE_CARRY")) c->move_carry = atoi(env) < 0 ? 0 : atoi(env) > 64 ? 64 : atoi(env);
+  c->move_carry_dry = OAKGPU_MOVE_CARRY_DRY_DEFAULT;
+  if (const char *env = getenv("OAKGPU_MOVE_CARRY_DRY")) c->move_carry_dry = atoi(env) < 0 ? 0 : atoi(env) > 64 ? 64 : atoi(env);
   c->migrate = 1;
   c->migrate_steps = 300;
   c->migrate_adopters = 0;
@@ -1883,6 +1902,12 @@ int oakgpu_set_standstill_skip(oakgpu_ctx *c, int on) {
 int oakgpu_set_move_carry(oakgpu_ctx *c, int below) {
   if (!c || below < 0 || below > 64) return bad("oakgpu_set_move_carry: below must be 0 (off) .. 64 lanes");
   c->move_carry = below;
+  return 0;
+}
+
+int oakgpu_set_move_carry_dry(oakgpu_ctx *c, int below) {
+  if (!c || below < 0 || below > 64) return bad("oakgpu_set_move_carry_dry: below must be 0 (off) .. 64 lanes");
+  c->move_carry_dry = below;
   return 0;
 }
 
@@ -2095,6 +2120,7 @@ static int launch_group(oakgpu_ctx *c, const oak::BatchDesc *descs, uint32_t cou
     q.count_out = c->d_queue + 2 * r + 1;
     q.sb = sb; q.sd = sd; q.sres = sres;
     q.suspend_below = r + 1 < rounds ? (uint32_t)(tail_pack ? c->tail_below : c->suspend_below) : 0u;
+    q.move_carry_dry = c->move_carry_dry > 0 ? std::max((uint32_t)c->move_carry_dry, q.suspend_below) : 0u; // (a wave that could suspend does not carry)
     q.queue = c->d_heads + (size_t)r * oak::QUEUE_HEADS * oak::QUEUE_HEAD_STRIDE;
     q.lanes = (tail_pack && r > 0) ? (uint32_t)c->tail_lanes : (r == 0 ? spread : 0u);
     hipLaunchKernelGGL((oak::k_rollout_queue<64, 4>), dim3(waves), dim3(64), lq, c->stream, g, q);

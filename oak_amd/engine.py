@@ -107,6 +107,11 @@ class Context:
         0 = off, at most 64); results never change."""
         _lib.check(self.lib.oakgpu_set_move_carry(self.handle, int(below)))
 
+    def set_move_carry_dry(self, below=0):
+        """A bulk wave whose queue has run dry goes on carrying while at least `below` of its lanes play (oakgpu_set_move_carry_dry;
+        0 = a dry wave never carries, at most 64); results never change."""
+        _lib.check(self.lib.oakgpu_set_move_carry_dry(self.handle, int(below)))
+
     def set_standstill_skip(self, on=True):
         """The queue kernel's exact fast-forward of proven inert standstills (oakgpu_set_standstill_skip); results never change."""
         _lib.check(self.lib.oakgpu_set_standstill_skip(self.handle, 1 if on else 0))
