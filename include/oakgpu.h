@@ -918,7 +918,31 @@ int oakgpu_selfplay_pick_host(uint32_t m, uint32_t n, const uint64_t *visit_matr
  * _last_stats: turns looped, p1 rows searched, p2 rows searched (summed over the turns), host reads of the per-turn record.
  * oakgpu_match_pick_host (no GPU involved) is ONE seat's pick and early-stop sign from one root output: side 0 / 1, the root matrices and
  * iterations, that side's nash and prior (nullable = 0), the seat's mode / temp / min, early_stop, rng in and out -> policy[9], index, ev,
- * sign.  A zeroed policy fails ("zero policy"). */
+ * sign.  A zeroed policy fails ("zero policy").
+ *   Records (vs.cc:221-222,308-309,329-333,380-395: the p1/ and p2/ `.battle.data` of a match).  oakgpu_forest_match_set_records(forest, 1)
+ *   switches recording on for the forest's later match calls (default 0; refused by name for a null forest and for `on` outside 0 and 1;
+ *   nothing else about the forest refuses it).  With it off a call is exactly the call described above: the same launches, host reads
+ *   (_last_stats), memory and outputs.  With it on every game is also written as TWO CompressedFrames records, one per seat, and the
+ *   call ends with each seat's records packed into one contiguous `.battle.data` byte stream in game order, resident in the forest's
+ *   workspace until the forest's next match call; no host read per turn is added.
+ *     A record is {u32 bytes, u16 frames, the game's INPUT battle (384 bytes; durations have no field, as in vs), result byte, updates}.
+ *     Every turn that makes its update -- the turns turns_out counts -- adds one update to each seat's record, encoded as self-play's
+ *     (selfplay_pick.hpp's encode_update, without contraction), both with the turn's JOINT choice (c1, c2).  A searched seat's update
+ *     holds its own search's output: the root's m and n, its iterations, empirical_value, nash_value and both sides' Nash strategies (zeros
+ *     without solve_nash), both sides' empirical strategies from process_output.  An unsearched seat's update (a seat with one choice) holds
+ *     the real m and n, iterations = 0 and 0 for both values and all four strategies.  THIS DEPARTS FROM THE REFERENCE, which stores a
+ *     value-initialised MCTS::Output there: its k = 0 makes the head byte 0xFF and the update 11 bytes long, which no reader can parse,
+ *     the reference's own included (compressed-frame.h:99,126-127 reads it as m = n = 16).  The form here is well-formed: a loader's
+ *     min_iterations filter skips it and a replay walks through it.  Both seats' updates of a turn have the same length, so the two
+ *     streams share offsets and frame counts.
+ *     An early-stop turn and a zeroed-policy turn add nothing.  Status OK: the record's result byte is the terminal byte.  EARLY_STOP: the
+ *     frames up to the stop, result byte 1 or 2.  MAX_TURNS and ZERO_POLICY: NO record -- zero bytes in both streams, the frame count
+ *     still reported -- as forest self-play drops its MAX_LENGTH / ZERO_POLICY games.  A game whose input result is terminal: a record
+ *     with 0 frames.  Independence holds as stated above: game g's two records depend on its own inputs and the parameters only.
+ *   oakgpu_forest_match_records copies seat `seat`'s (0 = p1, 1 = p2) stream of the forest's last match call out, with the shape and
+ *   nullable-output rules of oakgpu_forest_selfplay_records: stream nullable (*bytes alone is the size query), offsets[n + 1],
+ *   n_frames[n] (= turns_out), results[n], status[n] (OAKGPU_FM_*), to device memory with to_device != 0.  It fails by name when that
+ *   call was made with recording off (or none was made), and for a seat outside 0 and 1. */
 #define OAKGPU_FM_OK 0
 #define OAKGPU_FM_MAX_TURNS 1
 #define OAKGPU_FM_ZERO_POLICY 2
@@ -945,6 +969,9 @@ int oakgpu_forest_match(oakgpu_forest *forest, const oakgpu_forest_match_params 
                         const uint8_t *results_in, const uint64_t *seeds, uint32_t n, uint8_t *results_out, uint32_t *turns_out,
                         uint8_t *status_out, oakgpu_match_turn *turn_log, uint64_t counts_out[4]);
 int oakgpu_forest_match_last_stats(const oakgpu_forest *forest, uint64_t out[4]);
+int oakgpu_forest_match_set_records(oakgpu_forest *forest, int on);
+int oakgpu_forest_match_records(oakgpu_forest *forest, int seat, uint8_t *stream, size_t capacity, size_t *bytes, uint64_t *offsets, uint32_t *n_frames,
+                                uint8_t *results, uint8_t *status, int to_device);
 int oakgpu_match_pick_host(int side, uint32_t m, uint32_t n, const uint64_t *visit_matrix, const double *value_matrix, uint64_t iterations,
                            const double *nash, const double *prior, const char *policy_mode, double policy_temp, double policy_min,
                            double early_stop, uint64_t *rng, double *policy, int32_t *index, double *empirical_value, int32_t *sign);

@@ -417,19 +417,27 @@ private:
 // Matches between two search agents over the forest search (include/oakgpu.h: oakgpu_forest_match*): n games at once, resident on the
 // device, from the caller's states; seat p1 and seat p2 each search with their own parameters and network and play their own side's
 // move -- the per-game loop of vs.cc:230-345 with a budget.  status: OAKGPU_FM_*; log: n x params.log_turns records, game-major, 0xFF
-// bytes where no game came.
+// bytes where no game came.  play(..., records = true) also returns each seat's `.battle.data` byte stream of the games (vs.cc:380-395: what
+// `vs` saves under p1/ and p2/), in game order with offsets[n + 1] into it; a game cut at max_turns or stopped by a zeroed policy has zero
+// bytes, an unsearched seat's update has iterations 0 (include/oakgpu.h).
 class ForestMatch {
 public:
+  struct Records {
+    std::vector<uint8_t> stream;
+    std::vector<uint64_t> offsets;
+    std::vector<uint32_t> n_frames;
+  };
   struct Result {
     std::vector<uint8_t> results, status;
     std::vector<uint32_t> turns;
     std::vector<oakgpu_match_turn> log;
     std::array<uint64_t, 4> counts{}; // wins, ties, losses of seat p1 (early stops included), stopped at max_turns
     std::array<uint64_t, 4> stats{};  // turns looped, p1 rows searched, p2 rows searched, host reads of the per-turn record
+    std::array<Records, 2> records;   // seat p1's and seat p2's; empty without records
   };
   explicit ForestMatch(SearchForest &forest) : forest_{forest} {}
   // params.p1 / p2 .net: the seats' network handles (Network::get()) or null; one seed per start state
-  Result play(const oakgpu_forest_match_params &params, const std::vector<Leaf> &starts, const std::vector<uint64_t> &seeds) {
+  Result play(const oakgpu_forest_match_params &params, const std::vector<Leaf> &starts, const std::vector<uint64_t> &seeds, bool records = false) {
     if (seeds.size() != starts.size()) throw std::runtime_error{"oakgpu: ForestMatch::play: one seed per start state"};
     const uint32_t n = (uint32_t)starts.size();
     std::vector<uint8_t> b((size_t)n * OAKGPU_BATTLE_SIZE), d((size_t)n * OAKGPU_DURATIONS_SIZE), r(n);
@@ -442,9 +450,20 @@ public:
     out.results.assign(n, 0); out.status.assign(n, 0); out.turns.assign(n, 0);
     out.log.resize((size_t)n * params.log_turns);
     if (!out.log.empty()) std::memset(out.log.data(), 0xFF, out.log.size() * sizeof(oakgpu_match_turn));
+    check(oakgpu_forest_match_set_records(forest_.get(), records ? 1 : 0));
     check(oakgpu_forest_match(forest_.get(), &params, b.data(), d.data(), r.data(), seeds.data(), n, out.results.data(), out.turns.data(), out.status.data(),
                               out.log.empty() ? nullptr : out.log.data(), out.counts.data()));
     check(oakgpu_forest_match_last_stats(forest_.get(), out.stats.data()));
+    for (int seat = 0; seat < 2 && records; ++seat) {
+      Records &rec = out.records[seat];
+      size_t bytes = 0;
+      check(oakgpu_forest_match_records(forest_.get(), seat, nullptr, 0, &bytes, nullptr, nullptr, nullptr, nullptr, 0));
+      rec.stream.resize(bytes);
+      rec.offsets.assign((size_t)n + 1, 0); rec.n_frames.assign(n, 0);
+      uint8_t none = 0;
+      check(oakgpu_forest_match_records(forest_.get(), seat, bytes ? rec.stream.data() : &none, bytes, &bytes, rec.offsets.data(), rec.n_frames.data(), nullptr,
+                                        nullptr, 0));
+    }
     return out;
   }
 

@@ -36,6 +36,7 @@ SYMBOLS = [
     "oakgpu_forest_selfplay_check", "oakgpu_forest_selfplay_dev", "oakgpu_forest_selfplay_records", "oakgpu_forest_selfplay", "oakgpu_forest_selfplay_last_stats",
     "oakgpu_selfplay_pick_host",
     "oakgpu_forest_match_check", "oakgpu_forest_match_dev", "oakgpu_forest_match", "oakgpu_forest_match_last_stats", "oakgpu_match_pick_host",
+    "oakgpu_forest_match_set_records", "oakgpu_forest_match_records",
     "oakgpu_forest_create_kept", "oakgpu_forest_create_kept_check", "oakgpu_forest_kept_tree_bytes", "oakgpu_forest_advance_dev", "oakgpu_forest_advance",
     "oakgpu_forest_search_kept_dev", "oakgpu_forest_search_kept", "oakgpu_forest_keep_stats", "oakgpu_forest_mismatch", "oakgpu_forest_node_counts",
     "oakgpu_forest_selfplay_nodes_kept", "oakgpu_forest_selfplay_keep_stats",
@@ -353,6 +354,8 @@ def load():
     lib.oakgpu_forest_match_dev.argtypes = [vp, C.POINTER(ForestMatchParams), vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
     lib.oakgpu_forest_match.argtypes = [vp, C.POINTER(ForestMatchParams), vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
     lib.oakgpu_forest_match_last_stats.argtypes = [vp, C.POINTER(u64 * 4)]
+    lib.oakgpu_forest_match_set_records.argtypes = [vp, i32]
+    lib.oakgpu_forest_match_records.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, vp, vp, i32]
     lib.oakgpu_match_pick_host.argtypes = [i32, u32, u32, vp, vp, u64, vp, vp, C.c_char_p, C.c_double, C.c_double, C.c_double, C.POINTER(u64), vp,
                                            C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     _lib = lib

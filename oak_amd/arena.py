@@ -11,6 +11,7 @@ Nothing here computes on the CPU but the bookkeeping of a finished batch."""
 import contextlib
 import ctypes as C
 import math
+import os
 
 import numpy as np
 
@@ -153,7 +154,31 @@ def match_pick_host(side, m, n, visit_matrix, value_matrix, iterations, rng, nas
     return {"policy": pol, "index": idx.value, "empirical_value": ev.value, "sign": sign.value, "rng": state.value}
 
 
-def search_games(ctx, seats, battles, durations, results, seeds, forest=None, max_turns=1000, early_stop=0.0, log_turns=0, solve_nash=True, stats=None):
+def _match_records(ctx, forest, n, dev=None):
+    """Both seats' records of the forest's last match call (oakgpu_forest_match_records): (p1, p2), each a dict of stream (bytes; with
+    dev a uint8 tensor there), offsets [n + 1] and n_frames [n]."""
+    lib, seats = ctx.lib, []
+    for seat in (0, 1):
+        size = C.c_size_t(0)
+        _lib.check(lib.oakgpu_forest_match_records(forest.handle, seat, None, 0, C.byref(size), None, None, None, None, 0))
+        if dev is None:
+            stream, offsets, n_frames = np.zeros(max(size.value, 1), np.uint8), np.zeros(n + 1, np.uint64), np.zeros(max(n, 1), np.uint32)
+            vp = lambda a: a.ctypes.data_as(C.c_void_p)
+            _lib.check(lib.oakgpu_forest_match_records(forest.handle, seat, vp(stream), size.value, C.byref(size), vp(offsets), vp(n_frames), None, None, 0))
+            seats.append(dict(stream=stream[:size.value].tobytes(), offsets=offsets, n_frames=n_frames[:n]))
+        else:
+            import torch
+            stream = torch.zeros(max(size.value, 1), dtype=torch.uint8, device=dev)
+            offsets, n_frames = torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+            with _ordered(ctx, dev):
+                _lib.check(lib.oakgpu_forest_match_records(forest.handle, seat, stream.data_ptr(), size.value, C.byref(size), offsets.data_ptr(),
+                                                           n_frames.data_ptr(), None, None, 1))
+            seats.append(dict(stream=stream[:size.value], offsets=offsets, n_frames=n_frames[:n]))
+    return tuple(seats)
+
+
+def search_games(ctx, seats, battles, durations, results, seeds, forest=None, max_turns=1000, early_stop=0.0, log_turns=0, solve_nash=True, stats=None,
+                 records=False):
     """n whole games from the given states between two SEARCH agents on the forest search (oakgpu_forest_match*): seats = (p1, p2), each a
     dict as _match_seat takes it; seeds uint64[n], one per game.  forest: None (one made for this call, contextual when a seat is PUCB)
     or a search.Forest to reuse; stats: optional dict that receives turns, p1_rows, p2_rows, host_reads.
@@ -161,7 +186,10 @@ def search_games(ctx, seats, battles, durations, results, seeds, forest=None, ma
     numpy arrays in -> numpy arrays out; torch tensors on the GPU in (seeds int64 bit patterns) -> torch tensors out, nothing leaves the
     device but the counters.  Returns a dict: results uint8[n], turns uint32[n] (int32 for torch), status uint8[n] (FM_STATUS), counts =
     (wins, ties, losses of seat p1 with early stops, stopped at max_turns), log: TURN_DTYPE [n, log_turns] prefilled with 0xFF bytes
-    (torch: uint8 [n, log_turns, 24]); None without log_turns."""
+    (torch: uint8 [n, log_turns, 24]); None without log_turns.
+    records: the dict gains records = (p1, p2), each seat's `.battle.data` of the games (vs.cc:380-395) as a dict: stream (bytes, or a uint8
+    tensor on the device), offsets [n + 1] and n_frames [n]; a game cut at max_turns or stopped by a zeroed policy has zero bytes in both,
+    a seat that was not searched in a turn has iterations 0 there (include/oakgpu.h)."""
     from .search import Forest
     p = _match_params(seats, max_turns, early_stop, log_turns, solve_nash)
     counts = (C.c_uint64 * 4)()
@@ -172,6 +200,8 @@ def search_games(ctx, seats, battles, durations, results, seeds, forest=None, ma
         forest = Forest(ctx, max(n, 1), max(int(seats[0]["iterations"]), int(seats[1]["iterations"]), 1),
                         contextual="pucb" in (seats[0].get("bandit"), seats[1].get("bandit")))
     try:
+        if records or not own:                   # (a forest of the caller's keeps its switch: set it either way)
+            _lib.check(ctx.lib.oakgpu_forest_match_set_records(forest.handle, int(bool(records))))
         if not on_device:
             battles = np.ascontiguousarray(battles, dtype=np.uint8).reshape(n, 384)
             durations = np.ascontiguousarray(durations, dtype=np.uint8).reshape(n, 8)
@@ -196,6 +226,8 @@ def search_games(ctx, seats, battles, durations, results, seeds, forest=None, ma
                                                      ptr(out["turns"]), ptr(out["status"]), ptr(out["log"]), counts)
         _lib.check(rc)
         out["counts"] = tuple(int(x) for x in counts)
+        if records:
+            out["records"] = _match_records(ctx, forest, n, dev if on_device else None)
         if stats is not None:
             st = (C.c_uint64 * 4)()
             _lib.check(ctx.lib.oakgpu_forest_match_last_stats(forest.handle, C.byref(st)))
@@ -206,14 +238,17 @@ def search_games(ctx, seats, battles, durations, results, seeds, forest=None, ma
             forest.close()
 
 
-def search_match(ctx, agent_a, agent_b, teams, games, seed, mirror=False, max_turns=1000, early_stop=10.0, solve_nash=True, return_games=False):
+def search_match(ctx, agent_a, agent_b, teams, games, seed, mirror=False, max_turns=1000, early_stop=10.0, solve_nash=True, return_games=False,
+                 records_dir=None):
     """`games` matches between search agents A and B (dicts as _match_seat takes them; an evaluator may also be a `.battle.net` path, loaded
     for the call, "discrete": True choosing the int8 form) as vs.cc:355-377 plays them: per match two teams drawn from `teams` (uint8
     [T, 6, 5]; one team for both sides with mirror), played in both seatings with the agents swapped unless mirror is set.  A drawn pair
     that fails the endless-battle check (oakgpu_endless_battle_check, on the host) is drawn again.  Every seating is one search_games batch.
 
     Returns a dict from A's point of view: W, D, L, games, score, elo, early_stops, stopped (games cut at max_turns: counted as draws), and
-    zero_policy (games a zeroed policy stopped: counted nowhere else); with return_games the per-seating inputs and outputs."""
+    zero_policy (games a zeroed policy stopped: counted nowhere else); with return_games the per-seating inputs and outputs.
+    records_dir: every seating k also writes <dir>/p1/<k>.battle.data and <dir>/p2/<k>.battle.data, seat p1's and seat p2's records of its
+    games (vs.cc:380-395; in seating 1 seat p1 is agent B); the result gains record_files, the paths in that order."""
     import torch
     lib = _lib.load()
     teams = np.ascontiguousarray(teams, dtype=np.uint8).reshape(-1, 6, 5)
@@ -254,7 +289,7 @@ def search_match(ctx, agent_a, agent_b, teams, games, seed, mirror=False, max_tu
         both = np.ascontiguousarray(np.stack([teams[pick[:, 0]], teams[pick[:, 1]]], axis=1).reshape(pairs, 60))
         d_teams = torch.from_numpy(both).to(dev)
         w = d = l = stopped = early = zeroed = 0
-        played = []
+        played, files = [], []
         for s in range(seatings):
             d_seeds = torch.from_numpy(battle_seeds[s].view(np.int64)).to(dev)
             bt = torch.empty((pairs, 384), dtype=torch.uint8, device=dev)
@@ -264,7 +299,13 @@ def search_match(ctx, agent_a, agent_b, teams, games, seed, mirror=False, max_tu
                 _lib.check(ctx.lib.oakgpu_init_battles_dev(ctx.handle, C.c_void_p(d_teams.data_ptr()), C.c_void_p(d_seeds.data_ptr()), pairs, 1,
                                                            C.c_void_p(bt.data_ptr()), C.c_void_p(du.data_ptr()), C.c_void_p(rs.data_ptr())))
             out = search_games(ctx, (a, b) if s == 0 else (b, a), bt, du, rs, torch.from_numpy(streams[s].view(np.int64)).to(dev), forest=forest,
-                               max_turns=max_turns, early_stop=early_stop, solve_nash=solve_nash)
+                               max_turns=max_turns, early_stop=early_stop, solve_nash=solve_nash, records=records_dir is not None)
+            if records_dir is not None:
+                for name, rec in zip(("p1", "p2"), out["records"]):
+                    os.makedirs(os.path.join(records_dir, name), exist_ok=True)
+                    files.append(os.path.join(records_dir, name, "%d.battle.data" % s))
+                    with open(files[-1], "wb") as fh:
+                        fh.write(rec["stream"].cpu().numpy().tobytes())
             wins, ties, losses, cut = out["counts"]
             w += wins if s == 0 else losses
             l += losses if s == 0 else wins
@@ -286,6 +327,8 @@ def search_match(ctx, agent_a, agent_b, teams, games, seed, mirror=False, max_tu
     res = dict(W=w, D=d, L=l, games=total, score=score, elo=elo_difference(score), early_stops=early, stopped=stopped, zero_policy=zeroed)
     if return_games:
         res["seatings"] = played
+    if records_dir is not None:
+        res["record_files"] = files
     return res
 
 

@@ -1,7 +1,9 @@
 // oak_amd/csrc/forest_rows.hpp -- what the game loops over the forest search share (forestplay.hip: self-play; forestmatch.hip: two search
 // agents against each other): the scan behind a stable compaction, the integer payoffs of process_output's exact Nash solve with the host
-// threads that solve them, and the carving of one block of device memory into the forest search's output arrays.  The text is
-// forestplay.hip's, moved here unchanged; the kernels are `static` so that each translation unit that includes the header holds its own.
+// threads that solve them, the carving of one block of device memory into the forest search's output arrays, and the way from a turn-major
+// log of encoded updates to one contiguous `.battle.data` stream (the log entry, the scan of the record lengths, the head and log pack).
+// The text is forestplay.hip's, moved here unchanged; the kernels are `static` so that each translation unit that includes the header
+// holds its own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -13,6 +15,7 @@
 #include "../../include/oakgpu.h"
 #include "oakgpu_internal.h"
 #include "nash.hpp"
+#include "selfplay_pick.hpp"
 
 namespace oak {
 namespace fsp {
@@ -105,6 +108,79 @@ inline void solve_rows(const int32_t *pay, uint32_t rows, double *nash) {
   const uint32_t per = (rows + threads - 1) / threads;
   for (uint32_t t = 0; t < threads; ++t) pool.emplace_back(work, std::min(rows, t * per), std::min(rows, (t + 1) * per));
   for (auto &th : pool) th.join();
+}
+
+// ---- records: a game's CompressedFrames record is packed from the log at the end of the call.  `status` is 0 (OAKGPU_FSP_OK) for a game
+// whose record is kept; forestmatch.hip hands in a byte of its own making that is 0 for the games it keeps.
+constexpr uint32_t HEAD_BYTES = 4 + 2 + 384 + 1; // a record in front of its updates
+
+// one entry of the turn-major log: which game, where in its record, how long, the encoded update
+struct LogEntry { uint32_t game, cursor, length; uint8_t bytes[84]; };
+static_assert(sizeof(LogEntry) == 96 && oak_pick::MAX_UPDATE_BYTES <= 84, "one log entry is 96 bytes");
+
+// k_fsp_offsets' scan in 64 bits, over the record lengths in game order: offsets[g] = where game g's record starts, offsets[n] = the stream's size
+static __global__ __launch_bounds__(1024) void k_fsp_lengths(const uint32_t *length, uint32_t n, unsigned long long *offsets) {
+  __shared__ unsigned long long wave_total[16];
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned long long carry = 0;
+  for (uint32_t base = 0; base < n; base += 1024) {
+    const uint32_t i = base + tid;
+    const unsigned long long own = i < n ? length[i] : 0;
+    unsigned long long incl = own;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned long long up = __shfl_up(incl, d);
+      if ((int)lane >= d) incl += up;
+    }
+    if (lane == 63) wave_total[wave] = incl;
+    __syncthreads();
+    unsigned long long before = 0, all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < 16; ++w) { const unsigned long long t = wave_total[w]; if (w < wave) before += t; all += t; }
+    if (i < n) offsets[i] = carry + before + incl - own;
+    carry += all;
+    __syncthreads();
+  }
+  if (tid == 0) offsets[n] = carry;
+}
+
+struct PackArgs {
+  const unsigned long long *offsets;
+  const uint32_t *frames, *length;
+  const uint8_t *results, *status, *first; // first: n x 384, the battles after the opening update
+  const LogEntry *log;
+  uint8_t *stream;
+  uint32_t n, entries;
+};
+
+// the fixed part of every kept record: u32 byte length, u16 frame count, the 384-byte battle, the result byte.  One wave per game; the
+// record starts at any byte, so the bytes go out one by one.
+static __global__ __launch_bounds__(BLOCK) void k_fsp_pack_head(PackArgs a) {
+  const uint32_t g = blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (g >= a.n || a.status[g] != OAKGPU_FSP_OK) return;
+  uint8_t *dst = a.stream + a.offsets[g];
+  const uint32_t total = a.length[g], frames = a.frames[g];
+  const uint8_t *battle = a.first + (size_t)g * 384;
+  for (uint32_t i = lane; i < HEAD_BYTES; i += 64) {
+    uint8_t v;
+    if (i < 4) v = (uint8_t)(total >> (8 * i));
+    else if (i < 6) v = (uint8_t)(frames >> (8 * (i - 4)));
+    else if (i < 6 + 384) v = battle[i - 6];
+    else v = a.results[g];
+    dst[i] = v;
+  }
+}
+
+static __global__ __launch_bounds__(BLOCK) void k_fsp_pack_log(PackArgs a) {
+  const uint32_t e = blockIdx.x * (BLOCK / 16) + (threadIdx.x >> 4), lane = threadIdx.x & 15;
+  if (e >= a.entries) return;
+  const LogEntry &entry = a.log[e];
+  const uint32_t g = entry.game, len = entry.length;
+  if (g >= a.n || len == 0 || len > oak_pick::MAX_UPDATE_BYTES || a.status[g] != OAKGPU_FSP_OK) return; // (a dropped game's entries stay behind)
+  const uint32_t at = HEAD_BYTES + entry.cursor;
+  if (at + len > a.length[g]) return;
+  uint8_t *dst = a.stream + a.offsets[g] + at;
+  for (uint32_t i = lane; i < len; i += 16) dst[i] = entry.bytes[i];
 }
 
 } // namespace fsp

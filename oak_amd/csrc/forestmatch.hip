@@ -14,7 +14,15 @@
 //   k_fm_pick    : one lane per listed row: selfplay_pick.hpp's rule for ONE side of the seat's own root output, the early-stop sign,
 //                  scattered back by row list
 //   k_fm_finish  : one lane per live row: the early stop, the turn's log record, the turn count
-// Every kernel is a plain grid over rows (the scans: one workgroup); none waits for another block.  Between gather and pick runs
+// Recording (oakgpu_forest_match_set_records; the <true> forms of pick and finish, the <false> forms are the loop without it): each seat has
+// a turn-major log of forest_rows.hpp's LogEntry, one entry per live row per turn.  k_fm_pick<true> encodes the seat's own root output into
+// the row's entry while that output is still in the workspace, with the choice bytes open; k_fm_finish<true>, which runs when both seats
+// have picked, writes the joint choice into both entries, encodes an unsearched seat's entry whole, gives every entry its game, cursor and
+// length (0 for a turn that makes no update) and moves the game's cursor.  Both seats' entries of a turn have the same length, so ONE
+// cursor per game, kept by game index, serves both logs, and one scan of the record lengths serves both streams.
+//   k_fm_record_lengths: one lane per game: the record's length (0 for a cut or zeroed game) and the byte the pack kernels keep a game by
+//   k_fsp_lengths, k_fsp_pack_head, k_fsp_pack_log: (forest_rows.hpp) the record bases, then per seat the heads and the log's updates
+// Every kernel is a plain grid over rows, games or entries (the scans: one workgroup); none waits for another block.  Between gather and pick runs
 // oakgpu_forest_search_dev over exactly the seat's rows, after finish oakgpu_update_dev over the live rows.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,6 +44,8 @@ namespace fm {
 
 using fsp::BLOCK;
 using fsp::DEAD;
+using fsp::HEAD_BYTES;
+using fsp::LogEntry;
 using fsp::NO_ROW;
 enum : uint8_t { FLAG_NONE = 0, FLAG_ZERO_POLICY = 2, FLAG_EARLY_WIN = 3, FLAG_EARLY_LOSE = 4 }; // a row's stop flag between pick and retire
 static_assert(sizeof(oakgpu_match_turn) == 24, "one log record is 24 bytes");
@@ -49,11 +59,11 @@ OAK_PICK_HD inline int early_stop_sign(double ev, double early_stop) {
 }
 
 // One seat's pick from one root output (matrices of row stride 9): process_output, get_policy for `side`, sample_pdf.  false: the cut
-// zeroed the policy (nothing is drawn).
+// zeroed the policy (nothing is drawn).  e1 / e2 (9 entries each) receive process_output's empirical strategies of both sides.
 OAK_PICK_HD inline bool seat_pick(int side, const uint64_t *visit_matrix, const double *value_matrix, int m, int n, uint64_t iterations, const double *nash,
                                   const double *prior, const oak_pick::PolicyMode &mode, double temp, double minp, uint64_t &rng, double *policy, int *index,
-                                  double *ev) {
-  double e1[9], e2[9], nn[9], pr[9];
+                                  double *ev, double *e1, double *e2) {
+  double nn[9], pr[9];
   oak_pick::process_output(visit_matrix, value_matrix, m, n, iterations, ev, e1, e2, nullptr);
   const int k = side ? n : m;
   for (int q = 0; q < 9; ++q) {
@@ -264,20 +274,24 @@ struct PickArgs {
   double temp, minp, early_stop;
   uint32_t count;
   int side;                     // 0: seat p1, 1: seat p2
+  // recording: this seat's log entries of the turn, one per live row, and the search's whole solve (count x 9 of p1, count x 9 of p2, count
+  // values; null without solve_nash)
+  LogEntry *rlog;
+  const double *nash_all;
 };
 
-__global__ __launch_bounds__(BLOCK) void k_fm_pick(PickArgs a) {
+template <bool REC> __global__ __launch_bounds__(BLOCK) void k_fm_pick(PickArgs a) {
   const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
   if (k >= a.count) return;
   const uint32_t row = a.list[k];
   if (a.r.flag[row] != FLAG_NONE) return; // (seat p1's policy was zeroed: the game stopped there, seat p2 draws nothing)
   const int m = a.out.m[k], n = a.out.n[k];
-  double policy[9], ev;
+  double policy[9], ev, e1[9], e2[9];
   int index = 0;
   uint64_t rng = a.r.rng[row];
   const double *prior = (a.side ? a.out.p2_prior : a.out.p1_prior) + (size_t)k * 9;
   if (!seat_pick(a.side, a.out.visit_matrix + (size_t)k * 81, a.out.value_matrix + (size_t)k * 81, m, n, a.out.iterations[k],
-                 a.nash ? a.nash + (size_t)k * 9 : nullptr, prior, a.mode, a.temp, a.minp, rng, policy, &index, &ev)) {
+                 a.nash ? a.nash + (size_t)k * 9 : nullptr, prior, a.mode, a.temp, a.minp, rng, policy, &index, &ev, e1, e2)) {
     a.r.flag[row] = FLAG_ZERO_POLICY;
     return;
   }
@@ -292,20 +306,51 @@ __global__ __launch_bounds__(BLOCK) void k_fm_pick(PickArgs a) {
     a.r.ev2[row] = ev;
     a.r.s2[row] = s;
   }
+  if (REC) { // the seat's own output as the turn's update, the joint choice left open until both seats have picked (k_fm_finish)
+    double n1[9], n2[9], nv = 0.0;
+    for (int q = 0; q < 9; ++q) {
+      n1[q] = a.nash_all && q < m ? a.nash_all[(size_t)k * 9 + q] : 0.0;
+      n2[q] = a.nash_all && q < n ? a.nash_all[((size_t)a.count + k) * 9 + q] : 0.0;
+    }
+    if (a.nash_all) nv = a.nash_all[(size_t)a.count * 18 + k];
+    (void)oak_pick::encode_update(a.rlog[row].bytes, (uint32_t)m, (uint32_t)n, 0, 0, (uint32_t)a.out.iterations[k], ev, nv, e1, n1, e2, n2);
+  }
 }
 
 struct FinishArgs {
   Rows r;
   oakgpu_match_turn *log; // n x log_turns, game-major; nullable
   uint32_t rows, log_turns;
+  LogEntry *rlog1, *rlog2; // recording: the seats' log entries of this turn, one per live row
+  uint32_t *cursor;        // recording: by game index, the bytes of updates in the game's records so far (the same for both seats)
 };
 
-__global__ __launch_bounds__(BLOCK) void k_fm_finish(FinishArgs a) {
+template <bool REC> __global__ __launch_bounds__(BLOCK) void k_fm_finish(FinishArgs a) {
   const uint32_t row = blockIdx.x * BLOCK + threadIdx.x;
   if (row >= a.rows) return;
-  if (a.r.flag[row] != FLAG_NONE) return; // (a zeroed policy: no record, no turn)
+  const bool zeroed = a.r.flag[row] != FLAG_NONE;
   const int s1 = a.r.s1[row], s2 = a.r.s2[row];
   const bool stop = s1 * s2 > 0;
+  if (REC) {
+    const uint32_t g = a.r.game[row], m = a.r.m[row], n = a.r.n[row];
+    const bool made = !zeroed && !stop; // (a zeroed policy or an early stop: the update is not made, nothing is recorded)
+    const uint32_t at = a.cursor[g], len = made ? (uint32_t)oak_pick::update_bytes(m, n) : 0u;
+    LogEntry *e[2] = {a.rlog1 + row, a.rlog2 + row};
+    for (int s = 0; s < 2; ++s) {
+      e[s]->game = g;
+      e[s]->cursor = at;
+      e[s]->length = len;
+      if (!made) continue;
+      const uint8_t c1 = a.r.c1[row], c2 = a.r.c2[row];
+      if ((s ? n : m) > 1) { e[s]->bytes[1] = c1; e[s]->bytes[2] = c2; }
+      else { // an unsearched seat: the real m and n, the joint choice, iterations 0 and every value and strategy 0
+        const double zero[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        (void)oak_pick::encode_update(e[s]->bytes, m, n, c1, c2, 0u, 0.0, 0.0, zero, zero, zero, zero);
+      }
+    }
+    if (made) a.cursor[g] = at + len;
+  }
+  if (zeroed) return; // (a zeroed policy: no record, no turn)
   const uint32_t turn = a.r.turns[row];
   if (a.log && turn < a.log_turns) {
     oakgpu_match_turn t;
@@ -322,6 +367,16 @@ __global__ __launch_bounds__(BLOCK) void k_fm_finish(FinishArgs a) {
   else a.r.turns[row] = turn + 1;
 }
 
+// recording, after the last turn: a finished or early-stopped game keeps a record (head + its updates; 0 frames when its input was
+// terminal), a cut or zeroed game has none.  keep: 0 for a kept game -- what the pack kernels read as their status byte.
+__global__ __launch_bounds__(BLOCK) void k_fm_record_lengths(const uint8_t *status, const uint32_t *cursor, uint32_t *length, uint8_t *keep, uint32_t n) {
+  const uint32_t g = blockIdx.x * BLOCK + threadIdx.x;
+  if (g >= n) return;
+  const bool kept = status[g] == OAKGPU_FM_OK || status[g] == OAKGPU_FM_EARLY_STOP;
+  length[g] = kept ? HEAD_BYTES + cursor[g] : 0u;
+  keep[g] = kept ? 0 : 1;
+}
+
 } // namespace fm
 } // namespace oak
 
@@ -330,8 +385,12 @@ namespace {
 
 using namespace oak::fm;
 using oak::fsp::carve_outputs;
+using oak::fsp::k_fsp_lengths;
 using oak::fsp::k_fsp_offsets;
+using oak::fsp::k_fsp_pack_head;
+using oak::fsp::k_fsp_pack_log;
 using oak::fsp::k_fsp_payoffs;
+using oak::fsp::PackArgs;
 using oak::fsp::OUT_BYTES;
 using oak::fsp::PAY_STRIDE;
 using oak::fsp::PayoffArgs;
@@ -339,7 +398,9 @@ using oak::fsp::solve_rows;
 
 #define RC(x) do { int _r = (x); if (_r) return _r; } while (0)
 
-// the loop's workspace, attached to the forest and freed with it: grow-only, sized by the batch
+// the loop's workspace, attached to the forest and freed with it: grow-only, sized by the batch.  What recording needs is allocated by the
+// first call that records: the per-game arrays sized by the batch, the two logs grown by doubling between turns as forestplay.hip's, the
+// two streams sized by the records.
 struct Workspace {
   std::vector<void *> dev;
   uint32_t capacity = 0; // rows
@@ -361,11 +422,33 @@ struct Workspace {
   uint64_t stats[4] = {0, 0, 0, 0};
   std::vector<int32_t> h_pay;
   std::vector<double> h_nash;
+  // recording
+  bool records_on = false, have_records = false;
+  std::vector<void *> rec_dev;
+  uint32_t rec_capacity = 0, last_n = 0;               // games
+  uint32_t *cursor = nullptr, *length = nullptr;       // by game index
+  uint8_t *keep = nullptr;
+  unsigned long long *offsets = nullptr;               // games + 1
+  LogEntry *rlog[2] = {nullptr, nullptr};
+  size_t rlog_capacity = 0;                            // entries of each log
+  uint8_t *stream[2] = {nullptr, nullptr};
+  size_t stream_capacity = 0, stream_bytes = 0;        // of each stream: the two are the same size
+  void release_records() {
+    for (void *p : rec_dev) (void)hipFree(p);
+    rec_dev.clear();
+    for (int s = 0; s < 2; ++s) {
+      if (rlog[s]) (void)hipFree(rlog[s]);
+      if (stream[s]) (void)hipFree(stream[s]);
+      rlog[s] = nullptr; stream[s] = nullptr;
+    }
+    rec_capacity = 0; rlog_capacity = 0; stream_capacity = 0; stream_bytes = 0; have_records = false;
+  }
   void release() {
     for (void *p : dev) (void)hipFree(p);
     dev.clear();
     if (log_stage) (void)hipFree(log_stage);
     log_stage = nullptr; log_capacity = 0; capacity = 0;
+    release_records();
   }
   template <class T> int get(T *&p, size_t count) {
     RC(dev_alloc(p, count));
@@ -380,12 +463,36 @@ void workspace_free(void *p) {
   delete w;
 }
 
-int workspace_for(oakgpu_forest *f, uint32_t n, Workspace **out) {
+Workspace *workspace_of(oakgpu_forest *f) {
   Workspace *w = (Workspace *)oakgpu_forest_match_attachment(f);
   if (!w) {
     w = new Workspace();
     oakgpu_forest_set_match_attachment(f, w, workspace_free);
   }
+  return w;
+}
+
+// recording's per-game arrays for n games and the two logs' first size
+int records_for(Workspace *w, hipStream_t stream, uint32_t n) {
+  if (w->rec_capacity < n) {
+    HIPCHK(hipStreamSynchronize(stream));
+    for (void *p : w->rec_dev) (void)hipFree(p);
+    w->rec_dev.clear();
+    w->rec_capacity = 0;
+    auto get = [&](auto *&p, size_t count) { RC(dev_alloc(p, count)); w->rec_dev.push_back(p); return 0; };
+    RC(get(w->cursor, n)); RC(get(w->length, n)); RC(get(w->keep, n)); RC(get(w->offsets, (size_t)n + 1));
+    w->rec_capacity = n;
+  }
+  if (!w->rlog[0]) {
+    const size_t want = std::max<size_t>((size_t)n * 16, 4096);
+    for (int s = 0; s < 2; ++s) RC(dev_alloc(w->rlog[s], want));
+    w->rlog_capacity = want;
+  }
+  return 0;
+}
+
+int workspace_for(oakgpu_forest *f, uint32_t n, Workspace **out) {
+  Workspace *w = workspace_of(f);
   *out = w;
   if (w->capacity >= n) return 0;
   HIPCHK(hipStreamSynchronize((hipStream_t)oakgpu_ctx_stream(oakgpu_forest_ctx(f))));
@@ -463,7 +570,11 @@ int oakgpu_forest_match_dev(oakgpu_forest *f, const oakgpu_forest_match_params *
   RC(workspace_for(f, std::max(n, 1u), &w));
   w->stats[0] = w->stats[1] = w->stats[2] = w->stats[3] = 0;
   if (counts_out) counts_out[0] = counts_out[1] = counts_out[2] = counts_out[3] = 0;
-  if (n == 0) return 0;
+  const bool recording = w->records_on;
+  w->have_records = false;
+  w->last_n = n;
+  w->stream_bytes = 0;
+  if (n == 0) { w->have_records = recording; return 0; }
   const oakgpu_match_seat *seat[2] = {&prm->p1, &prm->p2};
   oak_pick::PolicyMode mode[2];
   oakgpu_search_params sp[2];
@@ -486,6 +597,11 @@ int oakgpu_forest_match_dev(oakgpu_forest *f, const oakgpu_forest_match_params *
     HIPCHK(hipMemsetAsync(w->counts, 0, 4 * sizeof(unsigned long long), stream));
     hipLaunchKernelGGL(k_fm_start, grid(n), dim3(BLOCK), 0, stream, r, seeds, n);
     HIPCHK(hipGetLastError());
+  }
+  size_t entries = 0; // recording: entries in each seat's log
+  if (recording) {
+    RC(records_for(w, stream, n));
+    HIPCHK(hipMemsetAsync(w->cursor, 0, (size_t)n * 4, stream));
   }
   for (uint64_t turn = 0;; ++turn) {
     // both sides' legal choices over the resident rows (finished ones included: their states are whole), retire what ended, compact the
@@ -517,6 +633,19 @@ int oakgpu_forest_match_dev(oakgpu_forest *f, const oakgpu_forest_match_params *
     ++w->stats[0];
     w->stats[1] += rec[1];
     w->stats[2] += rec[2];
+    if (recording && entries + rows > w->rlog_capacity) { // the logs follow the turns played: doubled between turns
+      const size_t want = std::max(w->rlog_capacity * 2, entries + rows);
+      HIPCHK(hipStreamSynchronize(stream));
+      for (int s = 0; s < 2; ++s) {
+        LogEntry *bigger = nullptr;
+        RC(dev_alloc(bigger, want));
+        HIPCHK(hipMemcpyAsync(bigger, w->rlog[s], entries * sizeof(LogEntry), hipMemcpyDeviceToDevice, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        (void)hipFree(w->rlog[s]);
+        w->rlog[s] = bigger;
+      }
+      w->rlog_capacity = want;
+    }
     for (int s = 0; s < 2; ++s) {
       const uint32_t count = rec[1 + s];
       if (count == 0) continue; // (no row of this seat has a choice to make: no search)
@@ -544,11 +673,20 @@ int oakgpu_forest_match_dev(oakgpu_forest *f, const oakgpu_forest_match_params *
       pk.r = r; pk.list = w->list[s]; pk.out = o; pk.nash = d_nash; pk.mode = mode[s];
       pk.temp = seat[s]->policy_temp > 0 ? seat[s]->policy_temp : 1.0; pk.minp = seat[s]->policy_min; pk.early_stop = prm->early_stop;
       pk.count = count; pk.side = s;
-      hipLaunchKernelGGL(k_fm_pick, grid(count), dim3(BLOCK), 0, stream, pk);
+      if (recording) {
+        pk.rlog = w->rlog[s] + entries; pk.nash_all = prm->solve_nash ? w->nash[s] : nullptr;
+        hipLaunchKernelGGL(k_fm_pick<true>, grid(count), dim3(BLOCK), 0, stream, pk);
+      } else hipLaunchKernelGGL(k_fm_pick<false>, grid(count), dim3(BLOCK), 0, stream, pk);
       HIPCHK(hipGetLastError());
     }
-    const FinishArgs fa{r, turn_log, rows, log_turns};
-    hipLaunchKernelGGL(k_fm_finish, grid(rows), dim3(BLOCK), 0, stream, fa);
+    if (recording) {
+      const FinishArgs fa{r, turn_log, rows, log_turns, w->rlog[0] + entries, w->rlog[1] + entries, w->cursor};
+      hipLaunchKernelGGL(k_fm_finish<true>, grid(rows), dim3(BLOCK), 0, stream, fa);
+      entries += rows;
+    } else {
+      const FinishArgs fa{r, turn_log, rows, log_turns, nullptr, nullptr, nullptr};
+      hipLaunchKernelGGL(k_fm_finish<false>, grid(rows), dim3(BLOCK), 0, stream, fa);
+    }
     HIPCHK(hipGetLastError());
     // PKMN::update(battle, c1, c2, options); durations <- options (vs.cc:312-318).  A row that stopped in this turn takes a legal step too
     // and is retired by its flag.
@@ -561,6 +699,34 @@ int oakgpu_forest_match_dev(oakgpu_forest *f, const oakgpu_forest_match_params *
   HIPCHK(hipMemcpyAsync(counts, w->counts, sizeof counts, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
   if (counts_out) for (int q = 0; q < 4; ++q) counts_out[q] = counts[q];
+  if (recording) { // pack: the record lengths and their bases in game order, then per seat the heads and the log's updates
+    if (entries > 0xFFFFFFFFull) return oakgpu_fail_msg("oakgpu_forest_match: more than 2^32 turns in one call");
+    hipLaunchKernelGGL(k_fm_record_lengths, grid(n), dim3(BLOCK), 0, stream, w->status_out, w->cursor, w->length, w->keep, n);
+    hipLaunchKernelGGL(k_fsp_lengths, dim3(1), dim3(1024), 0, stream, w->length, n, w->offsets);
+    HIPCHK(hipGetLastError());
+    unsigned long long total = 0;
+    HIPCHK(hipMemcpyAsync(&total, w->offsets + n, 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (total > w->stream_capacity) {
+      for (int s = 0; s < 2; ++s) {
+        if (w->stream[s]) (void)hipFree(w->stream[s]);
+        w->stream[s] = nullptr;
+      }
+      w->stream_capacity = 0;
+      for (int s = 0; s < 2; ++s) RC(dev_alloc(w->stream[s], (size_t)total));
+      w->stream_capacity = (size_t)total;
+    }
+    if (total)
+      for (int s = 0; s < 2; ++s) { // the stored battle is the game's input battle
+        const PackArgs pa{w->offsets, w->turns_out, w->length, w->results_out, w->keep, battles, w->rlog[s], w->stream[s], n, (uint32_t)entries};
+        hipLaunchKernelGGL(k_fsp_pack_head, dim3((n + BLOCK / 64 - 1) / (BLOCK / 64)), dim3(BLOCK), 0, stream, pa);
+        if (entries) hipLaunchKernelGGL(k_fsp_pack_log, dim3((uint32_t)((entries + BLOCK / 16 - 1) / (BLOCK / 16))), dim3(BLOCK), 0, stream, pa);
+        HIPCHK(hipGetLastError());
+      }
+    HIPCHK(hipStreamSynchronize(stream));
+    w->stream_bytes = (size_t)total;
+    w->have_records = true;
+  }
   return 0;
 }
 
@@ -611,6 +777,40 @@ int oakgpu_forest_match_last_stats(const oakgpu_forest *f, uint64_t out[4]) {
   return 0;
 }
 
+int oakgpu_forest_match_set_records(oakgpu_forest *f, int on) {
+  if (!f) return oakgpu_fail_msg("oakgpu_forest_match_set_records: null argument");
+  if (on != 0 && on != 1) return oakgpu_fail_msg("oakgpu_forest_match_set_records: on must be 0 or 1");
+  workspace_of(f)->records_on = on != 0;
+  return 0;
+}
+
+int oakgpu_forest_match_records(oakgpu_forest *f, int seat, uint8_t *stream_out, size_t capacity, size_t *bytes, uint64_t *offsets, uint32_t *n_frames,
+                                uint8_t *results, uint8_t *status, int to_device) {
+  if (!f) return oakgpu_fail_msg("oakgpu_forest_match_records: null argument");
+  if (seat != 0 && seat != 1) return oakgpu_fail_msg("oakgpu_forest_match_records: seat must be 0 (p1) or 1 (p2)");
+  Workspace *w = (Workspace *)oakgpu_forest_match_attachment(f);
+  if (!w || !w->have_records)
+    return oakgpu_fail_msg("oakgpu_forest_match_records: the forest holds no finished match call made with recording on (oakgpu_forest_match_set_records)");
+  if (bytes) *bytes = w->stream_bytes;
+  if (stream_out && capacity < w->stream_bytes) return oakgpu_fail_msg("oakgpu_forest_match_records: buffer too small");
+  oakgpu_ctx *ctx = oakgpu_forest_ctx(f);
+  RC(oakgpu_ctx_enter(ctx));
+  hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(ctx);
+  const hipMemcpyKind kind = to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const size_t n = w->last_n;
+  if (stream_out && w->stream_bytes) HIPCHK(hipMemcpyAsync(stream_out, w->stream[seat], w->stream_bytes, kind, stream));
+  if (offsets) {
+    if (n) HIPCHK(hipMemcpyAsync(offsets, w->offsets, (n + 1) * 8, kind, stream));
+    else if (to_device) HIPCHK(hipMemsetAsync(offsets, 0, 8, stream));
+    else offsets[0] = 0;
+  }
+  if (n_frames && n) HIPCHK(hipMemcpyAsync(n_frames, w->turns_out, n * 4, kind, stream));
+  if (results && n) HIPCHK(hipMemcpyAsync(results, w->results_out, n, kind, stream));
+  if (status && n) HIPCHK(hipMemcpyAsync(status, w->status_out, n, kind, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  return 0;
+}
+
 int oakgpu_match_pick_host(int side, uint32_t m, uint32_t n, const uint64_t *visit_matrix, const double *value_matrix, uint64_t iterations, const double *nash,
                            const double *prior, const char *policy_mode, double policy_temp, double policy_min, double early_stop, uint64_t *rng, double *policy,
                            int32_t *index, double *empirical_value, int32_t *sign) {
@@ -622,8 +822,9 @@ int oakgpu_match_pick_host(int side, uint32_t m, uint32_t n, const uint64_t *vis
     return oakgpu_fail_msg("oakgpu_match_pick_host: policy mode must be built from e / n / x / p words, 8 at the most (util/policy.h:22-98)");
   uint64_t state = *rng;
   int idx = 0;
-  double ev = 0;
-  if (!seat_pick(side, visit_matrix, value_matrix, (int)m, (int)n, iterations, nash, prior, mode, policy_temp > 0 ? policy_temp : 1.0, policy_min, state, policy, &idx, &ev))
+  double ev = 0, e1[9], e2[9];
+  if (!seat_pick(side, visit_matrix, value_matrix, (int)m, (int)n, iterations, nash, prior, mode, policy_temp > 0 ? policy_temp : 1.0, policy_min, state, policy, &idx, &ev,
+                 e1, e2))
     return oakgpu_fail_msg("oakgpu_match_pick_host: RuntimePolicy: zero policy (the minimum-probability cut left nothing)");
   *rng = state;
   *index = idx;

@@ -10,7 +10,7 @@
 //   k_fsp_payoffs  : (solve_nash) the integer payoffs of process_output's exact Nash solve, for the host threads that solve them
 //   k_fsp_pick     : one lane per live row: selfplay_pick.hpp's rule over the m x n live cells of the root matrices, the joint choice for the
 //                    update, one fixed-size entry of the turn-major log
-//   k_fsp_lengths  : one workgroup: the exclusive scan of the record lengths in game order = the record bases
+//   k_fsp_lengths  : (forest_rows.hpp, as the two below) one workgroup: the exclusive scan of the record lengths in game order = the record bases
 //   k_fsp_pack_head: one wave per game: length, frame count, first battle, result byte
 //   k_fsp_pack_log : 16 lanes per log entry: the update's bytes to base[game] + 391 + cursor
 // keep_node (a kept forest, oakgpu_forest_create_kept): the pick leaves the played cell (i, j) in the row and the update its observation; the
@@ -34,16 +34,10 @@
 #include "oakgpu_internal.h"
 #include "nash.hpp"
 #include "selfplay_pick.hpp"
-#include "forest_rows.hpp" // k_fsp_offsets, k_fsp_payoffs, carve_outputs, solve_rows: shared with forestmatch.hip
+#include "forest_rows.hpp" // k_fsp_offsets, k_fsp_payoffs, carve_outputs, solve_rows, LogEntry, k_fsp_lengths, k_fsp_pack_*: shared with forestmatch.hip
 
 namespace oak {
 namespace fsp {
-
-constexpr uint32_t HEAD_BYTES = 4 + 2 + 384 + 1; // a record in front of its updates
-
-// one entry of the turn-major log: which game, where in its record, how long, the encoded update
-struct LogEntry { uint32_t game, cursor, length; uint8_t bytes[84]; };
-static_assert(sizeof(LogEntry) == 96 && oak_pick::MAX_UPDATE_BYTES <= 84, "one log entry is 96 bytes");
 
 // one half of the double buffer: a row is its battle, durations, result byte, the joint choice between pick and the update, the stop flag
 // (OAKGPU_FSP_ZERO_POLICY), its game index, the game's stream, its frame count and the byte cursor within its record's updates
@@ -100,32 +94,6 @@ __global__ __launch_bounds__(BLOCK) void k_fsp_retire(RetireArgs a) {
   if (lane == 0) wave_live[tid >> 6] = (uint32_t)__popcll(ml);
   __syncthreads();
   if (tid == 0) a.block_live[blockIdx.x] = wave_live[0] + wave_live[1] + wave_live[2] + wave_live[3];
-}
-
-// k_fsp_offsets' scan (forest_rows.hpp) in 64 bits, over the record lengths in game order: offsets[g] = where game g's record starts, offsets[n] = the stream's size
-__global__ __launch_bounds__(1024) void k_fsp_lengths(const uint32_t *length, uint32_t n, unsigned long long *offsets) {
-  __shared__ unsigned long long wave_total[16];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  unsigned long long carry = 0;
-  for (uint32_t base = 0; base < n; base += 1024) {
-    const uint32_t i = base + tid;
-    const unsigned long long own = i < n ? length[i] : 0;
-    unsigned long long incl = own;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const unsigned long long up = __shfl_up(incl, d);
-      if ((int)lane >= d) incl += up;
-    }
-    if (lane == 63) wave_total[wave] = incl;
-    __syncthreads();
-    unsigned long long before = 0, all = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < 16; ++w) { const unsigned long long t = wave_total[w]; if (w < wave) before += t; all += t; }
-    if (i < n) offsets[i] = carry + before + incl - own;
-    carry += all;
-    __syncthreads();
-  }
-  if (tid == 0) offsets[n] = carry;
 }
 
 struct CompactArgs {
@@ -246,45 +214,6 @@ __global__ __launch_bounds__(BLOCK) void k_fsp_pick(PickArgs a) {
       a.r.carry[row] += a.carried[row];
     }
   }
-}
-
-struct PackArgs {
-  const unsigned long long *offsets;
-  const uint32_t *frames, *length;
-  const uint8_t *results, *status, *first; // first: n x 384, the battles after the opening update
-  const LogEntry *log;
-  uint8_t *stream;
-  uint32_t n, entries;
-};
-
-// the fixed part of every kept record: u32 byte length, u16 frame count, the 384-byte battle, the result byte.  One wave per game; the
-// record starts at any byte, so the bytes go out one by one.
-__global__ __launch_bounds__(BLOCK) void k_fsp_pack_head(PackArgs a) {
-  const uint32_t g = blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (g >= a.n || a.status[g] != OAKGPU_FSP_OK) return;
-  uint8_t *dst = a.stream + a.offsets[g];
-  const uint32_t total = a.length[g], frames = a.frames[g];
-  const uint8_t *battle = a.first + (size_t)g * 384;
-  for (uint32_t i = lane; i < HEAD_BYTES; i += 64) {
-    uint8_t v;
-    if (i < 4) v = (uint8_t)(total >> (8 * i));
-    else if (i < 6) v = (uint8_t)(frames >> (8 * (i - 4)));
-    else if (i < 6 + 384) v = battle[i - 6];
-    else v = a.results[g];
-    dst[i] = v;
-  }
-}
-
-__global__ __launch_bounds__(BLOCK) void k_fsp_pack_log(PackArgs a) {
-  const uint32_t e = blockIdx.x * (BLOCK / 16) + (threadIdx.x >> 4), lane = threadIdx.x & 15;
-  if (e >= a.entries) return;
-  const LogEntry &entry = a.log[e];
-  const uint32_t g = entry.game, len = entry.length;
-  if (g >= a.n || len == 0 || len > oak_pick::MAX_UPDATE_BYTES || a.status[g] != OAKGPU_FSP_OK) return; // (a dropped game's entries stay behind)
-  const uint32_t at = HEAD_BYTES + entry.cursor;
-  if (at + len > a.length[g]) return;
-  uint8_t *dst = a.stream + a.offsets[g] + at;
-  for (uint32_t i = lane; i < len; i += 16) dst[i] = entry.bytes[i];
 }
 
 } // namespace fsp

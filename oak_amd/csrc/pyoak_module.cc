@@ -16,7 +16,7 @@
 //           per-game loop of `vs --budget=0 --bandit=pucb-1.0 --policy-mode=p` (vs.cc:107-408) for a batch at once (oakgpu_policy_games)
 //   selfplay_forest(teams, battle_seeds, seeds, agent, policy_mode, ...) -> n self-play games at once over the forest search, the per-game
 //           loop of `generate` (generate.cc:238-322) as one `.battle.data` byte stream (oakgpu_forest_selfplay)
-//   match_forest(battles, durations, results, seeds, agent_p1, agent_p2, policy_p1, policy_p2, ...) -> n games between two SEARCH agents at
+//   match_forest(battles, durations, results, seeds, agent_p1, agent_p2, policy_p1, policy_p2, ..., records) -> n games between two SEARCH agents at
 //           once over the forest search, the per-game loop of `vs` with a budget (vs.cc:230-345) (oakgpu_forest_match)
 //   network hyper-parameter constants                                                    :586-596
 //   EncodedBattleFrames(size) {the reference's numpy fields + status, where, picks}, clear(), from_bytes(bytes, size)  py/battle/encoded-frames.h
@@ -468,10 +468,11 @@ PYBIND11_MODULE(pyoak, m) {
       [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> battles, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> durations,
          py::array_t<uint8_t, py::array::c_style | py::array::forcecast> results, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> seeds,
          Agent &agent_p1, Agent &agent_p2, const std::string &policy_p1, const std::string &policy_p2, double temp_p1, double temp_p2, double min_p1,
-         double min_p2, uint32_t max_turns, double early_stop, uint32_t log_turns, bool solve_nash) {
+         double min_p2, uint32_t max_turns, double early_stop, uint32_t log_turns, bool solve_nash, bool records) {
         // not in pyoak: the reference's `vs` loop with a budget for n games at once over the forest search (include/oakgpu.h:
         // oakgpu_forest_match); each seat's Agent strings go through search's own parser.  Returns a dict: results, turns, status, log
-        // (uint8 [n, log_turns, 24], 0xFF where no game came), counts (wins, ties, losses of seat p1, stopped at max_turns).
+        // (uint8 [n, log_turns, 24], 0xFF where no game came), counts (wins, ties, losses of seat p1, stopped at max_turns).  records: the
+        // dict gains records = (p1, p2), each seat's `.battle.data` of the games as a dict: stream (bytes), offsets, n_frames.
         const size_t n = (size_t)results.size();
         if ((size_t)battles.size() != n * OAKGPU_BATTLE_SIZE || (size_t)durations.size() != n * OAKGPU_DURATIONS_SIZE || (size_t)seeds.size() != n)
           throw std::runtime_error("match_forest: battles n x 384, durations n x 8, results n, seeds n");
@@ -483,6 +484,9 @@ PYBIND11_MODULE(pyoak, m) {
         py::array_t<uint8_t> log(std::vector<py::ssize_t>{(py::ssize_t)n, (py::ssize_t)log_turns, (py::ssize_t)sizeof(oakgpu_match_turn)});
         std::memset(log.mutable_data(), 0xFF, (size_t)log.size());
         uint64_t counts[4] = {0, 0, 0, 0};
+        std::string stream[2];
+        std::vector<uint64_t> offsets[2] = {std::vector<uint64_t>(n + 1, 0), std::vector<uint64_t>(n + 1, 0)};
+        std::vector<uint32_t> n_frames[2] = {std::vector<uint32_t>(n, 0), std::vector<uint32_t>(n, 0)};
         int rc = 0;
         std::string err;
         {
@@ -500,9 +504,19 @@ PYBIND11_MODULE(pyoak, m) {
           const int contextual = P.p1.search.bandit == 1 || P.p2.search.bandit == 1;
           if (!rc) rc = oakgpu_forest_match_check((uint32_t)n, cap, contextual, &P, (uint32_t)n);
           if (!rc && n) rc = oakgpu_forest_create(context(), (uint32_t)n, cap, contextual, &forest);
+          if (!rc && n && records) rc = oakgpu_forest_match_set_records(forest, 1);
           if (!rc && n)
             rc = oakgpu_forest_match(forest, &P, battles.data(), durations.data(), results.data(), seeds.data(), (uint32_t)n, res.mutable_data(), turns.mutable_data(),
                                      status.mutable_data(), log_turns ? (oakgpu_match_turn *)log.mutable_data() : nullptr, counts);
+          for (int seat = 0; seat < 2 && !rc && n && records; ++seat) {
+            size_t bytes = 0;
+            rc = oakgpu_forest_match_records(forest, seat, nullptr, 0, &bytes, nullptr, nullptr, nullptr, nullptr, 0);
+            if (rc) break;
+            stream[seat].resize(bytes);
+            uint8_t none = 0;
+            rc = oakgpu_forest_match_records(forest, seat, bytes ? (uint8_t *)stream[seat].data() : &none, bytes, &bytes, offsets[seat].data(), n_frames[seat].data(),
+                                             nullptr, nullptr, 0);
+          }
           if (rc) err = oakgpu_last_error();
           oakgpu_forest_destroy(context(), forest);
         }
@@ -510,11 +524,20 @@ PYBIND11_MODULE(pyoak, m) {
         py::dict out;
         out["results"] = res; out["turns"] = turns; out["status"] = status; out["log"] = log;
         out["counts"] = py::make_tuple(counts[0], counts[1], counts[2], counts[3]);
+        if (records) {
+          py::dict seat[2];
+          for (int q = 0; q < 2; ++q) {
+            seat[q]["stream"] = py::bytes(stream[q]);
+            seat[q]["offsets"] = py::array_t<uint64_t>((py::ssize_t)offsets[q].size(), offsets[q].data());
+            seat[q]["n_frames"] = py::array_t<uint32_t>((py::ssize_t)n_frames[q].size(), n_frames[q].data());
+          }
+          out["records"] = py::make_tuple(seat[0], seat[1]);
+        }
         return out;
       },
       py::arg("battles"), py::arg("durations"), py::arg("results"), py::arg("seeds"), py::arg("agent_p1"), py::arg("agent_p2"), py::arg("policy_p1") = "e",
       py::arg("policy_p2") = "e", py::arg("temp_p1") = 1.0, py::arg("temp_p2") = 1.0, py::arg("min_p1") = 0.0, py::arg("min_p2") = 0.0,
-      py::arg("max_turns") = 1000, py::arg("early_stop") = 0.0, py::arg("log_turns") = 0, py::arg("solve_nash") = true);
+      py::arg("max_turns") = 1000, py::arg("early_stop") = 0.0, py::arg("log_turns") = 0, py::arg("solve_nash") = true, py::arg("records") = false);
 
   m.def(
       "value_policy_inference",

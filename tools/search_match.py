@@ -10,13 +10,16 @@ usage: search_match.py [--budget N] [--bandit ucb-2.0] [--eval mc|fp|FILE.battle
                        [--pX-budget ... --pX-bandit ... --pX-eval ... --pX-policy-mode ... --pX-policy-temp ... --pX-policy-min ...
                         --pX-discrete]   (X = 1, 2: that seat alone; the unprefixed flags set both)
                        [--max-games N] [--teams FILE] [--mirror-match] [--early-stop 10.0] [--max-turns 1000] [--no-nash] [--seed S]
-                       [--json out.json]
+                       [--json out.json] [--dir DIR]
 
 --budget: iterations (time budgets are not run by the forest search).  --bandit: ucb-<c> or pucb-<c> (pucb needs a network eval).
 --max-games N: matches, as vs counts them: two teams are drawn per match and played in both seatings with the agents swapped, so 2 N games
 -- N with --mirror-match, where both sides get the same team.  --teams FILE: JSON {"teams": [[[species, move x 4] x 6] ...]} by name (the
 default: the reference's 16 sample teams).  --early-stop: vs's threshold (0 = off).  Output: `score: ... over ... games; Elo diff: ...`,
-`W D L:` and the three counts from agent 1's point of view, then the early stops and the games cut at --max-turns."""
+`W D L:` and the three counts from agent 1's point of view, then the early stops and the games cut at --max-turns.
+--dir DIR: every game is also saved as vs saves it (vs.cc:380-395), one record per seat: DIR/p1/<k>.battle.data and DIR/p2/<k>.battle.data per
+seating k (in seating 1 the agents are swapped: seat p1 is agent 2); the paths are printed.  A seat with one choice is not searched: its
+update has iterations 0, which a loader's min_iterations skips.  tools/verify_battle_data.py DIR/p1 DIR/p2 replays them."""
 import argparse
 import json
 import os
@@ -57,6 +60,7 @@ def main():
     ap.add_argument("--no-nash", action="store_true")
     ap.add_argument("--seed", type=int, default=0x0A4B)
     ap.add_argument("--json")
+    ap.add_argument("--dir")
     a = ap.parse_args()
     a1, a2 = agent(a, 1), agent(a, 2)
     import torch
@@ -66,11 +70,13 @@ def main():
     from policy_match import team_bytes
     ctx = Context(0)
     res = arena.search_match(ctx, a1, a2, team_bytes(a.teams), a.max_games, a.seed, mirror=a.mirror_match, max_turns=a.max_turns, early_stop=a.early_stop,
-                             solve_nash=not a.no_nash)
+                             solve_nash=not a.no_nash, records_dir=a.dir)
     print("score: %g over %d games; Elo diff: %g" % (res["score"], res["games"], res["elo"]))
     print("W D L:")
     print("%d %d %d" % (res["W"], res["D"], res["L"]))
     print("early stops: %d; stopped at %d turns: %d; zero policies: %d" % (res["early_stops"], a.max_turns, res["stopped"], res["zero_policy"]))
+    for path in res.get("record_files", []):
+        print("wrote %s (%d bytes)" % (path, os.path.getsize(path)))
     if a.json:
         with open(a.json, "w") as f:
             json.dump(dict(res, p1=a1, p2=a2, matches=a.max_games, mirror=a.mirror_match, early_stop=a.early_stop, max_turns=a.max_turns, seed=a.seed), f)

@@ -11,7 +11,8 @@ Per pairing and size: --rounds match runs alternated with baseline runs (the bas
 reported: the runs, the median, games/s and turn-steps/s (a turn-step = one update of one game), and the schedule counters.  --batch1-games
 (0 = skip): one more baseline run at batch = 1, the reference's one-at-a-time order, over that many games, and its ratio to the default batch.
 --direction N: PokeEngine against Monte-Carlo, ucb-1.0, mode x, N team pairs in both seatings at --direction-budget, W-D-L next to the
-TUTORIAL's 186-1-31 at budget 4,096.
+TUTORIAL's 186-1-31 at budget 4,096.  --records: the match runs record both seats' `.battle.data` (search_games(records=True): the two
+streams are copied to the host inside the clock); the cells are then named <pairing>/<games>/records.
 
   python tools/search_match_bench.py [--sizes 256,4096,65536] [--pairings pucb_vs_fp,fp_vs_fp] [--budget 256] [--rounds 3] [--out FILE]
 A run that is cut short keeps what it measured: --out is rewritten after every run, and a later run with the same --out goes on from it."""
@@ -128,7 +129,7 @@ def child(a):
     if a.child == "match":
         b, d, r = ctx.battle(teams.reshape(-1, 2, 6, 5), battle_seeds)
         forest = Forest(ctx, a.games, a.budget, contextual=any(s["bandit"] == "pucb" for s in seats))
-        kw = dict(forest=forest, early_stop=EARLY_STOP)
+        kw = dict(forest=forest, early_stop=EARLY_STOP, **({"records": True} if a.records else {}))
         search_games(ctx, seats, b, d, r, seeds, max_turns=2, **kw)
         ctx.synchronize()
         stats = {}
@@ -137,6 +138,8 @@ def child(a):
         s = time.perf_counter() - t
         res = dict(form="match", s=s, games=a.games, turn_steps=int(out["turns"].sum()), counts=list(out["counts"]),
                    early_stops=int((out["status"] == 3).sum()), **stats)
+        if a.records:
+            res.update(records=True, record_bytes=[len(x["stream"]) for x in out["records"]])
         forest.close()
     else:
         ctxs = [ctx] + [Context(0) for _ in range(15)]
@@ -150,9 +153,9 @@ def child(a):
     print("RESULT " + json.dumps(res), flush=True)
 
 
-def run_child(form, pairing, games, budget, seed, batch=0, timeout=1100):
+def run_child(form, pairing, games, budget, seed, batch=0, timeout=1100, records=False):
     cmd = [sys.executable, os.path.abspath(__file__), "--child", form, "--pairing", pairing, "--games", str(games), "--budget", str(budget), "--seed", str(seed),
-           "--batch", str(batch)]
+           "--batch", str(batch)] + (["--records"] if records and form == "match" else [])
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
     lines = [x for x in out.stdout.splitlines() if x.startswith("RESULT ")]
     if out.returncode != 0 or not lines:
@@ -173,6 +176,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0x0A4B)
     ap.add_argument("--max-seconds", type=float, default=1e9)
     ap.add_argument("--out")
+    ap.add_argument("--records", action="store_true")
     ap.add_argument("--child", choices=("match", "baseline", "direction"))
     ap.add_argument("--pairing", default="fp_vs_fp")
     ap.add_argument("--games", type=int, default=256)
@@ -202,13 +206,13 @@ def main():
     for pairing in a.pairings.split(","):
         base = res["cells"].setdefault(pairing + "/baseline", {"runs": []})
         for n in sizes:
-            cell = res["cells"].setdefault("%s/%d" % (pairing, n), {"pairing": pairing, "games": n, "runs": []})
+            cell = res["cells"].setdefault("%s/%d%s" % (pairing, n, "/records" if a.records else ""), {"pairing": pairing, "games": n, "runs": []})
             for k in range(a.rounds):
                 for which in (("match", "baseline") if k % 2 == 0 else ("baseline", "match")):
                     if late():
                         continue
                     if which == "match" and len(cell["runs"]) <= k:
-                        cell["runs"].append(run_child("match", pairing, n, a.budget, a.seed))
+                        cell["runs"].append(run_child("match", pairing, n, a.budget, a.seed, records=a.records))
                         print("  %s N=%d match run %d: %.2f s, %.1f games/s" % (pairing, n, k, cell["runs"][-1]["s"], cell["runs"][-1]["games_per_s"]), file=sys.stderr, flush=True)
                     if which == "baseline" and len(base["runs"]) <= k:
                         base["runs"].append(run_child("baseline", pairing, a.baseline_games, a.budget, a.seed))
