@@ -87,8 +87,9 @@ struct Tables {
   const lds_u16 *boost;  // [13] num | den<<8
   const lds_u32 *rcp;    // [256] floor((2^32-1)/d) + 1: exact x / d by one mul-hi for x < 2^24, d in 2..255
   const lds_u16 *fx;     // [68] per-effect descriptor (fx_desc below): gate / action class / secondary effect
+  const lds_u16 *bits;   // [32] the set-bit positions of a mask < 32, lowest first, 3 bits each (bit_list below): the random policy's pick
 };
-static constexpr int TABLE_LDS_BYTES = 166 * 4 + 168 + 152 * 4 + 152 * 4 + 228 + 28 + 256 * 4 + 68 * 2;
+static constexpr int TABLE_LDS_BYTES = 166 * 4 + 168 + 152 * 4 + 152 * 4 + 228 + 28 + 256 * 4 + 68 * 2 + 32 * 2;
 
 // ---- per-effect descriptors: what gen1_regs.hpp's run_move needs to know about a move effect, as data.
 // Lanes of a wave run different moves; a `switch (effect)` costs the wave every case any lane takes plus the
@@ -151,11 +152,23 @@ constexpr uint32_t fx_desc(uint32_t e) {
   default: return 0; // Splash, plain damage, effects handled outside run_move
   }
 }
+// the positions of the set bits of a mask < 32, lowest first, packed 3 bits each: (bit_list(m) >> 3 * k) & 7 is the k-th set bit of m
+constexpr uint32_t bit_list(uint32_t mask) {
+  uint32_t list = 0, k = 0;
+  for (uint32_t b = 0; b < 5; ++b)
+    if ((mask >> b) & 1) list |= b << (3 * k++);
+  return list;
+}
 struct FxTable {
   uint16_t d[68];
   constexpr FxTable() : d{} { for (uint32_t e = 0; e < 68; ++e) d[e] = (uint16_t)fx_desc(e); }
 };
 static __device__ const FxTable OAK_FX{};
+struct BitListTable {
+  uint16_t d[32];
+  constexpr BitListTable() : d{} { for (uint32_t m = 0; m < 32; ++m) d[m] = (uint16_t)bit_list(m); }
+};
+static __device__ const BitListTable OAK_BIT_LISTS{};
 
 // where each table sits in the workgroup's LDS table area (TABLE_LDS_BYTES)
 __device__ __forceinline__ Tables tables_at(lds_u8 *lds) {
@@ -167,12 +180,15 @@ __device__ __forceinline__ Tables tables_at(lds_u8 *lds) {
   lds_u16 *boost = (lds_u16 *)(chart + 228);
   lds_u32 *rcp = (lds_u32 *)(chart + 228 + 28);
   lds_u16 *fx = (lds_u16 *)(rcp + 256);
-  Tables t{mv, pp, sp0, sp1, chart, boost, rcp, fx};
+  Tables t{mv, pp, sp0, sp1, chart, boost, rcp, fx, fx + 68};
   return t;
 }
 
 // builds the tables in LDS from the packed images; call with all threads of the workgroup, then barrier.  (Only the
-// table-image builder does this: the rollout kernels copy the finished image, see stage_default_tables.)
+// table-image builder does this: the rollout kernels copy the finished image, see stage_default_tables.)  BIT_LISTS: fill
+// Tables::bits too -- the image builder does; only the random policy's pick reads that table, and only kernels that copy the image
+// play it, so a kernel that stages its own tables leaves it out.
+template <bool BIT_LISTS = false>
 __device__ inline Tables stage_tables(lds_u8 *lds, const uint32_t *g_mv, const uint8_t *g_pp, const uint32_t *g_sp0,
                                       const uint32_t *g_sp1, const uint8_t *g_chart, const uint16_t *g_boost) {
   lds_u32 *mv = (lds_u32 *)lds;
@@ -189,7 +205,9 @@ __device__ inline Tables stage_tables(lds_u8 *lds, const uint32_t *g_mv, const u
   for (int i = threadIdx.x; i < 152; i += blockDim.x) { sp0[i] = g_sp0[i]; sp1[i] = g_sp1[i]; }
   for (int i = threadIdx.x; i < 225; i += blockDim.x) chart[i] = g_chart[i];
   for (int i = threadIdx.x; i < 13; i += blockDim.x) boost[i] = g_boost[i];
-  Tables t{mv, pp, sp0, sp1, chart, boost, rcp, fx};
+  if constexpr (BIT_LISTS)
+    for (int i = threadIdx.x; i < 32; i += blockDim.x) fx[68 + i] = OAK_BIT_LISTS.d[i];
+  Tables t{mv, pp, sp0, sp1, chart, boost, rcp, fx, fx + 68};
   return t;
 }
 

@@ -255,9 +255,11 @@ struct EngineR {
   // against the LDS reciprocal table instead (exact for x < 2^24, d <= 255; see gen1_device.hpp).
   __device__ __forceinline__ uint32_t fast_div24(uint32_t x, uint32_t d) const { return d == 1 ? x : __umulhi(x, T.rcp[d]); }
   __device__ __forceinline__ uint32_t fast_mod(uint32_t x, uint32_t n) const { // any 32-bit x, n in 1..255
-    if (n == 1) return 0;
-    uint32_t r = x - __umulhi(x, T.rcp[n]) * n; // quotient estimate is exact or one too large
-    return (int32_t)r < 0 ? r + n : r;
+    return n == 1 ? 0 : mod_rcp(x, n, T.rcp[n]);
+  }
+  static __device__ __forceinline__ uint32_t mod_rcp(uint32_t x, uint32_t n, uint32_t rc) { // n in 2..255, rc = T.rcp[n]
+    const uint32_t r = x - __umulhi(x, rc) * n; // quotient estimate is exact or one too large: r in [-n, n)
+    return r < r + n ? r : r + n;               // (one unsigned min: a negative r is the larger of the two)
   }
   __device__ __forceinline__ uint32_t scale_boost(uint32_t x, int stage) const {
     if (stage == 0) return x;
@@ -1349,33 +1351,25 @@ struct EngineR {
     const uint32_t nm = (uint32_t)__popc(mv);
     return Legal{(uint32_t)__popc(sw) + (nm ? nm : 1u), sw, mv, C_MOVE}; // no usable move: Struggle (move, data 0)
   }
-  static __device__ __forceinline__ uint32_t kth_bit(uint32_t mask, uint32_t k) { // index of the k-th set bit (mask < 32)
-    uint32_t idx = 0, seen = 0;
-#pragma unroll
-    for (uint32_t b = 0; b < 5; ++b) {
-      const uint32_t bit = (mask >> b) & 1;
-      idx = (bit && seen == k) ? b : idx;
-      seen += bit;
-    }
-    return idx;
-  }
+  // The r-th choice (r < L.n): the switch bits and, behind them, the move bits are ONE list of set-bit positions, 3 bits each
+  // (Tables::bits: at most 5 + 4 entries, 27 bits), and the pick is one field of it.  A switch to party position p + 2 is the byte
+  // 4 p + 10, move slot p + 1 the byte 4 p + 5.  Behind the switches with no usable move stands L.forced: the pass, a locked side's
+  // move, Struggle (move, data 0).
   __device__ __forceinline__ uint32_t nth_choice(const Legal &L, uint32_t r) const {
-    if (L.n == 1 && L.sw == 0 && L.mv == 0) return L.forced;
+    static_assert(C_MOVE == 1 && C_SWITCH == 2, "the choice bytes below");
     const uint32_t nsw = (uint32_t)__popc(L.sw);
-    if (r < nsw) return ((kth_bit(L.sw, r) + 2) << 2) | C_SWITCH;
-    if (L.mv == 0) return C_MOVE;
-    return ((kth_bit(L.mv, r - nsw) + 1) << 2) | C_MOVE;
+    const uint32_t list = (uint32_t)T.bits[L.sw] | ((uint32_t)T.bits[L.mv] << (3 * nsw));
+    const uint32_t c = (((list >> (3 * r)) & 7) << 2) + (r < nsw ? 10u : 5u);
+    return (r >= nsw && L.mv == 0) ? L.forced : c;
   }
-  // the reference's draw (mcts.h:452-476): P1 takes seed % m on the 64-bit seed, P2 (seed >> 32) % n
-  __device__ __forceinline__ uint32_t draw_index(bool is_p1, uint32_t hi, uint32_t lo, uint32_t n) const {
-    if (n == 1) return 0;
-    uint32_t a = fast_mod(hi, n);
-    if (is_p1) {
-      uint32_t two32 = fast_mod(0xFFFFFFFFu, n) + 1; // 2^32 mod n
-      two32 = two32 == n ? 0 : two32;
-      a = fast_mod(a * two32 + fast_mod(lo, n), n);
-    }
-    return a;
+  // the reference's draw (mcts.h:452-476): P1 takes seed % m on the 64-bit seed, P2 (seed >> 32) % n.  (n <= 9)
+  __device__ __forceinline__ uint32_t draw_p2(uint32_t hi, uint32_t n) const { return fast_mod(hi, n); }
+  __device__ __forceinline__ uint32_t draw_p1(uint32_t hi, uint32_t lo, uint32_t n) const {
+    // 2^32 mod n for n = 0..9, 3 bits each: 1 for 3 and 5, 4 for 6, 7 and 9, else 0
+    constexpr uint32_t TWO32 = (1u << 9) | (1u << 15) | (4u << 18) | (4u << 21) | (4u << 27);
+    const uint32_t rc = T.rcp[n];
+    const uint32_t t = mod_rcp(hi, n, rc) * ((TWO32 >> (3 * n)) & 7) + mod_rcp(lo, n, rc); // < 81: the quotient below is exact
+    return n == 1 ? 0 : t - __umulhi(t, rc) * n;
   }
   // Is this position an INERT standstill: is every further turn-step the same no-op, one that changes nothing but the turn counter,
   // battle.rng by a constant number of draws, and fields the next turn-step overwrites before anything reads them?  Returns that
@@ -1455,8 +1449,10 @@ struct EngineR {
     const bool s_p1 = absp(S) == 0;
     const uint32_t req1 = (result >> 4) & 3, req2 = (result >> 6) & 3;
     const Legal LS = legal(S, s_p1 ? req1 : req2), LF = legal(F, s_p1 ? req2 : req1);
-    cS = nth_choice(LS, draw_index(s_p1, hi, lo, LS.n));
-    cF = nth_choice(LF, draw_index(!s_p1, hi, lo, LF.n));
+    // the draws go by PLAYER, not by frame side: the 64-bit reduction is worked once, for P1's count, instead of for both sides
+    const uint32_t r1 = draw_p1(hi, lo, s_p1 ? LS.n : LF.n), r2 = draw_p2(hi, s_p1 ? LF.n : LS.n);
+    cS = nth_choice(LS, s_p1 ? r1 : r2);
+    cF = nth_choice(LF, s_p1 ? r2 : r1);
   }
   __device__ __forceinline__ uint32_t random_step(uint32_t result, uint32_t hi, uint32_t lo) {
     OAK_SCOPE(PS_STEP);

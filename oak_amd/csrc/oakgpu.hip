@@ -34,7 +34,7 @@ using namespace walk; // the queue constants, cold_ptr_at and STAGE_STRIDE are r
 constexpr int STATE_WORDS = 96; // 384-byte battle
 constexpr int TABLE_LDS_PAD = TABLE_PAD; // (record_walk.hpp; this file's older name for it)
 
-// The engine's tables (moves, species, type chart, boosts, reciprocals, effect descriptors: 3.4 KB) as ONE image in exactly
+// The engine's tables (moves, species, type chart, boosts, reciprocals, effect descriptors, bit lists: 3.5 KB) as ONE image in exactly
 // their LDS layout, built once per device by k_build_table_image (oakgpu_create).  A kernel's prologue is then a straight
 // copy with all of a thread's loads in flight at once -- built table by table it was a dozen load -> wait -> store round
 // trips plus four integer divisions per thread in front of every launch (~10 us of the 61 us a one-turn launch takes).
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(64) void k_build_table_image() {
   extern __shared__ __align__(16) uint8_t smem[];
   for (int i = threadIdx.x; i < TABLE_IMAGE_WORDS; i += 64) ((lds_u32 *)smem)[i] = 0;
   __syncthreads();
-  (void)stage_tables((lds_u8 *)smem, OAK_MOVE_WORDS, OAK_MOVE_MAXPP, OAK_SPECIES_W0, OAK_SPECIES_W1, OAK_TYPE_CHART, OAK_BOOSTS);
+  (void)stage_tables<true>((lds_u8 *)smem, OAK_MOVE_WORDS, OAK_MOVE_MAXPP, OAK_SPECIES_W0, OAK_SPECIES_W1, OAK_TYPE_CHART, OAK_BOOSTS);
   __syncthreads();
   for (int i = threadIdx.x; i < TABLE_IMAGE_WORDS; i += 64) g_table_image[i] = ((lds_u32 *)smem)[i];
 }
