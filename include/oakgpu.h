@@ -297,6 +297,27 @@ typedef struct {
  * simplex on 512-bit integers; the reference's lrsnash + GMP is absent).  p1[m], p2[n] = equilibrium strategies, *value =
  * game value / discretize_factor.  Host code: no GPU involved. */
 int oakgpu_solve_matrix(const int32_t *payoffs, int m, int n, int discretize_factor, double *p1, double *p2, double *value);
+/* The same solve on the device (nashdev.hip), bit for bit oakgpu_solve_matrix's: the integer simplex is the same text (nash.hpp) on
+ * integers of 4 or 8 limbs (chosen per matrix from its largest shifted entry by Hadamard's bound), the final roundings are the host's
+ * x87 long double operations restated in integer arithmetic.
+ * oakgpu_nash_solve_dev: device pointers, on the context's stream, nothing is synchronised.  pay = rows x 82 int32 as the forest loops'
+ *   payoff kernel writes them (row-major m x n payoffs, m | n << 8 at index 81); nash = rows x 9 p1 strategies, rows x 9 p2 strategies,
+ *   rows values / 256.0.  A row the solver refuses (m or n outside 1 ... 9, a payoff beyond +-2^20) comes back as zeros.
+ * oakgpu_solve_matrices: host arrays; matrix k = the m[k] x n[k] row-major ints at payoffs + 81 k, its results at p1 + 9 k, p2 + 9 k (the
+ *   entries past m[k] / n[k] are 0) and value[k].  Entry k is oakgpu_solve_matrix of matrix k; what that call refuses fails the whole
+ *   call before anything is launched, naming the lowest such k. */
+int oakgpu_nash_solve_dev(oakgpu_ctx *ctx, const int32_t *pay, uint32_t rows, double *nash);
+int oakgpu_solve_matrices(oakgpu_ctx *ctx, const int32_t *payoffs, const int32_t *m, const int32_t *n, uint32_t count, int discretize_factor,
+                          double *p1, double *p2, double *value);
+/* Host-only diagnostics of the device solver's text (no GPU).  _soft_host: matrices laid out as for oakgpu_solve_matrices, solved by
+ *   solve_soft at `limbs` = 4, 8 or 0 (the selector's choice); value in payoff units; width[k] = the selector's choice, 0 for a refused
+ *   matrix (whose results are zeros).  _round_host: num / den are count x 8 64-bit limbs (two's complement, least significant first);
+ *   hard[k] = (double)(num.to_ld() / den.to_ld() - (long double)shift[k]) in x87 arithmetic, soft[k] = the integer restatement of it.
+ *   _width4_max_entry: the largest shifted entry the 4-limb width takes. */
+int oakgpu_nash_soft_host(const int32_t *payoffs, const int32_t *m, const int32_t *n, uint32_t count, int limbs, double *p1, double *p2, double *value,
+                          uint8_t *width);
+int oakgpu_nash_round_host(const uint64_t *num, const uint64_t *den, const int64_t *shift, uint32_t count, double *hard, double *soft);
+int oakgpu_nash_width4_max_entry(void);
 /* RuntimeSearch::run (util/search.h:17-66, search.cc:150-313): the search configured by the Agent's strings, as the
  * reference's binaries and pyoak.search configure it.  budget "4096" | "100ms" | "8s"; bandit "ucb-1.0" | "ucb1-2.0" |
  * "pucb-1.5" | "exp3-<gamma>[-<alpha>]" | "pexp3-..."; eval "" / "mc" | "fp" | <.battle.net path> (loaded once per device
@@ -423,7 +444,8 @@ int oakgpu_search_agent_heap(oakgpu_ctx *ctx, oakgpu_heap *heap, const uint8_t *
  * The calls: _create allocates the arenas on the context's device (the context must outlive the forest; all work runs on its stream);
  * _search_dev takes device arrays and returns with the search complete (the host reads a 4-byte live count per tree level);
  * _search takes host arrays, fills one oakgpu_search_output per tree as oakgpu_search does (process_output's empirical fields; the exact
- * Nash solve only with solve_nash, else those fields are 0; duration_us = the whole call's), streams_out (nullable) n x u64, trace
+ * Nash solve only with solve_nash, else those fields are 0 -- 1: one host solve per tree, 2: one oakgpu_nash_solve_dev over all n trees,
+ * the same bits; duration_us = the whole call's), streams_out (nullable) n x u64, trace
  * (nullable) a host buffer; _nodes reads `count` node records of one tree of the LAST call, from node `first`, into host memory;
  * _check is the host-only validation both searches run first (results: host bytes, nullable = not checked). */
 typedef struct oakgpu_forest oakgpu_forest;
@@ -837,6 +859,8 @@ int oakgpu_selfplay_games(oakgpu_ctx *const *ctxs, oakgpu_net *net, const uint8_
  *   entirely stops that game alone with OAKGPU_FSP_ZERO_POLICY and no record.
  *   solve_nash = 1: the integer payoffs are formed on the device, solved on up to 16 host threads (oakgpu_solve_matrix's solver) and go
  *   back up before the pick -- what oakgpu_forest_search(solve_nash = 1) computes.  0: the nash fields are stored as 0.
+ *   solve_nash = 2: the same strategies and values, bit for bit, from oakgpu_nash_solve_dev between the payoff kernel and the pick, on the
+ *   stream: no copy down, no host threads, no upload and neither of the two synchronisations that 1 adds to every turn.
  *   Refused before any launch (oakgpu_forest_selfplay_check; teams: host bytes, nullable = not checked): keep_node on a plain forest, an unknown mode
  *   letter or 'b' or more than 8 words, policy_min > 1, an 'n' word without solve_nash, a team pair that fails
  *   oakgpu_endless_battle_check (the lowest such game is named), and everything oakgpu_forest_check refuses.
@@ -860,6 +884,9 @@ int oakgpu_forest_selfplay_records(oakgpu_forest *forest, uint8_t *stream, size_
 int oakgpu_forest_selfplay(oakgpu_forest *forest, oakgpu_net *net, const oakgpu_selfplay_params *params, const uint8_t *teams,
                            const uint64_t *battle_seeds, const uint64_t *seeds, uint32_t n, int solve_nash);
 int oakgpu_forest_selfplay_last_stats(const oakgpu_forest *forest, uint64_t out[4]);
+/* The last call's turn loop as the host saw it: out[0] = stream synchronisations, out[1] = copies between host and device.  Per turn one
+ * of each for the live count (what _last_stats counts), and with solve_nash = 1 two more of each for the payoffs and the strategies. */
+int oakgpu_forest_selfplay_last_traffic(const oakgpu_forest *forest, uint64_t out[2]);
 /* keep_node = 1 on a kept forest (oakgpu_forest_create_kept; `contextual | OAKGPU_FOREST_KEPT` in _check): the game's tree goes on from turn
  * to turn as oakgpu_selfplay_game's heap does (generate.cc:324-333).  The pick leaves the played cell in the row, oakgpu_update_dev its
  * observation; the next turn's compaction hands its source-row list to ONE oakgpu_forest_advance_dev, which re-roots every live tree and
@@ -887,7 +914,7 @@ int oakgpu_selfplay_pick_host(uint32_t m, uint32_t n, const uint64_t *visit_matr
  *   is one oakgpu_forest_search_dev with p1's parameters (batch = 1, seed ignored) and net over exactly the live rows with m > 1, gathered
  *   into a contiguous buffer in row order; then seat p2's over the rows with n > 1; a seat without rows makes no call.  Tree k of a call
  *   is the standalone search of that state with that seed.  (4) solve_nash != 0: the exact Nash solve of every searched row's payoffs, as
- *   oakgpu_forest_selfplay does it (device payoffs, host threads, upload).  (5) Pick, seat p1 first, then seat p2, each from ITS OWN
+ *   oakgpu_forest_selfplay does it (1: device payoffs, host threads, upload; 2: oakgpu_nash_solve_dev on the stream).  (5) Pick, seat p1 first, then seat p2, each from ITS OWN
  *   search's output: process_output in double, get_policy for that seat's side with that seat's {policy_mode, policy_temp, policy_min},
  *   index = sample_pdf(policy, rng), the choice at that index; ev = the output's empirical_value (P1's point of view for both seats).  An
  *   unsearched seat plays its one choice, draws nothing, ev = 0.  The rule is selfplay_pick.hpp's text without contraction; pow

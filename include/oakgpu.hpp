@@ -12,6 +12,7 @@
 //   OakGPU::ForestMatch        <- the per-game loop of vs.cc:230-345 with a budget: two search agents, a batch of games at once over the forest search
 //   OakGPU::run                <- RuntimeSearch::run (util/search.h:66, search.cc:150-313): the Agent's strings pick everything
 //   OakGPU::solve_matrix       <- LRSNash::solve_fast as called at mcts.h:643-649 / pyoak.cc:394-426 (exact)
+//   OakGPU::solve_matrices     <- a batch of those on the device, the same bits
 //   OakGPU::SharedDeviceRollout<- benchmark.cc:23-31: n playouts from one root driven by ONE sequential std::mt19937
 //   OakGPU::Frames             <- Train::Battle::CompressedFrames (train/battle/compressed-frame.h:37-243)
 //   OakGPU::replay_check       <- the replay self-check of py/battle/frames.h:52-67, for a whole file at once
@@ -305,6 +306,10 @@ inline oakgpu_search_output run(Context &ctx, const Leaf &input, const Agent &ag
   return out;
 }
 
+// solve_nash of the forest search and the loops over it (and oakgpu_forest_match_params::solve_nash): no solve, the exact solves on the
+// host's threads, or on the device (oakgpu_nash_solve_dev: the same bits, nothing leaves the device).  `true` / `false` still mean 1 / 0.
+constexpr int NASH_NONE = 0, NASH_HOST = 1, NASH_DEVICE = 2;
+
 // The forest search (include/oakgpu.h: oakgpu_forest_*): up to max_trees searches at once, one GPU lane per tree, every tree resident
 // on the device; tree g is TreeSearch::run(roots[g], {params, seed = seeds[g], batch = 1}) iteration for iteration.  params.bandit 0 / 1
 // (1 needs contextual = true, eval = 1 and a network), params.eval 0 / 1 / 2; the Nash fields are solved only with solve_nash.
@@ -321,7 +326,7 @@ public:
   SearchForest(const SearchForest &) = delete;
   SearchForest &operator=(const SearchForest &) = delete;
   std::vector<oakgpu_search_output> search(const oakgpu_search_params &params, const std::vector<Leaf> &roots, const std::vector<uint64_t> &seeds,
-                                           Network *net = nullptr, bool solve_nash = false, std::vector<uint64_t> *streams = nullptr, bool keep = false) {
+                                           Network *net = nullptr, int solve_nash = NASH_NONE, std::vector<uint64_t> *streams = nullptr, bool keep = false) {
     if (seeds.size() != roots.size()) throw std::runtime_error{"oakgpu: SearchForest::search: one seed per root"};
     const uint32_t n = (uint32_t)roots.size();
     std::vector<uint8_t> b((size_t)n * OAKGPU_BATTLE_SIZE), d((size_t)n * OAKGPU_DURATIONS_SIZE), r(n);
@@ -333,7 +338,7 @@ public:
     std::vector<oakgpu_search_output> out(n);
     if (streams) streams->assign(n, 0);
     check((keep ? oakgpu_forest_search_kept : oakgpu_forest_search)(f_, net ? net->get() : nullptr, &params, b.data(), d.data(), r.data(), seeds.data(), n,
-                                                                    out.data(), solve_nash ? 1 : 0, streams ? streams->data() : nullptr, nullptr, 0));
+                                                                    out.data(), solve_nash, streams ? streams->data() : nullptr, nullptr, 0));
     return out;
   }
   // Heap::update of every tree and its move to another row (a kept forest): new tree t continues tree src[t] (src empty: tree t) along the
@@ -390,10 +395,10 @@ public:
   explicit ForestSelfplay(SearchForest &forest) : forest_{forest} {}
   // teams: n x 60 bytes; params.search.seed / batch and params.seed are ignored; keep_node = 1 needs a forest made with keep_arena
   Result play(const oakgpu_selfplay_params &params, const std::vector<uint8_t> &teams, const std::vector<uint64_t> &battle_seeds,
-              const std::vector<uint64_t> &seeds, Network *net = nullptr, bool solve_nash = true) {
+              const std::vector<uint64_t> &seeds, Network *net = nullptr, int solve_nash = NASH_HOST) {
     const uint32_t n = (uint32_t)seeds.size();
     if (teams.size() != (size_t)n * 60 || battle_seeds.size() != n) throw std::runtime_error{"oakgpu: ForestSelfplay::play: teams n x 60, one battle seed and one seed per game"};
-    check(oakgpu_forest_selfplay(forest_.get(), net ? net->get() : nullptr, &params, teams.data(), battle_seeds.data(), seeds.data(), n, solve_nash ? 1 : 0));
+    check(oakgpu_forest_selfplay(forest_.get(), net ? net->get() : nullptr, &params, teams.data(), battle_seeds.data(), seeds.data(), n, solve_nash));
     Result out;
     size_t bytes = 0;
     check(oakgpu_forest_selfplay_records(forest_.get(), nullptr, 0, &bytes, nullptr, nullptr, nullptr, nullptr, 0));
@@ -479,6 +484,29 @@ inline std::tuple<std::vector<double>, std::vector<double>, double> solve_matrix
   double value = 0;
   check(oakgpu_solve_matrix(payoffs.data(), m, n, discretize_factor, p1.data(), p2.data(), &value));
   return {p1, p2, value};
+}
+
+// A batch of solve_matrix calls on the device (oakgpu_solve_matrices): matrix k is the m[k] x n[k] row-major ints payoffs[k]; entry k of the
+// result is solve_matrix(payoffs[k], m[k], n[k], discretize_factor) bit for bit, and what that call refuses fails the whole call.
+inline std::vector<std::tuple<std::vector<double>, std::vector<double>, double>> solve_matrices(Context &ctx, const std::vector<std::vector<int32_t>> &payoffs,
+                                                                                                const std::vector<int> &m, const std::vector<int> &n,
+                                                                                                int discretize_factor = 256) {
+  const size_t count = payoffs.size();
+  if (m.size() != count || n.size() != count) throw std::runtime_error{"oakgpu: solve_matrices: one m and one n per matrix"};
+  std::vector<int32_t> flat(count * 81 + 1, 0), ms(count + 1, 0), ns(count + 1, 0);
+  for (size_t k = 0; k < count; ++k) {
+    if (m[k] < 1 || n[k] < 1 || m[k] > 9 || n[k] > 9 || payoffs[k].size() != static_cast<size_t>(m[k]) * static_cast<size_t>(n[k]))
+      throw std::runtime_error{"oakgpu: payoff matrix shape"};
+    std::copy(payoffs[k].begin(), payoffs[k].end(), flat.begin() + static_cast<std::ptrdiff_t>(k * 81));
+    ms[k] = m[k]; ns[k] = n[k];
+  }
+  std::vector<double> p1(count * 9 + 1), p2(count * 9 + 1), value(count + 1);
+  check(oakgpu_solve_matrices(ctx.get(), flat.data(), ms.data(), ns.data(), static_cast<uint32_t>(count), discretize_factor, p1.data(), p2.data(), value.data()));
+  std::vector<std::tuple<std::vector<double>, std::vector<double>, double>> out;
+  for (size_t k = 0; k < count; ++k)
+    out.emplace_back(std::vector<double>(p1.begin() + static_cast<std::ptrdiff_t>(k * 9), p1.begin() + static_cast<std::ptrdiff_t>(k * 9 + ms[k])),
+                     std::vector<double>(p2.begin() + static_cast<std::ptrdiff_t>(k * 9), p2.begin() + static_cast<std::ptrdiff_t>(k * 9 + ns[k])), value[k]);
+  return out;
 }
 
 // benchmark.cc:23-31 + mcts.h:250-263,448-496 on the device: `n` playouts from one root, every draw taken from ONE

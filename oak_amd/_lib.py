@@ -40,7 +40,18 @@ SYMBOLS = [
     "oakgpu_forest_create_kept", "oakgpu_forest_create_kept_check", "oakgpu_forest_kept_tree_bytes", "oakgpu_forest_advance_dev", "oakgpu_forest_advance",
     "oakgpu_forest_search_kept_dev", "oakgpu_forest_search_kept", "oakgpu_forest_keep_stats", "oakgpu_forest_mismatch", "oakgpu_forest_node_counts",
     "oakgpu_forest_selfplay_nodes_kept", "oakgpu_forest_selfplay_keep_stats",
+    "oakgpu_nash_solve_dev", "oakgpu_solve_matrices", "oakgpu_nash_soft_host", "oakgpu_nash_round_host", "oakgpu_nash_width4_max_entry",
+    "oakgpu_forest_selfplay_last_traffic",
 ]
+
+
+def nash_mode(solve_nash):
+    """The C ABI's solve_nash word: 0 none, 1 the host's threads, 2 ("device") the device solver -- the same bits either way."""
+    if isinstance(solve_nash, str):
+        if solve_nash not in ("host", "device"):
+            raise ValueError("solve_nash: True / False, \"host\", \"device\" or 0 / 1 / 2")
+        return 2 if solve_nash == "device" else 1
+    return 2 if (not isinstance(solve_nash, bool) and solve_nash == 2) else int(bool(solve_nash))
 
 
 class RolloutBatch(C.Structure):      # oakgpu_rollout_batch (include/oakgpu.h)
@@ -271,6 +282,11 @@ def load():
     lib.oakgpu_agent_networks_clear.argtypes = [vp]
     lib.oakgpu_agent_networks_clear.restype = None
     lib.oakgpu_solve_matrix.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+    lib.oakgpu_nash_solve_dev.argtypes = [vp, vp, u32, vp]
+    lib.oakgpu_solve_matrices.argtypes = [vp, vp, vp, vp, u32, i32, vp, vp, vp]
+    lib.oakgpu_nash_soft_host.argtypes = [vp, vp, vp, u32, i32, vp, vp, vp, vp]
+    lib.oakgpu_nash_round_host.argtypes = [vp, vp, vp, u32, vp, vp]
+    lib.oakgpu_nash_width4_max_entry.argtypes = []
     lib.oakgpu_bandit_select_run.argtypes = [i32, C.c_float, C.c_float, u32, vp, vp, vp, u32, vp, vp, vp, vp]
     lib.oakgpu_bandit_replay.argtypes = [i32, C.c_float, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp]
     lib.oakgpu_update_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, vp]
@@ -346,6 +362,7 @@ def load():
     lib.oakgpu_forest_selfplay_records.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, vp, vp, i32]
     lib.oakgpu_forest_selfplay.argtypes = [vp, vp, C.POINTER(SelfplayParams), vp, vp, vp, u32, i32]
     lib.oakgpu_forest_selfplay_last_stats.argtypes = [vp, C.POINTER(u64 * 4)]
+    lib.oakgpu_forest_selfplay_last_traffic.argtypes = [vp, C.POINTER(u64 * 2)]
     lib.oakgpu_forest_selfplay_nodes_kept.argtypes = [vp, vp, i32]
     lib.oakgpu_forest_selfplay_keep_stats.argtypes = [vp, C.POINTER(u64 * 4)]
     lib.oakgpu_selfplay_pick_host.argtypes = [u32, u32, vp, vp, u64, vp, vp, C.c_double, vp, vp, vp, vp, C.c_char_p, C.c_double, C.c_double, C.POINTER(u64),

@@ -127,7 +127,7 @@ def _match_seat(s):
 
 
 def _match_params(seats, max_turns, early_stop, log_turns, solve_nash):
-    return _lib.ForestMatchParams(_match_seat(seats[0]), _match_seat(seats[1]), int(max_turns), float(early_stop), int(log_turns), int(bool(solve_nash)))
+    return _lib.ForestMatchParams(_match_seat(seats[0]), _match_seat(seats[1]), int(max_turns), float(early_stop), int(log_turns), _lib.nash_mode(solve_nash))
 
 
 def forest_match_check(max_trees, max_iterations, contextual, seats, n=1, max_turns=0, early_stop=0.0, solve_nash=True):
@@ -181,7 +181,8 @@ def search_games(ctx, seats, battles, durations, results, seeds, forest=None, ma
                  records=False):
     """n whole games from the given states between two SEARCH agents on the forest search (oakgpu_forest_match*): seats = (p1, p2), each a
     dict as _match_seat takes it; seeds uint64[n], one per game.  forest: None (one made for this call, contextual when a seat is PUCB)
-    or a search.Forest to reuse; stats: optional dict that receives turns, p1_rows, p2_rows, host_reads.
+    or a search.Forest to reuse; stats: optional dict that receives turns, p1_rows, p2_rows, host_reads.  solve_nash: True / "host" (the exact
+    Nash solves of the searched rows on the host's threads), "device" / 2 (on the GPU, on the stream: the same bytes in every output) or False.
 
     numpy arrays in -> numpy arrays out; torch tensors on the GPU in (seeds int64 bit patterns) -> torch tensors out, nothing leaves the
     device but the counters.  Returns a dict: results uint8[n], turns uint32[n] (int32 for torch), status uint8[n] (FM_STATUS), counts =

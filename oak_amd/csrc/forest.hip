@@ -810,6 +810,8 @@ static int forest_search_host(oakgpu_forest *f, oakgpu_net *net, const oakgpu_se
   oakgpu_forest_outputs ho;
   carve_outputs(h.data(), n, &ho);
   const double us = std::chrono::duration<double, std::micro>(std::chrono::high_resolution_clock::now() - t0).count();
+  constexpr size_t NASH_PAY_STRIDE = 82; // oakgpu_nash_solve_dev's rows: 81 payoffs + (m | n << 8)
+  std::vector<int32_t> pay(solve_nash == 2 ? (size_t)n * NASH_PAY_STRIDE : 0, 0);
   for (uint32_t g = 0; g < n; ++g) {
     oakgpu_search_output &x = out[g];
     memset(&x, 0, sizeof x);
@@ -825,7 +827,26 @@ static int forest_search_host(oakgpu_forest *f, oakgpu_net *net, const oakgpu_se
     int32_t M[81];
     oak_pick::process_output(x.visit_matrix, x.value_matrix, m, nn, x.iterations, &x.empirical_value, x.p1_empirical, x.p2_empirical, M);
     double nv = 0;
-    if (solve_nash && oak_nash::solve(M, m, nn, x.p1_nash, x.p2_nash, &nv)) x.nash_value = nv / 256.0;
+    if (solve_nash == 2) { // one device solve over all n trees, below
+      memcpy(pay.data() + (size_t)g * NASH_PAY_STRIDE, M, sizeof M);
+      pay[(size_t)g * NASH_PAY_STRIDE + 81] = m | nn << 8;
+    } else if (solve_nash && oak_nash::solve(M, m, nn, x.p1_nash, x.p2_nash, &nv)) x.nash_value = nv / 256.0;
+  }
+  if (solve_nash == 2) {
+    OakHostCall call(f->ctx);
+    int32_t *d_pay = (int32_t *)call.get(pay.size() * 4);
+    double *d_nash = (double *)call.get((size_t)n * 19 * 8);
+    if (!d_pay || !d_nash) return -1;
+    std::vector<double> nash((size_t)n * 19);
+    HIPCHK(hipMemcpyAsync(d_pay, pay.data(), pay.size() * 4, hipMemcpyHostToDevice, stream));
+    RC(oakgpu_nash_solve_dev(f->ctx, d_pay, n, d_nash));
+    HIPCHK(hipMemcpyAsync(nash.data(), d_nash, nash.size() * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    for (uint32_t g = 0; g < n; ++g) {
+      memcpy(out[g].p1_nash, nash.data() + (size_t)g * 9, 72);
+      memcpy(out[g].p2_nash, nash.data() + ((size_t)n + g) * 9, 72);
+      out[g].nash_value = nash[(size_t)n * 18 + g];
+    }
   }
   return 0;
 }

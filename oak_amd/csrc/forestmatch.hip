@@ -10,7 +10,7 @@
 //   k_fm_prelude : one workgroup over the live rows: the streams advance, both seats' tree seeds, both seats' row lists by a stable prefix
 //                  sum, and the 12-byte record the host reads: live rows, p1 rows, p2 rows
 //   k_fm_gather  : 24 lanes per listed row: battle (16-byte pieces), durations, result byte into the seat's contiguous search input
-//   k_fsp_payoffs: (forest_rows.hpp, solve_nash) the integer payoffs for the host threads that solve them
+//   k_fsp_payoffs: (forest_rows.hpp, solve_nash) the integer payoffs for the host threads that solve them (1) or for oakgpu_nash_solve_dev (2)
 //   k_fm_pick    : one lane per listed row: selfplay_pick.hpp's rule for ONE side of the seat's own root output, the early-stop sign,
 //                  scattered back by row list
 //   k_fm_finish  : one lane per live row: the early stop, the turn's log record, the turn count
@@ -660,13 +660,16 @@ int oakgpu_forest_match_dev(oakgpu_forest *f, const oakgpu_forest_match_params *
         const PayoffArgs pay{o.m, o.n, o.visit_matrix, o.value_matrix, w->pay, count};
         hipLaunchKernelGGL(k_fsp_payoffs, grid(count), dim3(BLOCK), 0, stream, pay);
         HIPCHK(hipGetLastError());
-        w->h_pay.resize((size_t)count * PAY_STRIDE);
-        w->h_nash.resize((size_t)count * 19);
-        HIPCHK(hipMemcpyAsync(w->h_pay.data(), w->pay, w->h_pay.size() * 4, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        solve_rows(w->h_pay.data(), count, w->h_nash.data());
-        HIPCHK(hipMemcpyAsync(w->nash[s], w->h_nash.data(), w->h_nash.size() * 8, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipStreamSynchronize(stream)); // (the strategies' host copy is reused by the other seat)
+        if (prm->solve_nash == 2) RC(oakgpu_nash_solve_dev(ctx, w->pay, count, w->nash[s])); // on the stream: nothing leaves the device
+        else {
+          w->h_pay.resize((size_t)count * PAY_STRIDE);
+          w->h_nash.resize((size_t)count * 19);
+          HIPCHK(hipMemcpyAsync(w->h_pay.data(), w->pay, w->h_pay.size() * 4, hipMemcpyDeviceToHost, stream));
+          HIPCHK(hipStreamSynchronize(stream));
+          solve_rows(w->h_pay.data(), count, w->h_nash.data());
+          HIPCHK(hipMemcpyAsync(w->nash[s], w->h_nash.data(), w->h_nash.size() * 8, hipMemcpyHostToDevice, stream));
+          HIPCHK(hipStreamSynchronize(stream)); // (the strategies' host copy is reused by the other seat)
+        }
         d_nash = w->nash[s] + (s ? (size_t)count * 9 : 0);
       }
       PickArgs pk{};

@@ -7,7 +7,8 @@
 //   k_fsp_offsets  : one workgroup: the exclusive prefix sums of those per-block counts, and their total = the live count the host reads
 //   k_fsp_compact  : the live rows, in order, into the other half of the double buffer -- and the turn prelude: the row's stream advances,
 //                    its first draw is the seed of the row's tree
-//   k_fsp_payoffs  : (solve_nash) the integer payoffs of process_output's exact Nash solve, for the host threads that solve them
+//   k_fsp_payoffs  : (solve_nash) the integer payoffs of process_output's exact Nash solve, for the host threads that solve them (1) or for
+//                    oakgpu_nash_solve_dev (2: nashdev.hip, on the stream, the same bits)
 //   k_fsp_pick     : one lane per live row: selfplay_pick.hpp's rule over the m x n live cells of the root matrices, the joint choice for the
 //                    update, one fixed-size entry of the turn-major log
 //   k_fsp_lengths  : (forest_rows.hpp, as the two below) one workgroup: the exclusive scan of the record lengths in game order = the record bases
@@ -252,6 +253,7 @@ struct Workspace {
   uint8_t *adv_i = nullptr, *adv_j = nullptr, *adv_obs = nullptr, *advanced = nullptr;
   bool kept_call = false;
   uint64_t keep_stats[4] = {0, 0, 0, 0};
+  uint64_t loop_syncs = 0, loop_copies = 0; // the turn loop's stream synchronisations and host <-> device copies
   std::vector<int32_t> h_pay;
   std::vector<double> h_nash;
   void release() {
@@ -379,6 +381,7 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
   w->last_n = n;
   w->stream_bytes = 0;
   w->stats[0] = w->stats[1] = w->stats[2] = w->stats[3] = 0;
+  w->loop_syncs = w->loop_copies = 0;
   if (n == 0) { w->have = true; return 0; }
   oak_pick::PolicyMode mode;
   (void)oak_pick::parse_policy_mode(prm->policy_mode, sizeof prm->policy_mode, &mode);
@@ -420,6 +423,8 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
     HIPCHK(hipStreamSynchronize(stream));
     ++w->stats[3];
     ++w->stats[2];
+    ++w->loop_syncs;
+    ++w->loop_copies;
     cur ^= 1;
     if (live > rows) return oakgpu_fail_msg("oakgpu_forest_selfplay: the live count grew (internal error)");
     rows = live;
@@ -448,12 +453,17 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
       const PayoffArgs pa{o.m, o.n, o.visit_matrix, o.value_matrix, w->pay, rows};
       hipLaunchKernelGGL(k_fsp_payoffs, grid(rows), dim3(BLOCK), 0, stream, pa);
       HIPCHK(hipGetLastError());
-      w->h_pay.resize((size_t)rows * PAY_STRIDE);
-      w->h_nash.resize((size_t)rows * 19);
-      HIPCHK(hipMemcpyAsync(w->h_pay.data(), w->pay, w->h_pay.size() * 4, hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      solve_rows(w->h_pay.data(), rows, w->h_nash.data());
-      HIPCHK(hipMemcpyAsync(w->nash, w->h_nash.data(), w->h_nash.size() * 8, hipMemcpyHostToDevice, stream));
+      if (solve_nash == 2) RC(oakgpu_nash_solve_dev(ctx, w->pay, rows, w->nash)); // on the stream: nothing leaves the device
+      else {
+        w->h_pay.resize((size_t)rows * PAY_STRIDE);
+        w->h_nash.resize((size_t)rows * 19);
+        HIPCHK(hipMemcpyAsync(w->h_pay.data(), w->pay, w->h_pay.size() * 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        solve_rows(w->h_pay.data(), rows, w->h_nash.data());
+        HIPCHK(hipMemcpyAsync(w->nash, w->h_nash.data(), w->h_nash.size() * 8, hipMemcpyHostToDevice, stream));
+        w->loop_syncs += 2; // (this one and the one after the update)
+        w->loop_copies += 2;
+      }
       d_p1 = w->nash; d_p2 = w->nash + (size_t)rows * 9; d_nv = w->nash + (size_t)rows * 18;
     }
     PickArgs pk{};
@@ -466,7 +476,7 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
     entries += rows;
     // PKMN::update(battle, c1, c2, options); durations <- options (generate.cc:319-322)
     RC(oakgpu_update_dev(ctx, r.battles, r.c1, r.c2, r.durations, keep ? r.obs : nullptr, nullptr, rows, r.results));
-    if (solve_nash) HIPCHK(hipStreamSynchronize(stream)); // (the strategies' host copy is reused next turn)
+    if (solve_nash == 1) HIPCHK(hipStreamSynchronize(stream)); // (the strategies' host copy is reused next turn)
   }
 
   // pack: record bases in game order, the headers, the log's updates
@@ -574,6 +584,14 @@ int oakgpu_forest_selfplay(oakgpu_forest *f, oakgpu_net *net, const oakgpu_selfp
     HIPCHK(hipStreamSynchronize(stream));
   }
   return oakgpu_forest_selfplay_dev(f, net, prm, w->d_teams, w->d_seeds, w->d_seeds + n, n, solve_nash);
+}
+
+int oakgpu_forest_selfplay_last_traffic(const oakgpu_forest *f, uint64_t out[2]) {
+  if (!f || !out) return oakgpu_fail_msg("oakgpu_forest_selfplay_last_traffic: null argument");
+  const Workspace *w = (const Workspace *)oakgpu_forest_attachment(f);
+  out[0] = w ? w->loop_syncs : 0;
+  out[1] = w ? w->loop_copies : 0;
+  return 0;
 }
 
 int oakgpu_forest_selfplay_last_stats(const oakgpu_forest *f, uint64_t out[4]) {

@@ -84,6 +84,18 @@ void check(int rc) {
   if (rc != 0) throw std::runtime_error(oakgpu_last_error());
 }
 
+// solve_nash of the forest calls: False / True, "host" / "device", or the C ABI's 0 / 1 / 2 (2: the root matrices are solved on the GPU)
+int nash_mode(const py::object &v) {
+  if (py::isinstance<py::str>(v)) {
+    const std::string s = v.cast<std::string>();
+    if (s == "device") return 2;
+    if (s == "host") return 1;
+    throw std::runtime_error("solve_nash: True / False, \"host\", \"device\" or 0 / 1 / 2");
+  }
+  if (!py::isinstance<py::bool_>(v) && py::isinstance<py::int_>(v) && v.cast<long>() == 2) return 2;
+  return v.cast<bool>() ? 1 : 0;
+}
+
 std::mutex g_ctx_mu; // a context serves one caller at a time; search() drops the GIL, so two Python threads could meet here
 oakgpu_ctx *context() { // one context per process, created on first use (device from OAKGPU_DEVICE, default 0)
   static oakgpu_ctx *ctx = nullptr;
@@ -376,7 +388,8 @@ PYBIND11_MODULE(pyoak, m) {
       "search_forest",
       [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> battles, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> durations,
          py::array_t<uint8_t, py::array::c_style | py::array::forcecast> results, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> seeds,
-         Agent &agent) {
+         Agent &agent, py::object solve_nash_arg) {
+        const int solve_nash = nash_mode(solve_nash_arg);
         // not in pyoak: n positions searched at once, one GPU lane per tree (include/oakgpu.h: oakgpu_forest_search); output g is
         // search(input g, Heap(), agent, batch = 1, seed = seeds[g]).  The Agent's strings go through search's own parser; what the
         // forest does not run (time budgets, matrix_ucb, UCB1 / Exp3 / PExp3) is refused by name.
@@ -397,7 +410,7 @@ PYBIND11_MODULE(pyoak, m) {
           rc = oakgpu_agent_params(context(), &a, 1, 0, &P, &net);
           if (!rc) rc = oakgpu_forest_check((uint32_t)n, (uint32_t)std::min<uint64_t>(P.iterations, 0xFFFFFFFFu), P.bandit == 1, &P, net != nullptr, (uint32_t)n, results.data(), 0, 0);
           if (!rc && n) rc = oakgpu_forest_create(context(), (uint32_t)n, (uint32_t)P.iterations, P.bandit == 1, &forest);
-          if (!rc && n) rc = oakgpu_forest_search(forest, net, &P, battles.data(), durations.data(), results.data(), seeds.data(), (uint32_t)n, raw.data(), 1, nullptr, nullptr, 0);
+          if (!rc && n) rc = oakgpu_forest_search(forest, net, &P, battles.data(), durations.data(), results.data(), seeds.data(), (uint32_t)n, raw.data(), solve_nash, nullptr, nullptr, 0);
           if (rc) err = oakgpu_last_error();
           oakgpu_forest_destroy(context(), forest);
         }
@@ -405,13 +418,14 @@ PYBIND11_MODULE(pyoak, m) {
         for (size_t g = 0; g < n; ++g) out[g].raw = raw[g];
         return out;
       },
-      py::arg("battles"), py::arg("durations"), py::arg("results"), py::arg("seeds"), py::arg("agent"));
+      py::arg("battles"), py::arg("durations"), py::arg("results"), py::arg("seeds"), py::arg("agent"), py::arg("solve_nash") = true);
 
   m.def(
       "selfplay_forest",
       [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> teams, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> battle_seeds,
          py::array_t<uint64_t, py::array::c_style | py::array::forcecast> seeds, Agent &agent, const std::string &policy_mode, double policy_temp,
-         double policy_min, uint32_t max_battle_length, bool solve_nash, bool keep_node, uint32_t keep_arena) {
+         double policy_min, uint32_t max_battle_length, py::object solve_nash_arg, bool keep_node, uint32_t keep_arena) {
+        const int solve_nash = nash_mode(solve_nash_arg);
         // not in pyoak: the reference's `generate` loop for n games at once over the forest search (include/oakgpu.h:
         // oakgpu_forest_selfplay); game g is the per-game loop with batch = 1 and seed = seeds[g].  Returns (stream bytes, offsets, n_frames,
         // results, status); with keep_node (generate's --keep-node, on a kept forest of keep_arena nodes a tree, 0 = 4 * budget + 1) a sixth
@@ -440,10 +454,10 @@ PYBIND11_MODULE(pyoak, m) {
           const uint32_t cap = (uint32_t)std::min<uint64_t>(P.search.iterations, 0xFFFFFFFFu);
           if (!rc && keep_node) rc = oakgpu_forest_create_kept_check((uint32_t)std::max<size_t>(n, 1), cap, keep_arena);
           if (!rc) rc = oakgpu_forest_selfplay_check((uint32_t)n, cap, (P.search.bandit == 1 ? 1 : 0) | (keep_node ? OAKGPU_FOREST_KEPT : 0), &P, net != nullptr, (uint32_t)n,
-                                                     teams.data(), solve_nash ? 1 : 0);
+                                                     teams.data(), solve_nash);
           if (!rc && n) rc = keep_node ? oakgpu_forest_create_kept(context(), (uint32_t)n, cap, P.search.bandit == 1, keep_arena, &forest)
                                        : oakgpu_forest_create(context(), (uint32_t)n, cap, P.search.bandit == 1, &forest);
-          if (!rc && n) rc = oakgpu_forest_selfplay(forest, net, &P, teams.data(), battle_seeds.data(), seeds.data(), (uint32_t)n, solve_nash ? 1 : 0);
+          if (!rc && n) rc = oakgpu_forest_selfplay(forest, net, &P, teams.data(), battle_seeds.data(), seeds.data(), (uint32_t)n, solve_nash);
           size_t bytes = 0;
           if (!rc && n) rc = oakgpu_forest_selfplay_records(forest, nullptr, 0, &bytes, nullptr, nullptr, nullptr, nullptr, 0);
           if (!rc && n) {
@@ -468,7 +482,8 @@ PYBIND11_MODULE(pyoak, m) {
       [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> battles, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> durations,
          py::array_t<uint8_t, py::array::c_style | py::array::forcecast> results, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> seeds,
          Agent &agent_p1, Agent &agent_p2, const std::string &policy_p1, const std::string &policy_p2, double temp_p1, double temp_p2, double min_p1,
-         double min_p2, uint32_t max_turns, double early_stop, uint32_t log_turns, bool solve_nash, bool records) {
+         double min_p2, uint32_t max_turns, double early_stop, uint32_t log_turns, py::object solve_nash_arg, bool records) {
+        const int solve_nash = nash_mode(solve_nash_arg);
         // not in pyoak: the reference's `vs` loop with a budget for n games at once over the forest search (include/oakgpu.h:
         // oakgpu_forest_match); each seat's Agent strings go through search's own parser.  Returns a dict: results, turns, status, log
         // (uint8 [n, log_turns, 24], 0xFF where no game came), counts (wins, ties, losses of seat p1, stopped at max_turns).  records: the
@@ -499,7 +514,7 @@ PYBIND11_MODULE(pyoak, m) {
           std::memcpy(P.p1.policy_mode, policy_p1.c_str(), policy_p1.size() + 1);
           std::memcpy(P.p2.policy_mode, policy_p2.c_str(), policy_p2.size() + 1);
           P.p1.policy_temp = temp_p1; P.p2.policy_temp = temp_p2; P.p1.policy_min = min_p1; P.p2.policy_min = min_p2;
-          P.max_turns = max_turns; P.early_stop = early_stop; P.log_turns = log_turns; P.solve_nash = solve_nash ? 1 : 0;
+          P.max_turns = max_turns; P.early_stop = early_stop; P.log_turns = log_turns; P.solve_nash = solve_nash;
           const uint32_t cap = (uint32_t)std::min<uint64_t>(std::max(P.p1.search.iterations, P.p2.search.iterations), 0xFFFFFFFFu);
           const int contextual = P.p1.search.bandit == 1 || P.p2.search.bandit == 1;
           if (!rc) rc = oakgpu_forest_match_check((uint32_t)n, cap, contextual, &P, (uint32_t)n);
@@ -679,6 +694,42 @@ PYBIND11_MODULE(pyoak, m) {
         return py::make_tuple(p1, p2, (float)value);
       },
       py::arg("row_payoff"), py::arg("discretize_factor") = 256);
+
+  m.def(
+      "solve_matrices",
+      [](const std::vector<py::array_t<float>> &matrices, int discretize_factor) {
+        // not in pyoak: a batch of solve_matrix calls on the GPU (oakgpu_solve_matrices); entry k is solve_matrix(matrices[k], discretize_factor)
+        const size_t count = matrices.size();
+        std::vector<int32_t> disc(count * 81 + 1, 0), ms(count + 1, 0), ns(count + 1, 0);
+        for (size_t k = 0; k < count; ++k) {
+          if (matrices[k].ndim() != 2) throw std::runtime_error{"Expecting 2d array"};
+          const auto mm = matrices[k].shape(0), nn = matrices[k].shape(1);
+          if (mm < 1 || nn < 1 || mm > 9 || nn > 9) throw std::runtime_error("oakgpu_solve_matrices: matrix " + std::to_string(k) + ": payoff matrix must be between 1x1 and 9x9");
+          auto r = matrices[k].unchecked<2>();
+          for (py::ssize_t i = 0; i < mm; ++i)
+            for (py::ssize_t j = 0; j < nn; ++j) disc[k * 81 + (size_t)(i * nn + j)] = static_cast<int>(r(i, j) * discretize_factor);
+          ms[k] = (int32_t)mm; ns[k] = (int32_t)nn;
+        }
+        std::vector<double> a(count * 9 + 1), b(count * 9 + 1), value(count + 1);
+        int rc = 0;
+        std::string err;
+        {
+          py::gil_scoped_release release;
+          std::lock_guard<std::mutex> lock(g_ctx_mu);
+          rc = oakgpu_solve_matrices(context(), disc.data(), ms.data(), ns.data(), (uint32_t)count, discretize_factor, a.data(), b.data(), value.data());
+          if (rc) err = oakgpu_last_error();
+        }
+        if (rc) throw std::runtime_error(err);
+        py::list out;
+        for (size_t k = 0; k < count; ++k) {
+          py::array_t<float> p1(ms[k]), p2(ns[k]);
+          for (int i = 0; i < ms[k]; ++i) p1.mutable_unchecked<1>()(i) = (float)a[k * 9 + (size_t)i];
+          for (int j = 0; j < ns[k]; ++j) p2.mutable_unchecked<1>()(j) = (float)b[k * 9 + (size_t)j];
+          out.append(py::make_tuple(p1, p2, (float)value[k]));
+        }
+        return out;
+      },
+      py::arg("row_payoffs"), py::arg("discretize_factor") = 256);
 
   m.def(
       "read_battle_data",

@@ -138,7 +138,10 @@ def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="
                     keep_node=False, keep_arena=0):
     """n self-play games at once over the forest search, resident on the GPU (oakgpu_forest_selfplay*): game g is selfplay_game(ctx,
     teams[g], battle_seeds[g], batch=1, seed=seeds[g], ...).  teams uint8[n, 2, 6, 5]; forest: None (one made for this call) or a
-    search.Forest to reuse; stats: optional dict that receives turns, rows searched, compactions and host reads.
+    search.Forest to reuse; stats: optional dict that receives turns, rows searched, compactions and host reads (of the live count), and
+    loop_syncs / loop_copies: the turn loop's stream synchronisations and host <-> device copies.
+    solve_nash: True / "host" (the exact solves on the host's threads), "device" / 2 (on the GPU, on the stream: the same bits, two
+    synchronisations and two copies fewer per turn) or False (the nash fields are zeros).
     keep_node: generate's --keep-node -- each game's tree goes on from turn to turn (a kept forest: one made with keep_arena nodes per tree,
     0 = 4 * iterations + 1, or the caller's Forest(keep_arena=...)); a sixth value is then returned, nodes_kept uint32[n] (selfplay_game's
     stats["nodes_kept"] per game), and stats also receives nodes_kept, dropped, mismatches and carried_nodes.
@@ -166,7 +169,7 @@ def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="
             mine, theirs = torch.cuda.ExternalStream(ctx.stream_ptr(), device=dev), torch.cuda.current_stream(dev)
             mine.wait_stream(theirs)
             _lib.check(lib.oakgpu_forest_selfplay_dev(forest.handle, net, C.byref(prm), teams.data_ptr(), battle_seeds.data_ptr(), seeds.data_ptr(), n,
-                                                      int(bool(solve_nash))))
+                                                      _lib.nash_mode(solve_nash)))
             _lib.check(lib.oakgpu_forest_selfplay_records(forest.handle, None, 0, C.byref(size), None, None, None, None, 1))
             stream = torch.zeros(max(size.value, 1), dtype=torch.uint8, device=dev)
             offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
@@ -187,7 +190,7 @@ def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="
             bs = np.ascontiguousarray(np.asarray(battle_seeds).astype(np.uint64)).reshape(n)
             sd = np.ascontiguousarray(np.asarray(seeds).astype(np.uint64)).reshape(n)
             vp = lambda a: a.ctypes.data_as(C.c_void_p)
-            _lib.check(lib.oakgpu_forest_selfplay(forest.handle, net, C.byref(prm), vp(t), vp(bs), vp(sd), n, int(bool(solve_nash))))
+            _lib.check(lib.oakgpu_forest_selfplay(forest.handle, net, C.byref(prm), vp(t), vp(bs), vp(sd), n, _lib.nash_mode(solve_nash)))
             _lib.check(lib.oakgpu_forest_selfplay_records(forest.handle, None, 0, C.byref(size), None, None, None, None, 0))
             stream = np.zeros(max(size.value, 1), np.uint8)
             offsets, n_frames = np.zeros(n + 1, np.uint64), np.zeros(max(n, 1), np.uint32)
@@ -203,6 +206,9 @@ def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="
             st = (C.c_uint64 * 4)()
             _lib.check(lib.oakgpu_forest_selfplay_last_stats(forest.handle, C.byref(st)))
             stats.update(turns=int(st[0]), rows=int(st[1]), compactions=int(st[2]), host_reads=int(st[3]))
+            tr = (C.c_uint64 * 2)()
+            _lib.check(lib.oakgpu_forest_selfplay_last_traffic(forest.handle, C.byref(tr)))
+            stats.update(loop_syncs=int(tr[0]), loop_copies=int(tr[1]))
             if keep_node:
                 _lib.check(lib.oakgpu_forest_selfplay_keep_stats(forest.handle, C.byref(st)))
                 stats.update(nodes_kept=int(st[0]), dropped=int(st[1]), mismatches=int(st[2]), carried_nodes=int(st[3]))
@@ -224,7 +230,7 @@ def forest_selfplay_check(max_trees, max_iterations, contextual, iterations, n=1
     prm.keep_node, prm.search.matrix_ucb, prm.search.duration_us = int(bool(keep_node)), int(matrix_ucb), int(duration_us)
     t = None if teams is None else np.ascontiguousarray(teams, dtype=np.uint8).reshape(n, 60)
     _lib.check(_lib.load().oakgpu_forest_selfplay_check(int(max_trees), int(max_iterations), int(bool(contextual)) | (2 if kept else 0), C.byref(prm), int(bool(has_net)), int(n),
-                                                        None if t is None else t.ctypes.data_as(C.c_void_p), int(bool(solve_nash))))
+                                                        None if t is None else t.ctypes.data_as(C.c_void_p), _lib.nash_mode(solve_nash)))
 
 
 def selfplay_pick_host(m, n, visit_matrix, value_matrix, iterations, rng, p1_nash=None, p2_nash=None, nash_value=0.0, p1_prior=None, p2_prior=None,

@@ -5,6 +5,8 @@ Mirrors two pieces of the reference's search surface:
     MCTS::Search::process_output, cpp/include/search/mcts.h:620-659, through the absent lrsnash/GMP library):
     exact Nash equilibrium of a <= 9 x 9 one-sum matrix game with integer payoffs -- a thin call into the C ABI
     (oakgpu_solve_matrix: integer-pivoting simplex, Bland's rule, no floating point in the solve).
+  * `solve_matrices(ctx, matrices, discretize_factor)`: a batch of those on the GPU, one workgroup per matrix, the same bits
+    (oakgpu_solve_matrices, oak_amd/csrc/nashdev.hip).
   * `root_matrix_search(...)`: for every joint action (i, j) of the root and R replicas, re-seed + resample hidden
     counters (mcts.h:254-259), apply the joint action with ONE batched update on the GPU, evaluate the R x m x n
     children with GPU rollouts (or the GPU network), average into the value matrix and solve it.  Output fields
@@ -34,6 +36,24 @@ def solve_matrix(payoffs, discretize_factor=256):
     _lib.check(_lib.load().oakgpu_solve_matrix(M.ctypes.data_as(C.c_void_p), m, n, int(discretize_factor), p1.ctypes.data_as(C.c_void_p),
                                                p2.ctypes.data_as(C.c_void_p), C.cast(C.byref(v), C.c_void_p)))
     return p1, p2, v.value
+
+
+def solve_matrices(ctx, matrices, discretize_factor=256):
+    """A batch of solve_matrix calls on the GPU (oakgpu_solve_matrices: one workgroup per matrix, oak_amd/csrc/nashdev.hip): entry k is
+    solve_matrix(matrices[k], discretize_factor) bit for bit, and what that call refuses fails the whole call.  matrices: a sequence of
+    m x n integer arrays (shapes may differ).  Returns a list of (p1 float[m], p2 float[n], value float)."""
+    mats = [np.asarray(P) for P in matrices]
+    count = len(mats)
+    pay, ms, ns = np.zeros((max(count, 1), 81), np.int32), np.zeros(max(count, 1), np.int32), np.zeros(max(count, 1), np.int32)
+    for k, P in enumerate(mats):
+        if P.ndim != 2 or P.shape[0] < 1 or P.shape[1] < 1 or P.shape[0] > 9 or P.shape[1] > 9:
+            raise RuntimeError("solve_matrices: matrix %d: payoff matrix must be between 1x1 and 9x9" % k)
+        ms[k], ns[k] = P.shape
+        pay[k, :P.size] = np.ascontiguousarray(P, dtype=np.int32).reshape(-1)
+    p1, p2, v = np.zeros((max(count, 1), 9)), np.zeros((max(count, 1), 9)), np.zeros(max(count, 1))
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    _lib.check(ctx.lib.oakgpu_solve_matrices(ctx.handle, vp(pay), vp(ms), vp(ns), count, int(discretize_factor), vp(p1), vp(p2), vp(v)))
+    return [(p1[k, :ms[k]].copy(), p2[k, :ns[k]].copy(), float(v[k])) for k in range(count)]
 
 
 def root_matrix_search(ctx, battle, durations, result, replicas=256, seed=0x5EED, evaluator="mc", max_steps=1000):
@@ -353,7 +373,8 @@ def forest_search(ctx, battles, durations, results, seeds, iterations, c=2.0, ba
     "pucb"; evaluator "mc", "poke-engine" or a Network; forest: None (one made for this call) or a Forest to reuse.
     keep=True (a Forest made with keep_arena): the kept form, oakgpu_forest_search_kept* -- every tree goes on where the forest's last call
     or Forest.advance left it, as tree_search does on a heap; an initialised root is left alone and the outputs' priors are zeros.
-    numpy arrays in: a list of n dicts with tree_search's keys (nash fields only with solve_nash) plus "stream" (the tree's continuing
+    numpy arrays in: a list of n dicts with tree_search's keys (nash fields only with solve_nash; "device" or 2 solves all n
+    root matrices in one launch on the GPU, the same bits) plus "stream" (the tree's continuing
     fast_prng state) and, with trace_levels > 0, "trace" (iterations records of trace_dtype(trace_levels)) and -- when the call made its own
     forest -- "tree" (Forest.nodes of the tree: with a forest of the caller's, read them from it).
     torch GPU tensors in (battles [n, 384], durations [n, 8], results [n] uint8; seeds [n] int64 bit patterns): a dict of tensors on that
@@ -396,7 +417,7 @@ def forest_search(ctx, battles, durations, results, seeds, iterations, c=2.0, ba
         streams = np.zeros(max(n, 1), np.uint64)
         trace = np.zeros((n, int(iterations)), dtype=trace_dtype(trace_levels)) if trace_levels else None
         _lib.check((ctx.lib.oakgpu_forest_search_kept if keep else ctx.lib.oakgpu_forest_search)(forest.handle, net, C.byref(prm), battles.ctypes.data_as(C.c_void_p), durations.ctypes.data_as(C.c_void_p),
-                                                results.ctypes.data_as(C.c_void_p), seeds.ctypes.data_as(C.c_void_p), n, outs, int(bool(solve_nash)),
+                                                results.ctypes.data_as(C.c_void_p), seeds.ctypes.data_as(C.c_void_p), n, outs, _lib.nash_mode(solve_nash),
                                                 streams.ctypes.data_as(C.c_void_p), trace.ctypes.data_as(C.c_void_p) if trace_levels else None,
                                                 int(trace_levels)))
         res = []

@@ -51,8 +51,9 @@ def child(a):
     ev = w["eval"] if w["eval"] in ("mc", "poke-engine") else Network(ctx, path=os.path.join(ROOT, "tests", "golden", w["eval"]))
     teams, battle_seeds, seeds = draw(a.games, a.seed)
     if a.child == "forest":
+        nash = False if a.no_nash else ("device" if a.device_nash else True)
         forest = Forest(ctx, a.games, a.budget, contextual=w["bandit"] == "pucb", keep_arena=a.keep_arena if a.keep_node else None)
-        kw = dict(c=w["c"], bandit=w["bandit"], evaluator=ev, policy_mode=w["mode"], forest=forest, solve_nash=not a.no_nash, keep_node=a.keep_node)
+        kw = dict(c=w["c"], bandit=w["bandit"], evaluator=ev, policy_mode=w["mode"], forest=forest, solve_nash=nash, keep_node=a.keep_node)
         forest_selfplay(ctx, teams, battle_seeds, seeds, a.budget, max_battle_length=2, **kw)
         ctx.synchronize()
         stats = {}
@@ -60,7 +61,7 @@ def child(a):
         out = forest_selfplay(ctx, teams, battle_seeds, seeds, a.budget, stats=stats, **kw)
         s = time.perf_counter() - t
         frames, kept = int(out[2][out[4] == 0].sum()), int((out[4] == 0).sum())
-        res = dict(form="forest", s=s, games=kept, frames=frames, dropped=a.games - kept, bytes=len(out[0]), solve_nash=not a.no_nash, keep_node=a.keep_node)
+        res = dict(form="forest", s=s, games=kept, frames=frames, dropped=a.games - kept, bytes=len(out[0]), solve_nash=nash, keep_node=a.keep_node)
         if a.keep_node:
             res.update(keep_node_ratio=stats["nodes_kept"] / max(stats["rows"], 1), mean_kept_nodes_per_turn=stats["carried_nodes"] / max(stats["rows"], 1),
                        trees_dropped=stats.pop("dropped"))
@@ -110,6 +111,7 @@ def main():
     ap.add_argument("--workload", default="ucb_fp")
     ap.add_argument("--games", type=int, default=256)
     ap.add_argument("--no-nash", action="store_true")
+    ap.add_argument("--device-nash", action="store_true", help="child forest: solve the root matrices on the GPU (tools/device_nash_bench.py)")
     ap.add_argument("--keep-node", action="store_true")
     ap.add_argument("--keep-arena", type=int, default=0)
     a = ap.parse_args()

@@ -4,7 +4,7 @@ files under --out.
 
   python tools/generate_battle_data.py --out DIR [--games N] [--batch B] [--teams FILE] [--budget K] [--bandit ucb-2.0 | pucb-1.5]
          [--eval mc | fp | NET.battle.net] [--discrete] [--policy-mode e] [--policy-temp 1] [--policy-min 0] [--max-battle-length L]
-         [--no-nash] [--seed S] [--file-mb 8] [--keep-node [--keep-arena NODES]]
+         [--no-nash | --device-nash] [--seed S] [--file-mb 8] [--keep-node [--keep-arena NODES]]
 
 --teams FILE: JSON {"teams": [[[species, move, move, move, move] x 6] ...]} by name, the layout of tests/golden/ou_sample_teams.json (the
 default: the reference's 16 sample teams); each game draws its two teams from the file with --seed's generator, a pair that fails the
@@ -57,6 +57,7 @@ def main():
     ap.add_argument("--policy-min", type=float, default=0.0)
     ap.add_argument("--max-battle-length", type=int, default=0)
     ap.add_argument("--no-nash", action="store_true")
+    ap.add_argument("--device-nash", action="store_true", help="solve the root matrices on the GPU (the same bits, no host round trip)")
     ap.add_argument("--seed", type=int, default=0x0A4B)
     ap.add_argument("--file-mb", type=float, default=8.0)
     ap.add_argument("--keep-node", action="store_true")
@@ -102,7 +103,7 @@ def main():
         stats = {}
         stream, offsets, n_frames, results, status = forest_selfplay(
             ctx, teams, battle_seeds, seeds, a.budget, c=float(c or 2.0), bandit=name, evaluator=evaluator, policy_mode=a.policy_mode,
-            policy_temp=a.policy_temp, policy_min=a.policy_min, max_battle_length=a.max_battle_length, forest=forest, solve_nash=not a.no_nash,
+            policy_temp=a.policy_temp, policy_min=a.policy_min, max_battle_length=a.max_battle_length, forest=forest, solve_nash=False if a.no_nash else ("device" if a.device_nash else True),
             keep_node=a.keep_node, stats=stats)[:5]
         if a.keep_node:   # RuntimeData::update_with_node_counter / update_counter (generate.cc:412-416)
             updates, updates_with_node, trees_dropped = updates + int(n_frames.sum()), updates_with_node + stats["nodes_kept"], trees_dropped + stats["dropped"]

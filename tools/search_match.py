@@ -9,7 +9,7 @@ searching on the forest search (oak_amd.arena.search_match), and prints the refe
 usage: search_match.py [--budget N] [--bandit ucb-2.0] [--eval mc|fp|FILE.battle.net] [--policy-mode e] [--policy-temp T] [--policy-min M]
                        [--pX-budget ... --pX-bandit ... --pX-eval ... --pX-policy-mode ... --pX-policy-temp ... --pX-policy-min ...
                         --pX-discrete]   (X = 1, 2: that seat alone; the unprefixed flags set both)
-                       [--max-games N] [--teams FILE] [--mirror-match] [--early-stop 10.0] [--max-turns 1000] [--no-nash] [--seed S]
+                       [--max-games N] [--teams FILE] [--mirror-match] [--early-stop 10.0] [--max-turns 1000] [--no-nash | --device-nash] [--seed S]
                        [--json out.json] [--dir DIR]
 
 --budget: iterations (time budgets are not run by the forest search).  --bandit: ucb-<c> or pucb-<c> (pucb needs a network eval).
@@ -58,6 +58,7 @@ def main():
     ap.add_argument("--early-stop", type=float, default=10.0)
     ap.add_argument("--max-turns", type=int, default=1000)
     ap.add_argument("--no-nash", action="store_true")
+    ap.add_argument("--device-nash", action="store_true", help="solve the root matrices on the GPU (the same bits, no host round trip)")
     ap.add_argument("--seed", type=int, default=0x0A4B)
     ap.add_argument("--json")
     ap.add_argument("--dir")
@@ -70,7 +71,7 @@ def main():
     from policy_match import team_bytes
     ctx = Context(0)
     res = arena.search_match(ctx, a1, a2, team_bytes(a.teams), a.max_games, a.seed, mirror=a.mirror_match, max_turns=a.max_turns, early_stop=a.early_stop,
-                             solve_nash=not a.no_nash, records_dir=a.dir)
+                             solve_nash=False if a.no_nash else ("device" if a.device_nash else True), records_dir=a.dir)
     print("score: %g over %d games; Elo diff: %g" % (res["score"], res["games"], res["elo"]))
     print("W D L:")
     print("%d %d %d" % (res["W"], res["D"], res["L"]))
