@@ -1185,6 +1185,83 @@ int oakgpu_party_variant(const uint8_t base[24], uint8_t key, uint8_t out[24], u
 int oakgpu_set_search_party_table(oakgpu_ctx *ctx, int on);
 int oakgpu_search_party_table_stats(oakgpu_ctx *ctx, uint64_t *fills, uint64_t *evals);
 
+/* ---- Training the battle network: the optimiser step of the reference's `battle` program (src/oak/battle.py:203-262 around
+ * BattleNetwork.inference, src/oak/torch.py:399-430) on rows 0 .. n-1 of an oakgpu_encoded_frames, the tensors oakgpu_frames_sample_dev
+ * fills.  A TRAINER owns, for one network, the fp32 parameters of the 12 Affine blocks of a `.battle.net` (24 tensors in file order:
+ * bias, then weight [out][in], per block), a gradient block and Adam's m and v of the same layout -- each `count` floats, the tensors
+ * back to back -- and workspaces for up to max_rows rows.  It is made from the bytes of a `.battle.net`; header byte 0 gives the
+ * activation (0 relu, 1 clamp[0,1]).  The widths are held to the loader's limits, so every trained network loads into the evaluators:
+ * embedding widths <= 128, main / value / policy hidden <= 256, inputs 198 / 427, policy output 315, fc0's input = 2 x side.
+ *   Forward, per row:  party = act(pokemon_net(pokemon[:, :, 1:6])) and active = act(active_net(cat(active[:, :, 0], pokemon[:, :, 0])))
+ * -- both layers of an embedding net are activated -- each times (hp != 0) of its slot; side = [hp_0, active, 5 x (hp_slot, party_slot)];
+ * h = act(fc1(act(fc0(cat(side_0, side_1))))); value = sigmoid(value_fc3(act(value_fc2(h)))); per side s, with q = act(policy_fc2_s(h)):
+ * logit_i = policy_fc3_s(q)[choice_indices[s][i]] for i < k[s], and only those (an index outside 0 .. 314 names nothing: logit 0, no gradient;
+ * k above 9 counts as 9).
+ *   Loss: vt = (wn * nash_value + we * empirical_value) + ws * score;  sq_err = (value - vt)^2;  ce[s] = -sum_i t_i logp_i / max(1, #{t_i != 0})
+ * with t = (1 - pn) * empirical + pn * nash and logp the log-softmax over the k legal logits (oakgpu_corpus_loss_dev's terms);
+ * mse, ce_p1, ce_p2 = their means over the rows whose status is OK;  loss = value_weight * mse + policy_weight * (ce_p1 + ce_p2).  A row that
+ * is not OK contributes nothing to any term or gradient whatever its other tensors hold (NaN included), its per-row outputs are 0.
+ * value_weight == 0 && policy_weight == 0 is refused.
+ *   Backward: the exact gradient of `loss`, with torch autograd's conventions at the kinks (relu: 0 at 0; clamp: 1 at both ends).  Every
+ * sum over rows runs in a fixed order -- accumulation chains of 32 terms, their sums combined in a fixed order, no float
+ * atomics -- so two calls on the same inputs give the same bits.
+ *   Adam: torch.optim.Adam's defaults (betas 0.9 / 0.999, eps 1e-8, no weight decay, bias correction): m = b1 m + (1-b1) g; v = b2 v +
+ * (1-b2) g g; p -= [lr / (1 - b1^t)] * m / (sqrt(v) / sqrt(1 - b2^t) + eps), the two bracketed scalars computed on the host in double per
+ * step and passed as floats; clamp_weights: the weights (not the biases) are clamped to [-2, 2] after the update.  Three parameter GROUPS,
+ * each with its own step count t: TRUNK (both embedding nets, fc0, fc1), VALUE (value_fc2, value_fc3), POLICY (the four policy blocks).  A
+ * group whose loss weight is zero receives no gradient: its gradients, parameters, m, v and t stay bit for bit as they are.
+ *   A gradients / step call with no OK row: the report says rows = 0, the gradient block of the groups that receive one is zero, and
+ * step's update does not happen: parameters, m and v stay as they are, and the groups' t are set back at the next oakgpu_trainer_report.
+ *   The _dev calls take device rows and are asynchronous on the context's stream; nothing in a loop of steps waits for the device.  The report lives
+ * in device memory; oakgpu_trainer_report copies it out and is the call that waits. */
+/* battle.py's symmetries (permute_sides, permute_pokemon: it applies them to every batch unless told not to) on rows 0 .. n-1, in place, on the
+ * device, asynchronous on the context's stream.  Row i draws from its own fast_prng stream seeded seed + i, as the sampler's draws do, so a row
+ * does not depend on the batch: the first uniform_64 flips the sides when its lowest bit is set -- pokemon, active, hp, choice_indices, k,
+ * empirical_policies and nash_policies swap along the side axis, empirical_value, nash_value and score become 1 - x; four more draws make a
+ * Fisher-Yates permutation of the five bench slots (q = 4 .. 1: slot q <-> slot draw % (q + 1)), the same on both sides.  All five draws are
+ * made whatever flip_sides / permute_bench switch off.  DEPARTURE from the reference: hp[:, :, 1:] moves with its Pokemon (src/oak/torch.py:30-35
+ * leaves it in place, which pairs a Pokemon's embedding with another slot's hp and mask).  A row that is not OK is left as it is. */
+int oakgpu_frames_symmetries_dev(oakgpu_ctx *ctx, const oakgpu_encoded_frames *rows, uint32_t n, uint64_t seed, int flip_sides, int permute_bench);
+typedef struct oakgpu_trainer oakgpu_trainer;
+typedef struct { float wn, we, ws, pn, value_weight, policy_weight; } oakgpu_train_loss;
+typedef struct { double loss, mse, ce_p1, ce_p2; uint64_t rows; } oakgpu_train_report;
+/* each nullable: value [n], logits [n,2,9] (0 behind the counts), sq_err [n], ce [n,2] */
+typedef struct { float *value, *logits, *sq_err, *ce; } oakgpu_train_outputs;
+enum { OAKGPU_TRAIN_PARAMETERS = 0, OAKGPU_TRAIN_GRADIENTS = 1, OAKGPU_TRAIN_M = 2, OAKGPU_TRAIN_V = 3 };
+enum { OAKGPU_GROUP_TRUNK = 1, OAKGPU_GROUP_VALUE = 2, OAKGPU_GROUP_POLICY = 4 };
+/* Host only, no GPU: every refusal of create (the file, max_rows) and of a call (n > max_rows; loss, nullable: both weights zero), by name. */
+int oakgpu_trainer_check(const uint8_t *net, size_t size, uint32_t max_rows, uint32_t n, const oakgpu_train_loss *loss);
+/* The trainer belongs to ctx and must be destroyed before it. */
+int oakgpu_trainer_create(oakgpu_ctx *ctx, const uint8_t *net, size_t size, uint32_t max_rows, oakgpu_trainer **out);
+void oakgpu_trainer_destroy(oakgpu_trainer *trainer);
+/* dims (nullable): in, out of the 12 blocks; count (nullable): floats per block of parameters; max_rows (nullable). */
+int oakgpu_trainer_shape(const oakgpu_trainer *trainer, uint32_t dims[24], size_t *count, uint32_t *max_rows);
+/* forward + loss: the report and, where asked for, the per-row outputs.  No gradient, no parameter is touched. */
+int oakgpu_trainer_forward_dev(oakgpu_ctx *ctx, oakgpu_trainer *trainer, const oakgpu_encoded_frames *rows, uint32_t n, const oakgpu_train_loss *loss,
+                               const oakgpu_train_outputs *out /* nullable */);
+/* forward + backward into the gradient block (and the report) */
+int oakgpu_trainer_gradients_dev(oakgpu_ctx *ctx, oakgpu_trainer *trainer, const oakgpu_encoded_frames *rows, uint32_t n, const oakgpu_train_loss *loss);
+/* the Adam update alone, from the gradient block as it stands, of the groups named (OAKGPU_GROUP_* or-ed); their t advance by one */
+int oakgpu_trainer_adam_dev(oakgpu_ctx *ctx, oakgpu_trainer *trainer, float lr, int clamp_weights, uint32_t groups);
+/* gradients, then adam of the groups whose loss weight is not zero */
+int oakgpu_trainer_step_dev(oakgpu_ctx *ctx, oakgpu_trainer *trainer, const oakgpu_encoded_frames *rows, uint32_t n, const oakgpu_train_loss *loss, float lr,
+                            int clamp_weights);
+/* Waits for the stream.  out (nullable): the last forward / gradients / step call's report; steps (nullable): t of the three groups. */
+int oakgpu_trainer_report(oakgpu_ctx *ctx, oakgpu_trainer *trainer, oakgpu_train_report *out, uint64_t steps[3]);
+/* which = OAKGPU_TRAIN_*: `count` floats to the host, the 24 tensors in file order (waits for the stream) */
+int oakgpu_trainer_read(oakgpu_ctx *ctx, oakgpu_trainer *trainer, int which, float *host, size_t count);
+/* overwrites the gradient block from the host (the Adam update can then be run alone on any gradient) */
+int oakgpu_trainer_set_gradients(oakgpu_ctx *ctx, oakgpu_trainer *trainer, const float *host, size_t count);
+/* The parameters as `.battle.net` bytes: *size always; the bytes when out is not NULL and capacity >= *size.  Before any update these
+ * are exactly the bytes the trainer was made from. */
+int oakgpu_trainer_net_bytes(oakgpu_ctx *ctx, oakgpu_trainer *trainer, uint8_t *out, size_t capacity, size_t *size);
+/* host rows in (staged), host outputs out; the calls return complete */
+int oakgpu_trainer_forward(oakgpu_ctx *ctx, oakgpu_trainer *trainer, const oakgpu_encoded_frames *rows, uint32_t n, const oakgpu_train_loss *loss,
+                           const oakgpu_train_outputs *out /* nullable */);
+int oakgpu_trainer_gradients(oakgpu_ctx *ctx, oakgpu_trainer *trainer, const oakgpu_encoded_frames *rows, uint32_t n, const oakgpu_train_loss *loss);
+int oakgpu_trainer_step(oakgpu_ctx *ctx, oakgpu_trainer *trainer, const oakgpu_encoded_frames *rows, uint32_t n, const oakgpu_train_loss *loss, float lr,
+                        int clamp_weights);
+
 #ifdef __cplusplus
 }
 #endif

@@ -666,6 +666,74 @@ private:
   oakgpu_corpus *corpus_{};
 };
 
+// The optimiser step of a battle network on the device (oakgpu_trainer_*): parameters, gradients and Adam's state of one `.battle.net`, trained on
+// rows of an EncodedFrames (host rows, staged; the _dev calls of oakgpu.h take device rows).  Must not outlive its Context.
+class Trainer {
+public:
+  Trainer(Context &ctx, const std::vector<uint8_t> &net_bytes, uint32_t max_rows) : ctx_{ctx.get()} {
+    check(oakgpu_trainer_create(ctx_, net_bytes.data(), net_bytes.size(), max_rows, &trainer_));
+    check(oakgpu_trainer_shape(trainer_, nullptr, &count_, nullptr));
+  }
+  ~Trainer() { oakgpu_trainer_destroy(trainer_); }
+  Trainer(const Trainer &) = delete;
+  Trainer &operator=(const Trainer &) = delete;
+  oakgpu_trainer *get() const noexcept { return trainer_; }
+  size_t count() const noexcept { return count_; }   // floats per block: the 24 tensors in file order
+  // host only: throws naming what create, or a call of n rows with this loss, would refuse
+  static void check_net(const std::vector<uint8_t> &net_bytes, uint32_t max_rows, uint32_t n = 0, const oakgpu_train_loss *loss = nullptr) {
+    check(oakgpu_trainer_check(net_bytes.data(), net_bytes.size(), max_rows, n, loss));
+  }
+  // value [n], logits [n,2,9], sq_err [n], ce [n,2] of rows 0 .. n-1 (each vector nullable)
+  void forward(EncodedFrames &rows, uint32_t n, const oakgpu_train_loss &loss, std::vector<float> *value = nullptr, std::vector<float> *logits = nullptr,
+               std::vector<float> *sq_err = nullptr, std::vector<float> *ce = nullptr) {
+    if (n > rows.size) throw std::runtime_error{"oakgpu: more rows than the batch holds"};
+    if (value) value->assign(n, 0.0f);
+    if (logits) logits->assign(static_cast<size_t>(n) * 18, 0.0f);
+    if (sq_err) sq_err->assign(n, 0.0f);
+    if (ce) ce->assign(static_cast<size_t>(n) * 2, 0.0f);
+    const oakgpu_encoded_frames p = rows.pointers();
+    const oakgpu_train_outputs out{value ? value->data() : nullptr, logits ? logits->data() : nullptr, sq_err ? sq_err->data() : nullptr, ce ? ce->data() : nullptr};
+    check(oakgpu_trainer_forward(ctx_, trainer_, &p, n, &loss, &out));
+  }
+  void gradients(EncodedFrames &rows, uint32_t n, const oakgpu_train_loss &loss) {
+    if (n > rows.size) throw std::runtime_error{"oakgpu: more rows than the batch holds"};
+    const oakgpu_encoded_frames p = rows.pointers();
+    check(oakgpu_trainer_gradients(ctx_, trainer_, &p, n, &loss));
+  }
+  void adam(float lr, bool clamp_weights = false, uint32_t groups = OAKGPU_GROUP_TRUNK | OAKGPU_GROUP_VALUE | OAKGPU_GROUP_POLICY) {
+    check(oakgpu_trainer_adam_dev(ctx_, trainer_, lr, clamp_weights ? 1 : 0, groups));
+  }
+  void step(EncodedFrames &rows, uint32_t n, const oakgpu_train_loss &loss, float lr, bool clamp_weights = false) {
+    if (n > rows.size) throw std::runtime_error{"oakgpu: more rows than the batch holds"};
+    const oakgpu_encoded_frames p = rows.pointers();
+    check(oakgpu_trainer_step(ctx_, trainer_, &p, n, &loss, lr, clamp_weights ? 1 : 0));
+  }
+  // waits for the device; steps (nullable): the three groups' step counts
+  oakgpu_train_report report(uint64_t steps[3] = nullptr) {
+    oakgpu_train_report r{};
+    check(oakgpu_trainer_report(ctx_, trainer_, &r, steps));
+    return r;
+  }
+  std::vector<float> read(int which = OAKGPU_TRAIN_PARAMETERS) {
+    std::vector<float> block(count_);
+    check(oakgpu_trainer_read(ctx_, trainer_, which, block.data(), count_));
+    return block;
+  }
+  void set_gradients(const std::vector<float> &block) { check(oakgpu_trainer_set_gradients(ctx_, trainer_, block.data(), block.size())); }
+  std::vector<uint8_t> net_bytes() {
+    size_t size = 0;
+    check(oakgpu_trainer_net_bytes(ctx_, trainer_, nullptr, 0, &size));
+    std::vector<uint8_t> out(size);
+    check(oakgpu_trainer_net_bytes(ctx_, trainer_, out.data(), out.size(), &size));
+    return out;
+  }
+
+private:
+  oakgpu_ctx *ctx_{};
+  oakgpu_trainer *trainer_{};
+  size_t count_{};
+};
+
 // The path's one exchange step for root-parallel search sharded over the GPUs of a node (one process per GPU): reduce the
 // rank's leaf values to one mean per root on the device, then ONE ncclAllGather (RCCL over xGMI) of those means.
 class Exchange {

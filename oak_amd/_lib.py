@@ -42,6 +42,10 @@ SYMBOLS = [
     "oakgpu_forest_selfplay_nodes_kept", "oakgpu_forest_selfplay_keep_stats",
     "oakgpu_nash_solve_dev", "oakgpu_solve_matrices", "oakgpu_nash_soft_host", "oakgpu_nash_round_host", "oakgpu_nash_width4_max_entry",
     "oakgpu_forest_selfplay_last_traffic",
+    "oakgpu_frames_symmetries_dev", "oakgpu_trainer_check", "oakgpu_trainer_create", "oakgpu_trainer_destroy", "oakgpu_trainer_shape",
+    "oakgpu_trainer_forward_dev", "oakgpu_trainer_gradients_dev", "oakgpu_trainer_adam_dev", "oakgpu_trainer_step_dev", "oakgpu_trainer_report",
+    "oakgpu_trainer_read", "oakgpu_trainer_set_gradients", "oakgpu_trainer_net_bytes", "oakgpu_trainer_forward", "oakgpu_trainer_gradients",
+    "oakgpu_trainer_step",
 ]
 
 
@@ -115,6 +119,18 @@ class CorpusTerms(C.Structure):       # oakgpu_corpus_terms
 class CorpusLosses(C.Structure):      # oakgpu_corpus_losses
     _fields_ = [("sq_err", C.c_double), ("ce1", C.c_double), ("ce2", C.c_double), ("rows", C.c_uint64), ("excluded", C.c_uint64), ("failed", C.c_uint64),
                 ("mse", C.c_double), ("ce_p1", C.c_double), ("ce_p2", C.c_double)]
+
+
+class TrainLoss(C.Structure):         # oakgpu_train_loss
+    _fields_ = [(name, C.c_float) for name in ("wn", "we", "ws", "pn", "value_weight", "policy_weight")]
+
+
+class TrainReport(C.Structure):       # oakgpu_train_report
+    _fields_ = [("loss", C.c_double), ("mse", C.c_double), ("ce_p1", C.c_double), ("ce_p2", C.c_double), ("rows", C.c_uint64)]
+
+
+class TrainOutputs(C.Structure):      # oakgpu_train_outputs: one nullable pointer per tensor, device or host as the call says
+    _fields_ = [(name, C.c_void_p) for name in ("value", "logits", "sq_err", "ce")]
 
 
 class Seat(C.Structure):              # oakgpu_seat
@@ -375,6 +391,25 @@ def load():
     lib.oakgpu_forest_match_records.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, vp, vp, i32]
     lib.oakgpu_match_pick_host.argtypes = [i32, u32, u32, vp, vp, u64, vp, vp, C.c_char_p, C.c_double, C.c_double, C.c_double, C.POINTER(u64), vp,
                                            C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+    f32, sz = C.c_float, C.c_size_t
+    rows_p, loss_p, outs_p = C.POINTER(EncodedFrames), C.POINTER(TrainLoss), C.POINTER(TrainOutputs)
+    lib.oakgpu_frames_symmetries_dev.argtypes = [vp, rows_p, u32, u64, i32, i32]
+    lib.oakgpu_trainer_check.argtypes = [vp, sz, u32, u32, loss_p]
+    lib.oakgpu_trainer_create.argtypes = [vp, vp, sz, u32, C.POINTER(vp)]
+    lib.oakgpu_trainer_destroy.argtypes = [vp]
+    lib.oakgpu_trainer_destroy.restype = None
+    lib.oakgpu_trainer_shape.argtypes = [vp, C.POINTER(u32 * 24), C.POINTER(sz), C.POINTER(u32)]
+    lib.oakgpu_trainer_forward_dev.argtypes = [vp, vp, rows_p, u32, loss_p, outs_p]
+    lib.oakgpu_trainer_forward.argtypes = lib.oakgpu_trainer_forward_dev.argtypes
+    lib.oakgpu_trainer_gradients_dev.argtypes = [vp, vp, rows_p, u32, loss_p]
+    lib.oakgpu_trainer_gradients.argtypes = lib.oakgpu_trainer_gradients_dev.argtypes
+    lib.oakgpu_trainer_adam_dev.argtypes = [vp, vp, f32, i32, u32]
+    lib.oakgpu_trainer_step_dev.argtypes = [vp, vp, rows_p, u32, loss_p, f32, i32]
+    lib.oakgpu_trainer_step.argtypes = lib.oakgpu_trainer_step_dev.argtypes
+    lib.oakgpu_trainer_report.argtypes = [vp, vp, C.POINTER(TrainReport), C.POINTER(u64 * 3)]
+    lib.oakgpu_trainer_read.argtypes = [vp, vp, i32, vp, sz]
+    lib.oakgpu_trainer_set_gradients.argtypes = [vp, vp, vp, sz]
+    lib.oakgpu_trainer_net_bytes.argtypes = [vp, vp, vp, sz, C.POINTER(sz)]
     _lib = lib
     return lib
 

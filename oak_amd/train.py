@@ -12,7 +12,9 @@ With device=None the tensors are numpy arrays and the calls go through the stage
 Scoring a network on every frame of a corpus (k_frames_expand, k_corpus_terms, k_corpus_record_sums in oak_amd/csrc/corpuseval.hip):
 
     out = corpus.inference(net)                        # value [F,1], policy_logit [F,2,9], policy [F,2,9], k, status, where, picks
-    losses = corpus.evaluate(net, 0.0, 0.5, 0.5, 0.5)  # mse, ce_p1, ce_p2, rows, excluded, failed"""
+    losses = corpus.evaluate(net, 0.0, 0.5, 0.5, 0.5)  # mse, ce_p1, ce_p2, rows, excluded, failed
+
+The optimiser step on such batches (oak_amd/csrc/trainer.hip): Trainer, apply_symmetries, train_loss, trainer_check below."""
 import ctypes as C
 
 import numpy as np
@@ -181,9 +183,10 @@ class FrameCorpus:
             _lib.check(lib.oakgpu_frames_encode_dev(self.ctx.handle, self.handle, enc.picks.data_ptr(), n, C.byref(ptrs)))
         return int((enc.status[:n] == 0).sum())
 
-    def sample(self, enc, seed, max_battle_length=0, min_iterations=1, n=None):
+    def sample(self, enc, seed, max_battle_length=0, min_iterations=1, n=None, count_ok=True):
         """n (default: enc.size) draws of pyoak.sample's rule into enc (and enc.picks); draw i depends on seed + i alone.  Returns the
-        number of OK rows (all of them on a corpus that passes the replay check)."""
+        number of OK rows (all of them on a corpus that passes the replay check); count_ok=False on device tensors returns None and
+        does not wait for the device (a training loop: the trainer leaves out the rows that are not OK itself)."""
         lib, n = self.ctx.lib, enc.size if n is None else int(n)
         assert n <= enc.size
         ptrs = enc.pointers()
@@ -194,7 +197,7 @@ class FrameCorpus:
             return int(ok.value)
         with _Bracket(self.ctx, enc):
             _lib.check(lib.oakgpu_frames_sample_dev(self.ctx.handle, self.handle, *args))
-        return int((enc.status[:n] == 0).sum())
+        return int((enc.status[:n] == 0).sum()) if count_ok else None
 
 
     # ---- every frame of the corpus --------------------------------------------------------------------------------------------
@@ -276,3 +279,159 @@ def encode_battles(ctx, battles, durations, results, enc):
     with _Bracket(ctx, enc):
         _lib.check(ctx.lib.oakgpu_encode_battles_dev(ctx.handle, battles.data_ptr(), durations.data_ptr(), results.data_ptr(), n, enc.pokemon.data_ptr(),
                                                      enc.active.data_ptr(), enc.hp.data_ptr(), enc.choice_indices.data_ptr(), enc.k.data_ptr()))
+
+
+# ---- the optimiser step ----------------------------------------------------------------------------------------------------------------
+WHICH = {"parameters": 0, "gradients": 1, "m": 2, "v": 3}
+GROUPS = {"trunk": 1, "value": 2, "policy": 4}
+LAYERS = ("pokemon_net.fc0", "pokemon_net.fc1", "active_net.fc0", "active_net.fc1", "main_net.fc0", "main_net.fc1", "value_fc2", "value_fc3",
+          "p1_policy_fc2", "p1_policy_fc3", "p2_policy_fc2", "p2_policy_fc3")
+# name -> (shape behind the row axis): Trainer.forward's per-row outputs
+TRAIN_OUTPUTS = {"value": (), "logits": (2, 9), "sq_err": (), "ce": (2,)}
+
+
+def train_loss(value_nash_weight=0.0, value_empirical_weight=0.0, value_score_weight=1.0, p_nash_weight=0.0, value_weight=1.0, policy_weight=1.0):
+    """battle.py's loss options (its defaults) as an oakgpu_train_loss; --no-value-loss / --no-policy-loss are a zero weight."""
+    return _lib.TrainLoss(float(value_nash_weight), float(value_empirical_weight), float(value_score_weight), float(p_nash_weight), float(value_weight),
+                          float(policy_weight))
+
+
+def apply_symmetries(ctx, enc, seed, n=None, flip_sides=True, permute_bench=True):
+    """battle.py's permute_sides / permute_pokemon on rows 0 .. n-1 of device tensors, in place; row i is drawn from seed + i alone.  hp moves
+    with its Pokemon (the reference leaves it in place): include/oakgpu.h, oakgpu_frames_symmetries_dev."""
+    assert enc.device is not None, "apply_symmetries works on device tensors"
+    n = enc.size if n is None else int(n)
+    assert n <= enc.size
+    ptrs = enc.pointers()
+    with _Bracket(ctx, enc):
+        _lib.check(ctx.lib.oakgpu_frames_symmetries_dev(ctx.handle, C.byref(ptrs), n, int(seed) & (2 ** 64 - 1), int(bool(flip_sides)), int(bool(permute_bench))))
+
+
+def trainer_check(net_bytes, max_rows, n=0, loss=None):
+    """The host-only check (no GPU): raises OakGpuError naming what create or a call of n rows would refuse."""
+    data = bytes(net_bytes)
+    buf = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, np.uint8)
+    _lib.check(_lib.load().oakgpu_trainer_check(buf.ctypes.data, len(data), int(max_rows), int(n), C.byref(loss) if loss is not None else None))
+
+
+class Trainer:
+    """Parameters, gradients and Adam state of one `.battle.net` on the device, and the optimiser step on training rows (k_gemm, k_loss, k_adam
+    in oak_amd/csrc/trainer.hip; the contract is in include/oakgpu.h).  net_bytes_or_path: the bytes of a `.battle.net` or its path.
+
+        trainer = Trainer(ctx, "initial.battle.net", max_rows=4096)
+        corpus.sample(enc, seed=step)
+        trainer.step(enc, enc.size, loss=train_loss(policy_weight=1.0), lr=1e-3)      # asynchronous for device rows
+        trainer.report()                                                                # waits: loss, mse, ce_p1, ce_p2, rows, steps
+
+    frames: an EncodedBattleFrames, torch tensors on the context's device (ordered against torch's current stream) or numpy (staged)."""
+
+    def __init__(self, ctx, net_bytes_or_path, max_rows):
+        if isinstance(net_bytes_or_path, (bytes, bytearray, memoryview)):
+            data = bytes(net_bytes_or_path)
+        else:
+            with open(net_bytes_or_path, "rb") as f:
+                data = f.read()
+        self.ctx, self.max_rows, self.handle = ctx, int(max_rows), None
+        buf = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, np.uint8)
+        h = C.c_void_p()
+        _lib.check(ctx.lib.oakgpu_trainer_create(ctx.handle, buf.ctypes.data, len(data), self.max_rows, C.byref(h)))
+        self.handle = h
+        dims, count = (C.c_uint32 * 24)(), C.c_size_t(0)
+        _lib.check(ctx.lib.oakgpu_trainer_shape(h, C.byref(dims), C.byref(count), None))
+        self.dims = [(int(dims[2 * i]), int(dims[2 * i + 1])) for i in range(12)]
+        self.count = int(count.value)
+        self.last_groups = 0
+
+    def close(self):
+        if self.handle and self.ctx.handle:
+            self.ctx.lib.oakgpu_trainer_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _call(self, name, frames, *args):
+        lib = self.ctx.lib
+        ptrs = frames.pointers()
+        if frames.device is None:
+            _lib.check(getattr(lib, name)(self.ctx.handle, self.handle, C.byref(ptrs), *args))
+        else:
+            with _Bracket(self.ctx, frames):
+                _lib.check(getattr(lib, name + "_dev")(self.ctx.handle, self.handle, C.byref(ptrs), *args))
+
+    def forward(self, frames, n, loss, want=("value", "logits", "sq_err", "ce"), out=None):
+        """Forward and loss terms of rows 0 .. n-1: {name: array [n, ...]} for the names in `want` (torch on the rows' device, or numpy), and the
+        report.  out: tensors to write into, by name, each of at least n rows."""
+        n = int(n)
+        res = {}
+        for name in want:
+            if out is not None and name in out:
+                res[name] = out[name]
+            elif frames.device is None:
+                res[name] = np.zeros((n,) + TRAIN_OUTPUTS[name], dtype=np.float32)
+            else:
+                import torch
+                res[name] = torch.zeros((n,) + TRAIN_OUTPUTS[name], dtype=torch.float32, device=frames.device)
+        outs = _lib.TrainOutputs(**{name: frames._ptr(t) for name, t in res.items()})
+        self._call("oakgpu_trainer_forward", frames, n, C.byref(loss), C.byref(outs))
+        return res
+
+    def gradients(self, frames, n, loss):
+        """Forward and backward of rows 0 .. n-1 into the gradient block."""
+        self._call("oakgpu_trainer_gradients", frames, int(n), C.byref(loss))
+        self.last_groups = 1 | (2 if loss.value_weight != 0 else 0) | (4 if loss.policy_weight != 0 else 0)
+
+    def adam(self, lr, clamp_parameters=False, groups=None):
+        """The Adam update alone, from the gradient block: of `groups` (names of GROUPS or their bits; default: the groups the last gradients
+        call gave a gradient)."""
+        if groups is None:
+            groups = self.last_groups
+        elif not isinstance(groups, int):
+            groups = sum(GROUPS[g] for g in groups)
+        _lib.check(self.ctx.lib.oakgpu_trainer_adam_dev(self.ctx.handle, self.handle, float(lr), int(bool(clamp_parameters)), int(groups)))
+
+    def step(self, frames, n, loss, lr, clamp_parameters=False):
+        """gradients, then adam: one optimiser step on rows 0 .. n-1."""
+        self._call("oakgpu_trainer_step", frames, int(n), C.byref(loss), float(lr), int(bool(clamp_parameters)))
+        self.last_groups = 1 | (2 if loss.value_weight != 0 else 0) | (4 if loss.policy_weight != 0 else 0)
+
+    def report(self):
+        """Waits for the device: the last call's loss, mse, ce_p1, ce_p2, rows, and the groups' step counts."""
+        rep, steps = _lib.TrainReport(), (C.c_uint64 * 3)()
+        _lib.check(self.ctx.lib.oakgpu_trainer_report(self.ctx.handle, self.handle, C.byref(rep), C.byref(steps)))
+        out = {name: getattr(rep, name) for name, _ in _lib.TrainReport._fields_}
+        out["rows"] = int(out["rows"])
+        out["steps"] = {"trunk": int(steps[0]), "value": int(steps[1]), "policy": int(steps[2])}
+        return out
+
+    def read(self, which="parameters", flat=False):
+        """The parameters, "gradients", "m" or "v": a list of 12 (bias [out], weight [out, in]) pairs in file order, or the flat block."""
+        block = np.zeros(self.count, dtype=np.float32)
+        _lib.check(self.ctx.lib.oakgpu_trainer_read(self.ctx.handle, self.handle, WHICH[which], block.ctypes.data, self.count))
+        return block if flat else self.split(block)
+
+    def split(self, block):
+        out, p = [], 0
+        for i, o in self.dims:
+            out.append((block[p:p + o], block[p + o:p + o + o * i].reshape(o, i)))
+            p += o * (i + 1)
+        return out
+
+    def set_gradients(self, block):
+        block = np.ascontiguousarray(block, dtype=np.float32).reshape(-1)
+        _lib.check(self.ctx.lib.oakgpu_trainer_set_gradients(self.ctx.handle, self.handle, block.ctypes.data, block.size))
+
+    def net_bytes(self):
+        size = C.c_size_t(0)
+        _lib.check(self.ctx.lib.oakgpu_trainer_net_bytes(self.ctx.handle, self.handle, None, 0, C.byref(size)))
+        buf = np.zeros(size.value, dtype=np.uint8)
+        _lib.check(self.ctx.lib.oakgpu_trainer_net_bytes(self.ctx.handle, self.handle, buf.ctypes.data, buf.size, C.byref(size)))
+        return buf.tobytes()
+
+    def save(self, path):
+        data = self.net_bytes()
+        with open(path, "wb") as f:
+            f.write(data)
