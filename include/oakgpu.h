@@ -1262,6 +1262,89 @@ int oakgpu_trainer_gradients(oakgpu_ctx *ctx, oakgpu_trainer *trainer, const oak
 int oakgpu_trainer_step(oakgpu_ctx *ctx, oakgpu_trainer *trainer, const oakgpu_encoded_frames *rows, uint32_t n, const oakgpu_train_loss *loss, float lr,
                         int clamp_weights);
 
+/* ---- Team building: the other half of the reference's `generate` -- TeamBuilding::Provider::get_trajectory (cpp/include/util/team-building.h:
+ * 190-241), which completes teams with the BUILD NETWORK one species or move at a time (rollout_build_network, :36-84), and the
+ * CompressedTrajectory NoTeam records of `N.build.data` (encode/build/compressed-trajectory.h:23-105).
+ *   A TEAM is 30 bytes, 6 x {species, 4 moves}, with a SIZE, the slots in play (the reference's vector length); slots at or beyond it are
+ * not part of the team and come back as zeros.  A CELL is one (species, move) pair of Encode::Build::Tensorizer<Format::OU>: cells are
+ * numbered in legal_species order, within a species the (species, None) cell first, then its move pool in pool order; there are
+ * OAKGPU_BUILD_N_DIM of them.  The input x of the net has one float per cell.
+ *   A `.build.net` is policy_net then value_net, each three Affine layers `u32 in_dim, u32 out_dim, out_dim f32 biases, out_dim x in_dim f32
+ * weights row-major` (nn/affine.h:35-70); the policy net is n_dim -> h -> h -> n_dim with relu, relu, none (h <= 256 here), the value net
+ * n_dim -> v -> v -> 1, read and unused as in the reference.
+ *   THE ROLLOUT of one team, statement for statement the reference's: x = Tensorizer::write(team); the stream is splitmix64 (the self-play
+ * pick's) seeded with the row's seed.  Loop: the LEGAL LIST (Actions::get_singleton_additions) -- if a slot below size is empty, every
+ * legal species not on the team, in legal_species order, aimed at the FIRST empty slot; then, for each slot in order that holds a species
+ * and has an empty move slot, its pool moves in pool order minus the moves it holds, aimed at its first empty move slot -- and an empty
+ * list ends the loop.  One STEP: logits = policy_net(x); the softmax over the legal cells with expf in float, no maximum subtracted, the
+ * sum accumulated in double in list order, each quotient rounded to float; index = sample_pdf(policy) with one uniform01, the list walked
+ * sequentially with p -= (double)policy[i], p <= 0 stops, falling off the end gives 0; the action is applied; then x[index] = 1 -- the
+ * POSITION in the list, not the action's cell: what the reference does (team-building.h:67) and what nets trained by build.py have seen
+ * (input_update = 0).  input_update = 1 sets the action's own cell instead.  After the loop the slots 1 .. size-1 that hold a species are
+ * the LEAD SWAPS (cell: (species, None)); if there are any, one more step over them swaps slot 0 with the chosen one.  At most
+ * OAKGPU_BUILD_MAX_STEPS steps.
+ *   Numerics: fp32 with fp32 accumulation in a fixed order (buildnet.hip's header); only W1's columns at the ones of x and W3's rows at the
+ * legal cells are touched.  No float atomics: two calls give the same bits, and a row depends on its own team and seed alone.
+ *   THE PROVIDER, per row from the row's stream in the reference's draw order: team_index = uniform_64 % T over a pool of T teams (their
+ * Pokemon packed in the leading slots); truncation to max_pokemon, `changed` when that removed a Pokemon; one uniform, and only if it is
+ * < team_modify_prob and changed is still false, Omitter::delete_info (per slot in order: a present species with u < pokemon_delete_prob
+ * has its whole set cleared, no move draws for it; otherwise each present move with u < move_delete_prob is cleared).  Changed rows are
+ * rolled out, the stream continuing; they report team_index -1.  The others keep their team, n_updates 0, and report their team_index.
+ * The reference's team_shuffle_prob, which `generate` never sets, is left out.
+ *   RECORDS: 128 bytes, {u8 format 0, u8 score = 2 * score or 255 for none, u16 value = value * 65535}, then 31 x {u16 action, u16
+ * probability}: the INITIAL team's cells with probability 0 (per slot the species cell, then its held moves in slot order), then the
+ * updates with probability = (u16)(65535.0f * p), 1 when a p != 0 rounds to 0, then zeros.  Only rows with n_updates > 0 give a record,
+ * packed in row order.  A score that is negative or NaN means none.
+ *   The _dev calls take device arrays, launch ONE kernel and are asynchronous on the context's stream; they trust the teams: a row whose
+ * team would not pass oakgpu_build_teams_check is left with n_updates 255 and a zero team.  The host calls check first, stage, and return
+ * complete; per-step entries at or past n_updates and trace entries past n_legal keep what the caller's arrays held. */
+enum { OAKGPU_BUILD_N_DIM = 3749, OAKGPU_BUILD_MAX_ACTIONS = 339, OAKGPU_BUILD_MAX_STEPS = 31, OAKGPU_BUILD_RECORD_BYTES = 128 };
+typedef struct oakgpu_build_net oakgpu_build_net;
+typedef struct {
+  uint8_t *teams_out;          /* [n, 30] */
+  uint8_t *n_updates;          /* [n] */
+  uint16_t *action;            /* [n, 31]: the cell of each step's action */
+  uint16_t *index;             /* [n, 31]: its position in the legal list */
+  uint16_t *n_legal;           /* [n, 31] */
+  float *prob;                 /* [n, 31]: policy[index] */
+  int16_t *trace_legal;        /* nullable, all three or none: [n, 31, 339] the legal cells, */
+  float *trace_logits;         /*   their logits */
+  float *trace_policy;         /*   and the policy */
+  uint8_t *teams_init;         /* provide only: [n, 30] the team before the rollout (the record's initial team) */
+  uint8_t *sizes_out;          /* provide only: [n] */
+  int32_t *team_index;         /* provide only: [n] */
+} oakgpu_build_outputs;
+typedef struct { int32_t max_pokemon, input_update; double pokemon_delete_prob, move_delete_prob, team_modify_prob; } oakgpu_build_provider;
+/* The generated tables (each nullable): legal_species [149]; cells [3749, 2] = species_move_list; table [152, 166] = species_move_table, -1
+ * where there is no cell. */
+int oakgpu_build_tables(uint8_t *legal_species, uint8_t *cells, int32_t *table);
+/* Host only: refuses by name a truncated file, trailing bytes, dimensions that do not chain or do not start and end at n_dim, a NaN parameter. */
+int oakgpu_build_net_check(const uint8_t *bytes, size_t len);
+/* The net belongs to ctx and must be destroyed before it. */
+int oakgpu_build_net_load(oakgpu_ctx *ctx, const uint8_t *bytes, size_t len, oakgpu_build_net **out);
+void oakgpu_build_net_destroy(oakgpu_build_net *net);
+int oakgpu_build_net_shape(const oakgpu_build_net *net, uint32_t *policy_hidden, uint32_t *value_hidden);
+/* Host only, by name: n == 0, input_update outside {0, 1}, size > 6, a species outside legal_species, a duplicate species, a move outside its
+ * species' pool.  sizes nullable: 6. */
+int oakgpu_build_teams_check(const uint8_t *teams, const uint8_t *sizes, uint32_t n, int input_update);
+/* Host only, by name: n == 0, an empty pool, max_pokemon outside 1..6, a probability outside [0, 1], and the pool's teams as above. */
+int oakgpu_build_provide_check(const uint8_t *pool, uint32_t pool_n, uint32_t n, int max_pokemon, double pokemon_delete_prob, double move_delete_prob,
+                               double team_modify_prob);
+int oakgpu_build_rollout_dev(oakgpu_ctx *ctx, const oakgpu_build_net *net, const uint8_t *teams, const uint8_t *sizes /* nullable */, const uint64_t *seeds,
+                             uint32_t n, int input_update, const oakgpu_build_outputs *out);
+int oakgpu_build_provide_dev(oakgpu_ctx *ctx, const oakgpu_build_net *net, const uint8_t *pool, uint32_t pool_n, const uint64_t *seeds, uint32_t n,
+                             const oakgpu_build_provider *prm, const oakgpu_build_outputs *out);
+/* records: room for n x 128 bytes, 4-byte aligned; count: one device word, the number of records written */
+int oakgpu_build_records_dev(oakgpu_ctx *ctx, const uint8_t *teams_init, const uint8_t *sizes /* nullable */, const uint8_t *n_updates, const uint16_t *action,
+                             const float *prob, const float *value, const float *score, uint32_t n, uint8_t *records, uint32_t *count);
+/* host arrays in and out */
+int oakgpu_build_rollout(oakgpu_ctx *ctx, const oakgpu_build_net *net, const uint8_t *teams, const uint8_t *sizes /* nullable */, const uint64_t *seeds,
+                         uint32_t n, int input_update, const oakgpu_build_outputs *out);
+int oakgpu_build_provide(oakgpu_ctx *ctx, const oakgpu_build_net *net, const uint8_t *pool, uint32_t pool_n, const uint64_t *seeds, uint32_t n,
+                         const oakgpu_build_provider *prm, const oakgpu_build_outputs *out);
+int oakgpu_build_records(oakgpu_ctx *ctx, const uint8_t *teams_init, const uint8_t *sizes /* nullable */, const uint8_t *n_updates, const uint16_t *action,
+                         const float *prob, const float *value, const float *score, uint32_t n, uint8_t *records, uint32_t *count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -734,6 +734,97 @@ private:
   size_t count_{};
 };
 
+// The team-building network on the device (oakgpu_build_*): a `.build.net`'s policy net, the rollout that completes teams with it and the
+// provider of `generate` (TeamBuilding::Provider::get_trajectory).  Host vectors in and out.  Must not outlive its Context.
+class BuildNet {
+public:
+  // What one call leaves: per row the completed team, the number of steps, and per step the action's cell, its position in the legal list,
+  // the list's length and the probability; provide also the team the rollout started from (what a record's initial cells are), its size
+  // and the pool index of an unchanged team (-1 for a built one).
+  struct Trajectories {
+    uint32_t n{};
+    std::vector<uint8_t> teams_out, n_updates, teams_init, sizes;
+    std::vector<uint16_t> action, index, n_legal;
+    std::vector<float> prob;
+    std::vector<int32_t> team_index;
+  };
+  BuildNet(Context &ctx, const std::vector<uint8_t> &net_bytes) : ctx_{ctx.get()} {
+    check(oakgpu_build_net_load(ctx_, net_bytes.data(), net_bytes.size(), &net_));
+  }
+  ~BuildNet() { oakgpu_build_net_destroy(net_); }
+  BuildNet(const BuildNet &) = delete;
+  BuildNet &operator=(const BuildNet &) = delete;
+  oakgpu_build_net *get() const noexcept { return net_; }
+  // host only: throws naming what load would refuse
+  static void check_net(const std::vector<uint8_t> &net_bytes) { check(oakgpu_build_net_check(net_bytes.data(), net_bytes.size())); }
+  // teams: n x 30 bytes; sizes: n bytes or empty (6); seeds: n
+  Trajectories rollout(const std::vector<uint8_t> &teams, const std::vector<uint64_t> &seeds, const std::vector<uint8_t> &sizes = {}, int input_update = 0) {
+    const uint32_t n = static_cast<uint32_t>(seeds.size());
+    if (teams.size() != static_cast<size_t>(n) * 30 || (!sizes.empty() && sizes.size() != n)) throw std::runtime_error{"oakgpu: teams, sizes and seeds disagree"};
+    Trajectories t = make(n, false);
+    const oakgpu_build_outputs out = pointers(t, false);
+    check(oakgpu_build_rollout(ctx_, net_, teams.data(), sizes.empty() ? nullptr : sizes.data(), seeds.data(), n, input_update, &out));
+    t.teams_init = teams;
+    t.sizes = sizes.empty() ? std::vector<uint8_t>(n, 6) : sizes;
+    return t;
+  }
+  // pool: T x 30 bytes
+  Trajectories provide(const std::vector<uint8_t> &pool, const std::vector<uint64_t> &seeds, const oakgpu_build_provider &prm) {
+    const uint32_t n = static_cast<uint32_t>(seeds.size());
+    if (pool.size() % 30) throw std::runtime_error{"oakgpu: a pool is whole teams of 30 bytes"};
+    Trajectories t = make(n, true);
+    const oakgpu_build_outputs out = pointers(t, true);
+    check(oakgpu_build_provide(ctx_, net_, pool.data(), static_cast<uint32_t>(pool.size() / 30), seeds.data(), n, &prm, &out));
+    return t;
+  }
+  // the `.build.data` records of the built rows, in row order; a negative score means none
+  std::vector<uint8_t> records(const Trajectories &t, const std::vector<float> &value, const std::vector<float> &score) {
+    if (value.size() != t.n || score.size() != t.n) throw std::runtime_error{"oakgpu: one value and one score per row"};
+    std::vector<uint8_t> out(static_cast<size_t>(t.n) * OAKGPU_BUILD_RECORD_BYTES);
+    uint32_t count = 0;
+    check(oakgpu_build_records(ctx_, t.teams_init.data(), t.sizes.data(), t.n_updates.data(), t.action.data(), t.prob.data(), value.data(), score.data(), t.n,
+                               out.data(), &count));
+    out.resize(static_cast<size_t>(count) * OAKGPU_BUILD_RECORD_BYTES);
+    return out;
+  }
+
+private:
+  static Trajectories make(uint32_t n, bool provide) {
+    Trajectories t;
+    const size_t steps = static_cast<size_t>(n) * OAKGPU_BUILD_MAX_STEPS;
+    t.n = n;
+    t.teams_out.assign(static_cast<size_t>(n) * 30, 0);
+    t.n_updates.assign(n, 0);
+    t.action.assign(steps, 0);
+    t.index.assign(steps, 0);
+    t.n_legal.assign(steps, 0);
+    t.prob.assign(steps, 0.0f);
+    if (provide) {
+      t.teams_init.assign(static_cast<size_t>(n) * 30, 0);
+      t.sizes.assign(n, 0);
+      t.team_index.assign(n, 0);
+    }
+    return t;
+  }
+  static oakgpu_build_outputs pointers(Trajectories &t, bool provide) {
+    oakgpu_build_outputs o{};
+    o.teams_out = t.teams_out.data();
+    o.n_updates = t.n_updates.data();
+    o.action = t.action.data();
+    o.index = t.index.data();
+    o.n_legal = t.n_legal.data();
+    o.prob = t.prob.data();
+    if (provide) {
+      o.teams_init = t.teams_init.data();
+      o.sizes_out = t.sizes.data();
+      o.team_index = t.team_index.data();
+    }
+    return o;
+  }
+  oakgpu_ctx *ctx_{};
+  oakgpu_build_net *net_{};
+};
+
 // The path's one exchange step for root-parallel search sharded over the GPUs of a node (one process per GPU): reduce the
 // rank's leaf values to one mean per root on the device, then ONE ncclAllGather (RCCL over xGMI) of those means.
 class Exchange {

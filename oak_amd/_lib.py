@@ -46,6 +46,9 @@ SYMBOLS = [
     "oakgpu_trainer_forward_dev", "oakgpu_trainer_gradients_dev", "oakgpu_trainer_adam_dev", "oakgpu_trainer_step_dev", "oakgpu_trainer_report",
     "oakgpu_trainer_read", "oakgpu_trainer_set_gradients", "oakgpu_trainer_net_bytes", "oakgpu_trainer_forward", "oakgpu_trainer_gradients",
     "oakgpu_trainer_step",
+    "oakgpu_build_tables", "oakgpu_build_net_check", "oakgpu_build_net_load", "oakgpu_build_net_destroy", "oakgpu_build_net_shape", "oakgpu_build_teams_check",
+    "oakgpu_build_provide_check", "oakgpu_build_rollout_dev", "oakgpu_build_provide_dev", "oakgpu_build_records_dev", "oakgpu_build_rollout",
+    "oakgpu_build_provide", "oakgpu_build_records",
 ]
 
 
@@ -131,6 +134,16 @@ class TrainReport(C.Structure):       # oakgpu_train_report
 
 class TrainOutputs(C.Structure):      # oakgpu_train_outputs: one nullable pointer per tensor, device or host as the call says
     _fields_ = [(name, C.c_void_p) for name in ("value", "logits", "sq_err", "ce")]
+
+
+class BuildOutputs(C.Structure):      # oakgpu_build_outputs: one pointer per array, device or host as the call says
+    _fields_ = [(name, C.c_void_p) for name in ("teams_out", "n_updates", "action", "index", "n_legal", "prob", "trace_legal", "trace_logits",
+                                                "trace_policy", "teams_init", "sizes_out", "team_index")]
+
+
+class BuildProvider(C.Structure):     # oakgpu_build_provider
+    _fields_ = [("max_pokemon", C.c_int32), ("input_update", C.c_int32), ("pokemon_delete_prob", C.c_double), ("move_delete_prob", C.c_double),
+                ("team_modify_prob", C.c_double)]
 
 
 class Seat(C.Structure):              # oakgpu_seat
@@ -410,6 +423,21 @@ def load():
     lib.oakgpu_trainer_read.argtypes = [vp, vp, i32, vp, sz]
     lib.oakgpu_trainer_set_gradients.argtypes = [vp, vp, vp, sz]
     lib.oakgpu_trainer_net_bytes.argtypes = [vp, vp, vp, sz, C.POINTER(sz)]
+    f64, outs_b = C.c_double, C.POINTER(BuildOutputs)
+    lib.oakgpu_build_tables.argtypes = [vp, vp, vp]
+    lib.oakgpu_build_net_check.argtypes = [vp, sz]
+    lib.oakgpu_build_net_load.argtypes = [vp, vp, sz, C.POINTER(vp)]
+    lib.oakgpu_build_net_destroy.argtypes = [vp]
+    lib.oakgpu_build_net_destroy.restype = None
+    lib.oakgpu_build_net_shape.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+    lib.oakgpu_build_teams_check.argtypes = [vp, vp, u32, i32]
+    lib.oakgpu_build_provide_check.argtypes = [vp, u32, u32, i32, f64, f64, f64]
+    lib.oakgpu_build_rollout_dev.argtypes = [vp, vp, vp, vp, vp, u32, i32, outs_b]
+    lib.oakgpu_build_rollout.argtypes = lib.oakgpu_build_rollout_dev.argtypes
+    lib.oakgpu_build_provide_dev.argtypes = [vp, vp, vp, u32, vp, u32, C.POINTER(BuildProvider), outs_b]
+    lib.oakgpu_build_provide.argtypes = lib.oakgpu_build_provide_dev.argtypes
+    lib.oakgpu_build_records_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]
+    lib.oakgpu_build_records.argtypes = lib.oakgpu_build_records_dev.argtypes
     _lib = lib
     return lib
 

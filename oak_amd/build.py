@@ -1,0 +1,249 @@
+"""Team building on the GPU: the build network's rollout, the provider of `generate`, and `.build.data` records.
+
+Mirrors TeamBuilding::Provider::get_trajectory / rollout_build_network (cpp/include/util/team-building.h:36-84, 190-241) and
+Encode::Build::CompressedTrajectory (encode/build/compressed-trajectory.h); the rollout, the provider's prelude and the record packer are
+HIP (oak_amd/csrc/buildnet.hip, contract in include/oakgpu.h) -- this module only marshals arrays.  numpy arrays in give numpy arrays
+out; torch GPU tensors in give tensors on that device out and copy nothing to the host (seeds as int64 bit patterns, the u16 outputs
+as int16: every value is below 3,749)."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+N_DIM, MAX_ACTIONS, MAX_STEPS, RECORD_BYTES = 3749, 339, 31, 128
+_STEP_ARRAYS = (("action", np.uint16), ("index", np.uint16), ("n_legal", np.uint16), ("prob", np.float32))
+_TRACE_ARRAYS = (("trace_legal", np.int16), ("trace_logits", np.float32), ("trace_policy", np.float32))
+
+
+def tables():
+    """(legal_species uint8[149], species_move_list uint8[3749, 2], species_move_table int32[152, 166], -1 where there is no cell)."""
+    legal, cells, table = np.zeros(149, np.uint8), np.zeros((N_DIM, 2), np.uint8), np.zeros((152, 166), np.int32)
+    _lib.check(_lib.load().oakgpu_build_tables(legal.ctypes.data_as(C.c_void_p), cells.ctypes.data_as(C.c_void_p), table.ctypes.data_as(C.c_void_p)))
+    return legal, cells, table
+
+
+def check_net(data):
+    """The refusals of a `.build.net`, by name, without a GPU."""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    _lib.check(_lib.load().oakgpu_build_net_check(buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size))
+
+
+def check_teams(teams, sizes=None, input_update=0):
+    """The refusals of rollout's teams, by name, without a GPU."""
+    t = np.ascontiguousarray(teams, np.uint8).reshape(-1, 30)
+    s = None if sizes is None else np.ascontiguousarray(sizes, np.uint8).reshape(-1)
+    _lib.check(_lib.load().oakgpu_build_teams_check(t.ctypes.data_as(C.c_void_p) if t.size else None, None if s is None else s.ctypes.data_as(C.c_void_p),
+                                                    t.shape[0], int(input_update)))
+
+
+def check_provide(pool, n, max_pokemon=6, pokemon_delete_prob=0., move_delete_prob=0., team_modify_prob=0.):
+    """The refusals of provide, by name, without a GPU."""
+    p = np.ascontiguousarray(pool, np.uint8).reshape(-1, 30)
+    _lib.check(_lib.load().oakgpu_build_provide_check(p.ctypes.data_as(C.c_void_p) if p.size else None, p.shape[0], int(n), int(max_pokemon),
+                                                      float(pokemon_delete_prob), float(move_delete_prob), float(team_modify_prob)))
+
+
+class BuildNetwork:
+    """A `.build.net` resident on the context's device; close() (or the context manager) frees it before the context goes."""
+
+    def __init__(self, ctx, bytes_or_path):
+        data = bytes_or_path if isinstance(bytes_or_path, (bytes, bytearray, memoryview)) else open(bytes_or_path, "rb").read()
+        buf = np.frombuffer(bytes(data), np.uint8)
+        self.ctx, self.handle = ctx, C.c_void_p()
+        _lib.check(ctx.lib.oakgpu_build_net_load(ctx.handle, buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, C.byref(self.handle)))
+        p, v = C.c_uint32(0), C.c_uint32(0)
+        _lib.check(ctx.lib.oakgpu_build_net_shape(self.handle, C.byref(p), C.byref(v)))
+        self.policy_hidden, self.value_hidden = int(p.value), int(v.value)
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.oakgpu_build_net_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _alloc(n, trace, provide, device):
+    """The output arrays of one call, cleared (the legal trace to -1): numpy, or torch tensors on `device`."""
+    shapes = [("teams_out", (n, 30), np.uint8), ("n_updates", (n,), np.uint8)] + [(k, (n, MAX_STEPS), t) for k, t in _STEP_ARRAYS]
+    if trace:
+        shapes += [(k, (n, MAX_STEPS, MAX_ACTIONS), t) for k, t in _TRACE_ARRAYS]
+    if provide:
+        shapes += [("teams_init", (n, 30), np.uint8), ("sizes", (n,), np.uint8), ("team_index", (n,), np.int32)]
+    out = {}
+    for name, shape, dtype in shapes:
+        fill = -1 if name == "trace_legal" else 0
+        if device is None:
+            out[name] = np.full(shape, fill, dtype)
+        else:
+            import torch
+            tdt = {np.uint8: torch.uint8, np.uint16: torch.int16, np.int16: torch.int16, np.float32: torch.float32, np.int32: torch.int32}[dtype]
+            out[name] = torch.full(shape, fill, dtype=tdt, device=device)
+    return out
+
+
+def _pointers(out, ptr):
+    o = _lib.BuildOutputs()
+    fields = set(f[0] for f in _lib.BuildOutputs._fields_)
+    for name in out:
+        field = "sizes_out" if name == "sizes" else name
+        if field in fields and name != "teams_in":
+            setattr(o, field, ptr(out[name]))
+    return o
+
+
+def _run(ctx, on_device, device, inputs, call_dev, call_host, out):
+    if on_device:
+        import torch
+        mine, theirs = torch.cuda.ExternalStream(ctx.stream_ptr(), device=device), torch.cuda.current_stream(device)
+        mine.wait_stream(theirs)
+        _lib.check(call_dev(*[None if x is None else x.data_ptr() for x in inputs], _pointers(out, lambda a: a.data_ptr())))
+        theirs.wait_stream(mine)
+    else:
+        _lib.check(call_host(*[None if x is None else x.ctypes.data_as(C.c_void_p) for x in inputs], _pointers(out, lambda a: a.ctypes.data_as(C.c_void_p))))
+    return out
+
+
+def rollout(ctx, net, teams, seeds, sizes=None, input_update=0, trace=False, out=None):
+    """Complete every team with the build network: one launch (oakgpu_build_rollout).  teams uint8[n, 30] (6 x {species, 4 moves}), seeds
+    uint64[n], sizes uint8[n] or None (6).  Returns a dict: teams_out [n, 30], n_updates [n], and per step [n, 31] action (the cell), index
+    (the position in the legal list), n_legal, prob; with trace=True also trace_legal (-1 padded), trace_logits, trace_policy [n, 31, 339].
+    Entries at or past a row's n_updates / a step's n_legal are left as they were (zeros here).  out: the same dict preallocated by the
+    caller (a test's prefilled arrays)."""
+    on_device = hasattr(teams, "data_ptr")
+    if on_device:
+        n, device = int(teams.shape[0]), teams.device
+        t, sd, sz = teams.contiguous().view(n, 30), seeds.contiguous(), None if sizes is None else sizes.contiguous()
+    else:
+        t = np.ascontiguousarray(teams, np.uint8).reshape(-1, 30)
+        n, device = t.shape[0], None
+        sd = np.ascontiguousarray(np.asarray(seeds).astype(np.uint64)).reshape(n)
+        sz = None if sizes is None else np.ascontiguousarray(sizes, np.uint8).reshape(n)
+    out = _alloc(n, trace, False, device) if out is None else out
+    lib, iu = ctx.lib, int(input_update)
+    out.pop("sizes", None)
+    _run(ctx, on_device, device, (t, sz, sd),
+         lambda a, b, c, o: lib.oakgpu_build_rollout_dev(ctx.handle, net.handle, a, b, c, n, iu, C.byref(o)),
+         lambda a, b, c, o: lib.oakgpu_build_rollout(ctx.handle, net.handle, a, b, c, n, iu, C.byref(o)), out)
+    out["teams_in"] = t      # what records() starts from
+    if sz is not None:
+        out["sizes"] = sz
+    return out
+
+
+def provide(ctx, net, pool, seeds, max_pokemon=6, pokemon_delete_prob=0., move_delete_prob=0., team_modify_prob=0., input_update=0, trace=False):
+    """Provider::get_trajectory for len(seeds) rows over a pool of teams (uint8[T, 30]): rollout's dict plus teams_init [n, 30] and sizes [n]
+    (the team before the rollout, what a record starts from) and team_index int32[n] (-1 for built rows)."""
+    on_device = hasattr(pool, "data_ptr")
+    if on_device:
+        device = pool.device
+        p, sd = pool.contiguous().view(-1, 30), seeds.contiguous()
+        n = int(sd.shape[0])
+    else:
+        p, device = np.ascontiguousarray(pool, np.uint8).reshape(-1, 30), None
+        sd = np.ascontiguousarray(np.asarray(seeds).astype(np.uint64)).reshape(-1)
+        n = sd.shape[0]
+    prm = _lib.BuildProvider(int(max_pokemon), int(input_update), float(pokemon_delete_prob), float(move_delete_prob), float(team_modify_prob))
+    out = _alloc(n, trace, True, device)
+    lib, pool_n = ctx.lib, int(p.shape[0])
+    return _run(ctx, on_device, device, (p, sd),
+                lambda a, c, o: lib.oakgpu_build_provide_dev(ctx.handle, net.handle, a, pool_n, c, n, C.byref(prm), C.byref(o)),
+                lambda a, c, o: lib.oakgpu_build_provide(ctx.handle, net.handle, a, pool_n, c, n, C.byref(prm), C.byref(o)), out)
+
+
+def _next_seed(seed):
+    """One splitmix64 step: a redrawn row's fresh seed."""
+    m = (1 << 64) - 1
+    z = (int(seed) + 0x9E3779B97F4A7C15) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    return z ^ (z >> 31)
+
+
+def provide_pairs(ctx, net, pool, seeds, max_tries=16, **kw):
+    """Both seats' teams of len(seeds) games: seeds uint64[n, 2], one provide call per seat on the device; a pair that fails the endless
+    battle check (on the host, as generate.cc:224-227 draws again) gets fresh seeds -- one splitmix64 step of the old ones -- and is
+    provided again, before any game starts.  Returns (teams uint8[n, 60], (p1, p2)): provide's dict per seat, numpy; each also holds the
+    "seeds" the kept rows were made from."""
+    lib = ctx.lib
+    seeds = np.array(seeds, np.uint64).reshape(-1, 2)
+    n = seeds.shape[0]
+    seats = [None, None]
+    rows = np.arange(n)
+    for _ in range(max_tries):
+        for s in (0, 1):
+            got = provide(ctx, net, pool, seeds[rows, s], **kw)
+            if seats[s] is None:
+                seats[s] = got
+            else:
+                for name in got:
+                    seats[s][name][rows] = got[name]
+        teams = np.ascontiguousarray(np.concatenate([seats[0]["teams_out"], seats[1]["teams_out"]], axis=1))
+        rows = np.array([g for g in rows if lib.oakgpu_endless_battle_check(teams[g].ctypes.data_as(C.c_void_p))], np.int64)
+        if not rows.size:
+            seats[0]["seeds"], seats[1]["seeds"] = seeds[:, 0].copy(), seeds[:, 1].copy()
+            return teams, tuple(seats)
+        for g in rows:
+            seeds[g] = [_next_seed(seeds[g, 0]), _next_seed(seeds[g, 1])]
+    raise _lib.OakGpuError("provide_pairs: %d pairs still fail the endless battle check after %d draws" % (rows.size, max_tries))
+
+
+def records(ctx, trajectories, value, score):
+    """The `.build.data` records of the built rows (n_updates > 0) of a rollout / provide dict, in row order.  value, score: one float per row or
+    a scalar; a score that is None, NaN or negative means none.  numpy in: bytes; tensors in: a uint8 tensor."""
+    tr = trajectories
+    on_device = hasattr(tr["n_updates"], "data_ptr")
+    teams = tr["teams_init"] if "teams_init" in tr else tr["teams_in"]
+    sizes = tr.get("sizes")
+    n = int(tr["n_updates"].shape[0])
+    lib = ctx.lib
+    if on_device:
+        import torch
+        device = tr["n_updates"].device
+
+        def per_row(x):
+            if x is None:
+                x = -1.0
+            return x.to(torch.float32).contiguous() if hasattr(x, "data_ptr") else torch.full((n,), float(x), dtype=torch.float32, device=device)
+        v, s = per_row(value), per_row(score)
+        out, count = torch.zeros((n, RECORD_BYTES), dtype=torch.uint8, device=device), torch.zeros(1, dtype=torch.int32, device=device)
+        mine, theirs = torch.cuda.ExternalStream(ctx.stream_ptr(), device=device), torch.cuda.current_stream(device)
+        mine.wait_stream(theirs)
+        _lib.check(lib.oakgpu_build_records_dev(ctx.handle, teams.data_ptr(), None if sizes is None else sizes.data_ptr(), tr["n_updates"].data_ptr(),
+                                                tr["action"].data_ptr(), tr["prob"].data_ptr(), v.data_ptr(), s.data_ptr(), n, out.data_ptr(), count.data_ptr()))
+        theirs.wait_stream(mine)
+        return out[:int(count.item())].reshape(-1)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    per_row = lambda x: np.ascontiguousarray(np.broadcast_to(np.asarray(-1.0 if x is None else x, np.float32), (n,)))
+    v, s = per_row(value), np.nan_to_num(per_row(score), nan=-1.0)
+    out, count = np.zeros((n, RECORD_BYTES), np.uint8), C.c_uint32(0)
+    t = np.ascontiguousarray(teams, np.uint8).reshape(n, 30)
+    _lib.check(lib.oakgpu_build_records(ctx.handle, vp(t), None if sizes is None else vp(np.ascontiguousarray(sizes, np.uint8)), vp(tr["n_updates"]),
+                                        vp(np.ascontiguousarray(tr["action"])), vp(np.ascontiguousarray(tr["prob"])), vp(v), vp(s), n, vp(out), C.byref(count)))
+    return out[:count.value].tobytes()
+
+
+def decode_records(data):
+    """`.build.data` bytes (NoTeam records) -> a list of {"score" (None: no score), "value", "action" uint16[31], "probability" uint16[31]}."""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    if buf.size % RECORD_BYTES:
+        raise ValueError("decode_records: %d bytes is not a multiple of %d" % (buf.size, RECORD_BYTES))
+    out = []
+    for r in buf.reshape(-1, RECORD_BYTES):
+        if r[0] != 0:
+            raise ValueError("decode_records: a record of format %d (only NoTeam records are read)" % r[0])
+        ups = r[4:].view("<u2").reshape(MAX_STEPS, 2)
+        out.append({"score": None if r[1] == 255 else r[1] / 2.0, "value": int(r[2:4].view("<u2")[0]) / 65535.0, "action": ups[:, 0].copy(),
+                    "probability": ups[:, 1].copy()})
+    return out

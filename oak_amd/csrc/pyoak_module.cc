@@ -886,4 +886,66 @@ PYBIND11_MODULE(pyoak, m) {
   m.attr("value_hidden_dim") = 32;
   m.attr("policy_hidden_dim") = 64;
   m.attr("policy_out_dim") = 315;
+
+  // Build net hyper-parameters and index tables (pyoak.cc:598-620; nn/default-hyperparameters.h:22-23, encode/build/tensorizer.h)
+  m.attr("build_policy_hidden_dim") = 128;
+  m.attr("build_value_hidden_dim") = 128;
+  m.attr("build_max_actions") = (int)OAKGPU_BUILD_MAX_ACTIONS;
+  {
+    std::vector<uint8_t> cells((size_t)OAKGPU_BUILD_N_DIM * 2);
+    std::vector<int32_t> table(152 * 166);
+    check(oakgpu_build_tables(nullptr, cells.data(), table.data()));
+    std::vector<std::pair<int, int>> species_move_list;
+    for (int c = 0; c < (int)OAKGPU_BUILD_N_DIM; ++c) species_move_list.emplace_back(cells[2 * c], cells[2 * c + 1]);
+    m.attr("species_move_list") = std::move(species_move_list);
+    std::vector<std::vector<int>> species_move_table;
+    for (int s = 0; s < 152; ++s) species_move_table.emplace_back(table.begin() + s * 166, table.begin() + (s + 1) * 166);
+    m.attr("species_move_table") = std::move(species_move_table);
+  }
+
+  m.def(
+      "build_teams",
+      [](py::bytes net_bytes, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> pool, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> seeds,
+         int max_pokemon, double pokemon_delete_prob, double move_delete_prob, double team_modify_prob, int input_update) {
+        // not in pyoak: TeamBuilding::Provider::get_trajectory for len(seeds) rows at once (include/oakgpu.h: oakgpu_build_provide) over a
+        // pool of teams (n x 30 bytes, 6 x {species, 4 moves}) with the `.build.net` in net_bytes.  Returns a dict: teams [n, 30], team_index
+        // (-1: built), n_updates, teams_init, sizes, and per step [n, 31] action, index, n_legal, prob.
+        const std::string net = net_bytes;
+        const size_t n = (size_t)seeds.size();
+        if (pool.size() % 30) throw std::runtime_error("build_teams: a pool is whole teams of 30 bytes");
+        const size_t steps = n * OAKGPU_BUILD_MAX_STEPS;
+        py::array_t<uint8_t> teams_out(std::vector<size_t>{n, 30}), teams_init(std::vector<size_t>{n, 30}), n_updates(n), sizes(n);
+        py::array_t<int32_t> team_index(n);
+        py::array_t<uint16_t> action(std::vector<size_t>{n, OAKGPU_BUILD_MAX_STEPS}), index(std::vector<size_t>{n, OAKGPU_BUILD_MAX_STEPS}),
+            n_legal(std::vector<size_t>{n, OAKGPU_BUILD_MAX_STEPS});
+        py::array_t<float> prob(std::vector<size_t>{n, OAKGPU_BUILD_MAX_STEPS});
+        std::memset(action.mutable_data(), 0, steps * 2);
+        std::memset(index.mutable_data(), 0, steps * 2);
+        std::memset(n_legal.mutable_data(), 0, steps * 2);
+        std::memset(prob.mutable_data(), 0, steps * 4);
+        oakgpu_build_outputs out{};
+        out.teams_out = teams_out.mutable_data(); out.n_updates = n_updates.mutable_data(); out.action = action.mutable_data(); out.index = index.mutable_data();
+        out.n_legal = n_legal.mutable_data(); out.prob = prob.mutable_data(); out.teams_init = teams_init.mutable_data(); out.sizes_out = sizes.mutable_data();
+        out.team_index = team_index.mutable_data();
+        const oakgpu_build_provider prm{max_pokemon, input_update, pokemon_delete_prob, move_delete_prob, team_modify_prob};
+        int rc = 0;
+        std::string err;
+        {
+          py::gil_scoped_release release;
+          std::lock_guard<std::mutex> lock(g_ctx_mu);
+          oakgpu_build_net *bn = nullptr;
+          rc = oakgpu_build_provide_check(pool.data(), (uint32_t)(pool.size() / 30), (uint32_t)n, max_pokemon, pokemon_delete_prob, move_delete_prob, team_modify_prob);
+          if (!rc) rc = oakgpu_build_net_load(context(), (const uint8_t *)net.data(), net.size(), &bn);
+          if (!rc) rc = oakgpu_build_provide(context(), bn, pool.data(), (uint32_t)(pool.size() / 30), seeds.data(), (uint32_t)n, &prm, &out);
+          if (rc) err = oakgpu_last_error();
+          oakgpu_build_net_destroy(bn);
+        }
+        if (rc) throw std::runtime_error(err);
+        py::dict d;
+        d["teams"] = teams_out; d["team_index"] = team_index; d["n_updates"] = n_updates; d["teams_init"] = teams_init; d["sizes"] = sizes;
+        d["action"] = action; d["index"] = index; d["n_legal"] = n_legal; d["prob"] = prob;
+        return d;
+      },
+      py::arg("net_bytes"), py::arg("pool"), py::arg("seeds"), py::arg("max_pokemon") = 6, py::arg("pokemon_delete_prob") = 0.0, py::arg("move_delete_prob") = 0.0,
+      py::arg("team_modify_prob") = 0.0, py::arg("input_update") = 0);
 }

@@ -33,6 +33,22 @@ def write_random_net(path, seed=7, activation=1, **dims):
             f.write((rng.random((o, i)) * 2 * k - k).astype("<f4").tobytes())
 
 
+BUILD_N_DIM = 3749   # Encode::Build::Tensorizer<Format::OU>::n_dim (oak_amd/csrc/build_tables.inc)
+
+
+def write_random_build_net(path, seed, policy_hidden=128, value_hidden=128):
+    """Seeded synthetic `.build.net` (NN::Build::Network::read_parameters: policy_net then value_net, three Affine blocks each, no header):
+    n_dim -> policy_hidden -> policy_hidden -> n_dim and n_dim -> value_hidden -> value_hidden -> 1, the reference's initialiser."""
+    rng = np.random.default_rng(seed)
+    with open(path, "wb") as f:
+        for i, o in [(BUILD_N_DIM, policy_hidden), (policy_hidden, policy_hidden), (policy_hidden, BUILD_N_DIM),
+                     (BUILD_N_DIM, value_hidden), (value_hidden, value_hidden), (value_hidden, 1)]:
+            k = 1.0 / np.sqrt(i)
+            f.write(struct.pack("<II", i, o))
+            f.write((rng.random(o) * 2 * k - k).astype("<f4").tobytes())
+            f.write((rng.random((o, i)) * 2 * k - k).astype("<f4").tobytes())
+
+
 def flops_per_leaf(hidden=256, value_hidden=256, nnz_pokemon=12, nnz_active=45):
     """main value path + embeddings recomputed per leaf."""
     main = 2 * (768 * hidden + hidden * hidden + hidden * value_hidden + value_hidden)

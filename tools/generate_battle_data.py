@@ -5,6 +5,7 @@ files under --out.
   python tools/generate_battle_data.py --out DIR [--games N] [--batch B] [--teams FILE] [--budget K] [--bandit ucb-2.0 | pucb-1.5]
          [--eval mc | fp | NET.battle.net] [--discrete] [--policy-mode e] [--policy-temp 1] [--policy-min 0] [--max-battle-length L]
          [--no-nash | --device-nash] [--seed S] [--file-mb 8] [--keep-node [--keep-arena NODES]]
+         [--build-network NET.build.net [--team-modify-prob P] [--pokemon-delete-prob P] [--move-delete-prob P] [--max-pokemon K]]
 
 --teams FILE: JSON {"teams": [[[species, move, move, move, move] x 6] ...]} by name, the layout of tests/golden/ou_sample_teams.json (the
 default: the reference's 16 sample teams); each game draws its two teams from the file with --seed's generator, a pair that fails the
@@ -12,7 +13,15 @@ endless battle check is drawn again (generate.cc:222-225).  --batch games are re
 is closed once it holds --file-mb MiB of whole records; names are <seed>_<index>.battle.data.  A game that reaches --max-battle-length
 frames is dropped, as generate drops it.  --keep-node: each game's tree goes on into the next turn (generate.cc:324-333) on a kept forest
 of --keep-arena nodes per tree (0 = 4 * budget + 1); then the keep-node ratio is printed as generate prints it (updates that found their
-child / updates), with the trees dropped for want of room.  Prints games, frames, dropped games and seconds."""
+child / updates), with the trees dropped for want of room.  Prints games, frames, dropped games and seconds.
+
+--build-network: the other half of generate (TeamBuilding::Provider::get_trajectory): both seats' teams come from oak_amd.build.provide on
+the device -- a team of the pool, truncated to --max-pokemon, with probability --team-modify-prob thinned by --pokemon-delete-prob /
+--move-delete-prob and completed by the build network -- pairs that fail the endless battle check are provided again with fresh seeds
+before the games start, and every batch also writes <seed>_<batch>.build.data beside the `.battle.data`: one 128-byte record per built
+seat of a kept game, value 0.5, the p1 rows with the game's score and the p2 rows with 1 - score.  The engine takes teams with empty
+slots and empty move slots (init_side skips them as the reference's does), so --max-pokemon below 6 and species whose pools hold fewer
+than four moves are played as they are.  The seconds spent in team building are printed beside the total."""
 import argparse
 import os
 import sys
@@ -62,6 +71,11 @@ def main():
     ap.add_argument("--file-mb", type=float, default=8.0)
     ap.add_argument("--keep-node", action="store_true")
     ap.add_argument("--keep-arena", type=int, default=0)
+    ap.add_argument("--build-network", default="", help="a .build.net: build both seats' teams on the device and write .build.data")
+    ap.add_argument("--team-modify-prob", type=float, default=0.0)
+    ap.add_argument("--pokemon-delete-prob", type=float, default=0.0)
+    ap.add_argument("--move-delete-prob", type=float, default=0.0)
+    ap.add_argument("--max-pokemon", type=int, default=6)
     a = ap.parse_args()
     name, _, c = a.bandit.partition("-")
     if name not in ("ucb", "pucb"):
@@ -75,6 +89,14 @@ def main():
     if evaluator is None:
         evaluator = net = Network(ctx, path=a.eval, discrete=a.discrete)
     pool = team_bytes(a.teams)
+    build_net = None
+    if a.build_network:
+        from oak_amd import build
+        build.check_provide(np.asarray(pool, np.uint8).reshape(-1, 30), 1, a.max_pokemon, a.pokemon_delete_prob, a.move_delete_prob, a.team_modify_prob)
+        build_net = build.BuildNetwork(ctx, a.build_network)
+    elif a.max_pokemon != 6 or a.team_modify_prob or a.pokemon_delete_prob or a.move_delete_prob:
+        sys.exit("--max-pokemon / --team-modify-prob / --pokemon-delete-prob / --move-delete-prob need --build-network")
+    build_seconds, build_records, batches = 0.0, 0, 0
     rng = np.random.default_rng(a.seed)
     os.makedirs(a.out, exist_ok=True)
     batch = max(1, min(a.batch, a.games))
@@ -99,7 +121,15 @@ def main():
 
     while played < a.games:
         n = min(batch, a.games - played)
-        teams, battle_seeds, seeds = draw_games(pool, n, rng)
+        if build_net is None:
+            teams, battle_seeds, seeds = draw_games(pool, n, rng)
+        else:
+            tb = time.perf_counter()
+            teams, seats = build.provide_pairs(ctx, build_net, np.asarray(pool, np.uint8).reshape(-1, 30), rng.integers(0, 1 << 63, (n, 2), dtype=np.uint64),
+                                               max_pokemon=a.max_pokemon, pokemon_delete_prob=a.pokemon_delete_prob, move_delete_prob=a.move_delete_prob,
+                                               team_modify_prob=a.team_modify_prob)
+            build_seconds += time.perf_counter() - tb
+            battle_seeds, seeds = rng.integers(0, 1 << 63, n, dtype=np.uint64), rng.integers(0, 1 << 63, n, dtype=np.uint64)
         stats = {}
         stream, offsets, n_frames, results, status = forest_selfplay(
             ctx, teams, battle_seeds, seeds, a.budget, c=float(c or 2.0), bandit=name, evaluator=evaluator, policy_mode=a.policy_mode,
@@ -108,6 +138,18 @@ def main():
         if a.keep_node:   # RuntimeData::update_with_node_counter / update_counter (generate.cc:412-416)
             updates, updates_with_node, trees_dropped = updates + int(n_frames.sum()), updates_with_node + stats["nodes_kept"], trees_dropped + stats["dropped"]
         kept = status == 0
+        if build_net is not None:   # generate.cc:190-213, 361-386: the trajectories of the kept games with the game's score
+            tb = time.perf_counter()
+            score = np.array([{1: 1.0, 2: 0.0, 3: 0.5}.get(int(r) & 15, -1.0) for r in results], np.float32)
+            data = b""
+            for s_, seat in enumerate(seats):
+                seat["n_updates"] = np.where(kept, seat["n_updates"], 0).astype(np.uint8)
+                data += build.records(ctx, seat, 0.5, np.where(score < 0, -1.0, score if s_ == 0 else 1 - score).astype(np.float32))
+            with open(os.path.join(a.out, "%d_%d.build.data" % (a.seed, batches)), "wb") as f:
+                f.write(data)
+            build_records += len(data) // 128
+            build_seconds += time.perf_counter() - tb
+        batches += 1
         pending += [stream[int(offsets[g]):int(offsets[g + 1])] for g in range(n) if kept[g]]
         played, frames, dropped = played + n, frames + int(n_frames[kept].sum()), dropped + int((~kept).sum())
         flush(False)
@@ -115,6 +157,9 @@ def main():
     s = time.perf_counter() - t0
     print("games: %d, frames: %d, dropped: %d, files: %d, seconds: %.2f (%.1f games/s, %.0f frames/s)" % (played - dropped, frames, dropped, files, s,
                                                                                                        (played - dropped) / s, frames / s))
+    if build_net is not None:
+        print("team building: %d records, %.2f seconds (%.1f %% of the call)" % (build_records, build_seconds, 100 * build_seconds / s))
+        build_net.close()
     if a.keep_node:
         print("keep node ratio: %g" % (updates_with_node / max(updates, 1)))
         print("trees dropped for want of room: %d" % trees_dropped)
