@@ -810,8 +810,7 @@ static int forest_search_host(oakgpu_forest *f, oakgpu_net *net, const oakgpu_se
   oakgpu_forest_outputs ho;
   carve_outputs(h.data(), n, &ho);
   const double us = std::chrono::duration<double, std::micro>(std::chrono::high_resolution_clock::now() - t0).count();
-  constexpr size_t NASH_PAY_STRIDE = 82; // oakgpu_nash_solve_dev's rows: 81 payoffs + (m | n << 8)
-  std::vector<int32_t> pay(solve_nash == 2 ? (size_t)n * NASH_PAY_STRIDE : 0, 0);
+  std::vector<int32_t> pay(solve_nash == 2 ? (size_t)n * oak_nash::PAY_STRIDE : 0, 0);
   for (uint32_t g = 0; g < n; ++g) {
     oakgpu_search_output &x = out[g];
     memset(&x, 0, sizeof x);
@@ -828,8 +827,8 @@ static int forest_search_host(oakgpu_forest *f, oakgpu_net *net, const oakgpu_se
     oak_pick::process_output(x.visit_matrix, x.value_matrix, m, nn, x.iterations, &x.empirical_value, x.p1_empirical, x.p2_empirical, M);
     double nv = 0;
     if (solve_nash == 2) { // one device solve over all n trees, below
-      memcpy(pay.data() + (size_t)g * NASH_PAY_STRIDE, M, sizeof M);
-      pay[(size_t)g * NASH_PAY_STRIDE + 81] = m | nn << 8;
+      memcpy(pay.data() + (size_t)g * oak_nash::PAY_STRIDE, M, sizeof M);
+      pay[(size_t)g * oak_nash::PAY_STRIDE + 81] = m | nn << 8;
     } else if (solve_nash && oak_nash::solve(M, m, nn, x.p1_nash, x.p2_nash, &nv)) x.nash_value = nv / 256.0;
   }
   if (solve_nash == 2) {

@@ -4,13 +4,14 @@
 //   k_fm_start   : row g is game g at turn 0: its stream, its counter
 //   k_fm_retire  : one lane per row: a finished, stopped or cut row scatters result, turn count and status by game index and counts itself;
 //                  how many rows of each block are still live
-//   k_fsp_offsets: (forest_rows.hpp) the exclusive prefix sums of those per-block counts, and their total = the live count
+//   k_rows_offsets: (game_rows.hpp) the exclusive prefix sums of those per-block counts, and their total = the live count
 //   k_fm_compact : the live rows, in order, into the other half of the double buffer, each with its two choice counts and the first legal
 //                  choice of either side (what an unsearched seat plays)
 //   k_fm_prelude : one workgroup over the live rows: the streams advance, both seats' tree seeds, both seats' row lists by a stable prefix
-//                  sum, and the 12-byte record the host reads: live rows, p1 rows, p2 rows
+//                  sum (game_rows.hpp's scan pass), and the 12-byte record the host reads: live rows, p1 rows, p2 rows
 //   k_fm_gather  : 24 lanes per listed row: battle (16-byte pieces), durations, result byte into the seat's contiguous search input
-//   k_fsp_payoffs: (forest_rows.hpp, solve_nash) the integer payoffs for the host threads that solve them (1) or for oakgpu_nash_solve_dev (2)
+//   k_fsp_payoffs: (forest_rows.hpp's solve_turn, solve_nash) the integer payoffs for the host threads that solve them (1) or for
+//                  oakgpu_nash_solve_dev (2)
 //   k_fm_pick    : one lane per listed row: selfplay_pick.hpp's rule for ONE side of the seat's own root output, the early-stop sign,
 //                  scattered back by row list
 //   k_fm_finish  : one lane per live row: the early stop, the turn's log record, the turn count
@@ -23,7 +24,9 @@
 //   k_fm_record_lengths: one lane per game: the record's length (0 for a cut or zeroed game) and the byte the pack kernels keep a game by
 //   k_fsp_lengths, k_fsp_pack_head, k_fsp_pack_log: (forest_rows.hpp) the record bases, then per seat the heads and the log's updates
 // Every kernel is a plain grid over rows, games or entries (the scans: one workgroup); none waits for another block.  Between gather and pick runs
-// oakgpu_forest_search_dev over exactly the seat's rows, after finish oakgpu_update_dev over the live rows.
+// oakgpu_forest_search_dev over exactly the seat's rows, after finish oakgpu_update_dev over the live rows.  Retire and compact run on
+// game_rows.hpp's place, move and live count, with this loop's own row; the host's Nash solve, log growth, record bases, pack and records'
+// copies are forest_rows.hpp's, shared with forestplay.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -42,11 +45,12 @@
 namespace oak {
 namespace fm {
 
-using fsp::BLOCK;
-using fsp::DEAD;
+using game_rows::BLOCK;
+using game_rows::DEAD;
+using game_rows::NO_ROW;
+using game_rows::u32x4;
 using fsp::HEAD_BYTES;
 using fsp::LogEntry;
-using fsp::NO_ROW;
 enum : uint8_t { FLAG_NONE = 0, FLAG_ZERO_POLICY = 2, FLAG_EARLY_WIN = 3, FLAG_EARLY_LOSE = 4 }; // a row's stop flag between pick and retire
 static_assert(sizeof(oakgpu_match_turn) == 24, "one log record is 24 bytes");
 
@@ -105,7 +109,7 @@ struct RetireArgs {
 
 __global__ __launch_bounds__(BLOCK) void k_fm_retire(RetireArgs a) {
   __shared__ uint32_t wave_live[BLOCK / 64];
-  const uint32_t tid = threadIdx.x, row = blockIdx.x * BLOCK + tid, lane = tid & 63;
+  const uint32_t row = blockIdx.x * BLOCK + threadIdx.x;
   const bool in = row < a.rows;
   const uint32_t g = in ? a.r.game[row] : DEAD;
   bool live = false;
@@ -132,10 +136,7 @@ __global__ __launch_bounds__(BLOCK) void k_fm_retire(RetireArgs a) {
       }
     }
   }
-  const unsigned long long ml = __ballot(live);
-  if (lane == 0) wave_live[tid >> 6] = (uint32_t)__popcll(ml);
-  __syncthreads();
-  if (tid == 0) a.block_live[blockIdx.x] = wave_live[0] + wave_live[1] + wave_live[2] + wave_live[3];
+  game_rows::count_block_live(live, wave_live, a.block_live);
 }
 
 struct CompactArgs {
@@ -145,23 +146,13 @@ struct CompactArgs {
   uint32_t rows;
 };
 
-// Stable, as forestplay.hip's k_fsp_compact: a live row's place is its block's offset + the live rows in front of it in the block; the
-// 384-byte battles move as whole rows, 24 lanes x 16 bytes each.  The turn's choice counts and default choices ride along.
+// Stable (game_rows.hpp: compact_place, compact_battles).  The turn's choice counts and default choices ride along.
 __global__ __launch_bounds__(BLOCK) void k_fm_compact(CompactArgs a) {
   __shared__ uint32_t wave_total[BLOCK / 64];
   __shared__ uint32_t place[BLOCK];
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  const uint32_t tid = threadIdx.x, base = blockIdx.x * BLOCK, row = base + tid, lane = tid & 63, wave = tid >> 6;
+  const uint32_t row = blockIdx.x * BLOCK + threadIdx.x;
   const bool live = row < a.rows && a.from.game[row] != DEAD;
-  const unsigned long long m = __ballot(live);
-  const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-  if (lane == 0) wave_total[wave] = (uint32_t)__popcll(m);
-  __syncthreads();
-  uint32_t before = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < BLOCK / 64; ++w) if (w < wave) before += wave_total[w];
-  const uint32_t to = live ? a.block_offset[blockIdx.x] + before + prefix : NO_ROW;
-  place[tid] = to;
+  const uint32_t to = game_rows::compact_place(live, a.block_offset[blockIdx.x], wave_total, place);
   if (live) {
     *((uint2 *)a.to.durations + to) = *((const uint2 *)a.from.durations + row);
     a.to.results[to] = a.from.results[row];
@@ -179,21 +170,12 @@ __global__ __launch_bounds__(BLOCK) void k_fm_compact(CompactArgs a) {
     a.to.rng[to] = a.from.rng[row];
   }
   __syncthreads();
-  const u32x4 *src = (const u32x4 *)a.from.battles + (size_t)base * 24;
-  u32x4 *dst = (u32x4 *)a.to.battles;
-  const uint32_t in_block = a.rows - base < (uint32_t)BLOCK ? a.rows - base : (uint32_t)BLOCK;
-#pragma unroll 4
-  for (int q = 0; q < 24; ++q) {
-    const uint32_t i = q * BLOCK + tid, b = i / 24, w = i - b * 24;
-    if (b >= in_block) continue; // (rows past the end are not read)
-    const uint32_t t = place[b];
-    if (t != NO_ROW) dst[(size_t)t * 24 + w] = src[i];
-  }
+  game_rows::compact_battles(a.from.battles, a.to.battles, a.rows, place);
 }
 
 struct PreludeArgs {
   Rows r;
-  uint32_t *ctl;                 // [0] = the live count (k_fsp_offsets' total), [1], [2] = the seats' row counts: the host's 12 bytes
+  uint32_t *ctl;                 // [0] = the live count (k_rows_offsets' total), [1], [2] = the seats' row counts: the host's 12 bytes
   uint32_t *list1, *list2;       // the live rows with m > 1 / n > 1, in row order
   uint64_t *seed1, *seed2;       // per list entry: the seed of that seat's tree
   uint32_t capacity;             // rows the buffers hold (a live count above it is never followed)
@@ -201,48 +183,34 @@ struct PreludeArgs {
 
 // The turn prelude, one workgroup of 1,024: per live row the stream advances -- seat p1's seed first, then seat p2's, each only where the
 // seat has more than one choice -- and both row lists are built by one scan of the two flags packed into a dword (16 bits each: a pass
-// holds 1,024 rows), 1,024 rows per pass with the carries in registers.
+// holds 1,024 rows, so neither half overflows within game_rows.hpp's scan pass), with the carries of the two lists in registers.
 __global__ __launch_bounds__(1024) void k_fm_prelude(PreludeArgs a) {
   __shared__ uint32_t wave_total[16];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t live = a.ctl[0] < a.capacity ? a.ctl[0] : a.capacity;
   uint32_t carry1 = 0, carry2 = 0;
   for (uint32_t base = 0; base < live; base += 1024) {
-    const uint32_t row = base + tid;
+    const uint32_t row = base + threadIdx.x;
     const bool in = row < live;
     const bool f1 = in && a.r.m[row] > 1, f2 = in && a.r.n[row] > 1;
-    const uint32_t own = (f1 ? 1u : 0u) | (f2 ? 0x10000u : 0u);
-    uint32_t incl = own;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t up = __shfl_up(incl, d);
-      if ((int)lane >= d) incl += up;
-    }
-    if (lane == 63) wave_total[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < 16; ++w) { const uint32_t t = wave_total[w]; if (w < wave) before += t; all += t; }
-    const uint32_t excl = before + incl - own;
+    const game_rows::ScanPass<uint32_t> s = game_rows::scan_pass((f1 ? 1u : 0u) | (f2 ? 0x10000u : 0u), wave_total);
     if (f1 || f2) {
       uint64_t rng = a.r.rng[row];
       if (f1) {
-        const uint32_t k = carry1 + (excl & 0xFFFFu);
+        const uint32_t k = carry1 + (s.before & 0xFFFFu);
         a.list1[k] = row;
         a.seed1[k] = oak_pick::splitmix64(rng);
       }
       if (f2) {
-        const uint32_t k = carry2 + (excl >> 16);
+        const uint32_t k = carry2 + (s.before >> 16);
         a.list2[k] = row;
         a.seed2[k] = oak_pick::splitmix64(rng);
       }
       a.r.rng[row] = rng;
     }
-    carry1 += all & 0xFFFFu;
-    carry2 += all >> 16;
-    __syncthreads();
+    carry1 += s.total & 0xFFFFu;
+    carry2 += s.total >> 16;
   }
-  if (tid == 0) { a.ctl[1] = carry1; a.ctl[2] = carry2; }
+  if (threadIdx.x == 0) { a.ctl[1] = carry1; a.ctl[2] = carry2; }
 }
 
 struct GatherArgs {
@@ -254,7 +222,6 @@ struct GatherArgs {
 
 // 393 bytes per listed row: the battle as 24 pieces of 16 bytes, one lane each; the piece-0 lane also moves the durations and the result
 __global__ __launch_bounds__(BLOCK) void k_fm_gather(GatherArgs a) {
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   const uint32_t i = blockIdx.x * BLOCK + threadIdx.x, k = i / 24, w = i - k * 24;
   if (k >= a.count) return;
   const uint32_t row = a.list[k];
@@ -385,16 +352,19 @@ namespace {
 
 using namespace oak::fm;
 using oak::fsp::carve_outputs;
-using oak::fsp::k_fsp_lengths;
-using oak::fsp::k_fsp_offsets;
-using oak::fsp::k_fsp_pack_head;
-using oak::fsp::k_fsp_pack_log;
-using oak::fsp::k_fsp_payoffs;
-using oak::fsp::PackArgs;
+using oak::fsp::copy_records;
+using oak::fsp::DeviceArrays;
+using oak::fsp::first_log_capacity;
+using oak::fsp::grow_log;
+using oak::fsp::k_rows_offsets;
 using oak::fsp::OUT_BYTES;
+using oak::fsp::pack_records;
+using oak::fsp::PackArgs;
 using oak::fsp::PAY_STRIDE;
-using oak::fsp::PayoffArgs;
-using oak::fsp::solve_rows;
+using oak::fsp::policy_refusal;
+using oak::fsp::record_bases;
+using oak::fsp::Records;
+using oak::fsp::solve_turn;
 
 #define RC(x) do { int _r = (x); if (_r) return _r; } while (0)
 
@@ -402,7 +372,7 @@ using oak::fsp::solve_rows;
 // first call that records: the per-game arrays sized by the batch, the two logs grown by doubling between turns as forestplay.hip's, the
 // two streams sized by the records.
 struct Workspace {
-  std::vector<void *> dev;
+  DeviceArrays dev;
   uint32_t capacity = 0; // rows
   Rows half[2] = {};
   uint8_t *ch1 = nullptr, *cnt1 = nullptr, *ch2 = nullptr, *cnt2 = nullptr;
@@ -424,7 +394,7 @@ struct Workspace {
   std::vector<double> h_nash;
   // recording
   bool records_on = false, have_records = false;
-  std::vector<void *> rec_dev;
+  DeviceArrays rec_dev;
   uint32_t rec_capacity = 0, last_n = 0;               // games
   uint32_t *cursor = nullptr, *length = nullptr;       // by game index
   uint8_t *keep = nullptr;
@@ -434,8 +404,7 @@ struct Workspace {
   uint8_t *stream[2] = {nullptr, nullptr};
   size_t stream_capacity = 0, stream_bytes = 0;        // of each stream: the two are the same size
   void release_records() {
-    for (void *p : rec_dev) (void)hipFree(p);
-    rec_dev.clear();
+    rec_dev.free_all();
     for (int s = 0; s < 2; ++s) {
       if (rlog[s]) (void)hipFree(rlog[s]);
       if (stream[s]) (void)hipFree(stream[s]);
@@ -444,16 +413,10 @@ struct Workspace {
     rec_capacity = 0; rlog_capacity = 0; stream_capacity = 0; stream_bytes = 0; have_records = false;
   }
   void release() {
-    for (void *p : dev) (void)hipFree(p);
-    dev.clear();
+    dev.free_all();
     if (log_stage) (void)hipFree(log_stage);
     log_stage = nullptr; log_capacity = 0; capacity = 0;
     release_records();
-  }
-  template <class T> int get(T *&p, size_t count) {
-    RC(dev_alloc(p, count));
-    dev.push_back(p);
-    return 0;
   }
 };
 
@@ -476,17 +439,15 @@ Workspace *workspace_of(oakgpu_forest *f) {
 int records_for(Workspace *w, hipStream_t stream, uint32_t n) {
   if (w->rec_capacity < n) {
     HIPCHK(hipStreamSynchronize(stream));
-    for (void *p : w->rec_dev) (void)hipFree(p);
-    w->rec_dev.clear();
+    DeviceArrays &d = w->rec_dev;
+    d.free_all();
     w->rec_capacity = 0;
-    auto get = [&](auto *&p, size_t count) { RC(dev_alloc(p, count)); w->rec_dev.push_back(p); return 0; };
-    RC(get(w->cursor, n)); RC(get(w->length, n)); RC(get(w->keep, n)); RC(get(w->offsets, (size_t)n + 1));
+    RC(d.get(w->cursor, n)); RC(d.get(w->length, n)); RC(d.get(w->keep, n)); RC(d.get(w->offsets, (size_t)n + 1));
     w->rec_capacity = n;
   }
   if (!w->rlog[0]) {
-    const size_t want = std::max<size_t>((size_t)n * 16, 4096);
-    for (int s = 0; s < 2; ++s) RC(dev_alloc(w->rlog[s], want));
-    w->rlog_capacity = want;
+    for (int s = 0; s < 2; ++s) RC(dev_alloc(w->rlog[s], first_log_capacity(n)));
+    w->rlog_capacity = first_log_capacity(n);
   }
   return 0;
 }
@@ -496,24 +457,24 @@ int workspace_for(oakgpu_forest *f, uint32_t n, Workspace **out) {
   *out = w;
   if (w->capacity >= n) return 0;
   HIPCHK(hipStreamSynchronize((hipStream_t)oakgpu_ctx_stream(oakgpu_forest_ctx(f))));
-  for (void *p : w->dev) (void)hipFree(p);
-  w->dev.clear();
+  DeviceArrays &d = w->dev;
+  d.free_all();
   w->capacity = 0;
   const size_t T = n, blocks = (T + BLOCK - 1) / BLOCK;
   for (int h = 0; h < 2; ++h) {
     Rows &r = w->half[h];
-    RC(w->get(r.battles, T * 384)); RC(w->get(r.durations, T * 8)); RC(w->get(r.results, T)); RC(w->get(r.m, T)); RC(w->get(r.n, T)); RC(w->get(r.c1, T));
-    RC(w->get(r.c2, T)); RC(w->get(r.flag, T)); RC(w->get(r.s1, T)); RC(w->get(r.s2, T)); RC(w->get(r.game, T)); RC(w->get(r.turns, T)); RC(w->get(r.rng, T));
-    RC(w->get(r.ev1, T)); RC(w->get(r.ev2, T));
+    RC(d.get(r.battles, T * 384)); RC(d.get(r.durations, T * 8)); RC(d.get(r.results, T)); RC(d.get(r.m, T)); RC(d.get(r.n, T)); RC(d.get(r.c1, T));
+    RC(d.get(r.c2, T)); RC(d.get(r.flag, T)); RC(d.get(r.s1, T)); RC(d.get(r.s2, T)); RC(d.get(r.game, T)); RC(d.get(r.turns, T)); RC(d.get(r.rng, T));
+    RC(d.get(r.ev1, T)); RC(d.get(r.ev2, T));
   }
-  RC(w->get(w->ch1, T * 9)); RC(w->get(w->cnt1, T)); RC(w->get(w->ch2, T * 9)); RC(w->get(w->cnt2, T));
+  RC(d.get(w->ch1, T * 9)); RC(d.get(w->cnt1, T)); RC(d.get(w->ch2, T * 9)); RC(d.get(w->cnt2, T));
   for (int s = 0; s < 2; ++s) {
-    RC(w->get(w->list[s], T)); RC(w->get(w->seed[s], T)); RC(w->get(w->out_block[s], OUT_BYTES * T + 16 * 16)); RC(w->get(w->nash[s], T * 19));
+    RC(d.get(w->list[s], T)); RC(d.get(w->seed[s], T)); RC(d.get(w->out_block[s], OUT_BYTES * T + 16 * 16)); RC(d.get(w->nash[s], T * 19));
   }
-  RC(w->get(w->gb, T * 384)); RC(w->get(w->gd, T * 8)); RC(w->get(w->gr, T)); RC(w->get(w->pay, T * PAY_STRIDE));
-  RC(w->get(w->results_out, T)); RC(w->get(w->status_out, T)); RC(w->get(w->turns_out, T)); RC(w->get(w->block_live, blocks)); RC(w->get(w->block_offset, blocks));
-  RC(w->get(w->ctl, 4)); RC(w->get(w->counts, 4));
-  RC(w->get(w->in_b, T * 384)); RC(w->get(w->in_d, T * 8)); RC(w->get(w->in_r, T)); RC(w->get(w->in_seeds, T));
+  RC(d.get(w->gb, T * 384)); RC(d.get(w->gd, T * 8)); RC(d.get(w->gr, T)); RC(d.get(w->pay, T * PAY_STRIDE));
+  RC(d.get(w->results_out, T)); RC(d.get(w->status_out, T)); RC(d.get(w->turns_out, T)); RC(d.get(w->block_live, blocks)); RC(d.get(w->block_offset, blocks));
+  RC(d.get(w->ctl, 4)); RC(d.get(w->counts, 4));
+  RC(d.get(w->in_b, T * 384)); RC(d.get(w->in_d, T * 8)); RC(d.get(w->in_r, T)); RC(d.get(w->in_seeds, T));
   w->capacity = n;
   return 0;
 }
@@ -521,15 +482,8 @@ int workspace_for(oakgpu_forest *f, uint32_t n, Workspace **out) {
 int fail_seat(const char *seat, const std::string &what) { return oakgpu_fail_msg((std::string("oakgpu_forest_match: seat ") + seat + ": " + what).c_str()); }
 
 int check_seat(const char *name, const oakgpu_match_seat &s, uint32_t max_trees, uint32_t max_iterations, int contextual, uint32_t n, int solve_nash) {
-  oak_pick::PolicyMode mode;
-  const int bad = oak_pick::parse_policy_mode(s.policy_mode, sizeof s.policy_mode, &mode);
-  if (bad == 'b') return fail_seat(name, "policy mode 'b' (beta) is not supported (util/policy.h:59-60 throws)");
-  if (bad > 0) return fail_seat(name, std::string("unknown policy mode letter '") + (char)bad + "' (words are e / n / x / p with optional weights, util/policy.h:22-98)");
-  if (bad < 0) return fail_seat(name, "more than 8 policy mode words");
-  if (!(s.policy_min <= 1.0)) return fail_seat(name, "RuntimePolicy: zero policy (policy_min above 1 zeroes every policy)");
-  if (!solve_nash)
-    for (uint32_t q = 0; q < mode.count; ++q)
-      if (mode.word[q].kind == oak_pick::W_NASH) return fail_seat(name, "policy mode word 'n' needs solve_nash (the nash strategies are not computed)");
+  const std::string refusal = policy_refusal(s.policy_mode, sizeof s.policy_mode, s.policy_min, solve_nash);
+  if (!refusal.empty()) return fail_seat(name, refusal);
   if (int rc = oakgpu_forest_check(max_trees, max_iterations, contextual, &s.search, s.net != nullptr, n, nullptr, 0, 0)) {
     std::string msg = oakgpu_last_error();
     const std::string from = "oakgpu_forest_search:";
@@ -614,7 +568,7 @@ int oakgpu_forest_match_dev(oakgpu_forest *f, const oakgpu_forest_match_params *
     const uint32_t blocks = (rows + BLOCK - 1) / BLOCK;
     const RetireArgs ra{w->half[cur], w->results_out, w->status_out, w->turns_out, w->counts, w->block_live, rows, max_turns};
     hipLaunchKernelGGL(k_fm_retire, grid(rows), dim3(BLOCK), 0, stream, ra);
-    hipLaunchKernelGGL(k_fsp_offsets, dim3(1), dim3(1024), 0, stream, w->block_live, blocks, w->block_offset, w->ctl);
+    hipLaunchKernelGGL(k_rows_offsets, dim3(1), dim3(1024), 0, stream, w->block_live, blocks, w->block_offset, w->ctl);
     const CompactArgs ca{w->half[cur], w->half[cur ^ 1], w->block_offset, w->ch1, w->cnt1, w->ch2, w->cnt2, rows};
     hipLaunchKernelGGL(k_fm_compact, grid(rows), dim3(BLOCK), 0, stream, ca);
     cur ^= 1;
@@ -636,14 +590,7 @@ int oakgpu_forest_match_dev(oakgpu_forest *f, const oakgpu_forest_match_params *
     if (recording && entries + rows > w->rlog_capacity) { // the logs follow the turns played: doubled between turns
       const size_t want = std::max(w->rlog_capacity * 2, entries + rows);
       HIPCHK(hipStreamSynchronize(stream));
-      for (int s = 0; s < 2; ++s) {
-        LogEntry *bigger = nullptr;
-        RC(dev_alloc(bigger, want));
-        HIPCHK(hipMemcpyAsync(bigger, w->rlog[s], entries * sizeof(LogEntry), hipMemcpyDeviceToDevice, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        (void)hipFree(w->rlog[s]);
-        w->rlog[s] = bigger;
-      }
+      for (int s = 0; s < 2; ++s) RC(grow_log(w->rlog[s], entries, want, stream));
       w->rlog_capacity = want;
     }
     for (int s = 0; s < 2; ++s) {
@@ -657,19 +604,8 @@ int oakgpu_forest_match_dev(oakgpu_forest *f, const oakgpu_forest_match_params *
       RC(oakgpu_forest_search_dev(f, seat[s]->net, &sp[s], w->gb, w->gd, w->gr, w->seed[s], count, &o, nullptr, 0));
       const double *d_nash = nullptr;
       if (prm->solve_nash) {
-        const PayoffArgs pay{o.m, o.n, o.visit_matrix, o.value_matrix, w->pay, count};
-        hipLaunchKernelGGL(k_fsp_payoffs, grid(count), dim3(BLOCK), 0, stream, pay);
-        HIPCHK(hipGetLastError());
-        if (prm->solve_nash == 2) RC(oakgpu_nash_solve_dev(ctx, w->pay, count, w->nash[s])); // on the stream: nothing leaves the device
-        else {
-          w->h_pay.resize((size_t)count * PAY_STRIDE);
-          w->h_nash.resize((size_t)count * 19);
-          HIPCHK(hipMemcpyAsync(w->h_pay.data(), w->pay, w->h_pay.size() * 4, hipMemcpyDeviceToHost, stream));
-          HIPCHK(hipStreamSynchronize(stream));
-          solve_rows(w->h_pay.data(), count, w->h_nash.data());
-          HIPCHK(hipMemcpyAsync(w->nash[s], w->h_nash.data(), w->h_nash.size() * 8, hipMemcpyHostToDevice, stream));
-          HIPCHK(hipStreamSynchronize(stream)); // (the strategies' host copy is reused by the other seat)
-        }
+        RC(solve_turn(ctx, stream, prm->solve_nash, o, count, w->pay, w->nash[s], w->h_pay, w->h_nash));
+        if (prm->solve_nash == 1) HIPCHK(hipStreamSynchronize(stream)); // (the strategies' host copy is reused by the other seat)
         d_nash = w->nash[s] + (s ? (size_t)count * 9 : 0);
       }
       PickArgs pk{};
@@ -705,29 +641,13 @@ int oakgpu_forest_match_dev(oakgpu_forest *f, const oakgpu_forest_match_params *
   if (recording) { // pack: the record lengths and their bases in game order, then per seat the heads and the log's updates
     if (entries > 0xFFFFFFFFull) return oakgpu_fail_msg("oakgpu_forest_match: more than 2^32 turns in one call");
     hipLaunchKernelGGL(k_fm_record_lengths, grid(n), dim3(BLOCK), 0, stream, w->status_out, w->cursor, w->length, w->keep, n);
-    hipLaunchKernelGGL(k_fsp_lengths, dim3(1), dim3(1024), 0, stream, w->length, n, w->offsets);
-    HIPCHK(hipGetLastError());
-    unsigned long long total = 0;
-    HIPCHK(hipMemcpyAsync(&total, w->offsets + n, 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    if (total > w->stream_capacity) {
-      for (int s = 0; s < 2; ++s) {
-        if (w->stream[s]) (void)hipFree(w->stream[s]);
-        w->stream[s] = nullptr;
-      }
-      w->stream_capacity = 0;
-      for (int s = 0; s < 2; ++s) RC(dev_alloc(w->stream[s], (size_t)total));
-      w->stream_capacity = (size_t)total;
-    }
+    size_t total = 0;
+    RC(record_bases(stream, w->length, n, w->offsets, w->stream, 2, &w->stream_capacity, &total));
     if (total)
-      for (int s = 0; s < 2; ++s) { // the stored battle is the game's input battle
-        const PackArgs pa{w->offsets, w->turns_out, w->length, w->results_out, w->keep, battles, w->rlog[s], w->stream[s], n, (uint32_t)entries};
-        hipLaunchKernelGGL(k_fsp_pack_head, dim3((n + BLOCK / 64 - 1) / (BLOCK / 64)), dim3(BLOCK), 0, stream, pa);
-        if (entries) hipLaunchKernelGGL(k_fsp_pack_log, dim3((uint32_t)((entries + BLOCK / 16 - 1) / (BLOCK / 16))), dim3(BLOCK), 0, stream, pa);
-        HIPCHK(hipGetLastError());
-      }
+      for (int s = 0; s < 2; ++s) // the stored battle is the game's input battle
+        RC(pack_records(stream, PackArgs{w->offsets, w->turns_out, w->length, w->results_out, w->keep, battles, w->rlog[s], w->stream[s], n, (uint32_t)entries}));
     HIPCHK(hipStreamSynchronize(stream));
-    w->stream_bytes = (size_t)total;
+    w->stream_bytes = total;
     w->have_records = true;
   }
   return 0;
@@ -798,20 +718,8 @@ int oakgpu_forest_match_records(oakgpu_forest *f, int seat, uint8_t *stream_out,
   if (stream_out && capacity < w->stream_bytes) return oakgpu_fail_msg("oakgpu_forest_match_records: buffer too small");
   oakgpu_ctx *ctx = oakgpu_forest_ctx(f);
   RC(oakgpu_ctx_enter(ctx));
-  hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(ctx);
-  const hipMemcpyKind kind = to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  const size_t n = w->last_n;
-  if (stream_out && w->stream_bytes) HIPCHK(hipMemcpyAsync(stream_out, w->stream[seat], w->stream_bytes, kind, stream));
-  if (offsets) {
-    if (n) HIPCHK(hipMemcpyAsync(offsets, w->offsets, (n + 1) * 8, kind, stream));
-    else if (to_device) HIPCHK(hipMemsetAsync(offsets, 0, 8, stream));
-    else offsets[0] = 0;
-  }
-  if (n_frames && n) HIPCHK(hipMemcpyAsync(n_frames, w->turns_out, n * 4, kind, stream));
-  if (results && n) HIPCHK(hipMemcpyAsync(results, w->results_out, n, kind, stream));
-  if (status && n) HIPCHK(hipMemcpyAsync(status, w->status_out, n, kind, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  return 0;
+  const Records held{w->stream[seat], w->stream_bytes, w->offsets, w->turns_out, w->results_out, w->status_out, w->last_n};
+  return copy_records((hipStream_t)oakgpu_ctx_stream(ctx), held, stream_out, offsets, n_frames, results, status, to_device);
 }
 
 int oakgpu_match_pick_host(int side, uint32_t m, uint32_t n, const uint64_t *visit_matrix, const double *value_matrix, uint64_t iterations, const double *nash,

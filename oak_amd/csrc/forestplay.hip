@@ -4,11 +4,12 @@
 //   k_fsp_start    : row g is game g at frame 0: its stream, its counters
 //   k_fsp_retire   : one lane per row: a finished, dropped or stopped row scatters result, frame count, status and record length by game
 //                    index; how many rows of each block are still live
-//   k_fsp_offsets  : one workgroup: the exclusive prefix sums of those per-block counts, and their total = the live count the host reads
+//   k_rows_offsets : (game_rows.hpp) one workgroup: the exclusive prefix sums of those per-block counts, and their total = the live count the
+//                    host reads
 //   k_fsp_compact  : the live rows, in order, into the other half of the double buffer -- and the turn prelude: the row's stream advances,
 //                    its first draw is the seed of the row's tree
-//   k_fsp_payoffs  : (solve_nash) the integer payoffs of process_output's exact Nash solve, for the host threads that solve them (1) or for
-//                    oakgpu_nash_solve_dev (2: nashdev.hip, on the stream, the same bits)
+//   k_fsp_payoffs  : (forest_rows.hpp's solve_turn, solve_nash) the integer payoffs of process_output's exact Nash solve, for the host threads
+//                    that solve them (1) or for oakgpu_nash_solve_dev (2: nashdev.hip, on the stream, the same bits)
 //   k_fsp_pick     : one lane per live row: selfplay_pick.hpp's rule over the m x n live cells of the root matrices, the joint choice for the
 //                    update, one fixed-size entry of the turn-major log
 //   k_fsp_lengths  : (forest_rows.hpp, as the two below) one workgroup: the exclusive scan of the record lengths in game order = the record bases
@@ -20,7 +21,8 @@
 // successor.  The pick also keeps the row's nodes_kept count (selfplay.hip: + 1 per advance that kept, - 1 per root mismatch, never below 0).
 // Every kernel is a plain grid over rows, games or entries (the two scans: one workgroup); none waits for another block.  Between
 // compact and pick runs oakgpu_forest_search_dev over exactly the live rows (the forest refuses terminal roots), after pick
-// oakgpu_update_dev.  The pattern of retire / offsets / compact is policyplay.hip's, with this loop's own row.
+// oakgpu_update_dev.  Retire / offsets / compact run on game_rows.hpp's scan, place and move, as in policyplay.hip, with this loop's own
+// row; the Nash solve, the log, the record bases, the pack and the records' copies are forest_rows.hpp's, shared with forestmatch.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -28,14 +30,12 @@
 
 #include <algorithm>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/oakgpu.h"
 #include "oakgpu_internal.h"
-#include "nash.hpp"
 #include "selfplay_pick.hpp"
-#include "forest_rows.hpp" // k_fsp_offsets, k_fsp_payoffs, carve_outputs, solve_rows, LogEntry, k_fsp_lengths, k_fsp_pack_*: shared with forestmatch.hip
+#include "forest_rows.hpp"
 
 namespace oak {
 namespace fsp {
@@ -73,7 +73,7 @@ struct RetireArgs {
 
 __global__ __launch_bounds__(BLOCK) void k_fsp_retire(RetireArgs a) {
   __shared__ uint32_t wave_live[BLOCK / 64];
-  const uint32_t tid = threadIdx.x, row = blockIdx.x * BLOCK + tid, lane = tid & 63;
+  const uint32_t row = blockIdx.x * BLOCK + threadIdx.x;
   const bool in = row < a.rows;
   const uint32_t g = in ? a.r.game[row] : DEAD;
   bool live = false;
@@ -91,10 +91,7 @@ __global__ __launch_bounds__(BLOCK) void k_fsp_retire(RetireArgs a) {
       a.r.game[row] = DEAD;
     }
   }
-  const unsigned long long ml = __ballot(live);
-  if (lane == 0) wave_live[tid >> 6] = (uint32_t)__popcll(ml);
-  __syncthreads();
-  if (tid == 0) a.block_live[blockIdx.x] = wave_live[0] + wave_live[1] + wave_live[2] + wave_live[3];
+  game_rows::count_block_live(live, wave_live, a.block_live);
 }
 
 struct CompactArgs {
@@ -109,23 +106,13 @@ struct CompactArgs {
   int keep; // keep_node: the game's counts move with the row
 };
 
-// Stable: a live row's place is its block's offset + the live rows in front of it in the block.  The 384-byte battles move as whole rows, 24
-// lanes x 16 bytes each, as policyplay.hip's k_games_compact moves them.  The turn prelude rides along: search seed = splitmix64(rng).
+// Stable (game_rows.hpp: compact_place, compact_battles).  The turn prelude rides along: search seed = splitmix64(rng).
 __global__ __launch_bounds__(BLOCK) void k_fsp_compact(CompactArgs a) {
   __shared__ uint32_t wave_total[BLOCK / 64];
   __shared__ uint32_t place[BLOCK];
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  const uint32_t tid = threadIdx.x, base = blockIdx.x * BLOCK, row = base + tid, lane = tid & 63, wave = tid >> 6;
+  const uint32_t row = blockIdx.x * BLOCK + threadIdx.x;
   const bool live = row < a.rows && a.from.game[row] != DEAD;
-  const unsigned long long m = __ballot(live);
-  const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-  if (lane == 0) wave_total[wave] = (uint32_t)__popcll(m);
-  __syncthreads();
-  uint32_t before = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < BLOCK / 64; ++w) if (w < wave) before += wave_total[w];
-  const uint32_t to = live ? a.block_offset[blockIdx.x] + before + prefix : NO_ROW;
-  place[tid] = to;
+  const uint32_t to = game_rows::compact_place(live, a.block_offset[blockIdx.x], wave_total, place);
   if (live) {
     *((uint2 *)a.to.durations + to) = *((const uint2 *)a.from.durations + row);
     a.to.results[to] = a.from.results[row];
@@ -144,16 +131,7 @@ __global__ __launch_bounds__(BLOCK) void k_fsp_compact(CompactArgs a) {
     if (a.keep) { a.to.kept[to] = a.from.kept[row]; a.to.mism[to] = a.from.mism[row]; a.to.carry[to] = a.from.carry[row]; }
   }
   __syncthreads();
-  const u32x4 *src = (const u32x4 *)a.from.battles + (size_t)base * 24;
-  u32x4 *dst = (u32x4 *)a.to.battles;
-  const uint32_t in_block = a.rows - base < (uint32_t)BLOCK ? a.rows - base : (uint32_t)BLOCK;
-#pragma unroll 4
-  for (int q = 0; q < 24; ++q) {
-    const uint32_t i = q * BLOCK + tid, b = i / 24, w = i - b * 24;
-    if (b >= in_block) continue; // (rows past the end are not read)
-    const uint32_t t = place[b];
-    if (t != NO_ROW) dst[(size_t)t * 24 + w] = src[i];
-  }
+  game_rows::compact_battles(a.from.battles, a.to.battles, a.rows, place);
 }
 
 struct PickArgs {
@@ -230,7 +208,7 @@ using namespace oak::fsp;
 // the loop's workspace, attached to the forest and freed with it: everything sized by the batch is grow-only, the log grows by doubling
 // between turns, the stream is sized by the records
 struct Workspace {
-  std::vector<void *> dev;
+  DeviceArrays dev;
   uint32_t capacity = 0; // rows
   Rows half[2] = {};
   uint64_t *tree_seed = nullptr;
@@ -257,16 +235,10 @@ struct Workspace {
   std::vector<int32_t> h_pay;
   std::vector<double> h_nash;
   void release() {
-    for (void *p : dev) (void)hipFree(p);
-    dev.clear();
+    dev.free_all();
     if (log) (void)hipFree(log);
     if (stream) (void)hipFree(stream);
     log = nullptr; stream = nullptr; log_capacity = stream_capacity = 0; capacity = 0;
-  }
-  template <class T> int get(T *&p, size_t count) {
-    RC(dev_alloc(p, count));
-    dev.push_back(p);
-    return 0;
   }
 };
 
@@ -285,25 +257,25 @@ int workspace_for(oakgpu_forest *f, uint32_t n, Workspace **out) {
   *out = w;
   if (w->capacity >= n) return 0;
   HIPCHK(hipStreamSynchronize((hipStream_t)oakgpu_ctx_stream(oakgpu_forest_ctx(f))));
-  for (void *p : w->dev) (void)hipFree(p);
-  w->dev.clear();
+  DeviceArrays &d = w->dev;
+  d.free_all();
   w->capacity = 0;
   w->have = false;
   const size_t T = n, blocks = (T + BLOCK - 1) / BLOCK;
   for (int h = 0; h < 2; ++h) {
     Rows &r = w->half[h];
-    RC(w->get(r.battles, T * 384)); RC(w->get(r.durations, T * 8)); RC(w->get(r.results, T)); RC(w->get(r.c1, T)); RC(w->get(r.c2, T)); RC(w->get(r.flag, T));
-    RC(w->get(r.game, T)); RC(w->get(r.frames, T)); RC(w->get(r.cursor, T)); RC(w->get(r.rng, T));
-    if (oakgpu_forest_is_kept(f)) { RC(w->get(r.pi, T)); RC(w->get(r.pj, T)); RC(w->get(r.obs, T * 16)); RC(w->get(r.kept, T)); RC(w->get(r.mism, T)); RC(w->get(r.carry, T)); }
+    RC(d.get(r.battles, T * 384)); RC(d.get(r.durations, T * 8)); RC(d.get(r.results, T)); RC(d.get(r.c1, T)); RC(d.get(r.c2, T)); RC(d.get(r.flag, T));
+    RC(d.get(r.game, T)); RC(d.get(r.frames, T)); RC(d.get(r.cursor, T)); RC(d.get(r.rng, T));
+    if (oakgpu_forest_is_kept(f)) { RC(d.get(r.pi, T)); RC(d.get(r.pj, T)); RC(d.get(r.obs, T * 16)); RC(d.get(r.kept, T)); RC(d.get(r.mism, T)); RC(d.get(r.carry, T)); }
   }
   if (oakgpu_forest_is_kept(f)) {
-    RC(w->get(w->src_row, T)); RC(w->get(w->kept_out, T)); RC(w->get(w->mism_out, T)); RC(w->get(w->carry_out, T));
-    RC(w->get(w->adv_i, T)); RC(w->get(w->adv_j, T)); RC(w->get(w->adv_obs, T * 16)); RC(w->get(w->advanced, T));
+    RC(d.get(w->src_row, T)); RC(d.get(w->kept_out, T)); RC(d.get(w->mism_out, T)); RC(d.get(w->carry_out, T));
+    RC(d.get(w->adv_i, T)); RC(d.get(w->adv_j, T)); RC(d.get(w->adv_obs, T * 16)); RC(d.get(w->advanced, T));
   }
-  RC(w->get(w->tree_seed, T)); RC(w->get(w->out_block, OUT_BYTES * T + 16 * 16)); RC(w->get(w->pay, T * PAY_STRIDE)); RC(w->get(w->nash, T * 19));
-  RC(w->get(w->first, T * 384)); RC(w->get(w->results_out, T)); RC(w->get(w->status_out, T)); RC(w->get(w->d_teams, T * 60));
-  RC(w->get(w->frames_out, T)); RC(w->get(w->length_out, T)); RC(w->get(w->block_live, blocks)); RC(w->get(w->block_offset, blocks)); RC(w->get(w->ctl, 4));
-  RC(w->get(w->d_seeds, 2 * T)); RC(w->get(w->offsets, T + 1));
+  RC(d.get(w->tree_seed, T)); RC(d.get(w->out_block, OUT_BYTES * T + 16 * 16)); RC(d.get(w->pay, T * PAY_STRIDE)); RC(d.get(w->nash, T * 19));
+  RC(d.get(w->first, T * 384)); RC(d.get(w->results_out, T)); RC(d.get(w->status_out, T)); RC(d.get(w->d_teams, T * 60));
+  RC(d.get(w->frames_out, T)); RC(d.get(w->length_out, T)); RC(d.get(w->block_live, blocks)); RC(d.get(w->block_offset, blocks)); RC(d.get(w->ctl, 4));
+  RC(d.get(w->d_seeds, 2 * T)); RC(d.get(w->offsets, T + 1));
   w->capacity = n;
   return 0;
 }
@@ -324,15 +296,8 @@ int oakgpu_forest_selfplay_check(uint32_t max_trees, uint32_t max_iterations, in
   if (prm->keep_node != 0 && !(contextual & OAKGPU_FOREST_KEPT))
     return oakgpu_fail_msg("oakgpu_forest_selfplay: keep_node is not supported on this forest (every turn searches a fresh tree): oakgpu_forest_create_kept makes one that keeps its trees");
   contextual &= ~OAKGPU_FOREST_KEPT;
-  oak_pick::PolicyMode mode;
-  const int bad = oak_pick::parse_policy_mode(prm->policy_mode, sizeof prm->policy_mode, &mode);
-  if (bad == 'b') return oakgpu_fail_msg("oakgpu_forest_selfplay: policy mode 'b' (beta) is not supported (util/policy.h:59-60 throws)");
-  if (bad > 0) return fail_fmt("oakgpu_forest_selfplay: unknown policy mode letter '%c' (words are e / n / x / p with optional weights, util/policy.h:22-98)", (unsigned)bad);
-  if (bad < 0) return oakgpu_fail_msg("oakgpu_forest_selfplay: more than 8 policy mode words");
-  if (!(prm->policy_min <= 1.0)) return oakgpu_fail_msg("oakgpu_forest_selfplay: RuntimePolicy: zero policy (policy_min above 1 zeroes every policy)");
-  if (!solve_nash)
-    for (uint32_t q = 0; q < mode.count; ++q)
-      if (mode.word[q].kind == oak_pick::W_NASH) return oakgpu_fail_msg("oakgpu_forest_selfplay: policy mode word 'n' needs solve_nash (the nash strategies are not computed)");
+  const std::string refusal = policy_refusal(prm->policy_mode, sizeof prm->policy_mode, prm->policy_min, solve_nash);
+  if (!refusal.empty()) return oakgpu_fail_msg(("oakgpu_forest_selfplay: " + refusal).c_str());
   if (int rc = oakgpu_forest_check(max_trees, max_iterations, contextual, &prm->search, has_net, n, nullptr, 0, 0)) {
     std::string msg = oakgpu_last_error();
     const std::string from = "oakgpu_forest_search:";
@@ -401,9 +366,8 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
     HIPCHK(hipGetLastError());
   }
   if (!w->log) {
-    const size_t want = std::max<size_t>((size_t)n * 16, 4096);
-    RC(dev_alloc(w->log, want));
-    w->log_capacity = want;
+    RC(dev_alloc(w->log, first_log_capacity(n)));
+    w->log_capacity = first_log_capacity(n);
   }
   oakgpu_forest_outputs o;
   size_t entries = 0;
@@ -413,7 +377,7 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
     const RetireArgs ra{w->half[cur], w->results_out, w->status_out, w->frames_out, w->length_out, w->block_live, rows, max_len,
                         keep ? w->kept_out : nullptr, keep ? w->mism_out : nullptr, keep ? w->carry_out : nullptr};
     hipLaunchKernelGGL(k_fsp_retire, grid(rows), dim3(BLOCK), 0, stream, ra);
-    hipLaunchKernelGGL(k_fsp_offsets, dim3(1), dim3(1024), 0, stream, w->block_live, blocks, w->block_offset, w->ctl);
+    hipLaunchKernelGGL(k_rows_offsets, dim3(1), dim3(1024), 0, stream, w->block_live, blocks, w->block_offset, w->ctl);
     const bool advance = keep && turn > 0; // the first turn's trees are new
     const CompactArgs ca{w->half[cur], w->half[cur ^ 1], w->block_offset, w->tree_seed, rows, advance ? w->src_row : nullptr, w->adv_i, w->adv_j, w->adv_obs, keep ? 1 : 0};
     hipLaunchKernelGGL(k_fsp_compact, grid(rows), dim3(BLOCK), 0, stream, ca);
@@ -435,12 +399,7 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
     w->stats[1] += rows;
     if (entries + rows > w->log_capacity) { // the log follows the frames played: doubled between turns
       const size_t want = std::max(w->log_capacity * 2, entries + rows);
-      LogEntry *bigger = nullptr;
-      RC(dev_alloc(bigger, want));
-      HIPCHK(hipMemcpyAsync(bigger, w->log, entries * sizeof(LogEntry), hipMemcpyDeviceToDevice, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      (void)hipFree(w->log);
-      w->log = bigger;
+      RC(grow_log(w->log, entries, want, stream));
       w->log_capacity = want;
     }
     carve_outputs(w->out_block, rows, &o);
@@ -450,18 +409,9 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
     } else RC(oakgpu_forest_search_dev(f, net, &sp, r.battles, r.durations, r.results, w->tree_seed, rows, &o, nullptr, 0));
     double *d_p1 = nullptr, *d_p2 = nullptr, *d_nv = nullptr;
     if (solve_nash) {
-      const PayoffArgs pa{o.m, o.n, o.visit_matrix, o.value_matrix, w->pay, rows};
-      hipLaunchKernelGGL(k_fsp_payoffs, grid(rows), dim3(BLOCK), 0, stream, pa);
-      HIPCHK(hipGetLastError());
-      if (solve_nash == 2) RC(oakgpu_nash_solve_dev(ctx, w->pay, rows, w->nash)); // on the stream: nothing leaves the device
-      else {
-        w->h_pay.resize((size_t)rows * PAY_STRIDE);
-        w->h_nash.resize((size_t)rows * 19);
-        HIPCHK(hipMemcpyAsync(w->h_pay.data(), w->pay, w->h_pay.size() * 4, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        solve_rows(w->h_pay.data(), rows, w->h_nash.data());
-        HIPCHK(hipMemcpyAsync(w->nash, w->h_nash.data(), w->h_nash.size() * 8, hipMemcpyHostToDevice, stream));
-        w->loop_syncs += 2; // (this one and the one after the update)
+      RC(solve_turn(ctx, stream, solve_nash, o, rows, w->pay, w->nash, w->h_pay, w->h_nash));
+      if (solve_nash == 1) { // the host solve: the download and the upload, its synchronisation and the one after the update
+        w->loop_syncs += 2;
         w->loop_copies += 2;
       }
       d_p1 = w->nash; d_p2 = w->nash + (size_t)rows * 9; d_nv = w->nash + (size_t)rows * 18;
@@ -480,23 +430,11 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
   }
 
   // pack: record bases in game order, the headers, the log's updates
-  hipLaunchKernelGGL(k_fsp_lengths, dim3(1), dim3(1024), 0, stream, w->length_out, n, w->offsets);
-  HIPCHK(hipGetLastError());
-  unsigned long long total = 0;
-  HIPCHK(hipMemcpyAsync(&total, w->offsets + n, 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  if (total > w->stream_capacity) {
-    if (w->stream) (void)hipFree(w->stream);
-    w->stream = nullptr; w->stream_capacity = 0;
-    RC(dev_alloc(w->stream, (size_t)total));
-    w->stream_capacity = (size_t)total;
-  }
+  size_t total = 0;
+  RC(record_bases(stream, w->length_out, n, w->offsets, &w->stream, 1, &w->stream_capacity, &total));
   if (total) {
-    const PackArgs pa{w->offsets, w->frames_out, w->length_out, w->results_out, w->status_out, w->first, w->log, w->stream, n, (uint32_t)entries};
     if (entries > 0xFFFFFFFFull) return oakgpu_fail_msg("oakgpu_forest_selfplay: more than 2^32 frames in one call");
-    hipLaunchKernelGGL(k_fsp_pack_head, dim3((n + BLOCK / 64 - 1) / (BLOCK / 64)), dim3(BLOCK), 0, stream, pa);
-    if (entries) hipLaunchKernelGGL(k_fsp_pack_log, dim3((uint32_t)((entries + BLOCK / 16 - 1) / (BLOCK / 16))), dim3(BLOCK), 0, stream, pa);
-    HIPCHK(hipGetLastError());
+    RC(pack_records(stream, PackArgs{w->offsets, w->frames_out, w->length_out, w->results_out, w->status_out, w->first, w->log, w->stream, n, (uint32_t)entries}));
   }
   HIPCHK(hipStreamSynchronize(stream));
   if (keep) { // the per-game counts, read once: the call's totals
@@ -548,20 +486,8 @@ int oakgpu_forest_selfplay_records(oakgpu_forest *f, uint8_t *stream_out, size_t
   if (stream_out && capacity < w->stream_bytes) return oakgpu_fail_msg("oakgpu_forest_selfplay_records: buffer too small");
   oakgpu_ctx *ctx = oakgpu_forest_ctx(f);
   RC(oakgpu_ctx_enter(ctx));
-  hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(ctx);
-  const hipMemcpyKind kind = to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  const size_t n = w->last_n;
-  if (stream_out && w->stream_bytes) HIPCHK(hipMemcpyAsync(stream_out, w->stream, w->stream_bytes, kind, stream));
-  if (offsets) {
-    if (n) HIPCHK(hipMemcpyAsync(offsets, w->offsets, (n + 1) * 8, kind, stream));
-    else if (to_device) HIPCHK(hipMemsetAsync(offsets, 0, 8, stream));
-    else offsets[0] = 0;
-  }
-  if (n_frames && n) HIPCHK(hipMemcpyAsync(n_frames, w->frames_out, n * 4, kind, stream));
-  if (results && n) HIPCHK(hipMemcpyAsync(results, w->results_out, n, kind, stream));
-  if (status && n) HIPCHK(hipMemcpyAsync(status, w->status_out, n, kind, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  return 0;
+  const Records held{w->stream, w->stream_bytes, w->offsets, w->frames_out, w->results_out, w->status_out, w->last_n};
+  return copy_records((hipStream_t)oakgpu_ctx_stream(ctx), held, stream_out, offsets, n_frames, results, status, to_device);
 }
 
 int oakgpu_forest_selfplay(oakgpu_forest *f, oakgpu_net *net, const oakgpu_selfplay_params *prm, const uint8_t *teams, const uint64_t *battle_seeds,

@@ -40,6 +40,7 @@ namespace oak_nash {
 constexpr int MAX_PIVOTS = 100000;
 constexpr int64_t MAX_PAYOFF = 1 << 20;      // |payoff| beyond this is refused
 constexpr int64_t WIDTH4_MAX_ENTRY = 2048;   // largest shifted entry the 4-limb width takes (bound above)
+constexpr uint32_t PAY_STRIDE = 82;          // int32 words of one matrix as oakgpu_nash_solve_dev takes it: 81 payoffs + (m | n << 8)
 
 OAK_NASH_HD inline int limbs_for(int64_t max_shifted_entry) { return max_shifted_entry <= WIDTH4_MAX_ENTRY ? 4 : 8; }
 

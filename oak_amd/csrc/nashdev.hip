@@ -30,7 +30,7 @@ namespace {
 
 using oak_nash::WideT;
 using oak_nash::X87;
-constexpr uint32_t PAY_STRIDE = 82; // forest_rows.hpp: 81 payoffs + (m | n << 8)
+using oak_nash::PAY_STRIDE;
 constexpr int NASH_BLOCK = 256;
 constexpr int NO_COLUMN = 255;
 

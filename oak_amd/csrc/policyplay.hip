@@ -5,12 +5,13 @@
 //   k_policy_pick   : one lane per row: the joint choice of this turn from the two seats' rules, the row's draws, the choice log
 //   k_games_retire  : one lane per row: a finished row's outputs go to the caller's arrays by game index, the counters, the live count,
 //                     and how many rows of each block are still live
-//   k_games_offsets : one workgroup: the exclusive prefix sums of those per-block counts
+//   k_rows_offsets  : (game_rows.hpp) one workgroup: the exclusive prefix sums of those per-block counts
 //   k_games_compact : the live rows, in order, into the other half of the double buffer
-// Every kernel is a plain grid over rows (k_games_offsets: one workgroup); none waits for another block.  The turn in between is
-// oakgpu_tree_step_dev and oakgpu_leaf_eval_policy_dev over the resident rows.  A finished row is frozen -- pick draws nothing for it, the
-// tree step leaves it alone -- so it can be retired at any later turn: the host retires and reads the live count every `poll` turns only.
-// There is no CPU fallback in this library.
+// The scan, the place of a live row, the move of the battles and the count of a block's live rows are game_rows.hpp's, shared with the two
+// loops over the forest search.  Every kernel is a plain grid over rows (k_rows_offsets: one workgroup); none waits for another block.
+// The turn in between is oakgpu_tree_step_dev and oakgpu_leaf_eval_policy_dev over the resident rows.  A finished row is frozen -- pick
+// draws nothing for it, the tree step leaves it alone -- so it can be retired at any later turn: the host retires and reads the live
+// count every `poll` turns only.  There is no CPU fallback in this library.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -21,15 +22,18 @@
 
 #include "../../include/oakgpu.h"
 #include "fast_prng.hpp"
+#include "game_rows.hpp"
 #include "oakgpu_internal.h"
 
 namespace oak {
 namespace pg {
 
-constexpr uint32_t DEAD = 0xFFFFFFFFu;   // game index of a retired row
+using game_rows::BLOCK;
+using game_rows::DEAD;
+using game_rows::k_rows_offsets;
+using game_rows::NO_ROW;
+using game_rows::u32x4;
 constexpr uint32_t FLAGGED = 0xFFu;      // result byte of a game whose policy was all zero
-constexpr uint32_t NO_ROW = 0xFFFFFFFFu;
-constexpr int BLOCK = 256;
 enum : uint32_t { T_WIN = 1, T_LOSE = 2 }; // pkmn_result types (gen1_device.hpp's R_WIN / R_LOSE)
 
 // the control words: [0] live rows, [1] flagged games, [2] the lowest flagged game index; counters at byte 32
@@ -166,7 +170,6 @@ struct RetireArgs {
 
 __global__ __launch_bounds__(BLOCK) void k_games_retire(RetireArgs a) {
   __shared__ uint32_t wave_live[BLOCK / 64];
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   const uint32_t tid = threadIdx.x, row = blockIdx.x * BLOCK + tid, lane = tid & 63;
   const bool in = row < a.rows;
   const uint32_t g = in ? a.r.game[row] : DEAD;
@@ -204,65 +207,28 @@ __global__ __launch_bounds__(BLOCK) void k_games_retire(RetireArgs a) {
     const unsigned long long m = __ballot(done && cat == k);
     if (lane == 0 && m) atomicAdd(&a.ctl->counts[k], (unsigned long long)__popcll(m));
   }
-  const unsigned long long md = __ballot(done), mf = __ballot(flagged), ml = __ballot(g != DEAD && !done);
+  const unsigned long long md = __ballot(done), mf = __ballot(flagged);
   if (lane == 0) {
     if (md) atomicSub(&a.ctl->live, (uint32_t)__popcll(md));
     if (mf) atomicAdd(&a.ctl->flagged, (uint32_t)__popcll(mf));
-    wave_live[tid >> 6] = (uint32_t)__popcll(ml);
   }
-  __syncthreads();
-  if (tid == 0) a.block_live[blockIdx.x] = wave_live[0] + wave_live[1] + wave_live[2] + wave_live[3];
+  game_rows::count_block_live(g != DEAD && !done, wave_live, a.block_live);
 }
 
 // ---- compaction --------------------------------------------------------------------------------------------------------------------
-// exclusive prefix sums of the per-block live counts: one workgroup, 1,024 counts at a time (a wave scans its 64 by shuffles, the 16 wave
-// totals are scanned by every lane)
-__global__ __launch_bounds__(1024) void k_games_offsets(const uint32_t *block_live, uint32_t blocks, uint32_t *block_offset) {
-  __shared__ uint32_t wave_total[16];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  uint32_t carry = 0;
-  for (uint32_t base = 0; base < blocks; base += 1024) {
-    const uint32_t i = base + tid, own = i < blocks ? block_live[i] : 0;
-    uint32_t incl = own;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t up = __shfl_up(incl, d);
-      if ((int)lane >= d) incl += up;
-    }
-    if (lane == 63) wave_total[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < 16; ++w) { const uint32_t t = wave_total[w]; if (w < wave) before += t; all += t; }
-    if (i < blocks) block_offset[i] = carry + before + incl - own;
-    carry += all;
-    __syncthreads();
-  }
-}
-
 struct CompactArgs {
   Rows from, to;
   const uint32_t *block_offset;
   uint32_t rows;
 };
 
-// Stable: a live row's place is its block's offset + the live rows in front of it in the block (a ballot and a lane prefix within
-// the wave, the wave totals across the block).  The 384-byte battles move as whole rows, 24 lanes x 16 bytes each.
+// Stable (game_rows.hpp: compact_place, compact_battles); a live row's own fields go with it.
 __global__ __launch_bounds__(BLOCK) void k_games_compact(CompactArgs a) {
   __shared__ uint32_t wave_total[BLOCK / 64];
   __shared__ uint32_t place[BLOCK];
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  const uint32_t tid = threadIdx.x, base = blockIdx.x * BLOCK, row = base + tid, lane = tid & 63, wave = tid >> 6;
+  const uint32_t row = blockIdx.x * BLOCK + threadIdx.x;
   const bool live = row < a.rows && a.from.game[row] != DEAD;
-  const unsigned long long m = __ballot(live);
-  const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-  if (lane == 0) wave_total[wave] = (uint32_t)__popcll(m);
-  __syncthreads();
-  uint32_t before = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < BLOCK / 64; ++w) if (w < wave) before += wave_total[w];
-  const uint32_t to = live ? a.block_offset[blockIdx.x] + before + prefix : NO_ROW;
-  place[tid] = to;
+  const uint32_t to = game_rows::compact_place(live, a.block_offset[blockIdx.x], wave_total, place);
   if (live) {
     *((uint2 *)a.to.durations + to) = *((const uint2 *)a.from.durations + row);
     *((uint2 *)a.to.prng + to) = *((const uint2 *)a.from.prng + row);
@@ -273,13 +239,7 @@ __global__ __launch_bounds__(BLOCK) void k_games_compact(CompactArgs a) {
     a.to.turns[to] = a.from.turns[row];
   }
   __syncthreads();
-  const u32x4 *src = (const u32x4 *)a.from.battles + (size_t)base * 24;
-  u32x4 *dst = (u32x4 *)a.to.battles;
-#pragma unroll 4
-  for (int q = 0; q < 24; ++q) {
-    const uint32_t i = q * BLOCK + tid, b = i / 24, w = i - b * 24, t = place[b];
-    if (t != NO_ROW) dst[(size_t)t * 24 + w] = src[i];
-  }
+  game_rows::compact_battles(a.from.battles, a.to.battles, a.rows, place);
 }
 
 } // namespace pg
@@ -411,7 +371,7 @@ int oakgpu_policy_games_dev(oakgpu_ctx *c, const oakgpu_policy_games_params *par
       if (live == 0 || last) break;
       if (live < rows && compact_below >= 0.0f && (float)live / (float)rows < compact_below) {
         const uint32_t blocks = (rows + BLOCK - 1) / BLOCK;
-        hipLaunchKernelGGL(k_games_offsets, dim3(1), dim3(1024), 0, stream, w.block_live, blocks, w.block_offset);
+        hipLaunchKernelGGL(k_rows_offsets, dim3(1), dim3(1024), 0, stream, w.block_live, blocks, w.block_offset, (uint32_t *)nullptr);
         const CompactArgs ca{r, w.half[cur ^ 1], w.block_offset, rows};
         hipLaunchKernelGGL(k_games_compact, grid(rows), dim3(BLOCK), 0, stream, ca);
         cur ^= 1;
