@@ -10,7 +10,8 @@
 //                   per-battle embedding cache (nn/battle/cache.h) is oakgpu_leaf_eval_cached_dev (k_party_tags).
 //   K3  k_mainnet_wave : MainNet::propagate value path (nn/battle/main-net.h:57-64) + sigmoid, the three dense layers on
 //                   v_mfma_f32_32x32x2_f32 (exact fp32); k_policy: the policy heads (main-net.h:67-107).
-// Parameter file reader: nn/affine.h:35-70, network.h:52-70, main-net.h:36-55, search.cc:127-131.
+// Parameter file reader (net_pack.hpp: the loader's host half, file bytes -> checked and packed images): nn/affine.h:35-70,
+// network.h:52-70, main-net.h:36-55, search.cc:127-131.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -25,6 +26,7 @@
 #include "../../include/oakgpu.h"
 #include "oakgpu_internal.h"
 #include "encode_index.hpp"
+#include "net_layout.hpp"
 #include "party_key.hpp"
 
 namespace oak {
@@ -44,11 +46,11 @@ struct NetDev {
   const float *w0g, *w1g, *w2g; // the three weight matrices in k_mainnet_wave's MFMA-fragment order (frag_order_wave)
   float b3;
   int H, VH; // padded dims
-  // k_mainnet_split: the three matrices as ONE stream of bf16 triples in its MFMA-fragment order (split_stream), the k-steps
+  // k_mainnet_split: the three matrices as ONE stream of bf16 triples in its MFMA-fragment order (net_pack.hpp: main_stream<3>), the k-steps
   // of fc0 (ws_T0, a multiple of 4), the block count both widths are padded to (ws_NB: 1, 2, 4, 8)
   const uint16_t *ws;
   int ws_T0, ws_NB;
-  // k_mainnet_pair: the same stream as scaled fp16 pairs (pair_stream), and 1 / the scale of each of the three layers
+  // k_mainnet_pair: the same stream as scaled fp16 pairs (net_pack.hpp: main_stream<2>), and 1 / the scale of each of the three layers
   const uint16_t *wp;
   const float *wp_inv;        // 1 / the scale of every output row: [fc0: H | fc1: H | value_fc2: VH] (padded rows: 0)
   // policy heads (main-net.h:67-107): fc2 [PHp][H] (rows padded to 32), fc3 [315][PHp] (+ biases)
@@ -512,21 +514,21 @@ __global__ __launch_bounds__(EL_BLOCK) void k_embed_lds(EmbedTileArgs a) {
   EL_FLUSH();
 }
 
-constexpr int ER_ITEMS = 32, ER_RS = 128; // items per wave mini-tile; LDS weight row (floats) of k_embed_arows / k_embed_prows (a half-wave
-                                          // reads a whole row per instruction: contiguous, conflict-free at any stride -- no padding)
+constexpr int ER_ITEMS = 32; // items per wave mini-tile (the LDS weight row, ER_RS floats: net_layout.hpp)
 
 // ---- the embedding nets' SECOND layers on the bf16 matrix pipe (round 4) ----
 // Rounds 2-3 ran them on v_mfma_f32_32x32x2_f32: 128 (party) / 192 (actives) MFMAs of 64 cycles per 32-item mini-tile, 8.2 k of a
 // party mini-tile's 13.1 k matrix-pipe cycles.  The bf16 pipe is 16x faster per FLOP, and an fp32 value is the exact sum of three
 // bf16 parts (h, m, l), so, as in k_mainnet_split:
-//   second layer : the 128 hidden activations of an item as triples against W1's triples (LDS, prebuilt), the six largest partial
-//                  products per 32x32x16 block, fp32 accumulation: 8 k-steps x 6 x NBo MFMAs of 32 cycles (party 96: 3.1 k cycles
-//                  against 8.2 k) -- fp32 results (dropped terms < 2^-24 of a product);
+//   second layer : (round 4; scaled fp16 pairs since round 5, below and at embed_layer2) the 128 hidden activations of an item as
+//                  triples against W1's triples (LDS, prebuilt), the six largest partial products per 32x32x16 block, fp32
+//                  accumulation: 8 k-steps x 6 x NBo MFMAs of 32 cycles (party 96: 3.1 k cycles against 8.2 k) -- fp32 results
+//                  (dropped terms < 2^-24 of a product);
 //   transposition: on the bf16 pipe too (SelTranspose below: the one-hot selector is exact in bf16; twelve MFMAs move the (h, m, l)
 //                  parts of four k-steps' row sums into the item lanes).  A first attempt with the round-to-nearest split cost
 //                  ~1,000 more vector instructions per mini-tile and lost; with the truncation split it is 352, and the fp32
 //                  MFMAs it replaces turned out to hold the vector issue for their whole 64 cycles.
-// ---- fp32 values as SCALED fp16 PAIRS (round 5; the full argument is at k_mainnet_pair): x s = h + l to 2^-24 with h = fp16(x s), l =
+// ---- fp32 values as SCALED fp16 PAIRS (round 5; the full argument is at k_mainnet_pair): x s = h + l to 2^-23 with h = fp16(x s), l =
 // fp16(x s - h), s a power of two that takes the largest value of the row (weights: of the layer) into [2^14, 2^15) ----
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 // the power of two that takes m (> 0: callers floor it) into [2^14, 2^15), and the exact ratio of two such scales
@@ -839,8 +841,8 @@ __device__ __forceinline__ void zero_blocks(float *emb, uint32_t dead_off, int l
 // activation tile, no workgroup barrier per tile, every wave on the MFMA; the kernel fits 128 registers so that a CU holds
 // ONE 16-wave workgroup (4 waves per SIMD).  LDS: 65 x 528 B rows + 18 KB dense fragment + <= 64 KB W1 fragments + 1.4 KB
 // per wave (row indices) = <= 141 KB, staged from one prebuilt image (stage_image_dma).
-constexpr int AR_SPARSE = 64, AR_ZERO = 64;   // LDS-resident one-hot rows (ar_sparse_slot) + a zero row
-constexpr int AR_FIXED = 36, AR_HOT = 9, AR_MOVES = 8, AR_KT = (AR_FIXED + 7) / 8; // (dense features in k-steps of eight)
+constexpr int AR_ZERO = AR_SPARSE;            // the zero row behind the LDS-resident one-hot rows (AR_SPARSE, AR_FIXED, AR_KT: net_layout.hpp)
+constexpr int AR_HOT = 9, AR_MOVES = 8;
 constexpr int AR_ITEM_WORDS = 20;               // ready to use: 9 LDS byte offsets of the item's one-hot rows, 8 byte offsets of its move rows in L2 (+ 3 pad)
 constexpr int AR_WAVE_WORDS = ER_ITEMS * AR_ITEM_WORDS;
 #ifndef OAK_EMBED_WAVES
@@ -850,18 +852,12 @@ constexpr int AR_WAVE_WORDS = ER_ITEMS * AR_ITEM_WORDS;
 // 128 registers spill 150-400 of them (party pass 633 us), 12 of 168 spill 60-130 (246 us), 8 of 256 none (140 us).
 constexpr int AR_WAVES = OAK_EMBED_WAVES, AR_BLOCK = 64 * AR_WAVES;
 constexpr int AR_DENSE_WORDS = AR_KT * 4 * 3 * 64 * 2; // the dense weights' triples: [k-step][channel block][h m l][lane] x 8 B (dense_layer_bf16)
-constexpr int AR_COMBINED = 428; // first precombined (active + stored) move row of a_w0d: behind W0^T's 427 rows and the zero row
 constexpr int AR_MAX_NBO = 3; // W1's image (scaled fp16 pairs in the 3 x 1 KB per k-step the bf16 triples had: embed_pair_order): 24 KB per 32-wide output block; four blocks (outputs above 96) do not fit beside the rest
 constexpr size_t ar_bytes(int nbo) { return (size_t)((AR_SPARSE + 1) * ER_RS + AR_DENSE_WORDS + AR_WAVES * AR_WAVE_WORDS + 64 * nbo) * 4 + (size_t)nbo * E2_BLOCK_BYTES; }
-// channel held by register s (0..63) of a lane in half hh: the C layout of four 32x32 MFMA blocks, block b's row i being
-// channel 4 i + b (so that a lane's float4 of a weight row feeds the four blocks)
-__host__ __device__ constexpr int ar_channel(int s, int hh) { return 4 * ((s & 3) + 8 * ((s & 15) >> 2) + 4 * hh) + (s >> 4); }
-// W0^T row of dense feature d (1..35; 0 is the bias): active stats, boosts, volatiles, the stored Pokemon's stats
-__host__ __device__ constexpr int ar_dense_row(int d) { return d < 6 ? d - 1 : d < 12 ? 20 + (d - 6) : d < 31 ? 26 + (d - 12) : 229 + (d - 31); }
-// compact LDS slot of a one-hot row (types 5..19, rows 209..228, rows 398..426) and back
+// (ar_channel, ar_dense_row, ar_sparse_row: net_layout.hpp)
+// compact LDS slot of a one-hot row (types 5..19, rows 209..228, rows 398..426); back: ar_sparse_row
 __device__ __forceinline__ uint32_t ar_sparse_slot(uint32_t row) { return row < 20 ? row - 5 : row < 229 ? row - 209 + 15 : row - 398 + 35; }
-__host__ __device__ constexpr int ar_sparse_row(int slot) { return slot < 15 ? slot + 5 : slot < 35 ? slot - 15 + 209 : slot - 35 + 398; }
-// bias (padded to 32 NBo floats) behind W1's triples in both images: embed_scatter reads it from LDS
+// bias (padded to 32 NBo floats) behind W1's scaled fp16 pairs in both images: embed_scatter reads it from LDS
 constexpr int ar_img_words(int nbo) { return (AR_SPARSE + 1) * ER_RS + AR_DENSE_WORDS + nbo * (E2_BLOCK_BYTES / 4) + 64 * nbo; } // (... + b1 + 1 / W1's row scales)
 template <int WAVES, int NBO>
 __device__ __forceinline__ void embed_arows_body(const EmbedTileArgs &a, float *lds_f, const uint32_t bid, const uint32_t nblocks) {
@@ -1113,7 +1109,7 @@ __global__ __launch_bounds__(AR_BLOCK) void k_embed_arows(EmbedTileArgs a) {
 // row at the same column), and selector MFMAs transpose the sums into the item lanes.  Second layer (<= 2 output
 // blocks) with W1's scaled fp16 pairs from LDS (embed_layer2).  The input is read straight from global memory (the encode of a
 // Pokemon is 12 features; no staging).  LDS: 194 x 512 B rows + 3 KB dense fragment + 48 KB W1 image + bias + 512 B per wave.
-constexpr int PR_SPARSE = 193, PR_ZERO = 193, PR_KT = 1, PR_HOT = 7; // (6 dense features: one k-step of eight)
+constexpr int PR_ZERO = PR_SPARSE, PR_HOT = 7; // (PR_SPARSE, PR_KT: net_layout.hpp)
 constexpr int PR_ITEM_WORDS = 8;                 // 7 LDS byte offsets of the item's one-hot rows, ready to use (+ 1 pad: two 16-byte reads)
 constexpr int PR_WAVE_WORDS = ER_ITEMS * PR_ITEM_WORDS;
 constexpr int PR_WAVES = OAK_EMBED_WAVES, PR_BLOCK = 64 * PR_WAVES;
@@ -1554,7 +1550,6 @@ __global__ __launch_bounds__(256) void k_party_lookup(PartyLookupArgs a) {
 
 // ---- K3: main net on fp32 MFMA ------------------------------------------------------------------
 constexpr int MN_BLOCK = 256; // 4 waves
-constexpr int MAXH = 256;
 
 struct MainArgs {
   NetDev net;
@@ -1767,7 +1762,7 @@ __global__ __launch_bounds__(MN_BLOCK) void k_mainnet_wave(MainArgs a) {
 // lane -- which is exactly the B-operand layout of the next layer summing over those features (cdna_hip_programming.md, "an
 // accumulator tile as the next MFMA's operand"): activations never leave the registers, there is no LDS tile and no
 // transposition.  The k-order this implies (k-step t of fc1 / value_fc2 = registers 8 (t & 1) .. + 7 of block t >> 1 =
-// features 32 (t >> 1) + (reg & 3) + 8 (reg >> 2) + 4 h) is baked into the weight stream on the host (split_stream).
+// features 32 (t >> 1) + (reg & 3) + 8 (reg >> 2) + 4 h) is baked into the weight stream on the host (net_pack.hpp: main_stream<3>).
 //
 // One workgroup = 4 waves = 4 x 32 batch rows sharing ONE pass over the weight stream through a two-buffer LDS ring (a phase
 // = MS_G k-steps = NB x 6 KB): while the phase-p MFMAs run, phase p + 1 arrives in the other buffer by LDS-DMA (every wave
@@ -2058,19 +2053,20 @@ __global__ __launch_bounds__(MN_BLOCK) void k_mainnet_split(MainArgs a) {
 
 // ---- K3'': the main net on the fp16 matrix pipe, fp32 values carried as scaled fp16 PAIRS (round 5) ------------------------
 // k_mainnet_split pays six bf16 MFMAs per fp32 multiply-add block because a bf16 part holds 8 significant bits.  An fp16 part
-// holds 11, so TWO round-to-nearest parts carry an fp32 value to 2^-24: x s = h + l + e with h = fp16(x s), l = fp16(x s - h) (that
-// remainder is exact in fp32) and |e| <= 2^-12 |l| <= 2^-24 |x s|.  A product is then h.h + h.l + l.h (three MFMAs of the same
-// rate, each product exact in the fp32 accumulator) and drops l.l <= 2^-24 |x w| -- the error class of the triple form at half
-// the matrix work.  What fp16 lacks is RANGE (5 exponent bits), so every operand is multiplied by an exact power of two first:
+// holds 11, so TWO round-to-nearest parts carry an fp32 value to 2^-23: x s = h + l + e with h = fp16(x s), l = fp16(x s - h) (that
+// remainder is exact in fp32), |l| <= 2^-11 |x s| and |e| <= 2^-12 |l| <= 2^-23 |x s|.  A product is then h.h + h.l + l.h (three
+// MFMAs of the same rate, each product exact in the fp32 accumulator) and drops l.l <= 2^-22 |x w| in the worst case (~2^-27
+// typically): up to about four fp32 roundoffs per product, where the triple form drops < 2^-24 -- that the results stay at fp32's
+// level is measured (tests/test_gpu_mainnet.py), not bounded -- at half the matrix work.  What fp16 lacks is RANGE (5 exponent bits), so every operand is multiplied by an exact power of two first:
 //   * weights: one scale per ROW (= output feature), chosen on the host so that the row's largest weight lands in [2^14, 2^15)
-//     (pair_stream); the accumulators are scaled back per feature, next to the bias;
+//     (net_pack.hpp: main_stream<2>); the accumulators are scaled back per feature, next to the bias;
 //   * activations: one scale PER BATCH ROW (= per lane: the row's values of a layer sit in that lane's registers and its partner
 //     lane's), so that the row's largest value lands in [2^14, 2^15).  For fc1 / value_fc2 the row maximum is read off the
 //     accumulators; for fc0 the row arrives from memory 64 columns at a time, the scale is set from the first chunk and LOWERED
 //     when a later chunk holds a larger value -- the accumulators are then multiplied by the (exact) ratio, like an online softmax.
 // Accumulators are scaled back (two exact power-of-two factors) in front of the bias.  A part below 2^-14 of the scaled unit is an
 // fp16 SUBNORMAL, which both v_cvt_f16_f32 and the fp16 MFMA honour on gfx950 (tools/experiments/mfma_f16_denorm.hip, run on the
-// chip), so a value's absolute error is at most max(2^-24 |x|, 2^-39 x the row's / the layer's largest): the product is accurate
+// chip), so a value's absolute error is at most max(2^-23 |x|, 2^-39 x the row's / the layer's largest): the product is accurate
 // normwise like the fp32 multiply-add it replaces whenever a row's sum is not 2^13 times smaller than its largest term --
 // oakgpu_net_load* CHECKS the weight side of that (pair_layer_ok: rows and columns) and keeps a network that fails it on the bf16 triples.
 // Everything else -- orientation, the LDS-DMA ring, the software pipeline -- is k_mainnet_split's; a phase is MPair::G k-steps of
@@ -2544,6 +2540,7 @@ __global__ __launch_bounds__(PolicyRows<PB>::BLOCK) void k_policy_rows(PolicyArg
 } // namespace oak
 
 #include "mainnet_i8.hpp"
+#include "net_pack.hpp"
 
 // =================================== C ABI =====================================================
 struct oakgpu_net {
@@ -2554,6 +2551,7 @@ struct oakgpu_net {
   int in_dim, hidden, value_hidden, policy_hidden; // unpadded, as in the file
   int device;        // the device the weights live on
   int main_mode;     // which kernel runs the main net: 0 = k_mainnet_wave (fp32 MFMA), 1 = k_mainnet_split (bf16 triples), 2 = k_mainnet_pair (fp16 pairs)
+  // the three flags below are pack_net's (net_pack.hpp, where the reasons are written out)
   bool pair_safe;    // every main-net layer passes pair_layer_ok (rows keep fp32 accuracy as scaled fp16 pairs, no dwarfed column): k_mainnet_pair may run
   bool split_safe;   // no main-net weight above 2^20 in magnitude: what a flushed low bf16 part loses cannot be amplified back (else fp32 MFMA only)
   bool embed_safe;   // ... and none in the embedding nets' second layers either, which also pass pair_layer_ok: the row kernels' bf16 triples (first layer's dense part) and scaled fp16 pairs (second layer) are safe (else k_embed_lds: fp32 MFMA)
@@ -2562,435 +2560,35 @@ struct oakgpu_net {
 };
 
 namespace {
-struct HostAffine { uint32_t in, out; std::vector<float> b, w; };
-
-bool read_affine(const uint8_t *&p, const uint8_t *end, HostAffine &a) {
-  if (end - p < 8) return false;
-  memcpy(&a.in, p, 4);
-  memcpy(&a.out, p + 4, 4);
-  p += 8;
-  if (a.in == 0 || a.out == 0 || a.in > (1u << 16) || a.out > (1u << 16)) return false;
-  const size_t nb = (size_t)a.out * 4, nw = (size_t)a.out * a.in * 4;
-  if ((size_t)(end - p) < nb + nw) return false;
-  a.b.resize(a.out);
-  a.w.resize((size_t)a.out * a.in);
-  memcpy(a.b.data(), p, nb);
-  p += nb;
-  memcpy(a.w.data(), p, nw);
-  p += nw;
-  return true;
-}
-
-int upload(oakgpu_net *net, const std::vector<float> &h, const float **out) {
+// one device allocation per image of the packed network (net_pack.hpp), freed with the network
+int upload(oakgpu_net *net, const void *data, size_t bytes, void **out) {
   void *d = nullptr;
-  hipError_t e = hipMalloc(&d, h.size() * 4);
+  hipError_t e = hipMalloc(&d, bytes);
   if (e != hipSuccess) return oakgpu_fail_hip((int)e, "hipMalloc(net)");
   net->allocs.push_back(d);
-  e = hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice);
+  e = hipMemcpy(d, data, bytes, hipMemcpyHostToDevice);
   if (e != hipSuccess) return oakgpu_fail_hip((int)e, "hipMemcpy(net)");
-  *out = (const float *)d;
+  *out = d;
   return 0;
 }
-
-std::vector<float> transpose(const HostAffine &a) { // W[out][in] -> Wt[in][out]
-  std::vector<float> t((size_t)a.in * a.out);
-  for (uint32_t o = 0; o < a.out; ++o)
-    for (uint32_t i = 0; i < a.in; ++i) t[(size_t)i * a.out + o] = a.w[(size_t)o * a.in + i];
-  return t;
+// the NetDev / QNetDev field an image of that name feeds
+bool set_field(oakgpu_net *net, const char *name, void *d) {
+  oak::NetDev &D = net->dev;
+  oak::QNetDev &Q = net->q;
+#define OAK_FIELD(S, prefix, f) if (!strcmp(name, prefix #f)) { S.f = (std::remove_reference_t<decltype(S.f)>)d; return true; }
+#define OAK_D(f) OAK_FIELD(D, "", f)
+#define OAK_Q(f) OAK_FIELD(Q, "q.", f)
+  OAK_D(p_w0t) OAK_D(p_b0) OAK_D(p_w1) OAK_D(a_w1) OAK_D(p_b1) OAK_D(a_w0t) OAK_D(a_b0) OAK_D(a_b1) OAK_D(a_w0d) OAK_D(a_img) OAK_D(p_img)
+  OAK_D(b0) OAK_D(b1) OAK_D(b2) OAK_D(w3) OAK_D(w0g) OAK_D(w1g) OAK_D(w2g) OAK_D(ws) OAK_D(wp_inv) OAK_D(wp)
+  OAK_D(q1a) OAK_D(q1a_b) OAK_D(q1b) OAK_D(q1b_b) OAK_D(q2a) OAK_D(q2a_b) OAK_D(q2b) OAK_D(q2b_b)
+  OAK_D(q1a_f) OAK_D(q2a_f) OAK_D(q1b_img) OAK_D(q2b_img) OAK_D(q1a_t) OAK_D(q2a_t)
+  OAK_Q(img) OAK_Q(b0) OAK_Q(b1) OAK_Q(b2) OAK_Q(w3)
+  OAK_Q(pw2[0]) OAK_Q(pb2[0]) OAK_Q(pw3[0]) OAK_Q(pb3[0]) OAK_Q(pw2[1]) OAK_Q(pb2[1]) OAK_Q(pw3[1]) OAK_Q(pb3[1])
+#undef OAK_Q
+#undef OAK_D
+#undef OAK_FIELD
+  return false;
 }
-// pad rows (out) to a multiple of 32 and columns (in) to `in_pad` with zeros
-std::vector<float> pad_rows(const HostAffine &a, uint32_t out_pad, uint32_t in_pad) {
-  std::vector<float> t((size_t)out_pad * in_pad, 0.0f);
-  for (uint32_t o = 0; o < a.out; ++o)
-    for (uint32_t i = 0; i < a.in; ++i) t[(size_t)o * in_pad + i] = a.w[(size_t)o * a.in + i];
-  return t;
-}
-// k_mainnet_wave's MFMA-fragment order of a weight matrix: the 2 float4 x NB n-blocks of one SUB-chunk (8 k-steps) are contiguous:
-// float4 (((c*4 + u)*NB + nb)*2 + qq)*64 + lane -> W[nb*32 + r][c*64 + h*32 + 8u + 4qq .. +3], so the 16 loads of a sub-chunk
-// are one scalar base + the lane's offset + small constants (no per-block vector address arithmetic).  NB is rounded up to
-// the kernel's template width (1, 2, 4, 8) with all-zero blocks, so that every block index is a compile-time constant.
-std::vector<float> frag_order_wave(const HostAffine &a, uint32_t out_pad) {
-  const uint32_t nch = (a.in + 63) / 64, nb_real = out_pad / 32;
-  const uint32_t NB = nb_real > 4 ? 8 : nb_real > 2 ? 4 : nb_real; // the kernel's block count (wave_layer_nb): absent blocks are zeros
-  std::vector<float> f((size_t)nch * NB * 8 * 64 * 4, 0.0f);
-  for (uint32_t c = 0; c < nch; ++c)
-    for (uint32_t u = 0; u < 4; ++u)
-      for (uint32_t nb = 0; nb < NB; ++nb)
-        for (uint32_t qq = 0; qq < 2; ++qq)
-          for (uint32_t lane = 0; lane < 64; ++lane)
-            for (uint32_t e = 0; e < 4; ++e) {
-              const uint32_t row = nb * 32 + (lane & 31), col = c * 64 + (lane >> 5) * 32 + 8 * u + 4 * qq + e;
-              if (row < a.out && col < a.in) f[(((((size_t)c * 4 + u) * NB + nb) * 2 + qq) * 64 + lane) * 4 + e] = a.w[(size_t)row * a.in + col];
-            }
-  return f;
-}
-
-// k_mainnet_split's weight stream: fc0, fc1, value_fc2 back to back, every weight as the bf16 triple (h, m, l), in the order
-// the kernel's LDS ring is read: byte (((t * NB + nb) * 3 + part) * 64 + lane) * 16 + 2 j = part of W[32 nb + (lane & 31)][k],
-// k = 16 t + 8 h + j for fc0 (h = lane >> 5) and 32 (t >> 1) + (reg & 3) + 8 (reg >> 2) + 4 h, reg = 8 (t & 1) + j, for the two
-// layers whose input is the previous layer's accumulators.  Absent rows / columns are zeros.
-uint16_t f32_to_bf16(float f) { // round to nearest even (weights are finite; a NaN stays a NaN)
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40);
-  return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-float bf16_to_f32(uint16_t b) { const uint32_t u = (uint32_t)b << 16; float f; memcpy(&f, &u, 4); return f; }
-std::vector<uint16_t> split_stream(const HostAffine &fc0, const HostAffine &fc1, const HostAffine &v2, uint32_t NB, uint32_t T0) {
-  const uint32_t steps = T0 + 4 * NB;
-  std::vector<uint16_t> w((size_t)steps * NB * 3 * 64 * 8, 0);
-  auto put = [&](uint32_t t_flat, const HostAffine &a, uint32_t nb, uint32_t lane, uint32_t j, uint32_t k) {
-    const uint32_t n = 32 * nb + (lane & 31);
-    if (n >= a.out || k >= a.in) return;
-    const float x = a.w[(size_t)n * a.in + k];
-    const uint16_t hh = f32_to_bf16(x);
-    const float r1 = x - bf16_to_f32(hh);
-    const uint16_t mm = f32_to_bf16(r1);
-    const uint16_t ll = f32_to_bf16(r1 - bf16_to_f32(mm));
-    const size_t base = ((size_t)t_flat * NB + nb) * 3;
-    w[((base + 0) * 64 + lane) * 8 + j] = hh;
-    w[((base + 1) * 64 + lane) * 8 + j] = mm;
-    w[((base + 2) * 64 + lane) * 8 + j] = ll;
-  };
-  for (uint32_t nb = 0; nb < NB; ++nb)
-    for (uint32_t lane = 0; lane < 64; ++lane)
-      for (uint32_t j = 0; j < 8; ++j) {
-        const uint32_t hb = lane >> 5;
-        for (uint32_t t = 0; t < T0; ++t) put(t, fc0, nb, lane, j, 16 * t + 8 * hb + j);
-        for (uint32_t t = 0; t < 2 * NB; ++t) {
-          const uint32_t reg = 8 * (t & 1) + j, k = 32 * (t >> 1) + (reg & 3) + 8 * (reg >> 2) + 4 * hb;
-          put(T0 + t, fc1, nb, lane, j, k);
-          put(T0 + 2 * NB + t, v2, nb, lane, j, k);
-        }
-      }
-  return w;
-}
-
-// k_mainnet_pair's weight stream: the same order with TWO parts per weight, (h, l) = the fp16 pair of w x scale, scale = the power
-// of two that takes the largest |w| of the weight's ROW (= output feature) into [2^14, 2^15) (1 for an all-zero row): byte
-// (((t * NB + nb) * 2 + part) * 64 + lane) * 16 + 2 j.  inv = 1 / scale of every row: [fc0: Hp | fc1: Hp | value_fc2: VHp] (padded rows: 0).
-uint16_t f16_bits(_Float16 v) { uint16_t b; memcpy(&b, &v, 2); return b; }
-float pair_scale_of(float m) { // the power of two that takes m into [2^14, 2^15); 1 for m = 0
-  if (!(m > 0.0f) || !std::isfinite(m)) return 1.0f;
-  int e;
-  std::frexp(m, &e); // m = f x 2^e, f in [0.5, 1): m in [2^(e-1), 2^e)
-  e = 15 - e;        // (kept inside 2^+-100: the scale, its inverse and their products with a batch row's scale stay normal fp32 numbers;
-  return std::ldexp(1.0f, e > 100 ? 100 : e < -100 ? -100 : e); // a row beyond that fails pair_layer_ok or saturates like fp32 does)
-}
-float row_pair_scale(const HostAffine &a, uint32_t n) {
-  float m = 0.0f;
-  for (uint32_t k = 0; k < a.in; ++k) m = std::fmax(m, std::fabs(a.w[(size_t)n * a.in + k]));
-  return pair_scale_of(m);
-}
-std::vector<uint16_t> pair_stream(const HostAffine &fc0, const HostAffine &fc1, const HostAffine &v2, uint32_t NB, uint32_t T0, uint32_t Hp, uint32_t VHp,
-                                  std::vector<float> &inv) {
-  const uint32_t steps = T0 + 4 * NB;
-  std::vector<uint16_t> w((size_t)steps * NB * 2 * 64 * 8, 0);
-  inv.assign((size_t)2 * Hp + VHp, 0.0f);
-  std::vector<float> sc0(fc0.out), sc1(fc1.out), sc2(v2.out);
-  for (uint32_t n = 0; n < fc0.out; ++n) { sc0[n] = row_pair_scale(fc0, n); inv[n] = 1.0f / sc0[n]; }
-  for (uint32_t n = 0; n < fc1.out; ++n) { sc1[n] = row_pair_scale(fc1, n); inv[Hp + n] = 1.0f / sc1[n]; }
-  for (uint32_t n = 0; n < v2.out; ++n) { sc2[n] = row_pair_scale(v2, n); inv[2 * (size_t)Hp + n] = 1.0f / sc2[n]; }
-  auto put = [&](uint32_t t_flat, const HostAffine &a, const std::vector<float> &sc, uint32_t nb, uint32_t lane, uint32_t j, uint32_t k) {
-    const uint32_t n = 32 * nb + (lane & 31);
-    if (n >= a.out || k >= a.in) return;
-    const float x = a.w[(size_t)n * a.in + k] * sc[n];
-    const _Float16 hi = (_Float16)x;
-    const _Float16 lo = (_Float16)(x - (float)hi);
-    const size_t base = ((size_t)t_flat * NB + nb) * 2;
-    w[((base + 0) * 64 + lane) * 8 + j] = f16_bits(hi);
-    w[((base + 1) * 64 + lane) * 8 + j] = f16_bits(lo);
-  };
-  for (uint32_t nb = 0; nb < NB; ++nb)
-    for (uint32_t lane = 0; lane < 64; ++lane)
-      for (uint32_t j = 0; j < 8; ++j) {
-        const uint32_t hb = lane >> 5;
-        for (uint32_t t = 0; t < T0; ++t) put(t, fc0, sc0, nb, lane, j, 16 * t + 8 * hb + j);
-        for (uint32_t t = 0; t < 2 * NB; ++t) {
-          const uint32_t reg = 8 * (t & 1) + j, k = 32 * (t >> 1) + (reg & 3) + 8 * (reg >> 2) + 4 * hb;
-          put(T0 + t, fc1, sc1, nb, lane, j, k);
-          put(T0 + 2 * NB + t, v2, sc2, nb, lane, j, k);
-        }
-      }
-  return w;
-}
-// May this layer run as pairs?  Two checks on its weights:
-//   rows    -- every row (= output feature) carries its own scale, so a row of small weights next to rows of large ones loses nothing.
-//              Within a row the pair of w x scale misses w by at most 2^-24 |w| while its low part is a normal fp16 number and by up to
-//              2^-25 / scale (= 2^-39 x the row's largest weight) when it is a subnormal; the row passes when the sum of what its pairs
-//              miss stays within 2^-23 of the sum of its magnitudes -- the normwise error of ONE fp32 rounding per weight;
-//   columns -- a column whose largest weight is more than 2^16 below the layer's largest is carried with fewer bits, which is
-//              harmless while its input is no larger than the others' and wrong when the network compensates small weights with
-//              large inputs (an embedding net scaled up by 2^60 in front of fc0 columns scaled down by 2^60 is the same function in
-//              fp32).  The loader cannot see the inputs, so every non-zero column must reach 2^-18 of the layer's largest weight: a column
-//              that small matters only through inputs 2^18 times the others', and is then still carried to 2^-21 (the bound a
-//              nearly dead input unit of a trained network passes, a rescaled one does not).
-// With both, a layer's outputs are accurate to ~2^-23 of (the batch row's largest input) x (the weight row's magnitudes) -- the fp32
-// multiply-add's own normwise error -- for any input whose values of consequence lie within 2^15 of the row's largest.  A network that
-// fails stays on the bf16 triples, which have fp32's exponent range.
-bool pair_layer_ok(const HostAffine &a) {
-  float layer_max = 0.0f;
-  std::vector<float> col_max(a.in, 0.0f);
-  for (uint32_t n = 0; n < a.out; ++n) {
-    const float scale = row_pair_scale(a, n);
-    double miss = 0.0, mag = 0.0;
-    for (uint32_t k = 0; k < a.in; ++k) {
-      const float wv = a.w[(size_t)n * a.in + k], x = wv * scale;
-      const _Float16 hi = (_Float16)x;
-      const _Float16 lo = (_Float16)(x - (float)hi);
-      miss += std::fabs((double)x - ((double)(float)hi + (double)(float)lo));
-      mag += std::fabs((double)x);
-      col_max[k] = std::fmax(col_max[k], std::fabs(wv));
-      layer_max = std::fmax(layer_max, std::fabs(wv));
-    }
-    if (miss > mag * 0x1p-23 || !std::isfinite(mag)) return false;
-  }
-  for (uint32_t k = 0; k < a.in; ++k)
-    if (col_max[k] != 0.0f && col_max[k] < layer_max * 0x1p-18f) return false;
-  return true;
-}
-
-// k_policy_rows' A operand of a policy head's fc2 (H -> PH): float4 ((u * PB + b) * 64 + lane) = W[32 b + (lane & 31)][8 u + 4 (lane >> 5) .. + 3]
-// (four k-steps per load; the leaf's fc1 row supplies the same columns as the B operand).  Absent rows / columns are zeros.
-// ... and as bf16 triples, k_policy_rows<PB, true>'s A operand: 16-bit word ((((T * PB + b) * 3 + part) * 64 + lane) * 8 + j) = part of
-// W[32 b + (lane & 31)][16 T + 8 (lane >> 5) + j]; absent rows / columns are zeros.  Returned as floats (the upload's unit).
-std::vector<float> policy_triple_order(const HostAffine &a, uint32_t H, uint32_t PB);
-std::vector<float> policy_frag_order(const HostAffine &a, uint32_t H, uint32_t PB) {
-  const uint32_t nu = H / 8;
-  std::vector<float> f((size_t)nu * PB * 64 * 4, 0.0f);
-  for (uint32_t u = 0; u < nu; ++u)
-    for (uint32_t b = 0; b < PB; ++b)
-      for (uint32_t lane = 0; lane < 64; ++lane)
-        for (uint32_t e = 0; e < 4; ++e) {
-          const uint32_t row = 32 * b + (lane & 31), col = 8 * u + 4 * (lane >> 5) + e;
-          if (row < a.out && col < a.in) f[(((size_t)u * PB + b) * 64 + lane) * 4 + e] = a.w[(size_t)row * a.in + col];
-        }
-  return f;
-}
-
-// k_embed_arows: W0^T padded to 128 floats per row, + an all-zero last row (the move rows are read from this copy)
-// + rows AR_COMBINED + i (i = move id - 1, 0..164): the active move row 45 + i PLUS the stored Pokemon's move row 229 + 5 + i --
-// the two halves of a move slot hold the same move unless Transform / Mimic replaced the active one, so the pass loads one row
-std::vector<float> arows_rows(const HostAffine &a) { // a.w is [out = hidden][in]; row r of W0^T = column r of W
-  std::vector<float> d((size_t)(oak::AR_COMBINED + 165) * 128, 0.0f);
-  for (uint32_t r = 0; r < a.in; ++r)
-    for (uint32_t c = 0; c < a.out && c < 128; ++c) d[(size_t)r * 128 + c] = a.w[(size_t)c * a.in + r];
-  for (uint32_t i = 0; i < 165; ++i)
-    for (uint32_t c = 0; c < 128; ++c) d[(size_t)(oak::AR_COMBINED + i) * 128 + c] = d[(size_t)(45 + i) * 128 + c] + d[(size_t)(229 + 5 + i) * 128 + c];
-  return d;
-}
-// ... the dense part of W0 as bf16 triples, the A operand of dense_layer_bf16: 16-bit word ((((T * 4 + blk) * 3 + part) * 64 + lane) * 4 + j)
-// = part of W0[channel 4 (lane & 31) + blk][row of dense feature d = 8 T + 4 (lane >> 5) + j]  (d = 0: the bias; d >= F: zero)
-template <class RowOf>
-std::vector<float> dense_triple_frag(const HostAffine &a, uint32_t KT, uint32_t F, RowOf row_of) {
-  std::vector<uint16_t> w((size_t)KT * 4 * 3 * 64 * 4, 0);
-  for (uint32_t T = 0; T < KT; ++T)
-    for (uint32_t blk = 0; blk < 4; ++blk)
-      for (uint32_t lane = 0; lane < 64; ++lane)
-        for (uint32_t j = 0; j < 4; ++j) {
-          const uint32_t d = 8 * T + 4 * (lane >> 5) + j, c = 4 * (lane & 31) + blk;
-          if (d >= F || c >= a.out) continue;
-          const float x = d == 0 ? a.b[c] : a.w[(size_t)c * a.in + row_of(d)];
-          const uint16_t hh = f32_to_bf16(x);
-          const float r1 = x - bf16_to_f32(hh);
-          const uint16_t mm = f32_to_bf16(r1);
-          const uint16_t ll = f32_to_bf16(r1 - bf16_to_f32(mm));
-          const size_t base = ((size_t)T * 4 + blk) * 3;
-          w[((base + 0) * 64 + lane) * 4 + j] = hh;
-          w[((base + 1) * 64 + lane) * 4 + j] = mm;
-          w[((base + 2) * 64 + lane) * 4 + j] = ll;
-        }
-  std::vector<float> f(w.size() / 2);
-  memcpy(f.data(), w.data(), w.size() * 2);
-  return f;
-}
-std::vector<float> arows_dense_frag(const HostAffine &a) {
-  return dense_triple_frag(a, (uint32_t)oak::AR_KT, (uint32_t)oak::AR_FIXED, [](uint32_t d) { return (uint32_t)oak::ar_dense_row((int)d); });
-}
-// the same for k_embed_prows: dense feature d = 0 is the bias, d = 1..5 are W0^T rows 0..4 (the stats)
-std::vector<float> prows_dense_frag(const HostAffine &a) {
-  return dense_triple_frag(a, (uint32_t)oak::PR_KT, 6u, [](uint32_t d) { return d - 1; });
-}
-// ... and W1 [out][hidden] in MFMA-fragment order: [n-block][k-step s][lane (r32, hh)] = W1[nb * 32 + r32][ar_channel(s, hh)]
-std::vector<float> embed_frag_order(const HostAffine &a) {
-  const uint32_t NB = (a.out + 31) / 32;
-  std::vector<float> f((size_t)NB * 64 * 64, 0.0f);
-  for (uint32_t nb = 0; nb < NB; ++nb)
-    for (uint32_t s2 = 0; s2 < 64; ++s2)
-      for (uint32_t lane = 0; lane < 64; ++lane) {
-        const uint32_t o = nb * 32 + (lane & 31), c = (uint32_t)oak::ar_channel((int)s2, (int)(lane >> 5));
-        if (o < a.out && c < a.in) f[((size_t)nb * 64 + s2) * 64 + lane] = a.w[(size_t)o * a.in + c];
-      }
-  return f;
-}
-
-// fc3 of a policy head as k_policy_rows keeps it in LDS: 315 rows of PH floats at a stride of PH + 4, then the 315 biases (padded to 320)
-std::vector<float> policy_rows_image(const HostAffine &b, uint32_t PH) {
-  const uint32_t stride = PH + 4;
-  std::vector<float> img((size_t)315 * stride + 320, 0.0f);
-  for (uint32_t r = 0; r < 315 && r < b.out; ++r) {
-    for (uint32_t c = 0; c < b.in && c < PH; ++c) img[(size_t)r * stride + c] = b.w[(size_t)r * b.in + c];
-    img[(size_t)315 * stride + r] = b.b[r];
-  }
-  return img;
-}
-std::vector<float> policy_triple_order(const HostAffine &a, uint32_t H, uint32_t PB) {
-  const uint32_t nT = H / 16;
-  std::vector<uint16_t> w((size_t)nT * PB * 3 * 64 * 8, 0);
-  for (uint32_t T = 0; T < nT; ++T)
-    for (uint32_t b = 0; b < PB; ++b)
-      for (uint32_t lane = 0; lane < 64; ++lane)
-        for (uint32_t j = 0; j < 8; ++j) {
-          const uint32_t row = 32 * b + (lane & 31), col = 16 * T + 8 * (lane >> 5) + j;
-          if (row >= a.out || col >= a.in) continue;
-          const float x = a.w[(size_t)row * a.in + col];
-          const uint16_t hh = f32_to_bf16(x);
-          const float r1 = x - bf16_to_f32(hh);
-          const uint16_t mm = f32_to_bf16(r1);
-          const uint16_t ll = f32_to_bf16(r1 - bf16_to_f32(mm));
-          const size_t base = ((size_t)T * PB + b) * 3;
-          w[((base + 0) * 64 + lane) * 8 + j] = hh;
-          w[((base + 1) * 64 + lane) * 8 + j] = mm;
-          w[((base + 2) * 64 + lane) * 8 + j] = ll;
-        }
-  std::vector<float> f(w.size() / 2);
-  memcpy(f.data(), w.data(), w.size() * 2);
-  return f;
-}
-
-std::vector<float> pad_vec(const std::vector<float> &v, uint32_t n) {
-  std::vector<float> t(n, 0.0f);
-  for (size_t i = 0; i < v.size(); ++i) t[i] = v[i];
-  return t;
-}
-uint32_t up32(uint32_t x) { return (x + 31) & ~31u; }
-
-// W1 of an embedding net as scaled fp16 PAIRS in embed_layer2's order (round 5; rounds 3-4: bf16 triples -- the image keeps their three
-// 1-KB parts per k-step, the third is zeros): 16-bit word ((((nb * 8 + T) * 3 + part) * 64 + lane) * 8 + j) = part (0: h, 1: l) of
-// W1[32 nb + (lane & 31)][ar_channel(8 T + j, lane >> 5)] x row_pair_scale(W1, that row); absent rows / channels are zeros.  Returned as floats
-// (the LDS image's unit).
-std::vector<float> embed_pair_order(const HostAffine &a, uint32_t NB) {
-  std::vector<uint16_t> w((size_t)NB * 8 * 3 * 64 * 8, 0);
-  for (uint32_t nb = 0; nb < NB; ++nb)
-    for (uint32_t T = 0; T < 8; ++T)
-      for (uint32_t lane = 0; lane < 64; ++lane)
-        for (uint32_t j = 0; j < 8; ++j) {
-          const uint32_t o = nb * 32 + (lane & 31), c = (uint32_t)oak::ar_channel((int)(8 * T + j), (int)(lane >> 5));
-          if (o >= a.out || c >= a.in) continue;
-          const float x = a.w[(size_t)o * a.in + c] * row_pair_scale(a, o);
-          const _Float16 hi = (_Float16)x;
-          const _Float16 lo = (_Float16)(x - (float)hi);
-          const size_t base = ((size_t)nb * 8 + T) * 3;
-          w[((base + 0) * 64 + lane) * 8 + j] = f16_bits(hi);
-          w[((base + 1) * 64 + lane) * 8 + j] = f16_bits(lo);
-        }
-  std::vector<float> f(w.size() / 2);
-  memcpy(f.data(), w.data(), w.size() * 2);
-  return f;
-}
-std::vector<float> row_scale_inverses(const HostAffine &a, uint32_t padded) { // 1 / row_pair_scale of every output row (padded rows: 0)
-  std::vector<float> v(padded, 0.0f);
-  for (uint32_t o = 0; o < a.out; ++o) v[o] = 1.0f / row_pair_scale(a, o);
-  return v;
-}
-
-// the images of the two kernels' LDS weights: [one-hot rows (stride ER_RS) + a zero row | dense fragment | W1's fp16 pairs | b1 | 1 / W1's row scales]
-std::vector<float> arows_image(const HostAffine &a0, const HostAffine &a1) {
-  std::vector<float> img((size_t)(oak::AR_SPARSE + 1) * oak::ER_RS, 0.0f);
-  for (int sl = 0; sl < oak::AR_SPARSE; ++sl)
-    for (uint32_t c = 0; c < a0.out && c < 128; ++c) img[(size_t)sl * oak::ER_RS + c] = a0.w[(size_t)c * a0.in + (uint32_t)oak::ar_sparse_row(sl)];
-  const std::vector<float> d = arows_dense_frag(a0), f = embed_pair_order(a1, (a1.out + 31) / 32), bp = pad_vec(a1.b, up32(a1.out)), iv = row_scale_inverses(a1, up32(a1.out));
-  img.insert(img.end(), d.begin(), d.end());
-  img.insert(img.end(), f.begin(), f.end());
-  img.insert(img.end(), bp.begin(), bp.end());
-  img.insert(img.end(), iv.begin(), iv.end());
-  return img;
-}
-std::vector<float> prows_image(const HostAffine &p0, const HostAffine &p1) {
-  std::vector<float> img((size_t)(oak::PR_SPARSE + 1) * oak::ER_RS, 0.0f);
-  for (int sl = 0; sl < oak::PR_SPARSE; ++sl)
-    for (uint32_t c = 0; c < p0.out && c < 128; ++c) img[(size_t)sl * oak::ER_RS + c] = p0.w[(size_t)c * p0.in + (uint32_t)(sl + 5)];
-  const std::vector<float> d = prows_dense_frag(p0), f = embed_pair_order(p1, (p1.out + 31) / 32), bp = pad_vec(p1.b, up32(p1.out)), iv = row_scale_inverses(p1, up32(p1.out));
-  img.insert(img.end(), d.begin(), d.end());
-  img.insert(img.end(), f.begin(), f.end());
-  img.insert(img.end(), bp.begin(), bp.end());
-  img.insert(img.end(), iv.begin(), iv.end());
-  return img;
-}
-
-// ---- the quantized main net (oakgpu_net_load_discrete*): nn/battle/quantized/affine.h:74-99, main-net.h:36-66
-std::string float_text(float v) { char buf[64]; snprintf(buf, sizeof buf, "%f", (double)v); return buf; } // std::to_string(float)
-// visit_quantized_network's shape checks, in its order (network.h:182-275)
-int quant_shape_check(uint32_t in, uint32_t h, uint32_t vh, uint32_t ph) {
-  auto bad = [](const std::string &m) { return oakgpu_fail_msg(("Invalid layer size for quantized net " + m + " (check code for valid sizes).").c_str()); };
-  auto ok = [](uint32_t x) { return x == 32 || x == 64 || x == 128; };
-  if (in != 768) return bad("Side dim: " + std::to_string(in));
-  if (!ok(h)) return bad("Hidden: " + std::to_string(h));
-  if (!ok(vh)) return bad("Value hidden: " + std::to_string(vh));
-  if (!ok(ph)) return bad("Policy hidden: " + std::to_string(ph));
-  if (h < vh) return bad("Value hidden cannot be larger than hidden.");
-  if (h < ph) return bad("Policy hidden cannot be larger than hidden.");
-  return 0;
-}
-// AffineTransform::try_copy_parameters: weight int8 = trunc(w * 64), refused unless strictly inside (-2, 2) (NaN included: its
-// text is the reference's); bias int32 = trunc((b * 64) * 127), two fp32 operations (the reference's cast of a bias outside int32
-// is undefined: refused here).  `rows` pads the output rows with zeros (the policy fc3 layers: 315 -> 320).
-struct QLayer { std::vector<int8_t> w; std::vector<int32_t> b; };
-int quantize_layer(const HostAffine &a, uint32_t in, uint32_t out, uint32_t rows, const char *name, QLayer &q) {
-  if (a.in != in) return oakgpu_fail_msg("bad in dim");
-  if (std::min(a.out, rows) != out) return oakgpu_fail_msg("bad out dim");
-  q.w.assign((size_t)rows * in, 0);
-  q.b.assign(rows, 0);
-  for (size_t i = 0; i < (size_t)out * in; ++i) {
-    const float x = a.w[i];
-    if (!(x < 2.0f) || !(x > -2.0f)) return oakgpu_fail_msg((std::to_string(i) + "non clamped" + float_text(x)).c_str());
-    q.w[i] = (int8_t)(x * 64.0f);
-  }
-  for (uint32_t i = 0; i < out; ++i) {
-    const float x = (a.b[i] * 64.0f) * 127.0f;
-    if (!(x >= -2147483648.0f && x < 2147483648.0f))
-      return oakgpu_fail_msg(("quantized net: bias " + std::to_string(i) + " of " + name + " is outside int32 (" + float_text(a.b[i]) + ")").c_str());
-    q.b[i] = (int32_t)x;
-  }
-  return 0;
-}
-// k_mainnet_i8's LDS image.  fc0: 16 bytes ((t * NB + b) * 64 + lane) = W0[32 b + (lane & 31)][32 t + 16 (lane >> 5) + j];
-// fc1 and value_fc2 (input = the previous layer's accumulators): 16 bytes ((s * NBo + b) * 64 + lane) =
-// W[32 b + (lane & 31)][32 s + (j & 3) + 8 (j >> 2) + 4 (lane >> 5)] -- the k of byte j of lane half h in an accumulator tile.
-std::vector<uint8_t> qnet_image(const QLayer &fc0, const QLayer &fc1, const QLayer &v2, int H, int VH) {
-  const int NB = H / 32, NBv = VH / 32;
-  std::vector<uint8_t> img(oak::qi_lds_bytes(H, VH), 0);
-  uint8_t *p = img.data();
-  for (int t = 0; t < oak::QI_T0; ++t)
-    for (int b = 0; b < NB; ++b)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int j = 0; j < 16; ++j)
-          p[((size_t)(t * NB + b) * 64 + lane) * 16 + j] = (uint8_t)fc0.w[(size_t)(32 * b + (lane & 31)) * oak::QI_IN + 32 * t + 16 * (lane >> 5) + j];
-  p += (size_t)oak::QI_T0 * NB * 1024;
-  auto acc_order = [&](const QLayer &q, int nbo) {
-    for (int s = 0; s < NB; ++s)
-      for (int b = 0; b < nbo; ++b)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int j = 0; j < 16; ++j)
-            p[((size_t)(s * nbo + b) * 64 + lane) * 16 + j] = (uint8_t)q.w[(size_t)(32 * b + (lane & 31)) * H + 32 * s + (j & 3) + 8 * (j >> 2) + 4 * (lane >> 5)];
-    p += (size_t)NB * nbo * 1024;
-  };
-  acc_order(fc1, NB);
-  acc_order(v2, NBv);
-  return img;
-}
-template <class T>
-int upload_raw(oakgpu_net *net, const std::vector<T> &h, const T **out) {
-  void *d = nullptr;
-  hipError_t e = hipMalloc(&d, h.size() * sizeof(T));
-  if (e != hipSuccess) return oakgpu_fail_hip((int)e, "hipMalloc(net)");
-  net->allocs.push_back(d);
-  e = hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return oakgpu_fail_hip((int)e, "hipMemcpy(net)");
-  *out = (const T *)d;
-  return 0;
-}
-
 } // namespace
 
 extern "C" {
@@ -3003,199 +2601,41 @@ void oakgpu_net_free(oakgpu_ctx *ctx, oakgpu_net *net) {
   delete net;
 }
 
+// check the arguments -> parse, check and pack on the host (net_pack.hpp) -> upload every image -> scalars and flags.  Nothing is
+// allocated on the device before the file has passed every check.
 static int net_load_impl(oakgpu_ctx *ctx, const void *bytes, size_t size, bool discrete, oakgpu_net **out) {
   if (!ctx || !bytes || !out) return oakgpu_fail_msg("oakgpu_net_load_memory: null argument");
-  const uint8_t *p = (const uint8_t *)bytes, *end = p + size;
-  if (size < 8) return oakgpu_fail_msg("network file: truncated header");
-  const int activation = (int)p[0] + 1; // search.cc:127-131: byte0 = activation - 1
-  if (discrete && activation != 2) return oakgpu_fail_msg("Agent: .discrete was specified but the parsed header does not encode clamped activations.");
-  if (activation != 1 && activation != 2) return oakgpu_fail_msg("network file: unknown activation byte");
-  p += 8;
-  HostAffine L[12]; // p0 p1 a0 a1 fc0 fc1 v2 v3 q1a q1b q2a q2b
-  for (int i = 0; i < 12; ++i)
-    if (!read_affine(p, end, L[i])) return oakgpu_fail_msg("network file: truncated or malformed layer");
-  if (p != end) return oakgpu_fail_msg("network file: trailing bytes (network.h:60-63)");
-  // the quantized main net (search.cc:104-122): shapes as visit_quantized_network checks them, then try_copy_parameters layer by
-  // layer in main-net.h:36-66's order; a NaN weight is refused there as "non clamped", before the non-finite check below
-  QLayer Q[8]; // fc0 fc1 value_fc2 value_fc3 p1_fc2 p2_fc2 p1_fc3 p2_fc3
-  if (discrete) {
-    const uint32_t qh = L[4].out, qvh = L[6].out, qph = L[8].out;
-    if (int rc = quant_shape_check(L[4].in, qh, qvh, qph)) return rc;
-    const struct { int layer; uint32_t in, out, rows; const char *name; } qs[8] = {
-        {4, 768, qh, qh, "main_net.fc0"}, {5, qh, qh, qh, "main_net.fc1"}, {6, qh, qvh, qvh, "main_net.value_fc2"}, {7, qvh, 1, 1, "main_net.value_fc3"},
-        {8, qh, qph, qph, "main_net.p1_policy_fc2"}, {10, qh, qph, qph, "main_net.p2_policy_fc2"},
-        {9, qph, 315, 320, "main_net.p1_policy_fc3"}, {11, qph, 315, 320, "main_net.p2_policy_fc3"}};
-    for (int i = 0; i < 8; ++i)
-      if (int rc = quantize_layer(L[qs[i].layer], qs[i].in, qs[i].out, qs[i].rows, qs[i].name, Q[i])) return rc;
-  }
-  // Non-finite parameters are refused.  The reference would load them and propagate NaN / inf through every inference (its
-  // value_inference asserts !isnan in debug builds, network.h:77); a file with such a parameter is a failed training run, and
-  // here an infinite weight would also split into (inf, NaN, NaN) on the bf16 pipe -- a different wrong answer than fp32's.
-  {
-    static const char *names[12] = {"pokemon_net.fc0", "pokemon_net.fc1", "active_net.fc0", "active_net.fc1", "main_net.fc0", "main_net.fc1", "main_net.value_fc2",
-                                    "main_net.value_fc3", "main_net.p1_policy_fc2", "main_net.p1_policy_fc3", "main_net.p2_policy_fc2", "main_net.p2_policy_fc3"};
-    for (int i = 0; i < 12; ++i) {
-      bool finite = true;
-      for (float v : L[i].b) finite = finite && std::isfinite(v);
-      for (float v : L[i].w) finite = finite && std::isfinite(v);
-      if (!finite) return oakgpu_fail_msg((std::string("network file: non-finite parameter (NaN / inf) in ") + names[i]).c_str());
-    }
-  }
-  const HostAffine &p0 = L[0], &p1 = L[1], &a0 = L[2], &a1 = L[3], &fc0 = L[4], &fc1 = L[5], &v2 = L[6], &v3 = L[7];
-  if (p0.in != 198 || a0.in != 427) return oakgpu_fail_msg("network file: embedding input dims must be 198 / 427");
-  if (p1.in != p0.out || a1.in != a0.out || fc1.in != fc0.out || v2.in != fc1.out || v3.in != v2.out || v3.out != 1)
-    return oakgpu_fail_msg("network file: inconsistent layer dims");
-  if (p0.out > 128 || a0.out > 128 || p1.out > 128 || a1.out > 128) return oakgpu_fail_msg("embedding widths above 128 unsupported");
-  const uint32_t side_dim = (1 + a1.out) + 5 * (1 + p1.out);
-  if (fc0.in != 2 * side_dim) return oakgpu_fail_msg("network file: fc0 input != 2 * side embedding");
-  if (fc0.out != fc1.out) return oakgpu_fail_msg("network file: fc0/fc1 widths differ");
-  const uint32_t H = up32(fc0.out), VH = up32(v2.out);
-  if (H > (uint32_t)oak::MAXH || VH > (uint32_t)oak::MAXH) return oakgpu_fail_msg("main-net widths above 256 unsupported");
-  if (fc0.in % 4) return oakgpu_fail_msg("embedding dim must be a multiple of 4");
+  oak::pack::PackedNet P;
+  const std::string refusal = oak::pack::pack_net(bytes, size, discrete, P);
+  if (!refusal.empty()) return oakgpu_fail_msg(refusal.c_str());
   hipError_t he = hipSetDevice(oakgpu_ctx_device(ctx));
   if (he != hipSuccess) return oakgpu_fail_hip((int)he, "hipSetDevice");
   oakgpu_net *net = new oakgpu_net();
   net->device = oakgpu_ctx_device(ctx);
-  net->in_dim = (int)fc0.in;
-  net->hidden = (int)fc0.out;
-  net->value_hidden = (int)v2.out;
-  net->policy_hidden = (int)L[8].out;
+  for (const oak::pack::Image &img : P.images) {
+    void *d = nullptr;
+    int rc = upload(net, img.data(), img.bytes(), &d);
+    if (!rc && !set_field(net, img.name, d)) rc = oakgpu_fail_msg((std::string("net_load: no device field for image ") + img.name).c_str());
+    if (rc) { oakgpu_net_free(ctx, net); return rc; }
+  }
+  net->in_dim = P.in_dim; net->hidden = P.hidden; net->value_hidden = P.value_hidden; net->policy_hidden = P.policy_hidden;
   oak::NetDev &D = net->dev;
-  D.activation = activation;
-  D.p_hidden = (int)p0.out; D.p_out = (int)p1.out; D.a_hidden = (int)a0.out; D.a_out = (int)a1.out;
-  D.side_dim = (int)side_dim; D.emb_dim = (int)fc0.in;
-  D.H = (int)H; D.VH = (int)VH;
-  D.b3 = v3.b[0];
-  int rc = 0;
-  rc = rc ? rc : upload(net, transpose(p0), &D.p_w0t);
-  rc = rc ? rc : upload(net, p0.b, &D.p_b0);
-  rc = rc ? rc : upload(net, p1.w, &D.p_w1);
-  rc = rc ? rc : upload(net, a1.w, &D.a_w1);
-  rc = rc ? rc : upload(net, pad_vec(p1.b, up32(p1.out)), &D.p_b1); // (padded: embed_scatter reads whole float4 groups)
-  rc = rc ? rc : upload(net, transpose(a0), &D.a_w0t);
-  rc = rc ? rc : upload(net, a0.b, &D.a_b0);
-  rc = rc ? rc : upload(net, pad_vec(a1.b, up32(a1.out)), &D.a_b1);
-  rc = rc ? rc : upload(net, arows_rows(a0), &D.a_w0d);
-  rc = rc ? rc : upload(net, arows_image(a0, a1), &D.a_img);
-  rc = rc ? rc : upload(net, prows_image(p0, p1), &D.p_img);
-  rc = rc ? rc : upload(net, pad_vec(fc0.b, H), &D.b0);
-  rc = rc ? rc : upload(net, pad_vec(fc1.b, H), &D.b1);
-  rc = rc ? rc : upload(net, pad_vec(v2.b, VH), &D.b2);
-  rc = rc ? rc : upload(net, pad_vec(v3.w, VH), &D.w3);
-  rc = rc ? rc : upload(net, frag_order_wave(fc0, H), &D.w0g);
-  rc = rc ? rc : upload(net, frag_order_wave(fc1, H), &D.w1g);
-  rc = rc ? rc : upload(net, frag_order_wave(v2, VH), &D.w2g);
-  {
-    const uint32_t nbr = (H > VH ? H : VH) / 32, NB = nbr > 4 ? 8 : nbr > 2 ? 4 : nbr, T0 = 4 * ((fc0.in + 63) / 64);
-    const std::vector<uint16_t> ws = split_stream(fc0, fc1, v2, NB, T0);
-    void *dptr = nullptr;
-    if (!rc) {
-      he = hipMalloc(&dptr, ws.size() * 2);
-      if (he != hipSuccess) rc = oakgpu_fail_hip((int)he, "hipMalloc(weight stream)");
-      else {
-        net->allocs.push_back(dptr);
-        he = hipMemcpy(dptr, ws.data(), ws.size() * 2, hipMemcpyHostToDevice);
-        if (he != hipSuccess) rc = oakgpu_fail_hip((int)he, "hipMemcpy(weight stream)");
-      }
-    }
-    D.ws = (const uint16_t *)dptr; D.ws_T0 = (int)T0; D.ws_NB = (int)NB;
-    {
-      std::vector<float> wp_inv;
-      const std::vector<uint16_t> wp = pair_stream(fc0, fc1, v2, NB, T0, (uint32_t)H, (uint32_t)VH, wp_inv);
-      rc = rc ? rc : upload(net, wp_inv, &D.wp_inv);
-      void *pptr = nullptr;
-      if (!rc) {
-        he = hipMalloc(&pptr, wp.size() * 2);
-        if (he != hipSuccess) rc = oakgpu_fail_hip((int)he, "hipMalloc(pair stream)");
-        else {
-          net->allocs.push_back(pptr);
-          he = hipMemcpy(pptr, wp.data(), wp.size() * 2, hipMemcpyHostToDevice);
-          if (he != hipSuccess) rc = oakgpu_fail_hip((int)he, "hipMemcpy(pair stream)");
-        }
-      }
-      D.wp = (const uint16_t *)pptr;
-    }
-    // The bf16 triple (h, m, l) of a value x is exact to 2^-24 |x| only while its low parts are normal bf16 numbers (|x| >= ~2^-102);
-    // below that a part that flushes loses at most 2^-126 per factor -- an ABSOLUTE error of at most 2^-126 |other factor| per
-    // product.  That is harmless unless later layers amplify it: a layer scaled by 2^-120 feeding one scaled by 2^+120 computes an
-    // O(1) value in fp32, and there the lost parts would come back multiplied by 2^120.  So the triple form is used only while
-    // no main-net weight exceeds 2^20 in magnitude (two layers of 256 such weights amplify by < 2^56: 2^-126 x 768 x 2^56 is
-    // nothing); a network with a larger weight runs its main net on fp32 MFMA, whose products need no such care.
-    bool safe = true;
-    for (const HostAffine *a : {&fc0, &fc1, &v2})
-      for (float v : a->w) safe = safe && std::fabs(v) <= 0x1p20f;
-    net->split_safe = safe;
-    // The row kernels of the embedding passes (k_embed_prows / k_embed_arows) multiply the dense part of their first layer as bf16
-    // triples (the one-hot and move rows are added in fp32; the second layer: scaled fp16 pairs, below).  What a flushed part loses there is
-    // amplified by whatever comes BEHIND it -- the embedding nets' own second layers (L[1], L[3]) and the main net -- so a network
-    // with a weight above 2^20 in any of those runs its embedding nets through k_embed_lds (fp32 MFMA), whatever the main net's mode
-    // (round-4 advice: a layer scaled by 2^-110 in front of one scaled by 2^+110 is the same function in fp32).
-    bool esafe = safe;
-    for (const HostAffine *a : {&L[1], &L[3]})
-      for (float v : a->w) esafe = esafe && std::fabs(v) <= 0x1p20f;
-    // (round 5) ... and their second layers multiply as scaled fp16 pairs, which both must survive (pair_layer_ok: rows and columns)
-    esafe = esafe && pair_layer_ok(L[1]) && pair_layer_ok(L[3]);
-    net->embed_safe = esafe;
-    // fp16 pairs (k_mainnet_pair, the default since round 5): scaled per weight row and per batch row, so no absolute magnitude matters;
-    // what must hold is that every weight row survives the pairing to fp32 accuracy and no column is dwarfed (pair_layer_ok)
-    net->pair_safe = pair_layer_ok(fc0) && pair_layer_ok(fc1) && pair_layer_ok(v2);
-    const char *env = getenv("OAKGPU_MAIN_NET");
-    const int want = env ? (strcmp(env, "fp32") == 0 ? 0 : strcmp(env, "bf16x3") == 0 ? 1 : 2) : 2;
-    net->main_mode = want == 2 && net->pair_safe ? 2 : want >= 1 && safe ? 1 : 0;
-  }
-  {
-    const HostAffine &q1a = L[8], &q1b = L[9], &q2a = L[10], &q2b = L[11];
-    if (q1a.in != fc1.out || q2a.in != fc1.out || q1b.in != q1a.out || q2b.in != q2a.out || q1a.out != q2a.out ||
-        q1b.out != 315 || q2b.out != 315) { oakgpu_net_free(ctx, net); return oakgpu_fail_msg("network file: inconsistent policy-head dims"); }
-    const uint32_t ph32 = up32(q1a.out);
-    if (ph32 > (uint32_t)oak::MAXH) { oakgpu_net_free(ctx, net); return oakgpu_fail_msg("policy hidden width above 256 unsupported"); }
-    const uint32_t PB = ph32 > 128 ? 8 : ph32 > 64 ? 4 : ph32 > 32 ? 2 : 1, PH = 32 * PB; // k_policy_rows' block count: absent features are zeros
-    D.PH = (int)PH;
-    rc = rc ? rc : upload(net, pad_rows(q1a, PH, H), &D.q1a);
-    rc = rc ? rc : upload(net, pad_vec(q1a.b, PH), &D.q1a_b);
-    rc = rc ? rc : upload(net, pad_rows(q1b, 315, PH), &D.q1b);
-    rc = rc ? rc : upload(net, q1b.b, &D.q1b_b);
-    rc = rc ? rc : upload(net, pad_rows(q2a, PH, H), &D.q2a);
-    rc = rc ? rc : upload(net, pad_vec(q2a.b, PH), &D.q2a_b);
-    rc = rc ? rc : upload(net, pad_rows(q2b, 315, PH), &D.q2b);
-    rc = rc ? rc : upload(net, q2b.b, &D.q2b_b);
-    rc = rc ? rc : upload(net, policy_frag_order(q1a, H, PB), &D.q1a_f);
-    rc = rc ? rc : upload(net, policy_frag_order(q2a, H, PB), &D.q2a_f);
-    if (PH <= 64) { // (PolicyRows<PB>::WB_LDS: the rows fit the CU's LDS)
-      rc = rc ? rc : upload(net, policy_rows_image(q1b, PH), &D.q1b_img);
-      rc = rc ? rc : upload(net, policy_rows_image(q2b, PH), &D.q2b_img);
-    }
-    // the triples only while no weight of the heads is above 2^20 in magnitude (as for the main net: split_safe).  fc3 counts too:
-    // it is the later layer that multiplies back up what a flushed low part lost in fc2 (fc2 x 2^-120 in front of fc3 x 2^+120 is
-    // the same function in fp32; on the triples the logits were 2.3e-4 off -- tests/test_gpu_policy.py, down120_up120)
-    bool psafe = true;
-    for (const HostAffine *a : {&q1a, &q2a, &q1b, &q2b})
-      for (float v : a->w) psafe = psafe && std::fabs(v) <= 0x1p20f;
-    if (psafe) {
-      rc = rc ? rc : upload(net, policy_triple_order(q1a, H, PB), &D.q1a_t);
-      rc = rc ? rc : upload(net, policy_triple_order(q2a, H, PB), &D.q2a_t);
-    }
-  }
-  if (discrete && !rc) {
+  D.activation = P.activation;
+  D.p_hidden = P.p_hidden; D.p_out = P.p_out; D.a_hidden = P.a_hidden; D.a_out = P.a_out;
+  D.side_dim = P.side_dim; D.emb_dim = P.in_dim;
+  D.H = P.H; D.VH = P.VH; D.PH = P.PH;
+  D.b3 = P.b3;
+  D.ws_T0 = P.T0; D.ws_NB = P.NB;
+  if (P.discrete) {
     oak::QNetDev &q = net->q;
-    q.H = (int)fc0.out; q.VH = (int)v2.out; q.PH = (int)L[8].out;
-    const std::vector<uint8_t> img = qnet_image(Q[0], Q[1], Q[2], q.H, q.VH);
-    q.img_bytes = (int)img.size();
-    q.b3 = Q[3].b[0];
-    rc = rc ? rc : upload_raw(net, img, &q.img);
-    rc = rc ? rc : upload_raw(net, Q[0].b, &q.b0);
-    rc = rc ? rc : upload_raw(net, Q[1].b, &q.b1);
-    rc = rc ? rc : upload_raw(net, Q[2].b, &q.b2);
-    rc = rc ? rc : upload_raw(net, Q[3].w, &q.w3);
-    for (int hd = 0; hd < 2; ++hd) {
-      rc = rc ? rc : upload_raw(net, Q[4 + hd].w, &q.pw2[hd]);
-      rc = rc ? rc : upload_raw(net, Q[4 + hd].b, &q.pb2[hd]);
-      rc = rc ? rc : upload_raw(net, Q[6 + hd].w, &q.pw3[hd]);
-      rc = rc ? rc : upload_raw(net, Q[6 + hd].b, &q.pb3[hd]);
-    }
+    q.H = P.q_H; q.VH = P.q_VH; q.PH = P.q_PH; q.img_bytes = P.q_img_bytes; q.b3 = P.q_b3;
     net->discrete = true;
   }
-  if (rc) { oakgpu_net_free(ctx, net); return rc; }
+  // which number forms the weights allow (net_pack.hpp: pack_net); the heads' flag is carried by q1a_t / q2a_t being present
+  net->split_safe = P.split_safe; net->embed_safe = P.embed_safe; net->pair_safe = P.pair_safe;
+  const char *env = getenv("OAKGPU_MAIN_NET");
+  const int want = env ? (strcmp(env, "fp32") == 0 ? 0 : strcmp(env, "bf16x3") == 0 ? 1 : 2) : 2;
+  net->main_mode = want == 2 && net->pair_safe ? 2 : want >= 1 && net->split_safe ? 1 : 0;
   *out = net;
   return 0;
 }

@@ -18,11 +18,10 @@
 // u[2k] + u[2k+1] >= 259) gets its exact correction sat16(p) - p added per output on the vector ALU, the weights read back from
 // LDS.  Inputs of fc1 / value_fc2 / value_fc3 are crelu outputs (<= 127): 2 x 127 x 127 < 32767, those never saturate.
 #pragma once
+#include "net_layout.hpp" // QI_IN, QI_T0, qi_lds_bytes
 
 namespace oak {
 
-constexpr int QI_IN = 768;          // the battle embedding (visit_quantized_network: In == 768)
-constexpr int QI_T0 = QI_IN / 32;   // fc0's k-steps of 32 bytes
 constexpr int QI_BLOCK = 256;       // four waves, 32 leaves each
 constexpr int QI_ROWS = 315;        // policy rows (policy.h); fc3 is padded to 320 (main-net.h:53-66)
 typedef __attribute__((ext_vector_type(4))) int qi32x4;
@@ -48,7 +47,6 @@ struct QMainArgs {
   uint8_t *q_emb;     // nullable: n x 768 embedding bytes (diagnostic)
   int32_t *value_acc; // nullable: value_fc3's int32 (diagnostic)
 };
-__host__ __device__ constexpr size_t qi_lds_bytes(int H, int VH) { return (size_t)(QI_T0 * (H / 32) + (H / 32) * (H / 32) + (H / 32) * (VH / 32)) * 1024; }
 
 // static_cast<uint8_t>(127 * f) as the reference's g++ builds compile it (vcvttps2dq, then the low byte): values outside int32 --
 // and NaN -- become 0x80000000, i.e. 0.  (C++ leaves every result >= 256 undefined)
