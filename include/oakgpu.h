@@ -1345,6 +1345,102 @@ int oakgpu_build_provide(oakgpu_ctx *ctx, const oakgpu_build_net *net, const uin
 int oakgpu_build_records(oakgpu_ctx *ctx, const uint8_t *teams_init, const uint8_t *sizes /* nullable */, const uint8_t *n_updates, const uint16_t *action,
                          const float *prob, const float *value, const float *score, uint32_t n, uint8_t *records, uint32_t *count);
 
+/* ---- Reading `.build.data` back: the reference's read_build_trajectories (cpp/src/pyoak.cc:247-329) with Py::Build::Trajectories::write
+ * (cpp/include/py/build/trajectories.h:145-233), and the network-free half of build.py's process_targets (src/oak/build.py:119-129, 157-195).
+ * The rule is one text for the host and the device, oak_amd/csrc/build_traj.hpp; the kernels are oak_amd/csrc/buildtraj.hip.  Decoding runs
+ * on the GPU only; oakgpu_build_traj_check (statuses) is the one host form of the rule.
+ *   THE RULE, per 128-byte NoTeam record.  start = the first i with probability != 0 (none: 0); end = the last such i + 1 (none: 0); swap =
+ * end - 1 if the action at end - 1 is a (species, None) cell, else end; full = 1 + the last i < end - 1 with probability != 0 whose action is
+ * a (species, None) cell (none: 0) -- as the loops of trajectories.h:159-187 take them.  A HELPER holds the team: sets in the order they were
+ * added, each {species, counted moves, remaining pool}; a (species, None) action adds a set with the species' whole pool (a species already
+ * in the team adds a second set), a (species, move) action takes the move out of the remaining pool of the FIRST set of that species and
+ * counts it -- a move that is not in the remaining pool changes nothing.  A set is complete at 4 counted moves or an empty remaining pool.
+ *   Steps i < start: action -1, policy 0, mask row all -1; the action is applied to the helper.  Steps start <= i < end: action = the
+ * record's, policy = probability / 65535.0f (a correctly rounded float division); the mask row is, if i < swap, the (species, None) cells of
+ * the legal species no set holds, in legal_species order, when i < full, then for each incomplete set in team order its remaining pool in
+ * pool order; if i >= swap, every set's species cell in team order; the rest of the row is -1; the taken action is exchanged with entry 0;
+ * then the action is applied UNLESS i == end - 1.  (The reference applies that one too, after the row is written and with no later reader;
+ * on a team of six, where it is the lead swap, its helper writes a seventh set out of bounds.  Leaving it out gives the same arrays wherever
+ * the reference is defined.)  Steps i >= end: action -1, policy 0, mask row all -1.
+ *   value = header.value / 65535.0f.  score = header.score / 2.0 rounded to float; the reference compares the 8-bit score with 65,535, so a
+ * record without a score (byte 255) reads as 127.5: no_score = 0 keeps that, no_score = 1 gives the -1 it meant.
+ *   STATUS, one byte per record.  Where the reference asserts or runs out of bounds the record is not OK and is written as an ENDED
+ * trajectory: every action -1, policy 0, mask -1, n_legal 0, start = end = 0; value and score are still decoded.  BAD_ACTION: the action of a
+ * step below end is >= n_dim (looked for first).  Then in step order -- NO_SPECIES: a move of a species that is not in the team; TEAM_FULL: a
+ * (species, None) action applied to six sets; NOT_LEGAL: the taken action is not in its own step's list (the reference would write -1 into
+ * entry 0 and train on cell 0: the one place this deviates from a defined behaviour of the reference); LIST_OVERFLOW: a list longer than
+ * 339 entries (only duplicate pre-start species reach it; the reference writes past the row).  BAD_PICK (255) is not a record's status: a
+ * pick of a _dev call at or past the corpus' records reads nothing and gives an ended trajectory with value = score = 0.
+ *   A CORPUS is the bytes of one or more files on the device, copied once.  DRAWS follow the reference's two-stage rule with a stream per
+ * draw (oakgpu_frames_sample_dev's convention): draw i seeds fast_prng with seed + i; file = uniform_64 % n_files; record = uniform_64 %
+ * records(file); with replacement, draw i does not depend on n; records that are not OK are drawn like any other and show in status.  A
+ * PICK is a u32 global record index (the files' records in file order).
+ *   TARGETS from the decoded arrays: valid = action != -1 && policy > 0; rows = the (b, t) of the valid steps in row-major order (torch's
+ * x[valid]), compacted with game_rows.hpp's scan; the state of a valid step = the actions of the steps in front of it that are not -1, in
+ * step order (get_state sees the trajectory's actions, not the initial team: pre-start steps are -1 and vanish) as state_cells / state_n, the
+ * sparse form the rollout kernel's layer 1 consumes, padded with 65,535; old_logp = (float)log((double)policy): the device library's DOUBLE log (within 3 ulp
+ * of double, OpenCL's bound for log) rounded to float once, so within 0.5 + 3 x 2^-29 ulp of float of the exact logarithm, and exactly 0 at
+ * policy 1 -- the float logf of the same library promises 3 ulp and measures up to 1.9; rewards = value_weight * value + (1 - value_weight)
+ * x score at end - 1 and 0 elsewhere, the difference in
+ * double and both products and the sum rounded to float as torch computes build.py's line (a row with end == 0 is all 0).
+ *   The _dev calls take device arrays and are asynchronous on the context's stream.  Every byte of every non-null output of rows 0 .. n-1 is
+ * written (of the compacted arrays: of rows 0 .. n_valid-1), nothing outside them; two calls give the same bits; a row depends on its record
+ * alone; no float atomics.  The host forms stage, refuse a pick outside the corpus by name, and return complete. */
+enum { OAKGPU_BUILD_TRAJ_OK = 0, OAKGPU_BUILD_TRAJ_BAD_ACTION = 1, OAKGPU_BUILD_TRAJ_NO_SPECIES = 2, OAKGPU_BUILD_TRAJ_TEAM_FULL = 3,
+       OAKGPU_BUILD_TRAJ_NOT_LEGAL = 4, OAKGPU_BUILD_TRAJ_LIST_OVERFLOW = 5, OAKGPU_BUILD_TRAJ_N_STATUS = 6, OAKGPU_BUILD_TRAJ_BAD_PICK = 255 };
+enum { OAKGPU_BUILD_MASK_INT64 = 0 /* the reference's */, OAKGPU_BUILD_MASK_INT16 = 1 /* every value is -1 .. 3,748: a quarter of the bytes */ };
+typedef struct oakgpu_build_corpus oakgpu_build_corpus;
+typedef struct { uint32_t records, files, status_count[OAKGPU_BUILD_TRAJ_N_STATUS]; } oakgpu_build_corpus_stats;
+typedef struct { int32_t mask_dtype, no_score; } oakgpu_build_traj_params;
+typedef struct {             /* all nullable except status; a null mask makes the call cheap */
+  int64_t *action;           /* [n, 31] */
+  void *mask;                /* [n, 31, 339] int64 or int16 (mask_dtype), aligned to its entries */
+  uint16_t *n_legal;         /* [n, 31]: the length of each step's list, 0 outside [start, end) */
+  float *policy;             /* [n, 31] */
+  float *value, *score;      /* [n] */
+  int64_t *start, *end;      /* [n] */
+  uint8_t *status;           /* [n] */
+  uint32_t *t_max;           /* one word: max(end) */
+} oakgpu_build_trajectories;
+typedef struct {             /* all nullable except n_valid */
+  uint8_t *valid;            /* [n, 31] */
+  uint32_t *n_valid;         /* one word: V */
+  uint32_t *rows;            /* [V, 2] (b, t); room for n x 31 rows, like the three below */
+  uint16_t *state_cells;     /* [V, 31] */
+  uint8_t *state_n;          /* [V] */
+  float *old_logp;           /* [V] */
+  float *rewards;            /* [n, 31] */
+} oakgpu_build_target_outputs;
+/* Host only, no GPU needed: the status of every record by the header's host form.  Refuses by name no records, a length that is not a
+ * multiple of 128 and a record whose format byte is not 0. */
+int oakgpu_build_traj_check(const uint8_t *bytes, size_t len, uint8_t *status_out);
+/* buffer: the files' bytes one after the other; file_sizes [n_files] add up to size.  Refuses by name (before it looks at ctx) an empty
+ * corpus, an empty file, a file size that is not a multiple of 128 and a record whose format byte is not 0, with the file and the record.
+ * The corpus belongs to ctx and must be destroyed before it. */
+int oakgpu_build_corpus_create(oakgpu_ctx *ctx, const uint8_t *buffer, size_t size, const size_t *file_sizes, uint32_t n_files, oakgpu_build_corpus **out);
+void oakgpu_build_corpus_destroy(oakgpu_build_corpus *corpus);
+/* One lane per record: every record's status and the count per status, kept by the corpus (asynchronous). */
+int oakgpu_build_corpus_scan_dev(oakgpu_ctx *ctx, oakgpu_build_corpus *corpus);
+/* records, files and the count per status: of the last _scan_dev, or of a scan this call makes when there was none; synchronises once. */
+int oakgpu_build_corpus_info(oakgpu_build_corpus *corpus, oakgpu_build_corpus_stats *info);
+/* picks: n device words */
+int oakgpu_build_traj_dev(oakgpu_ctx *ctx, const oakgpu_build_corpus *corpus, const uint32_t *picks, uint32_t n, const oakgpu_build_traj_params *params,
+                          const oakgpu_build_trajectories *out);
+/* picks_out: nullable, n device words */
+int oakgpu_build_traj_sample_dev(oakgpu_ctx *ctx, oakgpu_build_corpus *corpus, uint32_t n, uint64_t seed, const oakgpu_build_traj_params *params,
+                                 uint32_t *picks_out, const oakgpu_build_trajectories *out);
+/* traj: action and policy (for rewards also value, score, end) of n decoded rows, device arrays */
+int oakgpu_build_targets_dev(oakgpu_ctx *ctx, const oakgpu_build_trajectories *traj, uint32_t n, double value_weight, const oakgpu_build_target_outputs *out);
+/* The dense 0/1 state of the valid rows lo .. hi-1 as f32 [hi - lo, 3749]: get_state(action)[valid][lo:hi], bit for bit. */
+int oakgpu_build_state_dense_dev(oakgpu_ctx *ctx, const uint16_t *state_cells, const uint8_t *state_n, uint32_t lo, uint32_t hi, float *out);
+/* host arrays in and out */
+int oakgpu_build_traj(oakgpu_ctx *ctx, const oakgpu_build_corpus *corpus, const uint32_t *picks, uint32_t n, const oakgpu_build_traj_params *params,
+                      const oakgpu_build_trajectories *out);
+int oakgpu_build_traj_sample(oakgpu_ctx *ctx, oakgpu_build_corpus *corpus, uint32_t n, uint64_t seed, const oakgpu_build_traj_params *params,
+                             uint32_t *picks_out, const oakgpu_build_trajectories *out);
+int oakgpu_build_targets(oakgpu_ctx *ctx, const oakgpu_build_trajectories *traj, uint32_t n, double value_weight, const oakgpu_build_target_outputs *out);
+int oakgpu_build_state_dense(oakgpu_ctx *ctx, const uint16_t *state_cells, const uint8_t *state_n, uint32_t lo, uint32_t hi, float *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -825,6 +825,98 @@ private:
   oakgpu_build_net *net_{};
 };
 
+// `.build.data` files resident on the device and read back into training arrays (oakgpu_build_corpus_*, oakgpu_build_traj*,
+// oakgpu_build_targets): the reference's read_build_trajectories and the network-free half of build.py's process_targets.  Host vectors in
+// and out.  Must not outlive its Context.
+class BuildTrajectories {
+public:
+  struct Rows { // what a decode leaves, row-major: [n, 31] per step, [n, 31, 339] the mask (empty when not asked for), [n] per row
+    uint32_t n{}, t_max{};
+    std::vector<int64_t> action, mask, start, end;
+    std::vector<uint16_t> n_legal;
+    std::vector<float> policy, value, score;
+    std::vector<uint8_t> status;
+    std::vector<uint32_t> picks;
+  };
+  struct Targets { // valid / rewards [n, 31]; rows [V, 2], state_cells [V, 31], state_n / old_logp [V]
+    uint32_t n_valid{};
+    std::vector<uint8_t> valid, state_n;
+    std::vector<uint32_t> rows;
+    std::vector<uint16_t> state_cells;
+    std::vector<float> old_logp, rewards;
+  };
+  // files: the bytes of each `.build.data` file
+  BuildTrajectories(Context &ctx, const std::vector<std::vector<uint8_t>> &files) : ctx_{ctx.get()} {
+    std::vector<uint8_t> all;
+    std::vector<size_t> sizes;
+    for (const auto &f : files) {
+      all.insert(all.end(), f.begin(), f.end());
+      sizes.push_back(f.size());
+    }
+    check(oakgpu_build_corpus_create(ctx_, all.data(), all.size(), sizes.data(), static_cast<uint32_t>(sizes.size()), &corpus_));
+  }
+  ~BuildTrajectories() { oakgpu_build_corpus_destroy(corpus_); }
+  BuildTrajectories(const BuildTrajectories &) = delete;
+  BuildTrajectories &operator=(const BuildTrajectories &) = delete;
+  oakgpu_build_corpus *get() const noexcept { return corpus_; }
+  // host only: the status of every record (OAKGPU_BUILD_TRAJ_*)
+  static std::vector<uint8_t> check_records(const std::vector<uint8_t> &bytes) {
+    std::vector<uint8_t> status(bytes.size() / OAKGPU_BUILD_RECORD_BYTES);
+    check(oakgpu_build_traj_check(bytes.data(), bytes.size(), status.data()));
+    return status;
+  }
+  oakgpu_build_corpus_stats info() {
+    oakgpu_build_corpus_stats st{};
+    check(oakgpu_build_corpus_info(corpus_, &st));
+    return st;
+  }
+  Rows decode(const std::vector<uint32_t> &picks, bool with_mask = true, bool no_score = false) {
+    Rows r = make(static_cast<uint32_t>(picks.size()), with_mask);
+    const oakgpu_build_trajectories out = pointers(r);
+    const oakgpu_build_traj_params prm{OAKGPU_BUILD_MASK_INT64, no_score ? 1 : 0};
+    check(oakgpu_build_traj(ctx_, corpus_, picks.data(), r.n, &prm, &out));
+    r.picks = picks;
+    return r;
+  }
+  Rows sample(uint32_t n, uint64_t seed, bool with_mask = true, bool no_score = false) {
+    Rows r = make(n, with_mask);
+    r.picks.assign(n, 0);
+    const oakgpu_build_trajectories out = pointers(r);
+    const oakgpu_build_traj_params prm{OAKGPU_BUILD_MASK_INT64, no_score ? 1 : 0};
+    check(oakgpu_build_traj_sample(ctx_, corpus_, n, seed, &prm, r.picks.data(), &out));
+    return r;
+  }
+  Targets targets(Rows &r, double value_weight) {
+    const size_t steps = static_cast<size_t>(r.n) * OAKGPU_BUILD_MAX_STEPS;
+    Targets t;
+    t.valid.assign(steps, 0); t.state_n.assign(steps, 0); t.rows.assign(steps * 2, 0); t.state_cells.assign(steps * OAKGPU_BUILD_MAX_STEPS, 0);
+    t.old_logp.assign(steps, 0.0f); t.rewards.assign(steps, 0.0f);
+    const oakgpu_build_trajectories in = pointers(r);
+    const oakgpu_build_target_outputs out{t.valid.data(), &t.n_valid, t.rows.data(), t.state_cells.data(), t.state_n.data(), t.old_logp.data(), t.rewards.data()};
+    check(oakgpu_build_targets(ctx_, &in, r.n, value_weight, &out));
+    t.state_n.resize(t.n_valid); t.rows.resize(static_cast<size_t>(t.n_valid) * 2); t.state_cells.resize(static_cast<size_t>(t.n_valid) * OAKGPU_BUILD_MAX_STEPS);
+    t.old_logp.resize(t.n_valid);
+    return t;
+  }
+
+private:
+  static Rows make(uint32_t n, bool with_mask) {
+    Rows r;
+    const size_t steps = static_cast<size_t>(n) * OAKGPU_BUILD_MAX_STEPS;
+    r.n = n;
+    r.action.assign(steps, 0); r.n_legal.assign(steps, 0); r.policy.assign(steps, 0.0f);
+    if (with_mask) r.mask.assign(steps * OAKGPU_BUILD_MAX_ACTIONS, 0);
+    r.start.assign(n, 0); r.end.assign(n, 0); r.value.assign(n, 0.0f); r.score.assign(n, 0.0f); r.status.assign(n, 0);
+    return r;
+  }
+  static oakgpu_build_trajectories pointers(Rows &r) {
+    return oakgpu_build_trajectories{r.action.data(), r.mask.empty() ? nullptr : r.mask.data(), r.n_legal.data(), r.policy.data(), r.value.data(), r.score.data(),
+                                     r.start.data(), r.end.data(), r.status.data(), &r.t_max};
+  }
+  oakgpu_ctx *ctx_{};
+  oakgpu_build_corpus *corpus_{};
+};
+
 // The path's one exchange step for root-parallel search sharded over the GPUs of a node (one process per GPU): reduce the
 // rank's leaf values to one mean per root on the device, then ONE ncclAllGather (RCCL over xGMI) of those means.
 class Exchange {

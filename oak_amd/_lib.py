@@ -49,6 +49,9 @@ SYMBOLS = [
     "oakgpu_build_tables", "oakgpu_build_net_check", "oakgpu_build_net_load", "oakgpu_build_net_destroy", "oakgpu_build_net_shape", "oakgpu_build_teams_check",
     "oakgpu_build_provide_check", "oakgpu_build_rollout_dev", "oakgpu_build_provide_dev", "oakgpu_build_records_dev", "oakgpu_build_rollout",
     "oakgpu_build_provide", "oakgpu_build_records",
+    "oakgpu_build_traj_check", "oakgpu_build_corpus_create", "oakgpu_build_corpus_destroy", "oakgpu_build_corpus_scan_dev", "oakgpu_build_corpus_info",
+    "oakgpu_build_traj_dev", "oakgpu_build_traj_sample_dev", "oakgpu_build_targets_dev", "oakgpu_build_state_dense_dev", "oakgpu_build_traj",
+    "oakgpu_build_traj_sample", "oakgpu_build_targets", "oakgpu_build_state_dense",
 ]
 
 
@@ -144,6 +147,22 @@ class BuildOutputs(C.Structure):      # oakgpu_build_outputs: one pointer per ar
 class BuildProvider(C.Structure):     # oakgpu_build_provider
     _fields_ = [("max_pokemon", C.c_int32), ("input_update", C.c_int32), ("pokemon_delete_prob", C.c_double), ("move_delete_prob", C.c_double),
                 ("team_modify_prob", C.c_double)]
+
+
+class BuildCorpusStats(C.Structure):  # oakgpu_build_corpus_stats
+    _fields_ = [("records", C.c_uint32), ("files", C.c_uint32), ("status_count", C.c_uint32 * 6)]
+
+
+class BuildTrajParams(C.Structure):   # oakgpu_build_traj_params
+    _fields_ = [("mask_dtype", C.c_int32), ("no_score", C.c_int32)]
+
+
+class BuildTrajectories(C.Structure):  # oakgpu_build_trajectories: one nullable pointer per array, device or host as the call says
+    _fields_ = [(name, C.c_void_p) for name in ("action", "mask", "n_legal", "policy", "value", "score", "start", "end", "status", "t_max")]
+
+
+class BuildTargetOutputs(C.Structure):  # oakgpu_build_target_outputs
+    _fields_ = [(name, C.c_void_p) for name in ("valid", "n_valid", "rows", "state_cells", "state_n", "old_logp", "rewards")]
 
 
 class Seat(C.Structure):              # oakgpu_seat
@@ -438,6 +457,21 @@ def load():
     lib.oakgpu_build_provide.argtypes = lib.oakgpu_build_provide_dev.argtypes
     lib.oakgpu_build_records_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]
     lib.oakgpu_build_records.argtypes = lib.oakgpu_build_records_dev.argtypes
+    traj_p, prm_t = C.POINTER(BuildTrajectories), C.POINTER(BuildTrajParams)
+    lib.oakgpu_build_traj_check.argtypes = [vp, sz, vp]
+    lib.oakgpu_build_corpus_create.argtypes = [vp, vp, sz, C.POINTER(sz), u32, C.POINTER(vp)]
+    lib.oakgpu_build_corpus_destroy.argtypes = [vp]
+    lib.oakgpu_build_corpus_destroy.restype = None
+    lib.oakgpu_build_corpus_scan_dev.argtypes = [vp, vp]
+    lib.oakgpu_build_corpus_info.argtypes = [vp, C.POINTER(BuildCorpusStats)]
+    lib.oakgpu_build_traj_dev.argtypes = [vp, vp, vp, u32, prm_t, traj_p]
+    lib.oakgpu_build_traj.argtypes = lib.oakgpu_build_traj_dev.argtypes
+    lib.oakgpu_build_traj_sample_dev.argtypes = [vp, vp, u32, u64, prm_t, vp, traj_p]
+    lib.oakgpu_build_traj_sample.argtypes = lib.oakgpu_build_traj_sample_dev.argtypes
+    lib.oakgpu_build_targets_dev.argtypes = [vp, traj_p, u32, f64, C.POINTER(BuildTargetOutputs)]
+    lib.oakgpu_build_targets.argtypes = lib.oakgpu_build_targets_dev.argtypes
+    lib.oakgpu_build_state_dense_dev.argtypes = [vp, vp, vp, u32, u32, vp]
+    lib.oakgpu_build_state_dense.argtypes = lib.oakgpu_build_state_dense_dev.argtypes
     _lib = lib
     return lib
 

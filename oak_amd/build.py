@@ -247,3 +247,178 @@ def decode_records(data):
         out.append({"score": None if r[1] == 255 else r[1] / 2.0, "value": int(r[2:4].view("<u2")[0]) / 65535.0, "action": ups[:, 0].copy(),
                     "probability": ups[:, 1].copy()})
     return out
+
+
+# ---- reading `.build.data` back: trajectories and the network-free half of process_targets (oak_amd/csrc/buildtraj.hip) -----------------
+TRAJ_STATUS = ("OK", "BAD_ACTION", "NO_SPECIES", "TEAM_FULL", "NOT_LEGAL", "LIST_OVERFLOW")
+_MASK_DTYPES = {"int64": (0, np.int64), "int16": (1, np.int16)}
+_TRAJ_ARRAYS = (("action", (MAX_STEPS,), np.int64), ("mask", (MAX_STEPS, MAX_ACTIONS), None), ("n_legal", (MAX_STEPS,), np.uint16),
+                ("policy", (MAX_STEPS,), np.float32), ("value", (), np.float32), ("score", (), np.float32), ("start", (), np.int64),
+                ("end", (), np.int64), ("status", (), np.uint8))
+_TARGET_ARRAYS = (("valid", (MAX_STEPS,), np.uint8, False), ("rows", (2,), np.uint32, True), ("state_cells", (MAX_STEPS,), np.uint16, True),
+                  ("state_n", (), np.uint8, True), ("old_logp", (), np.float32, True), ("rewards", (MAX_STEPS,), np.float32, False))
+
+
+def _torch_dtype(dtype):
+    import torch
+    return {np.uint8: torch.uint8, np.uint16: torch.int16, np.int16: torch.int16, np.uint32: torch.int32, np.int64: torch.int64, np.float32: torch.float32}[dtype]
+
+
+def _empty(shape, dtype, device):
+    if device is None:
+        return np.empty(shape, dtype)
+    import torch
+    return torch.empty(shape, dtype=_torch_dtype(dtype), device=device)
+
+
+def _ptr(a):
+    return None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
+
+
+def _on_stream(ctx, device, call):
+    """One _dev call on the context's stream, ordered after and before the caller's torch stream."""
+    import torch
+    mine, theirs = torch.cuda.ExternalStream(ctx.stream_ptr(), device=device), torch.cuda.current_stream(device)
+    mine.wait_stream(theirs)
+    _lib.check(call())
+    theirs.wait_stream(mine)
+
+
+def check_records(data):
+    """The status of every record of `.build.data` bytes (uint8[n], an index into TRAJ_STATUS), without a GPU; refuses by name a length that
+    is not a multiple of 128 and a record whose format byte is not 0."""
+    buf = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8).reshape(-1)
+    status = np.zeros(buf.size // RECORD_BYTES, np.uint8)
+    _lib.check(_lib.load().oakgpu_build_traj_check(buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, status.ctypes.data_as(C.c_void_p)))
+    return status
+
+
+class TrajectoryCorpus:
+    """The records of one or more `.build.data` files resident on the context's device: `paths_or_bytes` is a path, bytes, or a list of
+    either (one entry per file).  close() (or the context manager) frees it before the context goes."""
+
+    def __init__(self, ctx, paths_or_bytes):
+        is_bytes = lambda x: isinstance(x, (bytes, bytearray, memoryview))
+        files = [paths_or_bytes] if (is_bytes(paths_or_bytes) or isinstance(paths_or_bytes, str)) else list(paths_or_bytes)
+        blobs = [bytes(f) if is_bytes(f) else open(f, "rb").read() for f in files]
+        buf = np.frombuffer(b"".join(blobs), np.uint8)
+        sizes = (C.c_size_t * max(len(blobs), 1))(*[len(b) for b in blobs])
+        self.ctx, self.handle = ctx, C.c_void_p()
+        _lib.check(ctx.lib.oakgpu_build_corpus_create(ctx.handle, buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, sizes, len(blobs),
+                                                      C.byref(self.handle)))
+        self.file_records = [len(b) // RECORD_BYTES for b in blobs]
+        self.records = sum(self.file_records)
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.oakgpu_build_corpus_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """{"records", "files", "status": count per TRAJ_STATUS name}: one scan of all records on the device the first time."""
+        st = _lib.BuildCorpusStats()
+        _lib.check(self.ctx.lib.oakgpu_build_corpus_info(self.handle, C.byref(st)))
+        return {"records": int(st.records), "files": int(st.files), "status": {name: int(st.status_count[k]) for k, name in enumerate(TRAJ_STATUS)}}
+
+    def _call(self, n, device, mask_dtype, no_score, mask, out, trim, run_dev, run_host):
+        code, mdt = _MASK_DTYPES[mask_dtype]
+        if out is None:
+            out = {name: _empty((n,) + shape, mdt if dtype is None else dtype, device) for name, shape, dtype in _TRAJ_ARRAYS if mask or name != "mask"}
+            out["t_max"] = _empty((1,), np.uint32, device)
+        o, prm = _lib.BuildTrajectories(), _lib.BuildTrajParams(code, int(bool(no_score)))
+        for name in out:
+            setattr(o, name, _ptr(out[name]))
+        if device is None:
+            _lib.check(run_host(prm, o))
+        else:
+            _on_stream(self.ctx, device, lambda: run_dev(prm, o))
+        if trim and "t_max" in out:
+            t = int(out["t_max"][0])
+            for name in ("action", "mask", "n_legal", "policy"):
+                if name in out:
+                    out[name] = out[name][:, :t]
+        return out
+
+    def decode(self, picks, mask_dtype="int64", no_score=False, mask=True, out=None, trim=False):
+        """The trajectories of explicit picks (global record indices: the files' records in file order).  numpy picks give numpy arrays, a
+        torch GPU tensor (int32) gives tensors on its device and copies nothing to the host.  A dict: action int64 [n, 31], mask [n, 31, 339]
+        in mask_dtype (left out with mask=False, which makes the call cheap), n_legal [n, 31], policy f32 [n, 31], value / score f32 [n],
+        start / end int64 [n], status uint8 [n], t_max [1] = max(end).  trim=True slices the per-step arrays to [:, :t_max] (the T of
+        oak.torch.BuildTrajectories; it reads t_max, so it waits for the call).  out: the same dict preallocated by the caller."""
+        lib, ctx, h = self.ctx.lib, self.ctx.handle, self.handle
+        if hasattr(picks, "data_ptr"):
+            p, device = picks.contiguous(), picks.device
+        else:
+            p, device = np.ascontiguousarray(picks, np.uint32).reshape(-1), None
+        n = int(p.shape[0])
+        return self._call(n, device, mask_dtype, no_score, mask, out, trim,
+                          lambda prm, o: lib.oakgpu_build_traj_dev(ctx, h, _ptr(p), n, C.byref(prm), C.byref(o)),
+                          lambda prm, o: lib.oakgpu_build_traj(ctx, h, _ptr(p), n, C.byref(prm), C.byref(o)))
+
+    def sample(self, n, seed, mask_dtype="int64", no_score=False, mask=True, device=None, out=None, trim=False):
+        """n draws of the reference's two-stage rule (draw i: fast_prng seeded with seed + i, a file, then a record of it) decoded as decode
+        does, plus "picks" uint32 [n].  device None: numpy arrays; a torch device: tensors on it."""
+        lib, ctx, h = self.ctx.lib, self.ctx.handle, self.handle
+        picks = _empty((int(n),), np.uint32, device)
+        out = self._call(int(n), device, mask_dtype, no_score, mask, out, trim,
+                         lambda prm, o: lib.oakgpu_build_traj_sample_dev(ctx, h, int(n), int(seed), C.byref(prm), _ptr(picks), C.byref(o)),
+                         lambda prm, o: lib.oakgpu_build_traj_sample(ctx, h, int(n), int(seed), C.byref(prm), _ptr(picks), C.byref(o)))
+        out["picks"] = picks
+        return out
+
+
+def targets(ctx, traj, value_weight):
+    """The network-free half of build.py's process_targets from a decoded dict (untrimmed): valid bool [n, 31]; n_valid; rows [V, 2] = (b, t)
+    in the order of torch's x[valid]; state_cells [V, 31] / state_n [V], the actions in front of each valid step in step order (padded with
+    65,535; -1 as int16 on the device); old_logp f32 [V] = the logarithm of policy taken in double, rounded once; rewards f32 [n, 31]."""
+    on_device = hasattr(traj["action"], "data_ptr")
+    device = traj["action"].device if on_device else None
+    n = int(traj["action"].shape[0])
+    t = _lib.BuildTrajectories()
+    keep = {}
+    for name in ("action", "policy", "value", "score", "start", "end"):
+        keep[name] = traj[name].contiguous() if on_device else np.ascontiguousarray(traj[name])
+        setattr(t, name, _ptr(keep[name]))
+    out = {name: _empty((n * MAX_STEPS,) + shape if compact else (n,) + shape, dtype, device) for name, shape, dtype, compact in _TARGET_ARRAYS}
+    count = _empty((1,), np.uint32, device)
+    o = _lib.BuildTargetOutputs()
+    for name in out:
+        setattr(o, name, _ptr(out[name]))
+    o.n_valid = _ptr(count)
+    if on_device:
+        _on_stream(ctx, device, lambda: ctx.lib.oakgpu_build_targets_dev(ctx.handle, C.byref(t), n, float(value_weight), C.byref(o)))
+    else:
+        _lib.check(ctx.lib.oakgpu_build_targets(ctx.handle, C.byref(t), n, float(value_weight), C.byref(o)))
+    v = int(count[0])
+    for name, _, _, compact in _TARGET_ARRAYS:
+        if compact:
+            out[name] = out[name][:v]
+    out["valid"] = out["valid"].bool() if on_device else out["valid"].astype(bool)
+    out["n_valid"] = v
+    return out
+
+
+def dense_state(ctx, targets, lo, hi):
+    """f32 [hi - lo, 3749]: the dense 0/1 state of the valid rows lo .. hi-1, get_state(action)[valid][lo:hi] bit for bit."""
+    cells, counts = targets["state_cells"], targets["state_n"]
+    lo, hi = int(lo), int(hi)
+    if hasattr(cells, "data_ptr"):
+        import torch
+        out = torch.empty((hi - lo, N_DIM), dtype=torch.float32, device=cells.device)
+        _on_stream(ctx, cells.device, lambda: ctx.lib.oakgpu_build_state_dense_dev(ctx.handle, cells.data_ptr(), counts.data_ptr(), lo, hi, out.data_ptr()))
+        return out
+    out = np.empty((hi - lo, N_DIM), np.float32)
+    _lib.check(ctx.lib.oakgpu_build_state_dense(ctx.handle, _ptr(np.ascontiguousarray(cells)), _ptr(np.ascontiguousarray(counts)), lo, hi, _ptr(out)))
+    return out

@@ -25,8 +25,8 @@
 // (EncodedBattleFrames, SampleIndexer, sample) is the GPU loader of include/oakgpu.h behind the reference's names: the indexer's
 // files are uploaded once as a corpus (again when a path joins or leaves, or a file's size or time of last write changes) and a call draws, replays and encodes `size` rows on
 // the device, then copies them into the numpy fields; `threads` is accepted and ignored, the seed comes from std::random_device
-// as in the reference.  oak_amd/train.py is the same loader on torch tensors, without the copy.  Not carried over:
-// BuildTrajectories, which stays with the reference's Python.  Heap keeps the tree between searches (RuntimeSearch::Heap over oakgpu_heap; its C++
+// as in the reference.  oak_amd/train.py is the same loader on torch tensors, without the copy.  BuildTrajectories(size) and
+// read_build_trajectories(trajectories, paths, threads) are the GPU reader of `.build.data` behind the reference's names (:247-329, :697-715).  Heap keeps the tree between searches (RuntimeSearch::Heap over oakgpu_heap; its C++
 // `update(i, j, obs)` is exposed too, and `update(input, c1, c2)` returns the 16-byte observation that call needs), an
 // `output` passed to search() is resumed like MCTS::Search::run's by-value Output (mcts.h:153-155), p{1,2}_prior are the
 // softmax of the root's policy logits for contextual bandits (mcts.h:196-209).  cpp_inference takes a game record as
@@ -36,6 +36,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <cstdio>
 #include <cstring>
 #include <filesystem>
 #include <fstream>
@@ -215,6 +216,55 @@ struct SampleIndexer {
     return corpus;
   }
 };
+
+// Py::Build::Trajectories (py/build/trajectories.h:105-134): the reference's seven numpy fields in its shapes, plus the reader's status
+struct BuildTrajectories {
+  size_t size;
+  py::array_t<int64_t> action, mask, start, end;
+  py::array_t<float> policy, value, score;
+  py::array_t<uint8_t> status;
+  explicit BuildTrajectories(size_t sz)
+      : size{sz}, action(std::vector<size_t>{sz, 31, 1}), mask(std::vector<size_t>{sz, 31, OAKGPU_BUILD_MAX_ACTIONS}), start(std::vector<size_t>{sz, 1}),
+        end(std::vector<size_t>{sz, 1}), policy(std::vector<size_t>{sz, 31, 1}), value(std::vector<size_t>{sz, 1}), score(std::vector<size_t>{sz, 1}),
+        status(std::vector<size_t>{sz}) {
+    clear();
+  }
+  void clear() {
+    using E = EncodedBattleFrames;
+    E::zero(action); E::zero(mask); E::zero(start); E::zero(end); E::zero(policy); E::zero(value); E::zero(score); E::zero(status);
+  }
+};
+
+// The corpus behind read_build_trajectories: the listed files, uploaded once per list of (path, size, time of last write); under g_ctx_mu
+struct BuildCorpusCache {
+  std::vector<SampleIndexer::FileKey> files;
+  oakgpu_build_corpus *corpus = nullptr;
+  oakgpu_build_corpus *get(const std::vector<std::string> &paths) {
+    std::vector<SampleIndexer::FileKey> now;
+    for (const auto &path : paths) {
+      std::error_code ec1, ec2;
+      const uintmax_t size = std::filesystem::file_size(path, ec1);
+      const auto written = std::filesystem::last_write_time(path, ec2);
+      if (ec1 || ec2) throw std::runtime_error("read_build_trajectories: Failed to open file: " + path);
+      now.push_back(SampleIndexer::FileKey{path, size, written});
+    }
+    if (corpus && now == files) return corpus;
+    if (corpus) oakgpu_build_corpus_destroy(corpus);
+    corpus = nullptr;
+    files.clear();
+    std::vector<uint8_t> all;
+    std::vector<size_t> sizes;
+    for (const auto &path : paths) {
+      const std::vector<char> bytes = read_file(path, "read_build_trajectories");
+      all.insert(all.end(), bytes.begin(), bytes.end());
+      sizes.push_back(bytes.size());
+    }
+    check(oakgpu_build_corpus_create(context(), all.data(), all.size(), sizes.data(), (uint32_t)sizes.size(), &corpus));
+    files = now;
+    return corpus;
+  }
+};
+BuildCorpusCache g_build_corpus;
 
 template <class T, class F> py::array_t<T> vec9(F f) {
   py::array_t<T> arr(9);
@@ -902,6 +952,44 @@ PYBIND11_MODULE(pyoak, m) {
     for (int s = 0; s < 152; ++s) species_move_table.emplace_back(table.begin() + s * 166, table.begin() + (s + 1) * 166);
     m.attr("species_move_table") = std::move(species_move_table);
   }
+
+  py::class_<BuildTrajectories>(m, "BuildTrajectories")
+      .def(py::init<size_t>())
+      .def_readonly("size", &BuildTrajectories::size)
+      .def_readwrite("action", &BuildTrajectories::action)
+      .def_readwrite("mask", &BuildTrajectories::mask)
+      .def_readwrite("policy", &BuildTrajectories::policy)
+      .def_readwrite("value", &BuildTrajectories::value)
+      .def_readwrite("score", &BuildTrajectories::score)
+      .def_readwrite("start", &BuildTrajectories::start)
+      .def_readwrite("end", &BuildTrajectories::end)
+      .def_readwrite("status", &BuildTrajectories::status)
+      .def("clear", &BuildTrajectories::clear);
+
+  m.def(
+      "read_build_trajectories",
+      [](BuildTrajectories &t, const std::vector<std::string> &paths, size_t /*threads*/, int no_score) -> size_t {
+        // pyoak.cc:247-329: `size` draws of a random file and a random record of it, each written by Py::Build::Trajectories::write -- here
+        // one decode call on the device over the files' corpus (include/oakgpu.h), the seed from std::random_device as the reference's
+        // threads seed theirs.  Returns the count read, or 0 on a refusal (the message goes to stderr, as the reference's does).
+        if (t.size == 0 || paths.empty()) return 0;
+        const uint64_t seed = ((uint64_t)std::random_device{}() << 32) | std::random_device{}();
+        oakgpu_build_trajectories out{};
+        out.action = t.action.mutable_data(); out.mask = t.mask.mutable_data(); out.policy = t.policy.mutable_data(); out.value = t.value.mutable_data();
+        out.score = t.score.mutable_data(); out.start = t.start.mutable_data(); out.end = t.end.mutable_data(); out.status = t.status.mutable_data();
+        const oakgpu_build_traj_params prm{OAKGPU_BUILD_MASK_INT64, no_score};
+        try {
+          py::gil_scoped_release release;
+          std::lock_guard<std::mutex> lock(g_ctx_mu);
+          oakgpu_build_corpus *corpus = g_build_corpus.get(paths);
+          check(oakgpu_build_traj_sample(context(), corpus, (uint32_t)t.size, seed, &prm, nullptr, &out));
+        } catch (const std::exception &e) {
+          fprintf(stderr, "%s\n", e.what());
+          return 0;
+        }
+        return t.size;
+      },
+      py::arg("trajectories"), py::arg("paths"), py::arg("threads") = 1, py::arg("no_score") = 0);
 
   m.def(
       "build_teams",
