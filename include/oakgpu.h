@@ -1441,6 +1441,97 @@ int oakgpu_build_traj_sample(oakgpu_ctx *ctx, oakgpu_build_corpus *corpus, uint3
 int oakgpu_build_targets(oakgpu_ctx *ctx, const oakgpu_build_trajectories *traj, uint32_t n, double value_weight, const oakgpu_build_target_outputs *out);
 int oakgpu_build_state_dense(oakgpu_ctx *ctx, const uint16_t *state_cells, const uint8_t *state_n, uint32_t lo, uint32_t hi, float *out);
 
+/* ---- Training the build network: the optimiser step of the reference's `build` program (src/oak/build.py:153-251, 292-338) on the
+ * device -- process_targets, compute_loss_from_targets, backward() per chunk, torch.optim.Adam and rolling_average.  The kernels are
+ * oak_amd/csrc/buildtrain.hip; the two 31-step recursions are oak_amd/csrc/build_loss.hpp, one text for the host and the device.
+ *   WHICH NETWORK.  The network trained is the one this library's rollout READS (NN::Build::Network, oakgpu_build_net_check): two nets of
+ * three Affine blocks, policy 3749 -> h -> h -> 3749 (relu, relu, none) and value 3749 -> v1 -> v2 -> 1 (relu, relu, none, then sigmoid).
+ * This deviates from build.py, which trains two-layer EmbeddingNets (torch.py:448-475) that the reference's own C++ reader cannot load.
+ * Refused by name: whatever oakgpu_build_net_check refuses, and a value hidden width above 256.  v1 != v2 and ragged widths are allowed.
+ *   A CHUNK is n decoded trajectories with their targets, all device arrays, untrimmed, as oakgpu_build_traj_dev and
+ * oakgpu_build_targets_dev write them: mask (int64 or int16), n_legal, valid, rewards, and of the V = n_valid valid rows rows (b, t),
+ * state_cells, state_n; a nullable keep u8 [V] (the caller's torch.rand(...) < keep_prob); the scalars gamma, gamma_lam (doubles, each
+ * rounded to float once; gamma_lam is gamma * lam computed in double), the three loss weights, total (the batch size) and remaining.
+ * old_logp is not read (the reference's ratio is commented out).
+ *   THE RULE, for valid row i = (b, t) with state cells S_i (a cell counts once) and list L_i = mask[b, t, :n_legal[b, t]], entry 0 the
+ * taken action:
+ *     both nets: a1 = b1 + sum_{c in S_i} W1[:, c] (in the order of state_cells), h1 = relu(a1), h2 = relu(W2 h1 + b2)
+ *     z_j = W3[L_j, :] . h2 + b3[L_j] at the legal cells only;  val_i = sigmoid(W3v . h2v + b3v)
+ *     S = sum_j exp(z_j), NO maximum subtracted (torch.exp + normalize(p=1)); q_j = exp(z_j) / max(S, 1e-12); lp_i = log(q_0)
+ *     value_full[b, t] = val at valid steps, 0 elsewhere;  delta = rewards + gamma value_full[b, t+1] - value_full[b, t]
+ *     gae[b, t] = valid delta + gamma_lam gae[b, t+1] (t descending from 30, from 0);  ret = gae + value_full
+ *     cf_i = [z_0 > -2] min(gae_i, 0) + [z_0 < 2] max(gae_i, 0), detached;  forced_i = z_0 cf_i
+ *     k = sum keep (V when keep is null);  n_cap = min(k, remaining);  row i is SELECTED when it is kept and fewer than n_cap kept rows
+ *     stand in front of it (the [:n] slices after x[mask]);  k == 0 adds nothing
+ *     loss = (1 / total) sum_sel [ -pw forced_i + vw (ret_i - val_i)^2 + ew lp_i exp(lp_i) ]
+ *   THE GRADIENT is exact, and gae is NOT detached inside ret (the value loss trains through the whole recursion; the direct paths through
+ * value_full cancel).  With c = 1 / total and r_i = ret_i - val_i as computed in float:
+ *     dL/dz_{i,j} = sel_i c [ -pw cf_i [j = 0] + ew q_{i,0} (1 + lp_i) ([j = 0] - q_{i,j}) ]      (S < 1e-12: the q_{i,j} term is 0)
+ *     G[b, t] = sel 2 c vw r at valid rows, 0 elsewhere;  A[b, t] = G[b, t] + gamma_lam A[b, t-1] (t ascending);  D = valid A
+ *     dL/dvalue_full[b, t] = -D[b, t] + gamma D[b, t-1], times val (1 - val) at valid rows: unselected valid rows receive value gradient too
+ * then three layers per net; torch.relu has no gradient at 0.  An entry no row reaches (a W1 column whose cell is in no state; a W3 row
+ * and b3 entry whose cell is in no selected row's list) is exactly unchanged by a call.
+ *   ACCUMULATION.  _accumulate_dev forms the chunk's gradient on its own and adds it to the gradient block once per entry: after two
+ * calls the block is bit for bit fl(g1 + g2).  _adam_dev is torch.optim.Adam's defaults (betas 0.9 / 0.999, eps 1e-8, no weight decay)
+ * over all twelve tensors as one group at a host-given lr; _average_dev is avg = avg g + (1 - g) p on a second parameter block that starts
+ * equal to the initial parameters.
+ *   NUMERICS.  fp32 throughout.  No float atomics: every sum runs in a fixed order that depends on the rows alone (dense products: k_gemm's
+ * chains of 32 terms, 16 chains a middle sum; the transposed sparse products dW1 and dW3|db3: the entries of a cell in ascending entry
+ * order, in pieces of OAKGPU_BUILD_TRAINER_SEGMENT entries summed in chains of 32, the pieces combined pairwise).  Two calls give the same
+ * bits, and bits do not depend on the grid.  No workspace is allocated inside a call: capacities (31 max_traj rows, 339 x 31 max_traj list
+ * entries) are fixed at create.  Every _dev call is asynchronous on the context's stream; _report is the only call that waits.
+ *   _read / _set_gradients speak FILE ORDER: per layer the biases then the weights [out][in], policy net then value net -- a `.build.net`
+ * without its dims. */
+enum { OAKGPU_BUILD_TRAIN_PARAMETERS = 0, OAKGPU_BUILD_TRAIN_GRADIENTS = 1, OAKGPU_BUILD_TRAIN_M = 2, OAKGPU_BUILD_TRAIN_V = 3, OAKGPU_BUILD_TRAIN_AVERAGE = 4 };
+enum { OAKGPU_BUILD_TRAINER_SEGMENT = 256, OAKGPU_BUILD_TRAINER_MAX_TRAJ = 32768 };
+typedef struct oakgpu_build_trainer oakgpu_build_trainer;
+typedef struct {
+  const void *mask;             /* [n, 31, 339] int64 or int16 */
+  int32_t mask_dtype;           /* OAKGPU_BUILD_MASK_INT64 / _INT16 */
+  uint32_t n;                   /* trajectories */
+  const uint16_t *n_legal;      /* [n, 31] */
+  const uint8_t *valid;         /* [n, 31] */
+  const float *rewards;         /* [n, 31] */
+  uint32_t n_valid;             /* V, as the host knows it */
+  const uint32_t *rows;         /* [V, 2] */
+  const uint16_t *state_cells;  /* [V, 31] */
+  const uint8_t *state_n;       /* [V] */
+  const uint8_t *keep;          /* nullable [V] */
+  double gamma, gamma_lam;
+  float policy_loss_weight, value_loss_weight, entropy_loss_weight;
+  uint32_t total, remaining;
+} oakgpu_build_chunk;
+typedef struct {                /* all nullable, per valid row */
+  float *logits;                /* [V, 339], NaN beyond n_legal */
+  float *value, *logp, *gae, *returns, *forced;   /* [V] */
+  uint8_t *selected;            /* [V] */
+  float *du;                    /* [V]: dL/d(the value net's output before the sigmoid), as the last call's weights and selection make it */
+} oakgpu_build_train_outputs;
+typedef struct {                /* of the last _forward_dev / _accumulate_dev: the means are over the n_cap selected rows */
+  uint32_t rows, kept, n_cap, reserved;   /* V, k, n_cap */
+  double policy_loss, value_loss, entropy, loss;
+  uint64_t steps;               /* _adam_dev calls so far */
+} oakgpu_build_train_report;
+/* Host only, no GPU needed: the refusals of _create, by name. */
+int oakgpu_build_trainer_check(const uint8_t *net, size_t size, uint32_t max_traj);
+/* net: the bytes of a `.build.net`.  The trainer belongs to ctx and must be destroyed before it. */
+int oakgpu_build_trainer_create(oakgpu_ctx *ctx, const uint8_t *net, size_t size, uint32_t max_traj, oakgpu_build_trainer **out);
+void oakgpu_build_trainer_destroy(oakgpu_build_trainer *t);
+/* dims: (in, out) of the six layers in file order; count: floats of one parameter block */
+int oakgpu_build_trainer_shape(const oakgpu_build_trainer *t, uint32_t dims[12], size_t *count, uint32_t *max_traj);
+int oakgpu_build_trainer_forward_dev(oakgpu_ctx *ctx, oakgpu_build_trainer *t, const oakgpu_build_chunk *chunk, const oakgpu_build_train_outputs *out /* nullable */);
+int oakgpu_build_trainer_accumulate_dev(oakgpu_ctx *ctx, oakgpu_build_trainer *t, const oakgpu_build_chunk *chunk);
+int oakgpu_build_trainer_zero_gradients_dev(oakgpu_ctx *ctx, oakgpu_build_trainer *t);
+int oakgpu_build_trainer_adam_dev(oakgpu_ctx *ctx, oakgpu_build_trainer *t, float lr);
+int oakgpu_build_trainer_average_dev(oakgpu_ctx *ctx, oakgpu_build_trainer *t, double g);
+/* the only call that waits */
+int oakgpu_build_trainer_report(oakgpu_ctx *ctx, oakgpu_build_trainer *t, oakgpu_build_train_report *out);
+/* which: OAKGPU_BUILD_TRAIN_*; host: count floats in file order (these two wait for the copy) */
+int oakgpu_build_trainer_read(oakgpu_ctx *ctx, oakgpu_build_trainer *t, int which, float *host, size_t count);
+int oakgpu_build_trainer_set_gradients(oakgpu_ctx *ctx, oakgpu_build_trainer *t, const float *host, size_t count);
+/* which: _PARAMETERS (the net) or _AVERAGE.  out null: *size alone.  The bytes pass oakgpu_build_net_check. */
+int oakgpu_build_trainer_net_bytes(oakgpu_ctx *ctx, oakgpu_build_trainer *t, int which, uint8_t *out, size_t capacity, size_t *size);
+
 #ifdef __cplusplus
 }
 #endif

@@ -917,6 +917,56 @@ private:
   oakgpu_build_corpus *corpus_{};
 };
 
+// The optimiser step of the reference's build.py on the device, for the three-layer nets of a `.build.net` (oakgpu_build_trainer_*; the
+// rule is in oakgpu.h, "Training the build network").  A chunk's arrays are DEVICE arrays, as oakgpu_build_traj_dev and
+// oakgpu_build_targets_dev write them; parameters, gradients and nets cross as host vectors in file order.  Must not outlive its Context.
+class BuildTrainer {
+public:
+  BuildTrainer(Context &ctx, const std::vector<uint8_t> &net_bytes, uint32_t max_traj) : ctx_{ctx.get()} {
+    check(oakgpu_build_trainer_create(ctx_, net_bytes.data(), net_bytes.size(), max_traj, &t_));
+    check(oakgpu_build_trainer_shape(t_, dims_, &count_, &max_traj_));
+  }
+  ~BuildTrainer() { oakgpu_build_trainer_destroy(t_); }
+  BuildTrainer(const BuildTrainer &) = delete;
+  BuildTrainer &operator=(const BuildTrainer &) = delete;
+  oakgpu_build_trainer *get() const noexcept { return t_; }
+  // host only: the refusals of the constructor, by name
+  static void check_net(const std::vector<uint8_t> &net_bytes, uint32_t max_traj) { check(oakgpu_build_trainer_check(net_bytes.data(), net_bytes.size(), max_traj)); }
+  size_t count() const noexcept { return count_; }
+  uint32_t max_traj() const noexcept { return max_traj_; }
+  std::pair<uint32_t, uint32_t> layer(int k) const { return {dims_[2 * k], dims_[2 * k + 1]}; }   // (in, out) of layer k of six, file order
+  void forward_dev(const oakgpu_build_chunk &chunk, const oakgpu_build_train_outputs *out = nullptr) { check(oakgpu_build_trainer_forward_dev(ctx_, t_, &chunk, out)); }
+  void accumulate_dev(const oakgpu_build_chunk &chunk) { check(oakgpu_build_trainer_accumulate_dev(ctx_, t_, &chunk)); }
+  void zero_gradients() { check(oakgpu_build_trainer_zero_gradients_dev(ctx_, t_)); }
+  void adam(float lr) { check(oakgpu_build_trainer_adam_dev(ctx_, t_, lr)); }
+  void average(double gamma) { check(oakgpu_build_trainer_average_dev(ctx_, t_, gamma)); }
+  oakgpu_build_train_report report() {
+    oakgpu_build_train_report r{};
+    check(oakgpu_build_trainer_report(ctx_, t_, &r));
+    return r;
+  }
+  std::vector<float> read(int which = OAKGPU_BUILD_TRAIN_PARAMETERS) {
+    std::vector<float> out(count_);
+    check(oakgpu_build_trainer_read(ctx_, t_, which, out.data(), out.size()));
+    return out;
+  }
+  void set_gradients(const std::vector<float> &grads) { check(oakgpu_build_trainer_set_gradients(ctx_, t_, grads.data(), grads.size())); }
+  std::vector<uint8_t> net_bytes(int which = OAKGPU_BUILD_TRAIN_PARAMETERS) {
+    size_t size = 0;
+    check(oakgpu_build_trainer_net_bytes(ctx_, t_, which, nullptr, 0, &size));
+    std::vector<uint8_t> out(size);
+    check(oakgpu_build_trainer_net_bytes(ctx_, t_, which, out.data(), out.size(), &size));
+    return out;
+  }
+
+private:
+  oakgpu_ctx *ctx_{};
+  oakgpu_build_trainer *t_{};
+  uint32_t dims_[12]{};
+  size_t count_{};
+  uint32_t max_traj_{};
+};
+
 // The path's one exchange step for root-parallel search sharded over the GPUs of a node (one process per GPU): reduce the
 // rank's leaf values to one mean per root on the device, then ONE ncclAllGather (RCCL over xGMI) of those means.
 class Exchange {

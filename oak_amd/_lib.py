@@ -52,6 +52,9 @@ SYMBOLS = [
     "oakgpu_build_traj_check", "oakgpu_build_corpus_create", "oakgpu_build_corpus_destroy", "oakgpu_build_corpus_scan_dev", "oakgpu_build_corpus_info",
     "oakgpu_build_traj_dev", "oakgpu_build_traj_sample_dev", "oakgpu_build_targets_dev", "oakgpu_build_state_dense_dev", "oakgpu_build_traj",
     "oakgpu_build_traj_sample", "oakgpu_build_targets", "oakgpu_build_state_dense",
+    "oakgpu_build_trainer_check", "oakgpu_build_trainer_create", "oakgpu_build_trainer_destroy", "oakgpu_build_trainer_shape", "oakgpu_build_trainer_forward_dev",
+    "oakgpu_build_trainer_accumulate_dev", "oakgpu_build_trainer_zero_gradients_dev", "oakgpu_build_trainer_adam_dev", "oakgpu_build_trainer_average_dev",
+    "oakgpu_build_trainer_report", "oakgpu_build_trainer_read", "oakgpu_build_trainer_set_gradients", "oakgpu_build_trainer_net_bytes",
 ]
 
 
@@ -163,6 +166,22 @@ class BuildTrajectories(C.Structure):  # oakgpu_build_trajectories: one nullable
 
 class BuildTargetOutputs(C.Structure):  # oakgpu_build_target_outputs
     _fields_ = [(name, C.c_void_p) for name in ("valid", "n_valid", "rows", "state_cells", "state_n", "old_logp", "rewards")]
+
+
+class BuildChunk(C.Structure):        # oakgpu_build_chunk
+    _fields_ = [("mask", C.c_void_p), ("mask_dtype", C.c_int32), ("n", C.c_uint32), ("n_legal", C.c_void_p), ("valid", C.c_void_p), ("rewards", C.c_void_p),
+                ("n_valid", C.c_uint32), ("rows", C.c_void_p), ("state_cells", C.c_void_p), ("state_n", C.c_void_p), ("keep", C.c_void_p),
+                ("gamma", C.c_double), ("gamma_lam", C.c_double), ("policy_loss_weight", C.c_float), ("value_loss_weight", C.c_float),
+                ("entropy_loss_weight", C.c_float), ("total", C.c_uint32), ("remaining", C.c_uint32)]
+
+
+class BuildTrainOutputs(C.Structure):  # oakgpu_build_train_outputs
+    _fields_ = [(name, C.c_void_p) for name in ("logits", "value", "logp", "gae", "returns", "forced", "selected", "du")]
+
+
+class BuildTrainReport(C.Structure):  # oakgpu_build_train_report
+    _fields_ = [("rows", C.c_uint32), ("kept", C.c_uint32), ("n_cap", C.c_uint32), ("reserved", C.c_uint32), ("policy_loss", C.c_double),
+                ("value_loss", C.c_double), ("entropy", C.c_double), ("loss", C.c_double), ("steps", C.c_uint64)]
 
 
 class Seat(C.Structure):              # oakgpu_seat
@@ -472,6 +491,21 @@ def load():
     lib.oakgpu_build_targets.argtypes = lib.oakgpu_build_targets_dev.argtypes
     lib.oakgpu_build_state_dense_dev.argtypes = [vp, vp, vp, u32, u32, vp]
     lib.oakgpu_build_state_dense.argtypes = lib.oakgpu_build_state_dense_dev.argtypes
+    chunk_p = C.POINTER(BuildChunk)
+    lib.oakgpu_build_trainer_check.argtypes = [vp, sz, u32]
+    lib.oakgpu_build_trainer_create.argtypes = [vp, vp, sz, u32, C.POINTER(vp)]
+    lib.oakgpu_build_trainer_destroy.argtypes = [vp]
+    lib.oakgpu_build_trainer_destroy.restype = None
+    lib.oakgpu_build_trainer_shape.argtypes = [vp, C.POINTER(u32 * 12), C.POINTER(sz), C.POINTER(u32)]
+    lib.oakgpu_build_trainer_forward_dev.argtypes = [vp, vp, chunk_p, C.POINTER(BuildTrainOutputs)]
+    lib.oakgpu_build_trainer_accumulate_dev.argtypes = [vp, vp, chunk_p]
+    lib.oakgpu_build_trainer_zero_gradients_dev.argtypes = [vp, vp]
+    lib.oakgpu_build_trainer_adam_dev.argtypes = [vp, vp, C.c_float]
+    lib.oakgpu_build_trainer_average_dev.argtypes = [vp, vp, f64]
+    lib.oakgpu_build_trainer_report.argtypes = [vp, vp, C.POINTER(BuildTrainReport)]
+    lib.oakgpu_build_trainer_read.argtypes = [vp, vp, i32, vp, sz]
+    lib.oakgpu_build_trainer_set_gradients.argtypes = [vp, vp, vp, sz]
+    lib.oakgpu_build_trainer_net_bytes.argtypes = [vp, vp, i32, vp, sz, C.POINTER(sz)]
     _lib = lib
     return lib
 

@@ -422,3 +422,143 @@ def dense_state(ctx, targets, lo, hi):
     out = np.empty((hi - lo, N_DIM), np.float32)
     _lib.check(ctx.lib.oakgpu_build_state_dense(ctx.handle, _ptr(np.ascontiguousarray(cells)), _ptr(np.ascontiguousarray(counts)), lo, hi, _ptr(out)))
     return out
+
+
+# ---- training the build network: build.py's optimiser step on the device (oak_amd/csrc/buildtrain.hip) ------------------------------------
+TRAINER_SEGMENT = 256      # OAKGPU_BUILD_TRAINER_SEGMENT: entries of one piece of a cell's segment in the transposed sparse products
+TRAINER_PARTS = ("parameters", "gradients", "m", "v", "average")
+TRAINER_TENSORS = tuple("%s.fc%d.%s" % (net, k, part) for net in ("policy", "value") for k in (1, 2, 3) for part in ("bias", "weight"))
+
+
+def check_trainer(data, max_traj=1):
+    """The refusals of Trainer, by name, without a GPU."""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    _lib.check(_lib.load().oakgpu_build_trainer_check(buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, int(max_traj)))
+
+
+class Trainer:
+    """The optimiser step of the reference's build.py on the device, for the three-layer nets this project's rollout reads (a `.build.net`;
+    NOT build.py's two-layer EmbeddingNets, which the reference's own reader cannot load): forward on the valid rows of a chunk of decoded
+    trajectories, the loss with GAE, its exact gradient accumulated over chunks, torch.optim.Adam and the rolling average.  The rule is in
+    include/oakgpu.h, "Training the build network".  A chunk is (traj, targets) as TrajectoryCorpus.decode / sample (untrimmed, with the
+    mask) and build.targets return them on the device.  Every call but report / read / net_bytes is asynchronous on the context's stream."""
+
+    def __init__(self, ctx, bytes_or_path, max_traj):
+        data = bytes_or_path if isinstance(bytes_or_path, (bytes, bytearray, memoryview)) else open(bytes_or_path, "rb").read()
+        buf = np.frombuffer(bytes(data), np.uint8)
+        self.ctx, self.handle = ctx, C.c_void_p()
+        _lib.check(ctx.lib.oakgpu_build_trainer_create(ctx.handle, buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, int(max_traj), C.byref(self.handle)))
+        dims, count, cap = (C.c_uint32 * 12)(), C.c_size_t(0), C.c_uint32(0)
+        _lib.check(ctx.lib.oakgpu_build_trainer_shape(self.handle, C.byref(dims), C.byref(count), C.byref(cap)))
+        self.dims = [(int(dims[2 * k]), int(dims[2 * k + 1])) for k in range(6)]
+        self.count, self.max_traj = int(count.value), int(cap.value)
+        self.policy_hidden, self.value_hidden = self.dims[0][1], (self.dims[3][1], self.dims[4][1])
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.oakgpu_build_trainer_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chunk(self, traj, targets, keep, gamma, lam, policy_loss_weight, value_loss_weight, entropy_loss_weight, total, remaining):
+        mask = traj["mask"]
+        code = {8: 0, 2: 1}[mask.element_size()]
+        n, v = int(traj["action"].shape[0]), int(targets["n_valid"])
+        total = v if total is None else int(total)
+        held = [mask.contiguous(), traj["n_legal"].contiguous(), targets["valid"].contiguous(), targets["rewards"].contiguous(), targets["rows"].contiguous(),
+                targets["state_cells"].contiguous(), targets["state_n"].contiguous(), None if keep is None else keep.contiguous()]
+        if held[7] is not None and held[7].element_size() != 1:
+            raise ValueError("keep must be a bool or uint8 tensor of one entry per valid row")
+        ptr = [None if x is None else x.data_ptr() for x in held]
+        c = _lib.BuildChunk(ptr[0], code, n, ptr[1], ptr[2], ptr[3], v, ptr[4], ptr[5], ptr[6], ptr[7], float(gamma), float(gamma) * float(lam),
+                            float(policy_loss_weight), float(value_loss_weight), float(entropy_loss_weight), max(total, 1),
+                            max(total, 1) if remaining is None else max(int(remaining), 0))
+        return c, held, mask.device, v
+
+    def forward(self, traj, targets, keep=None, gamma=0.99, lam=0.95, policy_loss_weight=1.0, value_loss_weight=0.5, entropy_loss_weight=0.01, total=None,
+                remaining=None, out=None):
+        """The forward outputs of every valid row: logits [V, 339] (NaN beyond n_legal), value, logp, gae, returns, forced f32 [V], selected
+        uint8 [V], du f32 [V] (the loss's gradient at the value net's output before the sigmoid).  total None: V; remaining None: total.  out: the same dict preallocated by the caller."""
+        import torch
+        c, held, device, v = self._chunk(traj, targets, keep, gamma, lam, policy_loss_weight, value_loss_weight, entropy_loss_weight, total, remaining)
+        if out is None:
+            out = {name: torch.empty((v,), dtype=torch.float32, device=device) for name in ("value", "logp", "gae", "returns", "forced", "du")}
+            out["logits"] = torch.empty((v, MAX_ACTIONS), dtype=torch.float32, device=device)
+            out["selected"] = torch.empty((v,), dtype=torch.uint8, device=device)
+        o = _lib.BuildTrainOutputs()
+        for name in out:
+            setattr(o, name, out[name].data_ptr())
+        _on_stream(self.ctx, device, lambda: self.ctx.lib.oakgpu_build_trainer_forward_dev(self.ctx.handle, self.handle, C.byref(c), C.byref(o)))
+        return out
+
+    def accumulate(self, traj, targets, keep=None, gamma=0.99, lam=0.95, policy_loss_weight=1.0, value_loss_weight=0.5, entropy_loss_weight=0.01, total=None,
+                   remaining=None):
+        """loss.backward() of one chunk: its gradient is formed on its own and added to the gradient block."""
+        c, held, device, _ = self._chunk(traj, targets, keep, gamma, lam, policy_loss_weight, value_loss_weight, entropy_loss_weight, total, remaining)
+        _on_stream(self.ctx, device, lambda: self.ctx.lib.oakgpu_build_trainer_accumulate_dev(self.ctx.handle, self.handle, C.byref(c)))
+
+    def zero_gradients(self):
+        _lib.check(self.ctx.lib.oakgpu_build_trainer_zero_gradients_dev(self.ctx.handle, self.handle))
+
+    def adam(self, lr):
+        """torch.optim.Adam's defaults over all twelve tensors at lr."""
+        _lib.check(self.ctx.lib.oakgpu_build_trainer_adam_dev(self.ctx.handle, self.handle, float(lr)))
+
+    def average(self, gamma):
+        """rolling_average: average = average * gamma + (1 - gamma) * parameters."""
+        _lib.check(self.ctx.lib.oakgpu_build_trainer_average_dev(self.ctx.handle, self.handle, float(gamma)))
+
+    def report(self):
+        """Of the last forward / accumulate -- the only call that waits: {"rows" (V), "kept" (k), "n_cap", "policy_loss", "value_loss",
+        "entropy", "loss", "steps"}."""
+        r = _lib.BuildTrainReport()
+        _lib.check(self.ctx.lib.oakgpu_build_trainer_report(self.ctx.handle, self.handle, C.byref(r)))
+        return {name: getattr(r, name) for name in ("rows", "kept", "n_cap", "policy_loss", "value_loss", "entropy", "loss", "steps")}
+
+    def split(self, flat):
+        """A flat block in file order -> {name: array} over TRAINER_TENSORS (views; weights [out, in])."""
+        out, at = {}, 0
+        for k, (i, o) in enumerate(self.dims):
+            out[TRAINER_TENSORS[2 * k]] = flat[at:at + o]
+            out[TRAINER_TENSORS[2 * k + 1]] = flat[at + o:at + o + o * i].reshape(o, i)
+            at += o * (i + 1)
+        return out
+
+    def read(self, which="parameters"):
+        """One of TRAINER_PARTS as {name: float32 array} in file order (weights [out, in])."""
+        flat = np.empty(self.count, np.float32)
+        _lib.check(self.ctx.lib.oakgpu_build_trainer_read(self.ctx.handle, self.handle, TRAINER_PARTS.index(which), flat.ctypes.data_as(C.c_void_p), flat.size))
+        return self.split(flat)
+
+    def set_gradients(self, grads):
+        """grads: a flat float32 array of `count` entries in file order, a scalar, or a dict as read() returns it."""
+        if isinstance(grads, dict):
+            flat = np.concatenate([np.asarray(grads[name], np.float32).reshape(-1) for name in TRAINER_TENSORS])
+        else:
+            flat = np.ascontiguousarray(np.broadcast_to(np.asarray(grads, np.float32), (self.count,)) if np.ndim(grads) == 0 else np.asarray(grads, np.float32))
+        flat = np.ascontiguousarray(flat)
+        _lib.check(self.ctx.lib.oakgpu_build_trainer_set_gradients(self.ctx.handle, self.handle, flat.ctypes.data_as(C.c_void_p), flat.size))
+
+    def net_bytes(self, which="net"):
+        """The bytes of a `.build.net`: the parameters ("net") or the rolling average ("average")."""
+        code = {"net": 0, "parameters": 0, "average": 4}[which]
+        size = C.c_size_t(0)
+        _lib.check(self.ctx.lib.oakgpu_build_trainer_net_bytes(self.ctx.handle, self.handle, code, None, 0, C.byref(size)))
+        buf = np.empty(size.value, np.uint8)
+        _lib.check(self.ctx.lib.oakgpu_build_trainer_net_bytes(self.ctx.handle, self.handle, code, buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(size)))
+        return buf.tobytes()
+
+    def save(self, path, which="net"):
+        with open(path, "wb") as f:
+            f.write(self.net_bytes(which))
