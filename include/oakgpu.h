@@ -487,6 +487,35 @@ int oakgpu_forest_nodes(oakgpu_forest *forest, uint32_t tree, uint32_t first, ui
 /* Diagnostic: the schedule of the forest's last call -- iterations run, tree levels stepped (= tree-step launches), kernel launches
  * made (prep, steps, level kernels, evaluations, back-ups; an evaluation counts as one), host reads of the live count. */
 int oakgpu_forest_last_stats(const oakgpu_forest *forest, uint64_t out[4]);
+/* ---- per-tree budgets.  The four _budgets calls take their namesakes' arguments plus budgets: n x u32 (device memory for _dev, host
+ * memory otherwise) in front of n.  Tree g runs exactly budgets[g] iterations, 1 <= budgets[g] <= params->iterations <= max_iterations;
+ * params->iterations sizes the trace, the loop runs max(budgets) iterations.
+ *   Contract.  Every output of tree g -- m, n, choices, both root matrices, iterations, nodes, total_depth, initial value, logits, priors,
+ *   the continuing stream -- and every node of it is bit for bit what the call without budgets gives that tree with iterations =
+ *   budgets[g] and the same seed: UCB and PUCB, all three evaluators, plain and kept forests.  Trace records (g, t >= budgets[g]) are
+ *   not written.  A tree whose budget is spent is inert for the rest of the call (a state of its own, not the error lane's): it selects
+ *   and visits nothing, is not counted live, touches neither its root matrices nor its trace, and its stream is the one it had after its
+ *   last iteration, whatever later launches over its row draw.
+ *   Rows.  Iteration t launches root prep, the level kernels, the tree step, the evaluator and the back-up over the rows [0, n_t) only, n_t
+ *   = 1 + max{g : budgets[g] > t}: with budgets non-increasing in row order no launch covers a finished tree; any other order costs the
+ *   saving and nothing else.  oakgpu_forest_last_rows: out[0] = tree-iterations launched (the sum of the n_t), out[1] = tree-iterations
+ *   run (the sum of the budgets) of the forest's last search; both n * iterations after a call without budgets.
+ *   Refused by name before any launch, naming the lowest offending tree: a budget of 0, a budget above params->iterations
+ *   (oakgpu_forest_budgets_check, host only).  _dev copies the budgets to the host once, with the result bytes. */
+int oakgpu_forest_budgets_check(const uint32_t *budgets, uint32_t n, uint64_t iterations);
+int oakgpu_forest_search_budgets_dev(oakgpu_forest *forest, oakgpu_net *net, const oakgpu_search_params *params, const uint8_t *battles,
+                                     const uint8_t *durations, const uint8_t *results, const uint64_t *seeds, const uint32_t *budgets, uint32_t n,
+                                     const oakgpu_forest_outputs *dev_out, void *trace, uint32_t trace_levels);
+int oakgpu_forest_search_budgets(oakgpu_forest *forest, oakgpu_net *net, const oakgpu_search_params *params, const uint8_t *battles,
+                                 const uint8_t *durations, const uint8_t *results, const uint64_t *seeds, const uint32_t *budgets, uint32_t n,
+                                 oakgpu_search_output *out, int solve_nash, uint64_t *streams_out, void *trace, uint32_t trace_levels);
+int oakgpu_forest_search_budgets_kept_dev(oakgpu_forest *forest, oakgpu_net *net, const oakgpu_search_params *params, const uint8_t *battles,
+                                          const uint8_t *durations, const uint8_t *results, const uint64_t *seeds, const uint32_t *budgets, uint32_t n,
+                                          const oakgpu_forest_outputs *dev_out, void *trace, uint32_t trace_levels);
+int oakgpu_forest_search_budgets_kept(oakgpu_forest *forest, oakgpu_net *net, const oakgpu_search_params *params, const uint8_t *battles,
+                                      const uint8_t *durations, const uint8_t *results, const uint64_t *seeds, const uint32_t *budgets, uint32_t n,
+                                      oakgpu_search_output *out, int solve_nash, uint64_t *streams_out, void *trace, uint32_t trace_levels);
+int oakgpu_forest_last_rows(const oakgpu_forest *forest, uint64_t out[2]);
 
 /* ---- kept forests: a tree goes on into the next turn (generate's --keep-node: generate.cc:324-333, Heap::update in search.cc:27-52).
  * oakgpu_forest_create_kept makes a forest whose trees hold keep_arena nodes each (>= max_iterations + 1; 0 = 4 * max_iterations + 1) and
@@ -827,6 +856,16 @@ typedef struct {
   int32_t keep_node;           /* generate's --keep-node (generate.cc:324-333): one heap for the game, Heap::update with the played
                                 * indices and the observation after every turn (the subtree is searched on); 0 = a fresh heap per turn */
   uint32_t nodes_kept;         /* out: how many of the game's updates found their child (RuntimeData::update_with_node_counter) */
+  /* Fast searches (generate's --fast-budget / --fast-search-prob, generate.cc:292-299; rl.py trains with --min-iterations = fast_budget
+   * + 1, so only the full-budget frames reach the loss).  With fast_search_prob > 0 every turn starts with use_fast = uniform01(rng) <
+   * fast_search_prob on the game's stream, BEFORE the search seed is drawn; a fast turn is searched with fast_budget iterations and
+   * picked with fast_policy_mode, every other turn with search.iterations and policy_mode; the frame stores the iterations that ran, and
+   * every frame is written.  The rule is oak_amd/csrc/selfplay_pick.hpp's turn_prelude, one text for the host and the device loop.
+   * Two departures from the reference: the draw comes from the game's own stream (the reference: the worker thread's device), and it is
+   * skipped when fast_search_prob is 0 -- all zeros is a game without fast searches, byte for byte. */
+  uint32_t fast_budget;        /* 0 = search.iterations */
+  double fast_search_prob;     /* 0 = off */
+  char fast_policy_mode[16];   /* "" = policy_mode */
 } oakgpu_selfplay_params;
 /* endless_battle_check (cpp/src/generate.cc:127-152): 1 when every pairing of the two teams (2 x 6 x {species, 4 moves}) is a Ghost against a
  * Ghost with no move on either side that can hit a Ghost (type Normal / Fighting or base power 0) -- with ebc=false such a game runs to turn
@@ -896,6 +935,20 @@ int oakgpu_forest_selfplay_last_traffic(const oakgpu_forest *forest, uint64_t ou
  * A game is the host loop's game with keep_node = 1 as long as no tree is dropped for want of room (see oakgpu_forest_advance_dev), which
  * _keep_stats reports: out = { sum of nodes_kept, trees dropped, root mismatches, nodes carried into the turns' searches } of the last call. */
 int oakgpu_forest_selfplay_nodes_kept(oakgpu_forest *forest, uint32_t *nodes_kept, int to_device);
+/* Fast searches on the forest (params->fast_search_prob > 0; the rule is with oakgpu_selfplay_params).  The flag is drawn with the turn
+ * prelude; the turn's compaction becomes a stable two-class partition -- the live rows of the larger budget first, those of the smaller
+ * after -- so the turn's ONE oakgpu_forest_search_budgets(_kept)_dev gets non-increasing budgets and launches exactly the tree-iterations
+ * it runs; with keep_node the trees follow their rows through the advance's source-row list.  With fast_search_prob == 0 the order, the
+ * calls and the bytes are those of a call without the fields.  The per-turn host read stays the one of the live count.
+ * _check also refuses by name: fast_search_prob outside [0, 1] or NaN, fast_budget above max_iterations, and a fast_policy_mode that
+ * policy_mode would be refused for (an 'n' word without solve_nash included).
+ * _fast_stats: out = { fast frames, full frames (both of the records kept), tree-iterations launched, tree-iterations run } of the last call.
+ * _set_partition(0) (benchmarks only: tools/fast_search_bench.py's control run) leaves the rows of the forest's NEXT self-play call in game
+ * order, so that launched exceeds run; the call after it partitions again. */
+int oakgpu_forest_selfplay_fast_stats(oakgpu_forest *forest, uint64_t out[4]);
+int oakgpu_forest_selfplay_set_partition(oakgpu_forest *forest, int on);
+/* host only: selfplay_pick.hpp's turn prelude on one stream -- *rng advances, *use_fast and *search_seed are the turn's */
+int oakgpu_selfplay_prelude_host(uint64_t *rng, double fast_search_prob, int32_t *use_fast, uint64_t *search_seed);
 int oakgpu_forest_selfplay_keep_stats(const oakgpu_forest *forest, uint64_t out[4]);
 int oakgpu_selfplay_pick_host(uint32_t m, uint32_t n, const uint64_t *visit_matrix, const double *value_matrix, uint64_t iterations,
                               const double *p1_nash, const double *p2_nash, double nash_value, const double *p1_prior, const double *p2_prior,

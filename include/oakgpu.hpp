@@ -325,9 +325,13 @@ public:
   ~SearchForest() { oakgpu_forest_destroy(ctx_.get(), f_); }
   SearchForest(const SearchForest &) = delete;
   SearchForest &operator=(const SearchForest &) = delete;
+  // budgets (empty, or one per root): tree g runs budgets[g] <= params.iterations iterations and is, bit for bit, the tree of a search with
+  // iterations = budgets[g] (oakgpu_forest_search_budgets*); rows of non-increasing budgets cost no launch over a finished tree
   std::vector<oakgpu_search_output> search(const oakgpu_search_params &params, const std::vector<Leaf> &roots, const std::vector<uint64_t> &seeds,
-                                           Network *net = nullptr, int solve_nash = NASH_NONE, std::vector<uint64_t> *streams = nullptr, bool keep = false) {
+                                           Network *net = nullptr, int solve_nash = NASH_NONE, std::vector<uint64_t> *streams = nullptr, bool keep = false,
+                                           const std::vector<uint32_t> &budgets = {}) {
     if (seeds.size() != roots.size()) throw std::runtime_error{"oakgpu: SearchForest::search: one seed per root"};
+    if (!budgets.empty() && budgets.size() != roots.size()) throw std::runtime_error{"oakgpu: SearchForest::search: one budget per root"};
     const uint32_t n = (uint32_t)roots.size();
     std::vector<uint8_t> b((size_t)n * OAKGPU_BATTLE_SIZE), d((size_t)n * OAKGPU_DURATIONS_SIZE), r(n);
     for (uint32_t g = 0; g < n; ++g) {
@@ -337,8 +341,13 @@ public:
     }
     std::vector<oakgpu_search_output> out(n);
     if (streams) streams->assign(n, 0);
-    check((keep ? oakgpu_forest_search_kept : oakgpu_forest_search)(f_, net ? net->get() : nullptr, &params, b.data(), d.data(), r.data(), seeds.data(), n,
-                                                                    out.data(), solve_nash, streams ? streams->data() : nullptr, nullptr, 0));
+    if (!budgets.empty())
+      check((keep ? oakgpu_forest_search_budgets_kept : oakgpu_forest_search_budgets)(f_, net ? net->get() : nullptr, &params, b.data(), d.data(), r.data(), seeds.data(),
+                                                                                      budgets.data(), n, out.data(), solve_nash, streams ? streams->data() : nullptr,
+                                                                                      nullptr, 0));
+    else
+      check((keep ? oakgpu_forest_search_kept : oakgpu_forest_search)(f_, net ? net->get() : nullptr, &params, b.data(), d.data(), r.data(), seeds.data(), n,
+                                                                      out.data(), solve_nash, streams ? streams->data() : nullptr, nullptr, 0));
     return out;
   }
   // Heap::update of every tree and its move to another row (a kept forest): new tree t continues tree src[t] (src empty: tree t) along the
@@ -363,6 +372,18 @@ public:
   void search_dev(const oakgpu_search_params &params, const uint8_t *battles, const uint8_t *durations, const uint8_t *results, const uint64_t *seeds,
                   uint32_t n, const oakgpu_forest_outputs &dev_out, Network *net = nullptr) {
     check(oakgpu_forest_search_dev(f_, net ? net->get() : nullptr, &params, battles, durations, results, seeds, n, &dev_out, nullptr, 0));
+  }
+  // the budgets forms over device arrays (budgets: n x u32 on the device)
+  void search_budgets_dev(const oakgpu_search_params &params, const uint8_t *battles, const uint8_t *durations, const uint8_t *results, const uint64_t *seeds,
+                          const uint32_t *budgets, uint32_t n, const oakgpu_forest_outputs &dev_out, Network *net = nullptr, bool keep = false) {
+    check((keep ? oakgpu_forest_search_budgets_kept_dev : oakgpu_forest_search_budgets_dev)(f_, net ? net->get() : nullptr, &params, battles, durations, results, seeds,
+                                                                                            budgets, n, &dev_out, nullptr, 0));
+  }
+  // tree-iterations of the last search: launched (the sum of the iterations' row counts), run (the sum of the budgets)
+  std::array<uint64_t, 2> last_rows() const {
+    std::array<uint64_t, 2> out{};
+    check(oakgpu_forest_last_rows(f_, out.data()));
+    return out;
   }
   // `count` node records of one tree of the last call, from node `first`, in creation order (the root is node 0)
   std::vector<oakgpu_forest_node> nodes(uint32_t tree, uint32_t first, uint32_t count) {
@@ -391,9 +412,11 @@ public:
     std::array<uint64_t, 4> stats{}; // turns looped, rows searched summed over turns, compactions, host reads
     std::vector<uint32_t> nodes_kept;      // params.keep_node: per game, the updates that found their child (oakgpu_selfplay_params::nodes_kept); else zeros
     std::array<uint64_t, 4> keep_stats{};  // params.keep_node: sum of nodes_kept, trees dropped for want of room, root mismatches, nodes carried in
+    std::array<uint64_t, 4> fast_stats{};  // params.fast_search_prob: fast frames, full frames, tree-iterations launched, tree-iterations run
   };
   explicit ForestSelfplay(SearchForest &forest) : forest_{forest} {}
-  // teams: n x 60 bytes; params.search.seed / batch and params.seed are ignored; keep_node = 1 needs a forest made with keep_arena
+  // teams: n x 60 bytes; params.search.seed / batch and params.seed are ignored; keep_node = 1 needs a forest made with keep_arena;
+  // params.fast_budget / fast_search_prob / fast_policy_mode: generate's fast searches (the forest's max_iterations covers both budgets)
   Result play(const oakgpu_selfplay_params &params, const std::vector<uint8_t> &teams, const std::vector<uint64_t> &battle_seeds,
               const std::vector<uint64_t> &seeds, Network *net = nullptr, int solve_nash = NASH_HOST) {
     const uint32_t n = (uint32_t)seeds.size();
@@ -412,6 +435,7 @@ public:
     check(oakgpu_forest_selfplay_nodes_kept(forest_.get(), out.nodes_kept.data(), 0));
     out.nodes_kept.resize(n);
     check(oakgpu_forest_selfplay_keep_stats(forest_.get(), out.keep_stats.data()));
+    check(oakgpu_forest_selfplay_fast_stats(forest_.get(), out.fast_stats.data()));
     return out;
   }
 

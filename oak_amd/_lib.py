@@ -42,6 +42,9 @@ SYMBOLS = [
     "oakgpu_forest_selfplay_nodes_kept", "oakgpu_forest_selfplay_keep_stats",
     "oakgpu_nash_solve_dev", "oakgpu_solve_matrices", "oakgpu_nash_soft_host", "oakgpu_nash_round_host", "oakgpu_nash_width4_max_entry",
     "oakgpu_forest_selfplay_last_traffic",
+    "oakgpu_forest_budgets_check", "oakgpu_forest_search_budgets_dev", "oakgpu_forest_search_budgets", "oakgpu_forest_search_budgets_kept_dev",
+    "oakgpu_forest_search_budgets_kept", "oakgpu_forest_last_rows", "oakgpu_forest_selfplay_fast_stats", "oakgpu_forest_selfplay_set_partition",
+    "oakgpu_selfplay_prelude_host",
     "oakgpu_frames_symmetries_dev", "oakgpu_trainer_check", "oakgpu_trainer_create", "oakgpu_trainer_destroy", "oakgpu_trainer_shape",
     "oakgpu_trainer_forward_dev", "oakgpu_trainer_gradients_dev", "oakgpu_trainer_adam_dev", "oakgpu_trainer_step_dev", "oakgpu_trainer_report",
     "oakgpu_trainer_read", "oakgpu_trainer_set_gradients", "oakgpu_trainer_net_bytes", "oakgpu_trainer_forward", "oakgpu_trainer_gradients",
@@ -101,7 +104,8 @@ class FrameUpdate(C.Structure):       # oakgpu_frame_update
 
 class SelfplayParams(C.Structure):    # oakgpu_selfplay_params
     _fields_ = [("search", SearchParams), ("policy_mode", C.c_char * 16), ("policy_temp", C.c_double), ("policy_min", C.c_double),
-                ("max_battle_length", C.c_uint32), ("seed", C.c_uint64), ("keep_node", C.c_int32), ("nodes_kept", C.c_uint32)]
+                ("max_battle_length", C.c_uint32), ("seed", C.c_uint64), ("keep_node", C.c_int32), ("nodes_kept", C.c_uint32),
+                ("fast_budget", C.c_uint32), ("fast_search_prob", C.c_double), ("fast_policy_mode", C.c_char * 16)]
 
 
 class EncodedFrames(C.Structure):     # oakgpu_encoded_frames: one pointer per tensor, device or host as the call says
@@ -420,6 +424,12 @@ def load():
     lib.oakgpu_forest_search_kept_dev.argtypes = lib.oakgpu_forest_search_dev.argtypes
     lib.oakgpu_forest_search_kept.argtypes = lib.oakgpu_forest_search.argtypes
     lib.oakgpu_forest_keep_stats.argtypes = [vp, C.POINTER(u64 * 4)]
+    lib.oakgpu_forest_budgets_check.argtypes = [vp, u32, u64]
+    lib.oakgpu_forest_search_budgets_dev.argtypes = [vp, vp, C.POINTER(SearchParams), vp, vp, vp, vp, vp, u32, C.POINTER(ForestOutputs), vp, u32]
+    lib.oakgpu_forest_search_budgets.argtypes = [vp, vp, C.POINTER(SearchParams), vp, vp, vp, vp, vp, u32, C.POINTER(SearchOutput), i32, vp, vp, u32]
+    lib.oakgpu_forest_search_budgets_kept_dev.argtypes = lib.oakgpu_forest_search_budgets_dev.argtypes
+    lib.oakgpu_forest_search_budgets_kept.argtypes = lib.oakgpu_forest_search_budgets.argtypes
+    lib.oakgpu_forest_last_rows.argtypes = [vp, C.POINTER(u64 * 2)]
     lib.oakgpu_forest_mismatch.argtypes = [vp, vp, u32, i32]
     lib.oakgpu_forest_node_counts.argtypes = [vp, vp, u32, i32]
     lib.oakgpu_search_stream.argtypes = [vp, C.POINTER(u64)]
@@ -432,6 +442,9 @@ def load():
     lib.oakgpu_forest_selfplay_last_traffic.argtypes = [vp, C.POINTER(u64 * 2)]
     lib.oakgpu_forest_selfplay_nodes_kept.argtypes = [vp, vp, i32]
     lib.oakgpu_forest_selfplay_keep_stats.argtypes = [vp, C.POINTER(u64 * 4)]
+    lib.oakgpu_forest_selfplay_fast_stats.argtypes = [vp, C.POINTER(u64 * 4)]
+    lib.oakgpu_forest_selfplay_set_partition.argtypes = [vp, i32]
+    lib.oakgpu_selfplay_prelude_host.argtypes = [C.POINTER(u64), C.c_double, C.POINTER(i32), C.POINTER(u64)]
     lib.oakgpu_selfplay_pick_host.argtypes = [u32, u32, vp, vp, u64, vp, vp, C.c_double, vp, vp, vp, vp, C.c_char_p, C.c_double, C.c_double, C.POINTER(u64),
                                               C.POINTER(C.c_double), vp, vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.POINTER(u32)]
     lib.oakgpu_forest_match_check.argtypes = [u32, u32, i32, C.POINTER(ForestMatchParams), u32]

@@ -28,11 +28,20 @@
 // resolves in one ascending pass over ids, 64 at a time; the new id of a kept node is the count of kept nodes below it.  The kept edges
 // are re-inserted with renumbered ends under a new stamp.  The kept form of the search (k_forest_begin with keep = 1) leaves an
 // initialised root with the position's choice counts alone and runs on under the stamp the advance wrote.
+//
+// Per-tree budgets (oakgpu_forest_search_budgets*; self-play's fast searches).  Tree g runs budgets[g] iterations and must be, bit for bit, the
+// tree of a call with that many.  Its last back-up marks it ST_DONE and writes its stream to the outputs, because the launches that still
+// cover its row go on drawing from prng[g] (root prep, the Monte-Carlo evaluator).  A done tree is inert: k_forest_level(0) does not revive it
+// and leaves c1 / c2 = 0xFF for the tree step, it is not counted live, and the back-up returns before it touches bandits, root matrices or
+// trace.  The host knows the budgets (one copy, with the result bytes), so iteration t launches every kernel over rows [0, n_t) only, n_t = one
+// past the last tree with budgets[g] > t; the path stride stays the call's n.  Budgets that do not increase in row order (the game loop's
+// partition) therefore cost no launch over a finished tree.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <chrono>
 #include <string>
 #include <vector>
@@ -58,7 +67,9 @@ static_assert(sizeof(FEdge) == 32, "one edge slot is 32 bytes");
 static_assert(offsetof(FEdge, i) == 24 && offsetof(FEdge, j) == 25 && offsetof(FEdge, gen) == 26, "i, j and the stamp share the slot's dword 6");
 static_assert(sizeof(oakgpu_forest_trace_head) == 88 && sizeof(oakgpu_forest_trace_level) == 8, "trace record layout");
 
-enum : uint8_t { ST_WALK = 0, ST_TERMINAL = 1, ST_LEAF = 2, ST_DEAD = 3 };
+// ST_DONE: a tree whose own budget is spent (the budgets calls): inert for the rest of the call -- it selects nothing, visits nothing, is not
+// counted live and keeps c1 / c2 = 0xFF for the tree step -- where ST_DEAD is an error lane
+enum : uint8_t { ST_WALK = 0, ST_TERMINAL = 1, ST_LEAF = 2, ST_DEAD = 3, ST_DONE = 4 };
 enum : uint32_t { ERR_ARENA_FULL = 1, ERR_TABLE_FULL = 2 };
 constexpr uint32_t NONE = OAKGPU_FOREST_NO_NODE;
 constexpr int FBLOCK = 64;
@@ -120,7 +131,7 @@ __global__ __launch_bounds__(FBLOCK) void k_forest_level(ForestArgs a, uint32_t 
     uint32_t node = 0;
     const uint8_t st = a.status[lane];
     if (depth == 0) {
-      if (st != ST_DEAD) { go = true; a.status[lane] = ST_WALK; a.levels[lane] = 0; }
+      if (st != ST_DEAD && st != ST_DONE) { go = true; a.status[lane] = ST_WALK; a.levels[lane] = 0; }
       else { a.c1[lane] = 0xFF; a.c2[lane] = 0xFF; }
     } else if (st == ST_WALK) {
       if ((a.results[lane] & 15) != 0) { // terminal edge: the value comes from the result byte (mcts.h:427-441)
@@ -235,18 +246,26 @@ struct BackupArgs {
   FNode *nodes;
   uint32_t arena, n, stride, pucb, eval, iteration, iterations, trace_levels;
   const uint32_t *leaf, *levels, *path_node;
-  const uint8_t *status, *path_i, *path_j, *results, *cnt1, *cnt2;
+  uint8_t *status;
+  const uint8_t *path_i, *path_j, *results, *cnt1, *cnt2;
   const float *values, *pe_root, *pe_score, *l1, *l2;
   uint64_t *visit_matrix;
   double *value_matrix;
   uint8_t *trace;
   BanditParams P;
+  // the budgets calls (else null): tree g runs budgets[g] iterations; after its last one it is ST_DONE and its stream, which later launches
+  // over its row would advance, goes to the outputs here
+  const uint32_t *budgets;
+  const uint64_t *prng;
+  uint64_t *stream_out;
 };
 
 // End of an iteration: the leaf's init (+ set_logits) at its first evaluation, Bandit::update along the path, the root matrices.
 __global__ __launch_bounds__(FBLOCK) void k_forest_backup(BackupArgs a) {
   const uint32_t lane = blockIdx.x * FBLOCK + threadIdx.x;
   if (lane >= a.n) return;
+  const uint32_t budget = a.budgets ? a.budgets[lane] : a.iterations;
+  if (a.iteration >= budget) return; // a finished tree inside the launch's rows: no update, no root cell, no trace record
   const uint8_t st = a.status[lane];
   const uint32_t L = st == ST_DEAD ? 0 : a.levels[lane];
   const uint32_t t = a.results[lane] & 15;
@@ -295,16 +314,21 @@ __global__ __launch_bounds__(FBLOCK) void k_forest_backup(BackupArgs a) {
       lv[d] = x;
     }
   }
+  if (a.budgets && a.iteration + 1 == budget) {
+    if (st != ST_DEAD) a.status[lane] = ST_DONE;
+    a.stream_out[lane] = a.prng[lane];
+  }
 }
 
+// budgets (nullable): the tree's own iteration count; its stream was written by its last back-up
 __global__ __launch_bounds__(FBLOCK) void k_forest_finish(uint32_t n, uint64_t iterations, const uint32_t *n_nodes, const uint64_t *total_depth, const uint64_t *prng,
-                                                          oakgpu_forest_outputs out) {
+                                                          const uint32_t *budgets, oakgpu_forest_outputs out) {
   const uint32_t lane = blockIdx.x * FBLOCK + threadIdx.x;
   if (lane >= n) return;
-  out.iterations[lane] = iterations;
+  out.iterations[lane] = budgets ? (uint64_t)budgets[lane] : iterations;
   out.nodes[lane] = n_nodes[lane];
   out.total_depth[lane] = total_depth[lane];
-  out.stream[lane] = prng[lane];
+  if (!budgets) out.stream[lane] = prng[lane];
 }
 
 struct AdvanceArgs {
@@ -458,6 +482,8 @@ struct oakgpu_forest {
   uint8_t *stage = nullptr, *trace_stage = nullptr;
   size_t trace_stage_bytes = 0;
   uint64_t stats[4] = {0, 0, 0, 0};
+  uint64_t rows[2] = {0, 0};  // the last search's tree-iterations: launched (the sum of the iterations' row counts) and run (the sum of the budgets)
+  uint32_t *budget_stage = nullptr; // the host-array budgets calls' staging (made by their first use)
   // a kept forest (oakgpu_forest_create_kept): the back copy of arenas, tables and node counts that k_forest_advance writes and that then
   // becomes the front (nodes / edges / n_nodes above); `valid` = the trees of the front copy that hold what a call left
   bool kept = false;
@@ -491,6 +517,7 @@ struct oakgpu_forest {
     if (ctl) (void)hipFree(ctl);
     if (stage) (void)hipFree(stage);
     if (trace_stage) (void)hipFree(trace_stage);
+    if (budget_stage) (void)hipFree(budget_stage);
     if (h_live) (void)hipHostFree(h_live);
   }
 };
@@ -648,10 +675,30 @@ int oakgpu_forest_last_stats(const oakgpu_forest *f, uint64_t out[4]) {
   return 0;
 }
 
-// the body of both device searches: keep = the kept form (an initialised root goes on; the stamp is the one the advance wrote)
+int oakgpu_forest_last_rows(const oakgpu_forest *f, uint64_t out[2]) {
+  if (!f || !out) return oakgpu_fail_msg("oakgpu_forest_last_rows: null argument");
+  out[0] = f->rows[0]; out[1] = f->rows[1];
+  return 0;
+}
+
+int oakgpu_forest_budgets_check(const uint32_t *budgets, uint32_t n, uint64_t iterations) {
+  if (!budgets && n) return oakgpu_fail_msg("oakgpu_forest_search_budgets: null argument");
+  for (uint32_t g = 0; g < n; ++g) {
+    if (budgets[g] == 0) return oakgpu_fail_msg(("oakgpu_forest_search_budgets: the budget of tree " + std::to_string(g) + " is 0 (a tree runs 1 .. params->iterations iterations)").c_str());
+    if (budgets[g] > iterations)
+      return oakgpu_fail_msg(("oakgpu_forest_search_budgets: the budget of tree " + std::to_string(g) + " (" + std::to_string(budgets[g]) + ") exceeds params->iterations (" +
+                              std::to_string(iterations) + ")").c_str());
+  }
+  return 0;
+}
+
+// the body of the device searches: keep = the kept form (an initialised root goes on; the stamp is the one the advance wrote); budgets
+// (device, n x u32; null = every tree runs params->iterations) = the budgets form
 static int forest_search_body(oakgpu_forest *f, oakgpu_net *net, const oakgpu_search_params *prm, const uint8_t *battles, const uint8_t *durations,
-                              const uint8_t *results, const uint64_t *seeds, uint32_t n, const oakgpu_forest_outputs *o, void *trace, uint32_t trace_levels, bool keep) {
+                              const uint8_t *results, const uint64_t *seeds, uint32_t n, const oakgpu_forest_outputs *o, void *trace, uint32_t trace_levels, bool keep,
+                              const uint32_t *budgets = nullptr, bool with_budgets = false) {
   if (!f || !prm || !battles || !durations || !results || !seeds || !o) return oakgpu_fail_msg("oakgpu_forest_search: null argument");
+  if (with_budgets && !budgets && n) return oakgpu_fail_msg("oakgpu_forest_search_budgets: null argument");
   if (keep && !f->kept) return oakgpu_fail_msg("oakgpu_forest_search_kept: the forest was created without keep (oakgpu_forest_create_kept makes one that keeps its trees)");
   if (!o->m || !o->n || !o->p1_choices || !o->p2_choices || !o->visit_matrix || !o->value_matrix || !o->iterations || !o->nodes || !o->total_depth ||
       !o->initial_value || !o->p1_logit || !o->p2_logit || !o->p1_prior || !o->p2_prior || !o->stream)
@@ -661,15 +708,30 @@ static int forest_search_body(oakgpu_forest *f, oakgpu_net *net, const oakgpu_se
   oakgpu_ctx *ctx = f->ctx;
   RC(oakgpu_ctx_enter(ctx));
   hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(ctx);
+  std::vector<uint32_t> hb; // the budgets on the host: they ride with the result bytes
   { // a terminal root is refused before anything is launched: one copy of the n result bytes
     std::vector<uint8_t> h(n);
     HIPCHK(hipMemcpyAsync(h.data(), results, n, hipMemcpyDeviceToHost, stream));
+    if (budgets) { hb.resize(n); HIPCHK(hipMemcpyAsync(hb.data(), budgets, (size_t)n * 4, hipMemcpyDeviceToHost, stream)); }
     HIPCHK(hipStreamSynchronize(stream));
     RC(oakgpu_forest_check(f->max_trees, f->max_iterations, f->contextual, prm, net != nullptr, n, h.data(), trace != nullptr, trace_levels));
+    if (budgets) RC(oakgpu_forest_budgets_check(hb.data(), n, prm->iterations));
   }
   const bool pucb = prm->bandit == B_PUCB, use_net = prm->eval == 1, use_pe = prm->eval == 2;
   const uint32_t max_depth = prm->max_depth ? prm->max_depth : 100;
-  const uint32_t iterations = (uint32_t)prm->iterations;
+  // the loop runs max(budgets) iterations; iteration t covers rows [0, rows_at[t]): one past the last tree whose budget is above t
+  uint32_t iterations = (uint32_t)prm->iterations;
+  std::vector<uint32_t> rows_at;
+  uint64_t rows_launched = (uint64_t)n * iterations, rows_run = rows_launched;
+  if (budgets) {
+    iterations = *std::max_element(hb.begin(), hb.end());
+    rows_at.assign(iterations, 0);
+    rows_run = 0;
+    for (uint32_t g = 0; g < n; ++g) { rows_at[hb[g] - 1] = g + 1; rows_run += hb[g]; } // ascending g: the last writer is the highest row
+    for (uint32_t t = iterations - 1; t > 0; --t) rows_at[t - 1] = std::max(rows_at[t - 1], rows_at[t]);
+    rows_launched = 0;
+    for (uint32_t t = 0; t < iterations; ++t) rows_launched += rows_at[t];
+  }
   const BanditParams BP{prm->bandit, prm->ucb_c, 0.05f};
   if (f->path_levels < max_depth || !f->path_node) {
     HIPCHK(hipStreamSynchronize(stream));
@@ -718,22 +780,27 @@ static int forest_search_body(oakgpu_forest *f, oakgpu_net *net, const oakgpu_se
   A.results = f->r; A.act = f->act; A.ch1 = f->ch1; A.cnt1 = f->cnt1; A.ch2 = f->ch2; A.cnt2 = f->cnt2; A.root_ch1 = f->root_ch1; A.root_ch2 = f->root_ch2;
   A.c1 = f->c1; A.c2 = f->c2; A.ctl = f->ctl; A.total_depth = f->total_depth; A.P = BP; A.max_depth = max_depth;
   BackupArgs K{};
-  K.nodes = f->nodes; K.arena = f->arena; K.n = n; K.stride = n; K.pucb = pucb; K.eval = (uint32_t)prm->eval; K.iterations = iterations; K.trace_levels = trace_levels;
+  K.nodes = f->nodes; K.arena = f->arena; K.n = n; K.stride = n; K.pucb = pucb; K.eval = (uint32_t)prm->eval; K.iterations = (uint32_t)prm->iterations; K.trace_levels = trace_levels;
+  K.budgets = budgets; K.prng = f->prng; K.stream_out = o->stream;
   K.leaf = f->leaf; K.levels = f->levels; K.path_node = f->path_node; K.status = f->status; K.path_i = f->path_i; K.path_j = f->path_j;
   K.results = f->r; K.cnt1 = f->cnt1; K.cnt2 = f->cnt2; K.values = f->values; K.pe_root = f->pe_root; K.pe_score = f->pe_score; K.l1 = f->l1; K.l2 = f->l2;
   K.visit_matrix = o->visit_matrix; K.value_matrix = o->value_matrix; K.trace = (uint8_t *)trace; K.P = BP;
 
   for (uint32_t it = 0; it < iterations; ++it) {
+    // the iteration's rows (the outputs, the path stride and the finish cover the call's n); >= 1: some tree's budget is above `it`
+    const uint32_t rows = budgets ? rows_at[it] : n;
+    const dim3 row_grid((rows + FBLOCK - 1) / FBLOCK);
+    A.n = rows; K.n = rows;
     // root prep on the device (mcts.h:254-259): the rollout kernel with max_steps = 0, as the host search's begin_batch
-    RC(oakgpu_rollout_dev(ctx, battles, durations, results, (uint8_t *)f->prng, n, 0, 1, f->rout, f->steps, f->values, f->b, f->d));
-    HIPCHK(hipMemcpyAsync(f->r, results, n, hipMemcpyDeviceToDevice, stream));
+    RC(oakgpu_rollout_dev(ctx, battles, durations, results, (uint8_t *)f->prng, rows, 0, 1, f->rout, f->steps, f->values, f->b, f->d));
+    HIPCHK(hipMemcpyAsync(f->r, results, rows, hipMemcpyDeviceToDevice, stream));
     HIPCHK(hipMemsetAsync(f->ctl + 1, 0, (size_t)(max_depth + 1) * 4, stream));
-    hipLaunchKernelGGL(k_forest_level, grid, block, 0, stream, A, 0u);
+    hipLaunchKernelGGL(k_forest_level, row_grid, block, 0, stream, A, 0u);
     HIPCHK(hipGetLastError());
     launches += 2;
     for (uint32_t depth = 1; depth <= max_depth; ++depth) {
-      RC(oakgpu_tree_step_dev(ctx, f->b, f->d, f->r, f->c1, f->c2, n, depth == 1 ? prm->root_rolls : prm->other_rolls, f->act, f->ch1, f->cnt1, f->ch2, f->cnt2));
-      hipLaunchKernelGGL(k_forest_level, grid, block, 0, stream, A, depth);
+      RC(oakgpu_tree_step_dev(ctx, f->b, f->d, f->r, f->c1, f->c2, rows, depth == 1 ? prm->root_rolls : prm->other_rolls, f->act, f->ch1, f->cnt1, f->ch2, f->cnt2));
+      hipLaunchKernelGGL(k_forest_level, row_grid, block, 0, stream, A, depth);
       HIPCHK(hipGetLastError());
       launches += 2; ++levels_stepped;
       if (depth == max_depth) break; // no lane goes on below the cap
@@ -743,20 +810,21 @@ static int forest_search_body(oakgpu_forest *f, oakgpu_net *net, const oakgpu_se
       if (f->h_live[0] == 0) break;
     }
     // the leaf evaluation, over every row, as the host search's launch_eval
-    if (use_pe) RC(oakgpu_poke_engine_eval_dev(ctx, f->b, n, 0.0f, nullptr, f->pe_score));
-    else if (!use_net) RC(oakgpu_rollout_dev(ctx, f->b, f->d, f->r, (uint8_t *)f->prng, n, 1000, 0, f->rout, f->steps, f->values, nullptr, nullptr));
-    else if (pucb) RC(oakgpu_leaf_eval_policy_dev(ctx, net, f->b, f->d, n, f->ch1, f->cnt1, f->ch2, f->cnt2, f->values, f->l1, f->l2));
-    else RC(oakgpu_leaf_eval_dev(ctx, net, f->b, f->d, n, f->values, nullptr));
+    if (use_pe) RC(oakgpu_poke_engine_eval_dev(ctx, f->b, rows, 0.0f, nullptr, f->pe_score));
+    else if (!use_net) RC(oakgpu_rollout_dev(ctx, f->b, f->d, f->r, (uint8_t *)f->prng, rows, 1000, 0, f->rout, f->steps, f->values, nullptr, nullptr));
+    else if (pucb) RC(oakgpu_leaf_eval_policy_dev(ctx, net, f->b, f->d, rows, f->ch1, f->cnt1, f->ch2, f->cnt2, f->values, f->l1, f->l2));
+    else RC(oakgpu_leaf_eval_dev(ctx, net, f->b, f->d, rows, f->values, nullptr));
     K.iteration = it;
-    hipLaunchKernelGGL(k_forest_backup, grid, block, 0, stream, K);
+    hipLaunchKernelGGL(k_forest_backup, row_grid, block, 0, stream, K);
     HIPCHK(hipGetLastError());
     launches += 2;
   }
-  hipLaunchKernelGGL(k_forest_finish, grid, block, 0, stream, n, (uint64_t)iterations, f->n_nodes, f->total_depth, f->prng, *o);
+  hipLaunchKernelGGL(k_forest_finish, grid, block, 0, stream, n, (uint64_t)iterations, f->n_nodes, f->total_depth, f->prng, budgets, *o);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(f->h_live + 1, f->ctl, 4, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
   f->stats[0] = iterations; f->stats[1] = levels_stepped; f->stats[2] = launches; f->stats[3] = polls;
+  f->rows[0] = rows_launched; f->rows[1] = rows_run;
   f->last_n = n;
   f->valid = keep ? std::max(f->valid, n) : n;
   if (f->h_live[1] & ERR_ARENA_FULL) return oakgpu_fail_msg("oakgpu_forest_search: a tree's node arena is full");
@@ -777,10 +845,12 @@ int oakgpu_forest_search_kept_dev(oakgpu_forest *f, oakgpu_net *net, const oakgp
 // the body of both host-array searches
 static int forest_search_host(oakgpu_forest *f, oakgpu_net *net, const oakgpu_search_params *prm, const uint8_t *battles, const uint8_t *durations,
                               const uint8_t *results, const uint64_t *seeds, uint32_t n, oakgpu_search_output *out, int solve_nash, uint64_t *streams_out,
-                              void *trace, uint32_t trace_levels, bool keep) {
+                              void *trace, uint32_t trace_levels, bool keep, const uint32_t *budgets = nullptr, bool with_budgets = false) {
   if (!f || !prm || !battles || !durations || !results || !seeds || !out) return oakgpu_fail_msg("oakgpu_forest_search: null argument");
+  if (with_budgets && !budgets && n) return oakgpu_fail_msg("oakgpu_forest_search_budgets: null argument");
   if (keep && !f->kept) return oakgpu_fail_msg("oakgpu_forest_search_kept: the forest was created without keep (oakgpu_forest_create_kept makes one that keeps its trees)");
   RC(oakgpu_forest_check(f->max_trees, f->max_iterations, f->contextual, prm, net != nullptr, n, results, trace != nullptr, trace_levels));
+  if (budgets) RC(oakgpu_forest_budgets_check(budgets, n, prm->iterations));
   if (n == 0) return 0;
   const auto t0 = std::chrono::high_resolution_clock::now();
   RC(oakgpu_ctx_enter(f->ctx));
@@ -800,10 +870,17 @@ static int forest_search_host(oakgpu_forest *f, oakgpu_net *net, const oakgpu_se
   HIPCHK(hipMemcpyAsync(d_d, durations, (size_t)n * 8, hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(d_s, seeds, (size_t)n * 8, hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(d_r, results, n, hipMemcpyHostToDevice, stream));
+  if (budgets) {
+    if (!f->budget_stage) RC(dev_alloc(f->budget_stage, T));
+    HIPCHK(hipMemcpyAsync(f->budget_stage, budgets, (size_t)n * 4, hipMemcpyHostToDevice, stream));
+    // records past a tree's budget are not written: the caller's bytes there go down and come back
+    if (trace) HIPCHK(hipMemcpyAsync(f->trace_stage, trace, trace_bytes, hipMemcpyHostToDevice, stream));
+  }
   HIPCHK(hipStreamSynchronize(stream));
   oakgpu_forest_outputs o;
   carve_outputs(d_o, n, &o);
-  RC(forest_search_body(f, net, prm, d_b, d_d, d_r, (const uint64_t *)d_s, n, &o, trace ? f->trace_stage : nullptr, trace_levels, keep));
+  RC(forest_search_body(f, net, prm, d_b, d_d, d_r, (const uint64_t *)d_s, n, &o, trace ? f->trace_stage : nullptr, trace_levels, keep, budgets ? f->budget_stage : nullptr,
+                        with_budgets));
   std::vector<uint8_t> h(outputs_bytes(n));
   HIPCHK(hipMemcpy(h.data(), d_o, h.size(), hipMemcpyDeviceToHost));
   if (trace) HIPCHK(hipMemcpy(trace, f->trace_stage, trace_bytes, hipMemcpyDeviceToHost));
@@ -860,6 +937,31 @@ int oakgpu_forest_search_kept(oakgpu_forest *f, oakgpu_net *net, const oakgpu_se
                               const uint8_t *results, const uint64_t *seeds, uint32_t n, oakgpu_search_output *out, int solve_nash, uint64_t *streams_out,
                               void *trace, uint32_t trace_levels) {
   return forest_search_host(f, net, prm, battles, durations, results, seeds, n, out, solve_nash, streams_out, trace, trace_levels, true);
+}
+
+// the budgets forms: tree g runs budgets[g] iterations (the contract is in include/oakgpu.h)
+int oakgpu_forest_search_budgets_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_search_params *prm, const uint8_t *battles, const uint8_t *durations,
+                                     const uint8_t *results, const uint64_t *seeds, const uint32_t *budgets, uint32_t n, const oakgpu_forest_outputs *o, void *trace,
+                                     uint32_t trace_levels) {
+  return forest_search_body(f, net, prm, battles, durations, results, seeds, n, o, trace, trace_levels, false, budgets, true);
+}
+
+int oakgpu_forest_search_budgets_kept_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_search_params *prm, const uint8_t *battles, const uint8_t *durations,
+                                          const uint8_t *results, const uint64_t *seeds, const uint32_t *budgets, uint32_t n, const oakgpu_forest_outputs *o,
+                                          void *trace, uint32_t trace_levels) {
+  return forest_search_body(f, net, prm, battles, durations, results, seeds, n, o, trace, trace_levels, true, budgets, true);
+}
+
+int oakgpu_forest_search_budgets(oakgpu_forest *f, oakgpu_net *net, const oakgpu_search_params *prm, const uint8_t *battles, const uint8_t *durations,
+                                 const uint8_t *results, const uint64_t *seeds, const uint32_t *budgets, uint32_t n, oakgpu_search_output *out, int solve_nash,
+                                 uint64_t *streams_out, void *trace, uint32_t trace_levels) {
+  return forest_search_host(f, net, prm, battles, durations, results, seeds, n, out, solve_nash, streams_out, trace, trace_levels, false, budgets, true);
+}
+
+int oakgpu_forest_search_budgets_kept(oakgpu_forest *f, oakgpu_net *net, const oakgpu_search_params *prm, const uint8_t *battles, const uint8_t *durations,
+                                      const uint8_t *results, const uint64_t *seeds, const uint32_t *budgets, uint32_t n, oakgpu_search_output *out, int solve_nash,
+                                      uint64_t *streams_out, void *trace, uint32_t trace_levels) {
+  return forest_search_host(f, net, prm, battles, durations, results, seeds, n, out, solve_nash, streams_out, trace, trace_levels, true, budgets, true);
 }
 
 // Heap::update of every tree, and the move to another row (k_forest_advance): reads the front copy, writes the back one, then the two swap

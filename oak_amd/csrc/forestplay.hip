@@ -19,6 +19,13 @@
 // next turn's compaction carries them to the row's new place and lists each new row's source row, and ONE oakgpu_forest_advance_dev with
 // that list re-roots every tree and moves it along with its row; the search is then oakgpu_forest_search_kept_dev.  A retired row has no
 // successor.  The pick also keeps the row's nodes_kept count (selfplay.hip: + 1 per advance that kept, - 1 per root mismatch, never below 0).
+// Fast searches (params->fast_search_prob > 0; the rule is selfplay_pick.hpp's turn_prelude, one text with the host loop): the prelude first
+// draws the turn's flag from the game's stream, and the compaction becomes a stable partition into two classes, the rows of the larger
+// budget first -- k_fsp_retire counts both classes per block (it looks at the flag on a copy of the stream), the ONE scan runs over both
+// count arrays, so the second class's offsets follow the first's, and k_fsp_compact places each class by its own offsets and writes the
+// row's budget.  The search is then oakgpu_forest_search_budgets(_kept)_dev with budgets that do not increase in row order: no launch of it
+// covers a finished tree.  With keep_node the trees follow through src_row as before.  The pick takes fast_policy_mode for a fast row.  Two
+// departures from generate.cc:292-299: the draw is the game's own (there: the worker thread's), and none is made at probability 0.
 // Every kernel is a plain grid over rows, games or entries (the two scans: one workgroup); none waits for another block.  Between
 // compact and pick runs oakgpu_forest_search_dev over exactly the live rows (the forest refuses terminal roots), after pick
 // oakgpu_update_dev.  Retire / offsets / compact run on game_rows.hpp's scan, place and move, as in policyplay.hip, with this loop's own
@@ -49,7 +56,20 @@ struct Rows {
   // keep_node: the played cell, the update's observation, and the game's counts so far (advances that kept, root mismatches, nodes carried in)
   uint8_t *pi, *pj, *obs;
   uint32_t *kept, *mism, *carry;
+  // fast searches: this turn's flag (written by the compaction's prelude) and the game's fast frames so far
+  uint8_t *fast;
+  uint32_t *fastn;
 };
+
+// fast searches (fast_search_prob > 0; selfplay_pick.hpp's turn_prelude), as the retire and compact kernels need them.  The live rows of
+// the class with the larger budget go first (`fast_first`: that is the fast class), so the turn's budgets are non-increasing in row order;
+// partition == 0 (benchmarks) leaves every live row in the first class, in game order
+struct FastArgs {
+  double prob;
+  uint32_t on, fast_first, partition, blocks; // blocks: the second class's live counts and offsets start there
+  uint32_t budget_full, budget_fast;
+};
+__device__ __forceinline__ bool first_class(const FastArgs &f, bool fast) { return !f.partition || fast == (f.fast_first != 0); }
 
 __global__ __launch_bounds__(BLOCK) void k_fsp_start(Rows r, const uint64_t *seeds, uint32_t n, int keep) {
   const uint32_t row = blockIdx.x * BLOCK + threadIdx.x;
@@ -59,6 +79,8 @@ __global__ __launch_bounds__(BLOCK) void k_fsp_start(Rows r, const uint64_t *see
   r.frames[row] = 0;
   r.cursor[row] = 0;
   r.flag[row] = 0;
+  r.fast[row] = 0;
+  r.fastn[row] = 0;
   r.rng[row] = seeds[row] ^ oak_pick::GAME_STREAM_XOR;
 }
 
@@ -69,10 +91,12 @@ struct RetireArgs {
   uint32_t *block_live;              // per block of BLOCK rows: rows still live after this pass
   uint32_t rows, max_len;
   uint32_t *kept_out, *mism_out, *carry_out; // keep_node, by game index; else null
+  uint32_t *fast_out;                        // by game index: the game's fast frames
+  FastArgs fast;
 };
 
 __global__ __launch_bounds__(BLOCK) void k_fsp_retire(RetireArgs a) {
-  __shared__ uint32_t wave_live[BLOCK / 64];
+  __shared__ uint32_t wave_live[BLOCK / 64], wave_live2[BLOCK / 64];
   const uint32_t row = blockIdx.x * BLOCK + threadIdx.x;
   const bool in = row < a.rows;
   const uint32_t g = in ? a.r.game[row] : DEAD;
@@ -87,11 +111,20 @@ __global__ __launch_bounds__(BLOCK) void k_fsp_retire(RetireArgs a) {
       a.frames_out[g] = frames;
       a.status_out[g] = (uint8_t)status;
       a.length_out[g] = status == OAKGPU_FSP_OK ? HEAD_BYTES + a.r.cursor[row] : 0u;
+      a.fast_out[g] = a.r.fastn[row];
       if (a.kept_out) { a.kept_out[g] = a.r.kept[row]; a.mism_out[g] = a.r.mism[row]; a.carry_out[g] = a.r.carry[row]; }
       a.r.game[row] = DEAD;
     }
   }
-  game_rows::count_block_live(live, wave_live, a.block_live);
+  if (!a.fast.on) { game_rows::count_block_live(live, wave_live, a.block_live); return; }
+  // two classes: the flag the compaction's prelude will draw, looked at here on a copy of the stream
+  bool first = false;
+  if (live) {
+    uint64_t rng = a.r.rng[row];
+    first = first_class(a.fast, oak_pick::turn_is_fast(rng, a.fast.prob));
+  }
+  game_rows::count_block_live(first, wave_live, a.block_live);
+  game_rows::count_block_live(live && !first, wave_live2, a.block_live + a.fast.blocks);
 }
 
 struct CompactArgs {
@@ -104,15 +137,32 @@ struct CompactArgs {
   uint32_t *src_row;
   uint8_t *adv_i, *adv_j, *adv_obs;
   int keep; // keep_node: the game's counts move with the row
+  FastArgs fast;
+  uint32_t *budget; // fast searches: per compacted row, the iterations of this turn's search
 };
 
-// Stable (game_rows.hpp: compact_place, compact_battles).  The turn prelude rides along: search seed = splitmix64(rng).
+// Stable (game_rows.hpp: compact_place, compact_battles).  The turn prelude rides along (selfplay_pick.hpp's turn_prelude): with fast
+// searches the turn's flag, then search seed = splitmix64(rng).  With fast searches the compaction is a stable partition into two classes,
+// each placed by its own offsets (the second class's follow the first's in the one scan).
 __global__ __launch_bounds__(BLOCK) void k_fsp_compact(CompactArgs a) {
-  __shared__ uint32_t wave_total[BLOCK / 64];
-  __shared__ uint32_t place[BLOCK];
+  __shared__ uint32_t wave_total[BLOCK / 64], wave_total2[BLOCK / 64];
+  __shared__ uint32_t place[BLOCK], place2[BLOCK];
   const uint32_t row = blockIdx.x * BLOCK + threadIdx.x;
   const bool live = row < a.rows && a.from.game[row] != DEAD;
-  const uint32_t to = game_rows::compact_place(live, a.block_offset[blockIdx.x], wave_total, place);
+  uint64_t rng = 0;
+  oak_pick::TurnPrelude turn{0, false};
+  if (live) {
+    rng = a.from.rng[row];
+    turn = oak_pick::turn_prelude(rng, a.fast.on ? a.fast.prob : 0.0);
+  }
+  uint32_t to;
+  if (!a.fast.on) to = game_rows::compact_place(live, a.block_offset[blockIdx.x], wave_total, place);
+  else {
+    const bool first = live && first_class(a.fast, turn.fast);
+    to = game_rows::compact_place(first, a.block_offset[blockIdx.x], wave_total, place);
+    const uint32_t to2 = game_rows::compact_place(live && !first, a.block_offset[a.fast.blocks + blockIdx.x], wave_total2, place2);
+    if (live && !first) { to = to2; place[threadIdx.x] = to2; } // (the lane's own entry; read after the barrier below)
+  }
   if (live) {
     *((uint2 *)a.to.durations + to) = *((const uint2 *)a.from.durations + row);
     a.to.results[to] = a.from.results[row];
@@ -120,9 +170,11 @@ __global__ __launch_bounds__(BLOCK) void k_fsp_compact(CompactArgs a) {
     a.to.game[to] = a.from.game[row];
     a.to.frames[to] = a.from.frames[row];
     a.to.cursor[to] = a.from.cursor[row];
-    uint64_t rng = a.from.rng[row];
-    a.tree_seed[to] = oak_pick::splitmix64(rng);
+    a.tree_seed[to] = turn.search_seed;
     a.to.rng[to] = rng;
+    a.to.fast[to] = turn.fast ? 1 : 0;
+    a.to.fastn[to] = a.from.fastn[row];
+    if (a.fast.on) a.budget[to] = turn.fast ? a.fast.budget_fast : a.fast.budget_full;
     if (a.src_row) {
       a.src_row[to] = row;
       a.adv_i[to] = a.from.pi[row]; a.adv_j[to] = a.from.pj[row];
@@ -139,7 +191,7 @@ struct PickArgs {
   oakgpu_forest_outputs out;                 // the search's outputs, row-major over the live rows
   const double *p1_nash, *p2_nash, *nash_value; // rows x 9, rows x 9, rows; null without solve_nash
   LogEntry *log;                             // this turn's entries, one per row
-  oak_pick::PolicyMode mode;
+  oak_pick::PolicyMode mode, fast_mode;      // fast_mode: the pick of a fast turn (the row's flag)
   double temp, minp;
   uint32_t rows;
   // keep_node: the row keeps the played cell; from the second turn on (else null) the advance's results, the kept search's mismatch bytes and carried nodes
@@ -168,7 +220,9 @@ __global__ __launch_bounds__(BLOCK) void k_fsp_pick(PickArgs a) {
   uint8_t c1 = a.out.p1_choices[(size_t)row * 9], c2 = a.out.p2_choices[(size_t)row * 9];
   uint32_t len = 0;
   uint8_t pi = 0, pj = 0;
-  if (!oak_pick::get_policy(r1, e1, n1, m, a.mode, a.temp, a.minp, pol1) || !oak_pick::get_policy(r2, e2, n2, n, a.mode, a.temp, a.minp, pol2)) {
+  const bool fast = a.r.fast[row] != 0;
+  const oak_pick::PolicyMode &mode = fast ? a.fast_mode : a.mode;
+  if (!oak_pick::get_policy(r1, e1, n1, m, mode, a.temp, a.minp, pol1) || !oak_pick::get_policy(r2, e2, n2, n, mode, a.temp, a.minp, pol2)) {
     a.r.flag[row] = (uint8_t)OAKGPU_FSP_ZERO_POLICY; // the game stops here: its row takes a legal step and is retired with no record
   } else {
     uint64_t rng = a.r.rng[row];
@@ -179,6 +233,7 @@ __global__ __launch_bounds__(BLOCK) void k_fsp_pick(PickArgs a) {
     pi = (uint8_t)i; pj = (uint8_t)j;
     len = oak_pick::encode_update(entry->bytes, (uint32_t)m, (uint32_t)n, c1, c2, (uint32_t)iterations, ev, nv, e1, n1, e2, n2);
     a.r.frames[row] += 1;
+    if (fast) a.r.fastn[row] += 1;
     a.r.cursor[row] += len;
   }
   entry->length = len;
@@ -232,6 +287,10 @@ struct Workspace {
   bool kept_call = false;
   uint64_t keep_stats[4] = {0, 0, 0, 0};
   uint64_t loop_syncs = 0, loop_copies = 0; // the turn loop's stream synchronisations and host <-> device copies
+  // fast searches: the turn's budgets per compacted row, the games' fast frames, the last call's tree-iterations launched and run
+  uint32_t *budget = nullptr, *fast_out = nullptr;
+  uint64_t rows_launched = 0, rows_run = 0;
+  bool partition = true;
   std::vector<int32_t> h_pay;
   std::vector<double> h_nash;
   void release() {
@@ -265,7 +324,7 @@ int workspace_for(oakgpu_forest *f, uint32_t n, Workspace **out) {
   for (int h = 0; h < 2; ++h) {
     Rows &r = w->half[h];
     RC(d.get(r.battles, T * 384)); RC(d.get(r.durations, T * 8)); RC(d.get(r.results, T)); RC(d.get(r.c1, T)); RC(d.get(r.c2, T)); RC(d.get(r.flag, T));
-    RC(d.get(r.game, T)); RC(d.get(r.frames, T)); RC(d.get(r.cursor, T)); RC(d.get(r.rng, T));
+    RC(d.get(r.game, T)); RC(d.get(r.frames, T)); RC(d.get(r.cursor, T)); RC(d.get(r.rng, T)); RC(d.get(r.fast, T)); RC(d.get(r.fastn, T));
     if (oakgpu_forest_is_kept(f)) { RC(d.get(r.pi, T)); RC(d.get(r.pj, T)); RC(d.get(r.obs, T * 16)); RC(d.get(r.kept, T)); RC(d.get(r.mism, T)); RC(d.get(r.carry, T)); }
   }
   if (oakgpu_forest_is_kept(f)) {
@@ -274,7 +333,8 @@ int workspace_for(oakgpu_forest *f, uint32_t n, Workspace **out) {
   }
   RC(d.get(w->tree_seed, T)); RC(d.get(w->out_block, OUT_BYTES * T + 16 * 16)); RC(d.get(w->pay, T * PAY_STRIDE)); RC(d.get(w->nash, T * 19));
   RC(d.get(w->first, T * 384)); RC(d.get(w->results_out, T)); RC(d.get(w->status_out, T)); RC(d.get(w->d_teams, T * 60));
-  RC(d.get(w->frames_out, T)); RC(d.get(w->length_out, T)); RC(d.get(w->block_live, blocks)); RC(d.get(w->block_offset, blocks)); RC(d.get(w->ctl, 4));
+  RC(d.get(w->frames_out, T)); RC(d.get(w->length_out, T)); RC(d.get(w->block_live, 2 * blocks)); RC(d.get(w->block_offset, 2 * blocks)); RC(d.get(w->ctl, 4));
+  RC(d.get(w->budget, T)); RC(d.get(w->fast_out, T));
   RC(d.get(w->d_seeds, 2 * T)); RC(d.get(w->offsets, T + 1));
   w->capacity = n;
   return 0;
@@ -298,6 +358,10 @@ int oakgpu_forest_selfplay_check(uint32_t max_trees, uint32_t max_iterations, in
   contextual &= ~OAKGPU_FOREST_KEPT;
   const std::string refusal = policy_refusal(prm->policy_mode, sizeof prm->policy_mode, prm->policy_min, solve_nash);
   if (!refusal.empty()) return oakgpu_fail_msg(("oakgpu_forest_selfplay: " + refusal).c_str());
+  if (!(prm->fast_search_prob >= 0.0 && prm->fast_search_prob <= 1.0)) return oakgpu_fail_msg("oakgpu_forest_selfplay: fast_search_prob must be in [0, 1]");
+  if (prm->fast_budget > max_iterations) return oakgpu_fail_msg("oakgpu_forest_selfplay: fast_budget exceeds the forest's max_iterations");
+  const std::string fast_refusal = policy_refusal(prm->fast_policy_mode, sizeof prm->fast_policy_mode, prm->policy_min, solve_nash);
+  if (!fast_refusal.empty()) return oakgpu_fail_msg(("oakgpu_forest_selfplay: fast_policy_mode: " + fast_refusal).c_str());
   if (int rc = oakgpu_forest_check(max_trees, max_iterations, contextual, &prm->search, has_net, n, nullptr, 0, 0)) {
     std::string msg = oakgpu_last_error();
     const std::string from = "oakgpu_forest_search:";
@@ -348,11 +412,22 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
   w->stats[0] = w->stats[1] = w->stats[2] = w->stats[3] = 0;
   w->loop_syncs = w->loop_copies = 0;
   if (n == 0) { w->have = true; return 0; }
-  oak_pick::PolicyMode mode;
+  oak_pick::PolicyMode mode, fast_mode;
   (void)oak_pick::parse_policy_mode(prm->policy_mode, sizeof prm->policy_mode, &mode);
+  fast_mode = mode;
+  if (prm->fast_policy_mode[0]) (void)oak_pick::parse_policy_mode(prm->fast_policy_mode, sizeof prm->fast_policy_mode, &fast_mode);
   const uint32_t max_len = prm->max_battle_length ? prm->max_battle_length : 2048;
   oakgpu_search_params sp = prm->search;
   sp.batch = 1; sp.seed = 0;
+  // fast searches: the two budgets of a turn; the budgets search is sized by the larger
+  FastArgs fa{};
+  fa.prob = prm->fast_search_prob; fa.on = prm->fast_search_prob > 0 ? 1u : 0u; fa.partition = w->partition ? 1u : 0u;
+  w->partition = true; // (the benchmark's switch holds for one call)
+  fa.budget_full = (uint32_t)sp.iterations; fa.budget_fast = oak_pick::turn_budget(true, fa.budget_full, prm->fast_budget);
+  fa.fast_first = fa.budget_fast > fa.budget_full ? 1u : 0u;
+  oakgpu_search_params sp_budgets = sp;
+  sp_budgets.iterations = std::max(fa.budget_full, fa.budget_fast);
+  w->rows_launched = w->rows_run = 0;
   auto grid = [](uint32_t rows) { return dim3((rows + BLOCK - 1) / BLOCK); };
 
   // the opening: PKMN::battle + update(0, 0); the battle after it is the record's stored one
@@ -374,12 +449,14 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
   for (uint64_t turn = 0;; ++turn) {
     // retire what ended, compact the rest: the rows handed to the search are exactly the live games
     const uint32_t blocks = (rows + BLOCK - 1) / BLOCK;
+    fa.blocks = blocks;
     const RetireArgs ra{w->half[cur], w->results_out, w->status_out, w->frames_out, w->length_out, w->block_live, rows, max_len,
-                        keep ? w->kept_out : nullptr, keep ? w->mism_out : nullptr, keep ? w->carry_out : nullptr};
+                        keep ? w->kept_out : nullptr, keep ? w->mism_out : nullptr, keep ? w->carry_out : nullptr, w->fast_out, fa};
     hipLaunchKernelGGL(k_fsp_retire, grid(rows), dim3(BLOCK), 0, stream, ra);
-    hipLaunchKernelGGL(k_rows_offsets, dim3(1), dim3(1024), 0, stream, w->block_live, blocks, w->block_offset, w->ctl);
+    hipLaunchKernelGGL(k_rows_offsets, dim3(1), dim3(1024), 0, stream, w->block_live, fa.on ? 2 * blocks : blocks, w->block_offset, w->ctl);
     const bool advance = keep && turn > 0; // the first turn's trees are new
-    const CompactArgs ca{w->half[cur], w->half[cur ^ 1], w->block_offset, w->tree_seed, rows, advance ? w->src_row : nullptr, w->adv_i, w->adv_j, w->adv_obs, keep ? 1 : 0};
+    const CompactArgs ca{w->half[cur], w->half[cur ^ 1], w->block_offset, w->tree_seed, rows, advance ? w->src_row : nullptr, w->adv_i, w->adv_j, w->adv_obs, keep ? 1 : 0,
+                         fa, w->budget};
     hipLaunchKernelGGL(k_fsp_compact, grid(rows), dim3(BLOCK), 0, stream, ca);
     HIPCHK(hipGetLastError());
     uint32_t live = 0;
@@ -405,8 +482,15 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
     carve_outputs(w->out_block, rows, &o);
     if (advance) { // every live game's tree: re-rooted at the child it played into, and moved to the game's new row
       RC(oakgpu_forest_advance_dev(f, w->adv_i, w->adv_j, w->adv_obs, w->src_row, rows, w->advanced));
-      RC(oakgpu_forest_search_kept_dev(f, net, &sp, r.battles, r.durations, r.results, w->tree_seed, rows, &o, nullptr, 0));
-    } else RC(oakgpu_forest_search_dev(f, net, &sp, r.battles, r.durations, r.results, w->tree_seed, rows, &o, nullptr, 0));
+      if (fa.on) RC(oakgpu_forest_search_budgets_kept_dev(f, net, &sp_budgets, r.battles, r.durations, r.results, w->tree_seed, w->budget, rows, &o, nullptr, 0));
+      else RC(oakgpu_forest_search_kept_dev(f, net, &sp, r.battles, r.durations, r.results, w->tree_seed, rows, &o, nullptr, 0));
+    } else if (fa.on) RC(oakgpu_forest_search_budgets_dev(f, net, &sp_budgets, r.battles, r.durations, r.results, w->tree_seed, w->budget, rows, &o, nullptr, 0));
+    else RC(oakgpu_forest_search_dev(f, net, &sp, r.battles, r.durations, r.results, w->tree_seed, rows, &o, nullptr, 0));
+    {
+      uint64_t tree_iterations[2];
+      RC(oakgpu_forest_last_rows(f, tree_iterations));
+      w->rows_launched += tree_iterations[0]; w->rows_run += tree_iterations[1];
+    }
     double *d_p1 = nullptr, *d_p2 = nullptr, *d_nv = nullptr;
     if (solve_nash) {
       RC(solve_turn(ctx, stream, solve_nash, o, rows, w->pay, w->nash, w->h_pay, w->h_nash));
@@ -417,7 +501,7 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
       d_p1 = w->nash; d_p2 = w->nash + (size_t)rows * 9; d_nv = w->nash + (size_t)rows * 18;
     }
     PickArgs pk{};
-    pk.r = r; pk.out = o; pk.p1_nash = d_p1; pk.p2_nash = d_p2; pk.nash_value = d_nv; pk.log = w->log + entries; pk.mode = mode;
+    pk.r = r; pk.out = o; pk.p1_nash = d_p1; pk.p2_nash = d_p2; pk.nash_value = d_nv; pk.log = w->log + entries; pk.mode = mode; pk.fast_mode = fast_mode;
     pk.temp = prm->policy_temp > 0 ? prm->policy_temp : 1.0; pk.minp = prm->policy_min; pk.rows = rows;
     pk.keep = keep ? 1 : 0;
     if (advance) { pk.advanced = w->advanced; pk.mismatch = d_mismatch; pk.carried = d_carried; }
@@ -467,6 +551,40 @@ int oakgpu_forest_selfplay_nodes_kept(oakgpu_forest *f, uint32_t *nodes_kept, in
     else memset(nodes_kept, 0, n * 4);
   }
   HIPCHK(hipStreamSynchronize(stream));
+  return 0;
+}
+
+int oakgpu_forest_selfplay_fast_stats(oakgpu_forest *f, uint64_t out[4]) {
+  if (!f || !out) return oakgpu_fail_msg("oakgpu_forest_selfplay_fast_stats: null argument");
+  Workspace *w = (Workspace *)oakgpu_forest_attachment(f);
+  if (!w || !w->have) return oakgpu_fail_msg("oakgpu_forest_selfplay_fast_stats: the forest holds no finished self-play call");
+  oakgpu_ctx *ctx = oakgpu_forest_ctx(f);
+  RC(oakgpu_ctx_enter(ctx));
+  hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(ctx);
+  const size_t n = w->last_n;
+  std::vector<uint32_t> fast(n), frames(n);
+  std::vector<uint8_t> status(n);
+  if (n) { // the per-game counts, read when asked for
+    HIPCHK(hipMemcpyAsync(fast.data(), w->fast_out, n * 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(frames.data(), w->frames_out, n * 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(status.data(), w->status_out, n, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+  }
+  out[0] = out[1] = 0;
+  for (size_t g = 0; g < n; ++g)
+    if (status[g] == OAKGPU_FSP_OK) { out[0] += fast[g]; out[1] += frames[g] - fast[g]; }
+  out[2] = w->rows_launched; out[3] = w->rows_run;
+  return 0;
+}
+
+int oakgpu_forest_selfplay_set_partition(oakgpu_forest *f, int on) {
+  if (!f) return oakgpu_fail_msg("oakgpu_forest_selfplay_set_partition: null argument");
+  Workspace *w = (Workspace *)oakgpu_forest_attachment(f);
+  if (!w) {
+    w = new Workspace();
+    oakgpu_forest_set_attachment(f, w, workspace_free);
+  }
+  w->partition = on != 0;
   return 0;
 }
 

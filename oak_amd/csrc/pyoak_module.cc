@@ -438,8 +438,16 @@ PYBIND11_MODULE(pyoak, m) {
       "search_forest",
       [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> battles, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> durations,
          py::array_t<uint8_t, py::array::c_style | py::array::forcecast> results, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> seeds,
-         Agent &agent, py::object solve_nash_arg) {
+         Agent &agent, py::object solve_nash_arg, py::object budgets_arg) {
         const int solve_nash = nash_mode(solve_nash_arg);
+        // budgets (None, or n x uint32): tree g runs budgets[g] <= the agent's budget iterations (oakgpu_forest_search_budgets)
+        std::vector<uint32_t> budgets;
+        const bool with_budgets = !budgets_arg.is_none();
+        if (with_budgets) {
+          auto arr = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>::ensure(budgets_arg);
+          if (!arr || (size_t)arr.size() != (size_t)results.size()) throw std::runtime_error("search_forest: budgets: one uint32 per tree");
+          budgets.assign(arr.data(), arr.data() + arr.size());
+        }
         // not in pyoak: n positions searched at once, one GPU lane per tree (include/oakgpu.h: oakgpu_forest_search); output g is
         // search(input g, Heap(), agent, batch = 1, seed = seeds[g]).  The Agent's strings go through search's own parser; what the
         // forest does not run (time budgets, matrix_ucb, UCB1 / Exp3 / PExp3) is refused by name.
@@ -460,7 +468,11 @@ PYBIND11_MODULE(pyoak, m) {
           rc = oakgpu_agent_params(context(), &a, 1, 0, &P, &net);
           if (!rc) rc = oakgpu_forest_check((uint32_t)n, (uint32_t)std::min<uint64_t>(P.iterations, 0xFFFFFFFFu), P.bandit == 1, &P, net != nullptr, (uint32_t)n, results.data(), 0, 0);
           if (!rc && n) rc = oakgpu_forest_create(context(), (uint32_t)n, (uint32_t)P.iterations, P.bandit == 1, &forest);
-          if (!rc && n) rc = oakgpu_forest_search(forest, net, &P, battles.data(), durations.data(), results.data(), seeds.data(), (uint32_t)n, raw.data(), solve_nash, nullptr, nullptr, 0);
+          if (!rc && with_budgets) rc = oakgpu_forest_budgets_check(budgets.data(), (uint32_t)n, P.iterations);
+          if (!rc && n && with_budgets)
+            rc = oakgpu_forest_search_budgets(forest, net, &P, battles.data(), durations.data(), results.data(), seeds.data(), budgets.data(), (uint32_t)n, raw.data(), solve_nash,
+                                              nullptr, nullptr, 0);
+          else if (!rc && n) rc = oakgpu_forest_search(forest, net, &P, battles.data(), durations.data(), results.data(), seeds.data(), (uint32_t)n, raw.data(), solve_nash, nullptr, nullptr, 0);
           if (rc) err = oakgpu_last_error();
           oakgpu_forest_destroy(context(), forest);
         }
@@ -468,21 +480,23 @@ PYBIND11_MODULE(pyoak, m) {
         for (size_t g = 0; g < n; ++g) out[g].raw = raw[g];
         return out;
       },
-      py::arg("battles"), py::arg("durations"), py::arg("results"), py::arg("seeds"), py::arg("agent"), py::arg("solve_nash") = true);
+      py::arg("battles"), py::arg("durations"), py::arg("results"), py::arg("seeds"), py::arg("agent"), py::arg("solve_nash") = true, py::arg("budgets") = py::none());
 
   m.def(
       "selfplay_forest",
       [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> teams, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> battle_seeds,
          py::array_t<uint64_t, py::array::c_style | py::array::forcecast> seeds, Agent &agent, const std::string &policy_mode, double policy_temp,
-         double policy_min, uint32_t max_battle_length, py::object solve_nash_arg, bool keep_node, uint32_t keep_arena) {
+         double policy_min, uint32_t max_battle_length, py::object solve_nash_arg, bool keep_node, uint32_t keep_arena, uint32_t fast_budget,
+         double fast_search_prob, const std::string &fast_policy_mode) {
         const int solve_nash = nash_mode(solve_nash_arg);
         // not in pyoak: the reference's `generate` loop for n games at once over the forest search (include/oakgpu.h:
         // oakgpu_forest_selfplay); game g is the per-game loop with batch = 1 and seed = seeds[g].  Returns (stream bytes, offsets, n_frames,
         // results, status); with keep_node (generate's --keep-node, on a kept forest of keep_arena nodes a tree, 0 = 4 * budget + 1) a sixth
-        // value, nodes_kept per game.
+        // value, nodes_kept per game.  fast_budget / fast_search_prob / fast_policy_mode: generate's fast searches (oakgpu_selfplay_params).
         const size_t n = (size_t)seeds.size();
         if ((size_t)teams.size() != n * 60 || (size_t)battle_seeds.size() != n) throw std::runtime_error("selfplay_forest: teams n x 60, battle_seeds n, seeds n");
         if (policy_mode.size() > 15) throw std::runtime_error("selfplay_forest: policy_mode: at most 15 characters");
+        if (fast_policy_mode.size() > 15) throw std::runtime_error("selfplay_forest: fast_policy_mode: at most 15 characters");
         const oakgpu_agent a{agent.budget.c_str(), agent.bandit.c_str(), agent.eval.c_str(), agent.matrix_ucb.c_str(), agent.discrete, agent.table};
         std::string stream;
         py::array_t<uint64_t> offsets(n + 1);
@@ -501,7 +515,9 @@ PYBIND11_MODULE(pyoak, m) {
           rc = oakgpu_agent_params(context(), &a, 1, 0, &P.search, &net);
           std::memcpy(P.policy_mode, policy_mode.c_str(), policy_mode.size() + 1);
           P.policy_temp = policy_temp; P.policy_min = policy_min; P.max_battle_length = max_battle_length;
-          const uint32_t cap = (uint32_t)std::min<uint64_t>(P.search.iterations, 0xFFFFFFFFu);
+          std::memcpy(P.fast_policy_mode, fast_policy_mode.c_str(), fast_policy_mode.size() + 1);
+          P.fast_budget = fast_budget; P.fast_search_prob = fast_search_prob;
+          const uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(P.search.iterations, fast_budget), 0xFFFFFFFFu);
           if (!rc && keep_node) rc = oakgpu_forest_create_kept_check((uint32_t)std::max<size_t>(n, 1), cap, keep_arena);
           if (!rc) rc = oakgpu_forest_selfplay_check((uint32_t)n, cap, (P.search.bandit == 1 ? 1 : 0) | (keep_node ? OAKGPU_FOREST_KEPT : 0), &P, net != nullptr, (uint32_t)n,
                                                      teams.data(), solve_nash);
@@ -525,7 +541,8 @@ PYBIND11_MODULE(pyoak, m) {
         return py::tuple(py::make_tuple(py::bytes(stream), offsets, n_frames, results, status));
       },
       py::arg("teams"), py::arg("battle_seeds"), py::arg("seeds"), py::arg("agent"), py::arg("policy_mode") = "e", py::arg("policy_temp") = 1.0,
-      py::arg("policy_min") = 0.0, py::arg("max_battle_length") = 0, py::arg("solve_nash") = true, py::arg("keep_node") = false, py::arg("keep_arena") = 0);
+      py::arg("policy_min") = 0.0, py::arg("max_battle_length") = 0, py::arg("solve_nash") = true, py::arg("keep_node") = false, py::arg("keep_arena") = 0,
+      py::arg("fast_budget") = 0, py::arg("fast_search_prob") = 0.0, py::arg("fast_policy_mode") = "");
 
   m.def(
       "match_forest",

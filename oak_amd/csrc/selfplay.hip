@@ -242,10 +242,25 @@ int oakgpu_selfplay_game(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *teams,
   struct HeapOwner { oakgpu_heap *h = nullptr; ~HeapOwner() { oakgpu_heap_destroy(h); } } heap;
   if (prm->keep_node && oakgpu_heap_create(&heap.h)) return -1;
   prm->nodes_kept = 0;
+  // fast searches (selfplay_pick.hpp's turn_prelude): "" = the same mode, 0 = the same budget
+  if (!(prm->fast_search_prob >= 0.0 && prm->fast_search_prob <= 1.0)) return oakgpu_fail_msg("oakgpu_selfplay_game: fast_search_prob must be in [0, 1]");
+  {
+    oak_pick::PolicyMode words;
+    if (oak_pick::parse_policy_mode(prm->fast_policy_mode, sizeof prm->fast_policy_mode, &words))
+      return oakgpu_fail_msg("oakgpu_selfplay_game: fast_policy_mode must be built from e / n / x / p words, 8 at the most (util/policy.h:22-98)");
+  }
+  char fast_mode[17] = {};
+  memcpy(fast_mode, prm->fast_policy_mode[0] ? prm->fast_policy_mode : prm->policy_mode, 16);
+  char full_mode[17] = {};
+  memcpy(full_mode, prm->policy_mode, 16);
   while ((result & 15) == 0) {
     if (frames.size() >= max_len) return oakgpu_fail_msg("oakgpu_selfplay_game: max battle length exceeded (generate.cc:268-271)");
     oakgpu_search_output out;
-    sp.seed = splitmix64(rng);
+    const oak_pick::TurnPrelude turn = oak_pick::turn_prelude(rng, prm->fast_search_prob);
+    sp.seed = turn.search_seed;
+    if (turn.fast) sp.iterations = oak_pick::turn_budget(true, (uint32_t)prm->search.iterations, prm->fast_budget);
+    else sp.iterations = prm->search.iterations;
+    const char *mode = turn.fast ? fast_mode : full_mode;
     int src = oakgpu_search_heap(ctx, net, heap.h, battle, durations, result, &sp, nullptr, &out);
     if (src == OAKGPU_E_ROOT_MISMATCH && heap.h) {
       // --keep-node: the kept child was expanded by a playout whose RESAMPLED hidden variables (mcts.h:254-259) gave it other
@@ -257,8 +272,8 @@ int oakgpu_selfplay_game(oakgpu_ctx *ctx, oakgpu_net *net, const uint8_t *teams,
     }
     if (src) return src;
     double pol1[9], pol2[9];
-    if (!get_policy(out.p1_prior, out.p1_empirical, out.p1_nash, out.m, prm->policy_mode, prm->policy_temp > 0 ? prm->policy_temp : 1.0, prm->policy_min, pol1) ||
-        !get_policy(out.p2_prior, out.p2_empirical, out.p2_nash, out.n, prm->policy_mode, prm->policy_temp > 0 ? prm->policy_temp : 1.0, prm->policy_min, pol2))
+    if (!get_policy(out.p1_prior, out.p1_empirical, out.p1_nash, out.m, mode, prm->policy_temp > 0 ? prm->policy_temp : 1.0, prm->policy_min, pol1) ||
+        !get_policy(out.p2_prior, out.p2_empirical, out.p2_nash, out.n, mode, prm->policy_temp > 0 ? prm->policy_temp : 1.0, prm->policy_min, pol2))
       return oakgpu_fail_msg("oakgpu_selfplay_game: policy mode must be built from e / n / x words and leave a non-zero policy (util/policy.h:22-98)");
     const int i = sample_pdf(pol1, out.m, rng), j = sample_pdf(pol2, out.n, rng);
     oakgpu_frame_update u{};
@@ -309,6 +324,15 @@ int oakgpu_selfplay_games(oakgpu_ctx *const *ctxs, oakgpu_net *net, const uint8_
   for (auto &t : th) t.join();
   for (uint32_t g = 0; g < n; ++g)
     if (rc[g]) return oakgpu_fail_msg(("oakgpu_selfplay_games: game " + std::to_string(g) + ": " + err[g]).c_str());
+  return 0;
+}
+
+// Diagnostic (no GPU involved): selfplay_pick.hpp's turn prelude on one stream
+int oakgpu_selfplay_prelude_host(uint64_t *rng, double fast_search_prob, int32_t *use_fast, uint64_t *search_seed) {
+  if (!rng || !use_fast || !search_seed) return oakgpu_fail_msg("oakgpu_selfplay_prelude_host: null argument");
+  const oak_pick::TurnPrelude t = oak_pick::turn_prelude(*rng, fast_search_prob);
+  *use_fast = t.fast ? 1 : 0;
+  *search_seed = t.search_seed;
   return 0;
 }
 

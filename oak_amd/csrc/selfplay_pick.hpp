@@ -33,6 +33,22 @@ OAK_PICK_HD inline uint64_t splitmix64(uint64_t &x) {
 }
 OAK_PICK_HD inline double uniform01(uint64_t &rng) { return (double)(splitmix64(rng) >> 11) * (1.0 / 9007199254740992.0); }
 
+// The start of a turn, for the host loop and the device loop alike (generate.cc:292-299, playout-cap randomisation): with
+// fast_search_prob > 0 the game's stream first gives one uniform draw, and the turn is a fast one -- searched with fast_budget
+// iterations, picked with fast_policy_mode -- when the draw is below the probability; then, as ever, the next splitmix64 output is the
+// seed of the turn's search.  With fast_search_prob == 0 (or below, or NaN) no draw is made: the stream is the one of a game without
+// fast searches.  The reference draws from its worker thread's device; a game here owns its stream, so the draw comes from it.
+struct TurnPrelude { uint64_t search_seed; bool fast; };
+OAK_PICK_HD inline bool turn_is_fast(uint64_t &rng, double fast_search_prob) { return fast_search_prob > 0 && uniform01(rng) < fast_search_prob; }
+OAK_PICK_HD inline TurnPrelude turn_prelude(uint64_t &rng, double fast_search_prob) {
+  TurnPrelude t;
+  t.fast = turn_is_fast(rng, fast_search_prob);
+  t.search_seed = splitmix64(rng);
+  return t;
+}
+// the iterations of a turn's search: fast_budget == 0 means the full budget
+OAK_PICK_HD inline uint32_t turn_budget(bool fast, uint32_t iterations, uint32_t fast_budget) { return fast && fast_budget ? fast_budget : iterations; }
+
 OAK_PICK_HD inline uint16_t compress_prob(double x) { // compress_probs<double, uint16_t> (compressed-frame.h:11-25)
 #pragma clang fp contract(off)
   const double v = x * 65535.0;

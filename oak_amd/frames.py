@@ -55,12 +55,22 @@ def write_frames(battle, result, updates):
     return out[:written.value].tobytes()
 
 
+def _set_fast(prm, fast_budget, fast_search_prob, fast_policy_mode):
+    """The fast-search fields of oakgpu_selfplay_params (generate's --fast-budget / --fast-search-prob; all zero = off)."""
+    mode = fast_policy_mode.encode()
+    if len(mode) > 15:
+        raise ValueError("fast_policy_mode: at most 15 characters")
+    prm.fast_budget, prm.fast_search_prob, prm.fast_policy_mode = int(fast_budget), float(fast_search_prob), mode
+
+
 def selfplay_game(ctx, teams, battle_seed, iterations=1 << 12, batch=1024, bandit="ucb", c=2.0, evaluator="mc", policy_mode="e",
                   policy_temp=1.0, policy_min=0.0, max_battle_length=0, seed=1, alpha=0.05, root_rolls=3, other_rolls=1, keep_node=False,
-                  stats=None):
+                  stats=None, fast_budget=0, fast_search_prob=0.0, fast_policy_mode=""):
     """One self-play game on the GPU path (oakgpu_selfplay_game).  teams: uint8[2, 6, 5] (species + 4 moves per set).
     keep_node: generate's --keep-node (one heap for the game, Heap::update after every turn); stats: optional dict that
-    receives "nodes_kept".  Returns (record bytes, number of frames, final result byte)."""
+    receives "nodes_kept".  fast_search_prob > 0: generate's fast searches -- each turn is, with that probability (one draw from the
+    game's stream before the search seed), searched with fast_budget iterations (0 = iterations) and picked with fast_policy_mode
+    ("" = policy_mode); every frame stores the iterations that ran.  Returns (record bytes, number of frames, final result byte)."""
     use_net = not isinstance(evaluator, str)
     prm = _lib.SelfplayParams()
     prm.search = _lib.SearchParams(iterations=int(iterations), batch=int(batch), ucb_c=float(c),
@@ -72,6 +82,7 @@ def selfplay_game(ctx, teams, battle_seed, iterations=1 << 12, batch=1024, bandi
     prm.policy_temp, prm.policy_min = float(policy_temp), float(policy_min)
     prm.max_battle_length, prm.seed = int(max_battle_length), int(seed)
     prm.keep_node = 1 if keep_node else 0
+    _set_fast(prm, fast_budget, fast_search_prob, fast_policy_mode)
     t = np.ascontiguousarray(teams, dtype=np.uint8).reshape(60)
     cap = 4 + 2 + 384 + 1 + 83 * (int(max_battle_length) or 2048)
     out = np.zeros(cap, dtype=np.uint8)
@@ -85,7 +96,7 @@ def selfplay_game(ctx, teams, battle_seed, iterations=1 << 12, batch=1024, bandi
 
 def selfplay_games(ctxs, teams, battle_seeds, seeds, iterations=1 << 12, batch=1024, bandit="ucb", c=2.0, evaluator="mc", policy_mode="e",
                    policy_temp=1.0, policy_min=0.0, max_battle_length=0, alpha=0.05, root_rolls=3, other_rolls=1, keep_node=False,
-                   threads_per_game=0):
+                   threads_per_game=0, fast_budget=0, fast_search_prob=0.0, fast_policy_mode=""):
     """n self-play games at once on one GPU (oakgpu_selfplay_games): game g on ctxs[g] with teams[g] (uint8[n, 2, 6, 5]), battle_seeds[g]
     and policy seed seeds[g].  Returns a list of (record bytes, number of frames, final result byte) -- each what selfplay_game(ctxs[g],
     teams[g], battle_seeds[g], seed=seeds[g], ...) returns alone."""
@@ -102,6 +113,7 @@ def selfplay_games(ctxs, teams, battle_seeds, seeds, iterations=1 << 12, batch=1
         prms[g].policy_temp, prms[g].policy_min = float(policy_temp), float(policy_min)
         prms[g].max_battle_length, prms[g].seed = int(max_battle_length), int(seeds[g])
         prms[g].keep_node = 1 if keep_node else 0
+        _set_fast(prms[g], fast_budget, fast_search_prob, fast_policy_mode)
     t = np.ascontiguousarray(teams, dtype=np.uint8).reshape(n, 60)
     bs = (C.c_uint64 * n)(*[int(x) for x in battle_seeds])
     cap = 4 + 2 + 384 + 1 + 83 * (int(max_battle_length) or 2048)
@@ -135,7 +147,7 @@ def _selfplay_params(iterations, bandit, c, evaluator, policy_mode, policy_temp,
 
 def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="ucb", evaluator="mc", policy_mode="e", policy_temp=1.0,
                     policy_min=0.0, max_battle_length=0, root_rolls=3, other_rolls=1, max_depth=0, forest=None, solve_nash=True, stats=None,
-                    keep_node=False, keep_arena=0):
+                    keep_node=False, keep_arena=0, fast_budget=0, fast_search_prob=0.0, fast_policy_mode=""):
     """n self-play games at once over the forest search, resident on the GPU (oakgpu_forest_selfplay*): game g is selfplay_game(ctx,
     teams[g], battle_seeds[g], batch=1, seed=seeds[g], ...).  teams uint8[n, 2, 6, 5]; forest: None (one made for this call) or a
     search.Forest to reuse; stats: optional dict that receives turns, rows searched, compactions and host reads (of the live count), and
@@ -145,6 +157,10 @@ def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="
     keep_node: generate's --keep-node -- each game's tree goes on from turn to turn (a kept forest: one made with keep_arena nodes per tree,
     0 = 4 * iterations + 1, or the caller's Forest(keep_arena=...)); a sixth value is then returned, nodes_kept uint32[n] (selfplay_game's
     stats["nodes_kept"] per game), and stats also receives nodes_kept, dropped, mismatches and carried_nodes.
+    fast_search_prob > 0: generate's fast searches, as in selfplay_game; each turn is ONE budgets search over the live rows, those of the
+    larger budget first.  stats then also tells fast_frames, full_frames (the frames min_iterations = fast_budget + 1 keeps for training),
+    launched and run (tree-iterations: equal, since no launch covers a finished tree).  A forest made here holds max(iterations,
+    fast_budget) iterations.
     numpy arrays in: (stream bytes, offsets uint64[n + 1], n_frames uint32[n], results uint8[n], status uint8[n]) -- the stream is the
     kept games' records in game order, a dropped game (status MAX_LENGTH / ZERO_POLICY, see FSP_STATUS) has zero bytes.
     torch GPU tensors in (teams uint8 [n, 60]; battle_seeds, seeds int64 bit patterns): the same five as tensors on that device; nothing
@@ -153,12 +169,13 @@ def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="
     use_net = not isinstance(evaluator, str)
     prm = _selfplay_params(iterations, bandit, c, evaluator, policy_mode, policy_temp, policy_min, max_battle_length, root_rolls, other_rolls, max_depth)
     prm.keep_node = 1 if keep_node else 0
+    _set_fast(prm, fast_budget, fast_search_prob, fast_policy_mode)
     net = evaluator.handle if use_net else None
     on_device = hasattr(teams, "data_ptr")
     n = int(teams.shape[0]) if on_device else len(np.asarray(seeds).reshape(-1))
     own = forest is None
     if own:
-        forest = Forest(ctx, max(n, 1), max(int(iterations), 1), contextual=bandit == "pucb", keep_arena=int(keep_arena) if keep_node else None)
+        forest = Forest(ctx, max(n, 1), max(int(iterations), int(fast_budget), 1), contextual=bandit == "pucb", keep_arena=int(keep_arena) if keep_node else None)
     lib = ctx.lib
     try:
         size = C.c_size_t(0)
@@ -209,6 +226,8 @@ def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="
             tr = (C.c_uint64 * 2)()
             _lib.check(lib.oakgpu_forest_selfplay_last_traffic(forest.handle, C.byref(tr)))
             stats.update(loop_syncs=int(tr[0]), loop_copies=int(tr[1]))
+            _lib.check(lib.oakgpu_forest_selfplay_fast_stats(forest.handle, C.byref(st)))
+            stats.update(fast_frames=int(st[0]), full_frames=int(st[1]), launched=int(st[2]), run=int(st[3]))
             if keep_node:
                 _lib.check(lib.oakgpu_forest_selfplay_keep_stats(forest.handle, C.byref(st)))
                 stats.update(nodes_kept=int(st[0]), dropped=int(st[1]), mismatches=int(st[2]), carried_nodes=int(st[3]))
@@ -220,7 +239,8 @@ def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="
 
 def forest_selfplay_check(max_trees, max_iterations, contextual, iterations, n=1, teams=None, c=2.0, bandit="ucb", evaluator="mc", policy_mode="e",
                           policy_temp=1.0, policy_min=0.0, max_battle_length=0, root_rolls=3, other_rolls=1, max_depth=0, solve_nash=True,
-                          has_net=False, keep_node=False, matrix_ucb=0, duration_us=0, kept=False):
+                          has_net=False, keep_node=False, matrix_ucb=0, duration_us=0, kept=False, fast_budget=0, fast_search_prob=0.0,
+                          fast_policy_mode=""):
     """oakgpu_forest_selfplay_check alone (host only, no GPU): raises OakGpuError with the refusal's message.  evaluator "mc" | "poke-engine" |
     "net" (with has_net saying whether a network is given); kept: the limits are a kept forest's (oakgpu_forest_create_kept)."""
     prm = _selfplay_params(iterations, bandit, c, "mc" if evaluator == "net" else evaluator, policy_mode, policy_temp, policy_min, max_battle_length,
@@ -228,6 +248,7 @@ def forest_selfplay_check(max_trees, max_iterations, contextual, iterations, n=1
     if evaluator == "net":
         prm.search.eval = 1
     prm.keep_node, prm.search.matrix_ucb, prm.search.duration_us = int(bool(keep_node)), int(matrix_ucb), int(duration_us)
+    _set_fast(prm, fast_budget, fast_search_prob, fast_policy_mode)
     t = None if teams is None else np.ascontiguousarray(teams, dtype=np.uint8).reshape(n, 60)
     _lib.check(_lib.load().oakgpu_forest_selfplay_check(int(max_trees), int(max_iterations), int(bool(contextual)) | (2 if kept else 0), C.byref(prm), int(bool(has_net)), int(n),
                                                         None if t is None else t.ctypes.data_as(C.c_void_p), _lib.nash_mode(solve_nash)))
@@ -253,6 +274,14 @@ def selfplay_pick_host(m, n, visit_matrix, value_matrix, iterations, rng, p1_nas
                                              C.byref(state), C.byref(ev), vp(e1), vp(e2), vp(q1), vp(q2), C.byref(i), C.byref(j), vp(upd), C.byref(ulen)))
     return {"empirical_value": ev.value, "p1_empirical": e1, "p2_empirical": e2, "p1_policy": q1, "p2_policy": q2, "i": i.value, "j": j.value,
             "rng": state.value, "update": upd[:ulen.value].tobytes()}
+
+
+def selfplay_prelude_host(rng, fast_search_prob):
+    """oakgpu_selfplay_prelude_host (no GPU): the start of one turn on a game's stream, by the rule both game loops compile.  Returns
+    (use_fast, search_seed, rng advanced)."""
+    state, fast, seed = C.c_uint64(int(rng)), C.c_int32(0), C.c_uint64(0)
+    _lib.check(_lib.load().oakgpu_selfplay_prelude_host(C.byref(state), float(fast_search_prob), C.byref(fast), C.byref(seed)))
+    return bool(fast.value), int(seed.value), int(state.value)
 
 
 # ---- replay check of `.battle.data` records on the GPU (oakgpu_replay_records; the rules are in include/oakgpu.h) ----------------

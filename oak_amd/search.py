@@ -348,6 +348,13 @@ class Forest:
         _lib.check(self.ctx.lib.oakgpu_forest_last_stats(self.handle, C.byref(out)))
         return tuple(int(x) for x in out)
 
+    def last_rows(self):
+        """(tree-iterations launched, tree-iterations run) of the last search: the sum over the iterations of the rows their launches covered,
+        and the sum of the trees' budgets; equal when the budgets do not increase in row order, and after every call without budgets."""
+        out = (C.c_uint64 * 2)()
+        _lib.check(self.ctx.lib.oakgpu_forest_last_rows(self.handle, C.byref(out)))
+        return int(out[0]), int(out[1])
+
     def close(self):
         if self.handle:   # (a forest that outlived its context still frees its arenas: the library then waits for the device)
             self.ctx.lib.oakgpu_forest_destroy(self.ctx.handle, self.handle)
@@ -367,7 +374,7 @@ _FOREST_TENSORS = (("m", "uint8", ()), ("n", "uint8", ()), ("p1_choices", "uint8
 
 
 def forest_search(ctx, battles, durations, results, seeds, iterations, c=2.0, bandit="ucb", evaluator="mc", max_depth=0, root_rolls=3,
-                  other_rolls=1, solve_nash=False, trace_levels=0, forest=None, keep=False):
+                  other_rolls=1, solve_nash=False, trace_levels=0, forest=None, keep=False, budgets=None):
     """n searches at once, one GPU lane per tree, every tree on the device (include/oakgpu.h: oakgpu_forest_search*): tree g is
     tree_search(ctx, battles[g], durations[g], results[g], iterations, batch=1, seed=seeds[g], ...) iteration for iteration.  bandit "ucb" |
     "pucb"; evaluator "mc", "poke-engine" or a Network; forest: None (one made for this call) or a Forest to reuse.
@@ -380,7 +387,11 @@ def forest_search(ctx, battles, durations, results, seeds, iterations, c=2.0, ba
     torch GPU tensors in (battles [n, 384], durations [n, 8], results [n] uint8; seeds [n] int64 bit patterns): a dict of tensors on that
     device, one row per tree -- m, n, p1_choices, p2_choices, visit_matrix [n, 9, 9], value_matrix, iterations, nodes, total_depth,
     initial_value, p1_logit, p2_logit, p1_prior, p2_prior, stream (int64 bit patterns), and "trace" (uint8 [n, iterations, record bytes])
-    with trace_levels > 0; nothing is copied to the host."""
+    with trace_levels > 0; nothing is copied to the host.
+    budgets (None, or n x uint32; a torch int32 GPU tensor with tensors in): tree g runs budgets[g] iterations, 1 <= budgets[g] <=
+    iterations, and is bit for bit the tree of a call with iterations = budgets[g] (oakgpu_forest_search_budgets*); `iterations` sizes the
+    trace, whose records past a tree's budget stay zero.  Rows of non-increasing budgets cost no launch over a finished tree
+    (Forest.last_rows())."""
     use_net = not isinstance(evaluator, str)
     prm = _lib.SearchParams(iterations=int(iterations), batch=1, ucb_c=float(c), bandit={"ucb": 0, "pucb": 1, "ucb1": 2, "exp3": 3, "pexp3": 4}[bandit],
                             eval=1 if use_net else {"mc": 0, "poke-engine": 2}[evaluator], max_depth=int(max_depth), root_rolls=int(root_rolls),
@@ -402,7 +413,15 @@ def forest_search(ctx, battles, durations, results, seeds, iterations, c=2.0, ba
             ptrs = _lib.ForestOutputs(**{name: out[name].data_ptr() for name, _, _ in _FOREST_TENSORS})
             mine, theirs = torch.cuda.ExternalStream(ctx.stream_ptr(), device=dev), torch.cuda.current_stream(dev)
             mine.wait_stream(theirs)
-            _lib.check((ctx.lib.oakgpu_forest_search_kept_dev if keep else ctx.lib.oakgpu_forest_search_dev)(forest.handle, net, C.byref(prm), battles.data_ptr(), durations.data_ptr(), results.data_ptr(),
+            if budgets is not None:
+                budgets = budgets.to(torch.int32).contiguous()
+                if int(budgets.numel()) != n:
+                    raise ValueError("forest_search: one budget per tree")
+                _lib.check((ctx.lib.oakgpu_forest_search_budgets_kept_dev if keep else ctx.lib.oakgpu_forest_search_budgets_dev)(
+                    forest.handle, net, C.byref(prm), battles.data_ptr(), durations.data_ptr(), results.data_ptr(), seeds.data_ptr(), budgets.data_ptr(), n,
+                    C.byref(ptrs), trace.data_ptr() if trace_levels else None, int(trace_levels)))
+            else:
+                _lib.check((ctx.lib.oakgpu_forest_search_kept_dev if keep else ctx.lib.oakgpu_forest_search_dev)(forest.handle, net, C.byref(prm), battles.data_ptr(), durations.data_ptr(), results.data_ptr(),
                                                         seeds.data_ptr(), n, C.byref(ptrs), trace.data_ptr() if trace_levels else None, int(trace_levels)))
             theirs.wait_stream(mine)
             if trace_levels:
@@ -416,7 +435,16 @@ def forest_search(ctx, battles, durations, results, seeds, iterations, c=2.0, ba
         outs = (_lib.SearchOutput * max(n, 1))()
         streams = np.zeros(max(n, 1), np.uint64)
         trace = np.zeros((n, int(iterations)), dtype=trace_dtype(trace_levels)) if trace_levels else None
-        _lib.check((ctx.lib.oakgpu_forest_search_kept if keep else ctx.lib.oakgpu_forest_search)(forest.handle, net, C.byref(prm), battles.ctypes.data_as(C.c_void_p), durations.ctypes.data_as(C.c_void_p),
+        if budgets is not None:
+            budgets = np.ascontiguousarray(np.asarray(budgets).astype(np.uint32)).reshape(-1)
+            if len(budgets) != n:
+                raise ValueError("forest_search: one budget per tree")
+            _lib.check((ctx.lib.oakgpu_forest_search_budgets_kept if keep else ctx.lib.oakgpu_forest_search_budgets)(
+                forest.handle, net, C.byref(prm), battles.ctypes.data_as(C.c_void_p), durations.ctypes.data_as(C.c_void_p), results.ctypes.data_as(C.c_void_p),
+                seeds.ctypes.data_as(C.c_void_p), budgets.ctypes.data_as(C.c_void_p), n, outs, _lib.nash_mode(solve_nash), streams.ctypes.data_as(C.c_void_p),
+                trace.ctypes.data_as(C.c_void_p) if trace_levels else None, int(trace_levels)))
+        else:
+            _lib.check((ctx.lib.oakgpu_forest_search_kept if keep else ctx.lib.oakgpu_forest_search)(forest.handle, net, C.byref(prm), battles.ctypes.data_as(C.c_void_p), durations.ctypes.data_as(C.c_void_p),
                                                 results.ctypes.data_as(C.c_void_p), seeds.ctypes.data_as(C.c_void_p), n, outs, _lib.nash_mode(solve_nash),
                                                 streams.ctypes.data_as(C.c_void_p), trace.ctypes.data_as(C.c_void_p) if trace_levels else None,
                                                 int(trace_levels)))
@@ -438,3 +466,9 @@ def forest_search(ctx, battles, durations, results, seeds, iterations, c=2.0, ba
     finally:
         if own:
             forest.close()
+
+
+def forest_budgets_check(budgets, iterations):
+    """oakgpu_forest_budgets_check alone (host only, no GPU): raises OakGpuError naming the lowest tree whose budget is 0 or above iterations."""
+    b = np.ascontiguousarray(np.asarray(budgets).astype(np.uint32)).reshape(-1)
+    _lib.check(_lib.load().oakgpu_forest_budgets_check(b.ctypes.data_as(C.c_void_p) if len(b) else None, len(b), int(iterations)))

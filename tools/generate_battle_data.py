@@ -5,6 +5,7 @@ files under --out.
   python tools/generate_battle_data.py --out DIR [--games N] [--batch B] [--teams FILE] [--budget K] [--bandit ucb-2.0 | pucb-1.5]
          [--eval mc | fp | NET.battle.net] [--discrete] [--policy-mode e] [--policy-temp 1] [--policy-min 0] [--max-battle-length L]
          [--no-nash | --device-nash] [--seed S] [--file-mb 8] [--keep-node [--keep-arena NODES]]
+         [--fast-budget K --fast-search-prob P [--fast-policy-mode MODE]]
          [--build-network NET.build.net [--team-modify-prob P] [--pokemon-delete-prob P] [--move-delete-prob P] [--max-pokemon K]]
 
 --teams FILE: JSON {"teams": [[[species, move, move, move, move] x 6] ...]} by name, the layout of tests/golden/ou_sample_teams.json (the
@@ -14,6 +15,12 @@ is closed once it holds --file-mb MiB of whole records; names are <seed>_<index>
 frames is dropped, as generate drops it.  --keep-node: each game's tree goes on into the next turn (generate.cc:324-333) on a kept forest
 of --keep-arena nodes per tree (0 = 4 * budget + 1); then the keep-node ratio is printed as generate prints it (updates that found their
 child / updates), with the trees dropped for want of room.  Prints games, frames, dropped games and seconds.
+
+--fast-budget / --fast-search-prob / --fast-policy-mode (generate.cc:292-299; rl.py passes all of --budget, --fast-budget and
+--fast-search-prob): each turn is, with probability --fast-search-prob, searched with --fast-budget iterations and picked with
+--fast-policy-mode (default: --policy-mode) instead of --budget and --policy-mode; every frame is written with the iterations that ran.
+Training then wants --min-iterations = fast_budget + 1 (tools/train_battle_net.py), as rl.py sets it, so that only the full-budget
+frames reach the loss.  The fast and full frame counts and the tree-iterations launched and run are printed.
 
 --build-network: the other half of generate (TeamBuilding::Provider::get_trajectory): both seats' teams come from oak_amd.build.provide on
 the device -- a team of the pool, truncated to --max-pokemon, with probability --team-modify-prob thinned by --pokemon-delete-prob /
@@ -71,6 +78,9 @@ def main():
     ap.add_argument("--file-mb", type=float, default=8.0)
     ap.add_argument("--keep-node", action="store_true")
     ap.add_argument("--keep-arena", type=int, default=0)
+    ap.add_argument("--fast-budget", type=int, default=0, help="iterations for non-training frames (0 = --budget); train with --min-iterations = fast_budget + 1")
+    ap.add_argument("--fast-search-prob", type=float, default=0.0, help="probability that a turn is a fast search (0 = off)")
+    ap.add_argument("--fast-policy-mode", default="", help="policy mode of a fast turn's pick (default: --policy-mode)")
     ap.add_argument("--build-network", default="", help="a .build.net: build both seats' teams on the device and write .build.data")
     ap.add_argument("--team-modify-prob", type=float, default=0.0)
     ap.add_argument("--pokemon-delete-prob", type=float, default=0.0)
@@ -100,10 +110,11 @@ def main():
     rng = np.random.default_rng(a.seed)
     os.makedirs(a.out, exist_ok=True)
     batch = max(1, min(a.batch, a.games))
-    forest = Forest(ctx, batch, a.budget, contextual=name == "pucb", keep_arena=a.keep_arena if a.keep_node else None)
+    forest = Forest(ctx, batch, max(a.budget, a.fast_budget), contextual=name == "pucb", keep_arena=a.keep_arena if a.keep_node else None)
     limit = int(a.file_mb * (1 << 20))
     played = frames = dropped = files = 0
     updates = updates_with_node = trees_dropped = 0
+    fast_frames = full_frames = launched = run = 0
     pending = []
     t0 = time.perf_counter()
 
@@ -134,7 +145,8 @@ def main():
         stream, offsets, n_frames, results, status = forest_selfplay(
             ctx, teams, battle_seeds, seeds, a.budget, c=float(c or 2.0), bandit=name, evaluator=evaluator, policy_mode=a.policy_mode,
             policy_temp=a.policy_temp, policy_min=a.policy_min, max_battle_length=a.max_battle_length, forest=forest, solve_nash=False if a.no_nash else ("device" if a.device_nash else True),
-            keep_node=a.keep_node, stats=stats)[:5]
+            keep_node=a.keep_node, stats=stats, fast_budget=a.fast_budget, fast_search_prob=a.fast_search_prob, fast_policy_mode=a.fast_policy_mode)[:5]
+        fast_frames, full_frames, launched, run = fast_frames + stats["fast_frames"], full_frames + stats["full_frames"], launched + stats["launched"], run + stats["run"]
         if a.keep_node:   # RuntimeData::update_with_node_counter / update_counter (generate.cc:412-416)
             updates, updates_with_node, trees_dropped = updates + int(n_frames.sum()), updates_with_node + stats["nodes_kept"], trees_dropped + stats["dropped"]
         kept = status == 0
@@ -160,6 +172,9 @@ def main():
     if build_net is not None:
         print("team building: %d records, %.2f seconds (%.1f %% of the call)" % (build_records, build_seconds, 100 * build_seconds / s))
         build_net.close()
+    if a.fast_search_prob > 0:
+        print("fast frames: %d, full frames: %d (the frames --min-iterations %d keeps), tree-iterations launched: %d, run: %d" % (
+            fast_frames, full_frames, (a.fast_budget or a.budget) + 1, launched, run))
     if a.keep_node:
         print("keep node ratio: %g" % (updates_with_node / max(updates, 1)))
         print("trees dropped for want of room: %d" % trees_dropped)
