@@ -84,12 +84,12 @@ struct Tables {
   const lds_u32 *sp0;    // [152]
   const lds_u32 *sp1;    // [152]
   const lds_u8 *chart;   // [225]
-  const lds_u16 *boost;  // [13] num | den<<8
+  const lds_u32 *boost;  // [13] ceil(2^29 * num / den): x * num / den == umulhi(x << 3, boost) for x < 2^16
   const lds_u32 *rcp;    // [256] floor((2^32-1)/d) + 1: exact x / d by one mul-hi for x < 2^24, d in 2..255
   const lds_u16 *fx;     // [68] per-effect descriptor (fx_desc below): gate / action class / secondary effect
   const lds_u16 *bits;   // [32] the set-bit positions of a mask < 32, lowest first, 3 bits each (bit_list below): the random policy's pick
 };
-static constexpr int TABLE_LDS_BYTES = 166 * 4 + 168 + 152 * 4 + 152 * 4 + 228 + 28 + 256 * 4 + 68 * 2 + 32 * 2;
+static constexpr int TABLE_LDS_BYTES = 166 * 4 + 168 + 152 * 4 + 152 * 4 + 228 + 13 * 4 + 256 * 4 + 68 * 2 + 32 * 2;
 
 // ---- per-effect descriptors: what gen1_regs.hpp's run_move needs to know about a move effect, as data.
 // Lanes of a wave run different moves; a `switch (effect)` costs the wave every case any lane takes plus the
@@ -177,8 +177,8 @@ __device__ __forceinline__ Tables tables_at(lds_u8 *lds) {
   lds_u32 *sp0 = (lds_u32 *)(pp + 168);
   lds_u32 *sp1 = sp0 + 152;
   lds_u8 *chart = (lds_u8 *)(sp1 + 152);
-  lds_u16 *boost = (lds_u16 *)(chart + 228);
-  lds_u32 *rcp = (lds_u32 *)(chart + 228 + 28);
+  lds_u32 *boost = (lds_u32 *)(chart + 228);
+  lds_u32 *rcp = boost + 13;
   lds_u16 *fx = (lds_u16 *)(rcp + 256);
   Tables t{mv, pp, sp0, sp1, chart, boost, rcp, fx, fx + 68};
   return t;
@@ -190,14 +190,14 @@ __device__ __forceinline__ Tables tables_at(lds_u8 *lds) {
 // play it, so a kernel that stages its own tables leaves it out.
 template <bool BIT_LISTS = false>
 __device__ inline Tables stage_tables(lds_u8 *lds, const uint32_t *g_mv, const uint8_t *g_pp, const uint32_t *g_sp0,
-                                      const uint32_t *g_sp1, const uint8_t *g_chart, const uint16_t *g_boost) {
+                                      const uint32_t *g_sp1, const uint8_t *g_chart, const uint32_t *g_boost) {
   lds_u32 *mv = (lds_u32 *)lds;
   lds_u8 *pp = lds + 166 * 4;
   lds_u32 *sp0 = (lds_u32 *)(pp + 168);
   lds_u32 *sp1 = sp0 + 152;
   lds_u8 *chart = (lds_u8 *)(sp1 + 152);
-  lds_u16 *boost = (lds_u16 *)(chart + 228);
-  lds_u32 *rcp = (lds_u32 *)(chart + 228 + 28);
+  lds_u32 *boost = (lds_u32 *)(chart + 228);
+  lds_u32 *rcp = boost + 13;
   lds_u16 *fx = (lds_u16 *)(rcp + 256);
   for (int i = threadIdx.x; i < 256; i += blockDim.x) rcp[i] = i ? 0xFFFFFFFFu / (uint32_t)i + 1u : 0u;
   for (int i = threadIdx.x; i < 68; i += blockDim.x) fx[i] = OAK_FX.d[i];

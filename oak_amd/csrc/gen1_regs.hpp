@@ -261,11 +261,9 @@ struct EngineR {
     const uint32_t r = x - __umulhi(x, rc) * n; // quotient estimate is exact or one too large: r in [-n, n)
     return r < r + n ? r : r + n;               // (one unsigned min: a negative r is the larger of the two)
   }
-  __device__ __forceinline__ uint32_t scale_boost(uint32_t x, int stage) const {
-    if (stage == 0) return x;
-    const uint32_t b = T.boost[stage + 6], v = x * (b & 0xFF), den = b >> 8; // den is 100, 10 or 1
-    return den == 100 ? v / 100 : den == 10 ? v / 10 : v;
-  }
+  // x * num / den of the stage's ratio by one mul-hi against ceil(2^29 * num / den): exact for x < 2^16 at all 13 ratios
+  // (tests/test_stage_scaling.py walks every one), stage 0 included -- no branch, no division
+  __device__ __forceinline__ uint32_t scale_boost(uint32_t x, int stage) const { return __umulhi(x << 3, T.boost[stage + 6]); }
 
   // unmodified (party) stat idx of side x; through Transform this is the copied Pokemon's stat (LDS)
   __device__ __forceinline__ uint32_t unmodified_stat(const SideR &x, int idx) { // 0 atk 1 def 2 spe 3 spc

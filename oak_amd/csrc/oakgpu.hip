@@ -1694,6 +1694,8 @@ int oakgpu_device_count(void) {
   return n;
 }
 
+// the queue kernel runs four one-wave workgroups per SIMD: sixteen of them must fit in a CU's 160 KiB of LDS
+static_assert(24 * 64 * 4 + oak::TABLE_LDS_PAD + oak::COLD_LDS_BYTES <= 160 * 1024 / 16, "k_rollout_queue<64, 4>: sixteen workgroups no longer fit in a CU's LDS");
 static int set_lds_limits() {
   HIPCHK(hipFuncSetAttribute((const void *)oak::k_rollout_regs<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 24 * 64 * 4 + oak::TABLE_LDS_PAD));
   HIPCHK(hipFuncSetAttribute((const void *)oak::k_rollout_staged, hipFuncAttributeMaxDynamicSharedMemorySize, oak::STAGED_LDS_BYTES));
