@@ -111,6 +111,21 @@ int oakgpu_set_move_carry(oakgpu_ctx *ctx, int below);
  * OAKGPU_MOVE_CARRY_DRY at context creation.  Default OAKGPU_MOVE_CARRY_DRY_DEFAULT. */
 #define OAKGPU_MOVE_CARRY_DRY_DEFAULT 0
 int oakgpu_set_move_carry_dry(oakgpu_ctx *ctx, int below);
+/* Lean rollout.  The chance durations are observational state -- the caller's hidden-variable resampling and the leaf network's
+ * encoder read them, the engine's transitions never do (tests/test_durations_observational.py).  With on != 0 a group launch (the
+ * queue kernel) NONE of whose batches gives a durations_out runs an instantiation that keeps no durations at all: it reads a batch's
+ * durations for the prep of a fresh playout only (with prep = 0 the instantiation has no prep code either), parks none with a
+ * donated or suspended playout and writes none.  Any prep and any
+ * battles_out go with it; one batch with a durations_out and the whole group runs the kernel that keeps them.  Results, step counts,
+ * values, battles and the advanced prng are byte for byte the same either way (tests/test_gpu_lean_rollout.py).  on = 0: always the
+ * kernel that keeps durations (A / B; also OAKGPU_LEAN_ROLLOUT=0 at context creation).  Default OAKGPU_LEAN_ROLLOUT_DEFAULT.
+ * oakgpu_last_launch_lean: 1 if the context's last group launch ran lean, else 0.
+ * The sliced search steps (oakgpu_root_steps_*) return aggregates only and run lean the same way: a handle takes the setting when it
+ * is created and keeps it for its life (the carried playouts' records are laid out for the one kernel); aggregates, turn-step counts
+ * and lane streams are the same either way (tests/test_gpu_lean_root_step.py). */
+#define OAKGPU_LEAN_ROLLOUT_DEFAULT 1
+int oakgpu_set_lean_rollout(oakgpu_ctx *ctx, int on);
+int oakgpu_last_launch_lean(oakgpu_ctx *ctx);
 /* Words of that block written by the queue kernel's standstill skip (cleared by every queue launch). */
 #define OAKGPU_CTL_FAST_FORWARDED 44 /* playouts whose inert standstill was taken in one go */
 #define OAKGPU_CTL_SKIPPED_STEPS 45  /* turn-steps those playouts skipped (they are part of steps_out) */

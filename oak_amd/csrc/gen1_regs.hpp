@@ -81,7 +81,10 @@ enum { PS_REFILL = 0, PS_STEP, PS_LEGAL_DRAW, PS_ORDER, PS_EXEC_MOVE, PS_SWITCH_
        PS_CALC_DAMAGE, PS_APPLY_HITS, PS_DAMAGE_TAIL, PS_HEAVY, PS_H_CONVERSION, PS_H_HAZE, PS_H_HEAL, PS_H_MIMIC,
        PS_H_POISON, PS_H_SUBSTITUTE, PS_H_TRANSFORM, PS_H_BIDE, PS_H_SLEEP, PS_H_DISABLE, PS_EXEC_MOVE_K0, PS_EXEC_MOVE_K1, PS_COUNT };
 
-struct SideR {
+// KEEP_DUR = false: the record of an engine that keeps no chance durations (EngineR's KEEP_DUR) -- no `dur` member at all, so
+// nothing (swap_sides' "+v" operands least of all) can keep a register alive for it.
+template <bool KEEP_DUR>
+struct SideRT {
   uint32_t a0, a1, a2; // active: hp|atk<<16, def|spe<<16, spc|species<<16|types<<24
   uint32_t bo;         // boosts nibbles: atk def | spe spc | acc eva
   uint32_t vlo, vhi;   // volatiles
@@ -91,31 +94,53 @@ struct SideR {
   uint32_t dur;        // chance durations of this side
   uint32_t misc;       // bits 0-5 alive mask by order position, bit 8 absolute player, bits 16-23 damage override
 };
+template <>
+struct SideRT<false> {
+  uint32_t a0, a1, a2;
+  uint32_t bo;
+  uint32_t vlo, vhi;
+  uint32_t m01, m23;
+  uint32_t p0, p1, p2, p3, p4, p5;
+  uint32_t o0, o1;
+  uint32_t misc;
+};
+typedef SideRT<true> SideR;
 
 #define OAK_FOR_SIDE_FIELDS(X) X(a0) X(a1) X(a2) X(bo) X(vlo) X(vhi) X(m01) X(m23) X(p0) X(p1) X(p2) X(p3) X(p4) X(p5) X(o0) X(o1) X(dur) X(misc)
+#define OAK_FOR_SIDE_FIELDS_LEAN(X) X(a0) X(a1) X(a2) X(bo) X(vlo) X(vhi) X(m01) X(m23) X(p0) X(p1) X(p2) X(p3) X(p4) X(p5) X(o0) X(o1) X(misc)
 
-__device__ __forceinline__ void swap_sides(SideR &a, SideR &b) {
-  // v_swap_b32: one instruction per field (the compiler's own lowering is three moves through a temporary)
-#define X(f) asm("v_swap_b32 %0, %1" : "+v"(a.f), "+v"(b.f));
-  OAK_FOR_SIDE_FIELDS(X)
-#undef X
+// (one overload per record: the field list is a macro)
+#define OAK_SIDE_OPS(SIDE, FIELDS) \
+__device__ __forceinline__ void swap_sides(SIDE &a, SIDE &b) { \
+  /* v_swap_b32: one instruction per field (the compiler's own lowering is three moves through a temporary) */ \
+  FIELDS(OAK_SIDE_SWAP) \
+} \
+__device__ __forceinline__ void cswap_sides(bool c, SIDE &a, SIDE &b) { \
+  FIELDS(OAK_SIDE_CSWAP) \
+} \
+/* the sides by PLAYER, whichever frame they stand in (c: the frame is flipped, a holds P2): copies for a reader that must leave a and b alone */ \
+__device__ __forceinline__ void sides_by_player(bool c, const SIDE &a, const SIDE &b, SIDE &p1, SIDE &p2) { \
+  FIELDS(OAK_SIDE_BY_PLAYER) \
 }
-__device__ __forceinline__ void cswap_sides(bool c, SideR &a, SideR &b) {
-#define X(f) { uint32_t t = c ? b.f : a.f; b.f = c ? a.f : b.f; a.f = t; }
-  OAK_FOR_SIDE_FIELDS(X)
-#undef X
-}
-// the sides by PLAYER, whichever frame they stand in (c: the frame is flipped, a holds P2): copies for a reader that must leave a and b alone
-__device__ __forceinline__ void sides_by_player(bool c, const SideR &a, const SideR &b, SideR &p1, SideR &p2) {
-#define X(f) p1.f = c ? b.f : a.f; p2.f = c ? a.f : b.f;
-  OAK_FOR_SIDE_FIELDS(X)
-#undef X
-}
+#define OAK_SIDE_SWAP(f) asm("v_swap_b32 %0, %1" : "+v"(a.f), "+v"(b.f));
+#define OAK_SIDE_CSWAP(f) { uint32_t t = c ? b.f : a.f; b.f = c ? a.f : b.f; a.f = t; }
+#define OAK_SIDE_BY_PLAYER(f) p1.f = c ? b.f : a.f; p2.f = c ? a.f : b.f;
+OAK_SIDE_OPS(SideRT<true>, OAK_FOR_SIDE_FIELDS)
+OAK_SIDE_OPS(SideRT<false>, OAK_FOR_SIDE_FIELDS_LEAN)
+#undef OAK_SIDE_OPS
+#undef OAK_SIDE_SWAP
+#undef OAK_SIDE_CSWAP
+#undef OAK_SIDE_BY_PLAYER
 
 // GIN_LDS: the lane's input battle lives in LDS (k_rollout_staged's staged copy) -- `gin` is then an LDS pointer and the immutable party
 // data is read with ds_read; as a generic pointer (flat loads that resolve to LDS) the staged kernel carried 44-54 spilled SGPRs.
-template <int STRIDE, bool TRACK_ACTIONS, bool GIN_LDS = false>
+// KEEP_DUR = false: an engine for launches that hand no durations back.  The chance-durations word is observational state (the
+// caller's hidden-variable resampling, the leaf network's encoder): no transition reads it, so the battle, both RNG streams, the
+// result and the step count are what they are with it (tests/test_durations_observational.py).  dset is empty, dget is 0, and
+// prep takes the word as an argument (randomize_hidden).
+template <int STRIDE, bool TRACK_ACTIONS, bool GIN_LDS = false, bool KEEP_DUR = true>
 struct EngineR {
+  typedef SideRT<KEEP_DUR> SideR;
   lds_u32 *m; // party storage (lane-interleaved LDS: dword w of this lane at m[w * STRIDE])
   Tables T;
   SideR S, F; // mover / target frame
@@ -217,10 +242,15 @@ struct EngineR {
   static __device__ __forceinline__ void boost_put(SideR &x, int idx, int v) {
     x.bo = (x.bo & ~(15u << (4 * idx))) | (((uint32_t)v & 15) << (4 * idx));
   }
-  static __device__ __forceinline__ uint32_t dget(const SideR &x, int sh, int bits) { return (x.dur >> sh) & ((1u << bits) - 1); }
+  static __device__ __forceinline__ uint32_t dget(const SideR &x, int sh, int bits) {
+    if constexpr (KEEP_DUR) return (x.dur >> sh) & ((1u << bits) - 1);
+    else return 0;
+  }
   static __device__ __forceinline__ void dset(SideR &x, int sh, int bits, uint32_t v) {
-    uint32_t mask = ((1u << bits) - 1) << sh;
-    x.dur = (x.dur & ~mask) | ((v << sh) & mask);
+    if constexpr (KEEP_DUR) {
+      uint32_t mask = ((1u << bits) - 1) << sh;
+      x.dur = (x.dur & ~mask) | ((v << sh) & mask);
+    }
   }
   static __device__ __forceinline__ void clear_binding(SideR &x) { x.vlo &= ~V_BINDING; dset(x, 28, 3, 0); }
   static __device__ __forceinline__ void status_modify(uint32_t st, SideR &x) {
@@ -309,6 +339,12 @@ struct EngineR {
     x.p4 = ((gdw(sd, pi, 4) & 0x000000FFu) | ((pp >> 24) << 8) | ((hs & 0xFFFF) << 16)) & keep;
     x.p5 = ((gdw(sd, pi, 5) & 0xFFFFFF00u) | ((hs >> 16) & 0xFF)) & keep;
   }
+  // an engine that keeps no durations takes none.  (The three-argument form below stays the ONE body and ignores its words here: moved
+  // behind one more inline layer it changed the register allocation of eleven kernels that keep durations.)
+  __device__ __forceinline__ void load_battle_global(const uint8_t *battle384) {
+    static_assert(!KEEP_DUR, "an engine that keeps durations loads them with the battle");
+    load_battle_global(battle384, 0, 0);
+  }
   __device__ __forceinline__ void load_battle_global(const uint8_t *battle384, uint32_t dur0, uint32_t dur1) {
     gin = (gin_t)battle384;
 #pragma unroll
@@ -326,7 +362,7 @@ struct EngineR {
     { const uint4 v = gin4(84); F.a2 = v.x; F.bo = v.y; F.vlo = v.z; F.vhi = v.w; }
     { const uint4 v = gin4(88); F.m01 = v.x; F.m23 = v.y; F.o0 = v.z; F.o1 = v.w; }
     { const uint4 v = gin4(92); turn = v.x & 0xFFFF; last_damage = v.x >> 16; lm = v.y; rng = (uint64_t)v.z | ((uint64_t)v.w << 32); }
-    S.dur = dur0; F.dur = dur1;
+    if constexpr (KEEP_DUR) { S.dur = dur0; F.dur = dur1; }
     S.misc = 0; F.misc = 1u << 8;
     actS = actF = 0;
     alive_from_lds(S); // same-lane LDS write -> read: ordered by the wave's own lgkmcnt
@@ -363,11 +399,11 @@ struct EngineR {
     *(uint4 *)(g + 92) = make_uint4(turn | (last_damage << 16), lm, (uint32_t)rng, (uint32_t)(rng >> 32));
   }
   // MCTS::randomize_hidden_variables (cpp/include/search/durations.h:25-97) on the register image;
-  // every draw reuses the same un-advanced battle.rng value
-  __device__ __forceinline__ void randomize_hidden_side(SideR &x) {
+  // every draw reuses the same un-advanced battle.rng value.  `d` = the side's chance durations: an argument, so that an engine
+  // which keeps none can still prep a fresh playout from a word its caller loaded and drops
+  __device__ __forceinline__ void randomize_hidden_side(SideR &x, const uint32_t d) {
     const uint32_t hi = (uint32_t)(rng >> 32), lo = (uint32_t)rng;
     auto mod = [&](uint32_t mm) { uint32_t two32 = (0xFFFFFFFFu % mm + 1) % mm; return ((hi % mm) * two32 + (lo % mm)) % mm; };
-    const uint32_t d = x.dur;
     const uint32_t confusion = (d >> 18) & 7, disable = (d >> 21) & 15, attacking = (d >> 25) & 7, binding = (d >> 28) & 7;
     if (confusion) {
       const uint32_t one = confusion == 1;
@@ -399,7 +435,8 @@ struct EngineR {
       }
     }
   }
-  __device__ __forceinline__ void randomize_hidden() { randomize_hidden_side(S); randomize_hidden_side(F); }
+  __device__ __forceinline__ void randomize_hidden(uint32_t dS, uint32_t dF) { randomize_hidden_side(S, dS); randomize_hidden_side(F, dF); }
+  __device__ __forceinline__ void randomize_hidden() { static_assert(KEEP_DUR, "no durations kept: pass them"); randomize_hidden(S.dur, F.dur); }
   // last_moves accessors by absolute player
   __device__ __forceinline__ uint32_t lm_index(uint32_t ap) const { return (lm >> (16 * ap)) & 0xFF; }
   __device__ __forceinline__ void set_lm_index(uint32_t ap, uint32_t v) { lm = (lm & ~(0xFFu << (16 * ap))) | ((v & 0xFF) << (16 * ap)); }
@@ -424,11 +461,13 @@ struct EngineR {
     uint32_t nal = (al & ~(1u | (1u << (slot - 1)))) | akb | (a0b << (slot - 1));
     if (slot == 1) nal = al;
     x.misc = (x.misc & ~63u) | nal;
-    uint32_t d = x.dur;
-    const uint32_t s0 = d & 7, sk = (d >> (3 * (slot - 1))) & 7;
-    d = (d & ~7u) | sk;
-    if (slot != 1) d = (d & ~(7u << (3 * (slot - 1)))) | (s0 << (3 * (slot - 1)));
-    x.dur = d & ((1u << 18) - 1);
+    if constexpr (KEEP_DUR) { // the sleep turns go with their Pokemon; the active's other durations end
+      uint32_t d = x.dur;
+      const uint32_t s0 = d & 7, sk = (d >> (3 * (slot - 1))) & 7;
+      d = (d & ~7u) | sk;
+      if (slot != 1) d = (d & ~(7u << (3 * (slot - 1)))) | (s0 << (3 * (slot - 1)));
+      x.dur = d & ((1u << 18) - 1);
+    }
     set_last_used(x, 0);
     set_last_used(y, 0);
     load_stored(x);
@@ -1409,8 +1448,11 @@ struct EngineR {
     par = false;
     if (st == ST_FRZ) return (x.misc & 63) == 1 || (x.vlo & locked) != 0;
     constexpr uint32_t busy = V_FLINCH | V_RECHARGING | V_CONFUSION | V_BIDE | V_THRASHING | V_CHARGING | V_INVULNERABLE | V_MULTIHIT | V_BINDING;
-    if ((st != 0 && st != ST_PAR) || !(struggle || (x.vlo & V_RAGE)) || (x.vlo & busy) != 0 || disable_left(x) != 0 || disable_move(x) != 0 ||
-        dget(x, 25, 3) != 0 || dget(x, 28, 3) != 0) return false;
+    // (the two duration terms keep a skipped stalemate's DURATIONS exact: the paralysed outcome clears them.  No battle byte depends on
+    // them -- the volatile bits they go with are in `busy` -- and no transition reads the word, so an engine that keeps no durations
+    // skips on the battle alone: exact for the battle, both RNG streams, the result and the step count, all that such a launch returns)
+    if ((st != 0 && st != ST_PAR) || !(struggle || (x.vlo & V_RAGE)) || (x.vlo & busy) != 0 || disable_left(x) != 0 || disable_move(x) != 0) return false;
+    if constexpr (KEEP_DUR) if (dget(x, 25, 3) != 0 || dget(x, 28, 3) != 0) return false;
     const Move mv = move_data(sel);
     const uint32_t eff = mv.effect(), ft = types(y);
     const bool plain = mv.bp() != 0 && sel != M_Counter && eff != E_SpecialDamage && eff != E_SuperFang && eff != E_OHKO && eff != E_Charge &&

@@ -493,11 +493,18 @@ constexpr uint32_t LONG_STEPS = OAK_LONG_STEPS;
 #endif
 constexpr uint32_t PRIO_STILL = OAK_PRIO_STILL;
 // (REFILL_EVERY / REFILL_LANES, with their OAK_REFILL_* overrides, and QUEUE_HEADS / QUEUE_HEAD_STRIDE: record_walk.hpp)
-template <int BLK, int WPS>
+// KEEP_DUR = false, the LEAN instantiation (round 32): for a group none of whose batches takes durations back.  The engine keeps no
+// durations word (EngineR's KEEP_DUR): a batch's durations are read for the prep of a fresh playout only, the scratch durations
+// `sd` are neither written nor read when a playout is donated, parked or resumed, and no durations_out is written.  The schedule --
+// queue order, refill batching, migration, adopters, standstill skip, both carries -- is the same code.
+// PREP = false (lean launches with prep = 0, the headline's): the instantiation without the prep code -- randomize_hidden takes `%` by
+// run-time divisors, ~1,000 static VALU of cold code that such a launch never reaches (7,645 -> 6,290 instructions; 194.7 against
+// 195.8 wave cycles per turn-step, profiles/r32_lean_rollout.json).
+template <int BLK, int WPS, bool KEEP_DUR = true, bool PREP = true>
 __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, RoundArgs q_in) {
   extern __shared__ __align__(16) uint8_t smem[];
   lds_u32 *party = (lds_u32 *)smem;
-  using ER = EngineR<BLK, false>;
+  using ER = EngineR<BLK, false, false, KEEP_DUR>;
   Tables T = stage_default_tables((lds_u8 *)smem + ER::PARTY_WORDS * BLK * 4);
   lds_u32 *cold = (lds_u32 *)((lds_u8 *)smem + ER::PARTY_WORDS * BLK * 4 + TABLE_LDS_PAD);
   if (threadIdx.x == 0) {
@@ -670,15 +677,28 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
       if (load) {
         const BatchDesc *bd = find_batch(cold, idx);
         const uint32_t k = idx - bd->start; // playout k of its batch
-        const uint32_t *dsrc = from_scratch ? COLD_Q(sd, const uint32_t *) + 2 * (size_t)idx : (const uint32_t *)bd->durations + 2 * (size_t)k;
-        const uint32_t *psrc = (const uint32_t *)bd->prng + 2 * (size_t)k;
-        g.s0 = psrc[0];
-        g.s1 = psrc[1];
-        e.load_battle_global(from_scratch ? COLD_Q(sb, const uint8_t *) + (size_t)idx * 384 : bd->battles + (size_t)k * 384, dsrc[0], dsrc[1]);
-        if (IS_PREP && !from_scratch) { // mcts.h:254-259
-          const uint32_t hi = g.next32(), lo = g.next32();
-          e.rng = ((uint64_t)hi << 32) | lo;
-          e.randomize_hidden();
+        if constexpr (KEEP_DUR) {
+          const uint32_t *dsrc = from_scratch ? COLD_Q(sd, const uint32_t *) + 2 * (size_t)idx : (const uint32_t *)bd->durations + 2 * (size_t)k;
+          const uint32_t *psrc = (const uint32_t *)bd->prng + 2 * (size_t)k;
+          g.s0 = psrc[0];
+          g.s1 = psrc[1];
+          e.load_battle_global(from_scratch ? COLD_Q(sb, const uint8_t *) + (size_t)idx * 384 : bd->battles + (size_t)k * 384, dsrc[0], dsrc[1]);
+          if (IS_PREP && !from_scratch) { // mcts.h:254-259
+            const uint32_t hi = g.next32(), lo = g.next32();
+            e.rng = ((uint64_t)hi << 32) | lo;
+            e.randomize_hidden();
+          }
+        } else {
+          const uint32_t *psrc = (const uint32_t *)bd->prng + 2 * (size_t)k;
+          g.s0 = psrc[0];
+          g.s1 = psrc[1];
+          e.load_battle_global(from_scratch ? COLD_Q(sb, const uint8_t *) + (size_t)idx * 384 : bd->battles + (size_t)k * 384);
+          if (PREP && IS_PREP && !from_scratch) { // the batch's durations serve the prep of a fresh playout and nothing after it
+            const uint32_t *dsrc = (const uint32_t *)bd->durations + 2 * (size_t)k;
+            const uint32_t hi = g.next32(), lo = g.next32();
+            e.rng = ((uint64_t)hi << 32) | lo;
+            e.randomize_hidden(dsrc[0], dsrc[1]);
+          }
         }
         result = from_scratch ? COLD_Q(sres, const uint8_t *)[idx] : bd->results_in[k];
         steps = from_scratch ? bd->steps_out[k] : 0;
@@ -803,7 +823,7 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
       // the image is written from COPIES of the sides by player: normalising `e` in place (lane-masked) made the whole engine state a
       // value that differs between the two ways out of this branch, and the wave copied it to a second register set and back in
       // every iteration (round 18); the engine's own frame stays where the turn left it -- a parked or finished lane's is dead
-      SideR P1, P2;
+      typename ER::SideR P1, P2;
       sides_by_player(ER::absp(e.S) != 0, e.S, e.F, P1, P2);
       const BatchDesc *bd = find_batch(cold, idx);
       const uint32_t k = idx - bd->start;
@@ -814,10 +834,12 @@ __global__ __launch_bounds__(BLK, WPS) void k_rollout_queue(GroupArgs g_in, Roun
       uint32_t *pdst = (uint32_t *)bd->prng + 2 * (size_t)k;
       pdst[0] = g.s0;
       pdst[1] = g.s1;
-      uint32_t *ddst = fin ? (bd->durations_out ? (uint32_t *)bd->durations_out + 2 * (size_t)k : nullptr) : COLD_Q(sd, uint32_t *) + 2 * (size_t)idx;
-      if (ddst) {
-        ddst[0] = P1.dur;
-        ddst[1] = P2.dur;
+      if constexpr (KEEP_DUR) {
+        uint32_t *ddst = fin ? (bd->durations_out ? (uint32_t *)bd->durations_out + 2 * (size_t)k : nullptr) : COLD_Q(sd, uint32_t *) + 2 * (size_t)idx;
+        if (ddst) {
+          ddst[0] = P1.dur;
+          ddst[1] = P2.dur;
+        }
       }
       uint8_t *bdst = fin ? (bd->battles_out ? bd->battles_out + (size_t)k * 384 : nullptr) : COLD_Q(sb, uint8_t *) + (size_t)idx * 384;
       if (bdst) e.store_battle_global(bdst, P1, P2);
@@ -919,14 +941,19 @@ constexpr int CTL_STRIDE = 64; // words between two counters
 // image through store_battle_global / load_battle_global, whose stores each wait for a load of the immutable fields behind the
 // previous store -- stores count in vmcnt on gfx950 -- ~37 us of wave time per carried playout: 256 roots in slices of 64 ran at
 // 5.2 G turn-steps/s against 9.4 G without slices.)  The immutable party data is the ROOT's (`gin`), shared by the root's playouts.
+// KEEP_DUR = false (round 32): the step returns aggregates only, so the engine keeps no durations word -- a fresh playout's serve its
+// prep and nothing after, a carried playout's serve nothing.  The record stays CARRY_VEC = 18 vectors: the sides' 2 x 17 dwords packed
+// at 0 .. 33, dwords 34 and 35 are padding and the scalars behind them keep their places (a pad dword behind EACH side's set cost the
+// kernel 16 bytes of scratch).  Records of the two instantiations differ: a handle runs ONE of them for its whole life
+// (oakgpu_root_steps_create).
 constexpr int CARRY_VEC = 18;
 constexpr int ROOT_STEP_COLD_BYTES = ((sizeof(RootStepArgs) + 15) & ~15) + ROOT_SHARDS * 4;
 constexpr int ROOT_STEP_LDS_BYTES = 24 * 64 * 4 + TABLE_LDS_PAD + ROOT_STEP_COLD_BYTES;
-template <int WPS>
+template <int WPS, bool KEEP_DUR = true>
 __global__ __launch_bounds__(64, WPS) void k_root_step(RootStepArgs a_in) {
   extern __shared__ __align__(16) uint8_t smem[];
   lds_u32 *party = (lds_u32 *)smem;
-  using ER = EngineR<64, false>;
+  using ER = EngineR<64, false, false, KEEP_DUR>;
   Tables T = stage_default_tables((lds_u8 *)smem + ER::PARTY_WORDS * 64 * 4);
   // the cold arguments are parked in LDS, like k_rollout_queue's: as kernel arguments they would hold ~34 SGPRs across the turn loop
   lds_u32 *cold = (lds_u32 *)((lds_u8 *)smem + ER::PARTY_WORDS * 64 * 4 + TABLE_LDS_PAD);
@@ -991,12 +1018,21 @@ __global__ __launch_bounds__(64, WPS) void k_root_step(RootStepArgs a_in) {
         // (component i of the record by CONSTANT index: no pointer into the register array, which would put it in scratch)
         auto w = [&](int i) -> uint32_t { const uint4 &q = v[i >> 2]; return (i & 3) == 0 ? q.x : (i & 3) == 1 ? q.y : (i & 3) == 2 ? q.z : q.w; };
         int o = 0;
+        if constexpr (KEEP_DUR) {
 #define X(f) e.S.f = w(o++);
-        OAK_FOR_SIDE_FIELDS(X)
+          OAK_FOR_SIDE_FIELDS(X)
 #undef X
 #define X(f) e.F.f = w(o++);
-        OAK_FOR_SIDE_FIELDS(X)
+          OAK_FOR_SIDE_FIELDS(X)
 #undef X
+        } else {
+#define X(f) e.S.f = w(o++);
+          OAK_FOR_SIDE_FIELDS_LEAN(X)
+#undef X
+#define X(f) e.F.f = w(o++);
+          OAK_FOR_SIDE_FIELDS_LEAN(X)
+#undef X
+        }
         e.rng = (uint64_t)w(36) | ((uint64_t)w(37) << 32);
         e.turn = w(38) & 0xFFFF; e.last_damage = w(38) >> 16; e.lm = w(39);
 #pragma unroll
@@ -1014,10 +1050,17 @@ __global__ __launch_bounds__(64, WPS) void k_root_step(RootStepArgs a_in) {
         ps[0] = lane.s0; ps[1] = lane.s1;
         g.s0 = hi; g.s1 = (hi | lo) ? lo : 1u;
         const uint32_t *dsrc = (const uint32_t *)RS_PTR(root_durations, const uint8_t *) + 2 * (size_t)root;
-        e.load_battle_global(RS_PTR(root_battles, const uint8_t *) + (size_t)root * 384, dsrc[0], dsrc[1]);
-        const uint32_t bh = g.next32(), bl = g.next32();
-        e.rng = ((uint64_t)bh << 32) | bl;
-        e.randomize_hidden();
+        if constexpr (KEEP_DUR) {
+          e.load_battle_global(RS_PTR(root_battles, const uint8_t *) + (size_t)root * 384, dsrc[0], dsrc[1]);
+          const uint32_t bh = g.next32(), bl = g.next32();
+          e.rng = ((uint64_t)bh << 32) | bl;
+          e.randomize_hidden();
+        } else { // the root's durations serve the prep and are dropped
+          e.load_battle_global(RS_PTR(root_battles, const uint8_t *) + (size_t)root * 384);
+          const uint32_t bh = g.next32(), bl = g.next32();
+          e.rng = ((uint64_t)bh << 32) | bl;
+          e.randomize_hidden(dsrc[0], dsrc[1]);
+        }
         result = RS_PTR(root_results, const uint8_t *)[root];
         steps = 0;
       }
@@ -1052,12 +1095,22 @@ __global__ __launch_bounds__(64, WPS) void k_root_step(RootStepArgs a_in) {
       } else if (slot < seg) {
         uint32_t w[CARRY_VEC * 4];
         int o = 0;
+        if constexpr (KEEP_DUR) {
 #define X(f) w[o++] = e.S.f;
-        OAK_FOR_SIDE_FIELDS(X)
+          OAK_FOR_SIDE_FIELDS(X)
 #undef X
 #define X(f) w[o++] = e.F.f;
-        OAK_FOR_SIDE_FIELDS(X)
+          OAK_FOR_SIDE_FIELDS(X)
 #undef X
+        } else {
+#define X(f) w[o++] = e.S.f;
+          OAK_FOR_SIDE_FIELDS_LEAN(X)
+#undef X
+#define X(f) w[o++] = e.F.f;
+          OAK_FOR_SIDE_FIELDS_LEAN(X)
+#undef X
+          w[34] = w[35] = 0;
+        }
         w[36] = (uint32_t)e.rng; w[37] = (uint32_t)(e.rng >> 32); w[38] = e.turn | (e.last_damage << 16); w[39] = e.lm;
 #pragma unroll
         for (int q = 0; q < 24; ++q) w[40 + q] = e.m[q * 64];
@@ -1595,6 +1648,8 @@ struct oakgpu_ctx {
   int standstill_skip;    // 1 (default): the queue kernel takes a PROVEN inert standstill to its last turn-step in one go (exact); 0: plays every turn
   int move_carry;         // 0..64 (oakgpu_set_move_carry): the queue kernel's move carry, 0 = a turn's two actions in one wave iteration
   int move_carry_dry;     // 0..64 (oakgpu_set_move_carry_dry): a dry bulk wave carries while at least this many lanes play, 0 = never
+  int lean_rollout;       // 1 (default, oakgpu_set_lean_rollout): a group launch none of whose batches takes durations back runs the queue kernel that keeps none
+  int last_launch_lean;   // the last group launch ran that kernel (oakgpu_last_launch_lean)
   uint32_t *d_order;      // total entries
   size_t order_n;
   uint32_t order_pair = 0;      // k_queue_order's two counters: control words 32-33 and 34-35 in turn (each launch clears the next one's)
@@ -1701,6 +1756,8 @@ static int set_lds_limits() {
   HIPCHK(hipFuncSetAttribute((const void *)oak::k_rollout_staged, hipFuncAttributeMaxDynamicSharedMemorySize, oak::STAGED_LDS_BYTES));
   HIPCHK(hipFuncSetAttribute((const void *)oak::k_rollout_draws<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 24 * 64 * 4 + oak::TABLE_LDS_PAD));
   HIPCHK(hipFuncSetAttribute((const void *)oak::k_rollout_queue<64, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 24 * 64 * 4 + oak::TABLE_LDS_PAD + oak::COLD_LDS_BYTES));
+  HIPCHK(hipFuncSetAttribute((const void *)oak::k_rollout_queue<64, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 24 * 64 * 4 + oak::TABLE_LDS_PAD + oak::COLD_LDS_BYTES));
+  HIPCHK(hipFuncSetAttribute((const void *)oak::k_rollout_queue<64, 4, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 24 * 64 * 4 + oak::TABLE_LDS_PAD + oak::COLD_LDS_BYTES));
 #define STAGED_LIMIT(kernel)                                                                                                           \
   HIPCHK(hipFuncSetAttribute((const void *)oak::kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, oak::STAGED_LDS_BYTES)); \
   HIPCHK(hipFuncSetAttribute((const void *)oak::kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, oak::STAGED_LDS_BYTES))
@@ -1794,6 +1851,9 @@ int oakgpu_create(oakgpu_ctx **out, int device) {
   if (const char *env = getenv("OAKGPU_MOVE_CARRY")) c->move_carry = atoi(env) < 0 ? 0 : atoi(env) > 64 ? 64 : atoi(env);
   c->move_carry_dry = OAKGPU_MOVE_CARRY_DRY_DEFAULT;
   if (const char *env = getenv("OAKGPU_MOVE_CARRY_DRY")) c->move_carry_dry = atoi(env) < 0 ? 0 : atoi(env) > 64 ? 64 : atoi(env);
+  c->lean_rollout = OAKGPU_LEAN_ROLLOUT_DEFAULT;
+  if (const char *env = getenv("OAKGPU_LEAN_ROLLOUT")) c->lean_rollout = atoi(env) != 0;
+  c->last_launch_lean = 0;
   c->migrate = 1;
   c->migrate_steps = 300;
   c->migrate_adopters = 0;
@@ -1912,6 +1972,14 @@ int oakgpu_set_move_carry_dry(oakgpu_ctx *c, int below) {
   c->move_carry_dry = below;
   return 0;
 }
+
+int oakgpu_set_lean_rollout(oakgpu_ctx *c, int on) {
+  if (!c) return bad("null ctx");
+  c->lean_rollout = on != 0;
+  return 0;
+}
+
+int oakgpu_last_launch_lean(oakgpu_ctx *c) { return c ? c->last_launch_lean : 0; }
 
 int oakgpu_set_search_party_table(oakgpu_ctx *c, int on) {
   if (!c) return bad("null ctx");
@@ -2091,6 +2159,10 @@ static int launch_group(oakgpu_ctx *c, const oak::BatchDesc *descs, uint32_t cou
   lists[1] = lists[0] ? lists[0] + c->scratch_n : nullptr;
   uint8_t *sres = lists[1] ? (uint8_t *)(lists[1] + c->scratch_n) : nullptr;
   const oak::GroupArgs g{dt, count, total, max_steps, prep};
+  // no batch takes durations back: the kernel that keeps none (any prep, any battles_out), in every round of the launch
+  bool lean = c->lean_rollout != 0;
+  for (uint32_t i = 0; i < count; ++i) lean = lean && !descs[i].durations_out;
+  c->last_launch_lean = lean;
   const uint32_t *order = nullptr;
   if (c->queue_order && max_steps > 250 && total >= 8192) { // (a few thousand playouts have no queue to speak of: they all start at once)
     if (int r = launch_queue_order(c, g)) return r;
@@ -2125,7 +2197,9 @@ static int launch_group(oakgpu_ctx *c, const oak::BatchDesc *descs, uint32_t cou
     q.move_carry_dry = c->move_carry_dry > 0 ? std::max((uint32_t)c->move_carry_dry, q.suspend_below) : 0u; // (a wave that could suspend does not carry)
     q.queue = c->d_heads + (size_t)r * oak::QUEUE_HEADS * oak::QUEUE_HEAD_STRIDE;
     q.lanes = (tail_pack && r > 0) ? (uint32_t)c->tail_lanes : (r == 0 ? spread : 0u);
-    hipLaunchKernelGGL((oak::k_rollout_queue<64, 4>), dim3(waves), dim3(64), lq, c->stream, g, q);
+    if (lean && !prep) hipLaunchKernelGGL((oak::k_rollout_queue<64, 4, false, false>), dim3(waves), dim3(64), lq, c->stream, g, q); // (no prep code either)
+    else if (lean) hipLaunchKernelGGL((oak::k_rollout_queue<64, 4, false>), dim3(waves), dim3(64), lq, c->stream, g, q);
+    else hipLaunchKernelGGL((oak::k_rollout_queue<64, 4>), dim3(waves), dim3(64), lq, c->stream, g, q);
     waves = tail_pack ? (uint32_t)(c->tail_waves > 0 ? c->tail_waves : c->n_cu) : (waves + c->round_shrink - 1) / c->round_shrink;
     if (waves < 1) waves = 1;
   }
@@ -2229,6 +2303,7 @@ struct oakgpu_root_steps {
   uint32_t acc_stride;
   uint32_t *ctl;       // counters on 256-byte lines of their own: lines [0, 8) / [8, 16) the two lists' per-shard counts, [16, 24) the queue heads, 24 the sticky error word
   int cur;             // the list the NEXT launch reads
+  bool lean;           // the context's oakgpu_set_lean_rollout when the handle was made: k_root_step<4, false>, for the handle's whole life (the carry records are the instantiation's own)
 };
 
 int oakgpu_root_steps_create(oakgpu_ctx *c, uint32_t n_roots, uint32_t reps, uint32_t slice, uint32_t max_steps, oakgpu_root_steps **out) {
@@ -2239,6 +2314,7 @@ int oakgpu_root_steps_create(oakgpu_ctx *c, uint32_t n_roots, uint32_t reps, uin
   HIPCHK(hipSetDevice(c->device));
   oakgpu_root_steps *rs = new oakgpu_root_steps{};
   rs->ctx = c; rs->n_roots = n_roots; rs->reps = reps; rs->slice = slice; rs->max_steps = max_steps;
+  rs->lean = c->lean_rollout != 0;
   // every playout in flight is in at most one list: a step adds n_roots * reps and a playout lives ceil(max_steps / slice) launches
   const uint64_t lives = slice ? (max_steps + slice - 1) / slice : 1;
   const uint64_t worst = (uint64_t)n_roots * reps * (lives > 1 ? lives - 1 : 0);
@@ -2334,7 +2410,8 @@ int oakgpu_root_steps_launch_dev(oakgpu_root_steps *rs, const uint8_t *root_batt
   const uint64_t upper = (uint64_t)a.n_fresh + rs->cap;
   const uint32_t resident = (uint32_t)c->n_cu * 4u * 4u;
   const uint32_t waves = (uint32_t)std::min<uint64_t>(resident, (upper + 63) / 64);
-  hipLaunchKernelGGL(oak::k_root_step<4>, dim3(waves), dim3(64), oak::ROOT_STEP_LDS_BYTES, c->stream, a);
+  if (rs->lean) hipLaunchKernelGGL((oak::k_root_step<4, false>), dim3(waves), dim3(64), oak::ROOT_STEP_LDS_BYTES, c->stream, a);
+  else hipLaunchKernelGGL((oak::k_root_step<4>), dim3(waves), dim3(64), oak::ROOT_STEP_LDS_BYTES, c->stream, a);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(oak::k_root_step_report, dim3((rs->n_roots + 255) / 256), dim3(256), 0, c->stream, rs->acc, rs->acc_stride, rs->n_roots, cnt_out, errw,
                      a.seg, report);

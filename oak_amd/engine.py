@@ -112,6 +112,15 @@ class Context:
         0 = a dry wave never carries, at most 64); results never change."""
         _lib.check(self.lib.oakgpu_set_move_carry_dry(self.handle, int(below)))
 
+    def set_lean_rollout(self, on=True):
+        """A group launch none of whose batches takes durations back runs the queue kernel that keeps none (oakgpu_set_lean_rollout;
+        default on); results never change."""
+        _lib.check(self.lib.oakgpu_set_lean_rollout(self.handle, 1 if on else 0))
+
+    def last_launch_lean(self):
+        """Whether this context's last group launch ran the kernel that keeps no durations (oakgpu_last_launch_lean)."""
+        return bool(self.lib.oakgpu_last_launch_lean(self.handle))
+
     def set_standstill_skip(self, on=True):
         """The queue kernel's exact fast-forward of proven inert standstills (oakgpu_set_standstill_skip); results never change."""
         _lib.check(self.lib.oakgpu_set_standstill_skip(self.handle, 1 if on else 0))
@@ -138,7 +147,9 @@ class Context:
             self._pools = True
 
     # -- host-array API ------------------------------------------------------------------
-    def rollout(self, battles, durations, results, prng, max_steps=1000, prep=False, return_state=False):
+    def rollout(self, battles, durations, results, prng, max_steps=1000, prep=False, return_state=False, return_durations=True):
+        """return_state: also the final battles and durations; with return_durations=False the battles alone (a launch that takes no
+        durations back may run the kernel that keeps none: set_lean_rollout)."""
         battles = _u8(battles)
         n = battles.shape[0]
         durations = _u8(durations, (n, 8))
@@ -148,17 +159,21 @@ class Context:
         steps = np.zeros(n, dtype=np.uint32)
         values = np.zeros(n, dtype=np.float32)
         bo = np.zeros((n, 384), dtype=np.uint8) if return_state else None
-        do = np.zeros((n, 8), dtype=np.uint8) if return_state else None
+        do = np.zeros((n, 8), dtype=np.uint8) if return_state and return_durations else None
         _lib.check(self.lib.oakgpu_rollout(self.handle, _p(battles), _p(durations), _p(results), _p(prng), n,
                                            max_steps, 1 if prep else 0, _p(out), _p(steps), _p(values), _p(bo), _p(do)))
         res = dict(results=out, steps=steps, values=values, prng=prng)
         if return_state:
-            res.update(battles=bo, durations=do)
+            res.update(battles=bo)
+            if return_durations:
+                res.update(durations=do)
         return res
 
-    def rollout_group(self, batches, max_steps=1000, prep=False, return_state=False):
+    def rollout_group(self, batches, max_steps=1000, prep=False, return_state=False, return_durations=True):
         """Several independent batches [(battles, durations, results, prng), ...] drained by ONE launch
-        (oakgpu_rollout_group); returns one result dict per batch, identical to separate rollout() calls."""
+        (oakgpu_rollout_group); returns one result dict per batch, identical to separate rollout() calls.  return_durations: True,
+        False, or one flag per batch (return_state without it: the final battles alone)."""
+        flags = [bool(return_durations)] * len(batches) if isinstance(return_durations, (bool, int)) else [bool(f) for f in return_durations]
         descs = (_lib.RolloutBatch * len(batches))()
         outs, keep = [], []
         for k, (battles, durations, results, prng) in enumerate(batches):
@@ -168,7 +183,9 @@ class Context:
             res = dict(results=np.zeros(n, dtype=np.uint8), steps=np.zeros(n, dtype=np.uint32),
                        values=np.zeros(n, dtype=np.float32), prng=prng)
             if return_state:
-                res.update(battles=np.zeros((n, 384), dtype=np.uint8), durations=np.zeros((n, 8), dtype=np.uint8))
+                res.update(battles=np.zeros((n, 384), dtype=np.uint8))
+                if flags[k]:
+                    res.update(durations=np.zeros((n, 8), dtype=np.uint8))
             keep.append((battles, durations, results))
             a = lambda x: None if x is None or x.size == 0 else x.ctypes.data
             descs[k] = _lib.RolloutBatch(a(battles), a(durations), a(results), a(prng), n, a(res["results"]), a(res["steps"]),
