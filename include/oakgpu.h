@@ -62,6 +62,27 @@ int oakgpu_set_regroup(oakgpu_ctx *ctx, int rounds, int suspend_below, int shrin
  * playouts that run into the step cap; a wave that holds one of them alone advances it no faster than a wave that holds
  * a few, and hundreds of such waves slow each other down.  Results never depend on it. */
 int oakgpu_set_tail_pack(oakgpu_ctx *ctx, int below, int waves, int lanes);
+/* The yielding schedule: the tail pack for a context whose saturating group launches alternate with another context's on the same
+ * device.  The launch runs R = `waves` (0 = one per compute unit) waves FEWER than the device holds; when its queue is dry a wave with
+ * fewer than `below` (1..64) playouts still running parks them and leaves, so its slot goes to the other context's pending launch; ONE
+ * follow-up dispatch of at most R waves finishes the parked playouts, `lanes` per wave at a time (0 = 64), in the slots the other
+ * context's launch leaves free.  Migration is off in it and no wave waits for another: correct whatever part of a grid is resident.
+ * mode 0: off.  mode 1: automatic -- a launch that saturates the device with max_steps >= 500, when another live context of the device
+ * has issued such a launch since this context's previous one (a host-side registry: no device query, no synchronisation); a context on
+ * its own keeps the single dispatch with migration.  mode 2: every group launch of two waves or more (tests: a small launch parks with
+ * a quarter of its waves as R).  Results never depend on it.  Also OAKGPU_YIELD_SCHEDULE / _BELOW / _WAVES / _LANES at context
+ * creation.  Defaults below.
+ * oakgpu_set_yield_saturation: automatic mode counts a launch of `waves` waves or more as saturating (0 = the device's resident waves;
+ * tests lower it).  oakgpu_last_launch_yield: 1 if the context's last group launch took the schedule.  oakgpu_last_launch_parked
+ * (synchronises the stream): the playouts the last group launch parked for its follow-up dispatch, 0 for a single dispatch. */
+#define OAKGPU_YIELD_SCHEDULE_DEFAULT 1
+#define OAKGPU_YIELD_BELOW_DEFAULT 12
+#define OAKGPU_YIELD_WAVES_DEFAULT 256
+#define OAKGPU_YIELD_LANES_DEFAULT 0
+int oakgpu_set_yield_schedule(oakgpu_ctx *ctx, int mode, int below, int waves, int lanes);
+int oakgpu_set_yield_saturation(oakgpu_ctx *ctx, int waves);
+int oakgpu_last_launch_yield(oakgpu_ctx *ctx);
+int oakgpu_last_launch_parked(oakgpu_ctx *ctx, uint32_t *parked);
 /* Queue order of a launch of >= 8,192 playouts (default on): playouts with a Ghost-type Pokemon or a Ditto on either team are
  * handed out first.  They hold practically all of the playouts that run into the step cap (Normal-type Rage / Struggle locks
  * against a Ghost), and the launch ends with its longest playout: started early, the 1,000-step chains are mostly done when

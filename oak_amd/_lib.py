@@ -8,7 +8,7 @@ LIB_PATH = os.environ.get("OAKGPU_LIB") or os.path.join(_HERE, "liboakgpu.so")  
 
 # every symbol include/oakgpu.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
-    "oakgpu_create", "oakgpu_destroy", "oakgpu_last_error", "oakgpu_set_stream", "oakgpu_get_stream", "oakgpu_synchronize", "oakgpu_set_kernel_timing", "oakgpu_get_leaf_kernel_ms", "oakgpu_set_playouts_per_lane", "oakgpu_set_regroup", "oakgpu_set_tail_pack", "oakgpu_set_queue_order", "oakgpu_queue_order", "oakgpu_set_spread", "oakgpu_set_migration", "oakgpu_set_migration_window", "oakgpu_set_standstill_skip", "oakgpu_set_move_carry", "oakgpu_set_move_carry_dry", "oakgpu_set_lean_rollout", "oakgpu_last_launch_lean", "oakgpu_get_queue_counters",
+    "oakgpu_create", "oakgpu_destroy", "oakgpu_last_error", "oakgpu_set_stream", "oakgpu_get_stream", "oakgpu_synchronize", "oakgpu_set_kernel_timing", "oakgpu_get_leaf_kernel_ms", "oakgpu_set_playouts_per_lane", "oakgpu_set_regroup", "oakgpu_set_tail_pack", "oakgpu_set_yield_schedule", "oakgpu_set_yield_saturation", "oakgpu_last_launch_yield", "oakgpu_last_launch_parked", "oakgpu_set_queue_order", "oakgpu_queue_order", "oakgpu_set_spread", "oakgpu_set_migration", "oakgpu_set_migration_window", "oakgpu_set_standstill_skip", "oakgpu_set_move_carry", "oakgpu_set_move_carry_dry", "oakgpu_set_lean_rollout", "oakgpu_last_launch_lean", "oakgpu_get_queue_counters",
     "oakgpu_device_count", "oakgpu_rollout_dev", "oakgpu_rollout", "oakgpu_rollout_group_dev", "oakgpu_rollout_group",
     "oakgpu_mt19937_fill", "oakgpu_rollout_draws_dev", "oakgpu_rollout_shared_device", "oakgpu_update_dev", "oakgpu_update",
     "oakgpu_choices_dev", "oakgpu_choices", "oakgpu_init_battles_dev", "oakgpu_init_battles",
@@ -269,6 +269,10 @@ def load():
     lib.oakgpu_set_playouts_per_lane.argtypes = [vp, i32]
     lib.oakgpu_set_regroup.argtypes = [vp, i32, i32, i32]
     lib.oakgpu_set_tail_pack.argtypes = [vp, i32, i32, i32]
+    lib.oakgpu_set_yield_schedule.argtypes = [vp, i32, i32, i32, i32]
+    lib.oakgpu_set_yield_saturation.argtypes = [vp, i32]
+    lib.oakgpu_last_launch_yield.argtypes = [vp]
+    lib.oakgpu_last_launch_parked.argtypes = [vp, C.POINTER(u32)]
     lib.oakgpu_set_queue_order.argtypes = [vp, i32]
     lib.oakgpu_queue_order.argtypes = [vp, C.POINTER(RolloutBatch), u32, vp, C.POINTER(u32)]
     lib.oakgpu_set_spread.argtypes = [vp, i32]

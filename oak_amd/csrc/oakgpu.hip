@@ -1650,6 +1650,18 @@ struct oakgpu_ctx {
   int move_carry_dry;     // 0..64 (oakgpu_set_move_carry_dry): a dry bulk wave carries while at least this many lanes play, 0 = never
   int lean_rollout;       // 1 (default, oakgpu_set_lean_rollout): a group launch none of whose batches takes durations back runs the queue kernel that keeps none
   int last_launch_lean;   // the last group launch ran that kernel (oakgpu_last_launch_lean)
+  // The yielding schedule (oakgpu_set_yield_schedule): a context that alternates saturating group launches with
+  // another context of its device launches R waves FEWER than the device holds, its dry waves park their last lanes and leave, and ONE
+  // follow-up dispatch of at most R waves finishes the parked playouts in the slots the other context's launch leaves free.  Migration
+  // is off in it: no wave ever waits for another, so it is correct whatever part of a grid is resident.
+  int yield_mode;         // 0 off, 1 automatic (below), 2 every group launch of two waves or more (tests reach it at small sizes)
+  int yield_below;        //   a dry wave with fewer playing lanes than this parks them
+  int yield_waves;        //   R (0 = one per CU)
+  int yield_lanes;        //   lanes per follow-up wave that take playouts (0 = all 64)
+  int yield_min_waves;    //   automatic: a launch of this many waves counts as saturating (0 = the device's resident waves; tests lower it)
+  uint64_t sat_seq = 0;   //   the registry's sequence number of this context's last saturating group launch (0: none yet)
+  int last_launch_yield;  // the last group launch took the yielding schedule (oakgpu_last_launch_yield)
+  int last_launch_rounds; // dispatches of the last group launch: with more than one, control word 1 is its parked count
   uint32_t *d_order;      // total entries
   size_t order_n;
   uint32_t order_pair = 0;      // k_queue_order's two counters: control words 32-33 and 34-35 in turn (each launch clears the next one's)
@@ -1672,6 +1684,26 @@ struct oakgpu_ctx {
   void *attachment = nullptr;              // oakgpu_internal.h: the tree search's cached batch slots
   void (*attachment_dtor)(void *) = nullptr;
 };
+
+// Saturating group launches, per process: which context of a device issued one last (host side only -- no device query, no
+// synchronisation).  Automatic yielding applies to a context whose previous saturating launch has been followed by another live
+// context's on the same device: the two alternate, so each one's tail runs beside the other one's bulk phase.
+static std::mutex g_yield_mu;
+static std::vector<oakgpu_ctx *> g_live_ctx;
+static uint64_t g_sat_seq = 0;
+static void yield_registry_add(oakgpu_ctx *c) { std::lock_guard<std::mutex> lock(g_yield_mu); g_live_ctx.push_back(c); }
+static void yield_registry_remove(oakgpu_ctx *c) {
+  std::lock_guard<std::mutex> lock(g_yield_mu);
+  for (size_t i = 0; i < g_live_ctx.size(); ++i) if (g_live_ctx[i] == c) { g_live_ctx[i] = g_live_ctx.back(); g_live_ctx.pop_back(); break; }
+}
+// notes a saturating group launch of `c`; true when another live context of its device has issued one since c's previous one
+static bool yield_registry_launch(oakgpu_ctx *c) {
+  std::lock_guard<std::mutex> lock(g_yield_mu);
+  bool other = false;
+  if (c->sat_seq) for (const oakgpu_ctx *o : g_live_ctx) other |= o != c && o->device == c->device && o->sat_seq > c->sat_seq;
+  c->sat_seq = ++g_sat_seq;
+  return other;
+}
 
 static thread_local std::string g_err;
 static int fail(hipError_t e, const char *what) {
@@ -1854,6 +1886,16 @@ int oakgpu_create(oakgpu_ctx **out, int device) {
   c->lean_rollout = OAKGPU_LEAN_ROLLOUT_DEFAULT;
   if (const char *env = getenv("OAKGPU_LEAN_ROLLOUT")) c->lean_rollout = atoi(env) != 0;
   c->last_launch_lean = 0;
+  c->yield_mode = OAKGPU_YIELD_SCHEDULE_DEFAULT;
+  c->yield_below = OAKGPU_YIELD_BELOW_DEFAULT;
+  c->yield_waves = OAKGPU_YIELD_WAVES_DEFAULT;
+  c->yield_lanes = OAKGPU_YIELD_LANES_DEFAULT;
+  c->yield_min_waves = 0;
+  c->last_launch_yield = c->last_launch_rounds = 0;
+  if (const char *env = getenv("OAKGPU_YIELD_SCHEDULE")) c->yield_mode = atoi(env) < 0 ? 0 : atoi(env) > 2 ? 2 : atoi(env);
+  if (const char *env = getenv("OAKGPU_YIELD_BELOW")) c->yield_below = atoi(env) < 1 ? 1 : atoi(env) > 64 ? 64 : atoi(env);
+  if (const char *env = getenv("OAKGPU_YIELD_WAVES")) c->yield_waves = atoi(env) < 0 ? 0 : atoi(env);
+  if (const char *env = getenv("OAKGPU_YIELD_LANES")) c->yield_lanes = atoi(env) < 0 ? 0 : atoi(env) > 64 ? 64 : atoi(env);
   c->migrate = 1;
   c->migrate_steps = 300;
   c->migrate_adopters = 0;
@@ -1872,12 +1914,14 @@ int oakgpu_create(oakgpu_ctx **out, int device) {
   if (const char *env = getenv("OAKGPU_ROUND_SHRINK")) c->round_shrink = atoi(env) < 1 ? 1 : atoi(env);
   hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e != hipSuccess) { delete c; return fail(e, "hipStreamCreate"); }
+  yield_registry_add(c);
   *out = c;
   return 0;
 }
 
 void oakgpu_destroy(oakgpu_ctx *c) {
   if (!c) return;
+  yield_registry_remove(c);
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   if (c->attachment && c->attachment_dtor) { c->attachment_dtor(c->attachment); c->attachment = nullptr; }
@@ -2009,6 +2053,33 @@ int oakgpu_set_tail_pack(oakgpu_ctx *c, int below, int waves, int lanes) {
   return 0;
 }
 
+int oakgpu_set_yield_schedule(oakgpu_ctx *c, int mode, int below, int waves, int lanes) {
+  if (!c || mode < 0 || mode > 2 || below < 1 || below > 64 || waves < 0 || lanes < 0 || lanes > 64) return bad("oakgpu_set_yield_schedule: bad argument");
+  c->yield_mode = mode;
+  c->yield_below = below;
+  c->yield_waves = waves;
+  c->yield_lanes = lanes;
+  return 0;
+}
+
+int oakgpu_set_yield_saturation(oakgpu_ctx *c, int waves) {
+  if (!c || waves < 0) return bad("oakgpu_set_yield_saturation: bad argument");
+  c->yield_min_waves = waves;
+  return 0;
+}
+
+int oakgpu_last_launch_yield(oakgpu_ctx *c) { return c ? c->last_launch_yield : 0; }
+
+int oakgpu_last_launch_parked(oakgpu_ctx *c, uint32_t *parked) { // diagnostic: synchronises the stream
+  if (!c || !parked) return bad("oakgpu_last_launch_parked: null argument");
+  *parked = 0;
+  if (!c->d_queue || c->last_launch_rounds < 2) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipMemcpyAsync(parked, c->d_queue + 1, 4, hipMemcpyDeviceToHost, c->stream)); // round 0's count_out
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 void *oakgpu_get_stream(oakgpu_ctx *c) { return c ? (void *)c->stream : nullptr; }
 
 int oakgpu_set_kernel_timing(oakgpu_ctx *c, int on) {
@@ -2117,8 +2188,23 @@ static int launch_group(oakgpu_ctx *c, const oak::BatchDesc *descs, uint32_t cou
   // (round 3, tools/small_launch_sweep.py ... spread: 65,536 playouts 8.5 -> 7.7 ms at 8 lanes per wave, 16,384 playouts 7.8 ->
   // 6.2 ms at 4, a rank's share of configs[3] 9.3 -> 8.3 ms at 16).  Automatic: as few lanes per wave as fill the resident
   // waves, at least 4.  Not for callers that keep several contexts busy (the other context needs the slots).
+  // the yielding schedule (oakgpu_set_yield_schedule): automatic for a saturating launch of full-length playouts when another context
+  // of the device has issued one since this context's previous one -- a context on its own keeps the single dispatch with migration
+  bool yield = false;
+  uint32_t yield_r = 0;
+  {
+    const bool ysat = max_steps >= 500 && (saturated || (c->yield_min_waves > 0 && waves >= (uint32_t)c->yield_min_waves));
+    const bool alternating = ysat && yield_registry_launch(c);
+    yield = waves >= 2 && (c->yield_mode == 2 || (c->yield_mode == 1 && alternating));
+    if (yield) { // R slots stay free for the other context's follow-up dispatch, and this launch's own takes at most R
+      yield_r = (uint32_t)(c->yield_waves > 0 ? c->yield_waves : c->n_cu);
+      if (yield_r * 2 > waves) yield_r = waves / 4 ? waves / 4 : 1; // (a small launch: a quarter of its waves)
+      waves -= yield_r;
+    }
+  }
+  c->last_launch_yield = yield;
   uint32_t spread = 0;
-  if (!saturated && c->spread_lanes != 0 && !c->concurrent_hint && max_steps > 64) {
+  if (!yield && !saturated && c->spread_lanes != 0 && !c->concurrent_hint && max_steps > 64) {
     const uint64_t slots = ((uint64_t)total + c->playouts_per_lane - 1) / c->playouts_per_lane; // lanes in flight
     uint32_t lanes = c->spread_lanes > 0 ? (uint32_t)c->spread_lanes : (uint32_t)((slots + resident - 1) / resident);
     if (lanes < 4) lanes = 4;
@@ -2131,7 +2217,9 @@ static int launch_group(oakgpu_ctx *c, const oak::BatchDesc *descs, uint32_t cou
   // regrouping rounds pay off while the launch leaves SIMDs idle in its tail; a launch that saturates the device
   // for most of its life (a group of batches) runs as a single dispatch (measured: DESIGN.md 3)
   // ... and so does a launch capped at a few steps (stepping a resident batch turn by turn): there is no tail to regroup
-  const bool tail_pack = saturated && c->tail_below > 0 && max_steps > 64;
+  const bool tail_pack = yield || (saturated && c->tail_below > 0 && max_steps > 64);
+  const int tail_below = yield ? c->yield_below : c->tail_below, tail_lanes = yield ? c->yield_lanes : c->tail_lanes;
+  const uint32_t tail_waves = yield ? yield_r : (uint32_t)(c->tail_waves > 0 ? c->tail_waves : c->n_cu);
   // (one per FOUR CUs since the stalemate chains are fast-forwarded instead of played: the adopters hold ~700 live long playouts per
   // 1.31 M instead of ~1,800, and every adopter is a wave that takes no bulk work once donations exist.  Measured on the driver
   // command, profiles/r13_drain.json: 16 / 32 / 64 / 96 / 128 adopters 8.42 / 8.89 / 9.00 / 8.84 / 8.90 G at the median of four runs)
@@ -2147,6 +2235,7 @@ static int launch_group(oakgpu_ctx *c, const oak::BatchDesc *descs, uint32_t cou
   // (the tree search keeps two batches in flight on two contexts and asks for the rounds -- oakgpu_ctx_set_concurrent_hint --:
   // behind a single 8 ms dispatch the other context's small per-level kernels queued up: 11 -> 69 ms of waiting per search)
   const int rounds = tail_pack ? 2 : migrate ? 1 : ((!c->rounds_auto || (c->concurrent_hint && !saturated && max_steps > 64)) && c->suspend_below > 0 && waves >= 8) ? c->rounds : 1;
+  c->last_launch_rounds = rounds;
   if ((rounds > 1 || migrate) && c->scratch_n < total) {
     if (c->d_scratch) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(c->d_scratch)); c->d_scratch = nullptr; }
     HIPCHK(hipMalloc((void **)&c->d_scratch, (size_t)total * (384 + 8 + 4 + 4) + (((size_t)total + 15) & ~(size_t)15)));
@@ -2193,14 +2282,14 @@ static int launch_group(oakgpu_ctx *c, const oak::BatchDesc *descs, uint32_t cou
     q.list_out = lists[r & 1];
     q.count_out = c->d_queue + 2 * r + 1;
     q.sb = sb; q.sd = sd; q.sres = sres;
-    q.suspend_below = r + 1 < rounds ? (uint32_t)(tail_pack ? c->tail_below : c->suspend_below) : 0u;
+    q.suspend_below = r + 1 < rounds ? (uint32_t)(tail_pack ? tail_below : c->suspend_below) : 0u;
     q.move_carry_dry = c->move_carry_dry > 0 ? std::max((uint32_t)c->move_carry_dry, q.suspend_below) : 0u; // (a wave that could suspend does not carry)
     q.queue = c->d_heads + (size_t)r * oak::QUEUE_HEADS * oak::QUEUE_HEAD_STRIDE;
-    q.lanes = (tail_pack && r > 0) ? (uint32_t)c->tail_lanes : (r == 0 ? spread : 0u);
+    q.lanes = (tail_pack && r > 0) ? (uint32_t)tail_lanes : (r == 0 ? spread : 0u);
     if (lean && !prep) hipLaunchKernelGGL((oak::k_rollout_queue<64, 4, false, false>), dim3(waves), dim3(64), lq, c->stream, g, q); // (no prep code either)
     else if (lean) hipLaunchKernelGGL((oak::k_rollout_queue<64, 4, false>), dim3(waves), dim3(64), lq, c->stream, g, q);
     else hipLaunchKernelGGL((oak::k_rollout_queue<64, 4>), dim3(waves), dim3(64), lq, c->stream, g, q);
-    waves = tail_pack ? (uint32_t)(c->tail_waves > 0 ? c->tail_waves : c->n_cu) : (waves + c->round_shrink - 1) / c->round_shrink;
+    waves = tail_pack ? tail_waves : (waves + c->round_shrink - 1) / c->round_shrink;
     if (waves < 1) waves = 1;
   }
   HIPCHK(hipGetLastError());

@@ -121,6 +121,25 @@ class Context:
         """Whether this context's last group launch ran the kernel that keeps no durations (oakgpu_last_launch_lean)."""
         return bool(self.lib.oakgpu_last_launch_lean(self.handle))
 
+    def set_yield_schedule(self, mode=0, below=12, waves=256, lanes=0):
+        """The yielding schedule of group launches that alternate with another context's (oakgpu_set_yield_schedule: mode 0 off,
+        1 automatic, 2 always); results never change."""
+        _lib.check(self.lib.oakgpu_set_yield_schedule(self.handle, int(mode), int(below), int(waves), int(lanes)))
+
+    def set_yield_saturation(self, waves=0):
+        """Automatic yielding counts a launch of `waves` waves or more as saturating (oakgpu_set_yield_saturation; 0 = the device's)."""
+        _lib.check(self.lib.oakgpu_set_yield_saturation(self.handle, int(waves)))
+
+    def last_launch_yield(self):
+        """Whether this context's last group launch took the yielding schedule (oakgpu_last_launch_yield)."""
+        return bool(self.lib.oakgpu_last_launch_yield(self.handle))
+
+    def last_launch_parked(self):
+        """Playouts the last group launch parked for its follow-up dispatch (oakgpu_last_launch_parked; synchronises the stream)."""
+        n = C.c_uint32(0)
+        _lib.check(self.lib.oakgpu_last_launch_parked(self.handle, C.byref(n)))
+        return n.value
+
     def set_standstill_skip(self, on=True):
         """The queue kernel's exact fast-forward of proven inert standstills (oakgpu_set_standstill_skip); results never change."""
         _lib.check(self.lib.oakgpu_set_standstill_skip(self.handle, 1 if on else 0))
