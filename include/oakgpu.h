@@ -757,6 +757,43 @@ int oakgpu_frames_encode(oakgpu_ctx *ctx, oakgpu_corpus *corpus, const uint32_t 
 int oakgpu_frames_sample(oakgpu_ctx *ctx, oakgpu_corpus *corpus, uint32_t n, uint64_t seed, uint32_t max_battle_length,
                          uint32_t min_iterations, uint32_t *picks_out, const oakgpu_encoded_frames *out, uint32_t *ok_rows);
 
+/* ---- A replay window: a corpus that starts empty and that self-play appends to on the device -- the moving window of the newest data
+ * that the reference's reinforcement loop keeps on disk (src/oak/common_args.py:83-131: --data-window, --min-files; src/oak/rl.py runs
+ * generate and battle.py on one directory).  The window holds the newest records, in arrival order, such that records <= max_records and
+ * bytes <= max_bytes; older ones leave first, whole records at a time.  A batch that exceeds the window on its own leaves its newest
+ * tail; a record larger than max_bytes leaves an empty window and counts as evicted.
+ *   THE CONTRACT.  After any sequence of appends, every corpus call above and below (info -- with stopped_at = the surviving bytes --,
+ * frame_bases, frames_sample(_dev) for any filter pair and seed, frames_encode(_dev), corpus_states, _inference, _loss_dev, _evaluate) returns
+ * on the window bit for bit what it returns on oakgpu_corpus_create over the concatenation of the surviving records' bytes in order, and
+ * oakgpu_corpus_records returns exactly that concatenation (so it is also how a window is saved as a `.battle.data` file).  Where the records
+ * sit inside the window is the library's own business (each at a 16-byte aligned offset of one of two buffers that change places).
+ *   append_dev: `stream` and `offsets` (n + 1, 8-byte aligned) are device arrays as oakgpu_forest_selfplay_records and
+ * oakgpu_forest_match_records leave them with to_device = 1: record i is bytes offsets[i] .. offsets[i+1].  A slice of zero bytes is a
+ * dropped game and is skipped (the offsets must lie inside `stream`: that is the caller's to keep, as for every device array).  Every other slice is checked on the device by the rules of oakgpu_frames_read: a slice whose length field
+ * is not the slice's length (or is below the fixed 391 bytes) is REJECTED -- not appended, counted; a record damaged inside its own length
+ * (truncated or malformed update, frame count that disagrees) is appended with its malformed flag set, as oakgpu_replay_index does.
+ *   append: host bytes; the record boundaries are found by oakgpu_replay_index's length walk, bytes behind a length that cannot be
+ * trusted are left out (as oakgpu_corpus_create leaves them out), and the same device path runs.
+ *   Both wait for the context's stream ONCE and read one summary of 40 bytes plus the batch's own frame counts and classes (3 bytes per
+ * slice): nothing is read in proportion to the window.  (A call that has to grow one of the window's buffers waits once more.)  After an
+ * append the sampler's lists are rebuilt on the device at the next oakgpu_frames_sample_dev of a filter pair: the valid-frame counts, the
+ * eligibility flags, a scan and a scatter in record order; the host reads the count E alone.
+ *   Refused before anything is launched, by a message that names the argument: max_records == 0 or max_bytes < 391 (window_check, host
+ * only); a corpus that oakgpu_corpus_create_window did not make; a corpus of another ctx; null or misaligned offsets.
+ *   window_stats: out = {records, bytes, appended, evicted, rejected, appends} -- the window now, then lifetime counts: records that joined,
+ * records that left (those of a batch that never fitted included), slices refused, calls.
+ *   records: the window's bytes into `out` (device memory when to_device, else host memory; the host form waits for the stream); *bytes
+ * receives their number, and `out` NULL asks for the number alone. */
+int oakgpu_corpus_window_check(uint32_t max_records, size_t max_bytes);
+int oakgpu_corpus_create_window(oakgpu_ctx *ctx, uint32_t max_records, size_t max_bytes, oakgpu_corpus **out);
+int oakgpu_corpus_append_dev(oakgpu_ctx *ctx, oakgpu_corpus *corpus, const uint8_t *stream, const uint64_t *offsets, uint32_t n);
+int oakgpu_corpus_append(oakgpu_ctx *ctx, oakgpu_corpus *corpus, const uint8_t *buffer, size_t size);
+int oakgpu_corpus_window_stats(const oakgpu_corpus *corpus, uint64_t out[6]);
+int oakgpu_corpus_records(oakgpu_ctx *ctx, oakgpu_corpus *corpus, uint8_t *out, size_t capacity, size_t *bytes, int to_device);
+/* Diagnostic (no GPU involved): the slice rule of append_dev on host arrays, the text the device pass compiles (oak_amd/csrc/record_scan.hpp).
+ * kinds[i]: 0 dropped, 1 record, 2 record with its malformed flag, 3 rejected; frames[i]: the header's frame count of a record, else 0. */
+int oakgpu_window_scan_host(const uint8_t *stream, const uint64_t *offsets, uint32_t n, uint8_t *kinds, uint16_t *frames);
+
 /* ---- A network evaluated on EVERY frame of a corpus: what pyoak.cpp_inference (cpp/src/pyoak.cc:331-392) returns for one record and
  * the terms battle.py's loss (src/oak/battle.py:203-262) would report, for all records at once.  Each record is walked ONCE (the walk of
  * a pick, with every frame written down) and the evaluator runs once per CHUNK: a range of consecutive whole records.

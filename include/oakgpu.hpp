@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <array>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -685,9 +686,49 @@ public:
     return total;
   }
 
-private:
+protected:
+  explicit FrameCorpus(oakgpu_ctx *ctx) : ctx_{ctx} {} // (ReplayWindow makes its own corpus)
   oakgpu_ctx *ctx_{};
   oakgpu_corpus *corpus_{};
+};
+
+// A corpus that starts empty and keeps the newest records appended to it (oakgpu_corpus_create_window: the contract is in oakgpu.h): every
+// FrameCorpus call on it returns what it returns on FrameCorpus{ctx, window.records()}.
+class ReplayWindow : public FrameCorpus {
+public:
+  struct Stats { uint64_t records, bytes, appended, evicted, rejected, appends; };
+  ReplayWindow(Context &ctx, uint32_t max_records, size_t max_bytes) : FrameCorpus{ctx.get()} {
+    check(oakgpu_corpus_create_window(ctx_, max_records, max_bytes, &corpus_));
+  }
+  // device arrays as oakgpu_forest_selfplay_records leaves them with to_device = 1: record i = bytes offsets[i] .. offsets[i+1]
+  Stats append_dev(const uint8_t *stream, const uint64_t *offsets, uint32_t n) {
+    check(oakgpu_corpus_append_dev(ctx_, corpus_, stream, offsets, n));
+    return stats();
+  }
+  // host bytes, cut into records by their length fields
+  Stats append(const std::vector<uint8_t> &bytes) {
+    check(oakgpu_corpus_append(ctx_, corpus_, bytes.data(), bytes.size()));
+    return stats();
+  }
+  Stats stats() const {
+    uint64_t v[6] = {};
+    check(oakgpu_corpus_window_stats(corpus_, v));
+    return Stats{v[0], v[1], v[2], v[3], v[4], v[5]};
+  }
+  // the surviving records back to back: a `.battle.data` file's bytes
+  std::vector<uint8_t> records() {
+    size_t size = 0;
+    check(oakgpu_corpus_records(ctx_, corpus_, nullptr, 0, &size, 0));
+    std::vector<uint8_t> out(size);
+    if (size) check(oakgpu_corpus_records(ctx_, corpus_, out.data(), out.size(), &size, 0));
+    return out;
+  }
+  void save(const std::string &path) {
+    const std::vector<uint8_t> data = records();
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f || (data.size() && fwrite(data.data(), 1, data.size(), f) != data.size())) { if (f) fclose(f); throw std::runtime_error{"oakgpu: cannot write " + path}; }
+    fclose(f);
+  }
 };
 
 // The optimiser step of a battle network on the device (oakgpu_trainer_*): parameters, gradients and Adam's state of one `.battle.net`, trained on

@@ -27,6 +27,8 @@ SYMBOLS = [
     "oakgpu_frames_encode", "oakgpu_frames_sample",
     "oakgpu_corpus_frame_bases", "oakgpu_corpus_chunks", "oakgpu_corpus_states_dev", "oakgpu_corpus_states", "oakgpu_corpus_inference_dev", "oakgpu_corpus_loss_dev",
     "oakgpu_corpus_inference", "oakgpu_corpus_evaluate",
+    "oakgpu_corpus_window_check", "oakgpu_corpus_create_window", "oakgpu_corpus_append_dev", "oakgpu_corpus_append", "oakgpu_corpus_window_stats",
+    "oakgpu_corpus_records", "oakgpu_window_scan_host",
     "oakgpu_party_table_create", "oakgpu_party_table_destroy", "oakgpu_party_table_fill_dev", "oakgpu_party_table_fill", "oakgpu_leaf_eval_table_dev",
     "oakgpu_leaf_eval_policy_table_dev", "oakgpu_party_table_last_misses", "oakgpu_party_table_rows", "oakgpu_party_table_width", "oakgpu_party_key", "oakgpu_party_variant",
     "oakgpu_set_search_party_table", "oakgpu_search_party_table_stats", "oakgpu_leaf_eval_table", "oakgpu_leaf_eval_policy_table",
@@ -338,6 +340,13 @@ def load():
     lib.oakgpu_corpus_destroy.argtypes = [vp]
     lib.oakgpu_corpus_destroy.restype = None
     lib.oakgpu_corpus_info.argtypes = [vp, C.POINTER(CorpusStats)]
+    lib.oakgpu_corpus_window_check.argtypes = [u32, C.c_size_t]
+    lib.oakgpu_corpus_create_window.argtypes = [vp, u32, C.c_size_t, C.POINTER(vp)]
+    lib.oakgpu_corpus_append_dev.argtypes = [vp, vp, vp, vp, u32]
+    lib.oakgpu_corpus_append.argtypes = [vp, vp, vp, C.c_size_t]
+    lib.oakgpu_corpus_window_stats.argtypes = [vp, C.POINTER(C.c_uint64 * 6)]
+    lib.oakgpu_corpus_records.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t), i32]
+    lib.oakgpu_window_scan_host.argtypes = [vp, vp, u32, vp, vp]
     lib.oakgpu_frames_encode_dev.argtypes = [vp, vp, vp, u32, C.POINTER(EncodedFrames)]
     lib.oakgpu_frames_sample_dev.argtypes = [vp, vp, u32, u64, u32, u32, vp, C.POINTER(EncodedFrames)]
     lib.oakgpu_encode_battles_dev.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]

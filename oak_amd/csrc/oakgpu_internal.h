@@ -110,4 +110,10 @@ struct oakgpu_corpus {
   // corpuseval.hip's workspace of a chunk of rows (freed through eval_free; the stream must be idle)
   void *eval = nullptr;
   void (*eval_free)(void *) = nullptr;
+  // replaywindow.hip's half of a window corpus (oakgpu_corpus_create_window), null for a corpus made from a buffer: on such a corpus the
+  // arrays above change with every append, and the sampler lists the eligible records on the device
+  void *window = nullptr;
+  void (*window_free)(void *) = nullptr;
 };
+// trainframes.hip: the sampling caches and the evaluation workspace of a corpus whose records have changed (the stream must be idle)
+void oakgpu_corpus_drop_caches(oakgpu_corpus *corpus);

@@ -26,6 +26,7 @@
 #include "../../include/oakgpu.h"
 #include "oakgpu_internal.h"
 #include "selfplay_pick.hpp"
+#include "record_scan.hpp"
 
 namespace {
 
@@ -67,28 +68,23 @@ bool set_cant_hit_ghosts(const uint8_t *set) {
 // the fixed part or past the buffer's end -- so nothing behind this point can be found.  OAKGPU_RECORD_MALFORMED: the record is
 // damaged inside its own length (an m or n nibble above 8, an update past the record's end, a frame count that disagrees with the
 // header); *total is still where the next record starts.
+// The rule itself is record_scan.hpp's, the text the replay window's device pass compiles too.
 int oakgpu_record_scan_length(const uint8_t *buffer, size_t size, uint32_t *total, uint16_t *n_frames, const char **msg) {
-  if (size < 4 + 2 + 384 + 1) { *msg = "oakgpu_frames_read: truncated record"; return OAKGPU_RECORD_STOP; }
-  const uint8_t *p = buffer;
-  *total = get<uint32_t>(p);
-  *n_frames = get<uint16_t>(p);
-  if (*total > size || *total < 4 + 2 + 384 + 1) { *msg = "oakgpu_frames_read: record length out of range"; return OAKGPU_RECORD_STOP; }
-  return OAKGPU_RECORD_OK;
+  oak_scan::HostBytes rd{buffer};
+  int why = 0;
+  const int kind = oak_scan::scan_length(rd, size, total, n_frames, &why);
+  if (kind) *msg = oak_scan::why_message(why);
+  return kind;
 }
 int oakgpu_record_scan(const uint8_t *buffer, size_t size, uint32_t *total, uint16_t *n_frames, const char **msg) {
-  if (const int kind = oakgpu_record_scan_length(buffer, size, total, n_frames, msg)) return kind;
-  const uint8_t *p = buffer + 4 + 2 + 384 + 1, *end = buffer + *total;
-  uint32_t n_read = 0;
-  while (p < end) {
-    if ((size_t)(end - p) < 3) { *msg = "oakgpu_frames_read: truncated update"; return OAKGPU_RECORD_MALFORMED; }
-    const uint32_t m = (*p & 15) + 1, n = (*p >> 4) + 1;
-    if (m > 9 || n > 9 || (size_t)(end - p) < update_bytes(m, n)) { *msg = "oakgpu_frames_read: malformed update"; return OAKGPU_RECORD_MALFORMED; }
-    p += update_bytes(m, n);
-    ++n_read;
-  }
-  if (n_read != *n_frames) { *msg = "oakgpu_frames_read: frame count does not match the record"; return OAKGPU_RECORD_MALFORMED; }
-  return OAKGPU_RECORD_OK;
+  oak_scan::HostBytes rd{buffer};
+  int why = 0;
+  const int kind = oak_scan::scan(rd, size, total, n_frames, &why);
+  if (kind) *msg = oak_scan::why_message(why);
+  return kind;
 }
+static_assert(OAKGPU_RECORD_OK == oak_scan::RECORD_OK && OAKGPU_RECORD_MALFORMED == oak_scan::RECORD_MALFORMED && OAKGPU_RECORD_STOP == oak_scan::RECORD_STOP,
+              "one set of values");
 
 extern "C" {
 

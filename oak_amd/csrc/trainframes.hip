@@ -1,6 +1,7 @@
 // oak_amd/csrc/trainframes.hip -- training batches from `.battle.data` records on the GPU (the contract is in include/oakgpu.h).
 //
 //   k_frames_valid   : one lane per record, frames with iterations >= min_iterations (cached per min_iterations by the corpus)
+//   k_frames_eligible: a window corpus (replaywindow.hip) only: the eligible records listed on the device, one workgroup, 1,024 records a pass
 //   k_frames_draw    : one lane per draw, pyoak.sample's rule with a fast_prng stream per draw -> picks (record, frame)
 //   k_frames_order   : picks -> lane order, longest prefix first (one workgroup, counting sort by frame)
 //   k_frames_pick    : persistent lanes fed from eight queue heads, one pick at a time: the replay check's walk on the register
@@ -23,6 +24,7 @@
 #include "oakgpu_internal.h"
 #include "encode_index.hpp"
 #include "fast_prng.hpp"
+#include "game_rows.hpp"
 
 namespace oak {
 namespace tf {
@@ -377,6 +379,21 @@ __global__ __launch_bounds__(64) void k_frames_encode(EncodeArgs a) {
   }
 }
 
+// A window corpus' eligible records, in record order, listed on the device: one workgroup, 1,024 records a pass (game_rows.hpp's scan)
+__global__ __launch_bounds__(1024) void k_frames_eligible(const uint16_t *frames, const uint8_t *malformed, const uint32_t *valid, uint32_t n,
+                                                          uint32_t max_battle_length, uint32_t *list, uint32_t *count) {
+  __shared__ uint32_t wave_total[16];
+  uint32_t carry = 0;
+  for (uint32_t base = 0; base < n; base += 1024) {
+    const uint32_t r = base + threadIdx.x;
+    const bool in = r < n && !malformed[r] && valid[r] != 0 && (max_battle_length == 0 || frames[r] <= max_battle_length);
+    const game_rows::ScanPass<uint32_t> s = game_rows::scan_pass<uint32_t>(in ? 1u : 0u, wave_total);
+    if (in) list[carry + s.before] = r;
+    carry += s.total;
+  }
+  if (threadIdx.x == 0) *count = carry;
+}
+
 __global__ __launch_bounds__(256) void k_frames_count_ok(const uint8_t *status, uint32_t n, uint32_t *count) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   const uint64_t b = __ballot(i < n && status[i] == OAKGPU_REPLAY_OK);
@@ -404,7 +421,35 @@ void corpus_free(oakgpu_corpus *k) {
     if (p) (void)hipFree(p);
   cache_free(k);
   if (k->eval && k->eval_free) k->eval_free(k->eval);
+  if (k->window && k->window_free) k->window_free(k->window);
   delete k;
+}
+
+// A window corpus (replaywindow.hip): the valid counts stay on the device, k_frames_eligible lists the records, and the host reads E alone.
+int window_eligible(oakgpu_corpus *k, hipStream_t stream, uint32_t min_iterations, uint32_t max_battle_length) {
+  using namespace oak::tf;
+  const oakgpu_corpus::Valid *va = nullptr;
+  for (const auto &v : k->valids) if (v.min_iterations == min_iterations) va = &v;
+  if (!va) {
+    oakgpu_corpus::Valid v{min_iterations, nullptr, {}};
+    if (dev_alloc(v.d, k->n)) return -1;
+    if (k->n) hipLaunchKernelGGL(k_frames_valid, dim3((k->n + 255) / 256), dim3(256), 0, stream, k->records, k->offsets, k->frames, k->malformed, k->n, min_iterations, v.d);
+    k->valids.push_back(std::move(v)); // (kept even when what follows fails: a kernel may be running on it, and cache_free frees it behind a wait)
+    va = &k->valids.back();
+  }
+  oakgpu_corpus::Eligible e{min_iterations, max_battle_length, 0, nullptr, va->d};
+  if (dev_alloc(e.d, (size_t)k->n + 1)) return -1; // the list, and its length behind it
+  hipLaunchKernelGGL(k_frames_eligible, dim3(1), dim3(1024), 0, stream, k->frames, k->malformed, va->d, k->n, max_battle_length, e.d, e.d + k->n);
+  hipError_t err = hipGetLastError();
+  if (err == hipSuccess) err = hipMemcpyAsync(&e.count, e.d + k->n, 4, hipMemcpyDeviceToHost, stream);
+  const hipError_t done = hipStreamSynchronize(stream); // (always: the kernel may be running on e.d)
+  if (err == hipSuccess) err = done;
+  if (err != hipSuccess) {
+    (void)hipFree(e.d);
+    return oakgpu_fail_hip((int)err, "oakgpu_frames_sample_dev: k_frames_eligible");
+  }
+  k->eligibles.push_back(e);
+  return 0;
 }
 
 int corpus_reserve(oakgpu_corpus *k, uint32_t n) {
@@ -455,6 +500,12 @@ int encode_picks(oakgpu_ctx *c, oakgpu_corpus *k, const uint32_t *picks, uint32_
 }
 
 } // namespace
+
+void oakgpu_corpus_drop_caches(oakgpu_corpus *k) {
+  cache_free(k);
+  if (k->eval && k->eval_free) k->eval_free(k->eval);
+  k->eval = nullptr;
+}
 
 extern "C" {
 
@@ -548,6 +599,12 @@ int oakgpu_frames_sample_dev(oakgpu_ctx *c, oakgpu_corpus *k, uint32_t n, uint64
       HIPCHK(hipStreamSynchronize(stream));                // (an earlier draw may still read a list)
       cache_free(k);
     }
+    if (k->window) {
+      if (int rc = window_eligible(k, stream, min_iterations, max_battle_length)) return rc;
+      el = &k->eligibles.back();
+    }
+  }
+  if (!el) {
     // an entry joins the corpus only once it is filled: a failure below leaves nothing behind that a later call would trust
     const oakgpu_corpus::Valid *va = nullptr;
     for (const auto &v : k->valids) if (v.min_iterations == min_iterations) va = &v;

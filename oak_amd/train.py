@@ -270,6 +270,95 @@ class FrameCorpus:
         return out
 
 
+def window_check(max_records, max_bytes):
+    """The host-only check (no GPU): raises OakGpuError naming what ReplayWindow would refuse."""
+    _lib.check(_lib.load().oakgpu_corpus_window_check(int(max_records), int(max_bytes)))
+
+
+def window_scan_host(stream, offsets):
+    """The slice rule of ReplayWindow.append on host bytes (no GPU): (kinds uint8[n], frames uint16[n]); kinds: 0 dropped, 1 record,
+    2 record with its malformed flag, 3 rejected."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    data = bytes(stream)
+    buf = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, np.uint8)
+    kinds, frames = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint16)
+    _lib.check(_lib.load().oakgpu_window_scan_host(buf.ctypes.data, offsets.ctypes.data, n, kinds.ctypes.data, frames.ctypes.data))
+    return kinds[:n], frames[:n]
+
+
+class ReplayWindow(FrameCorpus):
+    """A corpus that starts empty and keeps the newest records appended to it: at most max_records of them in at most max_bytes, the oldest
+    leaving first (include/oakgpu.h: the contract).  Every FrameCorpus call on it returns what it returns on FrameCorpus(ctx, records()).
+
+        window = ReplayWindow(ctx, 65536, 1 << 30)
+        stream, offsets, *_ = forest_selfplay(ctx, teams_gpu, battle_seeds_gpu, seeds_gpu, ...)    # torch tensors on the device
+        window.append(stream, offsets)                                                             # nothing goes through the host
+        window.sample(enc, seed=step)"""
+
+    def __init__(self, ctx, max_records, max_bytes):
+        self.ctx, self.handle = ctx, None
+        h = C.c_void_p()
+        _lib.check(ctx.lib.oakgpu_corpus_create_window(ctx.handle, int(max_records), int(max_bytes), C.byref(h)))
+        self.handle = h
+
+    def append(self, data, offsets=None, chunk_bytes=64 << 20):
+        """append(stream, offsets): torch uint8 / int64 GPU tensors as forest_selfplay returns them (record i = bytes offsets[i] ..
+        offsets[i+1]; a slice of zero bytes is skipped).  append(bytes) or append([paths]): host bytes, cut into records by their length
+        fields.  Returns stats()."""
+        lib = self.ctx.lib
+        if offsets is not None:
+            import torch
+            assert data.is_cuda and offsets.is_cuda and data.dtype == torch.uint8 and offsets.dtype in (torch.int64, torch.uint64)
+            data, offsets = data.contiguous(), offsets.contiguous()
+            n = int(offsets.numel()) - 1
+            dev = data.device
+            mine, theirs = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=dev), torch.cuda.current_stream(dev)
+            mine.wait_stream(theirs)
+            _lib.check(lib.oakgpu_corpus_append_dev(self.ctx.handle, self.handle, data.data_ptr(), offsets.data_ptr(), max(n, 0)))
+            theirs.wait_stream(mine)   # (the tensors may be freed or rewritten once torch's stream has passed the move)
+            return self.stats()
+        if isinstance(data, (bytes, bytearray, memoryview)):
+            pieces = [bytes(data)]
+        else:
+            from .frames import _whole_records
+            pieces = []
+            for path in data:
+                with open(path, "rb") as f:
+                    pieces += [piece for _, piece in _whole_records(f, chunk_bytes) if piece]
+        for piece in pieces:
+            buf = np.frombuffer(piece, dtype=np.uint8) if piece else np.zeros(1, np.uint8)
+            _lib.check(lib.oakgpu_corpus_append(self.ctx.handle, self.handle, buf.ctypes.data, len(piece)))
+        return self.stats()
+
+    def stats(self):
+        out = (C.c_uint64 * 6)()
+        _lib.check(self.ctx.lib.oakgpu_corpus_window_stats(self.handle, C.byref(out)))
+        return dict(zip(("records", "bytes", "appended", "evicted", "rejected", "appends"), (int(v) for v in out)))
+
+    def records(self, device=None):
+        """The surviving records back to back, as a `.battle.data` file holds them: bytes, or a torch uint8 tensor on `device`."""
+        lib, size = self.ctx.lib, C.c_size_t(0)
+        _lib.check(lib.oakgpu_corpus_records(self.ctx.handle, self.handle, None, 0, C.byref(size), 0))
+        if device is None:
+            buf = np.zeros(max(size.value, 1), np.uint8)
+            _lib.check(lib.oakgpu_corpus_records(self.ctx.handle, self.handle, buf.ctypes.data, size.value, C.byref(size), 0))
+            return buf[:size.value].tobytes()
+        import torch
+        out = torch.zeros(max(size.value, 1), dtype=torch.uint8, device=device)
+        mine, theirs = torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=out.device), torch.cuda.current_stream(out.device)
+        mine.wait_stream(theirs)
+        _lib.check(lib.oakgpu_corpus_records(self.ctx.handle, self.handle, out.data_ptr(), size.value, C.byref(size), 1))
+        theirs.wait_stream(mine)
+        return out[:size.value]
+
+    def save(self, path):
+        data = self.records()
+        with open(path, "wb") as f:
+            f.write(data)
+        return len(data)
+
+
 def encode_battles(ctx, battles, durations, results, enc):
     """The position encoder alone on states the caller holds on the device: torch uint8 tensors battles [n, 384], durations [n, 8],
     results [n] -> enc.pokemon, active, hp, choice_indices, k (rows 0 .. n-1; enc on the same device)."""
