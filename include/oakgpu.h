@@ -940,6 +940,15 @@ typedef struct {
   double fast_search_prob;     /* 0 = off */
   char fast_policy_mode[16];   /* "" = policy_mode */
 } oakgpu_selfplay_params;
+/* Skipped battles (generate's --battle-skip-prob / --t1-budget, generate.cc:233-236, 293-296, 303-309, 344), for the forest loop's _build
+ * calls alone; oakgpu_selfplay_game(s), the host per-game loop, know nothing of them.  A game with a built seat is skipped with
+ * probability battle_skip_prob: its first turn is searched with t1_budget iterations for its matchup value, and it is dropped with
+ * status OAKGPU_FSP_SKIPPED.  The rule is selfplay_pick.hpp's game_is_skipped; the draw has a stream of its own (see the _build calls).
+ * A struct of its own beside oakgpu_selfplay_params, whose size and layout stay what they were. */
+typedef struct {
+  uint32_t t1_budget;          /* a skipped game's one search; 0 = search.iterations */
+  double battle_skip_prob;     /* 0 = off */
+} oakgpu_selfplay_skip;
 /* endless_battle_check (cpp/src/generate.cc:127-152): 1 when every pairing of the two teams (2 x 6 x {species, 4 moves}) is a Ghost against a
  * Ghost with no move on either side that can hit a Ghost (type Normal / Fighting or base power 0) -- with ebc=false such a game runs to turn
  * 1,000; the generator draws other teams, and oakgpu_selfplay_game(s) refuse the pair with "EBC check failed". */
@@ -987,6 +996,7 @@ int oakgpu_selfplay_games(oakgpu_ctx *const *ctxs, oakgpu_net *net, const uint8_
 #define OAKGPU_FSP_OK 0
 #define OAKGPU_FSP_MAX_LENGTH 1
 #define OAKGPU_FSP_ZERO_POLICY 2
+#define OAKGPU_FSP_SKIPPED 3 /* the _build calls: searched once for its matchup value, not played (see below) */
 int oakgpu_forest_selfplay_check(uint32_t max_trees, uint32_t max_iterations, int contextual, const oakgpu_selfplay_params *params, int has_net,
                                  uint32_t n, const uint8_t *teams, int solve_nash);
 int oakgpu_forest_selfplay_dev(oakgpu_forest *forest, oakgpu_net *net, const oakgpu_selfplay_params *params, const uint8_t *teams,
@@ -1023,6 +1033,35 @@ int oakgpu_forest_selfplay_set_partition(oakgpu_forest *forest, int on);
 /* host only: selfplay_pick.hpp's turn prelude on one stream -- *rng advances, *use_fast and *search_seed are the turn's */
 int oakgpu_selfplay_prelude_host(uint64_t *rng, double fast_search_prob, int32_t *use_fast, uint64_t *search_seed);
 int oakgpu_forest_selfplay_keep_stats(const oakgpu_forest *forest, uint64_t out[4]);
+/* Matchup values and skipped battles: the build network's side of self-play (generate.cc:233-236, 293-309, 344, 361-383).
+ * _matchup: n doubles, to host or device memory, valid after any forest self-play call: the empirical value (process_output's) of each
+ *   game's FIRST search, p1's view -- what generate stores as a built seat's trajectory value (p2's is 1 - it); NaN for a game that was
+ *   never searched.  The pick kernel scatters it by game index on the row's first frame; no other output changes.
+ * _build_dev / _build are _dev / the host-array call plus `built`: n bytes (device memory for _build_dev, host memory otherwise), bit 0 =
+ *   p1's team was built, bit 1 = p2's; NULL = no game is built, and that IS the call without it, byte for byte.
+ *   Skip rule (selfplay_pick.hpp's game_is_skipped; oakgpu_selfplay_skip_host is the same text on the host): game g is skipped when
+ *   built[g] != 0 && battle_skip_prob > 0 && uniform01(x) < battle_skip_prob, x = seeds[g] ^ 0x5B1D7C83A46E20F9.  Departure from the
+ *   reference, which draws from its worker thread's device: the draw has a stream of its own and the game's stream is untouched, so a
+ *   game that is NOT skipped is byte for byte the game of a call without the fields, whatever `built` says.
+ *   A skipped game runs turn 1's prelude as any game (with fast searches: the flag, then the search seed), is searched by the turn's one
+ *   search with t1_budget iterations whatever the flag (generate.cc:293-296; 0 = search.iterations), and the pick writes its matchup and
+ *   nothing else: no policy draw, no frame, no update bytes.  The next retire pass retires it with OAKGPU_FSP_SKIPPED: zero bytes in the
+ *   stream, n_frames 0, result byte 0; from turn 2 on it is in no launch.  On a kept forest its tree simply has no successor.
+ *   Turn 1's search is a budgets search whenever a skipped row's budget differs from another row's; its rows are NOT sorted by budget
+ *   on that one turn, so _fast_stats' launched may exceed run by that turn's slack.  _last_stats' rows searched counts a skipped game once.
+ *   `skip` (nullable = all zeros: nothing is skipped) holds battle_skip_prob and t1_budget.
+ * oakgpu_forest_selfplay_skip_check (host only; the _build calls run it after oakgpu_forest_selfplay_check, before any launch) refuses by
+ *   name: battle_skip_prob outside [0, 1] or NaN, t1_budget above the forest's max_iterations. */
+int oakgpu_forest_selfplay_skip_check(uint32_t max_iterations, const oakgpu_selfplay_skip *skip);
+int oakgpu_forest_selfplay_build_dev(oakgpu_forest *forest, oakgpu_net *net, const oakgpu_selfplay_params *params, const oakgpu_selfplay_skip *skip,
+                                     const uint8_t *teams, const uint64_t *battle_seeds, const uint64_t *seeds, const uint8_t *built, uint32_t n,
+                                     int solve_nash);
+int oakgpu_forest_selfplay_build(oakgpu_forest *forest, oakgpu_net *net, const oakgpu_selfplay_params *params, const oakgpu_selfplay_skip *skip,
+                                 const uint8_t *teams, const uint64_t *battle_seeds, const uint64_t *seeds, const uint8_t *built, uint32_t n,
+                                 int solve_nash);
+int oakgpu_forest_selfplay_matchup(oakgpu_forest *forest, double *out, int to_device);
+/* host only: 1 when the game of this seed is skipped, else 0 (probability 0 or built == 0: no draw) */
+int oakgpu_selfplay_skip_host(uint64_t seed, double prob, int built);
 int oakgpu_selfplay_pick_host(uint32_t m, uint32_t n, const uint64_t *visit_matrix, const double *value_matrix, uint64_t iterations,
                               const double *p1_nash, const double *p2_nash, double nash_value, const double *p1_prior, const double *p2_prior,
                               const uint8_t *p1_choices, const uint8_t *p2_choices, const char *policy_mode, double policy_temp,
@@ -1463,6 +1502,23 @@ int oakgpu_build_provide_dev(oakgpu_ctx *ctx, const oakgpu_build_net *net, const
 /* records: room for n x 128 bytes, 4-byte aligned; count: one device word, the number of records written */
 int oakgpu_build_records_dev(oakgpu_ctx *ctx, const uint8_t *teams_init, const uint8_t *sizes /* nullable */, const uint8_t *n_updates, const uint16_t *action,
                              const float *prob, const float *value, const float *score, uint32_t n, uint8_t *records, uint32_t *count);
+/* Both seats' records of a batch of self-play games, on the device (generate.cc:361-383): ONE launch, asynchronous on the context's stream.
+ * p1 / p2: the seat's oakgpu_build_provide_dev outputs (n rows each; sizes nullable = 6); status / results / matchup: the game loop's
+ * per-game outputs (oakgpu_forest_selfplay_records, _matchup), all device arrays.  A game with status OAKGPU_FSP_OK or _SKIPPED gives one
+ * record per seat with n_updates > 0; a dropped or stopped game gives none.  Order: game-major, p1 before p2.  p1's value = (float)matchup,
+ * p2's = (float)(1.0 - matchup); p1's score = PKMN::score(result) (win 1, lose 0, tie 0.5), p2's = 1 - it; a skipped game has no score
+ * (byte 255).  The bytes are otherwise oakgpu_build_records' (one record writer).  records: room for 2 n x 128 bytes, 4-byte aligned, left
+ * alone beyond the records written; count: one device word.
+ * oakgpu_build_game_targets_host (no GPU) is the value / score rule alone: returns 1 when a game of this status gives records (then *value,
+ * and *score, negative = none, are a `seat`'s, 0 = p1), 0 when it gives none, -1 for a refused argument. */
+typedef struct {
+  const uint8_t *teams_init, *sizes, *n_updates;
+  const uint16_t *action;
+  const float *prob;
+} oakgpu_build_seat_arrays;
+int oakgpu_build_game_records_dev(oakgpu_ctx *ctx, const oakgpu_build_seat_arrays *p1, const oakgpu_build_seat_arrays *p2, const uint8_t *status,
+                                  const uint8_t *results, const double *matchup, uint32_t n, uint8_t *records, uint32_t *count);
+int oakgpu_build_game_targets_host(int status, uint8_t result, double matchup, int seat, float *value, float *score);
 /* host arrays in and out */
 int oakgpu_build_rollout(oakgpu_ctx *ctx, const oakgpu_build_net *net, const uint8_t *teams, const uint8_t *sizes /* nullable */, const uint64_t *seeds,
                          uint32_t n, int input_update, const oakgpu_build_outputs *out);
@@ -1545,6 +1601,29 @@ int oakgpu_build_traj_check(const uint8_t *bytes, size_t len, uint8_t *status_ou
  * The corpus belongs to ctx and must be destroyed before it. */
 int oakgpu_build_corpus_create(oakgpu_ctx *ctx, const uint8_t *buffer, size_t size, const size_t *file_sizes, uint32_t n_files, oakgpu_build_corpus **out);
 void oakgpu_build_corpus_destroy(oakgpu_build_corpus *corpus);
+/* ---- the build window: the newest max_records `.build.data` records resident on the device, appended to by self-play (buildwindow.hip;
+ * the build side's counterpart of oakgpu_corpus_create_window).
+ *   Contract.  After any sequence of appends, every corpus call on oakgpu_build_window_corpus(w) -- _scan_dev, _info, oakgpu_build_traj(_dev),
+ *   oakgpu_build_traj_sample(_dev) -- returns bit for bit what it returns on oakgpu_build_corpus_create over the surviving records' bytes as
+ *   ONE file, oldest first: the two-stage draw still draws the file (% 1), then the record.  The oldest records leave first; a batch larger
+ *   than the window keeps its newest max_records; a record whose format byte is not 0 is rejected (counted, not appended); an append of 0
+ *   records is a no-op.  A window that holds no record refuses the trajectory calls by name; its _info reports 0 records.
+ *   _append_dev: records = max_count x 128 device bytes, 16-byte aligned; count = one device word (oakgpu_build_game_records_dev's), cut to
+ *   max_count.  Two launches on the context's stream (an append that evicts compacts into the window's second buffer); the host waits for
+ *   the stream ONCE and reads two words, the batch's accepted and rejected totals -- nothing in proportion to the window.  _append takes
+ *   host bytes (a multiple of 128).  _corpus is BORROWED: it lives as long as the window and is not to be destroyed.  _records copies the
+ *   held bytes to the host (out nullable: *bytes alone is the size query).  _stats: out = { records held, appended, evicted, rejected }
+ *   since creation; appended counts every accepted record, evicted those that left or never fitted: held = appended - evicted.
+ *   Refused by name: a null argument, max_records 0 or above 2^31 - 1, a window of another context, misaligned records, host bytes that are
+ *   no multiple of 128. */
+typedef struct oakgpu_build_window oakgpu_build_window;
+int oakgpu_build_window_create(oakgpu_ctx *ctx, uint32_t max_records, oakgpu_build_window **out);
+void oakgpu_build_window_destroy(oakgpu_build_window *window);
+int oakgpu_build_window_append_dev(oakgpu_ctx *ctx, oakgpu_build_window *window, const uint8_t *records, const uint32_t *count, uint32_t max_count);
+int oakgpu_build_window_append(oakgpu_ctx *ctx, oakgpu_build_window *window, const uint8_t *bytes, size_t len);
+oakgpu_build_corpus *oakgpu_build_window_corpus(oakgpu_build_window *window);
+int oakgpu_build_window_records(oakgpu_build_window *window, uint8_t *out, size_t capacity, size_t *bytes);
+int oakgpu_build_window_stats(const oakgpu_build_window *window, uint64_t out[4]);
 /* One lane per record: every record's status and the count per status, kept by the corpus (asynchronous). */
 int oakgpu_build_corpus_scan_dev(oakgpu_ctx *ctx, oakgpu_build_corpus *corpus);
 /* records, files and the count per status: of the last _scan_dev, or of a scan this call makes when there was none; synchronises once. */

@@ -414,15 +414,21 @@ public:
     std::vector<uint32_t> nodes_kept;      // params.keep_node: per game, the updates that found their child (oakgpu_selfplay_params::nodes_kept); else zeros
     std::array<uint64_t, 4> keep_stats{};  // params.keep_node: sum of nodes_kept, trees dropped for want of room, root mismatches, nodes carried in
     std::array<uint64_t, 4> fast_stats{};  // params.fast_search_prob: fast frames, full frames, tree-iterations launched, tree-iterations run
+    std::vector<double> matchup;           // per game: the first search's empirical value (a built seat's trajectory value); NaN if never searched
   };
   explicit ForestSelfplay(SearchForest &forest) : forest_{forest} {}
   // teams: n x 60 bytes; params.search.seed / batch and params.seed are ignored; keep_node = 1 needs a forest made with keep_arena;
   // params.fast_budget / fast_search_prob / fast_policy_mode: generate's fast searches (the forest's max_iterations covers both budgets)
+  // built (empty = no game is built; else one byte per game, bit 0 = p1's team was built, bit 1 = p2's) with skip.battle_skip_prob /
+  // t1_budget: generate's skipped battles -- such a game has status OAKGPU_FSP_SKIPPED, no record and a matchup
   Result play(const oakgpu_selfplay_params &params, const std::vector<uint8_t> &teams, const std::vector<uint64_t> &battle_seeds,
-              const std::vector<uint64_t> &seeds, Network *net = nullptr, int solve_nash = NASH_HOST) {
+              const std::vector<uint64_t> &seeds, Network *net = nullptr, int solve_nash = NASH_HOST, const std::vector<uint8_t> &built = {},
+              const oakgpu_selfplay_skip &skip = {}) {
     const uint32_t n = (uint32_t)seeds.size();
     if (teams.size() != (size_t)n * 60 || battle_seeds.size() != n) throw std::runtime_error{"oakgpu: ForestSelfplay::play: teams n x 60, one battle seed and one seed per game"};
-    check(oakgpu_forest_selfplay(forest_.get(), net ? net->get() : nullptr, &params, teams.data(), battle_seeds.data(), seeds.data(), n, solve_nash));
+    if (!built.empty() && built.size() != n) throw std::runtime_error{"oakgpu: ForestSelfplay::play: built is empty or one byte per game"};
+    check(oakgpu_forest_selfplay_build(forest_.get(), net ? net->get() : nullptr, &params, &skip, teams.data(), battle_seeds.data(), seeds.data(),
+                                       built.empty() ? nullptr : built.data(), n, solve_nash));
     Result out;
     size_t bytes = 0;
     check(oakgpu_forest_selfplay_records(forest_.get(), nullptr, 0, &bytes, nullptr, nullptr, nullptr, nullptr, 0));
@@ -437,6 +443,9 @@ public:
     out.nodes_kept.resize(n);
     check(oakgpu_forest_selfplay_keep_stats(forest_.get(), out.keep_stats.data()));
     check(oakgpu_forest_selfplay_fast_stats(forest_.get(), out.fast_stats.data()));
+    out.matchup.assign((size_t)n + 1, 0.0);
+    check(oakgpu_forest_selfplay_matchup(forest_.get(), out.matchup.data(), 0));
+    out.matchup.resize(n);
     return out;
   }
 
@@ -920,7 +929,7 @@ public:
     }
     check(oakgpu_build_corpus_create(ctx_, all.data(), all.size(), sizes.data(), static_cast<uint32_t>(sizes.size()), &corpus_));
   }
-  ~BuildTrajectories() { oakgpu_build_corpus_destroy(corpus_); }
+  ~BuildTrajectories() { if (owned_) oakgpu_build_corpus_destroy(corpus_); }
   BuildTrajectories(const BuildTrajectories &) = delete;
   BuildTrajectories &operator=(const BuildTrajectories &) = delete;
   oakgpu_build_corpus *get() const noexcept { return corpus_; }
@@ -964,6 +973,9 @@ public:
     return t;
   }
 
+protected:
+  BuildTrajectories(Context &ctx, oakgpu_build_corpus *borrowed) : ctx_{ctx.get()}, corpus_{borrowed}, owned_{false} {} // (BuildWindow's corpus)
+
 private:
   static Rows make(uint32_t n, bool with_mask) {
     Rows r;
@@ -980,6 +992,42 @@ private:
   }
   oakgpu_ctx *ctx_{};
   oakgpu_build_corpus *corpus_{};
+  bool owned_{true};
+};
+
+// The newest max_records `.build.data` records resident on the device (oakgpu_build_window_*): self-play appends, the oldest leave first,
+// and info / decode / sample / targets are BuildTrajectories' on the surviving records as one file, oldest first.  Must not outlive its Context.
+class BuildWindow : public BuildTrajectories {
+public:
+  BuildWindow(Context &ctx, uint32_t max_records) : BuildWindow(ctx, make_window(ctx, max_records)) {}
+  ~BuildWindow() { oakgpu_build_window_destroy(window_); }
+  oakgpu_build_window *window() const noexcept { return window_; }
+  void append(const std::vector<uint8_t> &bytes) { check(oakgpu_build_window_append(wctx_, window_, bytes.data(), bytes.size())); }
+  // device records (16-byte aligned) and a device count word, as oakgpu_build_game_records_dev leaves them
+  void append_dev(const uint8_t *records, const uint32_t *count, uint32_t max_count) { check(oakgpu_build_window_append_dev(wctx_, window_, records, count, max_count)); }
+  std::vector<uint8_t> records() {
+    size_t bytes = 0;
+    check(oakgpu_build_window_records(window_, nullptr, 0, &bytes));
+    std::vector<uint8_t> out(bytes + 1);
+    check(oakgpu_build_window_records(window_, out.data(), bytes, &bytes));
+    out.resize(bytes);
+    return out;
+  }
+  std::array<uint64_t, 4> stats() const { // records held, appended, evicted, rejected
+    std::array<uint64_t, 4> out{};
+    check(oakgpu_build_window_stats(window_, out.data()));
+    return out;
+  }
+
+private:
+  static oakgpu_build_window *make_window(Context &ctx, uint32_t max_records) {
+    oakgpu_build_window *w = nullptr;
+    check(oakgpu_build_window_create(ctx.get(), max_records, &w));
+    return w;
+  }
+  BuildWindow(Context &ctx, oakgpu_build_window *w) : BuildTrajectories(ctx, oakgpu_build_window_corpus(w)), wctx_{ctx.get()}, window_{w} {}
+  oakgpu_ctx *wctx_{};
+  oakgpu_build_window *window_{};
 };
 
 // The optimiser step of the reference's build.py on the device, for the three-layer nets of a `.build.net` (oakgpu_build_trainer_*; the

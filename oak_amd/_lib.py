@@ -47,13 +47,17 @@ SYMBOLS = [
     "oakgpu_forest_budgets_check", "oakgpu_forest_search_budgets_dev", "oakgpu_forest_search_budgets", "oakgpu_forest_search_budgets_kept_dev",
     "oakgpu_forest_search_budgets_kept", "oakgpu_forest_last_rows", "oakgpu_forest_selfplay_fast_stats", "oakgpu_forest_selfplay_set_partition",
     "oakgpu_selfplay_prelude_host",
+    "oakgpu_forest_selfplay_build_dev", "oakgpu_forest_selfplay_build", "oakgpu_forest_selfplay_matchup", "oakgpu_selfplay_skip_host",
+    "oakgpu_forest_selfplay_skip_check",
     "oakgpu_frames_symmetries_dev", "oakgpu_trainer_check", "oakgpu_trainer_create", "oakgpu_trainer_destroy", "oakgpu_trainer_shape",
     "oakgpu_trainer_forward_dev", "oakgpu_trainer_gradients_dev", "oakgpu_trainer_adam_dev", "oakgpu_trainer_step_dev", "oakgpu_trainer_report",
     "oakgpu_trainer_read", "oakgpu_trainer_set_gradients", "oakgpu_trainer_net_bytes", "oakgpu_trainer_forward", "oakgpu_trainer_gradients",
     "oakgpu_trainer_step",
     "oakgpu_build_tables", "oakgpu_build_net_check", "oakgpu_build_net_load", "oakgpu_build_net_destroy", "oakgpu_build_net_shape", "oakgpu_build_teams_check",
     "oakgpu_build_provide_check", "oakgpu_build_rollout_dev", "oakgpu_build_provide_dev", "oakgpu_build_records_dev", "oakgpu_build_rollout",
-    "oakgpu_build_provide", "oakgpu_build_records",
+    "oakgpu_build_provide", "oakgpu_build_records", "oakgpu_build_game_records_dev", "oakgpu_build_game_targets_host",
+    "oakgpu_build_window_create", "oakgpu_build_window_destroy", "oakgpu_build_window_append_dev", "oakgpu_build_window_append", "oakgpu_build_window_corpus",
+    "oakgpu_build_window_records", "oakgpu_build_window_stats",
     "oakgpu_build_traj_check", "oakgpu_build_corpus_create", "oakgpu_build_corpus_destroy", "oakgpu_build_corpus_scan_dev", "oakgpu_build_corpus_info",
     "oakgpu_build_traj_dev", "oakgpu_build_traj_sample_dev", "oakgpu_build_targets_dev", "oakgpu_build_state_dense_dev", "oakgpu_build_traj",
     "oakgpu_build_traj_sample", "oakgpu_build_targets", "oakgpu_build_state_dense",
@@ -110,6 +114,10 @@ class SelfplayParams(C.Structure):    # oakgpu_selfplay_params
                 ("fast_budget", C.c_uint32), ("fast_search_prob", C.c_double), ("fast_policy_mode", C.c_char * 16)]
 
 
+class SelfplaySkip(C.Structure):      # oakgpu_selfplay_skip
+    _fields_ = [("t1_budget", C.c_uint32), ("battle_skip_prob", C.c_double)]
+
+
 class EncodedFrames(C.Structure):     # oakgpu_encoded_frames: one pointer per tensor, device or host as the call says
     _fields_ = [(name, C.c_void_p) for name in ("pokemon", "active", "hp", "choice_indices", "k", "choice", "iterations", "empirical_policies",
                                                 "nash_policies", "empirical_value", "nash_value", "score", "status", "where")]
@@ -151,6 +159,10 @@ class TrainOutputs(C.Structure):      # oakgpu_train_outputs: one nullable point
 class BuildOutputs(C.Structure):      # oakgpu_build_outputs: one pointer per array, device or host as the call says
     _fields_ = [(name, C.c_void_p) for name in ("teams_out", "n_updates", "action", "index", "n_legal", "prob", "trace_legal", "trace_logits",
                                                 "trace_policy", "teams_init", "sizes_out", "team_index")]
+
+
+class BuildSeatArrays(C.Structure):   # oakgpu_build_seat_arrays
+    _fields_ = [(name, C.c_void_p) for name in ("teams_init", "sizes", "n_updates", "action", "prob")]
 
 
 class BuildProvider(C.Structure):     # oakgpu_build_provider
@@ -460,6 +472,11 @@ def load():
     lib.oakgpu_forest_selfplay_fast_stats.argtypes = [vp, C.POINTER(u64 * 4)]
     lib.oakgpu_forest_selfplay_set_partition.argtypes = [vp, i32]
     lib.oakgpu_selfplay_prelude_host.argtypes = [C.POINTER(u64), C.c_double, C.POINTER(i32), C.POINTER(u64)]
+    lib.oakgpu_forest_selfplay_build_dev.argtypes = [vp, vp, C.POINTER(SelfplayParams), C.POINTER(SelfplaySkip), vp, vp, vp, vp, u32, i32]
+    lib.oakgpu_forest_selfplay_build.argtypes = [vp, vp, C.POINTER(SelfplayParams), C.POINTER(SelfplaySkip), vp, vp, vp, vp, u32, i32]
+    lib.oakgpu_forest_selfplay_skip_check.argtypes = [u32, C.POINTER(SelfplaySkip)]
+    lib.oakgpu_forest_selfplay_matchup.argtypes = [vp, vp, i32]
+    lib.oakgpu_selfplay_skip_host.argtypes = [u64, C.c_double, i32]
     lib.oakgpu_selfplay_pick_host.argtypes = [u32, u32, vp, vp, u64, vp, vp, C.c_double, vp, vp, vp, vp, C.c_char_p, C.c_double, C.c_double, C.POINTER(u64),
                                               C.POINTER(C.c_double), vp, vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, C.POINTER(u32)]
     lib.oakgpu_forest_match_check.argtypes = [u32, u32, i32, C.POINTER(ForestMatchParams), u32]
@@ -504,6 +521,17 @@ def load():
     lib.oakgpu_build_provide.argtypes = lib.oakgpu_build_provide_dev.argtypes
     lib.oakgpu_build_records_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]
     lib.oakgpu_build_records.argtypes = lib.oakgpu_build_records_dev.argtypes
+    lib.oakgpu_build_game_records_dev.argtypes = [vp, C.POINTER(BuildSeatArrays), C.POINTER(BuildSeatArrays), vp, vp, vp, u32, vp, vp]
+    lib.oakgpu_build_window_create.argtypes = [vp, u32, C.POINTER(vp)]
+    lib.oakgpu_build_window_destroy.argtypes = [vp]
+    lib.oakgpu_build_window_destroy.restype = None
+    lib.oakgpu_build_window_append_dev.argtypes = [vp, vp, vp, vp, u32]
+    lib.oakgpu_build_window_append.argtypes = [vp, vp, vp, sz]
+    lib.oakgpu_build_window_corpus.argtypes = [vp]
+    lib.oakgpu_build_window_corpus.restype = vp
+    lib.oakgpu_build_window_records.argtypes = [vp, vp, sz, C.POINTER(sz)]
+    lib.oakgpu_build_window_stats.argtypes = [vp, C.POINTER(u64 * 4)]
+    lib.oakgpu_build_game_targets_host.argtypes = [i32, C.c_uint8, C.c_double, i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     traj_p, prm_t = C.POINTER(BuildTrajectories), C.POINTER(BuildTrajParams)
     lib.oakgpu_build_traj_check.argtypes = [vp, sz, vp]
     lib.oakgpu_build_corpus_create.argtypes = [vp, vp, sz, C.POINTER(sz), u32, C.POINTER(vp)]

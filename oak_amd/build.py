@@ -234,6 +234,61 @@ def records(ctx, trajectories, value, score):
     return out[:count.value].tobytes()
 
 
+def game_targets(status, result, matchup, seat):
+    """oakgpu_build_game_targets_host (no GPU): the (value, score) of a seat's record of one self-play game -- seat 0 = p1: value =
+    float32(matchup), seat 1: float32(1 - matchup); score from the result byte, None for a skipped game -- or None when a game of this
+    status (frames.FSP_STATUS) gives no record."""
+    v, s = C.c_float(0), C.c_float(0)
+    rc = _lib.load().oakgpu_build_game_targets_host(int(status), int(result), float(matchup), int(seat), C.byref(v), C.byref(s))
+    if rc < 0:
+        _lib.check(rc)
+    return None if rc == 0 else (v.value, None if s.value < 0 else s.value)
+
+
+def game_records(ctx, seats, status, results, matchup, out=None):
+    """Both seats' `.build.data` records of a batch of self-play games, on the device in one launch (oakgpu_build_game_records_dev):
+    seats = (p1, p2), provide's dict per seat; status, results, matchup: forest_selfplay's per-game outputs (stats["matchup"]).  A game
+    with status OK or SKIPPED gives one record per built seat, game-major, p1 before p2, with game_targets' value and score.  Tensors in:
+    returns (records uint8 [2 n, 128], count int32 [1]) -- both stay on the device, count is what BuildWindow.append takes; out: the caller's
+    records tensor.  numpy in: staged through torch (which must have initialised the GPU before the library did), returns the records' bytes."""
+    import torch
+    on_device = hasattr(status, "data_ptr")
+    device = status.device if on_device else torch.device("cuda", ctx.device)
+    steps = {"action": torch.int16, "prob": torch.float32}
+
+    def dev(x, dtype):
+        if hasattr(x, "data_ptr"):
+            return x.contiguous()
+        a = np.ascontiguousarray(x)
+        if a.dtype == np.uint16:
+            a = a.view(np.int16)
+        return torch.from_numpy(a).to(device=device, dtype=dtype)
+    n = int(status.shape[0])
+    held, arrays = [], []
+    for seat in seats:
+        t = {"teams_init": dev(seat["teams_init"], torch.uint8), "sizes": dev(seat["sizes"], torch.uint8), "n_updates": dev(seat["n_updates"], torch.uint8),
+             "action": dev(seat["action"], steps["action"]), "prob": dev(seat["prob"], steps["prob"])}
+        if any(int(t[k].shape[0]) != n for k in t):
+            raise ValueError("game_records: every seat array has one row per game")
+        held.append(t)
+        arrays.append(_lib.BuildSeatArrays(*[t[k].data_ptr() for k in ("teams_init", "sizes", "n_updates", "action", "prob")]))
+    st, rs, mu = dev(status, torch.uint8), dev(results, torch.uint8), dev(matchup, torch.float64)
+    if int(rs.shape[0]) != n or int(mu.shape[0]) != n or mu.dtype != torch.float64:
+        raise ValueError("game_records: status, results uint8[n] and matchup float64[n]")
+    records = torch.zeros((2 * n, RECORD_BYTES), dtype=torch.uint8, device=device) if out is None else out
+    if records.numel() < 2 * n * RECORD_BYTES or records.dtype != torch.uint8 or not records.is_contiguous():
+        raise ValueError("game_records: out holds 2 n x 128 bytes")
+    count = torch.zeros(1, dtype=torch.int32, device=device)
+    mine, theirs = torch.cuda.ExternalStream(ctx.stream_ptr(), device=device), torch.cuda.current_stream(device)
+    mine.wait_stream(theirs)
+    _lib.check(ctx.lib.oakgpu_build_game_records_dev(ctx.handle, C.byref(arrays[0]), C.byref(arrays[1]), st.data_ptr(), rs.data_ptr(), mu.data_ptr(), n,
+                                                     records.data_ptr(), count.data_ptr()))
+    theirs.wait_stream(mine)
+    if on_device:
+        return records, count
+    return records.reshape(-1)[:int(count.item()) * RECORD_BYTES].cpu().numpy().tobytes()
+
+
 def decode_records(data):
     """`.build.data` bytes (NoTeam records) -> a list of {"score" (None: no score), "value", "action" uint16[31], "probability" uint16[31]}."""
     buf = np.frombuffer(bytes(data), np.uint8)
@@ -379,6 +434,51 @@ class TrajectoryCorpus:
         return out
 
 
+class BuildWindow(TrajectoryCorpus):
+    """The newest max_records `.build.data` records resident on the context's device (oakgpu_build_window_*): self-play appends, the oldest
+    leave first, and info / decode / sample are TrajectoryCorpus's on the surviving records as ONE file, oldest first, bit for bit."""
+
+    def __init__(self, ctx, max_records):
+        self.ctx, self.window, self.handle, self.max_records = ctx, C.c_void_p(), C.c_void_p(), int(max_records)
+        _lib.check(ctx.lib.oakgpu_build_window_create(ctx.handle, int(max_records), C.byref(self.window)))
+        self.handle = C.c_void_p(ctx.lib.oakgpu_build_window_corpus(self.window))      # borrowed: freed with the window
+
+    def close(self):
+        if self.window:
+            self.ctx.lib.oakgpu_build_window_destroy(self.window)
+            self.window, self.handle = C.c_void_p(), C.c_void_p()
+
+    def append(self, records, count=None):
+        """records: `.build.data` bytes (or a uint8 array), or a uint8 GPU tensor of whole records with count, an int32 / uint32 GPU tensor of
+        one word (game_records' pair) -- count None: every record of the tensor.  A record whose format byte is not 0 is rejected."""
+        lib = self.ctx.lib
+        if hasattr(records, "data_ptr"):
+            import torch
+            r = records.contiguous().view(-1)
+            n = int(r.numel()) // RECORD_BYTES
+            if r.dtype != torch.uint8 or r.numel() % RECORD_BYTES:
+                raise ValueError("BuildWindow.append: a uint8 tensor of whole records")
+            if count is None:
+                count = torch.full((1,), n, dtype=torch.int32, device=r.device)
+            _on_stream(self.ctx, r.device, lambda: lib.oakgpu_build_window_append_dev(self.ctx.handle, self.window, r.data_ptr(), count.data_ptr(), n))
+        else:
+            buf = np.frombuffer(bytes(records), np.uint8) if isinstance(records, (bytes, bytearray, memoryview)) else np.ascontiguousarray(records, np.uint8).reshape(-1)
+            _lib.check(lib.oakgpu_build_window_append(self.ctx.handle, self.window, buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size))
+
+    def records(self):
+        """the held records' bytes, oldest first"""
+        size = C.c_size_t(0)
+        _lib.check(self.ctx.lib.oakgpu_build_window_records(self.window, None, 0, C.byref(size)))
+        out = np.zeros(max(size.value, 1), np.uint8)
+        _lib.check(self.ctx.lib.oakgpu_build_window_records(self.window, out.ctypes.data_as(C.c_void_p), size.value, C.byref(size)))
+        return out[:size.value].tobytes()
+
+    def stats(self):
+        st = (C.c_uint64 * 4)()
+        _lib.check(self.ctx.lib.oakgpu_build_window_stats(self.window, C.byref(st)))
+        return {"records": int(st[0]), "appended": int(st[1]), "evicted": int(st[2]), "rejected": int(st[3])}
+
+
 def targets(ctx, traj, value_weight):
     """The network-free half of build.py's process_targets from a decoded dict (untrimmed): valid bool [n, 31]; n_valid; rows [V, 2] = (b, t)
     in the order of torch's x[valid]; state_cells [V, 31] / state_n [V], the actions in front of each valid step in step order (padded with
@@ -434,6 +534,36 @@ def check_trainer(data, max_traj=1):
     """The refusals of Trainer, by name, without a GPU."""
     buf = np.frombuffer(bytes(data), np.uint8)
     _lib.check(_lib.load().oakgpu_build_trainer_check(buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, int(max_traj)))
+
+
+class NoValidStep(Exception):
+    """accumulate_batch: the first chunks of a run held no valid step"""
+
+
+def accumulate_batch(ctx, corpus, trainer, batch_size, trajectories_per_step, keep_prob, value_weight, seed0, chunks, rows, device, hyper, generator=None):
+    """One optimiser step's gradient (build.py:295-332: backward() per chunk until the batch is full), for tools/train_build_net.py and
+    rl.run alike: zero_gradients, then chunks of trajectories_per_step draws from `corpus` (a TrajectoryCorpus or a BuildWindow) -- chunk
+    number c draws with seed0 + c * trajectories_per_step, so no stream is used twice -- targets, the keep mask (torch.rand below
+    keep_prob, from `generator` when given) and trainer.accumulate until batch_size kept rows are in.  chunks, rows: the run's counts so
+    far; returns them advanced.  The caller follows with trainer.adam.  Raises NoValidStep when the run's first 16 chunks hold no valid step."""
+    import torch
+    trainer.zero_gradients()
+    b = 0
+    while b < batch_size:
+        seed = (seed0 + chunks * trajectories_per_step) & (2 ** 64 - 1)
+        chunks += 1
+        traj = corpus.sample(trajectories_per_step, seed, mask_dtype="int16", device=device)
+        tg = targets(ctx, traj, value_weight)
+        keep = None if keep_prob >= 1.0 else torch.rand(tg["n_valid"], device=device, generator=generator) < keep_prob
+        k = tg["n_valid"] if keep is None else int(keep.sum())
+        if k == 0:
+            if tg["n_valid"] == 0 and chunks > 16 and rows == 0:
+                raise NoValidStep("no valid step in the first chunks")
+            continue                                                 # "empty targets after sampling, probably a small buffer"
+        trainer.accumulate(traj, tg, keep=keep, total=batch_size, remaining=batch_size - b, **hyper)
+        b += k
+        rows += min(k, batch_size - (b - k))
+    return chunks, rows
 
 
 class Trainer:

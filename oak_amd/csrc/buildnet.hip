@@ -342,8 +342,34 @@ struct RecordArgs {
 };
 constexpr uint32_t RECORD_BLOCK = 256, RECORD_BYTES = OAKGPU_BUILD_RECORD_BYTES;
 
-__global__ __launch_bounds__(RECORD_BLOCK) void k_build_records(const RecordArgs a) {
+// one record (include/oakgpu.h, RECORDS) of a row's k updates, for both record kernels: team = the row's initial 30 bytes, action / prob =
+// the row's step arrays
+__device__ __forceinline__ void write_record(uint32_t *out, const uint8_t *team, uint32_t size, uint32_t k, const uint16_t *action, const float *prob, float value,
+                                             float score) {
 #pragma clang fp contract(off)
+  const uint32_t score8 = (score >= 0.f) ? (uint32_t)(uint8_t)(2.f * score) : 255u; // NaN or negative: no score
+  out[0] = 0u | score8 << 8 | (uint32_t)(uint16_t)(value * 65535.f) << 16;
+  uint32_t at = 0;
+  for (uint32_t i = 0; i < size; ++i) { // the initial team: per slot the species cell, then its held moves
+    const uint32_t s = team[5 * i];
+    if (s == 0) continue;
+    for (uint32_t j = 0; j < 5; ++j) {
+      const uint32_t m = j ? team[5 * i + j] : 0;
+      if (j && m == 0) continue;
+      const uint32_t c = dev_tab::cell_of(s, m);
+      if (at < STEPS) out[1 + at++] = c & 0xFFFF;
+    }
+  }
+  for (uint32_t u = 0; u < k && at < STEPS; ++u) {
+    const float p = prob[u];
+    uint32_t q = (uint16_t)(65535.f * p);
+    if (p != 0.f && q == 0) q = 1;
+    out[1 + at++] = (uint32_t)action[u] | q << 16;
+  }
+  for (; at < STEPS; ++at) out[1 + at] = 0;
+}
+
+__global__ __launch_bounds__(RECORD_BLOCK) void k_build_records(const RecordArgs a) {
   __shared__ uint32_t s_scan[RECORD_BLOCK];
   __shared__ uint32_t s_base;
   const uint32_t tid = threadIdx.x;
@@ -364,30 +390,72 @@ __global__ __launch_bounds__(RECORD_BLOCK) void k_build_records(const RecordArgs
     const uint32_t base = s_base;
     if (built) {
       uint32_t *out = (uint32_t *)(a.records + (size_t)(base + s_scan[tid] - 1) * RECORD_BYTES);
-      const float score = a.score[g], value = a.value[g];
-      const uint32_t score8 = (score >= 0.f) ? (uint32_t)(uint8_t)(2.f * score) : 255u; // NaN or negative: no score
-      out[0] = 0u | score8 << 8 | (uint32_t)(uint16_t)(value * 65535.f) << 16;
-      uint32_t at = 0;
       const uint32_t size = a.sizes ? (a.sizes[g] > 6 ? 6u : a.sizes[g]) : 6u;
-      const uint8_t *team = a.teams + (size_t)g * 30;
-      for (uint32_t i = 0; i < size; ++i) { // the initial team: per slot the species cell, then its held moves
-        const uint32_t s = team[5 * i];
-        if (s == 0) continue;
-        for (uint32_t j = 0; j < 5; ++j) {
-          const uint32_t m = j ? team[5 * i + j] : 0;
-          if (j && m == 0) continue;
-          const uint32_t c = dev_tab::cell_of(s, m);
-          if (at < STEPS) out[1 + at++] = c & 0xFFFF;
-        }
-      }
-      for (uint32_t u = 0; u < k && at < STEPS; ++u) {
-        const float p = a.prob[(size_t)g * STEPS + u];
-        uint32_t q = (uint16_t)(65535.f * p);
-        if (p != 0.f && q == 0) q = 1;
-        out[1 + at++] = (uint32_t)a.action[(size_t)g * STEPS + u] | q << 16;
-      }
-      for (; at < STEPS; ++at) out[1 + at] = 0;
+      write_record(out, a.teams + (size_t)g * 30, size, k, a.action + (size_t)g * STEPS, a.prob + (size_t)g * STEPS, a.value[g], a.score[g]);
     }
+    __syncthreads();
+    if (tid == RECORD_BLOCK - 1) s_base = base + s_scan[tid];
+    __syncthreads();
+  }
+  if (tid == 0) *a.count = s_base;
+}
+
+// ---- both seats' records of a batch of games (generate.cc:361-383): a game with status OK or SKIPPED gives one record per built seat, p1's
+// before p2's, games in order.  The value / score rule is one text for this kernel and oakgpu_build_game_targets_host.
+__host__ __device__ inline bool game_targets(uint32_t status, uint32_t result, double matchup, int seat, float *value, float *score) {
+#pragma clang fp contract(off)
+  if (status != OAKGPU_FSP_OK && status != OAKGPU_FSP_SKIPPED) return false; // dropped or stopped: the reference's catch ... continue
+  *value = seat == 0 ? (float)matchup : (float)(1.0 - matchup);
+  if (status == OAKGPU_FSP_SKIPPED) { *score = -1.f; return true; } // no battle: no score
+  const uint32_t type = result & 15;
+  const float s = type == 1 ? 1.f : type == 2 ? 0.f : 0.5f; // PKMN::score: win, lose, tie
+  *score = seat == 0 ? s : 1.f - s;
+  return true;
+}
+
+struct GameRecordArgs {
+  oakgpu_build_seat_arrays seat[2];
+  const uint8_t *status, *results;
+  const double *matchup;
+  uint32_t n;
+  uint8_t *records;
+  uint32_t *count;
+};
+
+__global__ __launch_bounds__(RECORD_BLOCK) void k_build_game_records(const GameRecordArgs a) {
+  __shared__ uint32_t s_scan[RECORD_BLOCK];
+  __shared__ uint32_t s_base;
+  const uint32_t tid = threadIdx.x;
+  if (tid == 0) s_base = 0;
+  __syncthreads();
+  for (uint32_t first = 0; first < a.n; first += RECORD_BLOCK) {
+    const uint32_t g = first + tid;
+    uint32_t k[2] = {0, 0};
+    float value[2] = {0.f, 0.f}, score[2] = {0.f, 0.f};
+    if (g < a.n)
+      for (int s = 0; s < 2; ++s) {
+        const uint32_t updates = a.seat[s].n_updates[g];
+        if (updates > 0 && updates <= STEPS && game_targets(a.status[g], a.results[g], a.matchup[g], s, &value[s], &score[s])) k[s] = updates;
+      }
+    const uint32_t own = (k[0] != 0) + (k[1] != 0);
+    s_scan[tid] = own;
+    __syncthreads();
+    for (uint32_t d = 1; d < RECORD_BLOCK; d <<= 1) { // inclusive scan
+      const uint32_t v = tid >= d ? s_scan[tid - d] : 0;
+      __syncthreads();
+      s_scan[tid] += v;
+      __syncthreads();
+    }
+    const uint32_t base = s_base;
+    uint32_t at = base + s_scan[tid] - own;
+    for (int s = 0; s < 2; ++s)
+      if (k[s]) {
+        const oakgpu_build_seat_arrays &p = a.seat[s];
+        const uint32_t size = p.sizes ? (p.sizes[g] > 6 ? 6u : p.sizes[g]) : 6u;
+        write_record((uint32_t *)(a.records + (size_t)at * RECORD_BYTES), p.teams_init + (size_t)g * 30, size, k[s], p.action + (size_t)g * STEPS,
+                     p.prob + (size_t)g * STEPS, value[s], score[s]);
+        ++at;
+      }
     __syncthreads();
     if (tid == RECORD_BLOCK - 1) s_base = base + s_scan[tid];
     __syncthreads();
@@ -623,6 +691,29 @@ int oakgpu_build_records_dev(oakgpu_ctx *ctx, const uint8_t *teams_init, const u
   hipLaunchKernelGGL(k_build_records, dim3(1), dim3(RECORD_BLOCK), 0, (hipStream_t)oakgpu_ctx_stream(ctx), a);
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+int oakgpu_build_game_records_dev(oakgpu_ctx *ctx, const oakgpu_build_seat_arrays *p1, const oakgpu_build_seat_arrays *p2, const uint8_t *status,
+                                  const uint8_t *results, const double *matchup, uint32_t n, uint8_t *records, uint32_t *count) {
+  const char *fn = "oakgpu_build_game_records_dev";
+  if (!ctx || !p1 || !p2 || !status || !results || !matchup || !records || !count) return fail(fn, "null argument");
+  for (const oakgpu_build_seat_arrays *p : {p1, p2})
+    if (!p->teams_init || !p->n_updates || !p->action || !p->prob) return fail(fn, "a seat's array is null");
+  if (n == 0) return fail(fn, "n == 0");
+  if ((uintptr_t)records & 3) return fail(fn, "records must be 4-byte aligned");
+  RC(oakgpu_ctx_enter(ctx));
+  const GameRecordArgs a{{*p1, *p2}, status, results, matchup, n, records, count};
+  hipLaunchKernelGGL(k_build_game_records, dim3(1), dim3(RECORD_BLOCK), 0, (hipStream_t)oakgpu_ctx_stream(ctx), a);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int oakgpu_build_game_targets_host(int status, uint8_t result, double matchup, int seat, float *value, float *score) {
+  const char *fn = "oakgpu_build_game_targets_host";
+  if (!value || !score) return fail(fn, "null argument");
+  if (seat != 0 && seat != 1) return fail(fn, "seat outside {0, 1}");
+  *value = 0.f; *score = -1.f;
+  return game_targets((uint32_t)status, result, matchup, seat, value, score) ? 1 : 0;
 }
 
 // ---- host-pointer wrappers: staged in, staged out, complete on return

@@ -21,24 +21,12 @@
 #include <vector>
 
 #include "oakgpu_internal.h"
+#include "build_corpus.hpp"
 #include "build_traj.hpp"
 #include "fast_prng.hpp"
 #include "game_rows.hpp"
 
 namespace bt = oak_build_traj;
-
-struct oakgpu_build_corpus {
-  oakgpu_ctx *ctx = nullptr;
-  uint32_t n_records = 0, n_files = 0;
-  uint8_t *records = nullptr;     // n_records x 128 bytes
-  uint32_t *file_first = nullptr; // n_files + 1: the first record of each file
-  uint8_t *status = nullptr;      // n_records, filled by the scan
-  uint32_t *counts = nullptr;     // N_STATUS words, filled by the scan
-  bool scan_launched = false, scanned = false;
-  uint32_t h_counts[bt::N_STATUS] = {};
-  uint32_t capacity = 0; // picks of a sample call: grow-only
-  uint32_t *picks = nullptr;
-};
 
 namespace {
 #define RC(x) do { int _r = (x); if (_r) return _r; } while (0)
@@ -287,6 +275,7 @@ int check_traj_call(const char *fn, oakgpu_ctx *ctx, const oakgpu_build_corpus *
   RC(check_params(fn, prm));
   if (!out->status) return fail(fn, "status is null");
   if (corpus->ctx != ctx) return fail(fn, "the corpus belongs to another context");
+  if (corpus->n_records == 0) return fail(fn, "the corpus holds no record (an empty window)");
   if ((uintptr_t)out->mask & (prm->mask_dtype == OAKGPU_BUILD_MASK_INT16 ? 1 : 7)) return fail(fn, "mask is not aligned to its entries");
   return 0;
 }
@@ -294,6 +283,7 @@ int check_traj_call(const char *fn, oakgpu_ctx *ctx, const oakgpu_build_corpus *
 int scan(oakgpu_ctx *ctx, oakgpu_build_corpus *corpus) {
   hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(ctx);
   HIPCHK(hipMemsetAsync(corpus->counts, 0, sizeof(uint32_t) * bt::N_STATUS, stream));
+  if (corpus->n_records == 0) return 0; // (an empty window)
   hipLaunchKernelGGL(k_traj_scan, dim3((corpus->n_records + 255) / 256), dim3(256), 0, stream, corpus->records, corpus->n_records, corpus->status, corpus->counts);
   HIPCHK(hipGetLastError());
   return 0;

@@ -26,6 +26,10 @@
 // row's budget.  The search is then oakgpu_forest_search_budgets(_kept)_dev with budgets that do not increase in row order: no launch of it
 // covers a finished tree.  With keep_node the trees follow through src_row as before.  The pick takes fast_policy_mode for a fast row.  Two
 // departures from generate.cc:292-299: the draw is the game's own (there: the worker thread's), and none is made at probability 0.
+// Matchup values and skipped battles (the _build calls; the rule is selfplay_pick.hpp's game_is_skipped): k_fsp_start draws each game's skip
+// byte from a stream of its own; the pick scatters every row's first empirical value by game index (the matchup), and a skipped row's
+// pick does that and nothing else -- it flags the row OAKGPU_FSP_SKIPPED, and the next retire pass retires it with no record.  On turn 1
+// the compaction writes a skipped row's budget (t1_budget), and the search is a budgets search when some row's budget differs.
 // Every kernel is a plain grid over rows, games or entries (the two scans: one workgroup); none waits for another block.  Between
 // compact and pick runs oakgpu_forest_search_dev over exactly the live rows (the forest refuses terminal roots), after pick
 // oakgpu_update_dev.  Retire / offsets / compact run on game_rows.hpp's scan, place and move, as in policyplay.hip, with this loop's own
@@ -71,9 +75,13 @@ struct FastArgs {
 };
 __device__ __forceinline__ bool first_class(const FastArgs &f, bool fast) { return !f.partition || fast == (f.fast_first != 0); }
 
-__global__ __launch_bounds__(BLOCK) void k_fsp_start(Rows r, const uint64_t *seeds, uint32_t n, int keep) {
+// matchup: by game index, NaN until the game's first search; skip (by game index) <- the skip rule, with `built` null: no game is skipped
+__global__ __launch_bounds__(BLOCK) void k_fsp_start(Rows r, const uint64_t *seeds, uint32_t n, int keep, double *matchup, const uint8_t *built, double skip_prob,
+                                                     uint8_t *skip) {
   const uint32_t row = blockIdx.x * BLOCK + threadIdx.x;
   if (row >= n) return;
+  matchup[row] = __longlong_as_double(0x7FF8000000000000ll);
+  skip[row] = built && oak_pick::game_is_skipped(seeds[row], skip_prob, built[row]) ? 1 : 0;
   if (keep) { r.kept[row] = 0; r.mism[row] = 0; r.carry[row] = 0; }
   r.game[row] = row;
   r.frames[row] = 0;
@@ -104,10 +112,11 @@ __global__ __launch_bounds__(BLOCK) void k_fsp_retire(RetireArgs a) {
   if (g != DEAD) {
     const uint32_t res = a.r.results[row], frames = a.r.frames[row];
     // the host loop's order: a policy that was zeroed ends the game where it stood; a terminal result ends it; only then is another frame due
-    const uint32_t status = a.r.flag[row] ? (uint32_t)OAKGPU_FSP_ZERO_POLICY : (res & 15) != 0 ? (uint32_t)OAKGPU_FSP_OK : frames >= a.max_len ? (uint32_t)OAKGPU_FSP_MAX_LENGTH : DEAD;
+    const uint32_t stopped = a.r.flag[row]; // the pick's: OAKGPU_FSP_ZERO_POLICY, or OAKGPU_FSP_SKIPPED (no frame, result byte 0)
+    const uint32_t status = stopped ? stopped : (res & 15) != 0 ? (uint32_t)OAKGPU_FSP_OK : frames >= a.max_len ? (uint32_t)OAKGPU_FSP_MAX_LENGTH : DEAD;
     if (status == DEAD) live = true;
     else {
-      a.results_out[g] = (uint8_t)res;
+      a.results_out[g] = status == OAKGPU_FSP_SKIPPED ? (uint8_t)0 : (uint8_t)res;
       a.frames_out[g] = frames;
       a.status_out[g] = (uint8_t)status;
       a.length_out[g] = status == OAKGPU_FSP_OK ? HEAD_BYTES + a.r.cursor[row] : 0u;
@@ -139,6 +148,9 @@ struct CompactArgs {
   int keep; // keep_node: the game's counts move with the row
   FastArgs fast;
   uint32_t *budget; // fast searches: per compacted row, the iterations of this turn's search
+  // skipped battles, turn 1 only (else null): the games' skip bytes; a skipped row's budget is t1_budget, every other row's its own
+  const uint8_t *skip;
+  uint32_t t1_budget;
 };
 
 // Stable (game_rows.hpp: compact_place, compact_battles).  The turn prelude rides along (selfplay_pick.hpp's turn_prelude): with fast
@@ -174,7 +186,8 @@ __global__ __launch_bounds__(BLOCK) void k_fsp_compact(CompactArgs a) {
     a.to.rng[to] = rng;
     a.to.fast[to] = turn.fast ? 1 : 0;
     a.to.fastn[to] = a.from.fastn[row];
-    if (a.fast.on) a.budget[to] = turn.fast ? a.fast.budget_fast : a.fast.budget_full;
+    if (a.skip && a.skip[a.from.game[row]]) a.budget[to] = a.t1_budget;
+    else if (a.fast.on || a.skip) a.budget[to] = turn.fast ? a.fast.budget_fast : a.fast.budget_full;
     if (a.src_row) {
       a.src_row[to] = row;
       a.adv_i[to] = a.from.pi[row]; a.adv_j[to] = a.from.pj[row];
@@ -198,6 +211,8 @@ struct PickArgs {
   int keep;
   const uint8_t *advanced, *mismatch;
   const uint32_t *carried;
+  double *matchup;     // by game index: the first search's empirical value
+  const uint8_t *skip; // by game index, turn 1 only (else null): a skipped row's pick writes its matchup and nothing else
 };
 
 __global__ __launch_bounds__(BLOCK) void k_fsp_pick(PickArgs a) {
@@ -215,9 +230,19 @@ __global__ __launch_bounds__(BLOCK) void k_fsp_pick(PickArgs a) {
   }
   if (a.nash_value) nv = a.nash_value[row];
   LogEntry *entry = a.log + row;
-  entry->game = a.r.game[row];
+  const uint32_t game = a.r.game[row];
+  entry->game = game;
   entry->cursor = a.r.cursor[row];
   uint8_t c1 = a.out.p1_choices[(size_t)row * 9], c2 = a.out.p2_choices[(size_t)row * 9];
+  if (a.r.frames[row] == 0) a.matchup[game] = ev; // generate.cc:303-305: the first search's value is the built seats' target
+  if (a.skip && a.skip[game]) { // no policy, no draw, no frame: the row takes a legal step with the rest and is retired with no record
+    a.r.flag[row] = (uint8_t)OAKGPU_FSP_SKIPPED;
+    entry->length = 0;
+    a.r.c1[row] = c1;
+    a.r.c2[row] = c2;
+    if (a.keep) { a.r.pi[row] = 0; a.r.pj[row] = 0; }
+    return;
+  }
   uint32_t len = 0;
   uint8_t pi = 0, pj = 0;
   const bool fast = a.r.fast[row] != 0;
@@ -291,6 +316,9 @@ struct Workspace {
   uint32_t *budget = nullptr, *fast_out = nullptr;
   uint64_t rows_launched = 0, rows_run = 0;
   bool partition = true;
+  // the build side, by game index: the first search's empirical value, the skip byte, the host-array call's staging of `built`
+  double *matchup = nullptr;
+  uint8_t *skip = nullptr, *d_built = nullptr;
   std::vector<int32_t> h_pay;
   std::vector<double> h_nash;
   void release() {
@@ -335,6 +363,7 @@ int workspace_for(oakgpu_forest *f, uint32_t n, Workspace **out) {
   RC(d.get(w->first, T * 384)); RC(d.get(w->results_out, T)); RC(d.get(w->status_out, T)); RC(d.get(w->d_teams, T * 60));
   RC(d.get(w->frames_out, T)); RC(d.get(w->length_out, T)); RC(d.get(w->block_live, 2 * blocks)); RC(d.get(w->block_offset, 2 * blocks)); RC(d.get(w->ctl, 4));
   RC(d.get(w->budget, T)); RC(d.get(w->fast_out, T));
+  RC(d.get(w->matchup, T)); RC(d.get(w->skip, T)); RC(d.get(w->d_built, T));
   RC(d.get(w->d_seeds, 2 * T)); RC(d.get(w->offsets, T + 1));
   w->capacity = n;
   return 0;
@@ -376,9 +405,17 @@ int oakgpu_forest_selfplay_check(uint32_t max_trees, uint32_t max_iterations, in
   return 0;
 }
 
-int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_selfplay_params *prm, const uint8_t *teams, const uint64_t *battle_seeds,
-                               const uint64_t *seeds, uint32_t n, int solve_nash) {
+int oakgpu_forest_selfplay_skip_check(uint32_t max_iterations, const oakgpu_selfplay_skip *skip) {
+  if (!skip) return 0;
+  if (!(skip->battle_skip_prob >= 0.0 && skip->battle_skip_prob <= 1.0)) return oakgpu_fail_msg("oakgpu_forest_selfplay: battle_skip_prob must be in [0, 1]");
+  if (skip->t1_budget > max_iterations) return oakgpu_fail_msg("oakgpu_forest_selfplay: t1_budget exceeds the forest's max_iterations");
+  return 0;
+}
+
+int oakgpu_forest_selfplay_build_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_selfplay_params *prm, const oakgpu_selfplay_skip *skip_prm, const uint8_t *teams,
+                                     const uint64_t *battle_seeds, const uint64_t *seeds, const uint8_t *built, uint32_t n, int solve_nash) {
   if (!f || !prm) return oakgpu_fail_msg("oakgpu_forest_selfplay: null argument");
+  const oakgpu_selfplay_skip skp = skip_prm ? *skip_prm : oakgpu_selfplay_skip{0, 0.0};
   uint32_t max_trees = 0, max_iterations = 0;
   int contextual = 0;
   oakgpu_forest_limits(f, &max_trees, &max_iterations, &contextual);
@@ -393,6 +430,7 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
   }
   if (oakgpu_forest_is_kept(f)) contextual |= OAKGPU_FOREST_KEPT;
   RC(oakgpu_forest_selfplay_check(max_trees, max_iterations, contextual, prm, net != nullptr, n, n ? h_teams.data() : nullptr, solve_nash));
+  RC(oakgpu_forest_selfplay_skip_check(max_iterations, &skp));
   const bool keep = prm->keep_node != 0;
   Workspace *w = nullptr;
   RC(workspace_for(f, std::max(n, 1u), &w));
@@ -428,6 +466,11 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
   oakgpu_search_params sp_budgets = sp;
   sp_budgets.iterations = std::max(fa.budget_full, fa.budget_fast);
   w->rows_launched = w->rows_run = 0;
+  // skipped battles: the games' skip bytes hold on turn 1 alone, where a skipped row is searched with t1_budget iterations
+  const bool skipping = built && skp.battle_skip_prob > 0;
+  const uint32_t t1_budget = skp.t1_budget ? skp.t1_budget : fa.budget_full;
+  oakgpu_search_params sp_first = sp_budgets;
+  sp_first.iterations = std::max((uint32_t)sp_budgets.iterations, t1_budget);
   auto grid = [](uint32_t rows) { return dim3((rows + BLOCK - 1) / BLOCK); };
 
   // the opening: PKMN::battle + update(0, 0); the battle after it is the record's stored one
@@ -437,7 +480,7 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
     Rows &r = w->half[0];
     RC(oakgpu_init_battles_dev(ctx, teams, battle_seeds, n, 1, r.battles, r.durations, r.results));
     HIPCHK(hipMemcpyAsync(w->first, r.battles, (size_t)n * 384, hipMemcpyDeviceToDevice, stream));
-    hipLaunchKernelGGL(k_fsp_start, grid(n), dim3(BLOCK), 0, stream, r, seeds, n, keep ? 1 : 0);
+    hipLaunchKernelGGL(k_fsp_start, grid(n), dim3(BLOCK), 0, stream, r, seeds, n, keep ? 1 : 0, w->matchup, skipping ? built : nullptr, skp.battle_skip_prob, w->skip);
     HIPCHK(hipGetLastError());
   }
   if (!w->log) {
@@ -455,8 +498,9 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
     hipLaunchKernelGGL(k_fsp_retire, grid(rows), dim3(BLOCK), 0, stream, ra);
     hipLaunchKernelGGL(k_rows_offsets, dim3(1), dim3(1024), 0, stream, w->block_live, fa.on ? 2 * blocks : blocks, w->block_offset, w->ctl);
     const bool advance = keep && turn > 0; // the first turn's trees are new
+    const bool first_skips = skipping && turn == 0;
     const CompactArgs ca{w->half[cur], w->half[cur ^ 1], w->block_offset, w->tree_seed, rows, advance ? w->src_row : nullptr, w->adv_i, w->adv_j, w->adv_obs, keep ? 1 : 0,
-                         fa, w->budget};
+                         fa, w->budget, first_skips ? w->skip : nullptr, t1_budget};
     hipLaunchKernelGGL(k_fsp_compact, grid(rows), dim3(BLOCK), 0, stream, ca);
     HIPCHK(hipGetLastError());
     uint32_t live = 0;
@@ -484,7 +528,9 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
       RC(oakgpu_forest_advance_dev(f, w->adv_i, w->adv_j, w->adv_obs, w->src_row, rows, w->advanced));
       if (fa.on) RC(oakgpu_forest_search_budgets_kept_dev(f, net, &sp_budgets, r.battles, r.durations, r.results, w->tree_seed, w->budget, rows, &o, nullptr, 0));
       else RC(oakgpu_forest_search_kept_dev(f, net, &sp, r.battles, r.durations, r.results, w->tree_seed, rows, &o, nullptr, 0));
-    } else if (fa.on) RC(oakgpu_forest_search_budgets_dev(f, net, &sp_budgets, r.battles, r.durations, r.results, w->tree_seed, w->budget, rows, &o, nullptr, 0));
+    } else if (first_skips && (fa.on || t1_budget != fa.budget_full)) // (turn 1: a skipped row's budget differs; the first turn's trees are new)
+      RC(oakgpu_forest_search_budgets_dev(f, net, &sp_first, r.battles, r.durations, r.results, w->tree_seed, w->budget, rows, &o, nullptr, 0));
+    else if (fa.on) RC(oakgpu_forest_search_budgets_dev(f, net, &sp_budgets, r.battles, r.durations, r.results, w->tree_seed, w->budget, rows, &o, nullptr, 0));
     else RC(oakgpu_forest_search_dev(f, net, &sp, r.battles, r.durations, r.results, w->tree_seed, rows, &o, nullptr, 0));
     {
       uint64_t tree_iterations[2];
@@ -505,6 +551,7 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
     pk.temp = prm->policy_temp > 0 ? prm->policy_temp : 1.0; pk.minp = prm->policy_min; pk.rows = rows;
     pk.keep = keep ? 1 : 0;
     if (advance) { pk.advanced = w->advanced; pk.mismatch = d_mismatch; pk.carried = d_carried; }
+    pk.matchup = w->matchup; pk.skip = first_skips ? w->skip : nullptr;
     hipLaunchKernelGGL(k_fsp_pick, grid(rows), dim3(BLOCK), 0, stream, pk);
     HIPCHK(hipGetLastError());
     entries += rows;
@@ -536,6 +583,25 @@ int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_s
   w->have = true;
   return 0;
 }
+
+int oakgpu_forest_selfplay_dev(oakgpu_forest *f, oakgpu_net *net, const oakgpu_selfplay_params *prm, const uint8_t *teams, const uint64_t *battle_seeds,
+                               const uint64_t *seeds, uint32_t n, int solve_nash) {
+  return oakgpu_forest_selfplay_build_dev(f, net, prm, nullptr, teams, battle_seeds, seeds, nullptr, n, solve_nash);
+}
+
+int oakgpu_forest_selfplay_matchup(oakgpu_forest *f, double *out, int to_device) {
+  if (!f || !out) return oakgpu_fail_msg("oakgpu_forest_selfplay_matchup: null argument");
+  Workspace *w = (Workspace *)oakgpu_forest_attachment(f);
+  if (!w || !w->have) return oakgpu_fail_msg("oakgpu_forest_selfplay_matchup: the forest holds no finished self-play call");
+  oakgpu_ctx *ctx = oakgpu_forest_ctx(f);
+  RC(oakgpu_ctx_enter(ctx));
+  hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(ctx);
+  if (w->last_n) HIPCHK(hipMemcpyAsync(out, w->matchup, (size_t)w->last_n * 8, to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  return 0;
+}
+
+int oakgpu_selfplay_skip_host(uint64_t seed, double prob, int built) { return oak_pick::game_is_skipped(seed, prob, built) ? 1 : 0; }
 
 int oakgpu_forest_selfplay_nodes_kept(oakgpu_forest *f, uint32_t *nodes_kept, int to_device) {
   if (!f || !nodes_kept) return oakgpu_fail_msg("oakgpu_forest_selfplay_nodes_kept: null argument");
@@ -608,14 +674,15 @@ int oakgpu_forest_selfplay_records(oakgpu_forest *f, uint8_t *stream_out, size_t
   return copy_records((hipStream_t)oakgpu_ctx_stream(ctx), held, stream_out, offsets, n_frames, results, status, to_device);
 }
 
-int oakgpu_forest_selfplay(oakgpu_forest *f, oakgpu_net *net, const oakgpu_selfplay_params *prm, const uint8_t *teams, const uint64_t *battle_seeds,
-                           const uint64_t *seeds, uint32_t n, int solve_nash) {
+int oakgpu_forest_selfplay_build(oakgpu_forest *f, oakgpu_net *net, const oakgpu_selfplay_params *prm, const oakgpu_selfplay_skip *skip_prm, const uint8_t *teams,
+                                 const uint64_t *battle_seeds, const uint64_t *seeds, const uint8_t *built, uint32_t n, int solve_nash) {
   if (!f || !prm || (n && (!teams || !battle_seeds || !seeds))) return oakgpu_fail_msg("oakgpu_forest_selfplay: null argument");
   uint32_t max_trees = 0, max_iterations = 0;
   int contextual = 0;
   oakgpu_forest_limits(f, &max_trees, &max_iterations, &contextual);
   if (oakgpu_forest_is_kept(f)) contextual |= OAKGPU_FOREST_KEPT;
   RC(oakgpu_forest_selfplay_check(max_trees, max_iterations, contextual, prm, net != nullptr, n, teams, solve_nash));
+  RC(oakgpu_forest_selfplay_skip_check(max_iterations, skip_prm));
   oakgpu_ctx *ctx = oakgpu_forest_ctx(f);
   RC(oakgpu_ctx_enter(ctx));
   hipStream_t stream = (hipStream_t)oakgpu_ctx_stream(ctx);
@@ -625,9 +692,15 @@ int oakgpu_forest_selfplay(oakgpu_forest *f, oakgpu_net *net, const oakgpu_selfp
     HIPCHK(hipMemcpyAsync(w->d_teams, teams, (size_t)n * 60, hipMemcpyHostToDevice, stream));
     HIPCHK(hipMemcpyAsync(w->d_seeds, battle_seeds, (size_t)n * 8, hipMemcpyHostToDevice, stream));
     HIPCHK(hipMemcpyAsync(w->d_seeds + n, seeds, (size_t)n * 8, hipMemcpyHostToDevice, stream));
+    if (built) HIPCHK(hipMemcpyAsync(w->d_built, built, n, hipMemcpyHostToDevice, stream));
     HIPCHK(hipStreamSynchronize(stream));
   }
-  return oakgpu_forest_selfplay_dev(f, net, prm, w->d_teams, w->d_seeds, w->d_seeds + n, n, solve_nash);
+  return oakgpu_forest_selfplay_build_dev(f, net, prm, skip_prm, w->d_teams, w->d_seeds, w->d_seeds + n, built && n ? w->d_built : nullptr, n, solve_nash);
+}
+
+int oakgpu_forest_selfplay(oakgpu_forest *f, oakgpu_net *net, const oakgpu_selfplay_params *prm, const uint8_t *teams, const uint64_t *battle_seeds,
+                           const uint64_t *seeds, uint32_t n, int solve_nash) {
+  return oakgpu_forest_selfplay_build(f, net, prm, nullptr, teams, battle_seeds, seeds, nullptr, n, solve_nash);
 }
 
 int oakgpu_forest_selfplay_last_traffic(const oakgpu_forest *f, uint64_t out[2]) {

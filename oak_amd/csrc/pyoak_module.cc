@@ -487,13 +487,22 @@ PYBIND11_MODULE(pyoak, m) {
       [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> teams, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> battle_seeds,
          py::array_t<uint64_t, py::array::c_style | py::array::forcecast> seeds, Agent &agent, const std::string &policy_mode, double policy_temp,
          double policy_min, uint32_t max_battle_length, py::object solve_nash_arg, bool keep_node, uint32_t keep_arena, uint32_t fast_budget,
-         double fast_search_prob, const std::string &fast_policy_mode) {
+         double fast_search_prob, const std::string &fast_policy_mode, py::object built_arg, double battle_skip_prob, uint32_t t1_budget, bool matchup) {
         const int solve_nash = nash_mode(solve_nash_arg);
         // not in pyoak: the reference's `generate` loop for n games at once over the forest search (include/oakgpu.h:
         // oakgpu_forest_selfplay); game g is the per-game loop with batch = 1 and seed = seeds[g].  Returns (stream bytes, offsets, n_frames,
         // results, status); with keep_node (generate's --keep-node, on a kept forest of keep_arena nodes a tree, 0 = 4 * budget + 1) a sixth
         // value, nodes_kept per game.  fast_budget / fast_search_prob / fast_policy_mode: generate's fast searches (oakgpu_selfplay_params).
+        // built (None, or one byte per game: bit 0 = p1's team was built, bit 1 = p2's) / battle_skip_prob / t1_budget: generate's skipped
+        // battles (status 3, no record); matchup = True appends the games' first-search values (float64 per game) to the tuple.
         const size_t n = (size_t)seeds.size();
+        py::array_t<uint8_t, py::array::c_style | py::array::forcecast> built;
+        const bool has_built = !built_arg.is_none();
+        if (has_built) {
+          built = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>::ensure(built_arg);
+          if (!built || (size_t)built.size() != n) throw std::runtime_error("selfplay_forest: built: one byte per game");
+        }
+        py::array_t<double> matchup_out(n);
         if ((size_t)teams.size() != n * 60 || (size_t)battle_seeds.size() != n) throw std::runtime_error("selfplay_forest: teams n x 60, battle_seeds n, seeds n");
         if (policy_mode.size() > 15) throw std::runtime_error("selfplay_forest: policy_mode: at most 15 characters");
         if (fast_policy_mode.size() > 15) throw std::runtime_error("selfplay_forest: fast_policy_mode: at most 15 characters");
@@ -517,13 +526,16 @@ PYBIND11_MODULE(pyoak, m) {
           P.policy_temp = policy_temp; P.policy_min = policy_min; P.max_battle_length = max_battle_length;
           std::memcpy(P.fast_policy_mode, fast_policy_mode.c_str(), fast_policy_mode.size() + 1);
           P.fast_budget = fast_budget; P.fast_search_prob = fast_search_prob;
-          const uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(P.search.iterations, fast_budget), 0xFFFFFFFFu);
+          const oakgpu_selfplay_skip skip{t1_budget, battle_skip_prob};
+          const uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(P.search.iterations, std::max(fast_budget, t1_budget)), 0xFFFFFFFFu);
           if (!rc && keep_node) rc = oakgpu_forest_create_kept_check((uint32_t)std::max<size_t>(n, 1), cap, keep_arena);
           if (!rc) rc = oakgpu_forest_selfplay_check((uint32_t)n, cap, (P.search.bandit == 1 ? 1 : 0) | (keep_node ? OAKGPU_FOREST_KEPT : 0), &P, net != nullptr, (uint32_t)n,
                                                      teams.data(), solve_nash);
+          if (!rc) rc = oakgpu_forest_selfplay_skip_check(cap, &skip);
           if (!rc && n) rc = keep_node ? oakgpu_forest_create_kept(context(), (uint32_t)n, cap, P.search.bandit == 1, keep_arena, &forest)
                                        : oakgpu_forest_create(context(), (uint32_t)n, cap, P.search.bandit == 1, &forest);
-          if (!rc && n) rc = oakgpu_forest_selfplay(forest, net, &P, teams.data(), battle_seeds.data(), seeds.data(), (uint32_t)n, solve_nash);
+          if (!rc && n) rc = oakgpu_forest_selfplay_build(forest, net, &P, &skip, teams.data(), battle_seeds.data(), seeds.data(), has_built ? built.data() : nullptr, (uint32_t)n,
+                                                          solve_nash);
           size_t bytes = 0;
           if (!rc && n) rc = oakgpu_forest_selfplay_records(forest, nullptr, 0, &bytes, nullptr, nullptr, nullptr, nullptr, 0);
           if (!rc && n) {
@@ -532,17 +544,20 @@ PYBIND11_MODULE(pyoak, m) {
                                                 results.mutable_data(), status.mutable_data(), 0);
           }
           if (!rc && n && keep_node) rc = oakgpu_forest_selfplay_nodes_kept(forest, nodes_kept.mutable_data(), 0);
+          if (!rc && n && matchup) rc = oakgpu_forest_selfplay_matchup(forest, matchup_out.mutable_data(), 0);
           if (rc) err = oakgpu_last_error();
           oakgpu_forest_destroy(context(), forest);
         }
         if (rc) throw std::runtime_error(err);
         if (!n) offsets.mutable_data()[0] = 0;
-        if (keep_node) return py::tuple(py::make_tuple(py::bytes(stream), offsets, n_frames, results, status, nodes_kept));
-        return py::tuple(py::make_tuple(py::bytes(stream), offsets, n_frames, results, status));
+        py::tuple out = keep_node ? py::tuple(py::make_tuple(py::bytes(stream), offsets, n_frames, results, status, nodes_kept))
+                                  : py::tuple(py::make_tuple(py::bytes(stream), offsets, n_frames, results, status));
+        return matchup ? py::tuple(out + py::make_tuple(matchup_out)) : out;
       },
       py::arg("teams"), py::arg("battle_seeds"), py::arg("seeds"), py::arg("agent"), py::arg("policy_mode") = "e", py::arg("policy_temp") = 1.0,
       py::arg("policy_min") = 0.0, py::arg("max_battle_length") = 0, py::arg("solve_nash") = true, py::arg("keep_node") = false, py::arg("keep_arena") = 0,
-      py::arg("fast_budget") = 0, py::arg("fast_search_prob") = 0.0, py::arg("fast_policy_mode") = "");
+      py::arg("fast_budget") = 0, py::arg("fast_search_prob") = 0.0, py::arg("fast_policy_mode") = "", py::arg("built") = py::none(),
+      py::arg("battle_skip_prob") = 0.0, py::arg("t1_budget") = 0, py::arg("matchup") = false);
 
   m.def(
       "match_forest",

@@ -49,6 +49,18 @@ OAK_PICK_HD inline TurnPrelude turn_prelude(uint64_t &rng, double fast_search_pr
 // the iterations of a turn's search: fast_budget == 0 means the full budget
 OAK_PICK_HD inline uint32_t turn_budget(bool fast, uint32_t iterations, uint32_t fast_budget) { return fast && fast_budget ? fast_budget : iterations; }
 
+// Skipped battles (generate's --battle-skip-prob, generate.cc:233-236): a game with at least one built seat (`built` != 0) is skipped with
+// probability `prob` -- searched once, on turn 1, for its matchup value, then dropped.  The draw is the first uniform of a stream of its
+// own, seeds[g] ^ SKIP_STREAM_XOR (the reference: the worker thread's device), so the game's stream is untouched: a game that is not
+// skipped is the game of a call without the fields, whatever `built` says.  No draw is made at probability 0 or for a game without a built
+// seat.
+constexpr uint64_t SKIP_STREAM_XOR = 0x5B1D7C83A46E20F9ull;
+OAK_PICK_HD inline bool game_is_skipped(uint64_t seed, double prob, int built) {
+  if (!built || !(prob > 0)) return false;
+  uint64_t x = seed ^ SKIP_STREAM_XOR;
+  return uniform01(x) < prob;
+}
+
 OAK_PICK_HD inline uint16_t compress_prob(double x) { // compress_probs<double, uint16_t> (compressed-frame.h:11-25)
 #pragma clang fp contract(off)
   const double v = x * 65535.0;

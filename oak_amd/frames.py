@@ -126,7 +126,7 @@ def selfplay_games(ctxs, teams, battle_seeds, seeds, iterations=1 << 12, batch=1
 
 
 # ---- self-play over the forest search (oakgpu_forest_selfplay*; the rules are in include/oakgpu.h) -------------------------------------
-FSP_STATUS = ("OK", "MAX_LENGTH", "ZERO_POLICY")
+FSP_STATUS = ("OK", "MAX_LENGTH", "ZERO_POLICY", "SKIPPED")
 
 
 def _selfplay_params(iterations, bandit, c, evaluator, policy_mode, policy_temp, policy_min, max_battle_length, root_rolls, other_rolls, max_depth):
@@ -147,7 +147,8 @@ def _selfplay_params(iterations, bandit, c, evaluator, policy_mode, policy_temp,
 
 def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="ucb", evaluator="mc", policy_mode="e", policy_temp=1.0,
                     policy_min=0.0, max_battle_length=0, root_rolls=3, other_rolls=1, max_depth=0, forest=None, solve_nash=True, stats=None,
-                    keep_node=False, keep_arena=0, fast_budget=0, fast_search_prob=0.0, fast_policy_mode=""):
+                    keep_node=False, keep_arena=0, fast_budget=0, fast_search_prob=0.0, fast_policy_mode="", built=None, battle_skip_prob=0.0,
+                    t1_budget=0):
     """n self-play games at once over the forest search, resident on the GPU (oakgpu_forest_selfplay*): game g is selfplay_game(ctx,
     teams[g], battle_seeds[g], batch=1, seed=seeds[g], ...).  teams uint8[n, 2, 6, 5]; forest: None (one made for this call) or a
     search.Forest to reuse; stats: optional dict that receives turns, rows searched, compactions and host reads (of the live count), and
@@ -160,7 +161,13 @@ def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="
     fast_search_prob > 0: generate's fast searches, as in selfplay_game; each turn is ONE budgets search over the live rows, those of the
     larger budget first.  stats then also tells fast_frames, full_frames (the frames min_iterations = fast_budget + 1 keeps for training),
     launched and run (tree-iterations: equal, since no launch covers a finished tree).  A forest made here holds max(iterations,
-    fast_budget) iterations.
+    fast_budget, t1_budget) iterations.
+    built: None, or uint8[n] (bit 0: p1's team was built, bit 1: p2's; a tensor with tensors in) -- generate's skipped battles: a game
+    with a built seat is skipped with probability battle_skip_prob (selfplay_skip_host is the rule): searched once with t1_budget iterations
+    (0 = iterations), status SKIPPED, zero bytes, no frames.  A game that is not skipped is the game of a call without the three, byte for
+    byte.  Turn 1's rows are not sorted by budget, so launched may exceed run by that turn's slack.
+    stats["matchup"]: float64[n] (a tensor with tensors in), the empirical value of each game's first search -- the value of a built
+    seat's trajectory (p2's is 1 - it); NaN for a game never searched.
     numpy arrays in: (stream bytes, offsets uint64[n + 1], n_frames uint32[n], results uint8[n], status uint8[n]) -- the stream is the
     kept games' records in game order, a dropped game (status MAX_LENGTH / ZERO_POLICY, see FSP_STATUS) has zero bytes.
     torch GPU tensors in (teams uint8 [n, 60]; battle_seeds, seeds int64 bit patterns): the same five as tensors on that device; nothing
@@ -170,12 +177,13 @@ def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="
     prm = _selfplay_params(iterations, bandit, c, evaluator, policy_mode, policy_temp, policy_min, max_battle_length, root_rolls, other_rolls, max_depth)
     prm.keep_node = 1 if keep_node else 0
     _set_fast(prm, fast_budget, fast_search_prob, fast_policy_mode)
+    skip = _lib.SelfplaySkip(int(t1_budget), float(battle_skip_prob))
     net = evaluator.handle if use_net else None
     on_device = hasattr(teams, "data_ptr")
     n = int(teams.shape[0]) if on_device else len(np.asarray(seeds).reshape(-1))
     own = forest is None
     if own:
-        forest = Forest(ctx, max(n, 1), max(int(iterations), int(fast_budget), 1), contextual=bandit == "pucb", keep_arena=int(keep_arena) if keep_node else None)
+        forest = Forest(ctx, max(n, 1), max(int(iterations), int(fast_budget), int(t1_budget), 1), contextual=bandit == "pucb", keep_arena=int(keep_arena) if keep_node else None)
     lib = ctx.lib
     try:
         size = C.c_size_t(0)
@@ -185,8 +193,12 @@ def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="
             teams, battle_seeds, seeds = teams.contiguous().view(n, 60), battle_seeds.contiguous(), seeds.contiguous()
             mine, theirs = torch.cuda.ExternalStream(ctx.stream_ptr(), device=dev), torch.cuda.current_stream(dev)
             mine.wait_stream(theirs)
-            _lib.check(lib.oakgpu_forest_selfplay_dev(forest.handle, net, C.byref(prm), teams.data_ptr(), battle_seeds.data_ptr(), seeds.data_ptr(), n,
-                                                      _lib.nash_mode(solve_nash)))
+            if built is not None:
+                built = built.contiguous().view(torch.uint8)
+                if built.numel() != n:
+                    raise ValueError("built: one byte per game")
+            _lib.check(lib.oakgpu_forest_selfplay_build_dev(forest.handle, net, C.byref(prm), C.byref(skip), teams.data_ptr(), battle_seeds.data_ptr(), seeds.data_ptr(),
+                                                            None if built is None or n == 0 else built.data_ptr(), n, _lib.nash_mode(solve_nash)))
             _lib.check(lib.oakgpu_forest_selfplay_records(forest.handle, None, 0, C.byref(size), None, None, None, None, 1))
             stream = torch.zeros(max(size.value, 1), dtype=torch.uint8, device=dev)
             offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
@@ -207,7 +219,9 @@ def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="
             bs = np.ascontiguousarray(np.asarray(battle_seeds).astype(np.uint64)).reshape(n)
             sd = np.ascontiguousarray(np.asarray(seeds).astype(np.uint64)).reshape(n)
             vp = lambda a: a.ctypes.data_as(C.c_void_p)
-            _lib.check(lib.oakgpu_forest_selfplay(forest.handle, net, C.byref(prm), vp(t), vp(bs), vp(sd), n, _lib.nash_mode(solve_nash)))
+            bt = None if built is None else np.ascontiguousarray(np.asarray(built).astype(np.uint8)).reshape(n)
+            _lib.check(lib.oakgpu_forest_selfplay_build(forest.handle, net, C.byref(prm), C.byref(skip), vp(t), vp(bs), vp(sd), None if bt is None or n == 0 else vp(bt), n,
+                                                        _lib.nash_mode(solve_nash)))
             _lib.check(lib.oakgpu_forest_selfplay_records(forest.handle, None, 0, C.byref(size), None, None, None, None, 0))
             stream = np.zeros(max(size.value, 1), np.uint8)
             offsets, n_frames = np.zeros(n + 1, np.uint64), np.zeros(max(n, 1), np.uint32)
@@ -228,6 +242,15 @@ def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="
             stats.update(loop_syncs=int(tr[0]), loop_copies=int(tr[1]))
             _lib.check(lib.oakgpu_forest_selfplay_fast_stats(forest.handle, C.byref(st)))
             stats.update(fast_frames=int(st[0]), full_frames=int(st[1]), launched=int(st[2]), run=int(st[3]))
+            if on_device:
+                matchup = torch.zeros(max(n, 1), dtype=torch.float64, device=dev)
+                mine.wait_stream(theirs)
+                _lib.check(lib.oakgpu_forest_selfplay_matchup(forest.handle, matchup.data_ptr(), 1))
+                theirs.wait_stream(mine)
+            else:
+                matchup = np.zeros(max(n, 1), np.float64)
+                _lib.check(lib.oakgpu_forest_selfplay_matchup(forest.handle, vp(matchup), 0))
+            stats["matchup"] = matchup[:n]
             if keep_node:
                 _lib.check(lib.oakgpu_forest_selfplay_keep_stats(forest.handle, C.byref(st)))
                 stats.update(nodes_kept=int(st[0]), dropped=int(st[1]), mismatches=int(st[2]), carried_nodes=int(st[3]))
@@ -240,7 +263,7 @@ def forest_selfplay(ctx, teams, battle_seeds, seeds, iterations, c=2.0, bandit="
 def forest_selfplay_check(max_trees, max_iterations, contextual, iterations, n=1, teams=None, c=2.0, bandit="ucb", evaluator="mc", policy_mode="e",
                           policy_temp=1.0, policy_min=0.0, max_battle_length=0, root_rolls=3, other_rolls=1, max_depth=0, solve_nash=True,
                           has_net=False, keep_node=False, matrix_ucb=0, duration_us=0, kept=False, fast_budget=0, fast_search_prob=0.0,
-                          fast_policy_mode=""):
+                          fast_policy_mode="", battle_skip_prob=0.0, t1_budget=0):
     """oakgpu_forest_selfplay_check alone (host only, no GPU): raises OakGpuError with the refusal's message.  evaluator "mc" | "poke-engine" |
     "net" (with has_net saying whether a network is given); kept: the limits are a kept forest's (oakgpu_forest_create_kept)."""
     prm = _selfplay_params(iterations, bandit, c, "mc" if evaluator == "net" else evaluator, policy_mode, policy_temp, policy_min, max_battle_length,
@@ -252,6 +275,8 @@ def forest_selfplay_check(max_trees, max_iterations, contextual, iterations, n=1
     t = None if teams is None else np.ascontiguousarray(teams, dtype=np.uint8).reshape(n, 60)
     _lib.check(_lib.load().oakgpu_forest_selfplay_check(int(max_trees), int(max_iterations), int(bool(contextual)) | (2 if kept else 0), C.byref(prm), int(bool(has_net)), int(n),
                                                         None if t is None else t.ctypes.data_as(C.c_void_p), _lib.nash_mode(solve_nash)))
+    skip = _lib.SelfplaySkip(int(t1_budget), float(battle_skip_prob))     # (what the _build calls check next)
+    _lib.check(_lib.load().oakgpu_forest_selfplay_skip_check(int(max_iterations), C.byref(skip)))
 
 
 def selfplay_pick_host(m, n, visit_matrix, value_matrix, iterations, rng, p1_nash=None, p2_nash=None, nash_value=0.0, p1_prior=None, p2_prior=None,
@@ -274,6 +299,12 @@ def selfplay_pick_host(m, n, visit_matrix, value_matrix, iterations, rng, p1_nas
                                              C.byref(state), C.byref(ev), vp(e1), vp(e2), vp(q1), vp(q2), C.byref(i), C.byref(j), vp(upd), C.byref(ulen)))
     return {"empirical_value": ev.value, "p1_empirical": e1, "p2_empirical": e2, "p1_policy": q1, "p2_policy": q2, "i": i.value, "j": j.value,
             "rng": state.value, "update": upd[:ulen.value].tobytes()}
+
+
+def selfplay_skip_host(seed, prob, built):
+    """oakgpu_selfplay_skip_host (no GPU): whether the forest loop skips the game of this seed (generate's --battle-skip-prob), by the rule
+    the device loop compiles: built != 0, prob > 0 and the first uniform of the stream seed ^ SKIP_STREAM_XOR below prob."""
+    return bool(_lib.load().oakgpu_selfplay_skip_host(int(seed) & 0xFFFFFFFFFFFFFFFF, float(prob), int(built)))
 
 
 def selfplay_prelude_host(rng, fast_search_prob):

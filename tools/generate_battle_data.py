@@ -6,7 +6,8 @@ files under --out.
          [--eval mc | fp | NET.battle.net] [--discrete] [--policy-mode e] [--policy-temp 1] [--policy-min 0] [--max-battle-length L]
          [--no-nash | --device-nash] [--seed S] [--file-mb 8] [--keep-node [--keep-arena NODES]]
          [--fast-budget K --fast-search-prob P [--fast-policy-mode MODE]]
-         [--build-network NET.build.net [--team-modify-prob P] [--pokemon-delete-prob P] [--move-delete-prob P] [--max-pokemon K]]
+         [--build-network NET.build.net [--team-modify-prob P] [--pokemon-delete-prob P] [--move-delete-prob P] [--max-pokemon K]
+          [--battle-skip-prob P] [--t1-budget N]]
 
 --teams FILE: JSON {"teams": [[[species, move, move, move, move] x 6] ...]} by name, the layout of tests/golden/ou_sample_teams.json (the
 default: the reference's 16 sample teams); each game draws its two teams from the file with --seed's generator, a pair that fails the
@@ -26,7 +27,10 @@ frames reach the loss.  The fast and full frame counts and the tree-iterations l
 the device -- a team of the pool, truncated to --max-pokemon, with probability --team-modify-prob thinned by --pokemon-delete-prob /
 --move-delete-prob and completed by the build network -- pairs that fail the endless battle check are provided again with fresh seeds
 before the games start, and every batch also writes <seed>_<batch>.build.data beside the `.battle.data`: one 128-byte record per built
-seat of a kept game, value 0.5, the p1 rows with the game's score and the p2 rows with 1 - score.  The engine takes teams with empty
+seat of a kept or skipped game, game-major, p1 before p2 (oak_amd.build.game_records, one launch): the value is the game's matchup -- the
+empirical value of its first search, 1 - it for p2 -- the p1 rows carry the game's score and the p2 rows 1 - score.  --battle-skip-prob: a
+game with a built seat is skipped with this probability: searched once with --t1-budget iterations (0 = --budget) for its matchup, written
+to `.build.data` without a score and to no `.battle.data`.  The engine takes teams with empty
 slots and empty move slots (init_side skips them as the reference's does), so --max-pokemon below 6 and species whose pools hold fewer
 than four moves are played as they are.  The seconds spent in team building are printed beside the total."""
 import argparse
@@ -86,6 +90,8 @@ def main():
     ap.add_argument("--pokemon-delete-prob", type=float, default=0.0)
     ap.add_argument("--move-delete-prob", type=float, default=0.0)
     ap.add_argument("--max-pokemon", type=int, default=6)
+    ap.add_argument("--battle-skip-prob", type=float, default=0.0, help="probability that a game with a built seat is searched once and not played")
+    ap.add_argument("--t1-budget", type=int, default=0, help="iterations of a skipped game's one search (0 = --budget)")
     a = ap.parse_args()
     name, _, c = a.bandit.partition("-")
     if name not in ("ucb", "pucb"):
@@ -93,6 +99,9 @@ def main():
     from oak_amd.engine import Context, Network
     from oak_amd.frames import forest_selfplay
     from oak_amd.search import Forest
+    if a.build_network:
+        import torch
+        torch.zeros(1, device="cuda:0")                                  # (build.game_records stages through torch, which initialises the GPU before the library does)
     ctx = Context(0)
     evaluator = {"mc": "mc", "": "mc", "fp": "poke-engine"}.get(a.eval)
     net = None
@@ -104,15 +113,15 @@ def main():
         from oak_amd import build
         build.check_provide(np.asarray(pool, np.uint8).reshape(-1, 30), 1, a.max_pokemon, a.pokemon_delete_prob, a.move_delete_prob, a.team_modify_prob)
         build_net = build.BuildNetwork(ctx, a.build_network)
-    elif a.max_pokemon != 6 or a.team_modify_prob or a.pokemon_delete_prob or a.move_delete_prob:
-        sys.exit("--max-pokemon / --team-modify-prob / --pokemon-delete-prob / --move-delete-prob need --build-network")
+    elif a.max_pokemon != 6 or a.team_modify_prob or a.pokemon_delete_prob or a.move_delete_prob or a.battle_skip_prob or a.t1_budget:
+        sys.exit("--max-pokemon / --team-modify-prob / --pokemon-delete-prob / --move-delete-prob / --battle-skip-prob / --t1-budget need --build-network")
     build_seconds, build_records, batches = 0.0, 0, 0
     rng = np.random.default_rng(a.seed)
     os.makedirs(a.out, exist_ok=True)
     batch = max(1, min(a.batch, a.games))
-    forest = Forest(ctx, batch, max(a.budget, a.fast_budget), contextual=name == "pucb", keep_arena=a.keep_arena if a.keep_node else None)
+    forest = Forest(ctx, batch, max(a.budget, a.fast_budget, a.t1_budget), contextual=name == "pucb", keep_arena=a.keep_arena if a.keep_node else None)
     limit = int(a.file_mb * (1 << 20))
-    played = frames = dropped = files = 0
+    played = frames = dropped = files = skipped = 0
     updates = updates_with_node = trees_dropped = 0
     fast_frames = full_frames = launched = run = 0
     pending = []
@@ -141,34 +150,35 @@ def main():
                                                team_modify_prob=a.team_modify_prob)
             build_seconds += time.perf_counter() - tb
             battle_seeds, seeds = rng.integers(0, 1 << 63, n, dtype=np.uint64), rng.integers(0, 1 << 63, n, dtype=np.uint64)
+        built = None if build_net is None else ((seats[0]["n_updates"] > 0) | ((seats[1]["n_updates"] > 0) << 1)).astype(np.uint8)
         stats = {}
         stream, offsets, n_frames, results, status = forest_selfplay(
             ctx, teams, battle_seeds, seeds, a.budget, c=float(c or 2.0), bandit=name, evaluator=evaluator, policy_mode=a.policy_mode,
             policy_temp=a.policy_temp, policy_min=a.policy_min, max_battle_length=a.max_battle_length, forest=forest, solve_nash=False if a.no_nash else ("device" if a.device_nash else True),
-            keep_node=a.keep_node, stats=stats, fast_budget=a.fast_budget, fast_search_prob=a.fast_search_prob, fast_policy_mode=a.fast_policy_mode)[:5]
+            keep_node=a.keep_node, stats=stats, fast_budget=a.fast_budget, fast_search_prob=a.fast_search_prob, fast_policy_mode=a.fast_policy_mode,
+            built=built, battle_skip_prob=a.battle_skip_prob, t1_budget=a.t1_budget)[:5]
         fast_frames, full_frames, launched, run = fast_frames + stats["fast_frames"], full_frames + stats["full_frames"], launched + stats["launched"], run + stats["run"]
         if a.keep_node:   # RuntimeData::update_with_node_counter / update_counter (generate.cc:412-416)
             updates, updates_with_node, trees_dropped = updates + int(n_frames.sum()), updates_with_node + stats["nodes_kept"], trees_dropped + stats["dropped"]
         kept = status == 0
-        if build_net is not None:   # generate.cc:190-213, 361-386: the trajectories of the kept games with the game's score
+        if build_net is not None:   # generate.cc:190-213, 361-386: the trajectories of the kept and the skipped games, matchup and score
             tb = time.perf_counter()
-            score = np.array([{1: 1.0, 2: 0.0, 3: 0.5}.get(int(r) & 15, -1.0) for r in results], np.float32)
-            data = b""
-            for s_, seat in enumerate(seats):
-                seat["n_updates"] = np.where(kept, seat["n_updates"], 0).astype(np.uint8)
-                data += build.records(ctx, seat, 0.5, np.where(score < 0, -1.0, score if s_ == 0 else 1 - score).astype(np.float32))
+            data = build.game_records(ctx, seats, status, results, stats["matchup"])
             with open(os.path.join(a.out, "%d_%d.build.data" % (a.seed, batches)), "wb") as f:
                 f.write(data)
             build_records += len(data) // 128
             build_seconds += time.perf_counter() - tb
         batches += 1
         pending += [stream[int(offsets[g]):int(offsets[g + 1])] for g in range(n) if kept[g]]
+        skipped += int((status == 3).sum())
         played, frames, dropped = played + n, frames + int(n_frames[kept].sum()), dropped + int((~kept).sum())
         flush(False)
     flush(True)
     s = time.perf_counter() - t0
     print("games: %d, frames: %d, dropped: %d, files: %d, seconds: %.2f (%.1f games/s, %.0f frames/s)" % (played - dropped, frames, dropped, files, s,
                                                                                                        (played - dropped) / s, frames / s))
+    if a.battle_skip_prob > 0:
+        print("skipped battles: %d of the %d dropped (searched once with %d iterations for their matchup)" % (skipped, dropped, a.t1_budget or a.budget))
     if build_net is not None:
         print("team building: %d records, %.2f seconds (%.1f %% of the call)" % (build_records, build_seconds, 100 * build_seconds / s))
         build_net.close()

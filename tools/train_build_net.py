@@ -78,23 +78,12 @@ def main(argv=None):
     lr, step, chunks, rows, t0 = a.lr, 0, 0, 0, time.perf_counter()
     print(json.dumps({"files": len(paths), "corpus": corpus.info(), "parameters": trainer.count, "dir": out_dir}), flush=True)
     while a.steps < 0 or step < a.steps:
-        trainer.zero_gradients()
-        b = 0
-        while b < a.batch_size:                                          # build.py:295-332: backward() per chunk until the batch is full
-            seed = (seed0 + chunks * a.trajectories_per_step) & (2 ** 64 - 1)   # draw i of a chunk is seeded seed + i: no stream is used twice
-            chunks += 1
-            traj = corpus.sample(a.trajectories_per_step, seed, mask_dtype="int16", device=device)
-            tg = build.targets(ctx, traj, a.value_weight)
-            keep = None if a.keep_prob >= 1.0 else torch.rand(tg["n_valid"], device=device) < a.keep_prob
-            k = tg["n_valid"] if keep is None else int(keep.sum())
-            if k == 0:
-                if tg["n_valid"] == 0 and chunks > 16 and rows == 0:
-                    print(json.dumps({"error": "no valid step in the first chunks"}))
-                    return 2
-                continue                                                 # "empty targets after sampling, probably a small buffer"
-            trainer.accumulate(traj, tg, keep=keep, total=a.batch_size, remaining=a.batch_size - b, **hyper)
-            b += k
-            rows += min(k, a.batch_size - (b - k))
+        try:                                                             # build.py:295-332: backward() per chunk until the batch is full
+            chunks, rows = build.accumulate_batch(ctx, corpus, trainer, a.batch_size, a.trajectories_per_step, a.keep_prob, a.value_weight, seed0, chunks, rows,
+                                                  device, hyper)
+        except build.NoValidStep as e:
+            print(json.dumps({"error": str(e)}))
+            return 2
         trainer.adam(lr)
         # save_and_decay (src/oak/common_args.py:134-153), then the rolling average and its checkpoint
         if step >= a.lr_decay_start and step % a.lr_decay_interval == 0:
